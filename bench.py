@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the PicoPose correspondence hot path on MI355X (driver contract: ONE JSON line).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--mode fast|exact]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--mode fast|exact] [--dump-outputs DIR]
 
 Default workload `full_b32_n162_vitb` = BASELINE.json configs[2] (the configuration the metric is quoted
 on): batch 32 synthetic 224x224 crops, 162 templates per crop, DINOv2 ViT-B/14, hyp 5 — one step is
@@ -444,6 +444,43 @@ def input_batches(prefetch_query, single_batch, sharded, cached):
     return 2 if prefetch_query and not single_batch and not sharded and not cached else 1
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: write every array of `arrays` (name -> tensor / array) as `path/<name>.npy`: float64 where the value is float64 or
+    an integer beyond float32's exact range (2**24), float32 otherwise — integers stay exact.  Over `budget` bytes in all, each array is
+    replaced by a fixed, seeded sample of its flattened elements (the same positions from run to run for the same shapes).
+    Returns {name: [shape written, sampled]}."""
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        v = np.asarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v)
+        wide = v.dtype == np.float64 or (np.issubdtype(v.dtype, np.integer) and v.size > 0 and np.abs(v).max() > 2 ** 24)
+        host[name] = v.astype(np.float64 if wide else np.float32)
+    total = sum(v.nbytes for v in host.values())
+    written = {}
+    for name, v in host.items():
+        sampled = total > budget
+        if sampled:
+            k = max(1, int(v.size * budget / total))
+            v = v.reshape(-1)[np.sort(np.random.default_rng(seed).choice(v.size, size=k, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), v)
+        written[name] = [list(v.shape), sampled]
+    return written
+
+
+def step_outputs(kind, out):
+    """What a caller of the timed path receives from one step, by name: stage 1 = (score, index); full path = (the Net.forward dicts of the
+    hypotheses, stacked over the hypothesis axis, (rot, tvec, inliers_ratio, success) of the batched PnP/RANSAC)."""
+    if kind == "stage1":
+        return {"score": out[0], "index": out[1]}
+    outs, (rot, tvec, ratio, ok) = out
+    arrays = {k: torch.stack([o[k] for o in outs]) for k in outs[0] if torch.is_tensor(outs[0][k])}
+    arrays.update(pnp_rot=rot, pnp_tvec=tvec, pnp_inliers_ratio=ratio, pnp_success=ok)
+    return arrays
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` from a plain shell: run the N ranks as a child torch.distributed.run job (nothing in
     this process has touched the GPU) and hand back its return code; rank 0 of the child prints the JSON line."""
@@ -501,12 +538,17 @@ def main():
     ap.add_argument("--graph", action="store_true",
                     help="stage-1 workloads: replay the five kernels of a matching call as ONE HIP graph (picopose_amd.utils.matching.MatchingGraph) "
                          "instead of launching them one by one — measured no faster on this runtime (profiles/r05/stage1_small.txt): off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the arrays its caller receives) as DIR/<name>.npy "
+                         "in float32 / float64, at most 64 MB in all; the inputs are seeded, so two builds compare output for output")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-exact-leg", action="store_true", help="skip the untimed --mode exact comparison leg")
     ap.add_argument("--no-train-leg", action="store_true", help="skip the training-step extra (default workload, fast mode only)")
     ap.add_argument("--no-latency-leg", action="store_true",
                     help="skip the per-image latency leg (the reference's own measurement: ViT-L/14, 162 templates, hyp 5, chunks of 4 detections)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error(f"--steps must be at least 1 and --warmup at least 0 (got {a.steps}, {a.warmup})")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and os.environ.get("PP_BENCH_REHEARSE") != "1":
         # (counting devices does not initialise the GPU on this image; a rank that asked for a GPU the node lacks would otherwise
@@ -697,8 +739,10 @@ def main():
 
         pnp_stream = torch.cuda.Stream(device=dev) if a.pnp_stream == "side" else None
 
-        def step_launch(i):
+        def step_launch(i, keep=None):
             outs = forward(i=i)
+            if keep is not None:        # (--dump-outputs: the caller keeps this step's forward outputs)
+                keep.append(outs)
             return pnp_for_outputs_async(outs, eps[i % 2]["real_K"], host=pinned[i % 2], stream=pnp_stream)
 
     if kind == "stage1":   # a step is ~1 ms: without ~0.3 s of load first, the timed steps run while the clocks still ramp
@@ -725,25 +769,32 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     pending = None
+    last_outs = [] if a.dump_outputs else None
     for i in range(a.steps):
         if kind == "stage1":
             out = step()
         elif a.sync_loop:
             out = step(i)
         else:
-            h = step_launch(i)
+            h = step_launch(i, keep=last_outs if i == a.steps - 1 else None)
             if pending is not None:
                 poses = pnp_collect(pending, 5, Bl)       # the previous step's poses, while this step runs
             pending = h
         marks[i + 1].record()
     if pending is not None:
-        poses = pnp_collect(pending, 5, Bl)               # noqa: F841
+        poses = pnp_collect(pending, 5, Bl)
     torch.cuda.synchronize()
     if distributed:
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps))
+    dumped = None
+    if a.dump_outputs and rank == 0:      # before any untimed step below can overwrite the last timed step's buffers
+        last = out if kind == "stage1" or a.sync_loop else (last_outs[0], poses)
+        dumped = {"dir": a.dump_outputs, "arrays": dump_outputs(a.dump_outputs, step_outputs(kind, last))}
+        del last
+    last_outs = None
 
     def collect_stage1(n):
         buf, cnt = (ctypes.c_float * n)(), ctypes.c_int()
@@ -1194,6 +1245,8 @@ def main():
                 line["roofline"]["train_step_ms"] = line["train_step_ms"]
         if world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_full(N, vit, sd) if kind == "full" else cpu_baseline_stage1(N, C)
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         print(json.dumps(line), flush=True)
     if distributed:
         dist.destroy_process_group()

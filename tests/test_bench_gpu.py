@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 gpu = pytest.mark.gpu
@@ -19,10 +20,11 @@ ROOFLINE_SCALARS = ["frac_algorithmic", "dominant_ms", "dominant_frac_algorithmi
 
 
 @gpu
-def test_bench_line_contract_on_a_small_workload():
-    """`python bench.py --workload full_b8_n42_vits --steps 2 --warmup 1 --no-latency-leg` (a child process): the line a driver reads."""
+def test_bench_line_contract_on_a_small_workload(tmp_path):
+    """`python bench.py --workload full_b8_n42_vits --steps 2 --warmup 1 --no-latency-leg --dump-outputs DIR` (a child process): the line a
+    driver reads, and the last timed step's outputs as DIR/<name>.npy."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "full_b8_n42_vits", "--steps", "2", "--warmup", "1",
-                        "--no-latency-leg"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=ROOT)
+                        "--no-latency-leg", "--dump-outputs", str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -50,3 +52,28 @@ def test_bench_line_contract_on_a_small_workload():
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1 and cb["unit"] == "crops/s" and isinstance(cb["sample"], str)
     x = d["exact_mode"]["f16x3_vs_exact"]
     assert x["pairs_with_same_template"] > 0 and x["flow_max_abs_px"] < 1e-2 and x["keypoint_slots_equal"] > 0.999
+    # --dump-outputs: the hypotheses' Net.forward outputs and the batched PnP/RANSAC results of the last timed step (hyp 5, batch 8)
+    dumped = {n: np.load(os.path.join(str(tmp_path), n + ".npy")) for n in d["dump_outputs"]["arrays"]}
+    assert dumped["pred_poses"].shape == (5, 8, 4, 4) and dumped["tem_pose"].shape == (5, 8, 4, 4) and dumped["pnp_rot"].shape == (5, 8, 3, 3)
+    assert dumped["pnp_tvec"].shape == (5, 8, 3, 1) and dumped["pnp_success"].shape == (5, 8) and dumped["pred_tar_pts"].shape[:2] == (5, 8)
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in dumped.values())
+    ok = dumped["pnp_success"] > 0
+    assert ok.any() and np.abs(np.linalg.det(dumped["pnp_rot"][ok]) - 1).max() < 1e-5      # the PnP poses of the step, not zeros
+
+
+@gpu
+def test_bench_steps_and_dumped_outputs_repeat(tmp_path):
+    """--steps sets the number of timed steps, and two runs with the same arguments compute the same outputs (seeded inputs): the
+    stage-1 workload of BASELINE configs[1], run twice."""
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "stage1_b8_n42_c384", "--steps", "3", "--warmup", "1",
+                            "--no-cpu-baseline", "--dump-outputs", str(tmp_path / run)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        lines.append(json.loads(r.stdout.decode().strip().splitlines()[-1]))
+    for d in lines:
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and abs(d["value"] - 8 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    a = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("score", "index")}
+    b = {n: np.load(str(tmp_path / "b" / (n + ".npy"))) for n in ("score", "index")}
+    assert a["score"].shape == (8, 5) and a["index"].shape == (8, 5) and a["index"].dtype == np.float32
+    assert np.array_equal(a["index"], b["index"]) and np.abs(a["score"] - b["score"]).max() <= 1e-6

@@ -207,3 +207,53 @@ def test_evaluator_loop_reproduces_the_reference_run_test_rows(golden_dir):
                               [data["score"][0][k].item() for k in range(len(inst))], preds, 0.0)
         rows += [ln.rsplit(",", 1)[0] for ln in lines]
     assert rows == d["rows"], next((a, b) for a, b in zip(rows, d["rows"]) if a != b)
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_budget(tmp_path):
+    """bench.py --dump-outputs: every array the timed step hands its caller becomes DIR/<name>.npy in float32 / float64 (integers
+    exactly); over the byte budget each array is replaced by a seeded sample of its elements, the same one on every run."""
+    import os
+    import sys
+
+    import torch
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+
+    outs = [{"pred_poses": torch.full((2, 4, 4), float(k)), "tem_pose": torch.eye(4).repeat(2, 1, 1), "note": "not an array",
+             "pred_tar_pts": torch.arange(-1, 7).reshape(2, 4)} for k in range(3)]
+    pnp = (np.zeros((3, 2, 3, 3)), np.ones((3, 2, 3, 1)), np.full((3, 2), 0.5), np.array([[True, False]] * 3))
+    arrays = bench.step_outputs("full", (outs, pnp))
+    assert sorted(arrays) == ["pnp_inliers_ratio", "pnp_rot", "pnp_success", "pnp_tvec", "pred_poses", "pred_tar_pts", "tem_pose"]
+    written = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    for name, (shape, sampled) in written.items():
+        v = np.load(tmp_path / "a" / (name + ".npy"))
+        assert list(v.shape) == shape and not sampled and v.dtype in (np.float32, np.float64), name
+    assert np.load(tmp_path / "a" / "pred_poses.npy").shape == (3, 2, 4, 4) and np.load(tmp_path / "a" / "pred_poses.npy")[2].min() == 2
+    assert np.load(tmp_path / "a" / "pnp_rot.npy").dtype == np.float64
+    assert np.load(tmp_path / "a" / "pnp_success.npy").tolist() == [[1.0, 0.0]] * 3
+    pts = np.load(tmp_path / "a" / "pred_tar_pts.npy")
+    assert pts.dtype == np.float32 and pts.tolist() == [np.arange(-1, 7).reshape(2, 4).tolist()] * 3      # small integers: float32, exact
+
+    big = {"score": torch.arange(1000, dtype=torch.float32), "index": torch.arange(1000, dtype=torch.int64) + 2 ** 40}
+    assert bench.step_outputs("stage1", (big["score"], big["index"])).keys() == big.keys()
+    for d in ("b", "c"):
+        written = bench.dump_outputs(str(tmp_path / d), big, budget=6000)
+        assert all(sampled for _, sampled in written.values())
+    sizes = [os.path.getsize(tmp_path / "b" / (n + ".npy")) - 128 for n in big]
+    assert sum(sizes) <= 6000, sizes
+    for n in big:
+        b, c = np.load(tmp_path / "b" / (n + ".npy")), np.load(tmp_path / "c" / (n + ".npy"))
+        assert np.array_equal(b, c) and b.size > 0
+    idx = np.load(tmp_path / "b" / "index.npy")
+    assert idx.dtype == np.float64 and (np.diff(idx) > 0).all() and (idx >= 2 ** 40).all() and (idx == np.round(idx)).all()
+
+
+def test_bench_refuses_a_run_without_timed_steps():
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stdout.decode(), r.stdout.decode()[-1000:]
