@@ -630,6 +630,37 @@ int pp_fixed_to_float(const long long* acc, long long n, float* out, void* strea
 int pp_flow_loss_backward(const float* flow, const float* certainty, const float* tar_pts, int B, int H, int W, float max_flow,
                           const float* g_flow, const float* g_cert, float* dflow, float* dcertainty, void* stream);
 
+
+/* ---- fused optimizer step (csrc/pp_optim.hip) ----
+ * Replaces the reference's `optim.AdamW` / `optim.Adam` step (run_train.py:79-85, config/base.yaml:9-20), i.e. torch's
+ * `_single_tensor_adam` per parameter, with two launches over ALL tensors: pass 1 updates p, exp_avg (m) and exp_avg_sq (v) in chunks of
+ * PP_ADAM_CHUNK elements; pass 2 (only when some tensor has an `hl` buffer and terms > 0) re-splits those tensors into the engine's weight
+ * operand — bit for bit what pp_split_weights_ws writes for the updated weight (hl layout, scale2 = [2^e, 2^-e]).
+ * The table (PpAdamTensor[], stable across steps: updates are in place) is laid out in the workspace when `rebuild` != 0 (the call then
+ * waits for the stream once); every step passes the per-tensor step record array `steps` (device memory, PpAdamStep[ntensors]).
+ * Per element, in fp32 and in torch's order:  mode 1 (AdamW): p *= decay;  mode 2 (Adam + weight decay): g += decay * p;
+ *   m = lerp(m, g, lerp_w);  v = v * beta2 + one_minus_beta2 * g * g;  p += neg_step_size * (m / (sqrt(v) * inv_bc2_sqrt + eps)),
+ * each torch op rounded on its own.  The host forms neg_step_size = -lr / (1 - beta1^step) and bc2_sqrt = sqrt(1 - beta2^step) in
+ * double, like torch, and inv_bc2_sqrt = 1 / bc2_sqrt in double, rounded to fp32 (ATen's division by a scalar).
+ * Tensors with n % 8 != 0 are updated and never split.  Null pointers, n <= 0, ntensors <= 0, terms not in {0,1,2}: PP_EINVAL. */
+#define PP_ADAM_CHUNK 65536
+typedef struct PpAdamTensor {
+    float* p;          /* parameter (n,) contiguous fp32, updated in place                                      */
+    float* m;          /* exp_avg (n,)                                                                           */
+    float* v;          /* exp_avg_sq (n,)                                                                        */
+    void* hl;          /* operand buffer pass 2 writes (fp16, terms * n halfs), or NULL: not split               */
+    float* scale2;     /* [2^e, 2^-e] of that split (NULL when hl is NULL)                                       */
+    long long n;
+} PpAdamTensor;
+typedef struct PpAdamStep {
+    const float* g;    /* gradient (n,) contiguous fp32 (may move between steps)                                 */
+    float neg_step_size, inv_bc2_sqrt, decay, lerp_w, beta2, one_minus_beta2, eps;
+    int mode;          /* 0: no weight decay, 1: decoupled (decay = 1 - lr wd), 2: L2 (decay = wd)                 */
+} PpAdamStep;
+int pp_adam_workspace_bytes(const PpAdamTensor* tensors, int ntensors, size_t* bytes);
+int pp_adam_multi_tensor(const PpAdamTensor* tensors, int ntensors, const PpAdamStep* steps, int terms, int rebuild, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,11 @@ class PpGemmDesc(ctypes.Structure):
     ]
 
 
+class PpAdamTensor(ctypes.Structure):
+    _fields_ = [("p", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("hl", ctypes.c_void_p),
+                ("scale2", ctypes.c_void_p), ("n", ctypes.c_longlong)]
+
+
 class PicoPoseHipError(RuntimeError):
     pass
 
@@ -193,6 +198,8 @@ def lib():
         L.pp_corr_lookup_backward_nhwc_fixed.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
         L.pp_fixed_to_float.argtypes = [vp, ll, vp, vp]
         L.pp_flow_loss_backward.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
+        L.pp_adam_workspace_bytes.argtypes = [c.POINTER(PpAdamTensor), i32, c.POINTER(sz)]
+        L.pp_adam_multi_tensor.argtypes = [c.POINTER(PpAdamTensor), i32, vp, i32, i32, vp, sz, vp]
         _lib = L
     return _lib
 

@@ -149,6 +149,27 @@ def split_weight_dev(w):
     return hit[0], hit[1]
 
 
+def device_split_targets(params):
+    """The cached operand buffers of the trained parameters among `params` (the `split_weight_dev` entries of the current operand
+    format), for an optimizer that writes the split of the updated weights itself (picopose_amd.optim, pp_adam_multi_tensor pass 2).
+    Returns (targets, stamp): targets = [(index into params, hl, scale2)], and stamp() — called after the step has written those buffers
+    and bumped the parameters' versions — marks each entry as the split of the new version, so the next forward launches nothing for it."""
+    t = terms()
+    found = []
+    if t:
+        for i, p in enumerate(params):
+            hit = _split_cache.get((p.data_ptr(), tuple(p.shape), t, "dev"))
+            if hit is not None and hit[2] is p:
+                found.append((i, hit[0], hit[4]))
+
+    def stamp():
+        for i, hl, buf in found:
+            p = params[i]
+            _split_cache[(p.data_ptr(), tuple(p.shape), t, "dev")] = (hl, buf[:2], p, p._version, buf)
+
+    return [(i, hl, buf[:2]) for i, hl, buf in found], stamp
+
+
 def drop_split_cache():
     """Forget every cached operand copy of a weight (Packed.invalidate_packed: after a write through `param.data`, which the
     (address, version) keys cannot see)."""
