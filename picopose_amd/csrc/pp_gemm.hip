@@ -321,6 +321,12 @@ __device__ __forceinline__ float top4(const f4 a, const f4 b) {
     return fmaxf(t, fabsf(b[3]));
 }
 
+// an element of 4 the activation split clamps (or a NaN): the on-the-fly kernel's saturation report (pp_common.h)
+__device__ __forceinline__ bool over4(const f4 v) {
+    return !(fabsf(v[0]) * A_SCALE < 65504.f) | !(fabsf(v[1]) * A_SCALE < 65504.f) | !(fabsf(v[2]) * A_SCALE < 65504.f) |
+           !(fabsf(v[3]) * A_SCALE < 65504.f);
+}
+
 template <bool WEIGHT = false>
 __device__ __forceinline__ void split_f16x4(const f4 v, float s, h4& hi, h4& lo) {
 #pragma unroll
@@ -464,12 +470,14 @@ __global__ __launch_bounds__(256, OCC) void gemm_f16x3_kernel(const PpGemmDesc d
     };
 
     const int nk = (d.K + BK - 1) / BK;
+    bool sat = false;   // an fp32 operand element beyond the split's range (|v| >= 16376): reported once per thread after the K loop
     fetch(0);
     for (int kt = 0; kt < nk; ++kt) {
         __syncthreads();  // previous tile fully consumed
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             h4 hh, ll;
+            sat |= over4(ra[j]);
             split_f16x4(ra[j], A_SCALE, hh, ll);
             *(h4*)(Ah + AROW(j) * LDH + kq) = hh;
             *(h4*)(Al + AROW(j) * LDH + kq) = ll;
@@ -478,6 +486,7 @@ __global__ __launch_bounds__(256, OCC) void gemm_f16x3_kernel(const PpGemmDesc d
                     hh = rbh[BSPLIT ? j : 0];
                     ll = rbl[BSPLIT ? j : 0];
                 } else {
+                    sat |= over4(rb[BSPLIT ? 0 : j]);
                     split_f16x4<true>(rb[BSPLIT ? 0 : j], A_SCALE, hh, ll);
                 }
                 *(h4*)(Bh + AROW(j) * LDH + kq) = hh;
@@ -509,6 +518,7 @@ __global__ __launch_bounds__(256, OCC) void gemm_f16x3_kernel(const PpGemmDesc d
                 }
         }
     }
+    pp_sat_flag(sat);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1303,20 +1313,17 @@ int pp_gemm(const PpGemmDesc* desc, void* stream) {
     // and on K; it is measured once per problem shape (timed launches of the same GEMM — idempotent
     // unless the output aliases a residual) and remembered.  PP_GEMM_AUTOTUNE=0 keeps the static choice.
     int cfg = fvec ? (d.N <= 64 ? 6 : 3) : (d.N <= 64 ? 2 : 0);
-    if (const char* f = getenv("PP_GEMM_FORCE_CFG")) {  // tests: pin one kernel configuration
+    bool pinned = false;
+    if (const char* f = getenv("PP_GEMM_FORCE_CFG")) {  // tests: pin one kernel configuration (recorded like any other launch)
         const int fc = atoi(f);
-        if ((fc == 9 || fc == 10) && (asplit || fvec)) {
-            launch(fc);
-            return finish();
-        }
-        if (fc >= 0 && fc <= 8 && (asplit || fc <= 2 || (fvec && fc <= 7))) {
-            launch(fc);
-            return finish();
+        if (((fc == 9 || fc == 10) && (asplit || fvec)) || (fc >= 0 && fc <= 8 && (asplit || fc <= 2 || (fvec && fc <= 7)))) {
+            cfg = fc;
+            pinned = true;
         }
     }
     const bool alias = d.C != nullptr && (d.residual == d.C || d.residual2 == d.C);  // (C is null for operand-only outputs)
     static const bool tune = [] { const char* e = getenv("PP_GEMM_AUTOTUNE"); return !(e && e[0] == '0'); }();
-    if (tune && !alias && (d.N > 64 || fvec)) {
+    if (!pinned && tune && !alias && (d.N > 64 || fvec)) {
         std::mutex& mu = g_tune_mu;
         std::unordered_map<std::string, int>& best = g_tune_best;
         static const bool env_loaded = [] {
@@ -1425,6 +1432,7 @@ int pp_gemm(const PpGemmDesc* desc, void* stream) {
         gp->shape[gp->count][3] = d.conv_kh;
         const int cfg_ = cfg;
         cfg = cfg == 9 ? 5 : cfg == 10 ? 4 : cfg;     // (a tail split is recorded under its big tile; the tail's share of the time rides along)
+        if (fvec && cfg < 3 && d.grp_rows != 0) cfg = 3;   // (launch1: a grouped batch runs on the engine's 128x128 tile)
         gp->shape[gp->count][4] = asplit ? ((!pp_gemm_u_vec_ok(d) && u_cfg(cfg) != 2) ? 0 : u_cfg(cfg)) : cfg;   // (element-wise epilogue: the small tiles)
         // pre-split kernels: the A-delivery mode; the others: 8 + (vector loads) + 2 (f16x3 on the fly) — bench.py names the instantiation
         gp->shape[gp->count][5] = asplit ? (u_cfg(cfg) == 6 ? 1 : pp_gemm_u_mode(d, terms))

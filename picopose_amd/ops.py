@@ -100,11 +100,12 @@ def _chk(hl, what):
     return hl
 
 
-def split_weight(w, cache=True):
+def split_weight(w, cache=True, t=None):
     """(hl, scale) — the f16x3 "hl" operand (fp16 (N, 2K): per 8 k the hi then the lo terms) and power-of-two scale
     of a weight matrix; split once per tensor version (one host sync to read the scale back).  cache=False: a transient matrix
-    (the training graph's re-packed convolution weights): split, not remembered, not kept alive."""
-    t = terms()
+    (the training graph's re-packed convolution weights): split, not remembered, not kept alive.  t: operand terms (default: the
+    current format's)."""
+    t = t or terms()
     if not cache:
         hl = torch.empty(w.shape[0], t * w.shape[1], dtype=torch.float16, device=w.device)
         scale = torch.empty(1, dtype=torch.float32, device=w.device)
@@ -309,10 +310,14 @@ def _fly_prec():
     return 0 if PRECISION == "f32" else 1
 
 
-def _fly_args(wargs):
-    """`wargs` for a launch whose A operand is NOT pre-split: the on-the-fly kernels read fp32 weights (f16 mode: the h-format
-    weights cannot be used there) or hl weights (f16x3)."""
+def _fly_args(wargs, w=None, cache=True):
+    """`wargs` for a launch whose A operand is NOT pre-split: the on-the-fly kernels read hl weights with their power-of-two scale
+    (f16x3; f16 mode: the h-format weights cannot be used there, the hl form of a cached weight `w` is made for them) or fp32 weights.
+    (Read as an ACTIVATION instead — fixed scale 4 — a weight loses its low bits below 2^-5 and saturates beyond 16376.)"""
     if PRECISION == "f16":
+        if w is not None and cache is True and "B_hl" in wargs:
+            hl, scale = split_weight(w, True, t=2)
+            return dict(prec=1, B_hl=_p(hl), b_scale=scale, _hl=hl)
         return dict(prec=1)
     if "alpha_dev" in wargs:     # device-scaled weights (cache="dev") belong to the pre-split kernels: these launches read the fp32 weights
         return dict(prec=_fly_prec())
@@ -375,7 +380,7 @@ def linear(x, weight, bias=None, act=None, gamma=None, residual=None, out=None, 
         out = torch.empty(M, N, dtype=torch.float32, device=x.device)
         ret, ldc, sargs = out, N, {}
     _run(_desc(A=_p(x), B=_p(weight), C=_p(out), bias=_p(bias), gamma=_p(gamma), residual=_p(residual), M=M, N=N, K=K,
-               lda=x.stride(0), ldb=K, ldc=ldc, act=ACT[act], relu_in=int(relu_in), **_fly_args(wargs)))
+               lda=x.stride(0), ldb=K, ldc=ldc, act=ACT[act], relu_in=int(relu_in), **_fly_args(wargs, weight, cache_weight)))
     return ret
 
 
@@ -686,7 +691,7 @@ def conv2d(x, wp, bias, ksize, stride=1, pad=0, act=None, relu_in=False, residua
                conv_bstride=x.stride(0), M=B * Ho * Wo, N=Cout,
                K=ksize * ksize * cin, lda=ld_in, ldb=wp.shape[1], ldc=ldc, act=ACT[act], relu_in=int(relu_in),
                conv_kh=ksize, conv_kw=ksize, conv_cin=cin, conv_stride=stride, conv_pad=pad, conv_h=H, conv_w=W,
-               conv_ho=Ho, conv_wo=Wo, **_fly_args(wargs)))
+               conv_ho=Ho, conv_wo=Wo, **_fly_args(wargs, wp, cache_weight)))
     return ret
 
 
@@ -1003,7 +1008,7 @@ def conv_transpose2d(x, wp, bias_tiled, r, out_split=False):
         return out
     out = torch.empty(B, H * r, W * r, Cout, dtype=torch.float32, device=x.device)
     _run(_desc(A=_p(x), B=_p(wp), C=_p(out), bias=_p(bias_tiled), M=B * H * W, N=r * r * Cout, K=Cin, lda=Cin, ldb=Cin,
-               ldc=Cout, shuffle_r=r, shuffle_h=H, shuffle_w=W, **_fly_args(wargs)))
+               ldc=Cout, shuffle_r=r, shuffle_h=H, shuffle_w=W, **_fly_args(wargs, wp)))
     return out
 
 

@@ -1,8 +1,15 @@
 """GPU numerics of the network engine (GEMM / implicit-GEMM conv / norms) against plain PyTorch
-fp32 CPU references of the same ops."""
+fp32 CPU references of the same ops; the contraction engine's results also against the float64 componentwise bound of
+tests/engine_bounds.py."""
+import os
+import sys
+
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import engine_bounds as eb  # noqa: E402
 
 gpu = pytest.mark.gpu
 TOL = 2e-4  # fp32 products/accumulation on both sides; differences are summation order only
@@ -34,6 +41,15 @@ def _close(a, b, tol=TOL):
     assert err <= tol * scale, (err, scale)
 
 
+def _bound(name, got, op, x, w, **kw):
+    """|got - float64 ref| <= the componentwise bound of the current mode (tests/engine_bounds.py); B's floor: the scaled weight
+    operand where K % 8 == 0 (pre-split or read pre-split by the on-the-fly kernel), else an operand split at activation scale."""
+    K = {"linear": lambda: w.shape[1], "conv2d": lambda: w[0].numel(), "conv_transpose2d": lambda: w.shape[0]}.get(op, lambda: 1)()
+    kw.setdefault("b_fmt", "weight" if K % 8 == 0 else "act")
+    ref, bound = eb.reference(op, x, w, _mode[0], **kw)
+    eb.check(name, got, ref, bound, _mode[0])
+
+
 @gpu
 @pytest.mark.parametrize("M,K,N", [(257, 384, 1152), (8224 // 8, 768, 768), (5, 16384, 1024), (130, 75, 256), (64, 256, 2), (1, 256, 1)])
 @pytest.mark.parametrize("act", [None, "relu", "gelu", "leaky01", "tanh"])
@@ -45,7 +61,9 @@ def test_linear(M, K, N, act):
     ref = F.linear(x, w, b)
     ref = {None: lambda t: t, "relu": F.relu, "gelu": F.gelu, "leaky01": lambda t: F.leaky_relu(t, 0.1),
            "tanh": torch.tanh}[act](ref)
-    _close(ops.linear(x.cuda(), w.cuda(), b.cuda(), act=act), ref)
+    got = ops.linear(x.cuda(), w.cuda(), b.cuda(), act=act)
+    _close(got, ref)
+    _bound(f"linear {M}x{K}x{N} {act}", got, "linear", x, w, bias=b, act=act)
 
 
 @gpu
@@ -58,7 +76,9 @@ def test_linear_layerscale_residual_and_strided_rows():
     gamma, res = torch.randn(96, generator=g), torch.randn(300, 96, generator=g)
     xs = x[:, 64:128]  # a column slice: row stride 192
     ref = res + gamma * F.linear(xs, w, b)
-    _close(ops.linear(x.cuda()[:, 64:128], w.cuda(), b.cuda(), gamma=gamma.cuda(), residual=res.cuda()), ref)
+    got = ops.linear(x.cuda()[:, 64:128], w.cuda(), b.cuda(), gamma=gamma.cuda(), residual=res.cuda())
+    _close(got, ref)
+    _bound("linear layerscale residual strided", got, "linear", xs, w, bias=b, gamma=gamma, residual=res)
 
 
 @gpu
@@ -76,6 +96,7 @@ def test_conv2d_vs_torch(cin, cout, k, s, p, hw):
     ref = F.relu(F.conv2d(x, w, b, stride=s, padding=p))
     out = ops.conv2d(ops.to_nhwc(x.cuda()), ops.pack_conv_weight(w.cuda()), b.cuda(), k, s, p, act="relu")
     _close(ops.to_nchw(out), ref)
+    _bound(f"conv {cin}->{cout} k{k}s{s}p{p}", ops.to_nchw(out), "conv2d", x, w, bias=b, act="relu", stride=s, padding=p)
 
 
 @gpu
@@ -90,6 +111,7 @@ def test_conv2d_relu_in_residual_and_concat_slices():
     xh = ops.to_nhwc(x.cuda())
     out = ops.conv2d(xh, ops.pack_conv_weight(w.cuda()), b.cuda(), 3, 1, 1, relu_in=True, residual=xh)
     _close(ops.to_nchw(out), ref)
+    _bound("conv relu_in residual", ops.to_nchw(out), "conv2d", x, w, bias=b, relu_in=True, residual=x, padding=1)
     if ops.presplit():
         # the same unit with an OPERAND-ONLY output (it feeds one 1x1 convolution: stage3.OUT_CONV_FIRST): residuals are added in the
         # epilogue, the fp32 map is never stored — the operand is the split of the fp32 result
@@ -105,6 +127,8 @@ def test_conv2d_relu_in_residual_and_concat_slices():
     ops.conv2d(wide_in[..., C:2 * C], ops.pack_conv_weight(w.cuda()), b.cuda(), 3, 1, 1, out=wide_out[..., C:], cin=C)
     ref2 = F.conv2d(wide_in[..., C:2 * C].permute(0, 3, 1, 2).cpu(), w, b, padding=1)
     _close(wide_out[..., C:].permute(0, 3, 1, 2), ref2)
+    _bound("conv channel slices", wide_out[..., C:].permute(0, 3, 1, 2), "conv2d", wide_in[..., C:2 * C].permute(0, 3, 1, 2).cpu(), w,
+           bias=b, padding=1)
     assert float(wide_out[..., :C].abs().max()) == 0.0
 
 
@@ -118,7 +142,9 @@ def test_conv_transpose(r, cin, cout):
     w, b = torch.randn(cin, cout, r, r, generator=g) / cin ** 0.5, torch.randn(cout, generator=g)
     ref = F.conv_transpose2d(x, w, b, stride=r)
     wp, bp = ops.pack_convT_weight(w.cuda(), b.cuda())
-    _close(ops.to_nchw(ops.conv_transpose2d(ops.to_nhwc(x.cuda()), wp, bp, r)), ref)
+    got = ops.to_nchw(ops.conv_transpose2d(ops.to_nhwc(x.cuda()), wp, bp, r))
+    _close(got, ref)
+    _bound(f"conv_transpose r={r}", got, "conv_transpose2d", x, w, bias=b, stride=r)
 
 
 @gpu
@@ -135,11 +161,13 @@ def test_attention_products_softmax_layernorm_groupnorm():
     qd, kd, vd = d[:, :, 0].permute(0, 2, 1, 3), d[:, :, 1].permute(0, 2, 1, 3), d[:, :, 2].permute(0, 2, 1, 3)
     s = ops.bmm_nt(qd, kd, alpha=hd ** -0.5)
     _close(s, (q * hd ** -0.5) @ k.transpose(-2, -1))
+    _bound("bmm_nt", s, "bmm_nt", q, k, alpha=hd ** -0.5, b_fmt="act")
     ops.softmax_rows_(s)
     _close(s, att, 1e-5)
     o = torch.empty(B, T, h, hd, device="cuda")
     ops.bmm_nn(s, vd, o.permute(0, 2, 1, 3))
     _close(o.reshape(B, T, h * hd), ref)
+    _bound("bmm_nn", o.permute(0, 2, 1, 3), "bmm_nn", s.cpu(), v, b_fmt="act")     # (against the probabilities it was given)
     fused = ops.attention(d.reshape(B * T, 3 * h * hd), B, T, h, hd)       # the fused kernel the ViT uses
     _close(fused.reshape(B, T, h * hd), ref, 1e-5)
     x = torch.randn(500, 384, generator=g) * 3 + 1
@@ -211,6 +239,7 @@ def test_row_shared_conv3x3_kernel_pinned(monkeypatch, engine_precision):
         monkeypatch.setenv("PP_GEMM_FORCE_CFG", "5")
         out5 = ops.conv2d(xn, wp, b.cuda(), 3, 1, 1, act="relu")
         _close(ops.to_nchw(out6), ref)
+        _bound(f"row-shared conv {B}x{cin}->{cout} {hw}", ops.to_nchw(out6), "conv2d", x, w, bias=b, act="relu", padding=1)
         assert torch.equal(out6, out5), (B, cin, cout, hw, float((out6 - out5).abs().max()))
     _pinned_big_kernel_cases(monkeypatch, "6")     # shapes it does not apply to fall back to the other kernels
 
@@ -222,7 +251,9 @@ def _pinned_big_kernel_cases(monkeypatch, cfg):
     g = torch.Generator().manual_seed(77)
     for M, K, N in [(257, 384, 1152), (1000, 768, 768), (300, 72, 130), (5, 4096, 64), (513, 32, 129), (70000, 96, 256)]:
         x, w, b = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) / K ** 0.5, torch.randn(N, generator=g)
-        _close(ops.linear(x.cuda(), w.cuda(), b.cuda(), act="gelu"), F.gelu(F.linear(x, w, b)))
+        got = ops.linear(x.cuda(), w.cuda(), b.cuda(), act="gelu")
+        _close(got, F.gelu(F.linear(x, w, b)))
+        _bound(f"cfg {cfg} linear {M}x{K}x{N}", got, "linear", x, w, bias=b, act="gelu")
     for cin, cout, k, s, p, hw in [(640, 512, 3, 1, 1, 32), (256, 256, 3, 2, 1, 16), (256, 256, 1, 1, 0, 16), (72, 136, 3, 1, 1, 20),
                                    (8, 64, 7, 1, 3, 32)]:
         x = torch.randn(3, cin, hw, hw, generator=g)
@@ -233,9 +264,13 @@ def _pinned_big_kernel_cases(monkeypatch, cfg):
         out = ops.conv2d(ops.to_nhwc(x.cuda()), ops.pack_conv_weight(w.cuda()), b.cuda(), k, s, p, act="relu",
                          residual=ops.to_nhwc(res.cuda()))
         _close(ops.to_nchw(out), ref)
+        _bound(f"cfg {cfg} conv {cin}->{cout} k{k}s{s}p{p}", ops.to_nchw(out), "conv2d", x, w, bias=b, act="relu", residual=res, stride=s,
+               padding=p)
     x, w, b = torch.randn(2, 64, 16, 16, generator=g), torch.randn(64, 96, 2, 2, generator=g) / 16, torch.randn(96, generator=g)
     wp, bp = ops.pack_convT_weight(w.cuda(), b.cuda())
-    _close(ops.to_nchw(ops.conv_transpose2d(ops.to_nhwc(x.cuda()), wp, bp, 2)), F.conv_transpose2d(x, w, b, stride=2))
+    got = ops.to_nchw(ops.conv_transpose2d(ops.to_nhwc(x.cuda()), wp, bp, 2))
+    _close(got, F.conv_transpose2d(x, w, b, stride=2))
+    _bound(f"cfg {cfg} conv_transpose", got, "conv_transpose2d", x, w, bias=b, stride=2)
 
 
 @gpu
@@ -346,6 +381,10 @@ def test_fp32_engine_agrees_bitwise_across_tile_configurations_and_with_the_roun
     _close(outs["3"][1], res.cpu() + gam.cpu() * F.linear(x.cpu(), w.cpu(), b.cpu()))
     _close(outs["3"][2], x2.cpu() @ w2.cpu().t())
     _close(outs["3"][3], F.leaky_relu(F.linear(xs.cpu(), w.cpu(), b.cpu()), 0.1))
+    _bound("fp32 engine gelu", outs["3"][0], "linear", x.cpu(), w.cpu(), bias=b.cpu(), act="gelu")
+    _bound("fp32 engine layerscale", outs["3"][1], "linear", x.cpu(), w.cpu(), bias=b.cpu(), gamma=gam.cpu(), residual=res.cpu())
+    _bound("fp32 engine K % 32 == 12", outs["3"][2], "linear", x2.cpu(), w2.cpu())
+    _bound("fp32 engine strided rows", outs["3"][3], "linear", xs.cpu(), w.cpu(), bias=b.cpu(), act="leaky01")
 
 
 @gpu
@@ -567,6 +606,7 @@ def test_tail_split_launches_equal_the_single_launch_bitwise(monkeypatch, engine
             assert torch.equal(a_, b_)
     ref = res.cpu() + gam.cpu() * F.gelu(F.linear(x.cpu(), w.cpu(), b.cpu()))
     _close(outs[0][0], ref)
+    _bound("tail split", outs[0][0], "linear", x.cpu(), w.cpu(), bias=b.cpu(), act="gelu", gamma=gam.cpu(), residual=res.cpu())
 
 
 @gpu
