@@ -476,6 +476,12 @@ int pp_winograd_chain_f32(const float* Y, int B, int H, int W, int C, const floa
  * DINOv2 residual streams hold a few very large channels. */
 int pp_set_saturation_word(unsigned int* word);
 
+/* Stream-ordered snapshot of a saturation word: enqueued on `stream`, one lane does *slot = atomicExch(word, 0).  Taken right after a
+ * forward on that forward's stream, the slot holds the flag of exactly the producers enqueued since the previous take (one batch's own
+ * verdict, however many batches are in flight) and the word is clear for the next one.  word: the registered device word
+ * (pp_set_saturation_word); slot: a device uint32.  Null pointers: PP_EINVAL.  Does not synchronise. */
+int pp_saturation_take(unsigned int* word, unsigned int* slot, void* stream);
+
 
 /* The tiled lookup on operands the producers already hold in the engine's hl format (fp16 [pixels][2 ld]: per 8 channels
  * the 8 hi then the 8 lo terms; include "hl" above): f1_hl with rows of ld_f1 channels (a column block of a wider operand

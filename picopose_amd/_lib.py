@@ -115,6 +115,7 @@ def lib():
         L.pp_winograd4_chain.argtypes = [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, c.c_longlong, vp]
         L.pp_winograd_chain_f32.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp]
         L.pp_set_saturation_word.argtypes = [vp]
+        L.pp_saturation_take.argtypes = [vp, vp, vp]
         L.pp_split_weights_t.argtypes = [vp, c.c_longlong, i32, vp, vp, vp]
         L.pp_split_weights_ws.argtypes = [vp, c.c_longlong, i32, vp, vp, vp, vp]
         L.pp_split_activation_t.argtypes = [vp, c.c_longlong, i32, i32, i32, i32, i32, vp, i32, i32, vp]

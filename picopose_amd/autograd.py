@@ -73,7 +73,7 @@ def _pow2_scale(t):
 def _ranged(t, on=True):
     """(range-normalised contiguous copy, its (scale, 1 / scale) pair) — identity in fp32 engine mode and for operands that are
     forward quantities (activations, weights, probabilities: in the operand format's range as they are; on=False)."""
-    if ops.PRECISION == "f32" or not on:
+    if ops.precision() == "f32" or not on:
         return t, None
     t = t.contiguous()
     s2 = _pow2_scale(t)
@@ -94,7 +94,7 @@ def _unscale(out, sa, sb, target=None):
 def _scale_of(t, on=True):
     """Device scale pair of a backward operand WITHOUT a scaled copy (None: fp32 engine, or a forward quantity that is in range as
     it is) — for the products whose operands are split with the scale applied (ops.split_scaled / split_transposed)."""
-    return None if (ops.PRECISION == "f32" or not on) else _pow2_scale(t.contiguous() if not t.is_contiguous() else t)
+    return None if (ops.precision() == "f32" or not on) else _pow2_scale(t.contiguous() if not t.is_contiguous() else t)
 
 
 def _inv(*scales):
@@ -265,7 +265,7 @@ class _Attention(torch.autograd.Function):
     def forward(ctx, qkv, B, T, heads, hd):
         qkv = _f32c(qkv)
         ctx.dims = (B, T, heads, hd)
-        ctx.fused = FUSED_ATTENTION and ops.PRECISION == "f16x3" and hd == 64
+        ctx.fused = FUSED_ATTENTION and ops.precision() == "f16x3" and hd == 64
         if ctx.fused:
             out = torch.empty(B * T, heads * hd, dtype=torch.float32, device=qkv.device)
             lse = torch.empty(B * heads, T, dtype=torch.float32, device=qkv.device)
@@ -806,7 +806,7 @@ class _Conv2d(torch.autograd.Function):
         rows = B * H * W
         db = colsum(dz.view(-1, Cout)) if has_bias and ctx.needs_input_grad[2] else None
         Cout0 = Cout
-        if Cout % 8 != 0 and Cout >= 64 and ops.PRECISION == "f16x3":
+        if Cout % 8 != 0 and Cout >= 64 and ops.precision() == "f16x3":
             # (the motion encoder's 126-channel convolution: its dz and weights zero-padded to 128 channels take the engine in both
             # backward products instead of the on-the-fly kernel; the pad rows of dW are dropped)
             padc = -Cout % 8
@@ -852,7 +852,7 @@ class _Conv2d(torch.autograd.Function):
                 if dzs is None:
                     dzs = _ew(1, dz, s[0:1], 1)
                 dzt = dzs.view(rows, Cout).t().contiguous()                   # (Cout, rows)
-                if ops.PRECISION == "f16x3" and Cout >= 64 and tiles > 24 and rows % 8 == 0:
+                if ops.precision() == "f16x3" and Cout >= 64 and tiles > 24 and rows % 8 == 0:
                     dwp = ops.matmul_nt_presplit(dzt, colT)                   # x is a forward activation: in range as it is
                 else:
                     dwp = _mm_kmajor(dzt, colT)

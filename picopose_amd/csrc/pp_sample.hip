@@ -516,6 +516,12 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) d4[i] = s4[i];
 }
 
+// Stream-ordered snapshot of the sticky saturation word (pp_saturation_take): one lane moves the word into the caller's slot and clears it,
+// so the slot covers exactly the producers enqueued on this stream since the previous take.
+__global__ __launch_bounds__(64) void saturation_take_kernel(unsigned* __restrict__ word, unsigned* __restrict__ slot) {
+    if (threadIdx.x == 0) *slot = atomicExch(word, 0u);
+}
+
 // Crop + resize + normalise of one detection (provider/bop_test_dataset.py:162-177 with utils/data_utils.py:231-250):
 // out_rgb[c] = (resize_linear(image[y1:y2, x1:x2, 2-c] / 255 [* (mask > 0)]) - mean[c]) / std[c], out_mask =
 // resize_nearest(mask[y1:y2, x1:x2]).  cv2.resize semantics on a float image (pixel centres, edge clamp), in double
@@ -869,6 +875,12 @@ int pp_gather_rows(const float* src, const long long* index, long long n_src_row
     const int gx = (int)((n4 + 255) / 256 < 64 ? (n4 + 255) / 256 : 64);
     hipLaunchKernelGGL(gather_rows_kernel, dim3(gx, n), dim3(256), 0, (hipStream_t)stream, src, index, row_floats, n_src_rows,
                        dst);
+    return pp_last_launch();
+}
+
+int pp_saturation_take(unsigned int* word, unsigned int* slot, void* stream) {
+    if (!word || !slot) return PP_EINVAL;
+    hipLaunchKernelGGL(saturation_take_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, word, slot);
     return pp_last_launch();
 }
 

@@ -2,8 +2,10 @@
 
 All activations are token-major / NHWC fp32 device tensors: (rows, C) or (B, H, W, C).  Nothing
 here computes with torch ops — torch only allocates the outputs."""
+import contextlib
 import ctypes
 import os
+import threading
 
 import torch
 
@@ -19,19 +21,47 @@ ACT = {None: 0, "none": 0, "relu": 1, "gelu": 2, "leaky01": 3, "tanh": 4}
 #   "f16"   plain fp16 operands f16(4 x) ("h" format), ONE fp16 MFMA per product, fp32 accumulate — the arithmetic BASELINE
 #           configs[4] names ("fp16 storage / MFMA with fp32 accumulate"); half the operand bytes and a third of the MFMAs
 #           of f16x3, at fp16-grade results (error ~5e-4 .. 5e-3 of a tensor's maximum, profiles/r02/precision_study.md).
+# PRECISION is the process-wide default; a thread may override it for a stretch of code with `precision_scope` (Net.precision runs each
+# forward under one).  Every reader goes through `precision()`.
 PRECISION = "f16x3"
 _PREC = {"f32": 0, "f16x3": 1, "f16": 2}
 _split_cache = {}
+_scope = threading.local()
+
+
+def precision():
+    """The arithmetic mode in force on this thread: the innermost `precision_scope`, else the global PRECISION."""
+    return getattr(_scope, "mode", None) or PRECISION
+
+
+def check_precision(mode):
+    """mode: None (follow the global) or one of "f32", "f16x3", "f16"; anything else raises ValueError."""
+    if mode is not None and mode not in _PREC:
+        raise ValueError(f"unknown arithmetic mode {mode!r}: expected None or one of {sorted(_PREC)}")
+    return mode
+
+
+@contextlib.contextmanager
+def precision_scope(mode):
+    """Run the body in arithmetic mode `mode` on this thread only (None: no override; the global PRECISION is never written)."""
+    check_precision(mode)
+    prev = getattr(_scope, "mode", None)
+    if mode is not None:
+        _scope.mode = mode
+    try:
+        yield
+    finally:
+        _scope.mode = prev
 
 
 def terms():
     """fp16 terms per operand element of the engine's current operand format: 2 = hl (f16x3), 1 = h (f16); 0 = no operands (f32)."""
-    return {"f32": 0, "f16x3": 2, "f16": 1}[PRECISION]
+    return {"f32": 0, "f16x3": 2, "f16": 1}[precision()]
 
 
 def presplit():
     """The engine runs on pre-split operands (Split objects between producers and consumers)."""
-    return PRECISION != "f32"
+    return precision() != "f32"
 
 # The f16x3 engine stores an activation operand as hi = f16(4 x), lo = f16(4 x - hi): |x| must stay below
 # 65504 / 4 = 16376, beyond which the split SATURATES (finite, but wrong) — fp32 has no such limit.  Trained networks
@@ -47,7 +77,9 @@ saturation_checks = 0        # operands verified since import (bench.py reports 
 # (csrc/pp_common.h pp_sat_flag: an atomic only from a wave that saw one — nothing in a healthy forward); the host reads the word together
 # with a batch's poses (picopose_amd/utils/pose_recovery.py: one more row of the packed device->host copy — no extra synchronisation) and
 # raises instead of returning poses computed from clipped operands.  A caller of the bare `Net.forward` asks with `saturation_raised()`
-# (a 4-byte copy + wait) or reads `saturation_word()` itself.  PP_SAT_FLAG=0 switches the reporting off.
+# (a 4-byte copy + wait) or reads `saturation_word()` itself.  PP_SAT_FLAG=0 switches the reporting off.  The evaluator's opt-in fallback
+# (pipeline.py on_saturation="exact") instead snapshots the word into a per-batch slot right after each forward (`saturation_take`) and
+# re-runs a flagged mini-batch in strict fp32.
 SATURATION_FLAG = os.environ.get("PP_SAT_FLAG", "1") != "0"
 _sat_words = {}            # device index -> registered int32 tensor (1,)
 
@@ -85,6 +117,20 @@ def saturation_raised(reset=True, device=None):
     if hit and reset:
         w.zero_()
     return hit
+
+
+def saturation_take(device, slot):
+    """Enqueue on `device`'s current stream: slot <- the saturation word, word <- 0 (pp_saturation_take; no synchronisation).  slot: int32 (1,)
+    on `device`.  Taken right after a forward, the slot is THAT forward's verdict — the producers enqueued since the previous take — however
+    many batches are in flight (picopose_amd/pipeline.py, on_saturation="exact").  With the reporting off the slot is zeroed."""
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        w = saturation_word(dev)
+        if w is None:
+            slot.zero_()
+        else:
+            _lib.check(_lib.lib().pp_saturation_take(_p(w), _p(slot), _lib.stream_ptr()), "pp_saturation_take")
+    return slot
 
 
 def _chk(hl, what):
@@ -298,23 +344,23 @@ def _weight_args(w, K, cache=True):
     if presplit() and K % 8 == 0 and w.data_ptr() % 16 == 0:
         if cache == "dev":                 # a trained parameter: scale on the device, taken by the launch through alpha_dev
             hl, s2 = split_weight_dev(w)
-            return dict(prec=_PREC[PRECISION], B_hl=_p(hl), b_scale=1.0, alpha_dev=_p(s2[1:2]), _hl=(hl, s2))
+            return dict(prec=_PREC[precision()], B_hl=_p(hl), b_scale=1.0, alpha_dev=_p(s2[1:2]), _hl=(hl, s2))
         hl, scale = split_weight_tracked(w, *cache) if isinstance(cache, tuple) else split_weight(w, cache)
-        return dict(prec=_PREC[PRECISION], B_hl=_p(hl), b_scale=scale, _hl=hl)
+        return dict(prec=_PREC[precision()], B_hl=_p(hl), b_scale=scale, _hl=hl)
     return dict(prec=_fly_prec())
 
 
 def _fly_prec():
     """Arithmetic of the kernels that take fp32 operands (tiny / unaligned layers, batched products): exact fp32 MFMA, or the
     f16x3 split on the fly — also in "f16" mode, whose single-term kernels exist for pre-split operands only."""
-    return 0 if PRECISION == "f32" else 1
+    return 0 if precision() == "f32" else 1
 
 
 def _fly_args(wargs, w=None, cache=True):
     """`wargs` for a launch whose A operand is NOT pre-split: the on-the-fly kernels read hl weights with their power-of-two scale
     (f16x3; f16 mode: the h-format weights cannot be used there, the hl form of a cached weight `w` is made for them) or fp32 weights.
     (Read as an ACTIVATION instead — fixed scale 4 — a weight loses its low bits below 2^-5 and saturates beyond 16376.)"""
-    if PRECISION == "f16":
+    if precision() == "f16":
         if w is not None and cache is True and "B_hl" in wargs:
             hl, scale = split_weight(w, True, t=2)
             return dict(prec=1, B_hl=_p(hl), b_scale=scale, _hl=hl)
@@ -414,7 +460,7 @@ def ksplit_choice(M, N, K, can_pad=True):
     work items of ONE engine launch (PpGemmDesc.ksplit), K padded with zeros to a multiple of 64 S when the producer can
     (can_pad).  Chosen from the shape only (a cost model in units of k per work item: rounds over the 256 CUs x (slice length + a
     tile's fixed cost)), so the summation order is a function of the shape.  S = 1: no slices."""
-    if not KSPLIT or M % 256 != 0 or N % 8 != 0 or PRECISION != "f16x3":     # (the sliced kernel exists for the hl format and the vector epilogue)
+    if not KSPLIT or M % 256 != 0 or N % 8 != 0 or precision() != "f16x3":     # (the sliced kernel exists for the hl format and the vector epilogue)
         return 1, K
     t = -(-M // 256) * -(-N // 256)
     base = -(-t // 256) * (K + 512)
@@ -431,7 +477,7 @@ def ksplit_choice(M, N, K, can_pad=True):
 
 def operands_ok(M, N, K):
     """Shapes the pre-split engine takes for a product of two transient operands (32-bit byte offsets into either operand)."""
-    return presplit() and PRECISION == "f16x3" and M >= 64 and N >= 64 and K % 8 == 0 and M * K < 2 ** 30 and N * K < 2 ** 30
+    return presplit() and precision() == "f16x3" and M >= 64 and N >= 64 and K % 8 == 0 and M * K < 2 ** 30 and N * K < 2 ** 30
 
 
 def matmul_operands(A, Bt, alpha_dev=(), out=None, ksplit=1):
@@ -446,14 +492,14 @@ def matmul_operands(A, Bt, alpha_dev=(), out=None, ksplit=1):
     ad = list(alpha_dev) + [None, None]
     if ksplit > 1:
         part = torch.empty(ksplit, M, N, dtype=torch.float32, device=A.device)
-        _run(_desc(A_hl=_p(A.hl), B_hl=_p(Bt.hl), b_scale=4.0, C=_p(part), M=M, N=N, K=K, lda=K, ldb=K, ldc=N, prec=_PREC[PRECISION],
+        _run(_desc(A_hl=_p(A.hl), B_hl=_p(Bt.hl), b_scale=4.0, C=_p(part), M=M, N=N, K=K, lda=K, ldb=K, ldc=N, prec=_PREC[precision()],
                    alpha_dev=_p(ad[0]), alpha_dev2=_p(ad[1]), ksplit=ksplit, _keep=(A.hl, Bt.hl, part)))
         tgt = out if out.is_contiguous() else torch.empty(M, N, dtype=torch.float32, device=A.device)
         _lib.check(_lib.lib().pp_sum_slices(_p(part), ksplit, M, N, None, 0, _p(tgt), _lib.stream_ptr()), "pp_sum_slices")
         if tgt is not out:
             out.copy_(tgt)
         return out
-    _run(_desc(A_hl=_p(A.hl), B_hl=_p(Bt.hl), b_scale=4.0, C=_p(out), M=M, N=N, K=K, lda=K, ldb=K, ldc=out.stride(0), prec=_PREC[PRECISION],
+    _run(_desc(A_hl=_p(A.hl), B_hl=_p(Bt.hl), b_scale=4.0, C=_p(out), M=M, N=N, K=K, lda=K, ldb=K, ldc=out.stride(0), prec=_PREC[precision()],
                alpha_dev=_p(ad[0]), alpha_dev2=_p(ad[1]), _keep=(A.hl, Bt.hl)))
     return out
 
@@ -466,11 +512,11 @@ def matmul_nt_presplit(a, bt):
     N = bt.shape[0]
     assert bt.shape[1] == K and a.is_contiguous() and bt.is_contiguous()
     out = torch.empty(M, N, dtype=torch.float32, device=a.device)
-    if presplit() and PRECISION == "f16x3" and N >= 64 and M >= 64 and _can_presplit(a, K, K, K) and bt.data_ptr() % 16 == 0 \
+    if presplit() and precision() == "f16x3" and N >= 64 and M >= 64 and _can_presplit(a, K, K, K) and bt.data_ptr() % 16 == 0 \
             and M * K < 2 ** 30 and N * K < 2 ** 30:
         ah = split_activation(a, 1, M, K, 0, K)
         bh = split_activation(bt, 1, N, K, 0, K)
-        _run(_desc(A_hl=_p(ah), B=_p(bt), B_hl=_p(bh), b_scale=4.0, C=_p(out), M=M, N=N, K=K, lda=K, ldb=K, ldc=N, prec=_PREC[PRECISION]))
+        _run(_desc(A_hl=_p(ah), B=_p(bt), B_hl=_p(bh), b_scale=4.0, C=_p(out), M=M, N=N, K=K, lda=K, ldb=K, ldc=N, prec=_PREC[precision()]))
         return out
     _run(_desc(A=_p(a), B=_p(bt), C=_p(out), M=M, N=N, K=K, lda=K, ldb=K, ldc=N, prec=_fly_prec()))
     return out
@@ -613,7 +659,7 @@ def conv2d(x, wp, bias, ksize, stride=1, pad=0, act=None, relu_in=False, residua
         _lib.check(_lib.lib().pp_conv_narrow_hl(_p(xs.hl), Cx, B, H, W, Cx, _p(wp), _p(bias), ksize, Cout, _p(residual), _p(out),
                                                 _lib.stream_ptr()), "pp_conv_narrow_hl")
         return out
-    if (xs is None and PRECISION == "f32" and Cout <= 2 and ksize in (1, 3) and stride == 1 and pad == ksize // 2 and act is None and out is None
+    if (xs is None and precision() == "f32" and Cout <= 2 and ksize in (1, 3) and stride == 1 and pad == ksize // 2 and act is None and out is None
             and not relu_in and residual2 is None and cin == Cx and Cx % 32 == 0 and W in (16, 32, 64) and H % (256 // W) == 0
             and ld_in % 4 == 0 and x.data_ptr() % 16 == 0 and x.stride(0) == H * W * ld_in and wp.dtype == torch.float32 and wp.is_contiguous()
             and (residual is None or (residual.is_contiguous() and tuple(residual.shape) == (B, H, W, Cout)))
@@ -730,7 +776,7 @@ class WinoInput:
 
 def _winograd_ok(B, H, W, cin, ld_in, x):
     P = B * (H // 2) * (W // 2)      # (P % 256 != 0: the products cannot share a launch — sixteen small launches pay only on larger maps)
-    return (PRECISION == "f32" and WINOGRAD and H % 2 == 0 and W % 2 == 0 and cin % 4 == 0
+    return (precision() == "f32" and WINOGRAD and H % 2 == 0 and W % 2 == 0 and cin % 4 == 0
             and B * H * W >= (WINOGRAD_MIN_PIXELS if P % 256 == 0 else 4 * WINOGRAD_MIN_PIXELS) and ld_in % 4 == 0 and x.data_ptr() % 16 == 0 and x.stride(0) % 4 == 0 and not torch.is_grad_enabled())
 
 
@@ -819,7 +865,7 @@ class WinoInput4:
 
 def _winograd4_ok(B, H, W, cin, cout):
     P = B * (H // 4) * (W // 4)
-    return (PRECISION == "f16x3" and WINOGRAD4 and H % 4 == 0 and W % 4 == 0 and cin % 8 == 0 and cout % 8 == 0
+    return (precision() == "f16x3" and WINOGRAD4 and H % 4 == 0 and W % 4 == 0 and cin % 8 == 0 and cout % 8 == 0
             and 36 * (P + 255) < 2 ** 31 and not torch.is_grad_enabled())
 
 
@@ -1186,7 +1232,7 @@ def corr_lookup(f1, f2, flow, levels, radius, c_pad=None, f1_hl=None, f2_hl=None
     n = levels * (2 * radius + 1) ** 2
     np_ = c_pad if c_pad and c_pad > n else n
     out = (torch.zeros if np_ > n else torch.empty)(B, H, W, np_, dtype=torch.float32, device=f1.device)
-    if (f1_hl is not None and f2_hl is not None and PRECISION == "f16x3" and f2_hl.terms == 2 and H % 8 == 0 and W % 8 == 0 and C % 32 == 0
+    if (f1_hl is not None and f2_hl is not None and precision() == "f16x3" and f2_hl.terms == 2 and H % 8 == 0 and W % 8 == 0 and C % 32 == 0
             and os.environ.get("PP_CORR_TILED", "1") != "0" and os.environ.get("PP_CORR_HL", "1") != "0"):
         tgt, col0 = f1_hl
         assert tgt.shape[0] == B * H * W and col0 % 8 == 0 and col0 + C <= tgt.shape[1] and f2_hl.shape == (f2.shape[0] * H * W, C)
@@ -1197,7 +1243,7 @@ def corr_lookup(f1, f2, flow, levels, radius, c_pad=None, f1_hl=None, f2_hl=None
         return out
     _lib.check(_lib.lib().pp_corr_lookup_nhwc_ex(_p(f1), f1.stride(2), _p(pyr[0]), _p(pyr[1]) if levels > 1 else None,
                                                  _p(pyr[2]) if levels > 2 else None, f2.shape[0], _p(flow), B, H, W, C,
-                                                 levels, radius, flow.stride(2), 2 if PRECISION == "f16" else _fly_prec(), _p(out), np_,
+                                                 levels, radius, flow.stride(2), 2 if precision() == "f16" else _fly_prec(), _p(out), np_,
                                                  _lib.stream_ptr()), "pp_corr_lookup_nhwc_ex")
     return out
 

@@ -39,7 +39,7 @@ def _tensor_key(t, fe=None):
     The address identifies the contents only while the tensor is ALIVE (the stash keeps it), and the version counter only sees writes made
     through torch: a buffer refilled in place by a custom kernel or through DLPack must be passed as a new tensor, or refilled with
     `copy_`."""
-    key = (t.data_ptr(), tuple(t.shape), t._version, ops.PRECISION)
+    key = (t.data_ptr(), tuple(t.shape), t._version, ops.precision())
     return key if fe is None else key + (fe._signatures()[0],)
 
 
@@ -70,6 +70,18 @@ class Net(nn.Module):
         self.keep_stage3 = False
         self.last_stage3 = None
         self.train_backward = True   # True / "full" | "vit+stage2" | "slice1" | False: what trains under autograd (picopose_amd/autograd.py)
+        # arithmetic of this network's forwards: None follows the global ops.PRECISION; "f32" / "f16x3" / "f16" holds for every call of this
+        # model (ops.precision_scope, per thread), whatever the global says — two models of one process can run in different modes
+        self.precision = None
+        self.range_fallbacks = 0     # mini-batches re-run in strict fp32 after a clamped operand (pipeline.py, on_saturation="exact")
+
+    @property
+    def precision(self):
+        return self._precision
+
+    @precision.setter
+    def precision(self, mode):
+        self._precision = ops.check_precision(mode)
 
     def invalidate_packed(self):
         """Drop every derived copy of the weights (packed / BatchNorm-folded / pre-split) in every sub-module.  Needed only after
@@ -338,6 +350,9 @@ class Net(nn.Module):
         return end_points
 
     def forward(self, end_points, hyp=5, next_real_rgb=None):
-        if self.training:
-            return self.forward_train(end_points)
-        return self.forward_test(end_points, hyp, next_real_rgb=next_real_rgb)
+        """Runs under `self.precision` (None: the global ops.PRECISION).  In training, the backward of `loss.backward()` runs outside this
+        call: it follows the mode in force where it is called."""
+        with ops.precision_scope(self.precision):
+            if self.training:
+                return self.forward_train(end_points)
+            return self.forward_test(end_points, hyp, next_real_rgb=next_real_rgb)

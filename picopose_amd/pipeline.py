@@ -1,11 +1,21 @@
 """Per-batch inference as the reference's evaluator runs it (run_test.py:151-186): network forward, then
 PnP/RANSAC for every (instance, hypothesis), hypotheses ranked by inlier ratio, stage-2 pose as the
 fallback when PnP fails.  One batched PnP launch and one device->host copy per batch instead of the
-reference's B*hyp host round trips."""
+reference's B*hyp host round trips.
+
+on_saturation: what a mini-batch whose forward clamped an f16x3 / f16 operand (ops.saturation_word) turns into.  "raise" (default): the
+PicoPoseHipError of pose_recovery.py.  "exact": a snapshot of the word is taken on the forward's stream right after it
+(ops.saturation_take), travels with the batch's poses, and a set snapshot re-runs that mini-batch alone in strict fp32 (Net.precision = "f32",
+match_mode = "exact") — its poses are then the f32 network's, the other mini-batches keep the fast mode's; net.range_fallbacks counts the
+re-runs.  The snapshot is taken from the word of the batch's own device, so several devices keep separate verdicts (by construction: the
+tests have one GPU)."""
 import numpy as np
 import torch
 
+from . import ops
 from .utils.pose_recovery import pose_recovery_ransac_pnp_batched
+
+ON_SATURATION = ("raise", "exact")
 
 
 def pnp_inputs(outputs, real_K):
@@ -16,22 +26,24 @@ def pnp_inputs(outputs, real_K):
             cat("pred_src_pts"))
 
 
-def pnp_for_outputs(outputs, real_K, return_npts=False):
+def pnp_for_outputs(outputs, real_K, return_npts=False, sat_slot=None):
     """outputs: list (hyp) of Net.forward dicts; real_K (B,3,3) -> rot (hyp,B,3,3), tvec (hyp,B,3,1), ratio, ok
-    [+ npts (hyp,B): correspondences each problem received]."""
+    [+ npts (hyp,B): correspondences each problem received] [+ saturated (bool): the forward's snapshot `sat_slot` was set]."""
     hyp, B = len(outputs), outputs[0]["pred_poses"].shape[0]
-    res = pose_recovery_ransac_pnp_batched(*pnp_inputs(outputs, real_K), return_npts=return_npts)
+    res = pose_recovery_ransac_pnp_batched(*pnp_inputs(outputs, real_K), return_npts=return_npts, sat_slot=sat_slot)
     rot, tvec, ratio, ok = res[:4]
     out = (rot.reshape(hyp, B, 3, 3), tvec.reshape(hyp, B, 3, 1), ratio.reshape(hyp, B), ok.reshape(hyp, B))
-    return out + (res[4].reshape(hyp, B),) if return_npts else out
+    out = out + (res[4].reshape(hyp, B),) if return_npts else out
+    return out + (res[-1],) if sat_slot is not None else out
 
 
-def pnp_for_outputs_async(outputs, real_K, host=None, stream=None):
+def pnp_for_outputs_async(outputs, real_K, host=None, stream=None, sat_slot=None):
     """pnp_for_outputs without the host wait -> handle; `pnp_collect(handle, hyp, B)` reads it (one batch later in a serving loop).
-    stream: run the PnP launch and the copy on this side stream, beside the next batch's forward (pose_recovery_ransac_pnp_batched_async)."""
+    stream: run the PnP launch and the copy on this side stream, beside the next batch's forward (pose_recovery_ransac_pnp_batched_async).
+    sat_slot: the forward's saturation snapshot rides in the copy; `handle.saturated` holds it after pnp_collect."""
     from .utils.pose_recovery import pose_recovery_ransac_pnp_batched_async
 
-    return pose_recovery_ransac_pnp_batched_async(*pnp_inputs(outputs, real_K), host=host, stream=stream)
+    return pose_recovery_ransac_pnp_batched_async(*pnp_inputs(outputs, real_K), host=host, stream=stream, sat_slot=sat_slot)
 
 
 def pnp_collect(handle, hyp, B):
@@ -56,18 +68,63 @@ def _rank_hypotheses(stage2, rot, tvec, ratio, ok, hyp):
     return results
 
 
-def infer_batch(net, end_points, hyp=5, pnp_fn=None):
+def _check_on_saturation(on_saturation):
+    if on_saturation not in ON_SATURATION:
+        raise ValueError(f"on_saturation must be one of {ON_SATURATION}, not {on_saturation!r}")
+    return on_saturation == "exact"
+
+
+def _new_slot(device):
+    return torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def _pnp_checked(outputs, real_K, slot, pnp_fn):
+    """PnP of a forward whose saturation snapshot is `slot` -> ((rot, tvec, ratio, ok), saturated)."""
+    if pnp_fn is None:
+        *res, saturated = pnp_for_outputs(outputs, real_K, sat_slot=slot)
+        return tuple(res), saturated
+    return pnp_fn(outputs, real_K), bool(slot.item())       # (an injected PnP: the slot is read on its own)
+
+
+def _forward_exact(net, end_points, hyp, pnp_fn=None):
+    """The fallback: one mini-batch again, alone (no look-ahead), in strict fp32 -> (outputs, (rot, tvec, ratio, ok)).  The mode is the
+    model's own for this call (Net.precision): the global ops.PRECISION is not touched."""
+    net.range_fallbacks += 1
+    prev = net.precision, net.match_mode
+    net.precision, net.match_mode = "f32", "exact"
+    try:
+        outputs = net(end_points, hyp)
+    finally:
+        net.precision, net.match_mode = prev
+    dev = end_points["real_rgb"].device
+    pnp, saturated = _pnp_checked(outputs, end_points["real_K"], ops.saturation_take(dev, _new_slot(dev)), pnp_fn)
+    if saturated:      # (fp32 has no operand format to leave: nothing is left to fall back to)
+        raise ops.saturation_error("the strict-fp32 re-run of a mini-batch")
+    return outputs, pnp
+
+
+def infer_batch(net, end_points, hyp=5, pnp_fn=None, on_saturation="raise"):
     """-> per-instance pose hypotheses sorted by inlier ratio (run_test.py:168-186):
     list over instances of list over hypotheses of dict(R (3,3), t (3,), inliers_ratio, pnp_success).
     pnp_fn(outputs, real_K) -> (rot (hyp,B,3,3), tvec (hyp,B,3,1), ratio (hyp,B), ok (hyp,B)) replaces the batched HIP
-    PnP (tests of the loop semantics inject canned answers)."""
-    outputs = net(end_points, hyp)
-    rot, tvec, ratio, ok = (pnp_fn or pnp_for_outputs)(outputs, end_points["real_K"])
+    PnP (tests of the loop semantics inject canned answers).
+    on_saturation: "raise" | "exact" (module docstring): with "exact" a forward that clamped an operand is run again in strict fp32."""
+    if not _check_on_saturation(on_saturation):
+        outputs = net(end_points, hyp)
+        rot, tvec, ratio, ok = (pnp_fn or pnp_for_outputs)(outputs, end_points["real_K"])
+    else:
+        dev = end_points["real_rgb"].device
+        ops.saturation_word(dev)            # (registered before the first producer of this device runs)
+        net._query_stash = None             # this forward computes its own query ViT: the snapshot then covers all of this batch
+        outputs = net(end_points, hyp)
+        (rot, tvec, ratio, ok), saturated = _pnp_checked(outputs, end_points["real_K"], ops.saturation_take(dev, _new_slot(dev)), pnp_fn)
+        if saturated:
+            outputs, (rot, tvec, ratio, ok) = _forward_exact(net, end_points, hyp, pnp_fn)
     stage2 = np.stack([o["pred_poses"].cpu().numpy() for o in outputs])            # (hyp,B,4,4) float32
     return _rank_hypotheses(stage2, rot, tvec, ratio, ok, hyp)
 
 
-def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=True, next_data=None):
+def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=True, next_data=None, on_saturation="raise"):
     """One test image exactly as run_test.py:141-188 walks it: `data` holds the image's instances on dim 1
     (data[key][0] = (n_instance, ...), plus 'obj_idx'), `templates_data[key]` the per-object template bank
     ((n_objects, N, ...), including 'template_feature' and, optionally, an extended bank under 'template_cache').
@@ -78,7 +135,12 @@ def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=
     the card does not idle while the host ranks hypotheses; same results, same order.  pipelined=False: the reference's strictly
     sequential walk (every mini-batch ends with a host wait).
     next_data: the NEXT test image's `data` (an evaluator's loader has it one iteration ahead): the query crops of its first mini-batch
-    ride in this image's last forward, as the mini-batches of one image do among themselves — same results."""
+    ride in this image's last forward, as the mini-batches of one image do among themselves — same results.
+    on_saturation: "raise" (default) | "exact" (module docstring), for both walks.  With "exact" no forward carries another mini-batch's query
+    crops (and next_data is not used): the snapshot taken after a forward is then that mini-batch's own verdict, and a batch re-run in
+    fp32 leaves no look-ahead behind that a later batch would have consumed.  The pipelined walk still launches mini-batch j + 1 before
+    it reads mini-batch j; a flagged j is re-run synchronously when it is read, and preds_image keeps the instance order."""
+    exact = _check_on_saturation(on_saturation)
     n_instance = data["score"].shape[1]
     preds_image = []
 
@@ -99,38 +161,48 @@ def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=
 
     if pnp_fn is not None or not pipelined:
         for start in range(0, n_instance, bs):
-            emit(infer_batch(net, inputs_of(start, min(start + bs, n_instance)), hyp, pnp_fn=pnp_fn))
+            emit(infer_batch(net, inputs_of(start, min(start + bs, n_instance)), hyp, pnp_fn=pnp_fn, on_saturation=on_saturation))
         return preds_image
-    pending = None      # (PnP handle, pinned stage-2 poses, their event, batch size) of the mini-batch in flight
+    pending = None      # (PnP handle, pinned stage-2 poses, their event, batch size, inputs) of the mini-batch in flight
     starts = list(range(0, n_instance, bs))
+    if exact and n_instance > 0:
+        dev = data["real_rgb"].device
+        ops.saturation_word(dev)            # (registered before the first producer of this device runs)
+        net._query_stash = None             # (a look-ahead left by an earlier call: this image's first forward computes its own query ViT)
     for j, start in enumerate(starts):
         inputs = inputs_of(start, min(start + bs, n_instance))
         # the next mini-batch's query crops ride in this one's template-side ViT pass (Net.forward_test): same bits, fuller launches
-        if j + 1 < len(starts):
+        if exact:
+            nxt = None
+        elif j + 1 < len(starts):
             nxt = data["real_rgb"][0][starts[j + 1]:min(starts[j + 1] + bs, n_instance)].contiguous()
         elif next_data is not None and next_data["score"].shape[1] > 0:
             nxt = next_data["real_rgb"][0][0:min(bs, next_data["score"].shape[1])].contiguous()
         else:
             nxt = None
         outputs = net(inputs, hyp, next_real_rgb=nxt) if nxt is not None else net(inputs, hyp)
-        handle = pnp_for_outputs_async(outputs, inputs["real_K"])
+        slot = ops.saturation_take(dev, _new_slot(dev)) if exact else None       # this forward's verdict, in stream order
+        handle = pnp_for_outputs_async(outputs, inputs["real_K"], sat_slot=slot)
         s2 = torch.stack([o["pred_poses"] for o in outputs])                        # (hyp,B,4,4) float32
         s2_host = torch.empty(s2.shape, dtype=s2.dtype, pin_memory=True)
         s2_host.copy_(s2, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         if pending is not None:
-            emit(_collect(pending, hyp))
-        pending = (handle, s2_host, ev, s2.shape[1])
+            emit(_collect(pending, hyp, net))
+        pending = (handle, s2_host, ev, s2.shape[1], inputs if exact else None)
     if pending is not None:
-        emit(_collect(pending, hyp))
+        emit(_collect(pending, hyp, net))
     return preds_image
 
 
-def _collect(pending, hyp):
-    handle, s2_host, ev, B = pending
+def _collect(pending, hyp, net):
+    handle, s2_host, ev, B, inputs = pending
     rot, tvec, ratio, ok = pnp_collect(handle, hyp, B)
     ev.synchronize()
+    if handle.saturated:    # (on_saturation="exact" only: the snapshot of this mini-batch's forward was set)
+        outputs, (rot, tvec, ratio, ok) = _forward_exact(net, inputs, hyp)
+        return _rank_hypotheses(np.stack([o["pred_poses"].cpu().numpy() for o in outputs]), rot, tvec, ratio, ok, hyp)
     return _rank_hypotheses(s2_host.numpy(), rot, tvec, ratio, ok, hyp)
 
 

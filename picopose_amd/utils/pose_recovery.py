@@ -67,28 +67,36 @@ def refit_branches(tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts, iterat
 
 
 def pose_recovery_ransac_pnp_batched(tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts, iterations=150,
-                                     reproj_error=2.0, return_npts=False):
+                                     reproj_error=2.0, return_npts=False, sat_slot=None):
     """All (instance, hypothesis) problems of a batch in ONE launch and ONE device->host copy
     (the reference loops over them on the host with a sync each, run_test.py:168-184).
 
     tar_pts_2d (P,2,H,W), src_pts_3d (P,3,H,W), K (P,3,3), tem_pose (P,4,4), tar_pts/src_pts (P,N,2) int64
     -> rot (P,3,3) f64, tvec (P,3,1) f64, inliers_ratio (P) f64, success (P) bool   (numpy arrays)
-    [+ npts (P) int32 with return_npts]."""
+    [+ npts (P) int32 with return_npts] [+ saturated (bool) with sat_slot].
+    sat_slot: a forward's saturation snapshot (ops.saturation_take): the copy carries THAT instead of the live word, and a set slot is
+    returned as `saturated` instead of raising (the caller recomputes the batch: pipeline.py, on_saturation="exact")."""
     rot, tvec, ratio, ok, npts = pnp_launch(tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts, iterations, reproj_error)
     P = rot.shape[0]
     # one packed device->host copy (P x 15 doubles + the saturation row) instead of four
-    host = _with_sat_row(torch.cat([rot.reshape(P, 9), tvec, ratio[:, None], ok.double()[:, None], npts.double()[:, None]], dim=1)).cpu().numpy()
-    host = _check_sat_row(host, P)
+    host = _with_sat_row(torch.cat([rot.reshape(P, 9), tvec, ratio[:, None], ok.double()[:, None], npts.double()[:, None]], dim=1),
+                         sat_slot).cpu().numpy()
+    if sat_slot is not None:
+        host, saturated = host[:P], bool(host[P, 0] != 0)
+    else:
+        host = _check_sat_row(host, P)
     res = (host[:, :9].reshape(P, 3, 3).copy(), host[:, 9:12].reshape(P, 3, 1).copy(), host[:, 12].copy(), host[:, 13] != 0)
-    return res + (host[:, 14].astype("int32"),) if return_npts else res
+    res = res + (host[:, 14].astype("int32"),) if return_npts else res
+    return res + (saturated,) if sat_slot is not None else res
 
 
-def _with_sat_row(packed):
+def _with_sat_row(packed, slot=None):
     """packed (P, 15) f64 on the device + ONE more row whose first entry is the sticky operand-saturation word (picopose_amd/ops.py): the
-    host learns with the poses' own copy — no extra synchronisation — whether the forward that produced them clamped an operand."""
+    host learns with the poses' own copy — no extra synchronisation — whether the forward that produced them clamped an operand.
+    slot: carry this snapshot of the word instead (ops.saturation_take; the row is then always there)."""
     from .. import ops
 
-    w = ops.saturation_word(packed.device)
+    w = ops.saturation_word(packed.device) if slot is None else slot
     if w is None:
         return packed
     row = torch.zeros(1, packed.shape[1], dtype=packed.dtype, device=packed.device)
@@ -110,27 +118,34 @@ def _check_sat_row(host, P):
 
 class PnPHandle:
     """A batched PnP launch whose result is on its way to the host (pose_recovery_ransac_pnp_batched_async)."""
-    __slots__ = ("host", "event", "P")
+    __slots__ = ("host", "event", "P", "slot", "saturated")
 
-    def __init__(self, host, event, P):
-        self.host, self.event, self.P = host, event, P
+    def __init__(self, host, event, P, slot=False):
+        self.host, self.event, self.P, self.slot, self.saturated = host, event, P, slot, None
 
     def result(self, return_npts=False):
-        """Wait for the copy and unpack: rot (P,3,3) f64, tvec (P,3,1) f64, inliers_ratio (P) f64, success (P) bool [+ npts]."""
+        """Wait for the copy and unpack: rot (P,3,3) f64, tvec (P,3,1) f64, inliers_ratio (P) f64, success (P) bool [+ npts].
+        A launch with a saturation snapshot (sat_slot) does not raise: `.saturated` tells whether the slot was set."""
         self.event.synchronize()
-        host, P = _check_sat_row(self.host.numpy(), self.P), self.P
+        P = self.P
+        if self.slot:
+            host = self.host.numpy()
+            host, self.saturated = host[:P], bool(host[P, 0] != 0)
+        else:
+            host = _check_sat_row(self.host.numpy(), P)
         res = (host[:, :9].reshape(P, 3, 3).copy(), host[:, 9:12].reshape(P, 3, 1).copy(), host[:, 12].copy(), host[:, 13] != 0)
         return res + (host[:, 14].astype("int32"),) if return_npts else res
 
 
 def pose_recovery_ransac_pnp_batched_async(tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts, iterations=150, reproj_error=2.0,
-                                           host=None, stream=None):
+                                           host=None, stream=None, sat_slot=None):
     """pose_recovery_ransac_pnp_batched without the host wait: the launch and ONE asynchronous device->host copy (P x 15 doubles
     into a pinned buffer, `host` to reuse one) are enqueued on the current stream; `.result()` of the returned handle waits for
     them.  A serving loop launches batch i + 1 before it reads batch i's poses, so the GPU never waits for the host.
     stream: a side torch.cuda.Stream for the PnP launch and the copy (it first waits for the current stream, i.e. for the forward
     that produced the inputs): the batch's PnP — one 512-thread workgroup per problem, latency-bound fp64 work on 160 of the
-    256 CUs — then runs beside the NEXT batch's forward instead of in front of it."""
+    256 CUs — then runs beside the NEXT batch's forward instead of in front of it.
+    sat_slot: the forward's saturation snapshot travels in the copy instead of the live word; `.result()` then reports it as `.saturated`."""
     inputs = (tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts)
     if stream is not None:
         stream.wait_stream(torch.cuda.current_stream())
@@ -139,13 +154,16 @@ def pose_recovery_ransac_pnp_batched_async(tar_pts_2d, src_pts_3d, K, tem_pose, 
     with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
         rot, tvec, ratio, ok, npts = pnp_launch(*inputs, iterations, reproj_error)
         P = rot.shape[0]
-        packed = _with_sat_row(torch.cat([rot.reshape(P, 9), tvec, ratio[:, None], ok.double()[:, None], npts.double()[:, None]], dim=1))
+        if sat_slot is not None and stream is not None:
+            sat_slot.record_stream(stream)
+        packed = _with_sat_row(torch.cat([rot.reshape(P, 9), tvec, ratio[:, None], ok.double()[:, None], npts.double()[:, None]], dim=1),
+                               sat_slot)
         if host is None or tuple(host.shape) != tuple(packed.shape):
             host = torch.empty(tuple(packed.shape), dtype=torch.float64, pin_memory=True)
         host.copy_(packed, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-    return PnPHandle(host, ev, P)
+    return PnPHandle(host, ev, P, slot=sat_slot is not None)
 
 
 def pose_recovery_ransac_pnp(tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts):
