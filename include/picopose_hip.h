@@ -72,6 +72,11 @@ int pp_prof_gemm_records2(int max_records, int* shape, float* ms, double* flops,
 int pp_gemm_tune_save(const char* path);
 int pp_gemm_tune_load(const char* path);
 int pp_gemm_tune_entries(void);
+/* The pre-split kernel's epilogue has straight-line bodies for the flag sets of the hot dense launches (the qkv / fc1 / proj / fc2
+ * linears, the Winograd products) next to one generic body that reads every flag at run time; both give the same bits.
+ * pp_gemm_generic_epilogue(1) makes every later launch of the process take the generic body, (0) restores the default.
+ * Returns the previous setting, PP_EINVAL for any other argument.  For tests and A/B timing. */
+int pp_gemm_generic_epilogue(int on);
 
 /* ------------------------------------------------------------------------- *
  * Stage 1: template matching — utils/matching.py:29-69 (matching_templates)

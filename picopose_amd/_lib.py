@@ -87,6 +87,7 @@ def lib():
         L.pp_gemm_tune_save.argtypes = [c.c_char_p]
         L.pp_gemm_tune_load.argtypes = [c.c_char_p]
         L.pp_gemm_tune_entries.argtypes = []
+        L.pp_gemm_generic_epilogue.argtypes = [i32]
         L.pp_stage1_workspace_bytes.argtypes = [i32, i32, i32, c.POINTER(sz)]
         L.pp_stage1_scores.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, sz, vp, vp, vp]
         L.pp_stage1_scores_ex.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, sz, vp, vp, vp]

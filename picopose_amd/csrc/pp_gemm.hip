@@ -23,6 +23,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <atomic>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -1099,7 +1100,33 @@ int pp_split_activation(const float* x, long long batch_stride, int B, int P, in
 
 }  // extern "C"
 PP_SAT_SETTER(pp_sat_set_gemm)
+
+// pp_gemm_generic_epilogue: every launch takes the generic epilogue body (tests compare the kinds against it)
+static std::atomic<int> g_epi_generic{0};
+
+// Epilogue kind of a vector-epilogue launch of the pre-split kernel (pp_gemm_dev.h): a kind only where the descriptor is exactly
+// its flag set, the generic body otherwise
+int pp_gemm_epi_kind(const PpGemmDesc& d) {
+    if (g_epi_generic.load(std::memory_order_relaxed)) return PP_EPI_GENERIC;
+    if (d.residual2 || d.shuffle_r != 0) return PP_EPI_GENERIC;
+    if (!d.C && d.C_hl && d.bias && !d.gamma && !d.residual && !d.c_relu) {
+        if (d.act == PP_ACT_NONE) return PP_EPI_HL_LIN;
+        if (d.act == PP_ACT_GELU) return PP_EPI_HL_GELU;
+        return PP_EPI_GENERIC;
+    }
+    if (d.C && !d.C_hl && d.act == PP_ACT_NONE) {
+        if (d.bias && d.gamma && d.residual) return PP_EPI_C_BGR;
+        if (!d.bias && !d.gamma && !d.residual) return PP_EPI_C_PLAIN;
+    }
+    return PP_EPI_GENERIC;
+}
+
 extern "C" {
+
+int pp_gemm_generic_epilogue(int on) {
+    if (on != 0 && on != 1) return PP_EINVAL;
+    return g_epi_generic.exchange(on);
+}
 
 int pp_gemm(const PpGemmDesc* desc, void* stream) {
     // (B may be NULL when BOTH operands arrive pre-split: products of two transient operands, picopose_amd/ops.matmul_operands)

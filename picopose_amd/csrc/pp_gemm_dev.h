@@ -169,27 +169,45 @@ __device__ __forceinline__ void pp_store_operand8(__amdgpu_buffer_rsrc_t H, cons
 //     GELU, the consumer's input ReLU as a max with 0 or -inf, the split, two 16-byte stores;
 //   * the general form (fp32 output, residuals, LayerScale, pixel-shuffle stores, optional operand output as well), with the
 //     residual rows of the next 16-row block loaded while the current one is processed.
-template <int MI, int NJ, int TERMS>
+// Epilogue kinds.  PP_EPI_GENERIC reads every flag of the descriptor at run time; the others are straight-line bodies for the
+// flag sets of the hot dense launches (pp_gemm_epi_kind on the host picks one only when the descriptor matches it exactly).  A
+// kind is the generic body with its flags turned into constants — the same expressions in the same order — so its results
+// are those of the generic body bit for bit (tests/test_epilogue_kinds_gpu.py).
+//   PP_EPI_HL_LIN   operand-only output (C == NULL, C_hl), bias, no activation, no input ReLU of the consumer  (the qkv linears)
+//   PP_EPI_HL_GELU  the same with GELU                                                                            (fc1)
+//   PP_EPI_C_BGR    fp32 C = residual + gamma * (acc + bias), no operand output                                  (proj, fc2)
+//   PP_EPI_C_PLAIN  fp32 C = descale * acc: no bias, LayerScale, residual or activation                          (Winograd products)
+enum { PP_EPI_GENERIC = 0, PP_EPI_HL_LIN = 1, PP_EPI_HL_GELU = 2, PP_EPI_C_BGR = 3, PP_EPI_C_PLAIN = 4, PP_EPI_KINDS = 5 };
+
+template <int MI, int NJ, int TERMS, int EPI = PP_EPI_GENERIC>
 __device__ __forceinline__ void epilogue_wave16(const PpGemmDesc& d, float descale, f32x4 (&acc)[MI][NJ], int mw, int nw, int lane) {
     static_assert(NJ % 2 == 0, "a lane's 8 columns come from a pair of 16-column tiles");
+    static_assert(EPI >= 0 && EPI < PP_EPI_KINDS, "epilogue kind");
+    constexpr bool GEN = EPI == PP_EPI_GENERIC, HL_ONLY = EPI == PP_EPI_HL_LIN || EPI == PP_EPI_HL_GELU;
+    // the descriptor's flags: read where they are used by the generic body (hoisted into registers they cost it ~10 spilled
+    // VGPRs), constants of a kind
+#define PP_EPI_HAS_C (GEN ? d.C != nullptr : !HL_ONLY)
+#define PP_EPI_HAS_HL (GEN ? d.C_hl != nullptr : HL_ONLY)
+#define PP_EPI_HAS_BIAS (GEN ? d.bias != nullptr : EPI != PP_EPI_C_PLAIN)
+#define PP_EPI_HAS_GAMMA (GEN ? d.gamma != nullptr : EPI == PP_EPI_C_BGR)
     const int l15 = lane & 15, lq = lane >> 4;
-    const __amdgpu_buffer_rsrc_t Hr = pp_rsrc(d.C_hl);
+    const __amdgpu_buffer_rsrc_t Hr = pp_rsrc(GEN || HL_ONLY ? d.C_hl : nullptr);
     const unsigned hrow = (unsigned)d.ldc_h * (2u * TERMS);       // operand bytes per output row
-    const float slope = d.act == PP_ACT_RELU ? 0.f : (d.act == PP_ACT_LEAKY01 ? 0.1f : 1.f);
-    const float hfloor = d.c_relu ? 0.f : -INFINITY;              // the consumer's input ReLU folded into the operand
-    const bool lin_act = d.act != PP_ACT_GELU && d.act != PP_ACT_TANH;
+    const float slope = !GEN ? 1.f : (d.act == PP_ACT_RELU ? 0.f : (d.act == PP_ACT_LEAKY01 ? 0.1f : 1.f));
+    const float hfloor = GEN && d.c_relu ? 0.f : -INFINITY;        // the consumer's input ReLU folded into the operand
+    const bool lin_act = GEN ? d.act != PP_ACT_GELU && d.act != PP_ACT_TANH : EPI != PP_EPI_HL_GELU;
     const int m0 = mw + l15;
     // lanes that turned a magnitude beyond the fp16 range into operand terms (rows past M / columns past N are products of zero-filled
     // operand tiles — bias and activation only — and cannot be what saturates)
     unsigned long long sbad = 0ull;
-    if (!d.C && !d.residual && !d.residual2 && !d.gamma && d.shuffle_r == 0 && d.act != PP_ACT_TANH) {
+    if (GEN ? (!d.C && !d.residual && !d.residual2 && !d.gamma && d.shuffle_r == 0 && d.act != PP_ACT_TANH) : HL_ONLY) {
         const float ds4 = descale * PP_A_SCALE;
 #pragma unroll
         for (int jp = 0; jp < NJ / 2; ++jp) {
             const int n = nw + jp * 32 + 8 * lq;
             const bool ncol = n < d.N;                        // N % 8 == 0: a group of 8 is in or out as a whole
             f4 bias[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-            if (d.bias && ncol) {
+            if (PP_EPI_HAS_BIAS && ncol) {
                 bias[0] = *(const f4*)(d.bias + n);
                 bias[1] = *(const f4*)(d.bias + n + 4);
             }
@@ -225,12 +243,14 @@ __device__ __forceinline__ void epilogue_wave16(const PpGemmDesc& d, float desca
         pp_sat_flag(sbad != 0ull && lane == 0);
         return;
     }
-    const __amdgpu_buffer_rsrc_t Cr = pp_rsrc(d.C), Rr = pp_rsrc(d.residual), R2r = pp_rsrc(d.residual2);
-    const bool hasR = d.residual != nullptr, hasR2 = d.residual2 != nullptr;
+    if constexpr (HL_ONLY) return;   // (the branch above is the whole of these kinds)
+    const __amdgpu_buffer_rsrc_t Cr = pp_rsrc(d.C), Rr = pp_rsrc(GEN || EPI == PP_EPI_C_BGR ? d.residual : nullptr);
+    const __amdgpu_buffer_rsrc_t R2r = pp_rsrc(GEN ? d.residual2 : nullptr);
+    const bool hasR = GEN ? d.residual != nullptr : EPI == PP_EPI_C_BGR, hasR2 = GEN && d.residual2 != nullptr;
     const unsigned crow = (unsigned)d.ldc * 4u;
     // byte offsets of the 8 columns n .. n + 7 of output row m: fp32 image and operand image (pixel-shuffle stores move both)
     auto offsets = [&](int m, int n, unsigned& coff, unsigned& hoff) __attribute__((always_inline)) {
-        if (d.shuffle_r == 0) {
+        if ((GEN ? d.shuffle_r : 0) == 0) {
             coff = (unsigned)m * crow + (unsigned)n * 4u;
             hoff = (unsigned)m * hrow + (unsigned)n * (2u * TERMS);
         } else {  // ConvTranspose2d(kernel = stride = r): columns n .. n + 7 = channels co .. co + 7 of sub-pixel (dy, dx)
@@ -251,8 +271,8 @@ __device__ __forceinline__ void epilogue_wave16(const PpGemmDesc& d, float desca
         if (ncol) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                if (d.bias) bias[h] = *(const f4*)(d.bias + n + 4 * h);
-                if (d.gamma) gam[h] = *(const f4*)(d.gamma + n + 4 * h);
+                if (PP_EPI_HAS_BIAS) bias[h] = *(const f4*)(d.bias + n + 4 * h);
+                if (PP_EPI_HAS_GAMMA) gam[h] = *(const f4*)(d.gamma + n + 4 * h);
             }
         }
         unsigned coff, hoff;
@@ -294,11 +314,11 @@ __device__ __forceinline__ void epilogue_wave16(const PpGemmDesc& d, float desca
                     t = lin_act ? fmaxf(t, t * slope) : act_apply(t, d.act);
                     v[h][c] = fmaf(t, gam[h][c], r[h][c] + r2[h][c]);
                 }
-            if (d.C) {
+            if (PP_EPI_HAS_C) {
                 pp_bstore(Cr, v[0], ok ? coff : 0xFFFFFFFFu);
                 pp_bstore(Cr, v[1], ok ? coff + 16 : 0xFFFFFFFFu);
             }
-            if (d.C_hl) {
+            if (PP_EPI_HAS_HL) {
                 f4 x[2];
 #pragma unroll
                 for (int h = 0; h < 2; ++h)
@@ -316,7 +336,11 @@ __device__ __forceinline__ void epilogue_wave16(const PpGemmDesc& d, float desca
             }
         }
     }
-    if (d.C_hl) pp_sat_flag(sbad != 0ull && lane == 0);
+    if (PP_EPI_HAS_HL) pp_sat_flag(sbad != 0ull && lane == 0);
+#undef PP_EPI_HAS_C
+#undef PP_EPI_HAS_HL
+#undef PP_EPI_HAS_BIAS
+#undef PP_EPI_HAS_GAMMA
 }
 
 // element-wise form of the same epilogue (N % 8 != 0, unaligned rows, pixel shuffle with odd channel counts)

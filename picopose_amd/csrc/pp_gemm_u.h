@@ -17,6 +17,8 @@ int pp_gemm_u_launch(const PpGemmDesc& d, int tile, int terms, int cus, hipStrea
 // 3x3 / stride 1 / pad 1 convolutions on the 256x256 tile with row-shared A delivery (see pp_gemm_u.hip); shape test + launch
 bool pp_gemm_uh_shape_ok(const PpGemmDesc& d, int terms);
 bool pp_gemm_u_vec_ok(const PpGemmDesc& d);
+// epilogue kind (PP_EPI_*, pp_gemm_dev.h) of a vector-epilogue launch; the dense launches of the 256-wide hl tiles use it
+int pp_gemm_epi_kind(const PpGemmDesc& d);
 int pp_gemm_uh_launch(const PpGemmDesc& d, int terms, int cus, hipStream_t st);
 // The fp32-operand engine (pp_gemm_f.hip: LDS-DMA ring + v_mfma_f32_32x32x2_f32, the same tile ids): eligibility test (fills the
 // operand extents a_hl_bytes / b_hl_bytes), A-delivery mode (0 dense, 1 / 2 convolution) and launch

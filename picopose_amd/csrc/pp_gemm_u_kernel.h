@@ -35,6 +35,7 @@
 //   * padded taps, M / N / K tails: out-of-range buffer offsets (the DMA writes zeros, no traffic, no branches).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "pp_gemm_dev.h"
 #include "pp_gemm_u.h"
 
@@ -77,7 +78,8 @@ __device__ __forceinline__ f32x4 pp_mfma16(const h8 a, const h8 b, f32x4 c) {
 // (any Cin % 8 == 0: the 8 k of a lane's chunk share a tap)
 // VEC: the epilogue's vector conditions hold (pp_gemm_u_vec_ok, checked on the host: N % 8 == 0, aligned rows); the
 // element-wise epilogue lives in its own instantiations (both in one kernel cost 100 registers and spills in the 256-wide tiles)
-template <class T, int MODE, int TERMS, bool VEC>
+// EPI: the vector epilogue's kind (pp_gemm_dev.h; chosen on the host by pp_gemm_epi_kind)
+template <class T, int MODE, int TERMS, bool VEC, int EPI = PP_EPI_GENERIC>
 __global__ __launch_bounds__(T::NW * 64, T::OCC) void pp_gemm_u_kernel(const PpGemmDesc d, int gx, int gy) {
 #if defined(__HIP_DEVICE_COMPILE__)  // the host pass only needs the launch stub (it cannot instantiate the LDS-DMA builtins)
     constexpr bool DENSE = MODE == 0 || MODE == 3, KS = MODE == 3;   // MODE 3: dense with K slices (PpGemmDesc.ksplit)
@@ -513,7 +515,7 @@ __global__ __launch_bounds__(T::NW * 64, T::OCC) void pp_gemm_u_kernel(const PpG
                 if (keep[0] + keep[1] + keep[2] + keep[3] == -12345.f) d.C[lane] = keep[0];
             }
 #else
-            if (VEC) epilogue_wave16<MI, NJ, TERMS>(d, descale, acc, mw, nw, lane);
+            if (VEC) epilogue_wave16<MI, NJ, TERMS, EPI>(d, descale, acc, mw, nw, lane);
             else epilogue_scalar16<MI, NJ, TERMS>(d, descale, acc, mw, nw, lane);
 #endif
             since_epi = VEC ? 0 : S;
@@ -684,7 +686,7 @@ __global__ __launch_bounds__(T::NW * 64, T::OCC) void pp_gemm_u_kernel(const PpG
             if (keep[0] + keep[1] + keep[2] + keep[3] == -12345.f) d.C[lane] = keep[0];
         }
 #else
-        if (VEC) epilogue_wave16<MI, NJ, TERMS>(d, descale, acc, mw, nw, lane);
+        if (VEC) epilogue_wave16<MI, NJ, TERMS, EPI>(d, descale, acc, mw, nw, lane);
         else epilogue_scalar16<MI, NJ, TERMS>(d, descale, acc, mw, nw, lane);
 #endif
         since_epi = VEC ? 0 : S;   // (the element-wise epilogue issues a data-dependent number of stores: full waits)
@@ -984,23 +986,35 @@ typedef TileCfg<256, 128, 4, 2, 3, 1, 1> T256x128;   // 8 waves, 64x64 each, 3 x
 typedef TileCfg<128, 128, 2, 2, 2, 2> T128x128;   // 4 waves, 64x64 each, 2 x 32 KB ring: two workgroups per CU
 typedef TileCfg<128, 64, 2, 2, 3, 2> T128x64;     // 4 waves, 64x32 each, 3 x 24 KB ring: two workgroups per CU
 
-template <class T, int MODE, int TERMS, bool VEC>
+template <class T, int MODE, int TERMS, bool VEC, int EPI = PP_EPI_GENERIC>
 static int pp_u_launch_one(const PpGemmDesc& d, int persistent_slots, hipStream_t st) {
     static signed char attr_state[PP_MAX_DEVICES];   // the > 64 KB dynamic-LDS opt-in is per device (and per kernel)
     signed char& ok = attr_state[pp_cur_device()];
     if (ok == 0)
-        ok = hipFuncSetAttribute((const void*)pp_gemm_u_kernel<T, MODE, TERMS, VEC>, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES) == hipSuccess ? 1 : -1;
+        ok = hipFuncSetAttribute((const void*)pp_gemm_u_kernel<T, MODE, TERMS, VEC, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES) == hipSuccess ? 1 : -1;
     if (ok < 0) return PP_ELAUNCH;
     const int gx = (d.N + T::BN - 1) / T::BN, gy = (d.M + T::BM - 1) / T::BM;
     const int nt = gx * gy;
     // persistent: one workgroup per slot (a multiple of 8) walks the tiles; fewer tiles than slots: one tile per workgroup
     const int g = nt < persistent_slots ? (nt + 7) / 8 * 8 : persistent_slots / 8 * 8;
-    hipLaunchKernelGGL((pp_gemm_u_kernel<T, MODE, TERMS, VEC>), dim3(g), dim3(T::NW * 64), T::LDS_BYTES, st, d, gx, gy);
+    hipLaunchKernelGGL((pp_gemm_u_kernel<T, MODE, TERMS, VEC, EPI>), dim3(g), dim3(T::NW * 64), T::LDS_BYTES, st, d, gx, gy);
     return PP_OK;
 }
 
 template <class T, int TERMS, bool VEC>
 static int pp_u_launch_tile(const PpGemmDesc& d, int mode, int slots, hipStream_t st) {
+    // the specialised epilogues: dense launches of the two 256-wide tiles in the hl format (the ViT linears, the Winograd products)
+    if constexpr (VEC && TERMS == 2 && (std::is_same<T, T256x256>::value || std::is_same<T, T256x128>::value)) {
+        if (mode == 0) {
+            switch (pp_gemm_epi_kind(d)) {
+                case PP_EPI_HL_LIN: return pp_u_launch_one<T, 0, TERMS, VEC, PP_EPI_HL_LIN>(d, slots, st);
+                case PP_EPI_HL_GELU: return pp_u_launch_one<T, 0, TERMS, VEC, PP_EPI_HL_GELU>(d, slots, st);
+                case PP_EPI_C_BGR: return pp_u_launch_one<T, 0, TERMS, VEC, PP_EPI_C_BGR>(d, slots, st);
+                case PP_EPI_C_PLAIN: return pp_u_launch_one<T, 0, TERMS, VEC, PP_EPI_C_PLAIN>(d, slots, st);
+                default: break;
+            }
+        }
+    }
     if (mode == 0) return pp_u_launch_one<T, 0, TERMS, VEC>(d, slots, st);
     if (mode == 1) return pp_u_launch_one<T, 1, TERMS, VEC>(d, slots, st);
     if (mode == 3) {   // K slices: the hl format with the vector epilogue only (weight gradients of the training step)
