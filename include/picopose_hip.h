@@ -55,7 +55,8 @@ int pp_prof_collect(float* out_ms, int max_out, int* count);
 int pp_prof_gemm_enable(int max_records);
 int pp_prof_gemm_collect(double* ms, double* flops, int* launches);
 /* Per-launch view of the same records (call BEFORE pp_prof_gemm_collect, which resets them): for record i < *count,
- * shape[6 i ..] = {M, N, K, conv kernel size (0: dense), tile configuration the launch used (PP_GEMM_FORCE_CFG numbering),
+ * shape[6 i ..] = {M, N, K, conv kernel size (0: dense), tile configuration the launch used (PP_GEMM_FORCE_CFG numbering, as
+ * resolved by the one launch plan of csrc/pp_gemm.hip gemm_plan: what ran, not what was requested),
  * kind (0 = both operands pre-split, 1 = other)}, ms[i] its duration, flops[i] = 2 M N K batch. */
 int pp_prof_gemm_records(int max_records, int* shape, float* ms, double* flops, int* count);
 /* The same with 8 ints per record — shape[8 i ..] = {M, N, K, conv kernel size, cfg, kind, A-delivery mode of the pre-split kernel

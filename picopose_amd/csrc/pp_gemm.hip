@@ -1121,14 +1121,21 @@ int pp_gemm_epi_kind(const PpGemmDesc& d) {
     return PP_EPI_GENERIC;
 }
 
-extern "C" {
+// The launch view of a pp_gemm call (gemm_normalise): the descriptor as the kernels take it, and what it says about the operands.
+struct GemmView {
+    PpGemmDesc d;   // grouped batches as one launch (grp_rows), K slices as extra rows (ks_rows), operand extents filled in
+    long long z;    // products in the batch (batch0 * batch1)
+    int terms;      // operand terms: 1 for plain fp16 operands (PP_PREC_F16), 2 otherwise
+    bool vec;       // 16-byte operand loads: K-contiguous operands with lda / ldb / Cin % 4 == 0
+    bool asplit;    // both operands pre-split: pp_gemm_u_kernel / pp_gemm_uh_kernel
+    bool split;     // fp32 operands split on the fly: gemm_f16x3_kernel (unaligned (tiny) layers stay on the fp32 kernel)
+    bool fvec;      // fp32 operands the fp32 engine takes: pp_gemm_f_kernel
+    bool u_vec;     // pre-split: the vector epilogue's conditions hold
+    bool h_shape;   // pre-split: a 3x3 convolution the row-shared kernel takes
+};
 
-int pp_gemm_generic_epilogue(int on) {
-    if (on != 0 && on != 1) return PP_EINVAL;
-    return g_epi_generic.exchange(on);
-}
-
-int pp_gemm(const PpGemmDesc* desc, void* stream) {
+// Validate *desc and rewrite it into the launch view v: PP_OK, or PP_EINVAL for a descriptor no kernel takes.
+static int gemm_normalise(const PpGemmDesc* desc, GemmView& v) {
     // (B may be NULL when BOTH operands arrive pre-split: products of two transient operands, picopose_amd/ops.matmul_operands)
     if (!desc || (!desc->A && !desc->A_hl) || (!desc->B && !(desc->A_hl && desc->B_hl)) || (!desc->C && !desc->C_hl)) return PP_EINVAL;
     {   // operand output: rows of ldc_h elements holding the N columns (pixel-shuffle stores: the N / r^2 channels of a pixel)
@@ -1137,7 +1144,8 @@ int pp_gemm(const PpGemmDesc* desc, void* stream) {
                            (desc->shuffle_r != 0 && (desc->N / r2) % 8 != 0)))
             return PP_EINVAL;
     }
-    PpGemmDesc d = *desc;
+    PpGemmDesc& d = v.d;
+    d = *desc;
     if (d.M <= 0 || d.N <= 0 || d.K <= 0 || d.batch0 <= 0 || d.batch1 <= 0) return PP_EINVAL;
     if (d.act < 0 || d.act > PP_ACT_TANH) return PP_EINVAL;
     if (d.conv_kh != 0) {
@@ -1157,11 +1165,11 @@ int pp_gemm(const PpGemmDesc* desc, void* stream) {
                (d.b_kn || d.ldb % 4 == 0) && d.a_bs0 % 4 == 0 && d.a_bs1 % 4 == 0 && d.b_bs0 % 4 == 0 &&
                d.b_bs1 % 4 == 0;
     if (d.conv_kh != 0 && (d.conv_cin % 4 != 0 || d.conv_bstride % 4 != 0)) vec = false;
+    v.vec = vec;
     static const bool dbg = getenv("PP_GEMM_DEBUG") != nullptr;
     if (dbg && !vec)
         fprintf(stderr, "[pp_gemm] scalar path: M=%d N=%d K=%d lda=%d ldb=%d conv=%dx%d cin=%d b_kn=%d batch=%d A%%16=%d B%%16=%d\n", d.M, d.N, d.K, d.lda,
                 d.ldb, d.conv_kh, d.conv_kw, d.conv_cin, d.b_kn, d.batch0 * d.batch1, (int)((uintptr_t)d.A % 16), (int)((uintptr_t)d.B % 16));
-    const int cus = pp_cu_count();   // cached per device (two runtime calls per GEMM launch otherwise)
     static const bool f_engine_on = [] { const char* e = getenv("PP_F32_ENGINE"); return !(e && e[0] == '0'); }();
     static const bool f_group_on = [] { const char* e = getenv("PP_F32_GROUPED"); return !(e && e[0] == '0'); }();
     d.grp_rows = 0;
@@ -1172,35 +1180,27 @@ int pp_gemm(const PpGemmDesc* desc, void* stream) {
         d.shuffle_r == 0 && !d.residual && !d.residual2 && d.ksplit <= 1 && d.M % 256 == 0 && d.a_bs0 == (long long)d.M * d.lda &&
         d.c_bs0 == (long long)d.M * d.ldc && (long long)d.M * d.batch0 < (1LL << 31) && d.b_bs0 >= 0) {
         PpGemmDesc g = d;
+        g.grp_rows = d.M;
+        g.grp_b_bytes = d.b_bs0 * 4;
         g.M = d.M * d.batch0;
         g.batch0 = 1;
-        const long long extra_b = (long long)(d.batch0 - 1) * d.b_bs0 * 4;
-        if (pp_gemm_f_ok(g) && g.b_hl_bytes + extra_b < 0xFFFFFF00LL) {
-            g.b_hl_bytes += extra_b;
-            g.grp_rows = d.M;
-            g.grp_b_bytes = d.b_bs0 * 4;
-            d = g;
-        }
+        if (pp_gemm_f_ok(g)) d = g;
     }
     // The same for a batch of PRE-SPLIT products (the 36 frequencies of a Winograd F(4x4, 3x3) convolution on the f16x3 engine): A_hl /
     // C blocks one behind the other, the weights of group g b_bs0 ELEMENTS further on — one persistent launch of pp_gemm_u_kernel.
-    long long grp_extra_b = 0;
     if (d.A_hl && d.B_hl && d.batch0 > 1 && d.batch1 == 1 && d.conv_kh == 0 && !d.b_kn && d.shuffle_r == 0 && !d.residual && !d.residual2 &&
         d.ksplit <= 1 && !d.C_hl && d.M % 256 == 0 && d.a_bs0 == (long long)d.M * d.lda && d.c_bs0 == (long long)d.M * d.ldc &&
         (long long)d.M * d.batch0 < (1LL << 31) && d.b_bs0 >= 0 && d.b_bs0 % 8 == 0) {
-        const int eb_ = d.prec == PP_PREC_F16 ? 2 : 4;
-        grp_extra_b = (long long)(d.batch0 - 1) * d.b_bs0;     // elements
         d.grp_rows = d.M;
-        d.grp_b_bytes = d.b_bs0 * eb_;
+        d.grp_b_bytes = d.b_bs0 * (d.prec == PP_PREC_F16 ? 2 : 4);
         d.M *= d.batch0;
         d.batch0 = 1;
     }
-    const long long rows = (d.M + BM - 1) / BM, z = (long long)d.batch0 * d.batch1;
-    hipStream_t st = (hipStream_t)stream;
+    const long long z = v.z = (long long)d.batch0 * d.batch1;
     const bool f16 = d.prec == PP_PREC_F16;          // plain fp16 operands: pre-split kernels only
-    const int terms = f16 ? 1 : 2, eb = 2 * terms;   // operand terms / bytes per element
-    const bool split = d.prec == PP_PREC_F16X3 && vec;  // unaligned (tiny) layers stay on the fp32 kernel
-    const bool asplit = d.A_hl != nullptr;
+    const int terms = v.terms = f16 ? 1 : 2;         // operand terms
+    const bool split = v.split = d.prec == PP_PREC_F16X3 && vec;
+    const bool asplit = v.asplit = d.A_hl != nullptr;
     if (f16 && !asplit) return PP_EINVAL;
     if (asplit) {
         const bool ok = d.B_hl && (d.prec == PP_PREC_F16X3 || f16) && z == 1 && !d.b_kn && !d.relu_in &&
@@ -1208,16 +1208,9 @@ int pp_gemm(const PpGemmDesc* desc, void* stream) {
                         (d.conv_kh == 0 || (d.conv_cin % 8 == 0 && d.conv_bstride % 8 == 0)) &&
                         ((uintptr_t)d.A_hl % 16 == 0) && ((uintptr_t)d.B_hl % 16 == 0);
         if (!ok) return PP_EINVAL;
-        // extents of the operand buffers for the bounds-checked buffer loads
-        const long long a_elems = d.conv_kh != 0
-            ? ((long long)((d.M + (long long)d.conv_ho * d.conv_wo - 1) / ((long long)d.conv_ho * d.conv_wo) - 1) * d.conv_bstride +
-               (long long)d.conv_h * d.conv_w * d.lda)
-            : (long long)(d.M - 1) * d.lda + d.K;
-        const long long b_elems = (long long)(d.N - 1) * d.ldb + d.K + grp_extra_b;
+        pp_gemm_extents(d, 2 * terms, d.a_hl_bytes, d.b_hl_bytes);
         // (32-bit byte offsets; 0xFFFFFFFF is the "reads zero" marker)
-        if (a_elems * eb >= 0xFFFFFF00LL || b_elems * eb >= 0xFFFFFF00LL) return PP_EINVAL;
-        d.a_hl_bytes = a_elems * eb;
-        d.b_hl_bytes = b_elems * eb;
+        if (d.a_hl_bytes >= 0xFFFFFF00LL || d.b_hl_bytes >= 0xFFFFFF00LL) return PP_EINVAL;
     }
     d.ks_rows = 0;
     if (d.ksplit > 1) {   // K slices as extra tile rows (include/picopose_hip.h): from here on d is the launch's view, M = S rows-blocks of K / S
@@ -1235,239 +1228,261 @@ int pp_gemm(const PpGemmDesc* desc, void* stream) {
         if (d.alpha_dev || d.alpha_dev2) return PP_EINVAL;
         d.B_hl = nullptr;
     }
-    // Tile configurations ("cfg", PP_GEMM_FORCE_CFG numbering).  Both operands pre-split (pp_gemm_u_kernel.h): 0 = 128x128 tile, two
-    // workgroups per CU; 2 = 128x64, two per CU; 4 = 256x128 (3, the former one-shot launch of it, is an alias); 5 = 256x256;
-    // 6 = 256x256 with row-shared A delivery (3x3 convolutions); 7 / 8 (the former two / three-workgroups-per-CU K-16 kernels) are
-    // aliases of 0.  All of them persistent (a launch with fewer tiles than slots is one tile per workgroup) and bit-identical
-    // in their results.  fp32 operands (split on the fly, or fp32 MFMA): 0 / 1 = 128x128 at 2 / 3 workgroups per CU, 2 = 128x64.
-    // fp32 operands on aligned shapes: the fp32 engine (pp_gemm_f.hip; configurations 3 = 128x128, 4 = 256x128, 5 = 256x256, 6 = 128x64
-    // — every one of them accumulates in the same order).  The round-1 gemm_kernel keeps batched products, B [K][N], unaligned rows.
-    const bool fvec = f_engine_on && !asplit && !split && vec && z == 1 && (d.grp_rows != 0 || pp_gemm_f_ok(d));
-    const bool h_shape = asplit && pp_gemm_uh_shape_ok(d, terms) && pp_gemm_u_vec_ok(d);
-    auto u_cfg = [&](int cfg) {   // canonical pre-split configuration
-        if (cfg == 3) cfg = 4;
-        if (cfg == 7 || cfg == 8 || cfg == 1) cfg = 0;
-        if (cfg == 6 && !(h_shape && d.N > 128)) cfg = 5;
+    v.fvec = f_engine_on && !asplit && !split && vec && z == 1 && pp_gemm_f_ok(d);
+    if (v.fvec) pp_gemm_extents(d, 4, d.a_hl_bytes, d.b_hl_bytes);
+    v.u_vec = asplit && pp_gemm_u_vec_ok(d);
+    v.h_shape = v.u_vec && pp_gemm_uh_shape_ok(d, terms);
+    return PP_OK;
+}
+
+// TAIL SPLIT (round 6; configurations 9 = 256x256 + tail, 10 = 256x128 + tail).  A persistent launch of T tiles on S slots takes
+// ceil(T / S) rounds; the ViT linears at M = 49 344 leave the last round of 256-row tiles 5-50 % filled (fc1: 9.05 rounds -> 10,
+// proj / fc2: 2.26 -> 3).  The rows of the full rounds run on the big tile, the remaining rows as a second launch on 128x128 tiles
+// (two workgroups per CU: a short round of quarter-size tiles).  Dense launches only (a row's address is base + m * pitch: the tail is the
+// same descriptor with shifted pointers); every tile configuration accumulates in the same order, so the split leaves no trace in the bits.
+static int tail_rows(const GemmView& v, int big_bn, int cus) {   // r: rows [0, r) on the 256 x big_bn tile, [r, M) on 128x128; 0: no split
+    const PpGemmDesc& d = v.d;
+    if (!((v.asplit || v.fvec) && d.conv_kh == 0 && d.shuffle_r == 0 && d.ks_rows == 0 && d.grp_rows == 0 && v.z == 1)) return 0;
+    const long long gx = (d.N + big_bn - 1) / big_bn, gy = (d.M + 255) / 256, tiles = gx * gy, full = tiles / cus;
+    if (full < 1 || tiles % cus == 0) return 0;
+    const long long r = full * cus / gx * 256;
+    return (r > 0 && r < d.M && d.M - r >= 128) ? (int)r : 0;
+}
+
+// What one pp_gemm call launches.  Its cfg, amode and engine are the launch record's fields (bench.py gemm_per_kernel decodes them).
+enum { GE_U, GE_UH, GE_F, GE_FLY, GE_R1 };   // pp_gemm_u_kernel, pp_gemm_uh_kernel, pp_gemm_f_kernel, gemm_f16x3_kernel, gemm_kernel
+struct GemmPlan {
+    int engine;      // GE_*
+    int cfg;         // the configuration that runs, canonical (PP_GEMM_FORCE_CFG numbering; a tail split: its big tile)
+    int tile;        // PP_U_* block tile of the pre-split / fp32 engine
+    int amode;       // MODE of pp_gemm_u_kernel (1: pp_gemm_uh_kernel), 16 + MODE of pp_gemm_f_kernel, others 8 + vec + 2 (on the fly)
+    bool vec;        // pre-split: the vector epilogue; gemm_kernel: 16-byte loads
+    int tail_rows;   // > 0: rows [0, tail_rows) on `tile`, the rest as a second launch on 128x128 tiles
+};
+
+// Tile configurations ("cfg", PP_GEMM_FORCE_CFG numbering): the one place a requested configuration becomes a kernel and a tile.
+// Both operands pre-split (pp_gemm_u_kernel.h): 0 = 128x128 tile, two workgroups per CU; 2 = 128x64, two per CU; 4 = 256x128 (3,
+// the former one-shot launch of it, is an alias); 5 = 256x256; 6 = 256x256 with row-shared A delivery (3x3 convolutions); 7 / 8 (the
+// former two / three-workgroups-per-CU K-16 kernels) are aliases of 0.  All of them persistent (a launch with fewer tiles than slots
+// is one tile per workgroup) and bit-identical in their results.  fp32 operands (split on the fly, or fp32 MFMA): 0 / 1 = 128x128 at
+// 2 / 3 workgroups per CU, 2 = 128x64.  fp32 operands on aligned shapes: the fp32 engine (pp_gemm_f.hip; configurations 3 = 128x128,
+// 4 = 256x128, 5 = 256x256, 6 = 128x64, 7 = 256x192 — every one of them accumulates in the same order).  The round-1 gemm_kernel
+// keeps batched products, B [K][N], unaligned rows.  9 / 10: the tail split (tail_rows) of 5 / 4.
+static GemmPlan gemm_plan(const GemmView& v, int cfg, int cus) {
+    const PpGemmDesc& d = v.d;
+    GemmPlan p{};
+    if (cfg == 9 || cfg == 10) {
+        p.tail_rows = cfg == 10 || d.N > 128 ? tail_rows(v, cfg == 9 ? 256 : 128, cus) : 0;
+        cfg = cfg == 9 ? 5 : 4;
+    }
+    if (v.asplit) {
+        cfg = cfg == 3 ? 4 : (cfg == 1 || cfg == 7 || cfg == 8) ? 0 : cfg;   // aliases
+        if (cfg == 6 && !(v.h_shape && d.N > 128)) cfg = 5;
         if (cfg == 5 && d.N <= 128) cfg = 4;
-        return cfg;
+        if (!v.u_vec && cfg != 2) cfg = 0;   // the element-wise epilogue exists for the two 128-row tiles
+        p.engine = cfg == 6 ? GE_UH : GE_U;
+        p.tile = cfg == 5 ? PP_U_256x256 : cfg == 4 ? PP_U_256x128 : cfg == 2 ? PP_U_128x64 : PP_U_128x128;
+        p.amode = cfg == 6 ? 1 : pp_gemm_u_mode(d, v.terms);
+        p.vec = v.u_vec;
+    } else if (v.fvec && (cfg >= 3 || d.grp_rows != 0)) {
+        if (cfg < 3) cfg = 3;   // a grouped batch exists on the engine only (the round-1 kernel would read group 0's weights for every row)
+        const int mode = pp_gemm_f_mode(d);
+        if (mode == 2 && (cfg == 5 || cfg == 7)) cfg = 4;   // (natural-order convolutions: the 256x128 tile, pp_f_launch_tile)
+        p.engine = GE_F;
+        p.tile = cfg == 7 ? PP_F_256x192 : cfg == 5 ? PP_U_256x256 : cfg == 4 ? PP_U_256x128 : cfg == 3 ? PP_U_128x128 : PP_U_128x64;
+        p.amode = 16 + mode;
+    } else {
+        p.engine = v.split ? GE_FLY : GE_R1;
+        p.amode = 8 + (v.vec ? 1 : 0) + (v.split ? 2 : 0);
+        p.vec = v.vec;
+    }
+    p.cfg = cfg;
+    return p;
+}
+
+// gemm_f16x3_kernel / gemm_kernel: 2 = the 128x64 tile, 0 / otherwise 128x128 at 2 / 3 workgroups per CU (2 without vector loads)
+static int gemm_r1_launch(const GemmPlan& p, const PpGemmDesc& d, long long z, hipStream_t st) {
+    const bool narrow = p.cfg == 2, occ2 = p.cfg == 0;
+    void (*k)(PpGemmDesc);
+    if (p.engine == GE_FLY && d.B_hl) k = narrow ? gemm_f16x3_kernel<1, 4, true> : occ2 ? gemm_f16x3_kernel<2, 2, true> : gemm_f16x3_kernel<2, 3, true>;
+    else if (p.engine == GE_FLY) k = narrow ? gemm_f16x3_kernel<1, 4, false> : occ2 ? gemm_f16x3_kernel<2, 2, false> : gemm_f16x3_kernel<2, 3, false>;
+    else if (!p.vec) k = narrow ? gemm_kernel<false, 1, 2> : gemm_kernel<false, 2, 2>;   // scalar loads (Cin % 4 != 0: 7x7 / 1x1 / patch embed)
+    else k = narrow ? gemm_kernel<true, 1, 4> : occ2 ? gemm_kernel<true, 2, 2> : gemm_kernel<true, 2, 3>;
+    const dim3 grid((d.N + (narrow ? 63 : 127)) / (narrow ? 64 : 128), (unsigned)((d.M + BM - 1) / BM), (unsigned)z);
+    void* args[] = {(void*)&d};
+    (void)hipLaunchKernel((const void*)k, grid, dim3(256), args, 0, st);
+    return PP_OK;
+}
+
+// The plan's launches (a tail split: the head on the plan's tile, then the tail on 128x128); PP_OK or the first error
+static int gemm_launch(const GemmPlan& p, const GemmView& v, int cus, hipStream_t st) {
+    auto one = [&](const PpGemmDesc& d, int tile) {
+        switch (p.engine) {
+            case GE_U: return (v.terms == 2 ? pp_gemm_u_launch_t2 : pp_gemm_u_launch_t1)(d, tile, p.amode, p.vec, cus, st);
+            case GE_UH: return pp_gemm_uh_launch(d, v.terms, cus, st);
+            case GE_F: return pp_gemm_f_launch(d, tile, p.amode - 16, cus, st);
+            default: return gemm_r1_launch(p, d, v.z, st);
+        }
     };
-    int launch_rc = PP_OK;
-    // TAIL SPLIT (round 6; configurations 9 = 256x256 + tail, 10 = 256x128 + tail).  A persistent launch of T tiles on S slots takes
-    // ceil(T / S) rounds; the ViT linears at M = 49 344 leave the last round of 256-row tiles 5-50 % filled (fc1: 9.05 rounds -> 10,
-    // proj / fc2: 2.26 -> 3).  The rows of the full rounds run on the big tile, the remaining rows as a second launch on 128x128 tiles
-    // (two workgroups per CU: a short round of quarter-size tiles).  Dense launches only (a row's address is base + m * pitch: the tail is the
-    // same descriptor with shifted pointers); every tile configuration accumulates in the same order, so the split leaves no trace in the bits.
-    const bool split_ok = (asplit || fvec) && d.conv_kh == 0 && d.shuffle_r == 0 && d.ks_rows == 0 && d.grp_rows == 0 && z == 1;
-    auto tail_rows = [&](int big_bm, int big_bn) -> int {   // rows [0, r) on the big tile (whole rounds), [r, M) on the small one; 0: no split
-        if (!split_ok) return 0;
-        const long long gx_ = (d.N + big_bn - 1) / big_bn, gy_ = (d.M + big_bm - 1) / big_bm, tiles_ = gx_ * gy_, full_ = tiles_ / cus;
-        if (full_ < 1 || tiles_ % cus == 0) return 0;
-        const long long r_ = full_ * cus / gx_ * big_bm;
-        return (r_ > 0 && r_ < d.M && d.M - r_ >= 128) ? (int)r_ : 0;
-    };
-    auto shifted = [&](const PpGemmDesc& src, int r0, int rows_) {   // rows [r0, r0 + rows_) of a dense launch as a launch of its own
-        PpGemmDesc t = src;
-        t.M = rows_;
-        const size_t eb_ = f16 ? 2 : 4;
-        if (t.A_hl) t.A_hl = (const char*)src.A_hl + (size_t)r0 * src.lda * eb_;
-        if (t.A) t.A = src.A + (size_t)r0 * src.lda;
-        if (t.C) t.C = src.C + (size_t)r0 * src.ldc;
-        if (t.C_hl) t.C_hl = (char*)src.C_hl + (size_t)r0 * src.ldc_h * eb_;
-        if (t.residual) t.residual = src.residual + (size_t)r0 * src.ldc;
-        if (t.residual2) t.residual2 = src.residual2 + (size_t)r0 * src.ldc;
-        if (asplit) t.a_hl_bytes = ((long long)(rows_ - 1) * src.lda + src.K) * (long long)eb_;
-        else if (fvec) (void)pp_gemm_f_ok(t);      // (recomputes the operand extents of the fp32 engine)
+    if (p.tail_rows == 0) return one(v.d, p.tile);
+    auto rows = [&](int r0, int m) {   // rows [r0, r0 + m) of the dense launch as a launch of its own
+        PpGemmDesc t = v.d;
+        t.M = m;
+        const size_t eb = v.terms == 1 ? 2 : 4;
+        if (t.A_hl) t.A_hl = (const char*)t.A_hl + (size_t)r0 * t.lda * eb;
+        if (t.A) t.A += (size_t)r0 * t.lda;
+        if (t.C) t.C += (size_t)r0 * t.ldc;
+        if (t.C_hl) t.C_hl = (char*)t.C_hl + (size_t)r0 * t.ldc_h * eb;
+        if (t.residual) t.residual += (size_t)r0 * t.ldc;
+        if (t.residual2) t.residual2 += (size_t)r0 * t.ldc;
+        pp_gemm_extents(t, (int)eb, t.a_hl_bytes, t.b_hl_bytes);
         return t;
     };
-    const PpGemmDesc* cur = &d;     // the descriptor `launch` works on
-    auto launch1 = [&](int cfg) {
-        const PpGemmDesc& d = *cur;
-        if (asplit) {
-            cfg = u_cfg(cfg);
-            if (cfg == 6) launch_rc = pp_gemm_uh_launch(d, terms, cus, st);
-            else launch_rc = pp_gemm_u_launch(d, cfg == 5 ? PP_U_256x256 : cfg == 4 ? PP_U_256x128 : cfg == 2 ? PP_U_128x64 : PP_U_128x128, terms, cus, st);
-            return;
+    const int rc = one(rows(0, p.tail_rows), p.tile);
+    return rc != PP_OK ? rc : one(rows(p.tail_rows, v.d.M - p.tail_rows), PP_U_128x128);
+}
+
+// The configurations the autotuner times for a launch view, in the order it times them, into c[]; returns their count (<= 12).
+static int tune_candidates(const GemmView& v, int cus, int* c) {
+    static const int tail_env = [] { const char* e = getenv("PP_GEMM_TAIL_SPLIT"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
+    const PpGemmDesc& d = v.d;
+    // tail-split candidates: pre-split engine opt-in (PP_GEMM_TAIL_SPLIT=1: measured neutral on the f16x3 step), fp32 engine on unless
+    // PP_GEMM_TAIL_SPLIT=0 (fc1 at M = 49 344: 7.18 -> 7.06 ms per burst; exact-mode step +0.5 %) — profiles/r06/README.md
+    const bool tail_on = tail_env == 1, tail_on_f = tail_env != 0;
+    const long long t4 = (long long)((d.M + 255) / 256) * ((d.N + 127) / 128), t5 = (long long)((d.M + 255) / 256) * ((d.N + 255) / 256);
+    int n = 0;
+    if (v.asplit) {
+        // the 128-row tiles always; the 256-row ones for problems that give at least half the chip a tile of theirs
+        c[n++] = 0;
+        c[n++] = 2;
+        if (t4 >= cus / 2) c[n++] = 4;
+        if (t5 >= cus / 2 && d.N > 128) c[n++] = 5;
+        if (t5 >= cus / 2 && d.N > 128 && v.h_shape) c[n++] = 6;
+        if (tail_on && d.N > 128 && tail_rows(v, 256, cus)) c[n++] = 9;
+        if (tail_on && tail_rows(v, 128, cus)) c[n++] = 10;
+    } else if (v.fvec) {
+        c[n++] = 6;
+        if (d.N > 64) c[n++] = 3;
+        if (t4 >= cus / 2 && d.N > 64) c[n++] = 4;
+        if (t5 >= cus / 2 && d.N > 128) c[n++] = 5;
+        // 256x192: layers whose N wastes less of a 192-wide tile than of a 128-wide one (the decoder's 192-channel maps)
+        if ((d.N + 191) / 192 * 192 - d.N < (d.N + 127) / 128 * 128 - d.N && (long long)((d.M + 255) / 256) * ((d.N + 191) / 192) >= cus / 2) c[n++] = 7;
+        if (tail_on_f && d.N > 128 && tail_rows(v, 256, cus)) c[n++] = 9;
+        if (tail_on_f && d.N > 64 && tail_rows(v, 128, cus)) c[n++] = 10;
+    } else {
+        for (int i = 0; i < (v.vec ? 3 : 2); ++i) c[n++] = v.vec ? i : (i == 0 ? 0 : 2);
+    }
+    return n;
+}
+
+// The fastest of the candidates on this call's own launch (timed launches of the same GEMM — idempotent unless the output aliases a
+// residual, which the caller excludes).  Round-robin: every round times one burst of four back-to-back launches of EACH candidate, and a
+// candidate keeps its best burst.  (Timing the candidates one after the other ranked them by the clock the chip happened to hold: the
+// first ones ran on a cool chip, and configurations within ~5-10 % changed places from run to run.)  The winner goes into the table
+// under `key` and is launched once more, so that the call leaves its result; a call that tunes records nothing.
+static int gemm_tune(const GemmView& v, const char* key, int cus, hipStream_t st) {
+    static const bool dbg = getenv("PP_GEMM_DEBUG") != nullptr;
+    hipEvent_t e0, e1;
+    PP_CHECK_HIP(hipEventCreate(&e0));
+    PP_CHECK_HIP(hipEventCreate(&e1));
+    int cands[12];
+    const int nc = tune_candidates(v, cus, cands);
+    GemmPlan plans[12];
+    float ms[12];
+    for (int i = 0; i < nc; ++i) {
+        plans[i] = gemm_plan(v, cands[i], cus);
+        ms[i] = 1e30f;
+        (void)gemm_launch(plans[i], v, cus, st);  // warm
+    }
+    for (int rep = 0; rep < 4; ++rep)
+        for (int i = 0; i < nc; ++i) {
+            (void)hipEventRecord(e0, st);
+            for (int k = 0; k < 4; ++k) (void)gemm_launch(plans[i], v, cus, st);
+            (void)hipEventRecord(e1, st);
+            (void)hipEventSynchronize(e1);
+            float t = 0.f;
+            (void)hipEventElapsedTime(&t, e0, e1);
+            ms[i] = t < ms[i] ? t : ms[i];
         }
-        if (fvec && cfg < 3 && d.grp_rows != 0) cfg = 3;   // a grouped batch exists on the engine only (the round-1 kernel would read group 0's weights for every row)
-        if (fvec && cfg >= 3) {
-            launch_rc = pp_gemm_f_launch(d, cfg == 7 ? PP_F_256x192 : cfg == 5 ? PP_U_256x256 : cfg == 4 ? PP_U_256x128 : cfg == 3 ? PP_U_128x128 : PP_U_128x64, cus, st);
-            return;
-        }
-        const bool narrow = cfg == 2;
-        const dim3 grid((d.N + (narrow ? 63 : 127)) / (narrow ? 64 : 128), (unsigned)rows, (unsigned)z);
-        if (split) {
-            if (d.B_hl) {
-                if (narrow) hipLaunchKernelGGL((gemm_f16x3_kernel<1, 4, true>), grid, dim3(256), 0, st, d);
-                else if (cfg == 0) hipLaunchKernelGGL((gemm_f16x3_kernel<2, 2, true>), grid, dim3(256), 0, st, d);
-                else hipLaunchKernelGGL((gemm_f16x3_kernel<2, 3, true>), grid, dim3(256), 0, st, d);
-            } else {
-                if (narrow) hipLaunchKernelGGL((gemm_f16x3_kernel<1, 4, false>), grid, dim3(256), 0, st, d);
-                else if (cfg == 0) hipLaunchKernelGGL((gemm_f16x3_kernel<2, 2, false>), grid, dim3(256), 0, st, d);
-                else hipLaunchKernelGGL((gemm_f16x3_kernel<2, 3, false>), grid, dim3(256), 0, st, d);
-            }
-        } else if (!vec) {  // scalar-load path (Cin not a multiple of 4: the small 7x7 / 1x1 / patch-embed layers)
-            if (narrow) hipLaunchKernelGGL((gemm_kernel<false, 1, 2>), grid, dim3(256), 0, st, d);
-            else hipLaunchKernelGGL((gemm_kernel<false, 2, 2>), grid, dim3(256), 0, st, d);
-        } else if (narrow) {
-            hipLaunchKernelGGL((gemm_kernel<true, 1, 4>), grid, dim3(256), 0, st, d);
-        } else if (cfg == 0) {
-            hipLaunchKernelGGL((gemm_kernel<true, 2, 2>), grid, dim3(256), 0, st, d);
-        } else {
-            hipLaunchKernelGGL((gemm_kernel<true, 2, 3>), grid, dim3(256), 0, st, d);
-        }
-    };
-    auto launch = [&](int cfg) {
-        if (cfg == 9 || cfg == 10) {
-            const int big = cfg == 9 ? 5 : 4, r0 = tail_rows(256, cfg == 9 ? 256 : 128);
-            if (r0 == 0 || (big == 5 && d.N <= 128)) {
-                launch1(big);
-                return;
-            }
-            const PpGemmDesc head = shifted(d, 0, r0), tail = shifted(d, r0, d.M - r0);
-            cur = &head;
-            launch1(big);
-            if (launch_rc == PP_OK) {
-                cur = &tail;
-                launch1(asplit ? 0 : 3);        // 128x128, two workgroups per CU (pre-split engine: 0, fp32 engine: 3)
-            }
-            cur = &d;
-            return;
-        }
-        launch1(cfg);
-    };
-    auto finish = [&]() { return launch_rc != PP_OK ? launch_rc : pp_last_launch(); };
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    int best = 0;
+    for (int i = 0; i < nc; ++i) {
+        if (dbg) fprintf(stderr, "[pp_gemm] autotune %s cfg %d: %.4f ms\n", key, cands[i], ms[i]);
+        if (ms[i] < ms[best]) best = i;
+    }
+    g_tune_best[key] = cands[best];
+    const int rc = gemm_launch(plans[best], v, cus, st);
+    return rc != PP_OK ? rc : pp_last_launch();
+}
+
+extern "C" {
+
+int pp_gemm_generic_epilogue(int on) {
+    if (on != 0 && on != 1) return PP_EINVAL;
+    return g_epi_generic.exchange(on);
+}
+
+int pp_gemm(const PpGemmDesc* desc, void* stream) {
+    GemmView v;
+    if (const int rc = gemm_normalise(desc, v); rc != PP_OK) return rc;
+    const PpGemmDesc& d = v.d;
+    hipStream_t st = (hipStream_t)stream;
+    const int cus = pp_cu_count();   // cached per device (two runtime calls per GEMM launch otherwise)
     // Which block tile / occupancy is fastest depends on how the tile count fills the CUs (wave quantisation)
-    // and on K; it is measured once per problem shape (timed launches of the same GEMM — idempotent
-    // unless the output aliases a residual) and remembered.  PP_GEMM_AUTOTUNE=0 keeps the static choice.
-    int cfg = fvec ? (d.N <= 64 ? 6 : 3) : (d.N <= 64 ? 2 : 0);
+    // and on K; it is measured once per problem shape (gemm_tune) and remembered.  PP_GEMM_AUTOTUNE=0 keeps the static choice.
+    int cfg = v.fvec ? (d.N <= 64 ? 6 : 3) : (d.N <= 64 ? 2 : 0);
     bool pinned = false;
     if (const char* f = getenv("PP_GEMM_FORCE_CFG")) {  // tests: pin one kernel configuration (recorded like any other launch)
         const int fc = atoi(f);
-        if (((fc == 9 || fc == 10) && (asplit || fvec)) || (fc >= 0 && fc <= 8 && (asplit || fc <= 2 || (fvec && fc <= 7)))) {
+        if (((fc == 9 || fc == 10) && (v.asplit || v.fvec)) || (fc >= 0 && fc <= 8 && (v.asplit || fc <= 2 || (v.fvec && fc <= 7)))) {
             cfg = fc;
             pinned = true;
         }
     }
     const bool alias = d.C != nullptr && (d.residual == d.C || d.residual2 == d.C);  // (C is null for operand-only outputs)
     static const bool tune = [] { const char* e = getenv("PP_GEMM_AUTOTUNE"); return !(e && e[0] == '0'); }();
-    if (!pinned && tune && !alias && (d.N > 64 || fvec)) {
-        std::mutex& mu = g_tune_mu;
-        std::unordered_map<std::string, int>& best = g_tune_best;
-        static const bool env_loaded = [] {
+    if (!pinned && tune && !alias && (d.N > 64 || v.fvec)) {
+        [[maybe_unused]] static const bool env_loaded = [] {
             if (const char* p = getenv("PP_GEMM_TUNE_FILE")) {
                 std::lock_guard<std::mutex> lock(g_tune_mu);
                 (void)tune_load_locked(p);
             }
             return true;
         }();
-        (void)env_loaded;
         char key[160];
-        snprintf(key, sizeof key, "%d.%d.%d.%d.%d.%lld.%d.%d.%d.%d.%d.%d", d.M, d.N, d.K, (int)vec, d.b_kn, z, d.conv_kh,
-                 d.conv_cin, d.conv_stride, d.conv_h, d.shuffle_r, (int)split + 2 * (d.B_hl != nullptr) + 4 * (int)asplit + 8 * (int)f16 + 16 * (int)fvec);
-        std::lock_guard<std::mutex> lock(mu);
-        auto it = best.find(key);
-        if (it == best.end()) {
-            hipEvent_t e0, e1;
-            PP_CHECK_HIP(hipEventCreate(&e0));
-            PP_CHECK_HIP(hipEventCreate(&e1));
-            float bt = 1e30f;
-            int bc = 0;
-            int cands[12], nc = 0;
-            // tail-split candidates: pre-split engine opt-in (PP_GEMM_TAIL_SPLIT=1: measured neutral on the f16x3 step), fp32 engine on unless
-            // PP_GEMM_TAIL_SPLIT=0 (fc1 at M = 49 344: 7.18 -> 7.06 ms per burst; exact-mode step +0.5 %) — profiles/r06/README.md
-            static const int tail_env = [] { const char* e = getenv("PP_GEMM_TAIL_SPLIT"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
-            const bool tail_on = tail_env == 1, tail_on_f = tail_env != 0;
-            if (asplit) {
-                // the 128-row tiles always; the 256-row ones for problems that give at least half the chip a tile of theirs
-                const long long t4 = (long long)((d.M + 255) / 256) * ((d.N + 127) / 128), t5 = (long long)((d.M + 255) / 256) * ((d.N + 255) / 256);
-                cands[nc++] = 0;
-                cands[nc++] = 2;
-                if (t4 >= cus / 2) cands[nc++] = 4;
-                if (t5 >= cus / 2 && d.N > 128) cands[nc++] = 5;
-                if (t5 >= cus / 2 && d.N > 128 && h_shape) cands[nc++] = 6;
-                if (tail_on && d.N > 128 && tail_rows(256, 256)) cands[nc++] = 9;
-                if (tail_on && tail_rows(256, 128)) cands[nc++] = 10;
-            } else if (fvec) {
-                const long long t4 = (long long)((d.M + 255) / 256) * ((d.N + 127) / 128), t5 = (long long)((d.M + 255) / 256) * ((d.N + 255) / 256);
-                cands[nc++] = 6;
-                if (d.N > 64) cands[nc++] = 3;
-                if (t4 >= cus / 2 && d.N > 64) cands[nc++] = 4;
-                if (t5 >= cus / 2 && d.N > 128) cands[nc++] = 5;
-                // 256x192: layers whose N wastes less of a 192-wide tile than of a 128-wide one (the decoder's 192-channel maps)
-                if ((d.N + 191) / 192 * 192 - d.N < (d.N + 127) / 128 * 128 - d.N && (long long)((d.M + 255) / 256) * ((d.N + 191) / 192) >= cus / 2) cands[nc++] = 7;
-                if (tail_on_f && d.N > 128 && tail_rows(256, 256)) cands[nc++] = 9;
-                if (tail_on_f && d.N > 64 && tail_rows(256, 128)) cands[nc++] = 10;
-            } else {
-                for (int c = 0; c < (vec ? 3 : 2); ++c) cands[nc++] = vec ? c : (c == 0 ? 0 : 2);
-            }
-            // Round-robin: every round times one burst of four back-to-back launches of EACH candidate, and a candidate keeps
-            // its best burst.  (Timing the candidates one after the other ranked them by the clock the chip happened to hold:
-            // the first ones ran on a cool chip, and configurations within ~5-10 % changed places from run to run.)
-            float ms[12];
-            for (int i = 0; i < nc; ++i) {
-                ms[i] = 1e30f;
-                launch(cands[i]);  // warm
-            }
-            for (int rep = 0; rep < 4; ++rep)
-                for (int i = 0; i < nc; ++i) {
-                    (void)hipEventRecord(e0, st);
-                    for (int k = 0; k < 4; ++k) launch(cands[i]);
-                    (void)hipEventRecord(e1, st);
-                    (void)hipEventSynchronize(e1);
-                    float t = 0.f;
-                    (void)hipEventElapsedTime(&t, e0, e1);
-                    ms[i] = t < ms[i] ? t : ms[i];
-                }
-            for (int i = 0; i < nc; ++i) {
-                if (dbg) fprintf(stderr, "[pp_gemm] autotune %s cfg %d: %.4f ms\n", key, cands[i], ms[i]);
-                if (ms[i] < bt) {
-                    bt = ms[i];
-                    bc = cands[i];
-                }
-            }
-            (void)hipEventDestroy(e0);
-            (void)hipEventDestroy(e1);
-            best[key] = bc;
-            // the result this call leaves is the CHOSEN configuration's, launched once more behind the timing bursts — not whatever candidate
-            // happened to be timed last (PP_GEMM_TUNE_KEEP_LAST=1: the former behaviour, for the study in tools/study_grad_cfg.py)
-            static const bool keep_last = [] { const char* e = getenv("PP_GEMM_TUNE_KEEP_LAST"); return e && e[0] == '1'; }();
-            if (!keep_last) launch(bc);
-            return finish();
-        }
+        snprintf(key, sizeof key, "%d.%d.%d.%d.%d.%lld.%d.%d.%d.%d.%d.%d", d.M, d.N, d.K, (int)v.vec, d.b_kn, v.z, d.conv_kh,
+                 d.conv_cin, d.conv_stride, d.conv_h, d.shuffle_r,
+                 (int)v.split + 2 * (d.B_hl != nullptr) + 4 * (int)v.asplit + 8 * (int)(v.terms == 1) + 16 * (int)v.fvec);
+        std::lock_guard<std::mutex> lock(g_tune_mu);
+        auto it = g_tune_best.find(key);
+        if (it == g_tune_best.end()) return gemm_tune(v, key, cus, st);
         cfg = it->second;
     }
+    const GemmPlan p = gemm_plan(v, cfg, cus);
     PpGemmProf* gp = pp_gemm_prof_state();
     const bool rec = gp->capacity > 0 && gp->count < gp->capacity;
     if (rec) (void)hipEventRecord(gp->ev[2 * gp->count], st);
-    launch(cfg);
+    const int rc = gemm_launch(p, v, cus, st);
     if (rec) {
         (void)hipEventRecord(gp->ev[2 * gp->count + 1], st);
-        gp->flops[gp->count] = 2.0 * d.M * d.N * d.K * (double)z;
-        {   // algorithmic bytes: every operand and result element once, in the format this launch reads / writes it
-            const double ea = asplit ? eb : 4.0, ew = (asplit || d.B_hl) ? eb : 4.0;
-            const long long per = (long long)d.conv_ho * d.conv_wo;
-            const double a_el = d.conv_kh != 0 ? (double)((d.M + per - 1) / per) * d.conv_h * d.conv_w * d.conv_cin   // the image, not its im2col
-                                               : (double)d.M * d.K;
-            const double mn = (double)d.M * d.N;
-            gp->bytes[gp->count] = (double)z * (a_el * ea + (double)d.N * d.K * ew * (d.grp_rows ? d.M / d.grp_rows : 1) + (d.C ? mn * 4.0 : 0.0) + (d.C_hl ? mn * eb : 0.0) +
-                                               (d.residual ? mn * 4.0 : 0.0) + (d.residual2 ? mn * 4.0 : 0.0));
-        }
-        gp->kind[gp->count] = asplit ? 0 : 1;   // (pp_prof_gemm_collect: two classes; the fp32 engine is told apart by its mode field, 16 + MODE)
-        gp->shape[gp->count][0] = d.M;
-        gp->shape[gp->count][1] = d.N;
-        gp->shape[gp->count][2] = d.K;
-        gp->shape[gp->count][3] = d.conv_kh;
-        const int cfg_ = cfg;
-        cfg = cfg == 9 ? 5 : cfg == 10 ? 4 : cfg;     // (a tail split is recorded under its big tile; the tail's share of the time rides along)
-        if (fvec && cfg < 3 && d.grp_rows != 0) cfg = 3;   // (launch1: a grouped batch runs on the engine's 128x128 tile)
-        gp->shape[gp->count][4] = asplit ? ((!pp_gemm_u_vec_ok(d) && u_cfg(cfg) != 2) ? 0 : u_cfg(cfg)) : cfg;   // (element-wise epilogue: the small tiles)
-        // pre-split kernels: the A-delivery mode; the others: 8 + (vector loads) + 2 (f16x3 on the fly) — bench.py names the instantiation
-        gp->shape[gp->count][5] = asplit ? (u_cfg(cfg) == 6 ? 1 : pp_gemm_u_mode(d, terms))
-                                         : (fvec && cfg >= 3 ? 16 + pp_gemm_f_mode(d) : 8 + (vec ? 1 : 0) + (split ? 2 : 0));
+        gp->flops[gp->count] = 2.0 * d.M * d.N * d.K * (double)v.z;
+        // algorithmic bytes: every operand and result element once, in the format this launch reads / writes it
+        const double eb = 2.0 * v.terms, ea = v.asplit ? eb : 4.0, ew = (v.asplit || d.B_hl) ? eb : 4.0;
+        const long long per = (long long)d.conv_ho * d.conv_wo;
+        const double a_el = d.conv_kh != 0 ? (double)((d.M + per - 1) / per) * d.conv_h * d.conv_w * d.conv_cin   // the image, not its im2col
+                                           : (double)d.M * d.K;
+        const double mn = (double)d.M * d.N;
+        gp->bytes[gp->count] = (double)v.z * (a_el * ea + (double)d.N * d.K * ew * (d.grp_rows ? d.M / d.grp_rows : 1) + (d.C ? mn * 4.0 : 0.0) +
+                                              (d.C_hl ? mn * eb : 0.0) + (d.residual ? mn * 4.0 : 0.0) + (d.residual2 ? mn * 4.0 : 0.0));
+        // (pp_prof_gemm_collect: two classes; the fp32 engine is told apart by its mode field, 16 + MODE)
+        gp->kind[gp->count] = p.engine == GE_U || p.engine == GE_UH ? 0 : 1;
+        // (a tail split is recorded under its big tile; the tail's share of the time rides along)
+        int* sh = gp->shape[gp->count];
+        sh[0] = d.M, sh[1] = d.N, sh[2] = d.K, sh[3] = d.conv_kh, sh[4] = p.cfg, sh[5] = p.amode;
         gp->count++;
-        cfg = cfg_;
     }
-    return finish();
+    return rc != PP_OK ? rc : pp_last_launch();
 }
 
 int pp_gemm_tune_save(const char* path) {

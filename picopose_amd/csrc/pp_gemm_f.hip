@@ -628,7 +628,7 @@ static int pp_f_launch_tile(const PpGemmDesc& d, int mode, int slots, hipStream_
     if (mode == 0) return pp_f_launch_one<T, 0>(d, slots, st);
     if (mode == 1) return pp_f_launch_one<T, 1>(d, slots, st);
     // (natural-order convolutions — odd channel counts, small layers — carry per-lane tap state: no 256x256 instantiation)
-    if constexpr (T::BM == 256 && T::BN == 256) return pp_f_launch_one<F256x128, 2>(d, slots, st);
+    if constexpr (T::BM == 256 && T::BN == 256) return PP_EINVAL;
     else return pp_f_launch_one<T, 2>(d, slots, st);
 }
 
@@ -639,35 +639,29 @@ int pp_gemm_f_mode(const PpGemmDesc& d) {
 
 // The fp32 engine takes a launch when: one problem (no batch), B [N][K], 16-byte aligned operands with rows of a multiple of 4
 // elements, K % 4 == 0 (a lane's 16-byte chunk is inside K or past it as a whole), fp32 output only, and every buffer within the
-// 32-bit byte offsets of the buffer instructions.  Fills a_hl_bytes / b_hl_bytes (the operand extents) on success.
-bool pp_gemm_f_ok(PpGemmDesc& d) {
+// 32-bit byte offsets of the buffer instructions.
+bool pp_gemm_f_ok(const PpGemmDesc& d) {
     if (!d.A || !d.B || !d.C || d.A_hl || d.C_hl || d.b_kn || d.batch0 * d.batch1 != 1 || d.ksplit > 1) return false;
     if (d.act == PP_ACT_TANH || (d.shuffle_r != 0 && d.act == PP_ACT_GELU)) return false;   // (epilogue variants this engine does not carry)
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     if (!al16(d.A) || !al16(d.B) || d.lda % 4 != 0 || d.ldb % 4 != 0 || d.K % 4 != 0) return false;
     if (d.conv_kh != 0 && (d.conv_cin % 4 != 0 || d.conv_bstride % 4 != 0)) return false;
-    const long long per = (long long)d.conv_ho * d.conv_wo;
-    const long long a_elems = d.conv_kh != 0 ? ((d.M + per - 1) / per - 1) * d.conv_bstride + (long long)d.conv_h * d.conv_w * d.lda
-                                             : (long long)(d.M - 1) * d.lda + d.K;
-    const long long b_elems = (long long)(d.N - 1) * d.ldb + d.K;
+    long long a_bytes, b_bytes;
+    pp_gemm_extents(d, 4, a_bytes, b_bytes);
     const long long abias = d.conv_kh != 0 ? ((long long)d.conv_pad * d.conv_w + d.conv_pad) * d.lda : 0;
-    if ((a_elems + abias) * 4 >= 0xFFFFFF00LL || b_elems * 4 >= 0xFFFFFF00LL) return false;
+    if (a_bytes + abias * 4 >= 0xFFFFFF00LL || b_bytes >= 0xFFFFFF00LL) return false;
     const int r2 = d.shuffle_r > 0 ? d.shuffle_r * d.shuffle_r : 1;
     const long long out_rows = (long long)d.M * r2, out_cols = d.N / r2;
-    if ((out_rows - 1) * d.ldc * 4 + out_cols * 4 >= 0xFFFFFF00LL) return false;
-    d.a_hl_bytes = a_elems * 4;
-    d.b_hl_bytes = b_elems * 4;
-    return true;
+    return (out_rows - 1) * d.ldc * 4 + out_cols * 4 < 0xFFFFFF00LL;
 }
 
-int pp_gemm_f_launch(const PpGemmDesc& d, int tile, int cus, hipStream_t st) {
-    const int mode = pp_gemm_f_mode(d);
+int pp_gemm_f_launch(const PpGemmDesc& d, int tile, int mode, int cus, hipStream_t st) {
     switch (tile) {
         case PP_U_256x256: return pp_f_launch_tile<F256x256>(d, mode, cus, st);
         case PP_U_256x128: return pp_f_launch_tile<F256x128>(d, mode, cus, st);
         case PP_U_128x128: return pp_f_launch_tile<F128x128>(d, mode, 2 * cus, st);
         case PP_U_128x64: return pp_f_launch_tile<F128x64>(d, mode, 2 * cus, st);
-        case PP_F_256x192: return mode == 2 ? pp_f_launch_tile<F256x128>(d, mode, cus, st) : pp_f_launch_tile<F256x192>(d, mode, cus, st);
+        case PP_F_256x192: return pp_f_launch_tile<F256x192>(d, mode, cus, st);
         default: return PP_EINVAL;
     }
 }

@@ -1029,7 +1029,8 @@ template <int TERMS>
 static int pp_u_launch_terms(const PpGemmDesc& d, int tile, int mode, bool vec, int cus, hipStream_t st) {
     if (!vec) {
         if (tile == PP_U_128x64) return pp_u_launch_tile<T128x64, TERMS, false>(d, mode, 2 * cus, st);
-        return pp_u_launch_tile<T128x128, TERMS, false>(d, mode, 2 * cus, st);
+        if (tile == PP_U_128x128) return pp_u_launch_tile<T128x128, TERMS, false>(d, mode, 2 * cus, st);
+        return PP_EINVAL;
     }
     switch (tile) {
         case PP_U_256x256: return pp_u_launch_tile<T256x256, TERMS, true>(d, mode, cus, st);

@@ -1,22 +1,10 @@
 // Row-shared 3x3 convolution kernel (both operand formats) and the host-side entry points of the unified pre-split kernels.
 #include "pp_gemm_u_kernel.h"
 
-int pp_gemm_u_launch_t1(const PpGemmDesc& d, int tile, int mode, bool vec, int cus, hipStream_t st);
-int pp_gemm_u_launch_t2(const PpGemmDesc& d, int tile, int mode, bool vec, int cus, hipStream_t st);
-
 int pp_gemm_u_mode(const PpGemmDesc& d, int terms) {
     const int kt = 64 / terms;
     if (d.conv_kh == 0) return d.ks_rows > 0 ? 3 : 0;
     return (d.conv_cin % kt == 0 && d.conv_kh * d.conv_kw <= 32) ? 1 : 2;
-}
-
-void pp_gemm_u_tile_shape(int tile, int& bm, int& bn, int& per_cu) {
-    switch (tile) {
-        case PP_U_256x256: bm = 256, bn = 256, per_cu = 1; break;
-        case PP_U_256x128: bm = 256, bn = 128, per_cu = 1; break;
-        case PP_U_128x128: bm = 128, bn = 128, per_cu = 2; break;
-        default: bm = 128, bn = 64, per_cu = 2; break;
-    }
 }
 
 
@@ -55,10 +43,4 @@ bool pp_gemm_u_vec_ok(const PpGemmDesc& d) {
            al(d.C_hl) && (!d.C_hl || (d.ldc_h & 7) == 0);
 }
 
-int pp_gemm_u_launch(const PpGemmDesc& d, int tile, int terms, int cus, hipStream_t st) {
-    const int mode = pp_gemm_u_mode(d, terms);
-    const bool vec = pp_gemm_u_vec_ok(d);
-    if (!vec && tile != PP_U_128x64) tile = PP_U_128x128;   // the element-wise epilogue exists for the two small tiles
-    return terms == 2 ? pp_gemm_u_launch_t2(d, tile, mode, vec, cus, st) : pp_gemm_u_launch_t1(d, tile, mode, vec, cus, st);
-}
 PP_SAT_SETTER(pp_sat_set_gemm_uh)
