@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the PicoPose correspondence hot path on MI355X (driver contract: ONE JSON line).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--mode fast|exact] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--mode fast|exact] [--dump-outputs DIR] [--full]
 
 Default workload `full_b32_n162_vitb` = BASELINE.json configs[2] (the configuration the metric is quoted
 on): batch 32 synthetic 224x224 crops, 162 templates per crop, DINOv2 ViT-B/14, hyp 5 — one step is
@@ -31,13 +31,18 @@ N > 1 (one rank per GPU, RCCL), two modes:
     data-parallel on the rank's own crops.  The line carries `phases_ms` (HIP events at the phase boundaries of one extra
     untimed step: features, exchange, stage1, tail, pnp).
 
-JSON extras: `roofline` = the dominant kernel of the workload.  Full path: the pre-split f16x3 GEMM/conv kernel
+A plain run does what its headline needs and no more: it sets up, warms up, times the K steps, writes --dump-outputs and prints
+the line (`value`, `ms_per_step`, `mfma` = whole-step FLOP rate; stage-1 workloads also `roofline`, whose events sit inside the
+timed steps).  `--full` adds, after the timed region, everything that takes runs of its own: the extras below, `pnp`,
+`operand_range`, `dead_layer1_computed`, `phases_ms` and, for N > 1, `sharded_leg` (each `--no-*-leg` flag drops one of them).
+
+JSON extras (--full): `roofline` = the dominant kernel of the workload.  Full path: the pre-split f16x3 GEMM/conv kernel
 (75 % of the step; MFMA-bound) — executed MFMA flops of all its launches in one step / their summed durations,
 measured live with HIP events around every launch (an extra, untimed step after the timed region, so the
 events do not perturb `value`).  Stage-1 workloads: the fused similarity kernel vs the HBM roofline (events
 around exactly that launch inside the timed steps); on the full path the same object is reported as
-`roofline_stage1`.  `mfma` = whole-step FLOP rate; `cpu_baseline` = the CPU oracle (a port of the reference's
-torch-CPU path) on a bounded sample.
+`roofline_stage1`.  `exact_mode` = the same step in --mode exact; `latency` and `train_step` = the reference's per-image
+measurement and the training step; `cpu_baseline` = the CPU oracle (a port of the reference's torch-CPU path) on a bounded sample.
 """
 import argparse
 import ctypes
@@ -531,7 +536,7 @@ def main():
                     help="every timed step runs the SAME input batch (rounds 1-5); default: two distinct synthetic batches alternate, so the look-ahead "
                          "(the next batch's query crops inside this batch's template-side ViT pass) prefetches a batch that really differs")
     ap.add_argument("--no-sharded-leg", action="store_true",
-                    help="N > 1, default (weak) run: skip the extra leg that runs BASELINE configs[3] — global batch = the workload's crops, "
+                    help="N > 1, --full (weak) run: skip the extra leg that runs BASELINE configs[3] — global batch = the workload's crops, "
                          "template-sharded bank, all-gathers over RCCL — after the timed region")
     ap.add_argument("--no-prefetch-query", dest="prefetch_query", action="store_false",
                     help="the query ViT of every batch as its own pass (rounds 1-4) instead of inside the previous batch's template-side pass")
@@ -541,11 +546,14 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (the arrays its caller receives) as DIR/<name>.npy "
                          "in float32 / float64, at most 64 MB in all; the inputs are seeded, so two builds compare output for output")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-exact-leg", action="store_true", help="skip the untimed --mode exact comparison leg")
-    ap.add_argument("--no-train-leg", action="store_true", help="skip the training-step extra (default workload, fast mode only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs that take runs of their own: roofline and per-kernel events, PnP and "
+                         "operand-range checks, the dead-layer, --mode exact, latency, training-step and sharded legs, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-exact-leg", action="store_true", help="--full: skip the untimed --mode exact comparison leg")
+    ap.add_argument("--no-train-leg", action="store_true", help="--full: skip the training-step extra (default workload, fast mode only)")
     ap.add_argument("--no-latency-leg", action="store_true",
-                    help="skip the per-image latency leg (the reference's own measurement: ViT-L/14, 162 templates, hyp 5, chunks of 4 detections)")
+                    help="--full: skip the per-image latency leg (the reference's own measurement: ViT-L/14, 162 templates, hyp 5, chunks of 4 detections)")
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0:
         ap.error(f"--steps must be at least 1 and --warmup at least 0 (got {a.steps}, {a.warmup})")
@@ -802,16 +810,18 @@ def main():
         _lib.check(L.pp_prof_enable(0), "pp_prof_enable")
         return sum(buf[i] for i in range(cnt.value)) / max(cnt.value, 1)
 
-    gemm = pnp = exact = phases = sharded_leg = dead_leg = None
-    if kind == "stage1" and s1_graphed:     # the kernel's own time: the same launches outside the graph, after the timed region
+    gemm = pnp = exact = phases = sharded_leg = dead_leg = sat_checked = kern_ms = None
+    if kind == "stage1" and not s1_graphed:     # (the events bracketed the kernel inside the timed steps)
+        kern_ms = collect_stage1(a.steps)
+    elif not a.full:
+        pass        # a plain run ends here: everything below runs steps of its own after the timed region
+    elif kind == "stage1":     # the kernel's own time: the same launches outside the graph, after the timed region
         n_ev = min(a.steps, 64)
         _lib.check(L.pp_prof_enable(n_ev), "pp_prof_enable")
         for _ in range(n_ev):
             hm.matching_templates(bank, query, None, mask, topk=5, mode=s1_mode)
         torch.cuda.synchronize()
         kern_ms = collect_stage1(n_ev)
-    elif kind == "stage1":
-        kern_ms = collect_stage1(a.steps)
     else:
         _lib.check(L.pp_prof_enable(3), "pp_prof_enable")       # 3 untimed steps with events around the stage-1 launch
         for _ in range(3):
@@ -1050,7 +1060,6 @@ def main():
         ms = dt / a.steps * 1e3
         bpe = 2 if bank_dtype == torch.float16 else 4
         kbytes = stage1_bytes(Bq, n_local, C, bpe)  # bytes one launch of the stage-1 kernel streams on this rank
-        achieved = kbytes / (kern_ms * 1e-3) / 1e9
         prof_dir = next((d for d in ("r03", "r02", "r01") if os.path.exists(os.path.join(ROOT, "profiles", d, "pmc_traffic_stage1.json"))), "r01")
         traffic = traffic_src = None  # HBM bytes per launch from a separate PMC pass (tools/pmc.sh): same kernel, same shape
         # the committed measurement set of this mode and workload, if any (tools/profile_set.sh: kernel trace, MFMA-busy, FETCH_SIZE and
@@ -1092,7 +1101,7 @@ def main():
                      + ("; the call's five launches replayed as ONE HIP graph (MatchingGraph: fixed buffers)" if (kind == "stage1" and a.graph and not sharded) else "")),
             "config": {"workload": f"{a.workload}: {desc}", "global_batch": B, "crops_per_rank": Bl, "templates": N,
                        "templates_per_rank": n_local, "backbone": vit, "channels": C,
-                       "hypotheses": 5, "mode": a.mode, "bank_dtype": "f16" if bpe == 2 else "f32",
+                       "hypotheses": 5, "mode": a.mode, "bank_dtype": "f16" if bpe == 2 else "f32", "full": bool(a.full),
                        "weights": "seeded random init, prediction heads calibrated (picopose_amd/utils/seeding.py)",
                        "shard": "none" if world == 1 else a.shard,
                        "prefetch_query": (bool(a.prefetch_query) and not cached) if kind != "stage1" else None,
@@ -1106,20 +1115,23 @@ def main():
                         f"weak scaling: {Bl} crops per rank x{world} (global batch {B}), each rank its own crops and their banks — independent "
                         f"units, no data-path collective (barrier + max-over-ranks of the timed region only); {backend}")},
         }
-        s1_roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                   "kernel_ms": kern_ms, "algorithmic_bytes_per_launch": kbytes, "traffic_measured_in_this_run": False,
-                   "kernel": f"s1_main<{s1_mode}> (stage-1 fused similarity)", "traffic_source": traffic_src,
-                   "timing": "HIP events on the launch stream around this launch, " +
-                             ("inside the timed steps" if kind == "stage1" and not s1_graphed else
-                              "the same launches outside the graph, after the timed region" if kind == "stage1" else "3 extra untimed steps after the timed region")}
-        # the other roof of the same launch: the 256 x 256 x C contraction per (crop, template) on the matrix cores
-        # (fast mode: one fp16 MFMA term; exact mode: fp32 MFMA).  With an fp16-stored bank the intensity is 2 C 256^2 / (2 C 256)
-        # = 256 flop/B against a ridge of 2500 / 8 = 312: the kernel then sits between both roofs and this reading is the binding one.
-        s1_flops = 2.0 * Bq * n_local * 256 * 256 * C
-        s1_peak = MFMA_F32_PEAK_TF if a.mode == "exact" else MFMA_F16_PEAK_TF
-        s1_roof["mfma"] = {"achieved": s1_flops / (kern_ms * 1e-3) / 1e12, "peak": s1_peak, "unit": "TFLOP/s",
-                           "frac": s1_flops / (kern_ms * 1e-3) / 1e12 / s1_peak, "flops_per_launch": s1_flops,
-                           "intensity_flop_per_byte": s1_flops / kbytes}
+        s1_roof = None      # (a plain run of the full path times no stage-1 launch on its own)
+        if kern_ms is not None:
+            achieved = kbytes / (kern_ms * 1e-3) / 1e9
+            s1_roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                       "kernel_ms": kern_ms, "algorithmic_bytes_per_launch": kbytes, "traffic_measured_in_this_run": False,
+                       "kernel": f"s1_main<{s1_mode}> (stage-1 fused similarity)", "traffic_source": traffic_src,
+                       "timing": "HIP events on the launch stream around this launch, " +
+                                 ("inside the timed steps" if kind == "stage1" and not s1_graphed else
+                                  "the same launches outside the graph, after the timed region" if kind == "stage1" else "3 extra untimed steps after the timed region")}
+            # the other roof of the same launch: the 256 x 256 x C contraction per (crop, template) on the matrix cores
+            # (fast mode: one fp16 MFMA term; exact mode: fp32 MFMA).  With an fp16-stored bank the intensity is 2 C 256^2 / (2 C 256)
+            # = 256 flop/B against a ridge of 2500 / 8 = 312: the kernel then sits between both roofs and this reading is the binding one.
+            s1_flops = 2.0 * Bq * n_local * 256 * 256 * C
+            s1_peak = MFMA_F32_PEAK_TF if a.mode == "exact" else MFMA_F16_PEAK_TF
+            s1_roof["mfma"] = {"achieved": s1_flops / (kern_ms * 1e-3) / 1e12, "peak": s1_peak, "unit": "TFLOP/s",
+                               "frac": s1_flops / (kern_ms * 1e-3) / 1e12 / s1_peak, "flops_per_launch": s1_flops,
+                               "intensity_flop_per_byte": s1_flops / kbytes}
         k = 1 if a.mode == "exact" else 0     # fast / fp16: the pre-split kernel; exact: the fp32-MFMA kernel
         if kind == "full" and gemm and gemm["launches"][k] > 0:
             mult, peak = {"fast": (3, MFMA_F16_PEAK_TF), "fp16": (1, MFMA_F16_PEAK_TF), "exact": (1, MFMA_F32_PEAK_TF)}[a.mode]
@@ -1173,7 +1185,7 @@ def main():
                 "per_kernel": pk,
             }
             line["roofline_stage1"] = s1_roof
-        else:
+        elif s1_roof is not None:
             line["roofline"] = s1_roof
         if kind == "full":
             tf = Bl * full_gflop_per_crop(N, vit, cached=cached) / (dt / a.steps) / 1e3   # useful (fp32-equivalent) TFLOP/s per GPU
@@ -1196,7 +1208,8 @@ def main():
                                 "note": "DIRECT-convolution-equivalent flops of the step: with Winograd on (ops.WINOGRAD) the large 3x3 convolutions execute "
                                         "2.25x fewer, so this fraction is not an MFMA utilisation and may exceed 1; `roofline` counts executed flops",
                                 "winograd": bool(ops.WINOGRAD)}
-            line["pnp"] = pnp
+            if pnp is not None:
+                line["pnp"] = pnp
             if phases is not None:
                 line["phases_ms"] = phases
             if sat_checked is not None:
@@ -1232,18 +1245,18 @@ def main():
                             "choice (shapes missing from it were tuned in this run)" if tune["loaded"] else
                             "tuned in this run and written for the other passes of the measurement set")
             line["autotune"] = tune
-        if world == 1 and emulate is None and kind == "full" and not a.no_latency_leg:
+        if a.full and world == 1 and emulate is None and kind == "full" and not a.no_latency_leg:
             ops.PRECISION = {"fast": "f16x3", "exact": "f32", "fp16": "f16"}[a.mode]
             line["latency"] = latency_leg(dev, s1_mode)
             line["latency_ms_per_image"] = line["latency"]["ms_per_image"]
             if "latency_ms_per_image" in line.get("roofline", {}):
                 line["roofline"]["latency_ms_per_image"] = line["latency_ms_per_image"]
-        if world == 1 and emulate is None and kind == "full" and a.workload == "full_b32_n162_vitb" and a.mode == "fast" and not a.no_train_leg:
+        if a.full and world == 1 and emulate is None and kind == "full" and a.workload == "full_b32_n162_vitb" and a.mode == "fast" and not a.no_train_leg:
             line["train_step"] = train_step_leg(dev)
             line["train_step_ms"] = line["train_step"]["ms_per_step"]
             if "train_step_ms" in line.get("roofline", {}):
                 line["roofline"]["train_step_ms"] = line["train_step_ms"]
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_full(N, vit, sd) if kind == "full" else cpu_baseline_stage1(N, C)
         if dumped is not None:
             line["dump_outputs"] = dumped

@@ -1,5 +1,6 @@
 """The measurement contract of bench.py as the driver parses it: ONE JSON line, the contract's keys, and a `roofline` object that STARTS with
-scalars (the driver's record keeps its first ~23 keys and drops unknown top-level keys: VERDICT r05 weak #4)."""
+scalars (the driver's record keeps its first ~23 keys and drops unknown top-level keys: VERDICT r05 weak #4).  A plain run carries the
+headline alone; `--full` adds the legs that take runs of their own."""
 import json
 import os
 import subprocess
@@ -11,6 +12,10 @@ import pytest
 gpu = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
+HEADLINE = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+            "config"]
+FULL_ONLY = ["roofline", "roofline_stage1", "cpu_baseline", "exact_mode", "exact_value", "latency", "train_step", "pnp", "operand_range",
+             "dead_layer1_computed", "phases_ms", "sharded_leg"]
 CONTRACT = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
             "config", "roofline", "cpu_baseline"]
 ROOFLINE_HEAD = ["bound", "achieved", "peak", "unit", "frac", "traffic"]
@@ -21,10 +26,11 @@ ROOFLINE_SCALARS = ["frac_algorithmic", "dominant_ms", "dominant_frac_algorithmi
 
 @gpu
 def test_bench_line_contract_on_a_small_workload(tmp_path):
-    """`python bench.py --workload full_b8_n42_vits --steps 2 --warmup 1 --no-latency-leg --dump-outputs DIR` (a child process): the line a
-    driver reads, and the last timed step's outputs as DIR/<name>.npy."""
+    """`python bench.py --workload full_b8_n42_vits --steps 2 --warmup 1 --full --no-latency-leg --dump-outputs DIR` (a child process): the
+    line a driver reads, and the last timed step's outputs as DIR/<name>.npy."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "full_b8_n42_vits", "--steps", "2", "--warmup", "1",
-                        "--no-latency-leg", "--dump-outputs", str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=ROOT)
+                        "--full", "--no-latency-leg", "--dump-outputs", str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600,
+                       cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -59,6 +65,30 @@ def test_bench_line_contract_on_a_small_workload(tmp_path):
     assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in dumped.values())
     ok = dumped["pnp_success"] > 0
     assert ok.any() and np.abs(np.linalg.det(dumped["pnp_rot"][ok]) - 1).max() < 1e-5      # the PnP poses of the step, not zeros
+
+
+@gpu
+def test_bench_plain_run_carries_the_headline_alone(tmp_path):
+    """`python bench.py --workload full_b8_n42_vits --steps 2 --warmup 1 --dump-outputs DIR` without --full: the headline's keys, the
+    whole-step FLOP rate, the last timed step's outputs — and none of the legs that run steps of their own after the timed region."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "full_b8_n42_vits", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    for k in HEADLINE:
+        assert k in d, k
+    for k in FULL_ONLY:
+        assert k not in d, k
+    assert d["unit"] == "crops/s" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["value"] - 8 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"] and d["config"]["full"] is False
+    assert d["metric"].startswith("image-crops/sec") and d["dtype"].startswith("f32 tensors") and d["mfma"]["useful_tflops"] > 0
+    dumped = {n: np.load(os.path.join(str(tmp_path), n + ".npy")) for n in d["dump_outputs"]["arrays"]}
+    assert dumped["pred_poses"].shape == (5, 8, 4, 4) and dumped["pnp_rot"].shape == (5, 8, 3, 3) and dumped["pnp_success"].shape == (5, 8)
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in dumped.values())
+    ok = dumped["pnp_success"] > 0
+    assert ok.any() and np.abs(np.linalg.det(dumped["pnp_rot"][ok]) - 1).max() < 1e-5
 
 
 @gpu

@@ -17,7 +17,7 @@ echo "1/4 trace done"
 bash tools/pmc_mfma_step.sh $tag > $out/pmc_mfma_step.txt 2>&1 || exit 1
 echo "2/4 mfma busy done"
 bash tools/pmc_step.sh $tag > /dev/null 2>&1 || exit 1
-cp gpurun_out/pmc_step_$tag.json $out/pmc_step.json
+cp ${PROF_OUT:-$root/build/profiles}/pmc_step_$tag.json $out/pmc_step.json
 echo "3/4 traffic per kernel done"
 cd /tmp
 for c in FETCH_SIZE WRITE_SIZE; do

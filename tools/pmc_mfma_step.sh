@@ -1,13 +1,16 @@
 #!/bin/bash
-# usage: tools/pmc_mfma_step.sh <tag> — MFMA pipe utilisation per kernel over the steps of the default bench
+# usage: tools/pmc_mfma_step.sh <tag> — MFMA pipe utilisation per kernel over the steps of the default bench with `--full` (the stage-1
+# launch of its first untimed leg closes the timed step); counter files under $PROF_OUT (default build/profiles)
 # (counters only, one group per run, no tracing); profiles/r01/pmc_mfma_step.txt is the same data cut to ONE step
 # (the dispatches between the last two stage-1 launches).  busy = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs * 1024 SIMDs).
 tag=$1
 root=$GRAFT_REPO_ROOT
+out=${PROF_OUT:-$root/build/profiles}/pmc_mfma_${tag}
+mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_MFMA --output-format csv -d $root/gpurun_out/pmc_mfma_${tag} -- python3 $root/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-exact-leg > $root/gpurun_out/pmc_mfma_${tag}.log 2>&1
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_MFMA --output-format csv -d $out -- python3 $root/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-exact-leg > $out.log 2>&1
 cd $root
-python3 - "$root/gpurun_out/pmc_mfma_${tag}" <<'PY'
+python3 - "$out" <<'PY'
 import csv, glob, sys, collections, re
 rows = []
 for f in glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True):
