@@ -134,6 +134,29 @@ int pp_stage1_match_ex(const void* bank, int bank_dtype, const float* query, con
                        float eps, void* workspace, size_t workspace_bytes, float* sim_avg,
                        float* out_score, int64_t* out_index, int32_t* stats, void* stream);
 
+/* Indexed bank: the evaluator's per-object template bank without a per-crop copy.  run_test.py:159-162 hands every detection
+ * its own copy of the bank, templates_data[key][obj_idx]; here
+ *   bank      (n_obj,N,C,16,16)  per-object banks, float or half (bank_dtype as in pp_stage1_scores_ex)
+ *   obj_index (B,)               device int64: crop b is matched against bank[obj_index[b]]
+ * and everything else is as in pp_stage1_scores_ex / pp_stage1_match_ex (utils/matching.py:29-69).  The results are those of
+ * the _ex entries on the gathered bank bank[obj_index], bit for bit, in both modes and for both bank types.  The crops are
+ * grouped by object on the device and the crops of one object stream each of its templates together, so a template read by
+ * several crops comes from HBM about once.  An index outside [0, n_obj) is clamped on the device (it never reads outside the
+ * bank); checking the range is the caller's business.  PP_S1_CPX=<n> pins the number of crops that share a template's
+ * stream (default 8; for A/B timing).
+ * Argument errors, returned before any launch: obj_index NULL, n_obj < 1 or n_obj * N >= 2^23, and every error of the _ex
+ * entries (PP_EINVAL); a workspace smaller than pp_stage1_indexed_workspace_bytes (PP_EWORKSPACE). */
+int pp_stage1_indexed_workspace_bytes(int B, int N, int C, size_t* bytes);
+int pp_stage1_scores_indexed(const void* bank, int bank_dtype, const int64_t* obj_index, int n_obj,
+                             const float* query, const float* mask, int mask_h, int mask_w, int B, int N,
+                             int C, int mode, float eps, void* workspace, size_t workspace_bytes,
+                             float* sim_avg, int32_t* stats, void* stream);
+int pp_stage1_match_indexed(const void* bank, int bank_dtype, const int64_t* obj_index, int n_obj,
+                            const float* query, const float* mask, int mask_h, int mask_w, int B, int N,
+                            int C, int k, int mode, float eps, void* workspace, size_t workspace_bytes,
+                            float* sim_avg, float* out_score, int64_t* out_index, int32_t* stats,
+                            void* stream);
+
 
 /* ------------------------------------------------------------------------- *
  * Stage 2/3 glue around the networks (picopose_amd/csrc/pp_geom.hip).

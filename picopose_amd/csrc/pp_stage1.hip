@@ -30,6 +30,12 @@
 //          HBM-bound; every row/column whose "index 0" decision lies within
 //          eps of a tie is re-evaluated by pp_s1_fixup in exact fp32, so the
 //          discrete outputs agree with EXACT mode.
+//
+// Indexed bank (pp_stage1_*_indexed): the bank is per object, (O, N, C, 16, 16), and crop b reads object
+// obj_index[b] (run_test.py:159-162 copies bank[obj_idx] per detection instead).  s1_group sorts the crops by
+// object; the item walk then hands the crops of one (object, template) to workgroups of one XCD in the same round,
+// so a slice shared by several crops comes from HBM about once.  Every item runs the same MFMA sequence and writes
+// the same per-(crop, template) records as on the gathered bank bank[obj_index]: bit-identical results.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -91,6 +97,64 @@ __host__ S1Ws carve(void* base, int B, int N, int C) {
     w.counters = (int*)take((size_t)B * 4);
     w.total = off;
     return w;
+}
+
+// Indexed bank: (B + 1) walk entries {crop, first sorted position of its chunk, chunk size, slice shared} in object order
+// (entry B: {any slice shared, -, -, -}) and the clamped object of every crop, after the S1Ws arrays.
+struct S1Idx {
+    int4* seq;
+    int* objc;
+    size_t total;
+};
+
+__host__ S1Idx carve_idx(void* base, int B, int N, int C) {
+    S1Idx x;
+    const size_t off = carve(nullptr, B, N, C).total;
+    x.seq = (int4*)((char*)base + off);
+    x.objc = (int*)((char*)base + off + align256((size_t)(B + 1) * 16));
+    x.total = off + align256((size_t)(B + 1) * 16) + align256((size_t)B * 4);
+    return x;
+}
+
+// Crops grouped by object: a counting sort of the B crops (each crop counts the crops with a smaller object, and those
+// with its object ahead of it: its position in a stable sort), one workgroup.  Objects outside [0, n_obj) are clamped,
+// so no index reads outside the bank.  The crops of an object are cut into chunks of at most `cpx` that walk the bank
+// one after the other (the XCD that takes a chunk's items of one template keeps the chunk's queries in its L2).
+__global__ __launch_bounds__(1024) void s1_group(const int64_t* __restrict__ obj_index, int B, int n_obj, int cpx,
+                                                 int4* __restrict__ seq, int* __restrict__ objc) {
+    __shared__ int tile[1024];
+    __shared__ int any_shared;
+    const int tid = threadIdx.x;
+    if (tid == 0) any_shared = 0;
+    auto obj_of = [&](int b) {
+        const int64_t o = obj_index[b];
+        return (int)(o < 0 ? 0 : o >= n_obj ? n_obj - 1 : o);
+    };
+    for (int b0 = 0; b0 < B; b0 += 1024) {
+        const int b = b0 + tid;
+        const int ob = b < B ? obj_of(b) : 0;
+        int lt = 0, eq = 0, eqb = 0;
+        for (int t0 = 0; t0 < B; t0 += 1024) {
+            __syncthreads();
+            if (t0 + tid < B) tile[tid] = obj_of(t0 + tid);
+            __syncthreads();
+            const int nt = min(1024, B - t0);
+            for (int j = 0; j < nt; ++j) {
+                const int o = tile[j];
+                lt += o < ob;
+                eq += o == ob;
+                eqb += (o == ob) & (t0 + j < b);
+            }
+        }
+        if (b < B) {
+            const int ci = eqb / cpx;
+            seq[lt + eqb] = make_int4(b, lt + ci * cpx, min(cpx, eq - ci * cpx), eq > 1);
+            objc[b] = ob;
+            if (eq > 1) any_shared = 1;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) seq[B] = make_int4(any_shared, 0, 0, 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -247,6 +311,7 @@ struct Cfg<PP_MATCH_FAST> {
 // The epilogue's transpose tile T lives in ring slot 2 + X buffer 1: slots 0/1 receive the NEXT item's first
 // query tiles while the epilogue runs, and X buffer 0 (written by the next item's step 0) stays untouched, so
 // the step's own barrier is the only one needed between an epilogue and the following K loop.
+constexpr int S1_IDX_CPX_DEFAULT = 8;            // indexed bank: crops per chunk (s1_group; profiles/r07/indexed_bank.md)
 constexpr int QS = 16384;                         // one query tile: 16 fragment chunks of 1 KB (fast) / [16][256] fp32
 constexpr int Q_RING = 3;
 constexpr int XS_MAX = Cfg<PP_MATCH_FAST>::XS_BYTES;
@@ -325,6 +390,28 @@ __device__ __forceinline__ void s1_item(int v, int N, int& b, int& n, int& half)
     half = r & 1;
 }
 
+// Indexed bank: work item v -> (crop, template, half) and its bank row (object * N + template).  The items are walked in s1_group's order: chunk by chunk, within a
+// chunk template by template (and half by half), the chunk's crops innermost — position u.  When some slice is shared (and
+// the grid is a multiple of 8) every full round of G items deals u to workgroups so that G/8 consecutive u land on equal
+// blockIdx.x % 8: one XCD under the round-robin placement.  Placement is for speed only; any walk computes the same records.
+template <int NW>
+__device__ __forceinline__ void s1_item_idx(int v, int N, int G, int total, bool stripe, const int4* __restrict__ seq,
+                                            const int* __restrict__ objc, int& b, int& n, int& half, int& row) {
+    int u = v;
+    if (stripe) {
+        const int r = v / G, g = v - r * G;
+        if ((r + 1) * G <= total) u = r * G + (g & 7) * (G >> 3) + (g >> 3);
+    }
+    const int per = NW == 8 ? N : 2 * N;   // items per crop
+    const int4 e = seq[u / per];           // {crop, chunk start, chunk size, -}
+    const int r2 = u - e.y * per;
+    const int unit = r2 / e.z;
+    b = seq[e.y + (r2 - unit * e.z)].x;
+    n = NW == 8 ? unit : unit >> 1;
+    half = NW == 8 ? 0 : unit & 1;
+    row = objc[b] * N + n;
+}
+
 // Persistent workgroups of NW waves.  NW = 8 (default): a work item = (crop b, template n), waves 0-3 own
 // template patches 0..127 and waves 4-7 patches 128..255, one workgroup per CU.  NW = 4: a work item =
 // (crop, template, half), two workgroups per CU.  Within a half the 4 waves are 2 x 2 over (128 query patches,
@@ -332,14 +419,18 @@ __device__ __forceinline__ void s1_item(int v, int N, int& b, int& n, int& half)
 // item's first tiles are in flight while the epilogue of the current one runs.
 // XT = element type of the bank in HBM: float (the reference's layout) or _Float16 (a bank stored in half precision —
 // BASELINE configs[4]: half the bytes per template; the values ARE the fp16-rounded features, all arithmetic as before).
-template <int MODE, int NW, typename XT = float>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void s1_main(const XT* __restrict__ bank,
+// IDX: the bank is per object (indexed form): seq / objc from s1_group, `stripe`: the XCD-striped walk (s1_item_idx).
+// AUX: cache policy of the bank loads.
+template <int MODE, int NW, typename XT, bool IDX, int AUX>
+__device__ __forceinline__ void s1_body(const XT* __restrict__ bank,
                                                   const _Float16* __restrict__ qh,
                                                   const float* __restrict__ qf, int N, int C, int total,
                                                   float4* __restrict__ rowrec,
                                                   float* __restrict__ simt0,
                                                   float* __restrict__ colmax,
-                                                  float* __restrict__ sim0s) {
+                                                  float* __restrict__ sim0s,
+                                                  const int4* __restrict__ seq, const int* __restrict__ objc,
+                                                  bool stripe) {
     using K = Cfg<MODE>;
     using L = Lay<NW>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -360,10 +451,19 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void s1_main(const XT* __
     const int G = gridDim.x;
 
     // ---- first item of this workgroup, and the one after it
-    int b, n, half;
+    // -> crop, template, half, bank row
+    auto item = [&](int v, int& b_, int& n_, int& h_, int& row_) __attribute__((always_inline)) {
+        if constexpr (IDX) {
+            s1_item_idx<NW>(v, N, G, total, stripe, seq, objc, b_, n_, h_, row_);
+        } else {
+            s1_item<NW>(v, N, b_, n_, h_);
+            row_ = b_ * N + n_;
+        }
+    };
+    int b, n, half, row;
     int v_cur = blockIdx.x;
     if (v_cur >= total) return;
-    s1_item<NW>(v_cur, N, b, n, half);
+    item(v_cur, b, n, half, row);
     if (NW == 8) half = hw;
     int v_nxt = v_cur + G;
 
@@ -374,20 +474,20 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void s1_main(const XT* __
     // Tiles past the end of a slice read zeros without memory traffic, so every step issues the same loads and
     // the counted waits below are exact.  After an item's last tile the descriptors switch to the next item's
     // (an empty slice when there is none).
-#define X_DESC(b_, n_, half_, ok_)                                                                         \
-    __builtin_amdgcn_make_buffer_rsrc((void*)(bank + ((size_t)(b_) * N + (n_)) * (size_t)C * P + (half_) * 128), 0, \
+#define X_DESC(row_, half_, ok_)                                                                           \
+    __builtin_amdgcn_make_buffer_rsrc((void*)(bank + (size_t)(row_) * (size_t)C * P + (half_) * 128), 0,        \
                                       (ok_) ? C * P * ES - (half_) * 128 * ES : 0, 0x00020000)
 #define Q_DESC(b_, ok_)                                                                                     \
     __builtin_amdgcn_make_buffer_rsrc(MODE == PP_MATCH_FAST ? (void*)(qh + (size_t)(b_) * C * P)           \
                                                             : (void*)(qf + (size_t)(b_) * C * P),          \
                                       0, (ok_) ? C * P * QELT : 0, 0x00020000)
-    __amdgpu_buffer_rsrc_t Xd = X_DESC(b, n, NW == 8 ? 0 : half, true), Qd = Q_DESC(b, true);
+    __amdgpu_buffer_rsrc_t Xd = X_DESC(row, NW == 8 ? 0 : half, true), Qd = Q_DESC(b, true);
     __amdgpu_buffer_rsrc_t XdN, QdN;
     {
-        int b2, n2, h2;
+        int b2, n2, h2, row2;
         const bool ok = v_nxt < total;
-        s1_item<NW>(ok ? v_nxt : v_cur, N, b2, n2, h2);
-        XdN = X_DESC(b2, n2, h2, ok);
+        item(ok ? v_nxt : v_cur, b2, n2, h2, row2);
+        XdN = X_DESC(row2, h2, ok);
         QdN = Q_DESC(b2, ok);
     }
     int xt = 0, qt = -1;  // next tile of the stream; the very first query copy is a dummy (out of bounds: zeros)
@@ -409,9 +509,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void s1_main(const XT* __
     do {                                                                                          \
         _Pragma("unroll") for (int j = 0; j < K::XL; ++j) {                                       \
             if constexpr (ES == 4)                                                                \
-                x_[j] = __builtin_bit_cast(xreg_t, __builtin_amdgcn_raw_buffer_load_b128(Xd, xvoff, (xt * K::KS + 8 * j) * P * 4, PP_S1_XAUX)); \
+                x_[j] = __builtin_bit_cast(xreg_t, __builtin_amdgcn_raw_buffer_load_b128(Xd, xvoff, (xt * K::KS + 8 * j) * P * 4, AUX)); \
             else                                                                                  \
-                x_[j] = __builtin_bit_cast(xreg_t, __builtin_amdgcn_raw_buffer_load_b64(Xd, xvoff, (xt * K::KS + 8 * j) * P * 2, PP_S1_XAUX)); \
+                x_[j] = __builtin_bit_cast(xreg_t, __builtin_amdgcn_raw_buffer_load_b64(Xd, xvoff, (xt * K::KS + 8 * j) * P * 2, AUX)); \
         }                                                                                         \
         if (++xt == KT3) {                                                                        \
             xt = 0;                                                                               \
@@ -754,14 +854,17 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void s1_main(const XT* __
             // ---- next item (its first tiles are already in flight)
             v_cur = v_nxt;
             if (v_cur >= total) break;
-            s1_item<NW>(v_cur, N, b, n, half);
+            {
+                int row_c;   // (the item's tiles are in flight: Xd already switched to them)
+                item(v_cur, b, n, half, row_c);
+            }
             if (NW == 8) half = hw;
             v_nxt = v_cur + G;
             {
-                int b2, n2, h2;
+                int b2, n2, h2, row2;
                 const bool ok = v_nxt < total;
-                s1_item<NW>(ok ? v_nxt : v_cur, N, b2, n2, h2);
-                XdN = X_DESC(b2, n2, h2, ok);
+                item(ok ? v_nxt : v_cur, b2, n2, h2, row2);
+                XdN = X_DESC(row2, h2, ok);
                 QdN = Q_DESC(b2, ok);
             }
 #pragma unroll
@@ -798,6 +901,27 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void s1_main(const XT* __
 #undef LOAD_XB
 #undef X_DESC
 #undef Q_DESC
+}
+
+// The kernel.  IDX: when some slice is read by several crops (s1_group's flag) the whole launch streams the bank with the
+// default cache policy — those slices are re-read from L2 by other CUs (MI355X_MICROARCH.md "nt-weights") — else with nt, as
+// the gathered bank is: a launch of distinct objects moves the same bytes as the gathered one.  (A per-slice choice costs
+// registers: the policy is an instruction bit, and a branch per load group spills.)  stripe_ok: the grid is a multiple of 8.
+template <int MODE, int NW, typename XT = float, bool IDX = false>
+__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void s1_main(const XT* __restrict__ bank, const _Float16* __restrict__ qh,
+                                                                    const float* __restrict__ qf, int N, int C, int total,
+                                                                    float4* __restrict__ rowrec, float* __restrict__ simt0,
+                                                                    float* __restrict__ colmax, float* __restrict__ sim0s,
+                                                                    const int4* __restrict__ seq, const int* __restrict__ objc,
+                                                                    int stripe_ok) {
+    if constexpr (IDX) {
+        if (seq[total / (NW == 8 ? N : 2 * N)].x != 0)
+            s1_body<MODE, NW, XT, true, 0>(bank, qh, qf, N, C, total, rowrec, simt0, colmax, sim0s, seq, objc, stripe_ok != 0);
+        else
+            s1_body<MODE, NW, XT, true, PP_S1_XAUX>(bank, qh, qf, N, C, total, rowrec, simt0, colmax, sim0s, seq, objc, false);
+    } else {
+        s1_body<MODE, NW, XT, false, PP_S1_XAUX>(bank, qh, qf, N, C, total, rowrec, simt0, colmax, sim0s, seq, objc, false);
+    }
 }
 
 // torch.topk(sim_avg, k, dim=1) (matching.py:68): descending score, NaN sorts above every
@@ -933,7 +1057,8 @@ __global__ __launch_bounds__(256) void s1_resolve(const XT* __restrict__ bank,
                                                   const float* __restrict__ sim0s,
                                                   float* __restrict__ sim_avg,
                                                   int32_t* __restrict__ stats, int topk_k, int* __restrict__ counters,
-                                                  float* __restrict__ out_score, int64_t* __restrict__ out_index) {
+                                                  float* __restrict__ out_score, int64_t* __restrict__ out_index,
+                                                  const int* __restrict__ objc) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* L = (float*)smem;  // [10][C]: q[:,t], x[:,0], x[:,c..c+3], x[:,c+32..c+35]
     __shared__ int nent;
@@ -965,7 +1090,9 @@ __global__ __launch_bounds__(256) void s1_resolve(const XT* __restrict__ bank,
         }
         __syncthreads();
         const int ne = nent;
-        const XT* X = bank + bn * (size_t)C * P;
+        // indexed bank (objc): template n of the crop's object
+        const size_t row = objc ? (size_t)objc[b] * N + (bn - (size_t)b * N) : bn;
+        const XT* X = bank + row * (size_t)C * P;
         const float* Q = qf + (size_t)b * C * P;
         for (int e = 0; e < ne; ++e) {
             const unsigned f = ent[e];
@@ -1107,6 +1234,24 @@ __global__ __launch_bounds__(256) void s1_resolve(const XT* __restrict__ bank,
     }
 }
 
+template <int MODE, int NW, typename XT, bool IDX>
+void s1_main_launch(int grid, hipStream_t stream, const void* bank, const S1Ws& w, int N, int C, int total, const int4* seq,
+                    const int* objc, int stripe_ok) {
+    hipLaunchKernelGGL((s1_main<MODE, NW, XT, IDX>), dim3(grid), dim3(64 * NW), Lay<NW>::SMEM_BYTES, stream, (const XT*)bank, w.qh,
+                       w.qf, N, C, total, w.rowrec, w.simt0, w.colmax, w.sim0s, seq, objc, stripe_ok);
+}
+
+template <bool IDX>
+void s1_main_dispatch(bool f16, int mode, int nw, int grid, hipStream_t stream, const void* bank, const S1Ws& w, int N, int C,
+                      int total, const int4* seq, const int* objc, int stripe_ok) {
+    const bool fast = mode == PP_MATCH_FAST;
+    auto go = f16 ? (fast ? (nw == 8 ? s1_main_launch<PP_MATCH_FAST, 8, _Float16, IDX> : s1_main_launch<PP_MATCH_FAST, 4, _Float16, IDX>)
+                          : (nw == 8 ? s1_main_launch<PP_MATCH_EXACT, 8, _Float16, IDX> : s1_main_launch<PP_MATCH_EXACT, 4, _Float16, IDX>))
+                  : (fast ? (nw == 8 ? s1_main_launch<PP_MATCH_FAST, 8, float, IDX> : s1_main_launch<PP_MATCH_FAST, 4, float, IDX>)
+                          : (nw == 8 ? s1_main_launch<PP_MATCH_EXACT, 8, float, IDX> : s1_main_launch<PP_MATCH_EXACT, 4, float, IDX>));
+    go(grid, stream, bank, w, N, C, total, seq, objc, stripe_ok);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -1119,24 +1264,34 @@ int pp_stage1_workspace_bytes(int B, int N, int C, size_t* bytes) {
     return PP_OK;
 }
 
+int pp_stage1_indexed_workspace_bytes(int B, int N, int C, size_t* bytes) {
+    if (!bytes || B <= 0 || N <= 0 || C <= 0) return PP_EINVAL;
+    *bytes = carve_idx(nullptr, B, N, C).total;
+    return PP_OK;
+}
+
 // topk_k > 0: the fused form of pp_stage1_match — the last resolve workgroup of a crop ranks the crop's scores (out_score / out_index)
-static int stage1_run(const void* bank_, int bank_dtype, const float* query, const float* mask, int mask_h,
-                      int mask_w, int B, int N, int C, int mode, float eps, void* workspace,
+// obj_index != nullptr: the indexed form (bank (n_obj, N, C, 16, 16), crop b reads object obj_index[b])
+static int stage1_run(const void* bank_, int bank_dtype, const int64_t* obj_index, int n_obj, const float* query, const float* mask,
+                      int mask_h, int mask_w, int B, int N, int C, int mode, float eps, void* workspace,
                       size_t workspace_bytes, float* sim_avg, int32_t* stats, int topk_k, float* out_score, int64_t* out_index,
                       void* stream_) {
     const float* bank = (const float*)bank_;
     const _Float16* bank16 = (const _Float16*)bank_;
     const bool f16 = bank_dtype == PP_BANK_F16;
+    const bool indexed = obj_index != nullptr;
     if (bank_dtype != PP_BANK_F32 && bank_dtype != PP_BANK_F16) return PP_EINVAL;
     if (!bank || !query || !mask || !sim_avg || !workspace) return PP_EINVAL;
     if (B <= 0 || N <= 0 || C <= 0 || mask_h <= 0 || mask_w <= 0) return PP_EINVAL;
     if (mode != PP_MATCH_EXACT && mode != PP_MATCH_FAST) return PP_EINVAL;
     if (C % 64 != 0 || C > 2048) return PP_EINVAL;
     if ((size_t)B * N >= (1u << 23)) return PP_EINVAL;
+    if (indexed && (n_obj < 1 || (size_t)n_obj * N >= (1u << 23))) return PP_EINVAL;
     if (((uintptr_t)workspace & 255) != 0) return PP_EWORKSPACE;
     if (((uintptr_t)bank & 15) != 0) return PP_EINVAL;   // (fp16: 8-byte loads of 16-byte aligned rows)
     S1Ws w = carve(workspace, B, N, C);
-    if (workspace_bytes < w.total) return PP_EWORKSPACE;
+    S1Idx x = carve_idx(workspace, B, N, C);
+    if (workspace_bytes < (indexed ? x.total : w.total)) return PP_EWORKSPACE;
     hipStream_t stream = (hipStream_t)stream_;
     // default band: 8 sigma of the fp16 rounding error of a score difference,
     // sigma ~ sqrt(2) * 2.8e-4 / sqrt(C) for unit vectors with spread-out energy
@@ -1170,7 +1325,19 @@ static int stage1_run(const void* bank_, int bank_dtype, const float* query, con
         auto set = [](const void* f, int bytes) {
             return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
         };
-        lds_ok = set((const void*)s1_main<PP_MATCH_FAST, 4>, Lay<4>::SMEM_BYTES) &&
+        auto set_idx = [&](auto idx) {
+            constexpr bool I = decltype(idx)::value;
+            return set((const void*)s1_main<PP_MATCH_FAST, 4, float, I>, Lay<4>::SMEM_BYTES) &&
+                   set((const void*)s1_main<PP_MATCH_EXACT, 4, float, I>, Lay<4>::SMEM_BYTES) &&
+                   set((const void*)s1_main<PP_MATCH_FAST, 8, float, I>, Lay<8>::SMEM_BYTES) &&
+                   set((const void*)s1_main<PP_MATCH_EXACT, 8, float, I>, Lay<8>::SMEM_BYTES) &&
+                   set((const void*)s1_main<PP_MATCH_FAST, 8, _Float16, I>, Lay<8>::SMEM_BYTES) &&
+                   set((const void*)s1_main<PP_MATCH_EXACT, 8, _Float16, I>, Lay<8>::SMEM_BYTES) &&
+                   set((const void*)s1_main<PP_MATCH_FAST, 4, _Float16, I>, Lay<4>::SMEM_BYTES) &&
+                   set((const void*)s1_main<PP_MATCH_EXACT, 4, _Float16, I>, Lay<4>::SMEM_BYTES);
+        };
+        lds_ok = set_idx(std::false_type()) && set_idx(std::true_type()) &&
+                 set((const void*)s1_main<PP_MATCH_FAST, 4>, Lay<4>::SMEM_BYTES) &&
                  set((const void*)s1_main<PP_MATCH_EXACT, 4>, Lay<4>::SMEM_BYTES) &&
                  set((const void*)s1_main<PP_MATCH_FAST, 8>, Lay<8>::SMEM_BYTES) &&
                  set((const void*)s1_main<PP_MATCH_EXACT, 8>, Lay<8>::SMEM_BYTES) &&
@@ -1183,57 +1350,54 @@ static int stage1_run(const void* bank_, int bank_dtype, const float* query, con
                      ? 1 : -1;
     }
     if (lds_ok < 0) return PP_ELAUNCH;
+    if (indexed) {
+        // crops per chunk of an object's crops (s1_group): PP_S1_CPX=<n> pins it (read per call, for A/B timing)
+        const char* cpx_env = getenv("PP_S1_CPX");
+        const int cpx = cpx_env && atoi(cpx_env) > 0 ? atoi(cpx_env) : S1_IDX_CPX_DEFAULT;
+        hipLaunchKernelGGL(s1_group, dim3(1), dim3(1024), 0, stream, obj_index, B, n_obj, cpx, x.seq, x.objc);
+    }
     {
         PpProfScope prof(stream);  // roofline kernel of stage 1 (bench.py)
         const int total = nw == 8 ? B * N : B * 2 * N, slots = nw == 8 ? cus : 2 * cus;
         const int grid = total < slots ? total : slots;
-#define S1_LAUNCH(MODE_, NW_)                                                                                  \
-    hipLaunchKernelGGL((s1_main<MODE_, NW_>), dim3(grid), dim3(64 * NW_), Lay<NW_>::SMEM_BYTES, stream, bank, w.qh, \
-                       w.qf, N, C, total, w.rowrec, w.simt0, w.colmax, w.sim0s)
-#define S1_LAUNCH16(MODE_, NW_)                                                                                \
-    hipLaunchKernelGGL((s1_main<MODE_, NW_, _Float16>), dim3(grid), dim3(64 * NW_), Lay<NW_>::SMEM_BYTES, stream, bank16, w.qh, \
-                       w.qf, N, C, total, w.rowrec, w.simt0, w.colmax, w.sim0s)
-        if (f16) {
-            if (mode == PP_MATCH_FAST) {
-                if (nw == 8) S1_LAUNCH16(PP_MATCH_FAST, 8);
-                else S1_LAUNCH16(PP_MATCH_FAST, 4);
-            } else {
-                if (nw == 8) S1_LAUNCH16(PP_MATCH_EXACT, 8);
-                else S1_LAUNCH16(PP_MATCH_EXACT, 4);
-            }
-        } else if (mode == PP_MATCH_FAST) {
-            if (nw == 8) S1_LAUNCH(PP_MATCH_FAST, 8);
-            else S1_LAUNCH(PP_MATCH_FAST, 4);
-        } else {
-            if (nw == 8) S1_LAUNCH(PP_MATCH_EXACT, 8);
-            else S1_LAUNCH(PP_MATCH_EXACT, 4);
-        }
-#undef S1_LAUNCH
-#undef S1_LAUNCH16
+        if (indexed)
+            s1_main_dispatch<true>(f16, mode, nw, grid, stream, bank_, w, N, C, total, x.seq, x.objc, grid % 8 == 0);
+        else
+            s1_main_dispatch<false>(f16, mode, nw, grid, stream, bank_, w, N, C, total, nullptr, nullptr, 0);
     }
     if (stats) PP_CHECK_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(int32_t), stream));
     if (f16)
         hipLaunchKernelGGL(s1_resolve<_Float16>, dim3(B * N), dim3(256), (size_t)10 * C * sizeof(float), stream,
                            bank16, w.qf, w.m16, N, C, mode == PP_MATCH_FAST ? 1 : 0, eps, w.rowrec,
-                           w.simt0, w.colmax, w.sim0s, sim_avg, stats, topk_k, w.counters, out_score, out_index);
+                           w.simt0, w.colmax, w.sim0s, sim_avg, stats, topk_k, w.counters, out_score, out_index,
+                           indexed ? x.objc : nullptr);
     else
         hipLaunchKernelGGL(s1_resolve<float>, dim3(B * N), dim3(256), (size_t)10 * C * sizeof(float), stream,
                            bank, w.qf, w.m16, N, C, mode == PP_MATCH_FAST ? 1 : 0, eps, w.rowrec,
-                           w.simt0, w.colmax, w.sim0s, sim_avg, stats, topk_k, w.counters, out_score, out_index);
+                           w.simt0, w.colmax, w.sim0s, sim_avg, stats, topk_k, w.counters, out_score, out_index,
+                           indexed ? x.objc : nullptr);
     return pp_last_launch();
 }
 
 int pp_stage1_scores_ex(const void* bank, int bank_dtype, const float* query, const float* mask, int mask_h,
                         int mask_w, int B, int N, int C, int mode, float eps, void* workspace,
                         size_t workspace_bytes, float* sim_avg, int32_t* stats, void* stream) {
-    return stage1_run(bank, bank_dtype, query, mask, mask_h, mask_w, B, N, C, mode, eps, workspace, workspace_bytes, sim_avg, stats, 0,
-                      nullptr, nullptr, stream);
+    return stage1_run(bank, bank_dtype, nullptr, 0, query, mask, mask_h, mask_w, B, N, C, mode, eps, workspace, workspace_bytes, sim_avg,
+                      stats, 0, nullptr, nullptr, stream);
 }
 
-int pp_stage1_match_ex(const void* bank, int bank_dtype, const float* query, const float* mask, int mask_h,
-                       int mask_w, int B, int N, int C, int k, int mode, float eps, void* workspace,
-                       size_t workspace_bytes, float* sim_avg, float* out_score, int64_t* out_index,
-                       int32_t* stats, void* stream) {
+int pp_stage1_scores_indexed(const void* bank, int bank_dtype, const int64_t* obj_index, int n_obj, const float* query,
+                             const float* mask, int mask_h, int mask_w, int B, int N, int C, int mode, float eps, void* workspace,
+                             size_t workspace_bytes, float* sim_avg, int32_t* stats, void* stream) {
+    if (!obj_index) return PP_EINVAL;
+    return stage1_run(bank, bank_dtype, obj_index, n_obj, query, mask, mask_h, mask_w, B, N, C, mode, eps, workspace, workspace_bytes,
+                      sim_avg, stats, 0, nullptr, nullptr, stream);
+}
+
+static int stage1_match(const void* bank, int bank_dtype, const int64_t* obj_index, int n_obj, const float* query, const float* mask,
+                        int mask_h, int mask_w, int B, int N, int C, int k, int mode, float eps, void* workspace,
+                        size_t workspace_bytes, float* sim_avg, float* out_score, int64_t* out_index,
+                        int32_t* stats, void* stream) {
     if (!out_score || !out_index || k <= 0 || k > N || N > 12288) return PP_EINVAL;
     // The last resolve workgroup of a crop CAN rank its scores itself (s1_resolve's topk_k argument, 5 N <= 40 C bytes of LDS):
     // measured slower than a second launch at BASELINE configs[1] — the agent-scope release / acquire of every resolve workgroup
@@ -1241,10 +1405,27 @@ int pp_stage1_match_ex(const void* bank, int bank_dtype, const float* query, con
     // against the 7.7 us of a top-k launch and its gap (profiles/r04/stage1_small.txt).  PP_S1_FUSE_TOPK=1 switches it on.
     static const bool fuse_env = [] { const char* e = getenv("PP_S1_FUSE_TOPK"); return e && e[0] == '1'; }();
     const bool fused = fuse_env && (long long)N * 5 <= 40LL * C;
-    int rc = stage1_run(bank, bank_dtype, query, mask, mask_h, mask_w, B, N, C, mode, eps, workspace, workspace_bytes, sim_avg, stats,
-                        fused ? k : 0, out_score, out_index, stream);
+    int rc = stage1_run(bank, bank_dtype, obj_index, n_obj, query, mask, mask_h, mask_w, B, N, C, mode, eps, workspace, workspace_bytes,
+                        sim_avg, stats, fused ? k : 0, out_score, out_index, stream);
     if (rc != PP_OK || fused) return rc;
     return pp_topk(sim_avg, B, N, k, out_score, out_index, stream);
+}
+
+int pp_stage1_match_ex(const void* bank, int bank_dtype, const float* query, const float* mask, int mask_h,
+                       int mask_w, int B, int N, int C, int k, int mode, float eps, void* workspace,
+                       size_t workspace_bytes, float* sim_avg, float* out_score, int64_t* out_index,
+                       int32_t* stats, void* stream) {
+    return stage1_match(bank, bank_dtype, nullptr, 0, query, mask, mask_h, mask_w, B, N, C, k, mode, eps, workspace, workspace_bytes,
+                        sim_avg, out_score, out_index, stats, stream);
+}
+
+int pp_stage1_match_indexed(const void* bank, int bank_dtype, const int64_t* obj_index, int n_obj, const float* query,
+                            const float* mask, int mask_h, int mask_w, int B, int N, int C, int k, int mode, float eps,
+                            void* workspace, size_t workspace_bytes, float* sim_avg, float* out_score, int64_t* out_index,
+                            int32_t* stats, void* stream) {
+    if (!obj_index) return PP_EINVAL;
+    return stage1_match(bank, bank_dtype, obj_index, n_obj, query, mask, mask_h, mask_w, B, N, C, k, mode, eps, workspace,
+                        workspace_bytes, sim_avg, out_score, out_index, stats, stream);
 }
 
 int pp_stage1_scores(const float* bank, const float* query, const float* mask, int mask_h,

@@ -20,7 +20,7 @@ from .utils.augment import aug_gtM_noise
 from .utils.correspondence import compute_init_correspondences, compute_stage3_correspondences
 from .utils.keypoints import KeypointInput, KeyPointSampler
 from .utils.loss_utils import compute_stage_two_loss, flow_level_losses, infonce_rows
-from .utils.matching import matching_features_similarity, matching_templates
+from .utils.matching import matching_features_similarity, matching_templates, matching_templates_indexed
 from .utils.pose_recovery import pose_recovery_2d_prediction
 from .utils.torch_utils import calc_pred_Ms
 
@@ -97,7 +97,8 @@ class Net(nn.Module):
     # model/picopose.py:52-70 — pick hypothesis k's template for every crop (pure indexing)
     def select_template_data(self, end_points, pred_id_src, k):
         idx = pred_id_src[:, k]
-        rows = torch.arange(idx.shape[0], device=idx.device)
+        rows = end_points.get("template_index")       # per-object banks: crop b's templates are row template_index[b]
+        rows = torch.arange(idx.shape[0], device=idx.device) if rows is None else rows
         sel = {key: end_points[key][rows, idx] for key in ("tem_pose", "tem_K", "tem_M", "tem_mask", "tem_rgb", "tem_pts3d")}
         for key in ("real_pts2d", "real_K", "real_M", "real_mask", "real_pose"):
             sel[key] = end_points[key]
@@ -190,12 +191,13 @@ class Net(nn.Module):
         """The loop of model/picopose.py:106-108 over the top-k templates of every crop -> list of k output dicts."""
         hyp = pred_id_src.shape[1]
         cache = end_points.get("template_cache")  # {"obj_index": (B,) long, "dpt": 3 x (O,N,h,w,256)} (precompute_templates)
+        tidx = end_points.get("template_index")   # (B,) long: the template tensors are per-object banks (O,N,...) (forward_test)
 
         def cached(rows, idx):
             if cache is None:
                 return None
-            obj = cache["obj_index"][rows]
-            return end_points["template_feature"][rows, idx], [m[obj, idx] for m in cache["dpt"]]
+            obj = (cache["obj_index"] if tidx is None else tidx)[rows]
+            return end_points["template_feature"][rows if tidx is None else obj, idx], [m[obj, idx] for m in cache["dpt"]]
 
         if not self.batch_hypotheses:
             rows = torch.arange(pred_id_src.shape[0], device=pred_id_src.device)
@@ -213,9 +215,10 @@ class Net(nn.Module):
         rows = torch.arange(B, device=idx.device).repeat(hyp)
         rep = lambda t: t.repeat(hyp, *([1] * (t.dim() - 1)))  # noqa: E731
         N = end_points["tem_pose"].shape[1]
-        flat = rows * N + idx                                            # row of (b, template) in the (B*N, ...) view
+        trow = rows if tidx is None else tidx[rows]                      # bank row of every sample: its crop, or the crop's object
+        flat = trow * N + idx                                            # row of (b, template) in the (B*N, ...) / (O*N, ...) view
         sel = {key: (ops.gather_rows(end_points[key].flatten(0, 1), flat) if end_points[key].is_contiguous()
-                     else end_points[key][rows, idx])
+                     else end_points[key][trow, idx])
                for key in ("tem_pose", "tem_K", "tem_M", "tem_mask", "tem_rgb", "tem_pts3d")}
         for key in ("real_pts2d", "real_K", "real_M", "real_mask", "real_pose"):
             sel[key] = rep(end_points[key])
@@ -227,6 +230,22 @@ class Net(nn.Module):
                                     cached(rows, idx))
         return [{key: v[k * B:(k + 1) * B] for key, v in out.items()} for k in range(hyp)]
 
+    TEMPLATE_KEYS = ("template_feature", "tem_pose", "tem_K", "tem_M", "tem_mask", "tem_rgb", "tem_pts3d")
+
+    def _check_template_index(self, end_points):
+        """end_points["template_index"] (B,) int64: every template tensor is a per-object bank (O, N, ...) and crop b uses object
+        template_index[b] (pipeline.infer_image(indexed_bank=True); run_test.py:159-162 gathers the banks per crop instead)."""
+        tidx = end_points["template_index"]
+        B = end_points["real_rgb"].shape[0]
+        if not isinstance(tidx, torch.Tensor) or tidx.dtype != torch.int64 or tuple(tidx.shape) != (B,) or tidx.device != end_points["real_rgb"].device:
+            raise ValueError(f"template_index must be a ({B},) int64 tensor on the crops' device")
+        lead = {key: tuple(end_points[key].shape[:2]) for key in self.TEMPLATE_KEYS if key in end_points}
+        if len(set(lead.values())) != 1:
+            raise ValueError(f"with template_index every template tensor is (O, N, ...) for the same O and N: {lead}")
+        cache = end_points.get("template_cache")
+        if cache is not None and cache["obj_index"] is not tidx and not torch.equal(cache["obj_index"].to(tidx.device), tidx):
+            raise ValueError("template_cache['obj_index'] and template_index name different objects")
+
     # model/picopose.py:97-112
     def forward_test(self, end_points, hyp=5, next_real_rgb=None):
         """next_real_rgb: the query crops of the batch this forward will be called with NEXT (a serving loop, the mini-batches of a test
@@ -234,6 +253,8 @@ class Net(nn.Module):
         template-side ViT launches ((hyp + 1) B images per launch instead of hyp B and, separately, B at a fifth of the rows and two thirds
         of the tile fill), and the next call finds its query levels stashed — same bits with or without (tests/test_e2e.py)."""
         with torch.no_grad():
+            if "template_index" in end_points:
+                self._check_template_index(end_points)
             fe = self.feature_extractor
             levels = None
             ops.saturation_word(end_points["real_rgb"].device)      # (registered before the first producer kernel of this device runs)
@@ -262,9 +283,14 @@ class Net(nn.Module):
                 real = (real_tok, (h0, w0), real_dpt)
             # matching.py normalises the bank itself; the reference's extra F.normalize of the whole bank
             # (picopose.py:99) is idempotent up to rounding and is not materialised here
-            pred_score_src, pred_id_src = matching_templates(
-                end_points["template_feature"], ops.tokens_to_nchw(real_tok[-1], 1, h0, w0), end_points["tem_mask"],
-                end_points["real_mask"], topk=hyp, mode=self.match_mode)
+            query = ops.tokens_to_nchw(real_tok[-1], 1, h0, w0)
+            if "template_index" in end_points:
+                pred_score_src, pred_id_src = matching_templates_indexed(
+                    end_points["template_feature"], end_points["template_index"], query, end_points["tem_mask"], end_points["real_mask"],
+                    topk=hyp, mode=self.match_mode)
+            else:
+                pred_score_src, pred_id_src = matching_templates(
+                    end_points["template_feature"], query, end_points["tem_mask"], end_points["real_mask"], topk=hyp, mode=self.match_mode)
             return self.forward_hypotheses(end_points, pred_id_src, real)
 
     # model/picopose.py:29-50

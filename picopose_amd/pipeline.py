@@ -124,7 +124,8 @@ def infer_batch(net, end_points, hyp=5, pnp_fn=None, on_saturation="raise"):
     return _rank_hypotheses(stage2, rot, tvec, ratio, ok, hyp)
 
 
-def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=True, next_data=None, on_saturation="raise"):
+def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=True, next_data=None, on_saturation="raise",
+                indexed_bank=False):
     """One test image exactly as run_test.py:141-188 walks it: `data` holds the image's instances on dim 1
     (data[key][0] = (n_instance, ...), plus 'obj_idx'), `templates_data[key]` the per-object template bank
     ((n_objects, N, ...), including 'template_feature' and, optionally, an extended bank under 'template_cache').
@@ -139,7 +140,10 @@ def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=
     on_saturation: "raise" (default) | "exact" (module docstring), for both walks.  With "exact" no forward carries another mini-batch's query
     crops (and next_data is not used): the snapshot taken after a forward is then that mini-batch's own verdict, and a batch re-run in
     fp32 leaves no look-ahead behind that a later batch would have consumed.  The pipelined walk still launches mini-batch j + 1 before
-    it reads mini-batch j; a flagged j is re-run synchronously when it is read, and preds_image keeps the instance order."""
+    it reads mini-batch j; a flagged j is re-run synchronously when it is read, and preds_image keeps the instance order.
+    indexed_bank: the per-object tensors of `templates_data` go to the network as they are, and each instance names its object
+    (end_points["template_index"] = its obj_idx): no copy of the bank per instance (run_test.py:159-162 makes one: ~308 MB per detection at
+    ViT-L, 162 views), and a template shared by several instances is streamed once by stage 1.  Same results as the default."""
     exact = _check_on_saturation(on_saturation)
     n_instance = data["score"].shape[1]
     preds_image = []
@@ -147,11 +151,14 @@ def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=
     def inputs_of(start, end):
         obj_idx = data["obj_idx"][0][start:end].reshape(-1)
         inputs = {k: v[0][start:end].contiguous() for k, v in data.items() if v[0].dim() > 0}
+        if indexed_bank:
+            obj_idx = obj_idx.long()
+            inputs["template_index"] = obj_idx
         for k, v in templates_data.items():
             if k == "template_cache":   # extended bank: maps stay per object, instances carry their object index
                 inputs[k] = {"obj_index": obj_idx, "dpt": v["dpt"]}
             else:
-                inputs[k] = v[obj_idx].contiguous()
+                inputs[k] = v if indexed_bank else v[obj_idx].contiguous()
         return inputs
 
     def emit(batch_results):

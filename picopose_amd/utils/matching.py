@@ -23,9 +23,9 @@ def _stream_ptr():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _workspace(B, N, C, device):
+def _workspace(B, N, C, device, query="pp_stage1_workspace_bytes"):
     need = ctypes.c_size_t()
-    _lib.check(_lib.lib().pp_stage1_workspace_bytes(B, N, C, ctypes.byref(need)), "pp_stage1_workspace_bytes")
+    _lib.check(getattr(_lib.lib(), query)(B, N, C, ctypes.byref(need)), query)
     key = (device.index, torch.cuda.current_stream().cuda_stream)
     ws = _ws_cache.get(key)
     if ws is None or ws.numel() < need.value:
@@ -103,6 +103,72 @@ def matching_templates(src_feats, tar_feat, src_masks, tar_mask, topk=5, mode=No
         mask.shape[2], B, N, C, int(topk), _MODES[mode or DEFAULT_MODE], 0.0, ws.data_ptr(), nbytes, sim_avg.data_ptr(),
         score.data_ptr(), index.data_ptr(), None, _stream_ptr())
     _lib.check(rc, "pp_stage1_match_ex")
+    return score, index
+
+
+def _check_indexed(src_feats, obj_index, tar_feat, tar_mask):
+    """The indexed bank's arguments, index first (on the host, before any launch) -> (B, N, C, O, obj_index on the bank's device)."""
+    if not isinstance(obj_index, torch.Tensor) or obj_index.dim() != 1 or obj_index.dtype != torch.int64:
+        raise _lib.PicoPoseHipError("obj_index must be a 1-D torch.int64 tensor (one object per crop)")
+    if src_feats.dim() != 5:
+        raise _lib.PicoPoseHipError(f"the indexed bank is (O,N,C,16,16), got {tuple(src_feats.shape)}")
+    O = src_feats.shape[0]
+    B = tar_feat.shape[0]
+    if obj_index.shape[0] != B:
+        raise _lib.PicoPoseHipError(f"obj_index has {obj_index.shape[0]} entries for {B} crops")
+    if not obj_index.is_cuda and B > 0 and (int(obj_index.min()) < 0 or int(obj_index.max()) >= O):
+        raise _lib.PicoPoseHipError(f"obj_index outside [0, {O}): the bank holds {O} objects")
+    if not (src_feats.is_cuda and tar_feat.is_cuda and tar_mask.is_cuda):
+        raise _lib.PicoPoseHipError("picopose_amd runs on the GPU only: inputs must be CUDA(HIP) tensors")
+    _, N, C, H, W = src_feats.shape
+    if H != 16 or W != 16:
+        raise _lib.PicoPoseHipError("the HIP stage-1 kernel is built for 16x16 patch grids")
+    if tuple(tar_feat.shape) != (B, C, H, W) or tar_mask.dim() != 3 or tar_mask.shape[0] != B:
+        raise _lib.PicoPoseHipError(f"query {tuple(tar_feat.shape)} / mask {tuple(tar_mask.shape)} do not fit the bank {tuple(src_feats.shape)}")
+    # (a device index is clamped by the kernel, never read outside the bank; its range is the caller's business)
+    return B, N, C, O, obj_index.to(src_feats.device, non_blocking=True).contiguous()
+
+
+def template_scores_indexed(src_feats, obj_index, tar_feat, tar_mask, mode=None, eps=0.0, return_stats=False):
+    """template_scores on a per-object bank: src_feats (O,N,C,16,16), obj_index (B,) int64 — crop b is matched against object
+    obj_index[b], with no per-crop copy of the bank (run_test.py:159-162 gathers bank[obj_idx] per detection).  Returns what
+    template_scores(src_feats[obj_index], ...) returns, bit for bit.  A CPU obj_index is range-checked here and copied without blocking."""
+    B, N, C, O, idx = _check_indexed(src_feats, obj_index, tar_feat, tar_mask)
+    mode_id = _MODES[mode or DEFAULT_MODE]
+    half = src_feats.dtype == torch.float16
+    bank = src_feats.contiguous() if half else src_feats.contiguous().float()
+    query = tar_feat.contiguous().float()
+    mask = tar_mask.contiguous().float()
+    ws, nbytes = _workspace(B, N, C, bank.device, "pp_stage1_indexed_workspace_bytes")
+    sim_avg = torch.empty(B, N, dtype=torch.float32, device=bank.device)
+    stats = torch.zeros(4, dtype=torch.int32, device=bank.device) if return_stats else None
+    rc = _lib.lib().pp_stage1_scores_indexed(
+        bank.data_ptr(), _lib.PP_BANK_F16 if half else _lib.PP_BANK_F32, idx.data_ptr(), O, query.data_ptr(), mask.data_ptr(),
+        mask.shape[1], mask.shape[2], B, N, C, mode_id, float(eps), ws.data_ptr(), nbytes, sim_avg.data_ptr(),
+        stats.data_ptr() if stats is not None else None, _stream_ptr())
+    _lib.check(rc, "pp_stage1_scores_indexed")
+    return (sim_avg, stats) if return_stats else sim_avg
+
+
+def matching_templates_indexed(src_feats, obj_index, tar_feat, src_masks, tar_mask, topk=5, mode=None):
+    """matching_templates (utils/matching.py:29-69) on a per-object bank: src_feats (O,N,C,16,16), obj_index (B,) int64.
+    Returns (pred_score_src (B,topk) f32, pred_id_src (B,topk) i64), bit for bit those of matching_templates(src_feats[obj_index], ...).
+    Crops of one object share its bank: each of its templates is streamed from HBM about once per call, not once per crop."""
+    B, N, C, O, idx = _check_indexed(src_feats, obj_index, tar_feat, tar_mask)
+    if topk > N:
+        raise RuntimeError(f"selected index k out of range: topk={topk} > N={N}")
+    half = src_feats.dtype == torch.float16
+    bank = src_feats.contiguous() if half else src_feats.contiguous().float()
+    query, mask = tar_feat.contiguous().float(), tar_mask.contiguous().float()
+    ws, nbytes = _workspace(B, N, C, bank.device, "pp_stage1_indexed_workspace_bytes")
+    sim_avg = torch.empty(B, N, dtype=torch.float32, device=bank.device)
+    score = torch.empty(B, topk, dtype=torch.float32, device=bank.device)
+    index = torch.empty(B, topk, dtype=torch.int64, device=bank.device)
+    rc = _lib.lib().pp_stage1_match_indexed(
+        bank.data_ptr(), _lib.PP_BANK_F16 if half else _lib.PP_BANK_F32, idx.data_ptr(), O, query.data_ptr(), mask.data_ptr(),
+        mask.shape[1], mask.shape[2], B, N, C, int(topk), _MODES[mode or DEFAULT_MODE], 0.0, ws.data_ptr(), nbytes, sim_avg.data_ptr(),
+        score.data_ptr(), index.data_ptr(), None, _stream_ptr())
+    _lib.check(rc, "pp_stage1_match_indexed")
     return score, index
 
 
