@@ -548,6 +548,47 @@ int pp_pnp_ransac_debug(const float* tar_pts_2d, const float* src_pts_3d, const 
                         float reproj_threshold, double* rot, double* tvec, double* inlier_ratio, int32_t* success,
                         int32_t* num_points, double* refit_branches, void* stream);
 
+/* pp_pnp_ransac followed by a Levenberg-Marquardt refinement of each pose on its RANSAC consensus set: what
+ * cv2.solvePnPRefineLM(inlier object points, inlier image points, K, None, rvec, tvec, criteria) does after
+ * cv2.solvePnPRansac(..., SOLVEPNP_EPNP) (OpenCV's default criteria: 20 iterations, FLT_EPSILON).  The consensus set
+ * (inlier_ratio), success and num_points are those of pp_pnp_ransac, computed by the same code; only rot / tvec move.
+ *   Cost: sum over the consensus set of the squared pixel reprojection error, in the object frame of pp_pnp_ransac (points
+ *   after the tem_pose transform, fp32 values evaluated in fp64) and K's fu, fv, uc, vc.  Parameters: a local so(3)
+ *   perturbation w applied on the left through the Cayley map (R <- cay(w) R, first-order equal to exp([w]x) R) and a
+ *   translation increment; analytic 2x6 Jacobian, fp64.
+ *   Start: the pose pp_pnp_ransac returns (the EPnP refit, or the RANSAC winner when the refit gave no pose).
+ *   Step: (J^T J + lambda diag(J^T J)) dx = -J^T r by Cholesky, lambda = 0 at the start (a Gauss-Newton step).  The trial
+ *   pose is accepted iff its cost is lower than the current cost and every point of the set has Z > 0; lambda is then divided
+ *   by 10, otherwise it becomes max(10 lambda, 1e-3) (also when the damped matrix is not positive definite).  The returned
+ *   cost is never above the starting cost.
+ *   Stop: after max_iters iterations (each is one pass over the points), after an ACCEPTED step whose cost decrease is
+ *   <= eps * the previous cost, or after any step with |dx|_2 <= eps (radians and the object's length unit).
+ *   Skipped (start pose returned, 0 iterations) when the set has fewer than 6 points or the start or its cost is not finite.
+ *   The sums of a pass are reduced in a fixed order: the result does not change from one launch to the next.
+ * Extra outputs: rms_before / rms_after (P) f64 = RMS reprojection error over the consensus set at the start / the returned
+ * pose in px; lm_iterations (P) int32 = accepted steps; for failed problems (success 0: the reference's failure outputs) 0, 0,
+ * 0.  inlier_mask (P, N) uint8 or null: 1 for a consensus-set member, in the order of the valid (no -1) entries of tar_pts /
+ * src_pts (cv2's `inliers`), 0 in the remaining N - num_points slots and for failed problems.
+ * PP_EINVAL (before any launch): what pp_pnp_ransac rejects, a null rms_before / rms_after / lm_iterations, max_iters <= 0,
+ * eps < 0 or NaN. */
+int pp_pnp_ransac_refine(const float* tar_pts_2d, const float* src_pts_3d, const float* K, const float* tem_pose,
+                         const int64_t* tar_pts, const int64_t* src_pts, int P, int H, int W, int N, int iterations,
+                         float reproj_threshold, int max_iters, double eps, double* rot, double* tvec, double* inlier_ratio,
+                         int32_t* success, int32_t* num_points, double* rms_before, double* rms_after, int32_t* lm_iterations,
+                         uint8_t* inlier_mask, void* stream);
+
+/* cv2.solvePnPRefineLM(object_points, image_points, K, None, rvec, tvec) over a ragged batch of P problems, one 512-thread
+ * workgroup each, with the refinement (cost, parameters, step, stopping rule) of pp_pnp_ransac_refine.
+ *   object_points (P, Nmax, 3), image_points (P, Nmax, 2) f64: problem p uses its first count[p] rows (count (P) int32,
+ *   clamped to [0, Nmax]); K (P, 3, 3) f64 (fu, fv, uc, vc; the skew entry is not used); rot_init (P, 3, 3) row-major,
+ *   tvec_init (P, 3) f64: the start.
+ *   out: rot (P, 3, 3), tvec (P, 3) f64 (may alias rot_init / tvec_init), rms_before, rms_after (P) f64 in px,
+ *   lm_iterations (P) int32.  A problem with count < 6 (or a non-finite start) returns its start and 0 iterations.
+ * PP_EINVAL (before any launch): a null pointer, P <= 0, Nmax <= 0 or > 4096, max_iters <= 0, eps < 0 or NaN. */
+int pp_pnp_refine_lm(const double* object_points, const double* image_points, const int32_t* count, const double* K,
+                     const double* rot_init, const double* tvec_init, int P, int Nmax, int max_iters, double eps, double* rot,
+                     double* tvec, double* rms_before, double* rms_after, int32_t* lm_iterations, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Training forward (model/picopose.py:114-137 — losses only, no gradients; csrc/pp_train.hip)
  * ------------------------------------------------------------------------- */

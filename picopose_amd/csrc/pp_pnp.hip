@@ -596,21 +596,245 @@ _Pragma("unroll")
     return best_err;
 }
 
+// ------------------------------------------------------------------ Levenberg-Marquardt refinement (opt-in tail)
+// Minimises the sum of squared pixel reprojection errors over a point set, from a start pose, over 6 parameters: a local so(3)
+// perturbation w applied on the left (R <- cay(w) R, first-order equal to exp([w]x) R) and a translation increment v
+// (t <- t + v).  With q = R X and
+// Pc = q + t, dPc/dw = -[q]x and dPc/dv = I; the 2x6 Jacobian of (u, v) is d(u, v)/dPc times that, analytic, fp64.
+// One iteration = one pass over the points that accumulates J^T J (21), J^T r (6), the cost and the point count at the TRIAL
+// pose (so an accepted trial already carries the next system), reduced in a fixed order: xor-butterfly within each wave (every
+// lane ends with the same bits: a + b == b + a), then the 8 wave partials summed w = 0..7 by every thread.  Every thread thus
+// holds the same sums and solves the same damped 6x6 system itself, bit for bit (no broadcast, one barrier per iteration).
+constexpr int LM_NV = 29;   // J^T J upper triangle (21, row-major), J^T r (6), cost, count
+
+struct LdsPoints {           // the fused tail: the RANSAC winner's consensus set, object-frame points and pixels in LDS
+    const float* p3;
+    const float* p2;
+    const unsigned char* use;
+    int n;
+    __device__ bool get(int i, double& X, double& Y, double& Z, double& u, double& v) const {
+        if (!use[i]) return false;
+        X = p3[3 * i]; Y = p3[3 * i + 1]; Z = p3[3 * i + 2]; u = p2[2 * i]; v = p2[2 * i + 1];
+        return true;
+    }
+};
+
+struct GlobalPoints {        // pp_pnp_refine_lm: a problem's first n rows of (Nmax, 3) / (Nmax, 2) f64 in global memory
+    const double* p3;
+    const double* p2;
+    int n;
+    __device__ bool get(int i, double& X, double& Y, double& Z, double& u, double& v) const {
+        X = p3[3 * i]; Y = p3[3 * i + 1]; Z = p3[3 * i + 2]; u = p2[2 * i]; v = p2[2 * i + 1];
+        return true;
+    }
+};
+
+// the sums of one LM pass at pose (R, t), reduced into every thread (s); red: LDS scratch of NW * LM_NV doubles that no thread
+// still reads (the caller alternates two such buffers, so one barrier per pass suffices).  A point with Z <= 0 (or a NaN) makes
+// the cost +inf / NaN, which no acceptance test passes.
+template <class PTS>
+__device__ inline void lm_pass(const PTS& pts, const Cam& cam, const double (&R)[9], const double (&t)[3], double* red,
+                               double (&s)[LM_NV]) {
+#pragma unroll
+    for (int c = 0; c < LM_NV; ++c) s[c] = 0.0;
+    for (int i = threadIdx.x; i < pts.n; i += NT) {
+        double X, Y, Z, uo, vo;
+        if (!pts.get(i, X, Y, Z, uo, vo)) continue;
+        const double qx = R[0] * X + R[1] * Y + R[2] * Z, qy = R[3] * X + R[4] * Y + R[5] * Z, qz = R[6] * X + R[7] * Y + R[8] * Z;
+        const double xc = qx + t[0], yc = qy + t[1], zc = qz + t[2];
+        const double iz = 1.0 / zc;
+        const double ru = cam.uc + cam.fu * xc * iz - uo, rv = cam.vc + cam.fv * yc * iz - vo;
+        const double a0 = cam.fu * iz, a2 = -cam.fu * xc * iz * iz;   // du/dPc = (a0, 0, a2)
+        const double b1 = cam.fv * iz, b2 = -cam.fv * yc * iz * iz;   // dv/dPc = (0, b1, b2)
+        const double ju[6] = {a2 * qy, a0 * qz - a2 * qx, -a0 * qy, a0, 0.0, a2};
+        const double jv[6] = {b2 * qy - b1 * qz, -b2 * qx, b1 * qx, 0.0, b1, b2};
+        int k = 0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int c = r; c < 6; ++c) s[k++] += ju[r] * ju[c] + jv[r] * jv[c];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) s[21 + r] += ju[r] * ru + jv[r] * rv;
+        s[27] += zc > 0.0 ? ru * ru + rv * rv : __builtin_inf();
+        s[28] += 1.0;
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < LM_NV; ++c) {
+        double x = s[c];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+        s[c] = x;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < LM_NV; ++c) red[wv * LM_NV + c] = s[c];
+    }
+    __syncthreads();
+    // lane c < LM_NV of every wave sums column c over the waves (w = 0..7), then the totals go round the wave (reading all
+    // 8 x 29 partials in every lane made the compiler keep them in flight at once, and spill)
+    double x = 0.0;
+    if (lane < LM_NV) {
+#pragma unroll
+        for (int w = 0; w < NW; ++w) x += red[w * LM_NV + lane];
+    }
+#pragma unroll
+    for (int c = 0; c < LM_NV; ++c) s[c] = __shfl(x, c);
+}
+
+// (A + lambda diag(A)) dx = -g by Cholesky, A given as its row-major upper triangle; false when the damped matrix is not
+// (numerically) positive definite
+__device__ inline bool lm_solve(const double* A, const double* g, double lambda, double (&dx)[6]) {
+    double L[6][6];
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c <= r; ++c) L[r][c] = A[c * 6 - c * (c - 1) / 2 + (r - c)] * (r == c ? 1.0 + lambda : 1.0);
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double d = L[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+        ok = ok && d > 0.0;
+        const double ljj = sqrt(d > 0.0 ? d : 1.0), il = 1.0 / ljj;
+        L[j][j] = ljj;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double x = L[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) x -= L[i][k] * L[j][k];
+            L[i][j] = x * il;
+        }
+    }
+    double y[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double x = -g[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) x -= L[i][k] * y[k];
+        y[i] = x / L[i][i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double x = y[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) x -= L[k][i] * dx[k];
+        dx[i] = x / L[i][i];
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) ok = ok && dx[i] - dx[i] == 0.0;   // finite
+    return ok;
+}
+
+// R <- cay(w) R, t <- t + v.  The Cayley map cay(w) = (I - [w/2]x)^-1 (I + [w/2]x) = I + 2 ([c]x + [c]x^2) / (1 + |c|^2), c = w / 2,
+// is a rotation (to rounding) that agrees with exp([w]x) to first order — the perturbation the Jacobian is taken for — and needs
+// no trigonometry (the fp64 sin / cos expansions more than doubled this code's register spills)
+__device__ inline void lm_apply(const double (&R)[9], const double (&t)[3], const double (&dx)[6], double (&Rn)[9], double (&tn)[3]) {
+    const double c0 = 0.5 * dx[0], c1 = 0.5 * dx[1], c2 = 0.5 * dx[2];
+    const double cc = c0 * c0 + c1 * c1 + c2 * c2, f = 2.0 / (1.0 + cc);
+    // E = I + f ([c]x + c c^T - |c|^2 I)
+    const double E[9] = {1.0 + f * (c0 * c0 - cc), f * (c0 * c1 - c2),       f * (c0 * c2 + c1),
+                         f * (c1 * c0 + c2),       1.0 + f * (c1 * c1 - cc), f * (c1 * c2 - c0),
+                         f * (c2 * c0 - c1),       f * (c2 * c1 + c0),       1.0 + f * (c2 * c2 - cc)};
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Rn[r * 3 + c] = E[r * 3] * R[c] + E[r * 3 + 1] * R[3 + c] + E[r * 3 + 2] * R[6 + c];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tn[k] = t[k] + dx[3 + k];
+}
+
+// The refinement, run by the whole workgroup with uniform control flow (every thread holds the same sums, see above).
+// red: 2 * NW * LM_NV doubles of LDS that no thread still reads.  In: the start pose (R, t) in every thread.  Out: the refined
+// pose, the RMS reprojection error over the points at the start and at the end (px), and the number of accepted steps.
+// Stopping rule (include/picopose_hip.h, pp_pnp_ransac_refine): lambda starts at 0 (the start is close to the minimum: a
+// Gauss-Newton step, which a damped step would shorten most along the weakly determined directions); an iteration solves the
+// damped system and evaluates the trial pose; it is accepted iff its cost is below the current one (every point with Z > 0),
+// then lambda /= 10, else lambda = max(10 lambda, 1e-3) (also when the damped system is not positive definite; no pass then).
+// The loop ends after max_iters iterations, after an accepted step with cost decrease <= eps * previous cost, or after a step with
+// |dx|_2 <= eps.  Skipped (pose unchanged, 0 iterations) when the set has fewer than 6 points or the start is not finite.
+template <class PTS>
+__device__ void lm_refine(const PTS& pts, const Cam& cam, double* red, int max_iters, double eps, double (&R)[9], double (&t)[3],
+                          double& rms0, double& rms1, int& accepted) {
+    double s[LM_NV];
+    lm_pass(pts, cam, R, t, red, s);
+    int buf = 1;
+    const double n = s[28];
+    double cost = s[27];
+    rms0 = n > 0.0 ? sqrt(cost / n) : 0.0;
+    rms1 = rms0;
+    accepted = 0;
+    bool finite = cost - cost == 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) finite = finite && R[k] - R[k] == 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) finite = finite && t[k] - t[k] == 0.0;
+    if (n < 6.0 || !finite) return;
+    double A[27];            // J^T J (21) and J^T r (6) at the current pose
+#pragma unroll
+    for (int k = 0; k < 27; ++k) A[k] = s[k];
+    double lambda = 0.0;
+    for (int it = 0; it < max_iters; ++it) {
+        double dx[6];
+        if (!lm_solve(A, A + 21, lambda, dx)) {
+            lambda = fmax(lambda * 10.0, 1e-3);
+            continue;
+        }
+        const double step = sqrt(dx[0] * dx[0] + dx[1] * dx[1] + dx[2] * dx[2] + dx[3] * dx[3] + dx[4] * dx[4] + dx[5] * dx[5]);
+        double Rn[9], tn[3];
+        lm_apply(R, t, dx, Rn, tn);
+        lm_pass(pts, cam, Rn, tn, red + buf * NW * LM_NV, s);
+        buf ^= 1;
+        if (s[27] < cost) {
+            const double dec = cost - s[27];
+            const bool small = dec <= eps * cost;
+            cost = s[27];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) R[k] = Rn[k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) t[k] = tn[k];
+#pragma unroll
+            for (int k = 0; k < 27; ++k) A[k] = s[k];
+            ++accepted;
+            lambda *= 0.1;
+            if (small || step <= eps) break;
+        } else {
+            lambda = fmax(lambda * 10.0, 1e-3);
+            if (step <= eps) break;
+        }
+    }
+    rms1 = sqrt(cost / n);
+}
+
 __device__ inline unsigned hash32(unsigned x) {
     x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
     return x;
 }
 
+// the outputs and settings of the refining instantiation (unused by pnp_ransac_kernel<false>)
+struct RefineArgs {
+    int max_iters;
+    double eps;
+    double* rms_before;      // (P)
+    double* rms_after;       // (P)
+    int32_t* iters;          // (P) accepted LM steps
+    uint8_t* mask;           // (P, N) consensus-set membership in gather order, or null
+};
+
 // One workgroup per problem.
 //   tar_pts_2d (P,2,H,W), src_pts_3d (P,3,H,W), K (P,3,3), tem_pose (P,4,4), tar_pts/src_pts (P,N,2) int64
 //   out: rot (P,9) f64, tvec (P,3) f64, ratio (P) f64, ok (P) int32, npts (P) int32
+// REFINE: the Levenberg-Marquardt tail after the refit (lm_refine on the consensus set) and the outputs of RefineArgs; the
+// <false> instantiation is the plain pp_pnp_ransac kernel.
+template <bool REFINE>
 __global__ __launch_bounds__(NT) void pnp_ransac_kernel(const float* __restrict__ tar2d, const float* __restrict__ src3d,
                                                         const float* __restrict__ Kmat, const float* __restrict__ tem_pose,
                                                         const int64_t* __restrict__ tar_pts, const int64_t* __restrict__ src_pts,
                                                         int H, int W, int N, int iters, float thresh, double* __restrict__ rot,
                                                         double* __restrict__ tvec, double* __restrict__ ratio,
                                                         int32_t* __restrict__ ok, int32_t* __restrict__ npts,
-                                                        double* __restrict__ dbg) {
+                                                        double* __restrict__ dbg, RefineArgs ra) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* p3 = (float*)smem;                      // [MAXP][3]
     float* p2 = p3 + 3 * MAXP;                     // [MAXP][2]
@@ -669,6 +893,13 @@ __global__ __launch_bounds__(NT) void pnp_ransac_kernel(const float* __restrict_
             tvec[(size_t)prob * 3] = 0.0; tvec[(size_t)prob * 3 + 1] = 0.0; tvec[(size_t)prob * 3 + 2] = 1.0;
             ratio[prob] = 0.0;
             ok[prob] = 0;
+            if constexpr (REFINE) {
+                ra.rms_before[prob] = 0.0; ra.rms_after[prob] = 0.0; ra.iters[prob] = 0;
+            }
+        }
+        if constexpr (REFINE) {
+            if (ra.mask)
+                for (int i = tid; i < N; i += NT) ra.mask[(size_t)prob * N + i] = 0;
         }
     };
     if (np < SAMPLE) { fail(); return; }
@@ -776,10 +1007,33 @@ __global__ __launch_bounds__(NT) void pnp_ransac_kernel(const float* __restrict_
         }
     }
     __syncthreads();
+    if constexpr (REFINE) {
+        if (ra.mask)
+            for (int i = tid; i < N; i += NT) ra.mask[(size_t)prob * N + i] = i < np ? use[i] : 0;
+    }
     // ---- refit on the inlier set (all threads cooperate, identical small algebra in every thread)
     PointSet<1> ps = {p3, p2, nullptr, use, np, red, nullptr};
     double R[9], t[3];
     const double e = epnp<1>(ps, cam, R, t, dbg ? dbg + (size_t)prob * 40 : nullptr);
+    if constexpr (REFINE) {
+        // start from the pose returned without refinement (the refit, else the RANSAC winner); the LM sums reuse the refit's
+        // reduction scratch `red` once every thread has read its last block sum
+        if (!(e < 1e299)) {
+            const double* M = hyp + best_h * 12;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) R[k] = M[k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) t[k] = M[9 + k];
+        }
+        __syncthreads();
+        const LdsPoints pts = {p3, p2, use, np};
+        double rms0, rms1;
+        int acc;
+        lm_refine(pts, cam, red, ra.max_iters, ra.eps, R, t, rms0, rms1, acc);
+        if (tid == 0) {
+            ra.rms_before[prob] = rms0; ra.rms_after[prob] = rms1; ra.iters[prob] = acc;
+        }
+    }
     if (tid == 0) {
         const bool good = e < 1e299;
         if (dbg) {   // the branch the refit kept: the first one of least error (-1: none, the RANSAC winner is returned)
@@ -787,34 +1041,69 @@ __global__ __launch_bounds__(NT) void pnp_ransac_kernel(const float* __restrict_
             d[39] = !good ? -1.0 : d[12] == e ? 0.0 : d[25] == e ? 1.0 : 2.0;
         }
         const double* M = hyp + best_h * 12;
-        for (int k = 0; k < 9; ++k) rot[(size_t)prob * 9 + k] = good ? R[k] : M[k];
-        for (int k = 0; k < 3; ++k) tvec[(size_t)prob * 3 + k] = good ? t[k] : M[9 + k];
+        // (REFINE: R, t hold the refined pose, whichever start it had)
+        for (int k = 0; k < 9; ++k) rot[(size_t)prob * 9 + k] = (REFINE || good) ? R[k] : M[k];
+        for (int k = 0; k < 3; ++k) tvec[(size_t)prob * 3 + k] = (REFINE || good) ? t[k] : M[9 + k];
         ratio[prob] = (double)best_c / (double)np;
         ok[prob] = 1;
     }
 }
 
+// pp_pnp_refine_lm: one workgroup per problem, the same lm_refine on the problem's first count[p] (clamped to [0, Nmax]) rows,
+// read from global memory in every pass (at most 4096 x 40 bytes a problem: they stay in the caches)
+__global__ __launch_bounds__(NT) void pnp_refine_lm_kernel(const double* __restrict__ obj, const double* __restrict__ img,
+                                                           const int32_t* __restrict__ count, const double* __restrict__ Kmat,
+                                                           const double* rot0, const double* tvec0, int Nmax, int max_iters,
+                                                           double eps, double* rot, double* tvec, double* __restrict__ rms_before,
+                                                           double* __restrict__ rms_after, int32_t* __restrict__ iters) {
+    __shared__ double red[2 * NW * LM_NV];
+    const int prob = blockIdx.x;
+    int n = count[prob];
+    n = n < 0 ? 0 : n > Nmax ? Nmax : n;
+    const double* Kp = Kmat + (size_t)prob * 9;
+    const Cam cam = {Kp[0], Kp[4], Kp[2], Kp[5]};
+    double R[9], t[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = rot0[(size_t)prob * 9 + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = tvec0[(size_t)prob * 3 + k];
+    const GlobalPoints pts = {obj + (size_t)prob * Nmax * 3, img + (size_t)prob * Nmax * 2, n};
+    double rms0, rms1;
+    int acc;
+    lm_refine(pts, cam, red, max_iters, eps, R, t, rms0, rms1, acc);   // (its barriers order every read of rot0 / tvec0 before
+    if (threadIdx.x == 0) {                                            //  these writes: the two may alias)
+        for (int k = 0; k < 9; ++k) rot[(size_t)prob * 9 + k] = R[k];
+        for (int k = 0; k < 3; ++k) tvec[(size_t)prob * 3 + k] = t[k];
+        rms_before[prob] = rms0;
+        rms_after[prob] = rms1;
+        iters[prob] = acc;
+    }
+}
+
 }  // namespace
 
+template <bool REFINE>
 static int pnp_launch(const float* tar_pts_2d, const float* src_pts_3d, const float* K, const float* tem_pose,
                       const int64_t* tar_pts, const int64_t* src_pts, int P, int H, int W, int N, int iterations,
                       float reproj_threshold, double* rot, double* tvec, double* inlier_ratio, int32_t* success,
-                      int32_t* num_points, double* dbg, void* stream) {
+                      int32_t* num_points, double* dbg, const RefineArgs& ra, void* stream) {
     if (!tar_pts_2d || !src_pts_3d || !K || !tem_pose || !tar_pts || !src_pts || !rot || !tvec || !inlier_ratio ||
         !success || !num_points)
         return PP_EINVAL;
     if (P <= 0 || H <= 0 || W <= 0 || N <= 0 || N > MAXP || iterations <= 0 || reproj_threshold <= 0.f) return PP_EINVAL;
+    if (REFINE && (!ra.rms_before || !ra.rms_after || !ra.iters || ra.max_iters <= 0 || !(ra.eps >= 0.0))) return PP_EINVAL;
     static_assert(HB * 48 >= NW * 144, "the refit's reduction scratch aliases the null-space vector buffer");
+    static_assert(NW * 144 >= 2 * NW * LM_NV, "the LM sums reuse the refit's reduction scratch");
     const size_t smem = (size_t)MAXP * (3 + 2) * sizeof(float) + MAXP + (size_t)HB * 48 * sizeof(double) +
                         (size_t)MAXH * 12 * sizeof(double) + MAXH * sizeof(int);
-    static bool attr_set[PP_MAX_DEVICES];   // the dynamic-LDS opt-in is per device
+    static bool attr_set[PP_MAX_DEVICES];   // the dynamic-LDS opt-in is per device (and per instantiation)
     if (!attr_set[pp_cur_device()]) {
-        PP_CHECK_HIP(hipFuncSetAttribute((const void*)pnp_ransac_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        PP_CHECK_HIP(hipFuncSetAttribute((const void*)pnp_ransac_kernel<REFINE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
         attr_set[pp_cur_device()] = true;
     }
-    hipLaunchKernelGGL(pnp_ransac_kernel, dim3(P), dim3(NT), smem, (hipStream_t)stream, tar_pts_2d, src_pts_3d, K,
+    hipLaunchKernelGGL(pnp_ransac_kernel<REFINE>, dim3(P), dim3(NT), smem, (hipStream_t)stream, tar_pts_2d, src_pts_3d, K,
                        tem_pose, tar_pts, src_pts, H, W, N, iterations, reproj_threshold, rot, tvec, inlier_ratio,
-                       success, num_points, dbg);
+                       success, num_points, dbg, ra);
     return pp_last_launch();
 }
 
@@ -824,8 +1113,8 @@ int pp_pnp_ransac(const float* tar_pts_2d, const float* src_pts_3d, const float*
                   const int64_t* tar_pts, const int64_t* src_pts, int P, int H, int W, int N, int iterations,
                   float reproj_threshold, double* rot, double* tvec, double* inlier_ratio, int32_t* success,
                   int32_t* num_points, void* stream) {
-    return pnp_launch(tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts, P, H, W, N, iterations, reproj_threshold, rot, tvec,
-                      inlier_ratio, success, num_points, nullptr, stream);
+    return pnp_launch<false>(tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts, P, H, W, N, iterations, reproj_threshold, rot,
+                             tvec, inlier_ratio, success, num_points, nullptr, RefineArgs{}, stream);
 }
 
 int pp_pnp_ransac_debug(const float* tar_pts_2d, const float* src_pts_3d, const float* K, const float* tem_pose,
@@ -833,8 +1122,30 @@ int pp_pnp_ransac_debug(const float* tar_pts_2d, const float* src_pts_3d, const 
                         float reproj_threshold, double* rot, double* tvec, double* inlier_ratio, int32_t* success,
                         int32_t* num_points, double* refit_branches, void* stream) {
     if (!refit_branches) return PP_EINVAL;
-    return pnp_launch(tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts, P, H, W, N, iterations, reproj_threshold, rot, tvec,
-                      inlier_ratio, success, num_points, refit_branches, stream);
+    return pnp_launch<false>(tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts, P, H, W, N, iterations, reproj_threshold, rot,
+                             tvec, inlier_ratio, success, num_points, refit_branches, RefineArgs{}, stream);
+}
+
+int pp_pnp_ransac_refine(const float* tar_pts_2d, const float* src_pts_3d, const float* K, const float* tem_pose,
+                         const int64_t* tar_pts, const int64_t* src_pts, int P, int H, int W, int N, int iterations,
+                         float reproj_threshold, int max_iters, double eps, double* rot, double* tvec, double* inlier_ratio,
+                         int32_t* success, int32_t* num_points, double* rms_before, double* rms_after, int32_t* lm_iterations,
+                         uint8_t* inlier_mask, void* stream) {
+    const RefineArgs ra = {max_iters, eps, rms_before, rms_after, lm_iterations, inlier_mask};
+    return pnp_launch<true>(tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts, P, H, W, N, iterations, reproj_threshold, rot,
+                            tvec, inlier_ratio, success, num_points, nullptr, ra, stream);
+}
+
+int pp_pnp_refine_lm(const double* object_points, const double* image_points, const int32_t* count, const double* K,
+                     const double* rot_init, const double* tvec_init, int P, int Nmax, int max_iters, double eps, double* rot,
+                     double* tvec, double* rms_before, double* rms_after, int32_t* lm_iterations, void* stream) {
+    if (!object_points || !image_points || !count || !K || !rot_init || !tvec_init || !rot || !tvec || !rms_before || !rms_after ||
+        !lm_iterations)
+        return PP_EINVAL;
+    if (P <= 0 || Nmax <= 0 || Nmax > MAXP || max_iters <= 0 || !(eps >= 0.0)) return PP_EINVAL;
+    hipLaunchKernelGGL(pnp_refine_lm_kernel, dim3(P), dim3(NT), 0, (hipStream_t)stream, object_points, image_points, count, K,
+                       rot_init, tvec_init, Nmax, max_iters, eps, rot, tvec, rms_before, rms_after, lm_iterations);
+    return pp_last_launch();
 }
 
 }  // extern "C"

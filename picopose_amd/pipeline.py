@@ -8,12 +8,16 @@ PicoPoseHipError of pose_recovery.py.  "exact": a snapshot of the word is taken 
 (ops.saturation_take), travels with the batch's poses, and a set snapshot re-runs that mini-batch alone in strict fp32 (Net.precision = "f32",
 match_mode = "exact") — its poses are then the f32 network's, the other mini-batches keep the fast mode's; net.range_fallbacks counts the
 re-runs.  The snapshot is taken from the word of the batch's own device, so several devices keep separate verdicts (by construction: the
-tests have one GPU)."""
+tests have one GPU).
+
+pnp_refine: None (default) | "lm" — the batched PnP refines each pose by Levenberg-Marquardt on its RANSAC consensus set
+(utils/pose_recovery.py, refine="lm").  Only R and t move: the inlier ratios, the success flags and therefore the order of the
+hypotheses are those of pnp_refine=None."""
 import numpy as np
 import torch
 
 from . import ops
-from .utils.pose_recovery import pose_recovery_ransac_pnp_batched
+from .utils.pose_recovery import check_refine, pose_recovery_ransac_pnp_batched
 
 ON_SATURATION = ("raise", "exact")
 
@@ -26,28 +30,31 @@ def pnp_inputs(outputs, real_K):
             cat("pred_src_pts"))
 
 
-def pnp_for_outputs(outputs, real_K, return_npts=False, sat_slot=None):
+def pnp_for_outputs(outputs, real_K, return_npts=False, sat_slot=None, pnp_refine=None):
     """outputs: list (hyp) of Net.forward dicts; real_K (B,3,3) -> rot (hyp,B,3,3), tvec (hyp,B,3,1), ratio, ok
-    [+ npts (hyp,B): correspondences each problem received] [+ saturated (bool): the forward's snapshot `sat_slot` was set]."""
+    [+ npts (hyp,B): correspondences each problem received] [+ saturated (bool): the forward's snapshot `sat_slot` was set].
+    pnp_refine="lm": rot / tvec are the refined poses (module docstring); ratio, ok and npts are pnp_refine=None's."""
     hyp, B = len(outputs), outputs[0]["pred_poses"].shape[0]
-    res = pose_recovery_ransac_pnp_batched(*pnp_inputs(outputs, real_K), return_npts=return_npts, sat_slot=sat_slot)
+    res = pose_recovery_ransac_pnp_batched(*pnp_inputs(outputs, real_K), return_npts=return_npts, sat_slot=sat_slot, refine=pnp_refine)
     rot, tvec, ratio, ok = res[:4]
     out = (rot.reshape(hyp, B, 3, 3), tvec.reshape(hyp, B, 3, 1), ratio.reshape(hyp, B), ok.reshape(hyp, B))
     out = out + (res[4].reshape(hyp, B),) if return_npts else out
     return out + (res[-1],) if sat_slot is not None else out
 
 
-def pnp_for_outputs_async(outputs, real_K, host=None, stream=None, sat_slot=None):
+def pnp_for_outputs_async(outputs, real_K, host=None, stream=None, sat_slot=None, pnp_refine=None):
     """pnp_for_outputs without the host wait -> handle; `pnp_collect(handle, hyp, B)` reads it (one batch later in a serving loop).
     stream: run the PnP launch and the copy on this side stream, beside the next batch's forward (pose_recovery_ransac_pnp_batched_async).
-    sat_slot: the forward's saturation snapshot rides in the copy; `handle.saturated` holds it after pnp_collect."""
+    sat_slot: the forward's saturation snapshot rides in the copy; `handle.saturated` holds it after pnp_collect.
+    pnp_refine: as pnp_for_outputs."""
     from .utils.pose_recovery import pose_recovery_ransac_pnp_batched_async
 
-    return pose_recovery_ransac_pnp_batched_async(*pnp_inputs(outputs, real_K), host=host, stream=stream, sat_slot=sat_slot)
+    return pose_recovery_ransac_pnp_batched_async(*pnp_inputs(outputs, real_K), host=host, stream=stream, sat_slot=sat_slot,
+                                                  refine=pnp_refine)
 
 
 def pnp_collect(handle, hyp, B):
-    rot, tvec, ratio, ok = handle.result()
+    rot, tvec, ratio, ok = handle.result()[:4]     # (a refining launch appends its refine_stats)
     return rot.reshape(hyp, B, 3, 3), tvec.reshape(hyp, B, 3, 1), ratio.reshape(hyp, B), ok.reshape(hyp, B)
 
 
@@ -78,17 +85,23 @@ def _new_slot(device):
     return torch.zeros(1, dtype=torch.int32, device=device)
 
 
-def _pnp_checked(outputs, real_K, slot, pnp_fn):
+def _check_pnp_refine(pnp_refine, pnp_fn):
+    check_refine(pnp_refine)
+    if pnp_refine is not None and pnp_fn is not None:
+        raise ValueError("pnp_refine applies to the batched HIP PnP, not to an injected pnp_fn")
+
+
+def _pnp_checked(outputs, real_K, slot, pnp_fn, pnp_refine=None):
     """PnP of a forward whose saturation snapshot is `slot` -> ((rot, tvec, ratio, ok), saturated)."""
     if pnp_fn is None:
-        *res, saturated = pnp_for_outputs(outputs, real_K, sat_slot=slot)
+        *res, saturated = pnp_for_outputs(outputs, real_K, sat_slot=slot, pnp_refine=pnp_refine)
         return tuple(res), saturated
     return pnp_fn(outputs, real_K), bool(slot.item())       # (an injected PnP: the slot is read on its own)
 
 
-def _forward_exact(net, end_points, hyp, pnp_fn=None):
+def _forward_exact(net, end_points, hyp, pnp_fn=None, pnp_refine=None):
     """The fallback: one mini-batch again, alone (no look-ahead), in strict fp32 -> (outputs, (rot, tvec, ratio, ok)).  The mode is the
-    model's own for this call (Net.precision): the global ops.PRECISION is not touched."""
+    model's own for this call (Net.precision): the global ops.PRECISION is not touched.  Its PnP refines as the batch's would (pnp_refine)."""
     net.range_fallbacks += 1
     prev = net.precision, net.match_mode
     net.precision, net.match_mode = "f32", "exact"
@@ -97,35 +110,42 @@ def _forward_exact(net, end_points, hyp, pnp_fn=None):
     finally:
         net.precision, net.match_mode = prev
     dev = end_points["real_rgb"].device
-    pnp, saturated = _pnp_checked(outputs, end_points["real_K"], ops.saturation_take(dev, _new_slot(dev)), pnp_fn)
+    pnp, saturated = _pnp_checked(outputs, end_points["real_K"], ops.saturation_take(dev, _new_slot(dev)), pnp_fn, pnp_refine)
     if saturated:      # (fp32 has no operand format to leave: nothing is left to fall back to)
         raise ops.saturation_error("the strict-fp32 re-run of a mini-batch")
     return outputs, pnp
 
 
-def infer_batch(net, end_points, hyp=5, pnp_fn=None, on_saturation="raise"):
+def infer_batch(net, end_points, hyp=5, pnp_fn=None, on_saturation="raise", pnp_refine=None):
     """-> per-instance pose hypotheses sorted by inlier ratio (run_test.py:168-186):
     list over instances of list over hypotheses of dict(R (3,3), t (3,), inliers_ratio, pnp_success).
     pnp_fn(outputs, real_K) -> (rot (hyp,B,3,3), tvec (hyp,B,3,1), ratio (hyp,B), ok (hyp,B)) replaces the batched HIP
     PnP (tests of the loop semantics inject canned answers).
-    on_saturation: "raise" | "exact" (module docstring): with "exact" a forward that clamped an operand is run again in strict fp32."""
+    on_saturation: "raise" | "exact" (module docstring): with "exact" a forward that clamped an operand is run again in strict fp32.
+    pnp_refine: None | "lm" (module docstring): the poses are refined on their consensus sets; the hypothesis order stays the inlier
+    ratio's of pnp_refine=None.  ValueError, before any device work, for another value or with pnp_fn."""
+    _check_pnp_refine(pnp_refine, pnp_fn)
     if not _check_on_saturation(on_saturation):
         outputs = net(end_points, hyp)
-        rot, tvec, ratio, ok = (pnp_fn or pnp_for_outputs)(outputs, end_points["real_K"])
+        if pnp_fn is not None:
+            rot, tvec, ratio, ok = pnp_fn(outputs, end_points["real_K"])
+        else:
+            rot, tvec, ratio, ok = pnp_for_outputs(outputs, end_points["real_K"], pnp_refine=pnp_refine)
     else:
         dev = end_points["real_rgb"].device
         ops.saturation_word(dev)            # (registered before the first producer of this device runs)
         net._query_stash = None             # this forward computes its own query ViT: the snapshot then covers all of this batch
         outputs = net(end_points, hyp)
-        (rot, tvec, ratio, ok), saturated = _pnp_checked(outputs, end_points["real_K"], ops.saturation_take(dev, _new_slot(dev)), pnp_fn)
+        (rot, tvec, ratio, ok), saturated = _pnp_checked(outputs, end_points["real_K"], ops.saturation_take(dev, _new_slot(dev)), pnp_fn,
+                                                         pnp_refine)
         if saturated:
-            outputs, (rot, tvec, ratio, ok) = _forward_exact(net, end_points, hyp, pnp_fn)
+            outputs, (rot, tvec, ratio, ok) = _forward_exact(net, end_points, hyp, pnp_fn, pnp_refine)
     stage2 = np.stack([o["pred_poses"].cpu().numpy() for o in outputs])            # (hyp,B,4,4) float32
     return _rank_hypotheses(stage2, rot, tvec, ratio, ok, hyp)
 
 
 def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=True, next_data=None, on_saturation="raise",
-                indexed_bank=False):
+                indexed_bank=False, pnp_refine=None):
     """One test image exactly as run_test.py:141-188 walks it: `data` holds the image's instances on dim 1
     (data[key][0] = (n_instance, ...), plus 'obj_idx'), `templates_data[key]` the per-object template bank
     ((n_objects, N, ...), including 'template_feature' and, optionally, an extended bank under 'template_cache').
@@ -143,7 +163,9 @@ def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=
     it reads mini-batch j; a flagged j is re-run synchronously when it is read, and preds_image keeps the instance order.
     indexed_bank: the per-object tensors of `templates_data` go to the network as they are, and each instance names its object
     (end_points["template_index"] = its obj_idx): no copy of the bank per instance (run_test.py:159-162 makes one: ~308 MB per detection at
-    ViT-L, 162 views), and a template shared by several instances is streamed once by stage 1.  Same results as the default."""
+    ViT-L, 162 views), and a template shared by several instances is streamed once by stage 1.  Same results as the default.
+    pnp_refine: None | "lm" (module docstring), for both walks and for the strict-fp32 re-runs; the hypothesis order does not change."""
+    _check_pnp_refine(pnp_refine, pnp_fn)
     exact = _check_on_saturation(on_saturation)
     n_instance = data["score"].shape[1]
     preds_image = []
@@ -168,7 +190,8 @@ def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=
 
     if pnp_fn is not None or not pipelined:
         for start in range(0, n_instance, bs):
-            emit(infer_batch(net, inputs_of(start, min(start + bs, n_instance)), hyp, pnp_fn=pnp_fn, on_saturation=on_saturation))
+            emit(infer_batch(net, inputs_of(start, min(start + bs, n_instance)), hyp, pnp_fn=pnp_fn, on_saturation=on_saturation,
+                             pnp_refine=pnp_refine))
         return preds_image
     pending = None      # (PnP handle, pinned stage-2 poses, their event, batch size, inputs) of the mini-batch in flight
     starts = list(range(0, n_instance, bs))
@@ -189,26 +212,26 @@ def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=
             nxt = None
         outputs = net(inputs, hyp, next_real_rgb=nxt) if nxt is not None else net(inputs, hyp)
         slot = ops.saturation_take(dev, _new_slot(dev)) if exact else None       # this forward's verdict, in stream order
-        handle = pnp_for_outputs_async(outputs, inputs["real_K"], sat_slot=slot)
+        handle = pnp_for_outputs_async(outputs, inputs["real_K"], sat_slot=slot, pnp_refine=pnp_refine)
         s2 = torch.stack([o["pred_poses"] for o in outputs])                        # (hyp,B,4,4) float32
         s2_host = torch.empty(s2.shape, dtype=s2.dtype, pin_memory=True)
         s2_host.copy_(s2, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         if pending is not None:
-            emit(_collect(pending, hyp, net))
+            emit(_collect(pending, hyp, net, pnp_refine))
         pending = (handle, s2_host, ev, s2.shape[1], inputs if exact else None)
     if pending is not None:
-        emit(_collect(pending, hyp, net))
+        emit(_collect(pending, hyp, net, pnp_refine))
     return preds_image
 
 
-def _collect(pending, hyp, net):
+def _collect(pending, hyp, net, pnp_refine=None):
     handle, s2_host, ev, B, inputs = pending
     rot, tvec, ratio, ok = pnp_collect(handle, hyp, B)
     ev.synchronize()
     if handle.saturated:    # (on_saturation="exact" only: the snapshot of this mini-batch's forward was set)
-        outputs, (rot, tvec, ratio, ok) = _forward_exact(net, inputs, hyp)
+        outputs, (rot, tvec, ratio, ok) = _forward_exact(net, inputs, hyp, pnp_refine=pnp_refine)
         return _rank_hypotheses(np.stack([o["pred_poses"].cpu().numpy() for o in outputs]), rot, tvec, ratio, ok, hyp)
     return _rank_hypotheses(s2_host.numpy(), rot, tvec, ratio, ok, hyp)
 
