@@ -737,6 +737,58 @@ int pp_adam_workspace_bytes(const PpAdamTensor* tensors, int ntensors, size_t* b
 int pp_adam_multi_tensor(const PpAdamTensor* tensors, int ntensors, const PpAdamStep* steps, int terms, int rebuild, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Training-pair assembly (provider/training_dataset.py:173-316; picopose_amd/provider/training_batch.py plans every call).
+ *
+ * Frames: buffer 0 = real views, (H_f, W_f, 3) uint8 RGB as load_im gives it plus the visible mask (H_f, W_f) uint8;
+ * buffer 1 = template views, (H_f, W_f, 4) RGBA.  Crops live in two ragged "ping-pong" buffers of 4-byte pixels, the colour
+ * BGR-ordered (image[..., ::-1]) and byte 3 the mask / alpha, carried along.
+ *
+ * images: n_images descriptors of PP_AUG_IMG_WORDS int32:
+ *   [0] frame buffer (0: frames0, 1: frames1)  [1] pixel offset of the frame  [2] W_f  [3] y1  [4] x1  [5] h  [6] w
+ *   [7] pixel offset of the crop in the ragged buffers  [8] seed (uint32 bits)  [9] index of the image's first op record
+ *   [10] nseg = passes the image takes (1..4)  [11 + s] first op of pass s, s = 0..nseg ([11 + nseg] = op count)
+ *   [16] mask mode (0: real, mask value out; 1: alpha, out = (alpha == 255))  [17..19] 0
+ * ops: records of PP_AUG_OP_WORDS int32, word 0 the recipe row (1..13), then (floats as their bit patterns):
+ *   1 CoarseDropout: -               2 GaussianBlur: radius, taps q0..q4 (sum q0 + 2 (q1..q4) = 256), sigma
+ *   3-6 Sharpness / Contrast / Brightness / Color: factor   7 Add: three ints   8 Invert: three 0/1 flags
+ *   9, 10 Multiply: three factors    11 AdditiveGaussianNoise: -   12 LinearContrast: three alphas   13 Grayscale: alpha
+ * Pass s > 0 of an image starts with its Blur, Sharpness or Contrast op and runs the pointwise ops up to the next one; pass 0
+ * crops the frame.  Pass p writes buf0 when p is even, buf1 when odd; an image's result is in buffer (nseg - 1) & 1.
+ * Random ops use the counter-based hash h(seed, a, b) = mix(seed ^ mix(a ^ mix(b + 0x9e3779b9))), mix = the
+ * "lowbias32" finalizer (x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16):
+ *   dropout drops cell c (grid max(h*5/100, 3) x max(w*5/100, 3), nearest) when h(seed, c, 0xd0) < PP_AUG_DROP_THRESHOLD;
+ *   noise of pixel p (= y w + x), channel c is ((2 sum of the 12 bytes of h(seed, 3p + c, k), k < 3) - 3060) * 10 + 256) >> 9
+ *   (an Irwin-Hall sum scaled to std ~10, not a true normal and not imgaug's stream).
+ * ------------------------------------------------------------------------- */
+#define PP_AUG_OP_WORDS 8
+#define PP_AUG_IMG_WORDS 20
+#define PP_AUG_MAX_OPS 13
+#define PP_AUG_MAX_PASSES 4
+#define PP_AUG_DROP_THRESHOLD 858993459u /* 0.2 * 2^32 */
+/* Runs every pass: tiles = int4 {image, y0, x0, 0} of 16 x 16 pixels, pass p's tiles at [pass_tiles[p], pass_tiles[p+1])
+ * (pass_tiles: HOST array of n_passes + 1 ints, pass_tiles[0] = 0, pass 0 non-empty); n_frame*_px / n_buf_px: uchar4 counts
+ * of the buffers (descriptors outside them are skipped); lsum: n_images uint32 workspace (zeroed here). */
+int pp_augment_execute(const unsigned char* rgb0, const unsigned char* mask0, long long n_frame0_px, const unsigned char* rgba1,
+                       long long n_frame1_px,
+                       const int* images, int n_images, const int* ops, int n_ops, const int* tiles, const int* pass_tiles,
+                       int n_passes, unsigned char* buf0, unsigned char* buf1, long long n_buf_px, unsigned int* lsum,
+                       void* stream);
+/* The executor's results -> out_rgb (n_images, 3, S, S) fp32 = Normalize(resize(crop [* (mask > 0) if rgb_mask_flag]) / 255)
+ * in double, out_mask (n_images, S, S) fp32 = INTER_NEAREST of the mask byte.  The resize is OpenCV's cv::resize on CV_8U,
+ * INTER_LINEAR fixed-point path in its scalar form (11-bit coefficients saturate_cast<short>((1 - f) 2048), integer
+ * horizontal pass, (v + 2^21) >> 22 vertical; the SIMD vertical pass of OpenCV rounds in two steps and may differ by 1 LSB),
+ * switching to INTER_AREA ((a + b + c + d + 2) >> 2) for an exact 2x downscale (h = w = 2 S).  mean3 / std3: host. */
+int pp_augment_resize(const unsigned char* buf0, const unsigned char* buf1, long long n_buf_px, const int* images, int n_images,
+                      int S, int rgb_mask_flag, const double* mean3, const double* std3, float* out_rgb, float* out_mask,
+                      void* stream);
+/* real depth (training_dataset.py:227-228): out = f32(d) * scale[frame] / 1000 in float32; depth (n_frames, n_per_frame)
+ * uint16 (8-byte aligned), scale: device fp32 per frame, out 16-byte aligned. */
+int pp_depth_u16_scaled(const unsigned short* depth, long long n_per_frame, int n_frames, const float* scale, float* out,
+                        void* stream);
+/* template depth (training_dataset.py:294): out = (float)(d * 0.1 / 1000.0) in double. */
+int pp_depth_u16_template(const unsigned short* depth, long long n, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

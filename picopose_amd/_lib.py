@@ -208,6 +208,10 @@ def lib():
         L.pp_flow_loss_backward.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
         L.pp_adam_workspace_bytes.argtypes = [c.POINTER(PpAdamTensor), i32, c.POINTER(sz)]
         L.pp_adam_multi_tensor.argtypes = [c.POINTER(PpAdamTensor), i32, vp, i32, i32, vp, sz, vp]
+        L.pp_augment_execute.argtypes = [vp, vp, ll, vp, ll, vp, i32, vp, i32, vp, c.POINTER(i32), i32, vp, vp, ll, vp, vp]
+        L.pp_augment_resize.argtypes = [vp, vp, ll, vp, i32, i32, i32, c.POINTER(c.c_double), c.POINTER(c.c_double), vp, vp, vp]
+        L.pp_depth_u16_scaled.argtypes = [vp, ll, i32, vp, vp, vp]
+        L.pp_depth_u16_template.argtypes = [vp, ll, vp, vp]
         _lib = L
     return _lib
 
