@@ -789,6 +789,25 @@ int pp_depth_u16_scaled(const unsigned short* depth, long long n_per_frame, int 
 /* template depth (training_dataset.py:294): out = (float)(d * 0.1 / 1000.0) in double. */
 int pp_depth_u16_template(const unsigned short* depth, long long n, float* out, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Detection batch of one test image (provider/bop_test_dataset.py:112-207; picopose_amd/provider/test_batch.py plans the call):
+ * pp_crop_resize_normalize for n detections of one frame in one launch, the masks given as COCO run lengths instead of frames.
+ *
+ * image (H, W, 3) uint8 as loaded (H * W < 2^31).  run_ends: the detections' cumulative run ends, concatenated — detection d owns
+ * run_ends[run_offset[d] .. run_offset[d + 1]), the inclusive prefix sums of its COCO counts (column-major over (H, W), runs
+ * alternate 0-run, 1-run, ..., so they are non-decreasing and the last one is H * W).  Pixel (y, x) is in the mask when an odd
+ * number of ends are <= x * H + y.  window[d] = {y1, y2, x1, x2}: crop rows [y1, y2), columns [x1, x2).
+ * out_rgb (n, 3, S, S), out_mask (n, S, S) fp32: per detection exactly what pp_crop_resize_normalize writes for the decoded mask
+ * (same arithmetic, bit for bit); mean3 / std3 host pointers.
+ * run_ends, run_offset (n + 1 ints) and window (4 n ints) are device pointers; run_offset_host / window_host are the HOST copies
+ * of the two tables, validated here before the launch.  PP_EINVAL: a null pointer, n <= 0 or > 65535, S <= 0 or > 4096, n_runs <= 0,
+ * H * W >= 2^31, run_offset_host decreasing, negative or past n_runs, a window that is empty or leaves the frame.  A workgroup
+ * stages the ends that touch its source columns in LDS when they are at most 2048, and searches global memory otherwise.
+ * ------------------------------------------------------------------------- */
+int pp_detections_crop(const unsigned char* image, int H, int W, const int* run_ends, int n_runs, const int* run_offset,
+                       const int* window, const int* run_offset_host, const int* window_host, int n, int S, int rgb_mask_flag,
+                       const double* mean3, const double* std3, float* out_rgb, float* out_mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -212,6 +212,8 @@ def lib():
         L.pp_augment_resize.argtypes = [vp, vp, ll, vp, i32, i32, i32, c.POINTER(c.c_double), c.POINTER(c.c_double), vp, vp, vp]
         L.pp_depth_u16_scaled.argtypes = [vp, ll, i32, vp, vp, vp]
         L.pp_depth_u16_template.argtypes = [vp, ll, vp, vp]
+        L.pp_detections_crop.argtypes = [vp, i32, i32, vp, i32, vp, vp, c.POINTER(i32), c.POINTER(i32), i32, i32, i32,
+                                         c.POINTER(c.c_double), c.POINTER(c.c_double), vp, vp, vp]
         _lib = L
     return _lib
 

@@ -226,6 +226,21 @@ def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=
     return preds_image
 
 
+ASSEMBLE_KEYS = ("scene_id", "img_id", "seg_filter_score", "img_size", "pts_size", "minimum_n_point", "rgb_mask_flag", "device", "stream")
+
+
+def infer_detections(net, image_u8, detections, K, templates_data, obj_idxs, **kw):
+    """One decoded test image and its CNOS detection records -> (preds_image, data): provider.test_batch.assemble_test_image
+    (the keywords of ASSEMBLE_KEYS go there; scene_id and img_id are required), then infer_image on its `data` with the
+    remaining keywords.  ([], None) when no detection passes the score filter."""
+    from .provider.test_batch import assemble_test_image
+
+    data = assemble_test_image(image_u8, detections, K, obj_idxs, **{k: kw.pop(k) for k in ASSEMBLE_KEYS if k in kw})
+    if data is None:
+        return [], None
+    return infer_image(net, data, templates_data, **kw), data
+
+
 def _collect(pending, hyp, net, pnp_refine=None):
     handle, s2_host, ev, B, inputs = pending
     rot, tvec, ratio, ok = pnp_collect(handle, hyp, B)

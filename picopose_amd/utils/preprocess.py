@@ -4,7 +4,9 @@ utils/data_utils.py:131-196, 231-250 on the device.
 The bounding-box arithmetic, the crop affine `M`, the 64x64 lookup grid `pts2d`, the channel flip and the CLIP
 normalisation give the reference's values (boxes pinned by reference-generated fixtures, tests/golden/preprocess_boxes.npz); the two `cv2.resize` calls run in `pp_crop_resize_normalize`
 (OpenCV's published INTER_LINEAR / INTER_NEAREST definitions; cv2 is not available here to pin them bit-for-bit).
-File IO (image / RLE decoding) stays with the caller."""
+File IO (image decoding) stays with the caller; `crop_instance` takes a decoded full-frame mask.  A whole image's detections
+go from their RLE records to the collated batch, without decoding a mask, through provider/test_batch.py
+(`assemble_test_image`), which reproduces `crop_instance`'s outputs bit for bit."""
 import ctypes
 
 import numpy as np
