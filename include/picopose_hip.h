@@ -808,6 +808,66 @@ int pp_detections_crop(const unsigned char* image, int H, int W, const int* run_
                        const int* window, const int* run_offset_host, const int* window_host, int n, int S, int rgb_mask_flag,
                        const double* mean3, const double* std3, float* out_rgb, float* out_mask, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Template rendering: a mesh to its rendered template views and their bank entries (picopose_amd/provider/template_bank.py plans
+ * every call).  Replaces the offline renderer rendering/src/custom_megapose/call_panda3d.py:48-98 (ambient light of colour 1:
+ * a pixel is the surface colour, unshaded; K and the 480 x 640 frame of :48-54; RGBA + 16-bit depth in mm of :87-98) for
+ * vertex-coloured meshes.  Parity with Panda3D / BlenderProc pixels is UNPINNED (neither can be run next to this library);
+ * the conventions below are the places where it could differ.
+ *
+ * THE RASTER CONTRACT (tests/render_oracle.py restates it in numpy; the kernels equal it bit for bit).  All float operations
+ * are IEEE float32, one rounding each, never contracted, in the order written.
+ *  1. Camera space of vertex (X, Y, Z) under the row-major pose P (4, 4) (object -> camera, t in the vertices' unit):
+ *       Xc = ((P00 X + P01 Y) + P02 Z) + P03, Yc and Zc likewise from rows 1 and 2.
+ *     A triangle with a vertex whose Zc > near is false is dropped whole and counted in *near_count (no geometric clipping).
+ *  2. Projection u = (fx Xc) / Zc + cx, v = (fy Yc) / Zc + cy.  Pixel (x, y) is sampled at (u, v) = (x, y): integer coordinates
+ *     are pixel centres — the convention of get_point_cloud_from_depth (utils/data_utils.py:97-115), so a rendered depth
+ *     back-projects onto the surface point that produced it.  (Whether Panda3D samples at x or x + 1/2 is unpinned.)
+ *  3. Snap: xs = (int) rint(clamp(256 u, -2^28, 2^28)) (round half to even), ys likewise: 1/256 pixel fixed point.
+ *  4. area2 = (xs1 - xs0)(ys2 - ys0) - (ys1 - ys0)(xs2 - xs0) in 64-bit integers.  area2 = 0: the triangle covers nothing.
+ *     area2 < 0: vertices 1 and 2 are exchanged (both windings are drawn, there is no back-face culling), so area2 > 0 below.
+ *  5. Edge function of a -> b at the sample (256 x, 256 y): E = (xb - xa)(256 y - ya) - (yb - ya)(256 x - xa), 64-bit exact.
+ *     w0 = E(1 -> 2), w1 = E(2 -> 0), w2 = E(0 -> 1); w0 + w1 + w2 = area2.  The sample is covered when every w_k >= 0 and
+ *     every edge with w_k = 0 is a left edge (yb < ya) or a top edge (yb = ya and xb > xa) — the top-left fill rule, y down:
+ *     two triangles sharing an edge cover each sample of it exactly once.  Samples are taken for 0 <= x < W, 0 <= y < H
+ *     inside the triangle's box only (clipping by the box, not by geometry).
+ *  6. Perspective weights p_k = ((float) w_k / (float) area2) * (1 / Zc_k), q = (p0 + p1) + p2, depth Z = 1 / q: camera Z
+ *     (not ray length), 1 / Z linear in screen space.  Colour channel c = min(255, max(0, floor(((p0 c0 + p1 c1) + p2 c2) / q + 0.5)))
+ *     with c_k the vertex colours as floats; alpha = 255 where covered, the pixel is (0, 0, 0, 0) elsewhere.
+ *  7. Depth test: the fragment with the smallest Z wins a sample; equal Z: the lowest face index.  The result does not depend
+ *     on launch order, stream or chunking: it is a 64-bit unsigned atomic minimum over (bits of Z) << 32 | face.
+ *  8. depth_mm = (uint16) min(65535, rint(1000 * Z)) (round half to even), 0 on background: what `*_depth.png` holds when the
+ *     vertices are in metres.  (bop_toolkit's save_depth is recalled to round with np.round; not verifiable here.)
+ *     depth_m = Z (0 on background), face_id = the winning face (-1 on background).
+ *
+ * vertices (Nv, 3) fp32, faces (Nf, 3) int32, colors (Nv, 3) uint8 RGB, poses (V, 4, 4) fp32: device.  faces_host: the HOST copy
+ * of faces, range-checked here before any launch (the kernels skip a triangle whose device indices are out of range anyway).
+ * rgba (V, H, W, 4) uint8 (4-byte aligned), depth_mm (V, H, W) uint16; depth_m (V, H, W) fp32 and face_id (V, H, W) int32 may be
+ * NULL; near_count: one device uint32, zeroed here.  The views are rendered in chunks of as many views as the workspace holds
+ * (pp_render_workspace_bytes(H, W, Nf, chunk) = 256 + chunk (H W + Nf) 8 bytes: a 64-bit depth/face word per sample and a queue
+ * slot per triangle); any chunk size gives the same bytes.  All work is enqueued on `stream`; nothing synchronises.
+ * PP_EINVAL: null pointer, V / Nv / Nf / H / W <= 0, H W >= 2^31, near <= 0, fx or fy = 0, an index of faces_host outside
+ * [0, Nv).  PP_EWORKSPACE: workspace misaligned (256 B) or smaller than one view needs.
+ * ------------------------------------------------------------------------- */
+int pp_render_workspace_bytes(int H, int W, int n_faces, int chunk_views, size_t* bytes);
+int pp_render_views(const float* vertices, int n_vertices, const int* faces, const int* faces_host, int n_faces,
+                    const unsigned char* colors, const float* poses, int n_views, float fx, float fy, float cx, float cy, int H,
+                    int W, float near, void* workspace, size_t workspace_bytes, unsigned char* rgba, unsigned short* depth_mm,
+                    float* depth_m, int* face_id, unsigned int* near_count, void* stream);
+/* Per view the first / last row and column with alpha != 0 — the np.any / np.where of get_bbox (utils/data_utils.py:131-137) on
+ * rgba[..., 3]: extents (V, 4) int32 = {rmin, rmax, cmin, cmax} (inclusive; -1 each for a view that covers nothing);
+ * counts (V) int32 covered samples, may be NULL. */
+int pp_template_extents(const unsigned char* rgba, int n_views, int H, int W, int* extents, int* counts, void* stream);
+/* `_get_template` (provider/bop_test_dataset.py:222-240) for V frames in one launch.  boxes (V, 4) int32 {y1, y2, x1, x2} on the
+ * device, boxes_host its HOST copy, validated here.  Per view: out_rgb (V, 3, S, S) = pp_crop_resize_normalize of the frame's
+ * colours (masked by alpha > 0 when rgb_mask_flag), out_mask (V, S, S) = its nearest-resized mask of alpha == 255, out_pts
+ * (V, P, P, 3) = pp_depth_points_nearest of the depth in metres — the same device functions, bit-equal to the per-view calls.
+ * depth: (V, H, W) uint16 millimetres, converted as (float)((double) d / 1000.0) (:230), or fp32 metres when depth_is_f32.
+ * PP_EINVAL: null pointer, V <= 0 or > 65535, S or P outside 1..4096, fx or fy = 0, a box that is empty or leaves the frame. */
+int pp_templates_crop(const unsigned char* rgba, const void* depth, int depth_is_f32, int n_views, int H, int W, const int* boxes,
+                      const int* boxes_host, float fx, float fy, float cx, float cy, int S, int P, int rgb_mask_flag,
+                      const double* mean3, const double* std3, float* out_rgb, float* out_mask, float* out_pts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include "../../include/picopose_hip.h"
 #include "pp_common.h"
+#include "pp_crop_dev.h"
 
 namespace {
 
@@ -534,24 +535,10 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(const unsigned char* _
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= S * S) return;
     const int oy = i / S, ox = i - oy * S, h = y2 - y1, w = x2 - x1;
-    auto taps = [](int o, int n, int S_, int& i0, int& i1, double& fr) {
-        const double f = ((double)o + 0.5) * ((double)n / (double)S_) - 0.5;
-        i0 = (int)floor(f);
-        fr = f - (double)i0;
-        if (i0 < 0) {
-            i0 = 0;
-            fr = 0.0;
-        }
-        if (i0 >= n - 1) {
-            i0 = n - 1;
-            fr = 0.0;
-        }
-        i1 = i0 + 1 < n ? i0 + 1 : n - 1;
-    };
     int ya, yb, xa, xb;
     double fy, fx;
-    taps(oy, h, S, ya, yb, fy);
-    taps(ox, w, S, xa, xb, fx);
+    pp_crop_taps(oy, h, S, ya, yb, fy);
+    pp_crop_taps(ox, w, S, xa, xb, fx);
     const double mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
     auto px = [&](int yy, int xx, int c) -> double {  // channel c of the flipped ([..., ::-1]) crop, / 255, optionally masked
         const size_t p = (size_t)(y1 + yy) * W + (x1 + xx);
@@ -560,15 +547,9 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(const unsigned char* _
         return v;
     };
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double top = px(ya, xa, c) * (1.0 - fx) + px(ya, xb, c) * fx;
-        const double bot = px(yb, xa, c) * (1.0 - fx) + px(yb, xb, c) * fx;
-        out_rgb[(size_t)c * S * S + i] = (float)(((top * (1.0 - fy) + bot * fy) - mean[c]) / stdv[c]);
-    }
+    for (int c = 0; c < 3; ++c) out_rgb[(size_t)c * S * S + i] = pp_crop_blend(px, c, ya, yb, xa, xb, fx, fy, mean[c], stdv[c]);
     if (out_mask) {
-        int yi = (int)floor((double)oy * ((double)h / (double)S)), xi = (int)floor((double)ox * ((double)w / (double)S));
-        yi = yi < h - 1 ? yi : h - 1;
-        xi = xi < w - 1 ? xi : w - 1;
+        const int yi = pp_crop_nearest(oy, h, S), xi = pp_crop_nearest(ox, w, S);
         out_mask[i] = mask ? (float)mask[(size_t)(y1 + yi) * W + (x1 + xi)] : 1.f;
     }
 }
@@ -581,14 +562,8 @@ __global__ __launch_bounds__(256) void depth_points_kernel(const float* __restri
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= P * P) return;
     const int oy = i / P, ox = i - oy * P, h = y2 - y1, w = x2 - x1;
-    int yi = (int)floor((double)oy * ((double)h / (double)P)), xi = (int)floor((double)ox * ((double)w / (double)P));
-    yi = yi < h - 1 ? yi : h - 1;
-    xi = xi < w - 1 ? xi : w - 1;
-    const int y = y1 + yi, x = x1 + xi;
-    const float z = depth[(size_t)y * W + x];
-    out[3 * i + 0] = ((float)x - cx) * z / fx;
-    out[3 * i + 1] = ((float)y - cy) * z / fy;
-    out[3 * i + 2] = z;
+    const int y = y1 + pp_crop_nearest(oy, h, P), x = x1 + pp_crop_nearest(ox, w, P);
+    pp_depth_point(depth[(size_t)y * W + x], x, y, fx, fy, cx, cy, out + 3 * i);
 }
 
 

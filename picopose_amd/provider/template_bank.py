@@ -1,0 +1,332 @@
+"""Onboarding an object from its mesh: the template bank rendered, cropped and featurised on the device.
+
+Replaces the reference's offline step rendering/scripts/render_bop_templates.py -> rendering/src/custom_megapose/call_panda3d.py
+(Panda3D inside MegaPose's image, 324 PNG files per object) followed by provider/bop_test_dataset.py:212-308 (`_get_template`,
+`get_templates`) and run_test.py:120-134 (the bank features):
+
+    mesh = load_ply(path)                                    # or {"vertices", "faces", "colors"} arrays of your own
+    bank = onboard_objects(net, [mesh, ...], view_poses)     # templates_data + template_feature
+    pipeline.infer_image(net, data, bank, indexed_bank=True)
+
+The render recipe is the reference's: one ambient light of colour 1 (the pixel is the surface colour, unshaded), TEMPLATE_K at
+480 x 640, object pose = a view rotation with t = (0, 0, diameter), RGBA uint8 with alpha = 255 on the object, depth in whole
+millimetres.  The rasteriser's conventions (pixel centres at integer coordinates, 1/256 px snapping, top-left fill rule, no
+back-face culling, no near-plane clipping, vertex colours only) are stated in include/picopose_hip.h; parity with Panda3D's or
+BlenderProc's pixels is UNPINNED — neither renderer is available to compare against.  Texture maps are not read: a UV-textured
+model must be baked to vertex colours by the caller.  The package reads no fixture: `view_poses` is the caller's array (the
+reference's is rendering/src/lib3d/predefined_poses/obj_poses_level1.npy, 162 views)."""
+import ctypes
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..utils.preprocess import CLIP_MEAN, CLIP_STD, _square
+
+TEMPLATE_K = np.array([[572.4114, 0.0, 320.0], [0.0, 573.57043, 240.0], [0.0, 0.0, 1.0]])     # call_panda3d.py:48-50
+DEFAULT_WORKSPACE_BYTES = 256 << 20      # bound of the render workspace: 100 views of 480 x 640 for a 20 k-triangle mesh
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def load_ply(path):
+    """A BOP model file -> {"vertices" (Nv,3) f32, "faces" (Nf,3) i32, "colors" (Nv,3) u8 or None}.  ASCII and
+    binary_little_endian PLY; element `vertex` with x y z (nx ny nz, red green blue [alpha], texture_u / texture_v and any other
+    scalar property are skipped or, for the colours, returned), element `face` with a `vertex_indices` / `vertex_index` list.
+    ValueError: not a PLY file, big-endian, a missing element or property, a face that is not a triangle, a truncated body."""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    end = raw.find(b"end_header")
+    if not raw.startswith(b"ply") or end < 0:
+        raise ValueError(f"{path}: not a PLY file (no 'ply' magic / 'end_header')")
+    body = raw.find(b"\n", end) + 1
+    fmt, elements = None, []
+    for line in raw[:end].decode("ascii", "replace").splitlines()[1:]:
+        tok = line.split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[0] == "property":
+            if not elements:
+                raise ValueError(f"{path}: property before any element")
+            if tok[1] == "list":
+                if tok[2] not in _PLY_TYPES or tok[3] not in _PLY_TYPES:
+                    raise ValueError(f"{path}: unknown PLY type in '{line}'")
+                elements[-1][2].append((tok[4], (_PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]])))
+            else:
+                if tok[1] not in _PLY_TYPES:
+                    raise ValueError(f"{path}: unknown PLY type in '{line}'")
+                elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]]))
+    if fmt == "binary_big_endian":
+        raise ValueError(f"{path}: big-endian PLY is not supported")
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError(f"{path}: unknown PLY format {fmt!r}")
+    names = [e[0] for e in elements]
+    for need in ("vertex", "face"):
+        if need not in names:
+            raise ValueError(f"{path}: no '{need}' element")
+    out = {}
+    tokens, pos = (raw[body:].split(), 0) if fmt == "ascii" else (None, body)
+    for name, count, props in elements:
+        lists = [p for p in props if isinstance(p[1], tuple)]
+        if name == "vertex":
+            if lists:
+                raise ValueError(f"{path}: list property in the vertex element")
+            pn = [p[0] for p in props]
+            for need in ("x", "y", "z"):
+                if need not in pn:
+                    raise ValueError(f"{path}: vertex element has no '{need}' property")
+            if fmt == "ascii":
+                if pos + count * len(props) > len(tokens):
+                    raise ValueError(f"{path}: truncated vertex data")
+                tab = np.array(tokens[pos:pos + count * len(props)], dtype=np.float64).reshape(count, len(props))
+                pos += count * len(props)
+                col = {n: tab[:, k] for k, n in enumerate(pn)}
+            else:
+                dt = np.dtype([(n, "<" + t) for n, t in props])
+                if pos + count * dt.itemsize > len(raw):
+                    raise ValueError(f"{path}: truncated vertex data")
+                tab = np.frombuffer(raw, dtype=dt, count=count, offset=pos)
+                pos += count * dt.itemsize
+                col = {n: tab[n] for n in pn}
+            out["vertices"] = np.ascontiguousarray(np.stack([col["x"], col["y"], col["z"]], axis=1).astype(np.float32))
+            out["colors"] = (np.ascontiguousarray(np.stack([col["red"], col["green"], col["blue"]], axis=1).astype(np.uint8))
+                             if all(c in col for c in ("red", "green", "blue")) else None)
+        elif name == "face":
+            if len(props) != 1 or not lists or props[0][0] not in ("vertex_indices", "vertex_index"):
+                raise ValueError(f"{path}: face element must hold one 'vertex_indices' / 'vertex_index' list")
+            ct, it = props[0][1]
+            if fmt == "ascii":
+                if pos + 4 * count > len(tokens):
+                    raise ValueError(f"{path}: truncated face data (or a face that is not a triangle)")
+                tab = np.array(tokens[pos:pos + 4 * count], dtype=np.int64).reshape(count, 4)
+                pos += 4 * count
+                n, idx = tab[:, 0], tab[:, 1:]
+            else:
+                dt = np.dtype([("n", "<" + ct), ("i", "<" + it, (3,))])
+                if pos + count * dt.itemsize > len(raw):
+                    raise ValueError(f"{path}: truncated face data (or a face that is not a triangle)")
+                tab = np.frombuffer(raw, dtype=dt, count=count, offset=pos)
+                pos += count * dt.itemsize
+                n, idx = tab["n"], tab["i"]
+            if np.any(n != 3):
+                raise ValueError(f"{path}: face {int(np.argmax(n != 3))} is not a triangle ({int(n[np.argmax(n != 3)])} vertices)")
+            out["faces"] = np.ascontiguousarray(idx.astype(np.int32))
+        else:                                                   # another element: skipped (fixed-size properties only)
+            if lists:
+                raise ValueError(f"{path}: cannot skip element '{name}' with a list property")
+            if fmt == "ascii":
+                pos += count * len(props)
+            else:
+                pos += count * np.dtype([(n_, "<" + t) for n_, t in props]).itemsize
+    return out
+
+
+def mesh_diameter(vertices):
+    """rendering/src/utils/trimesh.py:20-23: the norm of twice the axis-aligned extents, in the vertices' unit."""
+    v = np.asarray(vertices, dtype=np.float64)
+    return float(np.linalg.norm((v.max(axis=0) - v.min(axis=0)) * 2))
+
+
+def template_object_poses(view_poses, vertices):
+    """render_bop_templates.py:109-115: the view poses (V,4,4) with every translation replaced by (0, 0, diameter)."""
+    poses = np.array(view_poses, dtype=np.float64)
+    poses[:, :3, 3] = np.array([0.0, 0.0, mesh_diameter(vertices)])[None].repeat(len(poses), axis=0)
+    return poses
+
+
+def _mesh_arrays(mesh):
+    v = np.asarray(mesh["vertices"])
+    f = np.asarray(mesh["faces"])
+    if v.ndim != 2 or v.shape[1] != 3 or len(v) == 0 or not np.issubdtype(v.dtype, np.floating):
+        raise ValueError(f"vertices must be a non-empty (Nv, 3) float array, got {v.dtype} {v.shape}")
+    if f.ndim != 2 or f.shape[1] != 3 or len(f) == 0 or not np.issubdtype(f.dtype, np.integer):
+        raise ValueError(f"faces must be a non-empty (Nf, 3) integer array, got {f.dtype} {f.shape}")
+    if not np.all(np.isfinite(v)):
+        raise ValueError("vertices contain a non-finite value")
+    if f.min() < 0 or f.max() >= len(v):
+        bad = int(np.argmax(np.any((f < 0) | (f >= len(v)), axis=1)))
+        raise ValueError(f"face {bad} = {f[bad].tolist()} indexes outside the {len(v)} vertices")
+    c = mesh.get("colors")
+    if c is None:
+        c = np.full((len(v), 3), 128, dtype=np.uint8)
+    c = np.asarray(c)
+    if c.shape != (len(v), 3) or c.dtype != np.uint8:
+        raise ValueError(f"colors must be (Nv, 3) uint8, got {c.dtype} {c.shape}")
+    return (np.ascontiguousarray(v, dtype=np.float32), np.ascontiguousarray(f, dtype=np.int32), np.ascontiguousarray(c))
+
+
+def _unit_scale(units, vertices):
+    if units == "auto":                                          # call_panda3d.py:39-40
+        units = "m" if mesh_diameter(vertices) < 10 else "mm"
+    if units not in ("m", "mm"):
+        raise ValueError(f"units must be 'mm', 'm' or 'auto', got {units!r}")
+    return 1.0 if units == "m" else 1e-3
+
+
+def render_views(mesh, poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", near=1e-3, return_depth_m=False, return_face_id=False,
+                 workspace_bytes=DEFAULT_WORKSPACE_BYTES, check_near=True, device="cuda"):
+    """Render `mesh` ({"vertices", "faces", "colors" or None}) under the object -> camera poses (V,4,4) whose translation is in
+    the mesh's `units` ("mm" as BOP models are, "m", or "auto": the reference's rule, diameter < 10 -> metres).  The kernels work
+    in metres: vertices and translations are scaled by 1e-3 in float64 for "mm" and rounded to float32 once.
+    -> {"rgba" (V,H,W,4) uint8, "depth_mm" (V,H,W) uint16 [, "depth_m" (V,H,W) f32, "face_id" (V,H,W) int32], "near_count"
+    (1,) int32 device tensor}.  A mesh without colours renders mid-grey (128, 128, 128).  `workspace_bytes` bounds the
+    rasteriser's workspace; the views are rendered in as many chunks as that takes (at least one view's worth is allocated).
+    check_near: synchronise and raise ValueError when a triangle was dropped at the near plane (`near` metres); False leaves the
+    count on the device for the caller."""
+    v, f, c = _mesh_arrays(mesh)
+    scale = _unit_scale(units, v)
+    poses = np.array(poses, dtype=np.float64)
+    if poses.ndim != 3 or poses.shape[1:] != (4, 4) or len(poses) == 0 or not np.all(np.isfinite(poses)):
+        raise ValueError(f"poses must be a non-empty finite (V, 4, 4) array, got {poses.shape}")
+    poses[:, :3, 3] *= scale
+    K = np.asarray(K, dtype=np.float64)
+    H, W = int(resolution[0]), int(resolution[1])
+    V, L = len(poses), _lib.lib()
+    v_m = np.ascontiguousarray((v.astype(np.float64) * scale).astype(np.float32))
+    v_d, f_d, c_d = (torch.from_numpy(a).to(device) for a in (v_m, f, c))
+    p_d = torch.from_numpy(np.ascontiguousarray(poses.astype(np.float32))).to(device)
+    need = ctypes.c_size_t()
+    _lib.check(L.pp_render_workspace_bytes(H, W, len(f), 1, ctypes.byref(need)), "pp_render_workspace_bytes")
+    per_view = need.value - 256
+    chunk = max(1, min(V, (int(workspace_bytes) - 256) // per_view))
+    ws = torch.empty(256 + chunk * per_view, dtype=torch.uint8, device=device)
+    out = {"rgba": torch.empty(V, H, W, 4, dtype=torch.uint8, device=device),
+           "depth_mm": torch.empty(V, H, W, dtype=torch.uint16, device=device),
+           "near_count": torch.empty(1, dtype=torch.int32, device=device)}
+    if return_depth_m:
+        out["depth_m"] = torch.empty(V, H, W, dtype=torch.float32, device=device)
+    if return_face_id:
+        out["face_id"] = torch.empty(V, H, W, dtype=torch.int32, device=device)
+    _lib.check(L.pp_render_views(v_d.data_ptr(), len(v), f_d.data_ptr(), f.ctypes.data, len(f), c_d.data_ptr(), p_d.data_ptr(), V,
+                                 float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), H, W, float(near), ws.data_ptr(),
+                                 ws.numel(), out["rgba"].data_ptr(), out["depth_mm"].data_ptr(),
+                                 out["depth_m"].data_ptr() if return_depth_m else None,
+                                 out["face_id"].data_ptr() if return_face_id else None, out["near_count"].data_ptr(),
+                                 _lib.stream_ptr()), "pp_render_views")
+    if check_near:
+        _raise_on_near(int(out["near_count"].item()), near)
+    return out
+
+
+def _raise_on_near(count, near):
+    if count:
+        raise ValueError(f"{count} triangle(s) reach the near plane (Zc <= {near} m) and were dropped: move the object away "
+                         "from the camera (there is no near-plane clipping)")
+
+
+def _crop_frames(rgba, depth, depth_is_f32, K, poses_mm, near_count, near, img_size, pts_size, rgb_mask_flag):
+    """extents -> one device->host copy -> boxes -> one crop launch.  rgba (V,H,W,4) uint8 and depth (V,H,W) on the device."""
+    V, H, W = rgba.shape[:3]
+    dev, L = rgba.device, _lib.lib()
+    meta = torch.empty(V * 4 + 1, dtype=torch.int32, device=dev)
+    if near_count is None:
+        meta[-1] = 0
+    else:
+        meta[-1:] = near_count
+    _lib.check(L.pp_template_extents(rgba.data_ptr(), V, H, W, meta.data_ptr(), None, _lib.stream_ptr()), "pp_template_extents")
+    host = meta.cpu().numpy()                                    # the one device->host copy (it synchronises the stream)
+    _raise_on_near(int(host[-1]), near)
+    ext = host[:-1].reshape(V, 4)
+    empty = np.where(ext[:, 1] < 0)[0]
+    if len(empty):
+        raise ValueError(f"template view {int(empty[0])} covers no pixel" + (f" (and {len(empty) - 1} more)" if len(empty) > 1 else ""))
+    boxes = np.array([_square(int(e[0]), int(e[1]) + 1, int(e[2]), int(e[3]) + 1, H, W) for e in ext], dtype=np.int32)    # get_bbox
+    if np.any(boxes[:, 0] < 0) or np.any(boxes[:, 2] < 0):
+        raise ValueError("a template's square crop window leaves the frame (object larger than the smaller image dimension)")
+    boxes_d = torch.from_numpy(boxes).to(dev)
+    K = np.asarray(K, dtype=np.float64)
+    S, P = int(img_size), int(pts_size)
+    rgb = torch.empty(V, 3, S, S, dtype=torch.float32, device=dev)
+    mask = torch.empty(V, S, S, dtype=torch.float32, device=dev)
+    pts = torch.empty(V, P, P, 3, dtype=torch.float32, device=dev)
+    mean, std = (ctypes.c_double * 3)(*CLIP_MEAN), (ctypes.c_double * 3)(*CLIP_STD)
+    _lib.check(L.pp_templates_crop(rgba.data_ptr(), depth.data_ptr(), int(depth_is_f32), V, H, W, boxes_d.data_ptr(), boxes.ctypes.data,
+                                   float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), S, P, int(rgb_mask_flag), mean, std,
+                                   rgb.data_ptr(), mask.data_ptr(), pts.data_ptr(), _lib.stream_ptr()), "pp_templates_crop")
+    y1, y2, x1, x2 = (boxes[:, k].astype(np.float64) for k in range(4))
+    M = np.zeros((V, 3, 3), dtype=np.float32)                    # M_resize @ M_crop of :246-254, entry by entry in float32
+    M[:, 0, 0] = (S / (y2 - y1)).astype(np.float32)
+    M[:, 1, 1] = (S / (x2 - x1)).astype(np.float32)
+    M[:, 0, 2] = M[:, 0, 0] * (-boxes[:, 2]).astype(np.float32)
+    M[:, 1, 2] = M[:, 1, 1] * (-boxes[:, 0]).astype(np.float32)
+    M[:, 2, 2] = 1
+    pose = np.array(poses_mm, dtype=np.float64)
+    pose[:, :3, 3] = pose[:, :3, 3] / 1000.0                     # :244
+    return {"tem_rgb": rgb, "tem_mask": mask, "tem_pts3d": pts, "tem_bbox": torch.from_numpy(boxes.astype(np.float32)).to(dev),
+            "tem_M": torch.from_numpy(M).to(dev), "tem_K": torch.from_numpy(K.astype(np.float32))[None].repeat(V, 1, 1).to(dev),
+            "tem_pose": torch.from_numpy(pose.astype(np.float32)).to(dev)}
+
+
+def templates_from_frames(rgba, depth_mm, K, poses_mm, img_size=224, pts_size=64, rgb_mask_flag=False, device="cuda"):
+    """The bank entries of frames the caller already has (decoded `NNNNNN.png` / `NNNNNN_depth.png`): rgba (V,H,W,4) uint8,
+    depth_mm (V,H,W) (any integer or float dtype holding whole millimetres up to 65535), poses (V,4,4) with t in mm -> the `tem_*`
+    tensors of one object, each view equal to utils.preprocess.crop_template's — with one upload, one extents launch, one
+    device->host copy and one crop launch instead of three uploads and three launches per view."""
+    rgba_d = torch.as_tensor(np.ascontiguousarray(rgba) if isinstance(rgba, np.ndarray) else rgba).to(device).contiguous()
+    if rgba_d.dtype != torch.uint8 or rgba_d.dim() != 4 or rgba_d.shape[-1] != 4:
+        raise ValueError(f"rgba must be (V, H, W, 4) uint8, got {rgba_d.dtype} {tuple(rgba_d.shape)}")
+    if isinstance(depth_mm, np.ndarray):
+        if depth_mm.dtype != np.uint16:
+            if depth_mm.min() < 0 or depth_mm.max() > 65535 or np.any(depth_mm != np.floor(depth_mm)):
+                raise ValueError("depth_mm must hold whole millimetres in [0, 65535] (a 16-bit depth PNG's values)")
+            depth_mm = depth_mm.astype(np.uint16)
+        depth_d = torch.from_numpy(np.ascontiguousarray(depth_mm)).to(device)
+    else:
+        depth_d = depth_mm.to(device).contiguous()
+        if depth_d.dtype != torch.uint16:
+            raise ValueError(f"a depth_mm tensor must be uint16, got {depth_d.dtype}")
+    if tuple(depth_d.shape) != tuple(rgba_d.shape[:3]) or len(poses_mm) != rgba_d.shape[0]:
+        raise ValueError("rgba, depth_mm and poses_mm disagree on (V, H, W)")
+    return _crop_frames(rgba_d, depth_d, False, K, poses_mm, None, 0.0, img_size, pts_size, rgb_mask_flag)
+
+
+def render_templates(mesh, view_poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", depth="png", img_size=224, pts_size=64,
+                     rgb_mask_flag=False, near=1e-3, workspace_bytes=DEFAULT_WORKSPACE_BYTES, device="cuda"):
+    """One object's template bank from its mesh: `tem_rgb` (V,3,S,S), `tem_mask` (V,S,S), `tem_pts3d` (V,P,P,3) metres, `tem_bbox`
+    (V,4), `tem_M` (V,3,3), `tem_K` (V,3,3), `tem_pose` (V,4,4) (t in metres), float32 device tensors with `_get_template`'s values
+    for the rendered frames (bop_test_dataset.py:212-264).  view_poses (V,4,4): only the rotations are used; the object sits at
+    (0, 0, diameter) (template_object_poses).  Render, extents, ONE device->host copy (extents + near-plane count), one crop launch.
+    depth="png" (default): the lookup points come from the uint16 millimetres a depth file would hold, as the reference's do;
+    depth="float": from the float32 depth directly — a deviation from the reference that removes the 0.5 mm quantisation.
+    ValueError: a triangle at the near plane, or a view that covers no pixel (named)."""
+    if depth not in ("png", "float"):
+        raise ValueError(f"depth must be 'png' or 'float', got {depth!r}")
+    v = _mesh_arrays(mesh)[0]
+    to_mm = 1.0 / (_unit_scale(units, v) * 1000.0)               # the returned pose follows the file convention: t in mm, then / 1000
+    poses = template_object_poses(view_poses, v)
+    r = render_views(mesh, poses, K=K, resolution=resolution, units=units, near=near, return_depth_m=depth == "float",
+                     workspace_bytes=workspace_bytes, check_near=False, device=device)
+    poses_mm = poses.copy()
+    poses_mm[:, :3, 3] *= to_mm
+    return _crop_frames(r["rgba"], r["depth_m"] if depth == "float" else r["depth_mm"], depth == "float", K, poses_mm, r["near_count"],
+                        near, img_size, pts_size, rgb_mask_flag)
+
+
+def onboard_objects(net, meshes, view_poses, bs=16, extended=False, **render_kw):
+    """`templates_data` for a list of meshes, stacked over objects as `get_templates` returns it (bop_test_dataset.py:266-308:
+    every `tem_*` tensor (n_objects, V, ...)), plus `template_feature` (n_objects, V, C, 16, 16) computed as run_test.py:123-134
+    does (the feature extractor's last level in mini-batches of `bs`).  extended=True adds the extended bank under
+    `template_cache` (Net.precompute_templates with chunk=bs; its "feature" then serves as `template_feature`).  The result goes
+    to pipeline.infer_image(net, data, templates_data, indexed_bank=True) as it is.  render_kw: render_templates' keywords."""
+    banks = [render_templates(m, view_poses, **render_kw) for m in meshes]
+    if not banks:
+        raise ValueError("no meshes")
+    data = {k: torch.stack([b[k] for b in banks]) for k in banks[0]}
+    feats, dpt = [], []
+    with torch.no_grad():
+        for b in banks:
+            if extended:
+                pre = net.precompute_templates(b["tem_rgb"], chunk=bs)
+                feats.append(pre["feature"])
+                dpt.append(pre["dpt"])
+            else:
+                n = b["tem_rgb"].shape[0]
+                feats.append(torch.cat([net.feature_extractor(b["tem_rgb"][s:s + bs].contiguous())[-1] for s in range(0, n, bs)]))
+    data["template_feature"] = torch.stack(feats)
+    if extended:
+        data["template_cache"] = {"dpt": [torch.stack([d[k] for d in dpt]) for k in range(3)]}
+    return data
