@@ -868,6 +868,58 @@ int pp_templates_crop(const unsigned char* rgba, const void* depth, int depth_is
                       const int* boxes_host, float fx, float fy, float cx, float cy, int S, int P, int rgb_mask_flag,
                       const double* mean3, const double* std3, float* out_rgb, float* out_mask, float* out_pts, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Pose errors against ground truth (picopose_amd/evaluation.py plans every call): MSSD, MSPD (Hodan et al., "BOP Challenge 2020
+ * on 6D Object Localization", section 2.2), ADD and ADD-S (Hinterstoisser et al. 2012) of n_pairs (estimate, ground truth) pairs
+ * that may mix objects, in one launch sequence: one compose launch (when MSSD or MSPD is asked for), one launch per kind, one
+ * finalize launch (the minimum over symmetries of MSSD / MSPD and the tile sums of ADD-S).
+ *
+ * THE ARITHMETIC (tests/pose_error_oracle.py restates it in numpy; MSSD, MSPD and their indices equal it bit for bit).  float32,
+ * one rounding per operation, never contracted, in the order written, unless float64 is named:
+ *  1. compose, per (pair p, symmetry s of its object): G = f32(R_gt R_s), g = f32(R_gt t_s + t_gt), every entry evaluated in float64
+ *     as ((a0 b0 + a1 b1) + a2 b2) [+ t] from the float32 inputs and rounded once.
+ *  2. a point under a map (R, t): X = ((R00 x + R01 y) + R02 z) + t0, and Y, Z alike.
+ *  3. MSSD_s = sqrt(max over the object's vertices of (dx dx + dy dy) + dz dz), d = est(x) - (G, g)(x).  A squared distance that is
+ *     NaN (a pose that holds a NaN or an infinity) counts as +inf: such a pair has MSSD +inf, never a small value.
+ *  4. MSPD_s = sqrt(max of du du + dv dv), u = (fx X) (1 / Z), v = (fy Y) (1 / Z), d = est - gt.  The principal point cancels in the
+ *     difference and is not added.  A squared distance is +inf when a point of either side has Z <= 0 (or when it is NaN).
+ *  5. mssd / mspd = the minimum over s, *_sym = its index within the object's symmetry list (the lowest on a tie; 0 when all are +inf).
+ *     (ADD of a pair with a non-finite pose is NaN or +inf, ADD-S +inf or NaN: never a finite value.)
+ *  6. ADD = f32(sum / Nv): the distances sqrt((dx dx + dy dy) + dz dz) against (R_gt, t_gt) itself, added in float64: lane l of 256
+ *     adds vertices l, l + 256, ... in order, the 64 lanes of a wave combine by xor-shuffles 32, 16, ... 1, the 4 waves in order.
+ *  7. ADD-S = f32(sum / Nv'): per estimate-side vertex the square root of the minimum over the ground-truth-side vertices of the
+ *     squared distance in difference form, over the ADD-S vertex set; tiles of PP_EVAL_ADDS_TILE vertices (lane l holds vertices
+ *     l, l + 256, l + 512, l + 768 of its tile) are summed as in 6 and the tiles added in order.
+ * Every result is independent of launch order, stream, pair order and of how the caller splits the pairs over calls.  No atomics.
+ *
+ * vertices / adds_vertices: every object's (Nv, 3) fp32 vertices concatenated (millimetres), object o at rows
+ * [vert_off[o], vert_off[o + 1]) / [adds_off[o], adds_off[o + 1]) (adds_vertices: the set ADD-S runs on, e.g. a subsample; it may be
+ * the same buffer).  sym_R (S, 9) / sym_t (S, 3) fp32: every object's symmetry transforms concatenated, object o at
+ * [sym_off[o], sym_off[o + 1]), at least one each.  The three *_off tables (n_objects + 1 ints) are device pointers, *_off_host
+ * their HOST copies, validated here.  pair_obj (n_pairs) int32 object index per pair, device, pair_obj_host its HOST copy.
+ * R_est, R_gt (n_pairs, 9), t_est, t_gt (n_pairs, 3) fp32, translations in millimetres; focal (n_pairs, 2) fp32 {fx, fy}, needed
+ * for PP_EVAL_MSPD only.  kinds: an OR of PP_EVAL_*; outputs of kinds not asked for may be NULL.  mssd, mspd, add, adds (n_pairs)
+ * fp32, mssd_sym, mspd_sym (n_pairs) int32.
+ * Workspace (256-byte aligned): pp_pose_errors_workspace_bytes(n_pairs, max_syms, max_adds_vertices, kinds), where max_syms /
+ * max_adds_vertices are the largest symmetry count / ADD-S vertex count among the objects of the call's pairs: 12 floats per
+ * (pair, symmetry) for the composed maps, one per (pair, symmetry) and requested symmetric kind, one double per (pair, ADD-S tile).
+ * PP_EINVAL (before any launch): a null pointer that is needed, n_pairs / n_objects <= 0, kinds 0 or with an unknown bit, an offset
+ * table that does not start at 0 or has an empty object, a pair_obj_host entry outside [0, n_objects), n_pairs max_syms >= 2^31.
+ * PP_EWORKSPACE: workspace misaligned or smaller than pp_pose_errors_workspace_bytes says.
+ * ------------------------------------------------------------------------- */
+#define PP_EVAL_MSSD 1
+#define PP_EVAL_MSPD 2
+#define PP_EVAL_ADD 4
+#define PP_EVAL_ADDS 8
+#define PP_EVAL_ADDS_TILE 1024
+int pp_pose_errors_workspace_bytes(int n_pairs, int max_syms, int max_adds_vertices, int kinds, size_t* bytes);
+int pp_pose_errors(const float* vertices, const int* vert_off, const float* adds_vertices, const int* adds_off, const float* sym_R,
+                   const float* sym_t, const int* sym_off, const int* vert_off_host, const int* adds_off_host,
+                   const int* sym_off_host, int n_objects, const int* pair_obj, const int* pair_obj_host, const float* R_est,
+                   const float* t_est, const float* R_gt, const float* t_gt, const float* focal, int n_pairs, int kinds,
+                   void* workspace, size_t workspace_bytes, float* mssd, int* mssd_sym, float* mspd, int* mspd_sym, float* add,
+                   float* adds, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,8 @@ def lib():
         L.pp_template_extents.argtypes = [vp, i32, i32, i32, vp, vp, vp]
         L.pp_templates_crop.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, f32, f32, f32, f32, i32, i32, i32,
                                         c.POINTER(c.c_double), c.POINTER(c.c_double), vp, vp, vp, vp]
+        L.pp_pose_errors_workspace_bytes.argtypes = [i32, i32, i32, i32, c.POINTER(sz)]
+        L.pp_pose_errors.argtypes = [vp] * 10 + [i32] + [vp] * 7 + [i32, i32, vp, sz] + [vp] * 7
         _lib = L
     return _lib
 
