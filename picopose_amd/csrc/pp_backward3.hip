@@ -307,8 +307,9 @@ __global__ __launch_bounds__(256) void warp_backward_kernel(const float* __restr
     gx = wave_sum(gx);
     gy = wave_sum(gy);
     if (lane == 0) {   // (a clamped coordinate is outside every tap's range: all taps invalid, the sums above are zero)
-        dflow[((size_t)b * H * W + p) * 2] = rx == ix ? gx : 0.f;
-        dflow[((size_t)b * H * W + p) * 2 + 1] = ry == iy ? gy : 0.f;
+        // (a map one pixel wide / high: the round trip multiplies by size - 1 = 0, the coordinate does not depend on the flow)
+        dflow[((size_t)b * H * W + p) * 2] = rx == ix && W > 1 ? gx : 0.f;
+        dflow[((size_t)b * H * W + p) * 2 + 1] = ry == iy && H > 1 ? gy : 0.f;
     }
 }
 

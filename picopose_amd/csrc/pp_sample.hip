@@ -13,6 +13,15 @@ namespace {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
+// One blend for every path of resize_kernel, with the contraction spelled out: left to the compiler, the 4-channel path fused the outer
+// sum into an fma and the scalar and 8-channel paths did not, so the same element differed in its last bit between the plain map, the
+// dual output's map and a misaligned view (tests/test_kernel_bounds_gpu.py).  This is the form the scalar and operand paths had.
+__device__ __forceinline__ float resize_blend(float a, float b, float c, float d, float hx, float lx, float hy, float ly, float mul) {
+#pragma clang fp contract(off)
+    const float top = fmaf(hx, a, lx * b), bot = fmaf(hx, c, lx * d);
+    return (hy * top + ly * bot) * mul;
+}
+
 // F.interpolate(mode="bilinear", align_corners=True) — dpt.py:150-152, flow_decoder.py:88-92.
 // ATen: src = dst * (in-1)/(out-1); i0 = floor, i1 = min(i0+1, in-1), lambda = src - i0.
 __global__ __launch_bounds__(256) void resize_kernel(const float* __restrict__ in, int H, int W, int C,
@@ -44,7 +53,7 @@ __global__ __launch_bounds__(256) void resize_kernel(const float* __restrict__ i
                 f4 vq;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float v = (hy * (hx * a[k] + lx * bq[k]) + ly * (hx * cq[k] + lx * dq[k])) * mul;
+                    const float v = resize_blend(a[k], bq[k], cq[k], dq[k], hx, lx, hy, ly, mul);
                     _Float16 h, l;
                     pp_split_f16_chk(v, h, l);
                     hh[4 * q + k] = h;
@@ -70,7 +79,7 @@ __global__ __launch_bounds__(256) void resize_kernel(const float* __restrict__ i
             const f4 cq = *(const f4*)(ib + ((size_t)y1 * W + x0) * C + c), dq = *(const f4*)(ib + ((size_t)y1 * W + x1) * C + c);
             f4 v;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = (hy * (hx * a[k] + lx * bq[k]) + ly * (hx * cq[k] + lx * dq[k])) * mul;
+            for (int k = 0; k < 4; ++k) v[k] = resize_blend(a[k], bq[k], cq[k], dq[k], hx, lx, hy, ly, mul);
             *(f4*)(ob + (size_t)ox * C + c) = v;
         }
         return;
@@ -80,9 +89,8 @@ __global__ __launch_bounds__(256) void resize_kernel(const float* __restrict__ i
         const float fx = sx * (float)ox;
         const int x0 = (int)fx, x1 = x0 + (x0 < W - 1 ? 1 : 0);
         const float lx = fx - (float)x0, hx = 1.f - lx;
-        const float v = hy * (hx * ib[((size_t)y0 * W + x0) * C + c] + lx * ib[((size_t)y0 * W + x1) * C + c]) +
-                        ly * (hx * ib[((size_t)y1 * W + x0) * C + c] + lx * ib[((size_t)y1 * W + x1) * C + c]);
-        ob[i] = v * mul;
+        ob[i] = resize_blend(ib[((size_t)y0 * W + x0) * C + c], ib[((size_t)y0 * W + x1) * C + c], ib[((size_t)y1 * W + x0) * C + c],
+                             ib[((size_t)y1 * W + x1) * C + c], hx, lx, hy, ly, mul);
     }
 }
 
