@@ -349,17 +349,18 @@ inline int grid_for(long long n) { return (int)((n + 255) / 256 < 8192 ? (n + 25
 // t = w 16 + h and m the template mask sampled at the patch (F.interpolate nearest, :16)  ->  dS[b][t][s] = dout m [out > 0]
 __global__ void simvol_backward_kernel(const float* __restrict__ out, const float* __restrict__ dout, const float* __restrict__ mask, int mh,
                                        int mw, long long total, float* __restrict__ dS) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // over dS: ((b 256 + t) 256 + s)
-    if (i >= total) return;
-    const int s = (int)(i & 255), t = (int)((i >> 8) & 255);
-    const long long b = i >> 16;
-    const int sy = s >> 4, sx = s & 15;
-    int my = (int)floorf((float)sy * ((float)mh / 16.0f)), mx = (int)floorf((float)sx * ((float)mw / 16.0f));
-    my = my < mh - 1 ? my : mh - 1;
-    mx = mx < mw - 1 ? mx : mw - 1;
-    const float m = mask[(b * mh + my) * mw + mx];
-    const long long o = ((b * 256 + s) * 16 + (t & 15)) * 16 + (t >> 4);
-    dS[i] = out[o] > 0.f ? dout[o] * m : 0.f;
+    // over dS: ((b 256 + t) 256 + s); grid-stride: grid_for caps the grid at 8192 blocks, 32 images' worth
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int s = (int)(i & 255), t = (int)((i >> 8) & 255);
+        const long long b = i >> 16;
+        const int sy = s >> 4, sx = s & 15;
+        int my = (int)floorf((float)sy * ((float)mh / 16.0f)), mx = (int)floorf((float)sx * ((float)mw / 16.0f));
+        my = my < mh - 1 ? my : mh - 1;
+        mx = mx < mw - 1 ? mx : mw - 1;
+        const float m = mask[(b * mh + my) * mw + mx];
+        const long long o = ((b * 256 + s) * 16 + (t & 15)) * 16 + (t >> 4);
+        dS[i] = out[o] > 0.f ? dout[o] * m : 0.f;
+    }
 }
 
 // im2col written TRANSPOSED: colT[(ky, kx, c)][row], row = (b, oy, ox) — the K-major operand of the weight-gradient product

@@ -76,13 +76,15 @@ def test_stage3_correspondences_bit_exact(geo):
     assert tar.dtype == torch.int64 and tar.shape == (6, 4096, 2)
     assert np.array_equal(tar.cpu().numpy(), z["tar_pts"])
     assert np.array_equal(src.cpu().numpy(), z["src_pts"])
-    # seeded random inputs against the oracle, incl. a non-square map
+    # seeded random inputs against the oracle: a square map and two non-square ones (k = w H + h, and the reference's x < H - 1,
+    # y < W - 1; the float64 decision with its sigmoid band is tests/test_geom_bounds_gpu.py's)
     g = torch.Generator().manual_seed(9)
-    flow = 4 * torch.randn(3, 2, 32, 32, generator=g)
-    cert = torch.randn(3, 1, 32, 32, generator=g)
-    rt, rs = og.compute_stage3_correspondences(flow, cert, threshold=0.3)
-    gt, gs = compute_stage3_correspondences(flow.cuda(), cert.cuda(), threshold=0.3)
-    assert torch.equal(gt.cpu(), rt) and torch.equal(gs.cpu(), rs)
+    for (H, W) in [(32, 32), (20, 36), (36, 20)]:
+        flow = 4 * torch.randn(3, 2, H, W, generator=g)
+        cert = torch.randn(3, 1, H, W, generator=g)
+        rt, rs = og.compute_stage3_correspondences(flow, cert, threshold=0.3)
+        gt, gs = compute_stage3_correspondences(flow.cuda(), cert.cuda(), threshold=0.3)
+        assert torch.equal(gt.cpu(), rt) and torch.equal(gs.cpu(), rs), (H, W)
 
 
 @gpu
