@@ -920,6 +920,70 @@ int pp_pose_errors(const float* vertices, const int* vert_off, const float* adds
                    void* workspace, size_t workspace_bytes, float* mssd, int* mssd_sym, float* mspd, int* mspd_sym, float* add,
                    float* adds, void* stream);
 
+/* -------------------------------------------------------------------------
+ * VSD, the Visible Surface Discrepancy of BOP (picopose_amd/evaluation.py plans every call): per (estimate, ground truth) pair two
+ * depth renders of the object's mesh and a three-image comparison with the test depth image.  This is the BOP toolkit's
+ * pose_error.vsd with visib_mode = "bop19" and cost_type = "step", WRITTEN FROM MEMORY: the toolkit cannot be run next to this
+ * library, so parity with its pixels is UNPINNED.  Known places where it can differ: its renderer's sampling convention (here pixel
+ * centres at integer coordinates, raster contract item 2) and its geometric near-plane clipping (here a triangle with a vertex at
+ * Zc <= near is dropped whole and counted).
+ *
+ * THE DEFINITION.  Z_est, Z_gt: camera-Z depth renders (mm, 0 = background) of the mesh under the two poses; Z_test: the test depth
+ * in mm, "missing" where Z_test > 0 is false (zero, negative, NaN).  Per pixel (x, y) with the image's fx, fy, cx, cy:
+ *   r = sqrt(((x - cx) / fx)^2 + ((y - cy) / fy)^2 + 1),  D_* = Z_* r                                   (distance along the ray)
+ *   visib_gt  = D_gt  > 0 and (missing or D_gt  - D_test <= delta)
+ *   visib_est = D_est > 0 and (missing or D_est - D_test <= delta or visib_gt)
+ *   inter = visib_gt and visib_est, union = visib_gt or visib_est;  on inter: dd = |D_gt - D_est| / diameter, n_t = #{dd >= tau_t}
+ *   e_t = (n_t + |union| - |inter|) / |union|, and e_t = 1 when |union| = 0.
+ *
+ * THE DEPTH RASTER.  Items 1-5 and 7 of THE RASTER CONTRACT above apply unchanged and item 6 for Z only (no colour), with the
+ * vertices in millimetres, the camera of the view's image and sampling clipped to the view's WINDOW {x0, y0, x1, y1}
+ * (x0 <= x < x1, y0 <= y < y1, inside the frame) instead of the frame.  A window that contains every sample the full-frame render
+ * covers gives the full-frame render's bits (tests/vsd_oracle.py restates the windowed render; the kernels equal it bit for bit).
+ * A view with an empty window renders nothing and counts nothing.  A triangle whose clipped box holds at most 64 samples is walked
+ * by one lane, a larger one goes through a queue to 16 x 16 tiles, as in pp_render_views.
+ *
+ * THE PAIR REDUCTION, float32, one rounding per operation, never contracted, in this order:
+ *   xr = ((float) x - cx) / fx, yr = ((float) y - cy) / fy;  r = sqrtf((xr xr + yr yr) + 1);  D = Z r for est, gt and test;
+ *   the compares are D_model - D_test <= delta;  dd = fabsf(D_gt - D_est) / diameter, then dd >= tau_t.
+ * One workgroup per pair walks the union box of the two windows (outside a view's window its Z is 0).  |union|, |inter| and n_t
+ * are INTEGER counters per lane, reduced by xor-shuffles within a wave and through LDS across waves (no atomics), then
+ *   e_t = f32((double)(n_t + union - inter) / (double) union), or 1 when union = 0.
+ * Integers make the result independent of order, stream, pair order and of how the caller splits the pairs over calls.
+ *
+ * Objects: vertices (millimetres) and faces (indices LOCAL to their object) of every object concatenated, object o at rows
+ * [vert_off[o], vert_off[o + 1]) / [face_off[o], face_off[o + 1]); diameters (n_objects) fp32.  cams (n_images, 4) fp32 = fx, fy, cx, cy.
+ * Views: view_obj, view_img (n_views) int32, poses (n_views, 4, 4) fp32 row-major object -> camera, windows (n_views, 4) int32,
+ * view_zoff (n_views + 1) int64: the prefix sums of the windows' sample counts — view v owns z-buffer words
+ * [view_zoff[v], view_zoff[v + 1]).  Pairs: pair_est, pair_gt (n_pairs) int32 view indices.  depth (n_images, H, W) fp32 millimetres.
+ * Every table is a device pointer; the *_host arguments are HOST copies of the offset, window and index tables (and of faces,
+ * diameters, cams), validated here before any launch.  taus_host: n_taus floats on the host (they travel as kernel arguments).
+ * Outputs: vsd (n_pairs, n_taus) fp32, counts (n_pairs, 2 + n_taus) int32 = {union, inter, n_1 .. n_T}, near_count (n_views) uint32
+ * (zeroed here): the triangles of each view dropped at the near plane; depth_out (n_views, H, W) fp32 (0 = background) or NULL.
+ * n_pairs = 0 with depth_out renders only (the pair tables, depth, vsd and counts may then be NULL).
+ * Workspace (256-byte aligned): pp_vsd_workspace_bytes(window_samples, view_faces) = 256 + roundup256(8 window_samples) + 8 view_faces
+ * with window_samples = view_zoff[n_views] and view_faces = the sum over the views of their object's face count (one queue slot per
+ * (view, triangle)).  One call is one launch sequence over all its views: the caller (evaluation.vsd_errors) splits the PAIRS into
+ * groups whose views fit its workspace bound, one call per group, with identical results.  All work is enqueued on `stream`;
+ * nothing synchronises.
+ * PP_EINVAL (before any launch): a null pointer that is needed; n_objects / n_images / n_views / H / W <= 0, n_pairs < 0, n_pairs = 0
+ * without depth_out, H W >= 2^31; n_taus outside 1..PP_VSD_MAX_TAUS, a NaN tau; delta, near or a diameter not positive and finite;
+ * fx or fy = 0, a camera entry that is not finite; an offset table that does not start at 0, an object without vertices, a view whose object has no faces; a
+ * face index outside its object; a view's object or image index out of range; a window outside the frame or with x1 < x0 / y1 < y0;
+ * view_zoff not the prefix sums of the windows; a pair index out of range; a pair whose two views differ in image or object;
+ * view_faces >= 2^32.  PP_EWORKSPACE: workspace misaligned or smaller than pp_vsd_workspace_bytes says.
+ * ------------------------------------------------------------------------- */
+#define PP_VSD_MAX_TAUS 16
+int pp_vsd_workspace_bytes(long long window_samples, long long view_faces, size_t* bytes);
+int pp_vsd_errors(const float* vertices, const int* vert_off, const int* faces, const int* face_off, const float* diameters,
+                  const int* vert_off_host, const int* faces_host, const int* face_off_host, const float* diameters_host,
+                  int n_objects, const float* cams, const float* cams_host, int n_images, int H, int W, const int* view_obj,
+                  const int* view_img, const float* poses, const int* windows, const long long* view_zoff, const int* view_obj_host,
+                  const int* view_img_host, const int* windows_host, const long long* view_zoff_host, int n_views,
+                  const int* pair_est, const int* pair_gt, const int* pair_est_host, const int* pair_gt_host, int n_pairs,
+                  const float* depth, float delta, const float* taus_host, int n_taus, float near, void* workspace,
+                  size_t workspace_bytes, float* vsd, int* counts, unsigned int* near_count, float* depth_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -221,6 +221,9 @@ def lib():
                                         c.POINTER(c.c_double), c.POINTER(c.c_double), vp, vp, vp, vp]
         L.pp_pose_errors_workspace_bytes.argtypes = [i32, i32, i32, i32, c.POINTER(sz)]
         L.pp_pose_errors.argtypes = [vp] * 10 + [i32] + [vp] * 7 + [i32, i32, vp, sz] + [vp] * 7
+        L.pp_vsd_workspace_bytes.argtypes = [ll, ll, c.POINTER(sz)]
+        L.pp_vsd_errors.argtypes = ([vp] * 9 + [i32, vp, vp, i32, i32, i32] + [vp] * 9 + [i32] + [vp] * 4 + [i32, vp, f32, vp, i32, f32,
+                                    vp, sz] + [vp] * 5)
         _lib = L
     return _lib
 

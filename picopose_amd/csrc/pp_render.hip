@@ -18,114 +18,14 @@
 #include "pp_crop_dev.h"
 
 #pragma clang fp contract(off)
+#include "pp_raster_dev.h"   // snap, tri_setup, edge_fn, edge_owns, covers, weights, depth_test: shared with pp_vsd.hip
 
 namespace {
 
-constexpr int SUB = 256;                 // sub-pixel units per pixel
-constexpr float SNAP_LIMIT = 268435456.f;   // 2^28 sub-pixel units: the edge functions stay below 2^60
-constexpr int SMALL_BOX = 64;            // samples a single lane walks
-constexpr int TILE = 16;
 constexpr size_t WS_HEADER = 256;
 
-enum : int { TRI_OK = 0, TRI_NEAR = 1, TRI_SKIP = 2 };
-
-struct Cam {
-    float fx, fy, cx, cy, near;
-    int H, W;
-};
-
-struct Tri {
-    int x[3], y[3];      // snapped screen coordinates, ordered so that area2 > 0
-    int id[3];           // vertex indices in that order
-    float iz[3];         // 1 / Zc
-    long long area2;
-    int bx0, bx1, by0, by1;   // inclusive sample box, clipped to the frame
-};
-
-__device__ __forceinline__ int snap(float u) {
-    const float s = fminf(fmaxf(u * (float)SUB, -SNAP_LIMIT), SNAP_LIMIT);
-    return (int)rintf(s);
-}
-
-__device__ __forceinline__ int tri_setup(const float* __restrict__ verts, const int* __restrict__ faces, int Nv,
-                                         const float* __restrict__ P, const Cam& c, int f, Tri& t) {
-    bool near_hit = false;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int id = faces[3 * (size_t)f + k];
-        if ((unsigned)id >= (unsigned)Nv) return TRI_SKIP;   // (the entry validated the host copy; never a fault)
-        const float X = verts[3 * (size_t)id], Y = verts[3 * (size_t)id + 1], Z = verts[3 * (size_t)id + 2];
-        const float xc = ((P[0] * X + P[1] * Y) + P[2] * Z) + P[3];
-        const float yc = ((P[4] * X + P[5] * Y) + P[6] * Z) + P[7];
-        const float zc = ((P[8] * X + P[9] * Y) + P[10] * Z) + P[11];
-        t.id[k] = id;
-        if (!(zc > c.near)) {
-            near_hit = true;
-            t.x[k] = t.y[k] = 0;
-            t.iz[k] = 0.f;
-        } else {
-            t.x[k] = snap((c.fx * xc) / zc + c.cx);
-            t.y[k] = snap((c.fy * yc) / zc + c.cy);
-            t.iz[k] = 1.f / zc;
-        }
-    }
-    if (near_hit) return TRI_NEAR;
-    long long area2 = (long long)(t.x[1] - t.x[0]) * (t.y[2] - t.y[0]) - (long long)(t.y[1] - t.y[0]) * (t.x[2] - t.x[0]);
-    if (area2 == 0) return TRI_SKIP;
-    if (area2 < 0) {
-        area2 = -area2;
-        int s = t.x[1]; t.x[1] = t.x[2]; t.x[2] = s;
-        s = t.y[1]; t.y[1] = t.y[2]; t.y[2] = s;
-        s = t.id[1]; t.id[1] = t.id[2]; t.id[2] = s;
-        const float z = t.iz[1]; t.iz[1] = t.iz[2]; t.iz[2] = z;
-    }
-    t.area2 = area2;
-    const int xmin = min(t.x[0], min(t.x[1], t.x[2])), xmax = max(t.x[0], max(t.x[1], t.x[2]));
-    const int ymin = min(t.y[0], min(t.y[1], t.y[2])), ymax = max(t.y[0], max(t.y[1], t.y[2]));
-    t.bx0 = max((xmin + SUB - 1) >> 8, 0);       // ceil / floor of the sub-pixel extent (arithmetic shifts)
-    t.bx1 = min(xmax >> 8, c.W - 1);
-    t.by0 = max((ymin + SUB - 1) >> 8, 0);
-    t.by1 = min(ymax >> 8, c.H - 1);
-    if (t.bx0 > t.bx1 || t.by0 > t.by1) return TRI_SKIP;
-    return TRI_OK;
-}
-
-// edge function of a -> b at the sample (px, py) (pixels): > 0 inside for area2 > 0
-__device__ __forceinline__ long long edge_fn(int ax, int ay, int bx, int by, int px, int py) {
-    return (long long)(bx - ax) * ((long long)py * SUB - ay) - (long long)(by - ay) * ((long long)px * SUB - ax);
-}
-// top-left rule: a sample exactly on the edge a -> b belongs to the triangle when the edge is a left edge (dy < 0) or a top edge
-// (dy == 0, dx > 0) of the positively ordered triangle
-__device__ __forceinline__ bool edge_owns(int ax, int ay, int bx, int by) { return by < ay || (by == ay && bx > ax); }
-
-__device__ __forceinline__ bool covers(const Tri& t, int px, int py, long long w[3]) {
-    w[0] = edge_fn(t.x[1], t.y[1], t.x[2], t.y[2], px, py);
-    w[1] = edge_fn(t.x[2], t.y[2], t.x[0], t.y[0], px, py);
-    w[2] = edge_fn(t.x[0], t.y[0], t.x[1], t.y[1], px, py);
-    if (w[0] < 0 || w[1] < 0 || w[2] < 0) return false;
-    if (w[0] == 0 && !edge_owns(t.x[1], t.y[1], t.x[2], t.y[2])) return false;
-    if (w[1] == 0 && !edge_owns(t.x[2], t.y[2], t.x[0], t.y[0])) return false;
-    if (w[2] == 0 && !edge_owns(t.x[0], t.y[0], t.x[1], t.y[1])) return false;
-    return true;
-}
-
-// perspective weights p_k = (w_k / area2) / Z_k and their sum q = 1 / Z
-__device__ __forceinline__ float weights(const Tri& t, const long long w[3], float p[3]) {
-    const float a = (float)t.area2;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) p[k] = ((float)w[k] / a) * t.iz[k];
-    return (p[0] + p[1]) + p[2];
-}
-
 __device__ __forceinline__ void shade(const Tri& t, int px, int py, int face, unsigned long long* __restrict__ zrow) {
-    long long w[3];
-    if (!covers(t, px, py, w)) return;
-    float p[3];
-    const float z = 1.f / weights(t, w, p);
-    const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)face;
-    unsigned long long* slot = zrow + px;
-    // the slot only ever decreases: a (possibly stale) value at or below the key already rules this fragment out
-    if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > key) atomicMin(slot, key);
+    depth_test(t, px, py, face, zrow + px);
 }
 
 __global__ __launch_bounds__(256) void raster_small_kernel(const float* __restrict__ verts, const int* __restrict__ faces, int Nv,
@@ -166,14 +66,7 @@ __global__ __launch_bounds__(TILE * TILE) void raster_large_kernel(const float* 
         for (int tile = blockIdx.x; tile < ntx * nty; tile += gridDim.x) {
             const int x0 = t.bx0 + (tile % ntx) * TILE, y0 = t.by0 + (tile / ntx) * TILE;
             const int x1 = min(x0 + TILE - 1, t.bx1), y1 = min(y0 + TILE - 1, t.by1);
-            bool out = false;   // an edge with all four tile corners outside: no sample of the tile is covered
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const int a = (k + 1) % 3, b = (k + 2) % 3;
-                out |= edge_fn(t.x[a], t.y[a], t.x[b], t.y[b], x0, y0) < 0 && edge_fn(t.x[a], t.y[a], t.x[b], t.y[b], x1, y0) < 0 &&
-                       edge_fn(t.x[a], t.y[a], t.x[b], t.y[b], x0, y1) < 0 && edge_fn(t.x[a], t.y[a], t.x[b], t.y[b], x1, y1) < 0;
-            }
-            if (out) continue;
+            if (tile_outside(t, x0, y0, x1, y1)) continue;   // an edge with all four tile corners outside
             const int px = x0 + tx, py = y0 + ty;
             if (px <= x1 && py <= y1) shade(t, px, py, (int)q.y, zv + (size_t)py * cam.W);
         }

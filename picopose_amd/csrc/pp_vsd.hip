@@ -1,0 +1,334 @@
+// BOP19 VSD of (estimate, ground truth) pairs (picopose_amd/evaluation.py plans every call; the contract is stated in
+// include/picopose_hip.h and restated in numpy by tests/vsd_oracle.py).
+//
+//   vsd_raster_small_kernel  one lane per (view, triangle of the view's object): tri_setup under the view's camera and window; a box
+//                            of at most SMALL_BOX samples is walked by the lane, a larger one goes to the queue
+//   vsd_raster_large_kernel  queue entries -> 16 x 16 tiles, one workgroup step per tile (the template renderer's scheme)
+//   vsd_depth_kernel         optional: the window's z-buffer words -> a dense (n_views, H, W) float32 depth image
+//   vsd_pair_kernel          one workgroup per pair: walks the union box of the two windows, reads Z_est / Z_gt from the z-buffer
+//                            words and the test depth from the image, keeps |union|, |inter| and n_1 .. n_T as per-lane INTEGERS,
+//                            reduces them by xor-shuffles and through LDS, and divides once in float64
+//
+// The z-buffer is ragged: 8 bytes per WINDOW sample, view v at words [view_zoff[v], view_zoff[v + 1]).  Depth is a 64-bit unsigned
+// atomic minimum over (bits of Z) << 32 | face and the pair reduction adds integers: no result depends on launch order, stream, pair
+// order or on how the caller splits the pairs over calls.
+#include <stdint.h>
+#include <limits.h>
+#include <math.h>
+#include "pp_common.h"
+
+#pragma clang fp contract(off)
+#include "pp_raster_dev.h"
+
+namespace {
+
+constexpr size_t WS_HEADER = 256;
+constexpr int BLOCK = 256;
+constexpr int WAVES = BLOCK / 64;
+constexpr int NC = 2 + PP_VSD_MAX_TAUS;   // counters of a pair: union, inter, n_1 .. n_16
+
+struct Taus {
+    float v[PP_VSD_MAX_TAUS];
+};
+
+// the tables of a call (device pointers)
+struct Scene {
+    const float* verts;
+    const int* vert_off;
+    const int* faces;
+    const int* face_off;
+    const float* cams;         // (n_images, 4) fx, fy, cx, cy
+    const int* view_obj;
+    const int* view_img;
+    const float* poses;        // (n_views, 16)
+    const int* windows;        // (n_views, 4) x0, y0, x1, y1 (exclusive upper corner)
+    const long long* view_zoff;
+    int n_views, H, W;
+    float near;
+};
+
+struct View {
+    const float* verts;
+    const int* faces;
+    const float* pose;
+    int Nv, Nf, x0, y0, ww;
+    Cam cam;
+};
+
+// false: the view's window is empty, nothing is rendered
+__device__ __forceinline__ bool load_view(const Scene& s, int v, View& out) {
+    const int* w = s.windows + 4 * (size_t)v;
+    const int x0 = w[0], y0 = w[1], x1 = w[2], y1 = w[3];
+    if (x1 <= x0 || y1 <= y0) return false;
+    const int o = s.view_obj[v];
+    const float* k = s.cams + 4 * (size_t)s.view_img[v];
+    const int v0 = s.vert_off[o], f0 = s.face_off[o];
+    out.verts = s.verts + 3 * (size_t)v0;
+    out.Nv = s.vert_off[o + 1] - v0;
+    out.faces = s.faces + 3 * (size_t)f0;
+    out.Nf = s.face_off[o + 1] - f0;
+    out.pose = s.poses + 16 * (size_t)v;
+    out.x0 = x0;
+    out.y0 = y0;
+    out.ww = x1 - x0;
+    out.cam = Cam{k[0], k[1], k[2], k[3], s.near, s.H, s.W, x0, y0, x1, y1};
+    return true;
+}
+
+__device__ __forceinline__ unsigned long long* slot_of(unsigned long long* zv, const View& vw, int px, int py) {
+    return zv + (size_t)(py - vw.y0) * vw.ww + (px - vw.x0);
+}
+
+// view blockIdx.y, blockIdx.y + gridDim.y, ...; faces blockIdx.x * 256 + lane of that view's object
+__global__ __launch_bounds__(BLOCK) void vsd_raster_small_kernel(Scene s, unsigned long long* __restrict__ zbuf,
+                                                                 uint2* __restrict__ queue, unsigned* __restrict__ qcount,
+                                                                 unsigned* __restrict__ near_count) {
+    const int f = blockIdx.x * BLOCK + threadIdx.x;
+    for (int v = blockIdx.y; v < s.n_views; v += gridDim.y) {
+        View vw;
+        if (!load_view(s, v, vw) || f >= vw.Nf) continue;
+        Tri t;
+        const int st = tri_setup(vw.verts, vw.faces, vw.Nv, vw.pose, vw.cam, f, t);
+        if (st == TRI_NEAR) atomicAdd(near_count + v, 1u);
+        if (st != TRI_OK) continue;
+        if ((t.bx1 - t.bx0 + 1) * (long long)(t.by1 - t.by0 + 1) > SMALL_BOX) {
+            queue[atomicAdd(qcount, 1u)] = make_uint2((unsigned)v, (unsigned)f);
+            continue;
+        }
+        unsigned long long* zv = zbuf + s.view_zoff[v];
+        for (int py = t.by0; py <= t.by1; ++py)
+            for (int px = t.bx0; px <= t.bx1; ++px) depth_test(t, px, py, f, slot_of(zv, vw, px, py));
+    }
+}
+
+// queue entry blockIdx.y, blockIdx.y + gridDim.y, ...; its tiles blockIdx.x, blockIdx.x + gridDim.x, ...
+__global__ __launch_bounds__(TILE * TILE) void vsd_raster_large_kernel(Scene s, unsigned long long* __restrict__ zbuf,
+                                                                       const uint2* __restrict__ queue,
+                                                                       const unsigned* __restrict__ qcount) {
+    const unsigned n = *qcount;
+    const int ty = threadIdx.x / TILE, tx = threadIdx.x % TILE;
+    for (unsigned e = blockIdx.y; e < n; e += gridDim.y) {
+        const uint2 q = queue[e];
+        if (q.x >= (unsigned)s.n_views) continue;
+        View vw;
+        if (!load_view(s, (int)q.x, vw) || q.y >= (unsigned)vw.Nf) continue;
+        Tri t;
+        if (tri_setup(vw.verts, vw.faces, vw.Nv, vw.pose, vw.cam, (int)q.y, t) != TRI_OK) continue;
+        unsigned long long* zv = zbuf + s.view_zoff[q.x];
+        const int ntx = (t.bx1 - t.bx0) / TILE + 1, nty = (t.by1 - t.by0) / TILE + 1;
+        for (int tile = blockIdx.x; tile < ntx * nty; tile += gridDim.x) {
+            const int x0 = t.bx0 + (tile % ntx) * TILE, y0 = t.by0 + (tile / ntx) * TILE;
+            const int x1 = min(x0 + TILE - 1, t.bx1), y1 = min(y0 + TILE - 1, t.by1);
+            if (tile_outside(t, x0, y0, x1, y1)) continue;
+            const int px = x0 + tx, py = y0 + ty;
+            if (px <= x1 && py <= y1) depth_test(t, px, py, (int)q.y, slot_of(zv, vw, px, py));
+        }
+    }
+}
+
+__device__ __forceinline__ float word_depth(unsigned long long key) {
+    return key == ~0ull ? 0.f : __uint_as_float((unsigned)(key >> 32));
+}
+
+// view blockIdx.y, ...: the covered samples of its window into the (zeroed) dense image
+__global__ __launch_bounds__(BLOCK) void vsd_depth_kernel(Scene s, const unsigned long long* __restrict__ zbuf,
+                                                          float* __restrict__ depth_out) {
+    for (int v = blockIdx.y; v < s.n_views; v += gridDim.y) {
+        const int* w = s.windows + 4 * (size_t)v;
+        const int x0 = w[0], y0 = w[1], ww = w[2] - w[0], wh = w[3] - w[1];
+        if (ww <= 0 || wh <= 0) continue;
+        const unsigned long long* zv = zbuf + s.view_zoff[v];
+        float* out = depth_out + (size_t)v * s.H * s.W;
+        for (int i = blockIdx.x * BLOCK + threadIdx.x; i < ww * wh; i += gridDim.x * BLOCK) {
+            const int y = i / ww, x = i - y * ww;
+            const unsigned long long key = zv[i];
+            if (key != ~0ull) out[(size_t)(y0 + y) * s.W + (x0 + x)] = word_depth(key);
+        }
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void vsd_pair_kernel(Scene s, const unsigned long long* __restrict__ zbuf,
+                                                         const int* __restrict__ pair_est, const int* __restrict__ pair_gt,
+                                                         const float* __restrict__ diameters, const float* __restrict__ depth,
+                                                         float delta, Taus taus, int T, float* __restrict__ vsd,
+                                                         int* __restrict__ counts) {
+    const int p = blockIdx.x;
+    const int ve = pair_est[p], vg = pair_gt[p];
+    const int* we = s.windows + 4 * (size_t)ve;
+    const int* wg = s.windows + 4 * (size_t)vg;
+    const int ex0 = we[0], ey0 = we[1], ex1 = we[2], ey1 = we[3];
+    const int gx0 = wg[0], gy0 = wg[1], gx1 = wg[2], gy1 = wg[3];
+    const bool has_e = ex1 > ex0 && ey1 > ey0, has_g = gx1 > gx0 && gy1 > gy0;
+    // the union box of the two windows (an empty window contributes nothing)
+    int ux0 = 0, uy0 = 0, ux1 = 0, uy1 = 0;
+    if (has_e && has_g) {
+        ux0 = min(ex0, gx0), uy0 = min(ey0, gy0), ux1 = max(ex1, gx1), uy1 = max(ey1, gy1);
+    } else if (has_e) {
+        ux0 = ex0, uy0 = ey0, ux1 = ex1, uy1 = ey1;
+    } else if (has_g) {
+        ux0 = gx0, uy0 = gy0, ux1 = gx1, uy1 = gy1;
+    }
+    const int img = s.view_img[ve];
+    const float* k = s.cams + 4 * (size_t)img;
+    const float fx = k[0], fy = k[1], cx = k[2], cy = k[3];
+    const float diameter = diameters[s.view_obj[ve]];
+    const unsigned long long* ze = zbuf + s.view_zoff[ve];
+    const unsigned long long* zg = zbuf + s.view_zoff[vg];
+    const float* dimg = depth + (size_t)img * s.H * s.W;
+    int cnt[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) cnt[c] = 0;
+    const int bw = ux1 - ux0, n = bw * (uy1 - uy0);
+    for (int i = threadIdx.x; i < n; i += BLOCK) {
+        const int yy = i / bw, y = uy0 + yy, x = ux0 + (i - yy * bw);
+        float z_est = 0.f, z_gt = 0.f;
+        if (has_e && x >= ex0 && x < ex1 && y >= ey0 && y < ey1) z_est = word_depth(ze[(size_t)(y - ey0) * (ex1 - ex0) + (x - ex0)]);
+        if (has_g && x >= gx0 && x < gx1 && y >= gy0 && y < gy1) z_gt = word_depth(zg[(size_t)(y - gy0) * (gx1 - gx0) + (x - gx0)]);
+        if (!(z_est > 0.f) && !(z_gt > 0.f)) continue;           // neither model covers the sample: in no set
+        const float z_test = dimg[(size_t)y * s.W + x];
+        const bool missing = !(z_test > 0.f);
+        const float xr = ((float)x - cx) / fx, yr = ((float)y - cy) / fy;
+        const float r = sqrtf((xr * xr + yr * yr) + 1.f);
+        const float d_est = z_est * r, d_gt = z_gt * r, d_test = z_test * r;
+        const bool visib_gt = d_gt > 0.f && (missing || d_gt - d_test <= delta);
+        const bool visib_est = d_est > 0.f && (missing || d_est - d_test <= delta || visib_gt);
+        cnt[0] += (visib_gt || visib_est) ? 1 : 0;
+        if (visib_gt && visib_est) {
+            cnt[1] += 1;
+            const float dd = fabsf(d_gt - d_est) / diameter;
+#pragma unroll
+            for (int t = 0; t < PP_VSD_MAX_TAUS; ++t) cnt[2 + t] += (t < T && dd >= taus.v[t]) ? 1 : 0;
+        }
+    }
+    __shared__ int sm[WAVES][NC];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        int v = cnt[c];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+        if (lane == 0) sm[wave][c] = v;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < 2 + T) {
+        int v = sm[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) v += sm[w][threadIdx.x];
+        counts[(size_t)p * (2 + T) + threadIdx.x] = v;
+        if (threadIdx.x >= 2) {
+            int uni = 0, inter = 0;
+#pragma unroll
+            for (int w = 0; w < WAVES; ++w) {
+                uni += sm[w][0];
+                inter += sm[w][1];
+            }
+            vsd[(size_t)p * T + (threadIdx.x - 2)] = uni > 0 ? (float)((double)(v + uni - inter) / (double)uni) : 1.f;
+        }
+    }
+}
+
+inline size_t align256(size_t n) { return (n + 255) / 256 * 256; }
+
+inline bool positive_finite(float v) { return v > 0.f && v <= 3.402823466e38f; }
+
+}  // namespace
+
+extern "C" {
+
+int pp_vsd_workspace_bytes(long long window_samples, long long view_faces, size_t* bytes) {
+    if (!bytes || window_samples < 0 || view_faces <= 0 || window_samples > (LLONG_MAX >> 5) || view_faces > (long long)UINT_MAX)
+        return PP_EINVAL;
+    *bytes = WS_HEADER + align256((size_t)window_samples * 8) + (size_t)view_faces * 8;
+    return PP_OK;
+}
+
+int pp_vsd_errors(const float* vertices, const int* vert_off, const int* faces, const int* face_off, const float* diameters,
+                  const int* vert_off_host, const int* faces_host, const int* face_off_host, const float* diameters_host,
+                  int n_objects, const float* cams, const float* cams_host, int n_images, int H, int W, const int* view_obj,
+                  const int* view_img, const float* poses, const int* windows, const long long* view_zoff, const int* view_obj_host,
+                  const int* view_img_host, const int* windows_host, const long long* view_zoff_host, int n_views,
+                  const int* pair_est, const int* pair_gt, const int* pair_est_host, const int* pair_gt_host, int n_pairs,
+                  const float* depth, float delta, const float* taus_host, int n_taus, float near, void* workspace,
+                  size_t workspace_bytes, float* vsd, int* counts, unsigned int* near_count, float* depth_out, void* stream) {
+    if (!vertices || !vert_off || !faces || !face_off || !diameters || !vert_off_host || !faces_host || !face_off_host ||
+        !diameters_host || !cams || !cams_host || !view_obj || !view_img || !poses || !windows || !view_zoff || !view_obj_host ||
+        !view_img_host || !windows_host || !view_zoff_host || !taus_host || !workspace || !near_count)
+        return PP_EINVAL;
+    if (n_objects <= 0 || n_images <= 0 || n_views <= 0 || n_pairs < 0 || H <= 0 || W <= 0 || (long long)H * W > INT_MAX ||
+        n_taus < 1 || n_taus > PP_VSD_MAX_TAUS || !positive_finite(delta) || !positive_finite(near))
+        return PP_EINVAL;
+    if (n_pairs == 0 && !depth_out) return PP_EINVAL;             // nothing to do
+    if (n_pairs > 0 && (!pair_est || !pair_gt || !pair_est_host || !pair_gt_host || !depth || !vsd || !counts)) return PP_EINVAL;
+    for (int t = 0; t < n_taus; ++t)
+        if (!(taus_host[t] == taus_host[t])) return PP_EINVAL;
+    if (vert_off_host[0] != 0 || face_off_host[0] != 0) return PP_EINVAL;
+    for (int o = 0; o < n_objects; ++o) {
+        if (vert_off_host[o + 1] <= vert_off_host[o] || face_off_host[o + 1] < face_off_host[o]) return PP_EINVAL;
+        if (!positive_finite(diameters_host[o])) return PP_EINVAL;
+        const unsigned nv = (unsigned)(vert_off_host[o + 1] - vert_off_host[o]);
+        for (size_t k = 3 * (size_t)face_off_host[o]; k < 3 * (size_t)face_off_host[o + 1]; ++k)
+            if ((unsigned)faces_host[k] >= nv) return PP_EINVAL;
+    }
+    for (int i = 0; i < n_images; ++i) {
+        const float* k = cams_host + 4 * (size_t)i;
+        if (k[0] == 0.f || k[1] == 0.f || !(fabsf(k[0]) <= 3.402823466e38f) || !(fabsf(k[1]) <= 3.402823466e38f) ||
+            !(fabsf(k[2]) <= 3.402823466e38f) || !(fabsf(k[3]) <= 3.402823466e38f))
+            return PP_EINVAL;
+    }
+    if (view_zoff_host[0] != 0) return PP_EINVAL;
+    long long total_faces = 0;
+    int max_faces = 0;
+    for (int v = 0; v < n_views; ++v) {
+        const int o = view_obj_host[v];
+        if ((unsigned)o >= (unsigned)n_objects || (unsigned)view_img_host[v] >= (unsigned)n_images) return PP_EINVAL;
+        const int nf = face_off_host[o + 1] - face_off_host[o];
+        if (nf <= 0) return PP_EINVAL;                            // an object of the call without faces
+        const int* w = windows_host + 4 * (size_t)v;
+        if (w[0] < 0 || w[1] < 0 || w[2] < w[0] || w[3] < w[1] || w[2] > W || w[3] > H) return PP_EINVAL;
+        if (view_zoff_host[v + 1] - view_zoff_host[v] != (long long)(w[2] - w[0]) * (w[3] - w[1])) return PP_EINVAL;
+        total_faces += nf;
+        max_faces = nf > max_faces ? nf : max_faces;
+    }
+    if (total_faces > (long long)UINT_MAX) return PP_EINVAL;
+    for (int p = 0; p < n_pairs; ++p) {
+        const int e = pair_est_host[p], g = pair_gt_host[p];
+        if ((unsigned)e >= (unsigned)n_views || (unsigned)g >= (unsigned)n_views) return PP_EINVAL;
+        if (view_obj_host[e] != view_obj_host[g] || view_img_host[e] != view_img_host[g]) return PP_EINVAL;
+    }
+    const long long samples = view_zoff_host[n_views];
+    size_t need = 0;
+    if (pp_vsd_workspace_bytes(samples, total_faces, &need) != PP_OK) return PP_EINVAL;
+    if (((uintptr_t)workspace % 256) != 0 || workspace_bytes < need) return PP_EWORKSPACE;
+
+    hipStream_t st = (hipStream_t)stream;
+    unsigned* qcount = (unsigned*)workspace;
+    unsigned long long* zbuf = (unsigned long long*)((char*)workspace + WS_HEADER);
+    uint2* queue = (uint2*)((char*)zbuf + align256((size_t)samples * 8));
+    const Scene s{vertices, vert_off, faces, face_off, cams, view_obj, view_img, poses, windows, view_zoff, n_views, H, W, near};
+    const unsigned gv = (unsigned)(n_views < 65535 ? n_views : 65535);
+    PP_CHECK_HIP(hipMemsetAsync(near_count, 0, sizeof(unsigned) * (size_t)n_views, st));
+    PP_CHECK_HIP(hipMemsetAsync(qcount, 0, sizeof(unsigned), st));
+    if (samples > 0) PP_CHECK_HIP(hipMemsetAsync(zbuf, 0xFF, (size_t)samples * 8, st));
+    if (samples > 0) {
+        hipLaunchKernelGGL(vsd_raster_small_kernel, dim3((unsigned)((max_faces + BLOCK - 1) / BLOCK), gv), dim3(BLOCK), 0, st, s, zbuf,
+                           queue, qcount, near_count);
+        const unsigned gy = (unsigned)(total_faces < 4096 ? total_faces : 4096);
+        hipLaunchKernelGGL(vsd_raster_large_kernel, dim3(8, gy), dim3(TILE * TILE), 0, st, s, zbuf, queue, qcount);
+    }
+    if (depth_out) {
+        PP_CHECK_HIP(hipMemsetAsync(depth_out, 0, (size_t)n_views * H * W * sizeof(float), st));
+        if (samples > 0) {
+            const long long per = ((long long)H * W + BLOCK - 1) / BLOCK;
+            hipLaunchKernelGGL(vsd_depth_kernel, dim3((unsigned)(per < 64 ? per : 64), gv), dim3(BLOCK), 0, st, s, zbuf, depth_out);
+        }
+    }
+    if (n_pairs > 0) {
+        Taus taus;
+        for (int t = 0; t < PP_VSD_MAX_TAUS; ++t) taus.v[t] = t < n_taus ? taus_host[t] : INFINITY;
+        hipLaunchKernelGGL(vsd_pair_kernel, dim3((unsigned)n_pairs), dim3(BLOCK), 0, st, s, zbuf, pair_est, pair_gt, diameters, depth,
+                           delta, taus, n_taus, vsd, counts);
+    }
+    return pp_last_launch();
+}
+
+}  // extern "C"

@@ -5,6 +5,8 @@ Object Localization", section 2.2), ADD and ADD-S (Hinterstoisser et al. 2012), 
     err = pose_errors(models, obj_ids, R_est, t_est, R_gt, t_gt, K=K)            # {"mssd", "mspd", "mssd_sym", "mspd_sym"}
     res = match_and_score(read_bop_results(csv), {scene: read_scene_gt(...)}, read_targets(...), models,
                           {scene: read_scene_camera(...)})                        # {"AR_MSSD", "AR_MSPD", "vsd": None, ...}
+    vsd = vsd_errors(models, obj_ids, R_est, t_est, R_gt, t_gt, K, depth_u16, depth_scale=1.0)   # needs "faces" in the models
+    res = match_and_score(..., depth_images=lambda scene, im: depth_png_as_array)  # adds "AR_VSD" and "AR" = the three-term mean
 
 For an estimate (R^, t^), a ground truth (R_, t_), the model vertices V (millimetres), the object's symmetry set S and the camera K:
 
@@ -14,9 +16,15 @@ For an estimate (R^, t^), a ground truth (R_, t_), the model vertices V (millime
     ADD-S = mean over x of min over y in V of |(R^ x + t^) - (R_ y + t_)|
 
 The arithmetic of the kernels (float32, stated operation by operation in include/picopose_hip.h) is restated in numpy by
-tests/pose_error_oracle.py.  VSD, the third term of the BOP average recall, needs the test depth images and a depth render of every
-estimate and is NOT computed here: match_and_score returns "vsd": None and no three-term average.  Translations are millimetres
-everywhere, as the results rows (pipeline.bop_csv_lines) and scene_gt.json hold them."""
+tests/pose_error_oracle.py.  Translations are millimetres everywhere, as the results rows (pipeline.bop_csv_lines) and scene_gt.json
+hold them.
+
+VSD, the third term of the BOP average recall, needs the test depth images and two depth renders per pair, so it has its own entry
+point: vsd_errors renders every distinct (image, object, pose) view once into a ragged z-buffer (a host-planned window per view)
+and reduces every pair on the device (csrc/pp_vsd.hip; the definition and the arithmetic are stated in include/picopose_hip.h and
+restated by tests/vsd_oracle.py).  It is the BOP toolkit's VSD (visib_mode "bop19", step cost) written from memory: parity with
+the toolkit's pixels is unpinned, and a triangle that reaches the near plane is dropped whole where the toolkit's renderer clips it.
+match_and_score computes it when it is given the depth images, and then also returns AR = (AR_VSD + AR_MSSD + AR_MSPD) / 3."""
 import ctypes
 import json
 import math
@@ -31,6 +39,9 @@ KINDS = {"mssd": 1, "mspd": 2, "add": 4, "adds": 8}             # PP_EVAL_* of i
 DEFAULT_WORKSPACE_BYTES = 256 << 20
 MSSD_THRESHOLDS = np.arange(1, 11) / 20.0                       # 0.05 .. 0.5 of the object diameter
 MSPD_THRESHOLDS = np.arange(1, 11) * 5.0                        # 5 r .. 50 r pixels, r = image_width / 640
+VSD_TAUS = np.arange(1, 11) / 20.0                              # misalignment tolerances, 0.05 .. 0.5 of the object diameter
+VSD_THRESHOLDS = np.arange(1, 11) / 20.0                        # a pair is correct at (tau, theta) when e_tau < theta
+VSD_MAX_TAUS = 16                                               # PP_VSD_MAX_TAUS
 
 
 def _rotation(axis, angle):
@@ -89,7 +100,9 @@ def symmetry_transforms(model_info, max_sym_disc_step=0.01):
 
 class ObjectModels:
     """The models of a dataset, uploaded once: {obj_id: {"vertices": (Nv, 3) millimetres (as template_bank.load_ply returns them),
-    "info": the object's models_info.json entry}}.  Holds every object's vertices concatenated, their symmetry transforms
+    "info": the object's models_info.json entry, optionally "faces": (Nf, 3) integer vertex indices (as load_ply returns them; needed
+    by vsd_errors and render_depth only — `has_faces` says whether every object has them)}}.  Holds every object's vertices (and
+    faces, indices local to their object) concatenated, their symmetry transforms
     (symmetry_transforms) concatenated as float32 (R, t), the offset tables and the diameters (`info["diameter"]`).
     max_points: None, or a bound on the vertices ADD-S runs on: every ceil(Nv / max_points)-th vertex is kept (deterministic);
     the other errors always use every vertex, and pose_errors reports the bound under "adds_max_points"."""
@@ -102,7 +115,7 @@ class ObjectModels:
         self.obj_ids = [int(k) for k in objects]
         self.index = {o: k for k, o in enumerate(self.obj_ids)}
         self.max_points, self.device = max_points, torch.device(device)
-        verts, sub, syms, diam = [], [], [], []
+        verts, sub, syms, diam, faces = [], [], [], [], []
         for key, obj in objects.items():
             v = np.asarray(obj["vertices"])
             if v.ndim != 2 or v.shape[1] != 3 or len(v) == 0 or not np.issubdtype(v.dtype, np.floating):
@@ -115,6 +128,17 @@ class ObjectModels:
                 raise ValueError(f"object {key}: info['diameter'] must be a positive number")
             v = np.ascontiguousarray(v, dtype=np.float32)
             verts.append(v)
+            f = obj.get("faces")
+            if f is None:
+                f = np.zeros((0, 3), dtype=np.int32)
+            else:
+                f = np.asarray(f)
+                if f.ndim != 2 or f.shape[1] != 3 or len(f) == 0 or not np.issubdtype(f.dtype, np.integer):
+                    raise ValueError(f"object {key}: faces must be a non-empty (Nf, 3) integer array, got {f.dtype} {f.shape}")
+                if f.min() < 0 or f.max() >= len(v):
+                    raise ValueError(f"object {key}: a face index lies outside [0, {len(v)})")
+                f = np.ascontiguousarray(f, dtype=np.int32)
+            faces.append(f)
             sub.append(v if max_points is None else np.ascontiguousarray(v[::-(-len(v) // max_points)]))
             syms.append(symmetry_transforms(info, max_sym_disc_step))
             diam.append(d)
@@ -123,6 +147,12 @@ class ObjectModels:
         self.vert_off = self._offsets(verts)
         self.adds_off = self.vert_off if max_points is None else self._offsets(sub)
         self.sym_off = self._offsets(syms)
+        self.face_off = self._offsets(faces)
+        self.faces_host = np.concatenate(faces)
+        self.has_faces = all(len(f) for f in faces)
+        self.diameters_f32 = self.diameters.astype(np.float32)
+        self.aabb_corners = [np.array([[x, y, z] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])], dtype=np.float64)
+                             for lo, hi in ((v.min(axis=0), v.max(axis=0)) for v in verts)]          # per object (8, 3)
         sym = np.concatenate(syms)
         self.sym_R_host = np.ascontiguousarray(sym[:, :3, :3].reshape(-1, 9).astype(np.float32))
         self.sym_t_host = np.ascontiguousarray(sym[:, :3, 3].astype(np.float32))
@@ -134,6 +164,8 @@ class ObjectModels:
         self.sym_R, self.sym_t = up(self.sym_R_host), up(self.sym_t_host)
         self.vert_off_d, self.sym_off_d = up(self.vert_off), up(self.sym_off)
         self.adds_off_d = self.vert_off_d if max_points is None else up(self.adds_off)
+        self.faces = up(self.faces_host) if len(self.faces_host) else None
+        self.face_off_d, self.diameters_d = up(self.face_off), up(self.diameters_f32)
 
     @staticmethod
     def _offsets(parts):
@@ -149,6 +181,10 @@ class ObjectModels:
 
     def diameter(self, obj_id):
         return float(self.diameters[self.index[int(obj_id)]])
+
+    def n_faces(self, obj_id):
+        k = self.index[int(obj_id)]
+        return int(self.face_off[k + 1] - self.face_off[k])
 
 
 def _pose_tensor(name, a, P, tail, device):
@@ -209,7 +245,7 @@ def pose_errors(models, obj_ids, R_est, t_est, R_gt, t_gt, K=None, kinds=("mssd"
     has +inf when all have.  A pose that holds a NaN or an infinity gives MSSD +inf (MSPD +inf, ADD / ADD-S NaN or +inf): it can never
     fall below a threshold, and match_and_score never matches it.  The composed-transform workspace is 56 bytes per (pair, symmetry):
     when P needs more than `workspace_bytes` the pairs are processed in chunks (pose_error_chunks says how many), with identical results.  P = 0: empty tensors, no launch.
-    ValueError: a shape or dtype mismatch, an unknown obj_id or kind, "mspd" without K."""
+    ValueError: a shape or dtype mismatch, an unknown obj_id or kind ("vsd" among them: it needs images, see vsd_errors), "mspd" without K."""
     if not isinstance(models, ObjectModels):
         raise ValueError("models must be an ObjectModels")
     kinds = (kinds,) if isinstance(kinds, str) else tuple(kinds)
@@ -269,6 +305,313 @@ def pose_errors(models, obj_ids, R_est, t_est, R_gt, t_gt, K=None, kinds=("mssd"
             ptr(out.get("mspd_sym"), p0, 4), ptr(out.get("add"), p0, 4), ptr(out.get("adds"), p0, 4), _lib.stream_ptr()),
             "pp_pose_errors")
     return out
+
+
+# ---- VSD: depth renders and visibility ---------------------------------------------------------------------------------------------
+def plan_window(corners, pose, K4, H, W, near):
+    """The sampling window {x0, y0, x1, y1} (x1, y1 exclusive) of one view, planned on the host in float64: the 8 corners (8, 3) of the
+    object's vertex box under `pose` (4, 4); when all have Zc > near the window is the box of their pixels grown by one pixel and
+    clipped to the frame ((0, 0, 0, 0) when that is empty: the object is off-frame), otherwise the whole frame.  The projection of the
+    box contains the projection of every vertex, and one pixel exceeds the float32 error of the kernel's own projection by orders
+    of magnitude, so the window holds every sample the full-frame render covers.  A pose with a NaN or an infinity: (0, 0, 0, 0)."""
+    P = np.asarray(pose, dtype=np.float64)
+    if not np.all(np.isfinite(P[:3])):
+        return (0, 0, 0, 0)
+    c = np.asarray(corners, dtype=np.float64) @ P[:3, :3].T + P[:3, 3]
+    if not np.all(c[:, 2] > near):
+        return (0, 0, W, H)
+    fx, fy, cx, cy = K4
+    u, v = fx * c[:, 0] / c[:, 2] + cx, fy * c[:, 1] / c[:, 2] + cy
+    if not (np.all(np.isfinite(u)) and np.all(np.isfinite(v))):
+        return (0, 0, W, H)
+    x0, x1 = int(np.clip(np.floor(u.min()) - 1, 0, W)), int(np.clip(np.ceil(u.max()) + 2, 0, W))
+    y0, y1 = int(np.clip(np.floor(v.min()) - 1, 0, H)), int(np.clip(np.ceil(v.max()) + 2, 0, H))
+    return (x0, y0, x1, y1) if x1 > x0 and y1 > y0 else (0, 0, 0, 0)
+
+
+def _host_f32(name, a, P, tail):
+    """_pose_tensor's rules, result on the host: (P,) + tail float32 numpy (the views are planned on the host)."""
+    return _pose_tensor(name, a, P, tail, "cpu").numpy()
+
+
+def _obj_index(models, obj_ids, need_faces=True):
+    if not isinstance(models, ObjectModels):
+        raise ValueError("models must be an ObjectModels")
+    if isinstance(obj_ids, torch.Tensor):
+        obj_ids = obj_ids.cpu().numpy()
+    ids = np.asarray(obj_ids)
+    if ids.ndim != 1 or (len(ids) and not np.issubdtype(ids.dtype, np.integer)):
+        raise ValueError(f"obj_ids must be a 1-D integer sequence, got {ids.dtype} {ids.shape}")
+    for o in ids:
+        if int(o) not in models.index:
+            raise ValueError(f"unknown obj_id {int(o)}: the models hold {models.obj_ids}")
+        if need_faces and models.n_faces(o) == 0:
+            raise ValueError(f"object {int(o)} has no faces: give ObjectModels its 'faces' to render it")
+    return np.array([models.index[int(o)] for o in ids], dtype=np.int32)
+
+
+def _cams(K, n_images):
+    """K (3, 3) or (n_images, 3, 3) -> (n_images, 4) float32 {fx, fy, cx, cy} on the host (no skew)."""
+    Kt = _pose_tensor("K", K, n_images, [(3, 3), (n_images, 3, 3)], "cpu").numpy()
+    if Kt.ndim == 2:
+        Kt = np.broadcast_to(Kt, (n_images, 3, 3))
+    cams = np.ascontiguousarray(np.stack([Kt[:, 0, 0], Kt[:, 1, 1], Kt[:, 0, 2], Kt[:, 1, 2]], axis=1), dtype=np.float32)
+    if not (np.all(np.isfinite(cams)) and np.all(cams[:, :2] != 0)):
+        raise ValueError("K must be finite with fx and fy non-zero")
+    return cams
+
+
+def _image_index(image_index, P, n_images):
+    if image_index is None:
+        return np.zeros(P, dtype=np.int32)
+    if isinstance(image_index, torch.Tensor):
+        image_index = image_index.cpu().numpy()
+    idx = np.asarray(image_index)
+    if idx.shape != (P,) or (P and not np.issubdtype(idx.dtype, np.integer)):
+        raise ValueError(f"image_index must be {P} integers, got {idx.dtype} {idx.shape}")
+    if P and (idx.min() < 0 or idx.max() >= n_images):
+        raise ValueError(f"image_index must lie in [0, {n_images})")
+    return idx.astype(np.int32)
+
+
+def _pose44(R, t):
+    P = np.zeros((len(R), 4, 4), dtype=np.float32)
+    P[:, :3, :3], P[:, :3, 3], P[:, 3, 3] = R, t, 1.0
+    return P
+
+
+def _check_scalars(near, window, workspace_bytes):
+    if not (isinstance(near, (int, float)) and math.isfinite(near) and near > 0):
+        raise ValueError(f"near must be a positive number, got {near!r}")
+    if window not in ("auto", "full"):
+        raise ValueError(f"window must be 'auto' or 'full', got {window!r}")
+    if not (isinstance(workspace_bytes, int) and workspace_bytes > 0):
+        raise ValueError(f"workspace_bytes must be a positive int, got {workspace_bytes!r}")
+
+
+def _windows(models, view_obj, view_img, poses, cams, H, W, near, window):
+    out = np.zeros((len(view_obj), 4), dtype=np.int32)
+    for v, (o, i, P) in enumerate(zip(view_obj, view_img, poses)):
+        if window == "full":
+            out[v] = (0, 0, W, H) if np.all(np.isfinite(P[:3])) else (0, 0, 0, 0)
+        else:
+            out[v] = plan_window(models.aabb_corners[o], P, cams[i].astype(np.float64), H, W, float(np.float32(near)))
+    return out
+
+
+def _view_groups(models, view_obj, windows, pair_est, pair_gt, workspace_bytes):
+    """Consecutive pairs (or, without pairs, consecutive views) whose distinct views fit `workspace_bytes`: 8 bytes per window sample and
+    per triangle of a view.  At least one pair (view) per group.  -> [(view ids in order of first use, pair ids or None)]."""
+    nf = (models.face_off[1:] - models.face_off[:-1]).astype(np.int64)
+    cost = 8 * ((windows[:, 2] - windows[:, 0]).astype(np.int64) * (windows[:, 3] - windows[:, 1]) + nf[view_obj]) + 256
+    budget = max(int(workspace_bytes) - 512, 0)
+    groups, views, seen, used, first = [], [], set(), 0, 0
+    if pair_est is None:
+        for v in range(len(view_obj)):
+            if views and used + cost[v] > budget:
+                groups.append((np.array(views, dtype=np.int64), None))
+                views, used = [], 0
+            views.append(v)
+            used += int(cost[v])
+        groups.append((np.array(views, dtype=np.int64), None))
+        return groups
+    for p, (e, g) in enumerate(zip(pair_est.tolist(), pair_gt.tolist())):
+        new = [v for v in dict.fromkeys((e, g)) if v not in seen]
+        add = sum(int(cost[v]) for v in new)
+        if p > first and used + add > budget:
+            groups.append((np.array(views, dtype=np.int64), np.arange(first, p)))
+            views, seen, used, first = [], set(), 0, p
+            new = list(dict.fromkeys((e, g)))
+            add = sum(int(cost[v]) for v in new)
+        views += new
+        seen.update(new)
+        used += add
+    groups.append((np.array(views, dtype=np.int64), np.arange(first, len(pair_est))))
+    return groups
+
+
+def _vsd_launch(models, cams, H, W, view_obj, view_img, poses, windows, groups, near, pair_est=None, pair_gt=None, depth=None,
+                delta=15.0, taus=None, want_depth=False):
+    """One pp_vsd_errors call per group -> (vsd, counts, per-view near counts, dense depth or None), device tensors."""
+    dev, L = models.device, _lib.lib()
+    if dev.type != "cuda":
+        raise _lib.PicoPoseHipError("picopose_amd runs on the GPU only: build the ObjectModels on a CUDA(HIP) device")
+    U, P = len(view_obj), 0 if pair_est is None else len(pair_est)
+    T = 1 if taus is None else len(taus)
+    taus_h = np.ascontiguousarray(np.zeros(1) if taus is None else taus, dtype=np.float32)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+    cams_d = up(cams)
+    vsd = torch.empty((P, T), dtype=torch.float32, device=dev)
+    counts = torch.empty((P, 2 + T), dtype=torch.int32, device=dev)
+    near_all = torch.zeros(U, dtype=torch.int32, device=dev)
+    dense = torch.empty((U, H, W), dtype=torch.float32, device=dev) if want_depth else None
+    need = ctypes.c_size_t()
+    nf = (models.face_off[1:] - models.face_off[:-1]).astype(np.int64)
+    for views, pairs in groups:
+        vo, vi = np.ascontiguousarray(view_obj[views]), np.ascontiguousarray(view_img[views])
+        win, pose = np.ascontiguousarray(windows[views]), np.ascontiguousarray(poses[views])
+        zoff = np.zeros(len(views) + 1, dtype=np.int64)
+        np.cumsum((win[:, 2] - win[:, 0]).astype(np.int64) * (win[:, 3] - win[:, 1]), out=zoff[1:])
+        _lib.check(L.pp_vsd_workspace_bytes(int(zoff[-1]), int(nf[vo].sum()), ctypes.byref(need)), "pp_vsd_workspace_bytes")
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        vo_d, vi_d, win_d, pose_d, zoff_d = up(vo), up(vi), up(win), up(pose), up(zoff)
+        near_d = torch.empty(len(views), dtype=torch.int32, device=dev)
+        pe = pg = pe_d = pg_d = None
+        n_pairs = 0
+        if pairs is not None:
+            local = {int(v): k for k, v in enumerate(views.tolist())}
+            pe = np.array([local[int(v)] for v in pair_est[pairs]], dtype=np.int32)
+            pg = np.array([local[int(v)] for v in pair_gt[pairs]], dtype=np.int32)
+            pe_d, pg_d, n_pairs = up(pe), up(pg), len(pairs)
+        p0 = 0 if pairs is None else int(pairs[0])
+        ptr = lambda a: None if a is None else a.ctypes.data             # noqa: E731
+        dptr = lambda a: None if a is None else a.data_ptr()             # noqa: E731
+        dense_ptr = None
+        if want_depth:                                            # (render_depth: the groups are consecutive views)
+            dense_ptr = dense.data_ptr() + int(views[0]) * H * W * 4
+        _lib.check(L.pp_vsd_errors(
+            models.vertices.data_ptr(), models.vert_off_d.data_ptr(), models.faces.data_ptr(), models.face_off_d.data_ptr(),
+            models.diameters_d.data_ptr(), models.vert_off.ctypes.data, models.faces_host.ctypes.data, models.face_off.ctypes.data,
+            models.diameters_f32.ctypes.data, len(models.obj_ids), cams_d.data_ptr(), cams.ctypes.data, len(cams), H, W,
+            vo_d.data_ptr(), vi_d.data_ptr(), pose_d.data_ptr(), win_d.data_ptr(), zoff_d.data_ptr(), vo.ctypes.data, vi.ctypes.data,
+            win.ctypes.data, zoff.ctypes.data, len(views), dptr(pe_d), dptr(pg_d), ptr(pe), ptr(pg), n_pairs, dptr(depth), float(delta),
+            taus_h.ctypes.data, T, float(near), ws.data_ptr(), ws.numel(), vsd.data_ptr() + p0 * T * 4 if n_pairs else None,
+            counts.data_ptr() + p0 * (2 + T) * 4 if n_pairs else None, near_d.data_ptr(), dense_ptr, _lib.stream_ptr()), "pp_vsd_errors")
+        near_all[torch.from_numpy(views).to(dev)] = near_d
+    return vsd, counts, near_all, dense
+
+
+def render_depth(models, obj_ids, R, t, K, resolution, image_index=None, near=1.0, window="auto",
+                 workspace_bytes=DEFAULT_WORKSPACE_BYTES):
+    """Depth renders of U (object, pose) views -> {"depth": (U, H, W) float32 device tensor, camera Z in millimetres, 0 = background,
+    "near_count": the triangles dropped because a vertex had Zc <= near}.  resolution = (H, W); K (3, 3) or (n_images, 3, 3) with
+    image_index (U,) choosing the camera of each view (default: image 0); R (U, 3, 3), t (U, 3) millimetres; near in millimetres.
+    window: "auto" samples the host-planned window of each view (plan_window), "full" the whole frame — the same bits.  The views are
+    rendered in as many launch sequences as `workspace_bytes` needs.  U = 0: an empty tensor, no launch.  ValueError as vsd_errors."""
+    obj = _obj_index(models, obj_ids)
+    U = len(obj)
+    _check_scalars(near, window, workspace_bytes)
+    try:
+        H, W = (int(v) for v in resolution)
+    except (TypeError, ValueError):
+        raise ValueError(f"resolution must be (H, W), got {resolution!r}") from None
+    if H <= 0 or W <= 0 or H * W >= 2 ** 31:
+        raise ValueError(f"resolution must be positive with H W < 2^31, got {(H, W)}")
+    Rh, th = _host_f32("R", R, U, (3, 3)), _host_f32("t", t, U, (3,))
+    n_images = 1
+    if not isinstance(K, (list, tuple)) and getattr(K, "ndim", 2) == 3:
+        n_images = int(K.shape[0])
+    cams = _cams(K, n_images)
+    img = _image_index(image_index, U, n_images)
+    if U == 0:
+        return {"depth": torch.empty((0, H, W), dtype=torch.float32, device=models.device), "near_count": 0}
+    poses = _pose44(Rh, th)
+    windows = _windows(models, obj, img, poses, cams, H, W, near, window)
+    groups = _view_groups(models, obj, windows, None, None, workspace_bytes)
+    _, _, near_all, dense = _vsd_launch(models, cams, H, W, obj, img, poses, windows, groups, near, want_depth=True)
+    return {"depth": dense, "near_count": int(near_all.sum().item())}
+
+
+def _check_depth(depth, depth_scale):
+    """-> (n_images, H, W, per-image scale float64 or None for float millimetres); ValueError for anything else."""
+    is_t = isinstance(depth, torch.Tensor)
+    if not is_t and not isinstance(depth, np.ndarray):
+        raise ValueError(f"depth must be a numpy array or a torch tensor, got {type(depth).__name__}")
+    if depth.ndim != 3 or 0 in tuple(depth.shape):
+        raise ValueError(f"depth must have shape (n_images, H, W), got {tuple(depth.shape)}")
+    n, H, W = (int(v) for v in depth.shape)
+    if H * W >= 2 ** 31:
+        raise ValueError("depth frames must hold fewer than 2^31 samples")
+    if depth.dtype == (getattr(torch, "uint16", None) if is_t else np.uint16):
+        if depth_scale is None:
+            raise ValueError("uint16 depth is raw: depth_scale (millimetres per unit) is required")
+        try:
+            sc = np.asarray(depth_scale, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"depth_scale must be a number or one per image, got {depth_scale!r}") from None
+        if sc.shape not in ((), (n,)) or not np.all(np.isfinite(sc)) or not np.all(sc > 0):
+            raise ValueError(f"depth_scale must be a positive number or one per image, got {depth_scale!r}")
+        return n, H, W, np.broadcast_to(sc, (n,))
+    if not (depth.dtype.is_floating_point if is_t else np.issubdtype(depth.dtype, np.floating)):
+        raise ValueError(f"depth must be uint16 (raw, with depth_scale) or float millimetres, got {depth.dtype}")
+    if depth_scale is not None:
+        raise ValueError("float depth is millimetres already: depth_scale must be None")
+    return n, H, W, None
+
+
+def _depth_mm(depth, scale, dev):
+    """(n_images, H, W) uint16 raw with its per-image scale, or float millimetres (scale None) -> float32 mm on the device."""
+    is_t = isinstance(depth, torch.Tensor)
+    if scale is None:
+        d = depth if is_t else torch.from_numpy(np.ascontiguousarray(depth, dtype=np.float32))
+        return d.to(device=dev, dtype=torch.float32).contiguous()
+    n, H, W = (int(v) for v in depth.shape)
+    # pp_depth_u16_scaled writes (f32(d) * s) / 1000 in float32: s = f32(1000 depth_scale) gives millimetres
+    s = torch.from_numpy((scale * 1000.0).astype(np.float32)).to(dev)
+    raw = (depth.contiguous().view(torch.int16) if is_t else torch.from_numpy(np.ascontiguousarray(depth).view(np.int16))).to(dev)
+    out = torch.empty((n, H, W), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().pp_depth_u16_scaled(raw.data_ptr(), H * W, n, s.data_ptr(), out.data_ptr(), _lib.stream_ptr()),
+               "pp_depth_u16_scaled")
+    return out
+
+
+def vsd_errors(models, obj_ids, R_est, t_est, R_gt, t_gt, K, depth, image_index=None, depth_scale=None, delta=15.0, taus=VSD_TAUS,
+               near=1.0, window="auto", workspace_bytes=DEFAULT_WORKSPACE_BYTES):
+    """The BOP19 VSD of P (estimate, ground truth) pairs over n_images test depth images -> {"vsd": (P, T) float32 e_tau,
+    "visib_union", "visib_inter": (P,) int32, "n_far": (P, T) int32 (intersection pixels with |D_gt - D_est| / diameter >= tau)
+    device tensors, "n_views": the distinct views rendered, "near_count": the triangles dropped at the near plane over those views,
+    "n_groups": the pp_vsd_errors calls made (1 unless the views exceed `workspace_bytes`)}.
+
+    depth: (n_images, H, W), uint16 raw values with `depth_scale` (millimetres per unit, a number or one per image) or float millimetres
+    (depth_scale None); numpy or tensor; a value that is not > 0 is missing.  K: (3, 3) or (n_images, 3, 3); image_index (P,): the image
+    of each pair (default 0).  delta (mm) and taus (T <= 16, fractions of the diameter) as in the definition (include/picopose_hip.h).
+    Identical (image, object, pose bytes) views are rendered once: a ground truth shared by several estimates, an estimate paired with
+    several instances.  window "auto": each view is sampled inside its host-planned window (plan_window); "full": the whole frame — the
+    same bits.  A pose holding a NaN or an infinity gets an empty window: it renders nothing and e = 1 for every tau.  When the views of
+    all pairs need more than `workspace_bytes` the pairs are processed in groups, with identical results.  P = 0: empty tensors, no launch.
+    ValueError: an object without faces, an unknown obj_id, shape or dtype mismatches, image_index out of range, T outside 1..16."""
+    obj = _obj_index(models, obj_ids)
+    P, dev = len(obj), models.device
+    _check_scalars(near, window, workspace_bytes)
+    if not (isinstance(delta, (int, float)) and math.isfinite(delta) and delta > 0):
+        raise ValueError(f"delta must be a positive number, got {delta!r}")
+    tau = np.asarray(taus, dtype=np.float64)
+    if tau.ndim != 1 or not 1 <= len(tau) <= VSD_MAX_TAUS or not np.all(np.isfinite(tau)):
+        raise ValueError(f"taus must be 1 .. {VSD_MAX_TAUS} finite numbers, got shape {tau.shape}")
+    T = len(tau)
+    Re, te = _host_f32("R_est", R_est, P, (3, 3)), _host_f32("t_est", t_est, P, (3,))
+    Rg, tg = _host_f32("R_gt", R_gt, P, (3, 3)), _host_f32("t_gt", t_gt, P, (3,))
+    n_images, H, W, scale = _check_depth(depth, depth_scale)
+    cams = _cams(K, n_images)
+    img = _image_index(image_index, P, n_images)
+    if P == 0:
+        z = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)     # noqa: E731
+        return {"vsd": torch.empty((0, T), dtype=torch.float32, device=dev), "visib_union": z(0), "visib_inter": z(0), "n_far": z(0, T),
+                "n_views": 0, "near_count": 0}
+    if dev.type != "cuda":
+        raise _lib.PicoPoseHipError("picopose_amd runs on the GPU only: build the ObjectModels on a CUDA(HIP) device")
+    depth_d = _depth_mm(depth, scale, dev)
+    # the distinct views: (image, object, bytes of the float32 pose)
+    Pe, Pg = _pose44(Re, te), _pose44(Rg, tg)
+    index, view_obj, view_img, poses = {}, [], [], []
+    pair_est, pair_gt = np.zeros(P, dtype=np.int32), np.zeros(P, dtype=np.int32)
+    for p in range(P):
+        for dst, pose in ((pair_est, Pe[p]), (pair_gt, Pg[p])):
+            key = (int(img[p]), int(obj[p]), pose.tobytes())
+            v = index.get(key)
+            if v is None:
+                v = index[key] = len(poses)
+                view_obj.append(obj[p])
+                view_img.append(img[p])
+                poses.append(pose)
+            dst[p] = v
+    view_obj, view_img, poses = np.array(view_obj, dtype=np.int32), np.array(view_img, dtype=np.int32), np.stack(poses)
+    windows = _windows(models, view_obj, view_img, poses, cams, H, W, near, window)
+    groups = _view_groups(models, view_obj, windows, pair_est, pair_gt, workspace_bytes)
+    vsd, counts, near_all, _ = _vsd_launch(models, cams, H, W, view_obj, view_img, poses, windows, groups, near, pair_est, pair_gt,
+                                           depth_d, delta, tau, want_depth=False)
+    return {"vsd": vsd, "visib_union": counts[:, 0], "visib_inter": counts[:, 1], "n_far": counts[:, 2:], "n_views": len(poses),
+            "near_count": int(near_all.sum().item()), "n_groups": len(groups)}
 
 
 # ---- parsers: JSON and CSV only ----------------------------------------------------------------------------------------------------
@@ -380,7 +723,8 @@ def score_pairs(pairs, errors, limits, scores, targets):
     return matched
 
 
-def match_and_score(estimates, ground_truth, targets, models, cameras, image_width=640, workspace_bytes=DEFAULT_WORKSPACE_BYTES):
+def match_and_score(estimates, ground_truth, targets, models, cameras, image_width=640, workspace_bytes=DEFAULT_WORKSPACE_BYTES,
+                    depth_images=None, vsd_delta=15.0, vsd_taus=VSD_TAUS, images_per_call=64):
     """The BOP localization protocol for MSSD and MSPD.  estimates: read_bop_results' dict; ground_truth / cameras:
     {scene_id: read_scene_gt(...) / read_scene_camera(...)}; targets: read_targets' rows; models: ObjectModels.
 
@@ -390,7 +734,14 @@ def match_and_score(estimates, ground_truth, targets, models, cameras, image_wid
     greedily (score_pairs).  Recall = matched / sum of inst_count.  -> {"AR_MSSD", "AR_MSPD": mean recall over the thresholds,
     "recall_mssd", "recall_mspd" (10,), "thresholds_mssd", "thresholds_mspd", "per_object": {obj_id: the same four and "targets"},
     "pairs": plan_pairs' arrays plus "mssd", "mspd" (float32 numpy), "n_targets": sum of inst_count, "vsd": None}.
-    VSD is out of scope ("vsd" is None), so there is no three-term BOP average here: AR_MSSD and AR_MSPD are two of its three terms."""
+    Without depth_images VSD is not computed ("vsd" is None) and there is no three-term average: AR_MSSD and AR_MSPD are two of its terms.
+
+    depth_images: {scene_id: {im_id: (H, W) array}} or a callable (scene_id, im_id) -> (H, W) array: the test depth images, uint16 raw
+    or float raw values, scaled by cameras[scene][im]["depth_scale"] to millimetres (decoding the PNGs stays with the caller).  Only the
+    images that occur in pairs are asked for, images_per_call at a time, one vsd_errors call each (delta = vsd_delta, taus = vsd_taus;
+    the models need faces).  A pair is correct at (tau, theta) when e_tau < theta, theta = VSD_THRESHOLDS; matching is score_pairs per tau.
+    Adds "vsd": {"errors" (n_pairs, T), "taus", "thresholds", "delta"}, "recall_vsd" (T, 10), "AR_VSD", "AR" = (AR_VSD + AR_MSSD +
+    AR_MSPD) / 3, and the last three per object."""
     targets = np.asarray(targets, dtype=np.int64).reshape(-1, 4)
     pairs = plan_pairs(estimates, ground_truth, targets)
     n = len(pairs["est"])
@@ -406,11 +757,41 @@ def match_and_score(estimates, ground_truth, targets, models, cameras, image_wid
     err = pose_errors(models, obj, estimates["R"][pairs["est"]], estimates["t"][pairs["est"]], R_gt, t_gt, K=K, kinds=("mssd", "mspd"),
                       workspace_bytes=workspace_bytes)
     mssd, mspd = err["mssd"].cpu().numpy(), err["mspd"].cpu().numpy()
-    return score_errors(pairs, mssd, mspd, estimates["score"], targets, models, image_width)
+    vsd = None
+    if depth_images is not None:
+        if not (isinstance(images_per_call, int) and images_per_call > 0):
+            raise ValueError(f"images_per_call must be a positive int, got {images_per_call!r}")
+        taus = np.asarray(vsd_taus, dtype=np.float64)
+        if taus.ndim != 1 or not 1 <= len(taus) <= VSD_MAX_TAUS:
+            raise ValueError(f"vsd_taus must hold 1 .. {VSD_MAX_TAUS} numbers, got shape {taus.shape}")
+        where = [(int(targets[pairs["target"][i], 0]), int(targets[pairs["target"][i], 1])) for i in range(n)]
+        images = list(dict.fromkeys(where))                       # the images that occur in pairs, in order of first use
+        e = np.ones((n, len(taus)), dtype=np.float32)
+        for b0 in range(0, len(images), images_per_call):
+            batch = images[b0:b0 + images_per_call]
+            slot = {k: j for j, k in enumerate(batch)}
+            rows = np.array([i for i in range(n) if where[i] in slot], dtype=np.int64)
+            frames = [np.asarray(depth_images(*k) if callable(depth_images) else depth_images[k[0]][k[1]]) for k in batch]
+            if any(f.ndim != 2 or f.shape != frames[0].shape for f in frames):
+                raise ValueError("depth images of one call must share one (H, W) resolution")
+            scale = np.array([cameras[k[0]][k[1]]["depth_scale"] for k in batch], dtype=np.float64)
+            if all(f.dtype == np.uint16 for f in frames):
+                depth, depth_scale = np.stack(frames), scale
+            else:
+                depth = np.stack([f.astype(np.float32) * np.float32(sc) for f, sc in zip(frames, scale)])
+                depth_scale = None
+            Kb = np.stack([cameras[k[0]][k[1]]["K"] for k in batch]).astype(np.float64)
+            r = vsd_errors(models, obj[rows], estimates["R"][pairs["est"][rows]], estimates["t"][pairs["est"][rows]], R_gt[rows], t_gt[rows],
+                           Kb, depth, image_index=np.array([slot[where[i]] for i in rows], dtype=np.int32), depth_scale=depth_scale,
+                           delta=vsd_delta, taus=taus, workspace_bytes=workspace_bytes)
+            e[rows] = r["vsd"].cpu().numpy()
+        vsd = {"errors": e, "taus": taus.copy(), "thresholds": VSD_THRESHOLDS.copy(), "delta": float(vsd_delta)}
+    return score_errors(pairs, mssd, mspd, estimates["score"], targets, models, image_width, vsd=vsd)
 
 
-def score_errors(pairs, mssd, mspd, scores, targets, models, image_width=640):
-    """match_and_score's host half: the recalls from the per-pair errors (numpy arrays)."""
+def score_errors(pairs, mssd, mspd, scores, targets, models, image_width=640, vsd=None):
+    """match_and_score's host half: the recalls from the per-pair errors (numpy arrays).  vsd: None, or {"errors" (n_pairs, T), "taus",
+    "thresholds" (10,), "delta"}: per tau the pairs are matched by score_pairs with the thresholds as limits."""
     targets = np.asarray(targets, dtype=np.int64).reshape(-1, 4)
     n = len(pairs["est"])
     obj = targets[pairs["target"], 2] if n else np.zeros(0, dtype=np.int64)
@@ -421,12 +802,22 @@ def score_errors(pairs, mssd, mspd, scores, targets, models, image_width=640):
     hit = {"mssd": score_pairs(pairs, np.asarray(mssd, dtype=np.float64), lim_mssd, scores, targets),
            "mspd": score_pairs(pairs, np.asarray(mspd, dtype=np.float64), lim_mspd, scores, targets)}
     total = int(targets[:, 3].sum())
+    hit_vsd = None
+    if vsd is not None:
+        ev, th = np.asarray(vsd["errors"], dtype=np.float64).reshape(n, -1), np.asarray(vsd["thresholds"], dtype=np.float64)
+        lim = np.broadcast_to(th[None], (n, len(th)))
+        hit_vsd = np.stack([score_pairs(pairs, ev[:, k], lim, scores, targets) for k in range(ev.shape[1])], axis=1)   # (targets, T, 10)
 
     def recalls(rows):
         cnt = int(targets[rows, 3].sum())
         rec = {k: (hit[k][rows].sum(axis=0) / cnt if cnt else np.zeros(10)) for k in hit}
-        return {"AR_MSSD": float(rec["mssd"].mean()), "AR_MSPD": float(rec["mspd"].mean()), "recall_mssd": rec["mssd"],
-                "recall_mspd": rec["mspd"], "targets": cnt}
+        out = {"AR_MSSD": float(rec["mssd"].mean()), "AR_MSPD": float(rec["mspd"].mean()), "recall_mssd": rec["mssd"],
+               "recall_mspd": rec["mspd"], "targets": cnt}
+        if hit_vsd is not None:
+            out["recall_vsd"] = hit_vsd[rows].sum(axis=0) / cnt if cnt else np.zeros(hit_vsd.shape[1:])
+            out["AR_VSD"] = float(out["recall_vsd"].mean())
+            out["AR"] = (out["AR_VSD"] + out["AR_MSSD"] + out["AR_MSPD"]) / 3.0
+        return out
 
     res = recalls(np.arange(len(targets)))
     res["n_targets"] = total
@@ -434,5 +825,5 @@ def score_errors(pairs, mssd, mspd, scores, targets, models, image_width=640):
     res["thresholds_mssd"], res["thresholds_mspd"] = MSSD_THRESHOLDS.copy(), MSPD_THRESHOLDS * r
     res["per_object"] = {int(o): recalls(np.where(targets[:, 2] == o)[0]) for o in np.unique(targets[:, 2])}
     res["pairs"] = dict(pairs, mssd=np.asarray(mssd), mspd=np.asarray(mspd))
-    res["vsd"] = None
+    res["vsd"] = None if vsd is None else dict(vsd)
     return res
