@@ -984,6 +984,83 @@ int pp_vsd_errors(const float* vertices, const int* vert_off, const int* faces, 
                   const float* depth, float delta, const float* taus_host, int n_taus, float near, void* workspace,
                   size_t workspace_bytes, float* vsd, int* counts, unsigned int* near_count, float* depth_out, void* stream);
 
+/* -------------------------------------------------------------------------
+ * DEPTH REFINEMENT: projective point-to-plane ICP of n_views poses of mixed objects against the test depth images
+ * (picopose_amd/depth_refine.py plans every call; tests/depth_refine_oracle.py restates this text in numpy float64).  This is THIS
+ * library's own algorithm.  The project it was modelled on refines with OpenCV's ppf_match_3d ICP after a centroid shift; that code
+ * cannot be run next to this library and sub-samples its points, so PARITY WITH IT IS UNPINNED AND NOT ATTEMPTED.
+ * Millimetres throughout.
+ *
+ * THE ALGORITHM.  Per pose, at most `iterations` times:
+ *  1. Render.  THE DEPTH RASTER of the VSD block, unchanged: the object under the CURRENT float32 pose into the view's window of the
+ *     ragged z-buffer, word = (bits of Z) << 32 | face, 64-bit unsigned atomic minimum.  The window is fixed for the whole call (the
+ *     caller plans it once from the input pose: evaluation.plan_window grown by a margin and clipped to the frame); a sample that
+ *     leaves it is not rendered and therefore not associated.
+ *  2. Associate and accumulate.  For every window sample (x, y) with a z-buffer hit (Z_r, face f):
+ *       Z_t = the test depth at (x, y); the sample is skipped unless Z_t > 0 (zero, negative, NaN: missing);
+ *       the gate, in float32, never contracted: fabsf(Z_t - Z_r) <= max_distance, otherwise skipped;
+ *     from here float64, computed from the float32 inputs (fx, fy, cx, cy, the pose, the vertices, Z_r, Z_t):
+ *       xr = (x - cx) / fx, yr = (y - cy) / fy;  p_m = Z_r (xr, yr, 1), p_t = Z_t (xr, yr, 1);
+ *       m = R ((v1 - v0) x (v2 - v0)) with v0, v1, v2 the face's vertices in the order of the faces table; a face whose cross product
+ *       is the zero vector (or whose |m| is not > 0) is skipped;  n = m / |m|, negated when n . p_m > 0 (so that n . p_m <= 0);
+ *       skipped when -(n . p_m) / |p_m| < min_cos (grazing);
+ *       residual r = n . (p_t - p_m);  row J = [ ((p_m - c) x n) / rho , n ] with c = R (centre of the object's vertex box) + t,
+ *       the centre = ((double) lo + (double) hi) / 2 of `boxes`, and rho = (double) diameter / 2: the unknowns (rho theta, v) are mm.
+ *     Sums (PP_DEPTH_REFINE_SUMS = 29 doubles): the 21 upper entries of J^T J row by row ((0,0), (0,1) .. (0,5), (1,1) ..), the 6 of
+ *     J^T r, sum r^2, and the count N (an integer held in a double).  A workgroup of 256 lanes owns one STRIP of
+ *     PP_DEPTH_REFINE_STRIP_ROWS window rows: lane l adds samples l, l + 256, .. of the strip (row-major) in order, the 64 lanes of a
+ *     wave combine by xor-shuffles 32, 16 .. 1, the 4 waves are added in wave order, and the strips of a view in index order.  No
+ *     floating-point atomics: the sums are the same bits for any stream, pose order, batch composition and grouping.
+ *  3. Solve and update.  The symmetric 6 x 6 matrix is decomposed by cyclic Jacobi rotations (12 sweeps, float64).  With lambda_max
+ *     the largest eigenvalue, a direction is KEPT when lambda > 0 and lambda >= rcond lambda_max; rank = the directions kept;
+ *     x = sum over the kept directions of e (e . J^T r) / lambda: the pseudo-inverse step.  Directions the depth does not constrain
+ *     (a plate's in-plane motion, a sphere's rotation) are left where the input pose put them.  theta = x[0..3] / rho, v = x[3..6];
+ *     Exp(theta) = I + A K + B K K (K the cross-product matrix of theta, a = |theta|, A = sin a / a, B = (1 - cos a) / a^2; for
+ *     a^2 < 1e-12: A = 1 - a^2 / 6, B = 1/2 - a^2 / 24);  R <- Exp(theta) R,  t <- c + Exp(theta) (t - c) + v, each entry rounded once
+ *     to float32: the rasteriser's input format.
+ *  4. Stop.  status per pose, decided after every linearisation in this order:
+ *       2  N < min_points in this linearisation                                              -> the INPUT pose is returned
+ *       3  |t - t_in| > max_translation or angle(R R_in^T) > max_rotation for the updated float32 pose (the angle is
+ *          acos(clamp((trace - 1) / 2, -1, 1)); a non-finite value counts as exceeding)       -> the INPUT pose is returned
+ *       0  max(|rho theta|, |v|) < eps: converged                                             -> the updated pose
+ *       1  none of these after `iterations` linearisations                                   -> the updated pose
+ *       4  (before the first) an input pose whose first three rows hold a NaN or an infinity, or an empty window -> the input pose
+ *     A stopped pose is frozen: later launches neither render it nor move it, and nothing of another pose depends on it.
+ *
+ * Objects, cams, views, windows and view_zoff are the tables of pp_vsd_errors (device pointers, with *_host copies validated here);
+ * boxes (n_objects, 6) fp32 = the lower and the upper corner of each object's vertex box.  view_soff (n_views + 1) int32: the prefix
+ * sums of the views' strip counts, ceil(window height / PP_DEPTH_REFINE_STRIP_ROWS), 0 for an empty window.  poses_in (n_views, 4, 4)
+ * fp32 row-major object -> camera; depth (n_images, H, W) fp32 millimetres.  max_distance, min_cos, rcond, eps, max_translation
+ * (mm), max_rotation (rad) are float32 arguments, converted to float64 where they are compared with float64.
+ * Outputs (device): poses_out (n_views, 4, 4) fp32 (also the working poses; it must not be poses_in); active (n_views) int32 work
+ * table; status, n_iterations (linearisations performed), rank and n_points (of the last linearisation; rank 0 when it stopped with
+ * status 2) (n_views) int32; rms_before, rms_after (n_views) fp32 = sqrt(sum r^2 / N) of the first and the last linearisation (NaN
+ * without one, or when N = 0); near_count (n_views) uint32: the triangles dropped at the near plane, over all iterations.
+ * Optional (NULL: off): trajectory (n_views, iterations + 1, 4, 4) fp32, entry 0 the input pose and entry k + 1 the pose after
+ * round k (a stopped pose repeats its result); sums (n_views, iterations, 29) fp64, the sums of each linearisation (0 where none).
+ * Workspace (256-byte aligned): pp_depth_refine_workspace_bytes(window_samples, view_faces, strips) = 256 + roundup256(8
+ * window_samples) + roundup256(8 view_faces) + 232 strips.  All `iterations` rounds (clear, two raster launches, accumulate, solve)
+ * are enqueued on `stream`; nothing synchronises with the host.
+ * PP_EINVAL (before any launch): every case of pp_vsd_errors that applies; poses_out = poses_in; a box that is not finite or has
+ * hi < lo; view_soff not the prefix sums of the strip counts; iterations outside 1..PP_DEPTH_REFINE_MAX_ITERATIONS; min_points < 1;
+ * max_distance, max_translation, max_rotation or near not positive and finite; min_cos or rcond outside [0, 1); eps negative or not
+ * finite.  PP_EWORKSPACE: workspace misaligned or smaller than pp_depth_refine_workspace_bytes says.
+ * ------------------------------------------------------------------------- */
+#define PP_DEPTH_REFINE_STRIP_ROWS 8
+#define PP_DEPTH_REFINE_SUMS 29
+#define PP_DEPTH_REFINE_MAX_ITERATIONS 1000
+int pp_depth_refine_workspace_bytes(long long window_samples, long long view_faces, long long strips, size_t* bytes);
+int pp_depth_refine(const float* vertices, const int* vert_off, const int* faces, const int* face_off, const float* diameters,
+                    const float* boxes, const int* vert_off_host, const int* faces_host, const int* face_off_host,
+                    const float* diameters_host, const float* boxes_host, int n_objects, const float* cams, const float* cams_host,
+                    int n_images, int H, int W, const int* view_obj, const int* view_img, const float* poses_in, const int* windows,
+                    const long long* view_zoff, const int* view_soff, const int* view_obj_host, const int* view_img_host,
+                    const int* windows_host, const long long* view_zoff_host, const int* view_soff_host, int n_views,
+                    const float* depth, int iterations, float max_distance, int min_points, float min_cos, float rcond, float eps,
+                    float max_translation, float max_rotation, float near, void* workspace, size_t workspace_bytes, float* poses_out,
+                    int* active, int* status, int* n_iterations, int* rank, int* n_points, float* rms_before, float* rms_after,
+                    unsigned int* near_count, float* trajectory, double* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -224,6 +224,9 @@ def lib():
         L.pp_vsd_workspace_bytes.argtypes = [ll, ll, c.POINTER(sz)]
         L.pp_vsd_errors.argtypes = ([vp] * 9 + [i32, vp, vp, i32, i32, i32] + [vp] * 9 + [i32] + [vp] * 4 + [i32, vp, f32, vp, i32, f32,
                                     vp, sz] + [vp] * 5)
+        L.pp_depth_refine_workspace_bytes.argtypes = [ll, ll, ll, c.POINTER(sz)]
+        L.pp_depth_refine.argtypes = ([vp] * 11 + [i32, vp, vp, i32, i32, i32] + [vp] * 11 + [i32, vp, i32, f32, i32] + [f32] * 6 +
+                                      [vp, sz] + [vp] * 12)
         _lib = L
     return _lib
 

@@ -1,0 +1,453 @@
+// Projective point-to-plane ICP of poses against the test depth images (picopose_amd/depth_refine.py plans every call; the contract is
+// stated in include/picopose_hip.h, "DEPTH REFINEMENT", and restated in numpy by tests/depth_refine_oracle.py).
+//
+//   refine_init_kernel        one lane per view: the working pose, the active flag and the per-pose state
+//   vsd_raster_small_kernel, vsd_raster_large_kernel  the windowed depth raster of pp_vsd_raster_dev.h (shared with pp_vsd.hip);
+//                             a view whose active flag is 0 renders nothing
+//   refine_accumulate_kernel  one workgroup per STRIP (PP_DEPTH_REFINE_STRIP_ROWS rows of one view's window): associates the strip's
+//                             samples with the test depth and adds J^T J, J^T r, sum r^2 and N as per-lane float64 partial sums,
+//                             reduced by xor-shuffles within a wave and through LDS across waves in wave order -> 29 doubles per strip
+//   refine_solve_kernel       one wave per view: adds the view's strips in index order, solves the 6 x 6 system by a cyclic Jacobi
+//                             eigen-decomposition with a truncated pseudo-inverse, updates the pose and decides the status
+//
+// The split into strips depends on the view's window alone and no sum is an atomic: every output is the same bits whatever the
+// stream, the pose order, the other poses of the call or the caller's grouping.  Nothing synchronises with the host: all
+// `iterations` rounds are enqueued, and a pose that has stopped is skipped by every later launch.
+#include <stdint.h>
+#include <limits.h>
+#include <math.h>
+#include "pp_common.h"
+
+#pragma clang fp contract(off)
+#include "pp_vsd_raster_dev.h"
+
+namespace {
+
+constexpr size_t WS_HEADER = 256;
+constexpr int BLOCK = 256;
+constexpr int WAVES = BLOCK / 64;
+constexpr int ROWS = PP_DEPTH_REFINE_STRIP_ROWS;
+constexpr int NS = PP_DEPTH_REFINE_SUMS;      // 21 upper entries of J^T J, 6 of J^T r, sum r^2, N
+constexpr int JACOBI_SWEEPS = 12;
+
+enum : int { ST_CONVERGED = 0, ST_LIMIT = 1, ST_FEW = 2, ST_DRIFT = 3, ST_INVALID = 4 };
+
+// the per-pose tables of a call (device pointers)
+struct State {
+    const float* poses_in;     // (n_views, 16)
+    float* poses;              // (n_views, 16): the working poses, the result
+    int* active;
+    int* status;
+    int* iters;
+    int* rank;
+    int* n_points;
+    float* rms_before;
+    float* rms_after;
+    float* trajectory;         // (n_views, iterations + 1, 16) or null
+    double* sums;              // (n_views, iterations, NS) or null
+    int iterations;
+};
+
+__device__ __forceinline__ bool finite32(float v) { return fabsf(v) <= 3.402823466e38f; }
+
+__global__ __launch_bounds__(BLOCK) void refine_init_kernel(State st, const int* __restrict__ windows, int n_views) {
+    const int v = blockIdx.x * BLOCK + threadIdx.x;
+    if (v >= n_views) return;
+    const float* src = st.poses_in + 16 * (size_t)v;
+    float* dst = st.poses + 16 * (size_t)v;
+    bool ok = true;
+    for (int k = 0; k < 16; ++k) {
+        dst[k] = src[k];
+        if (k < 12) ok = ok && finite32(src[k]);
+    }
+    const int* w = windows + 4 * (size_t)v;
+    ok = ok && w[2] > w[0] && w[3] > w[1];
+    st.active[v] = ok ? 1 : 0;
+    st.status[v] = ok ? ST_LIMIT : ST_INVALID;
+    st.iters[v] = 0;
+    st.rank[v] = 0;
+    st.n_points[v] = 0;
+    st.rms_before[v] = NAN;
+    st.rms_after[v] = NAN;
+    if (st.trajectory)
+        for (int i = 0; i <= st.iterations; ++i)
+            for (int k = 0; k < 16; ++k) st.trajectory[((size_t)v * (st.iterations + 1) + i) * 16 + k] = src[k];
+}
+
+// the object's constants in the camera frame: c = R (centre of the vertex box) + t and rho = diameter / 2, float64 from the float32 tables
+struct Frame {
+    double R[9], t[3], c[3], rho;
+};
+
+__device__ __forceinline__ void load_frame(const float* __restrict__ P, const float* __restrict__ box, float diameter, Frame& f) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) f.R[3 * i + j] = (double)P[4 * i + j];
+        f.t[i] = (double)P[4 * i + 3];
+    }
+    double m[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) m[i] = 0.5 * ((double)box[i] + (double)box[3 + i]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) f.c[i] = ((f.R[3 * i] * m[0] + f.R[3 * i + 1] * m[1]) + f.R[3 * i + 2] * m[2]) + f.t[i];
+    f.rho = 0.5 * (double)diameter;
+}
+
+// strip blockIdx.x of the call -> partial[blockIdx.x] (NS doubles); a strip of a stopped view writes nothing
+__global__ __launch_bounds__(BLOCK) void refine_accumulate_kernel(Scene s, const unsigned long long* __restrict__ zbuf,
+                                                                  const int* __restrict__ view_soff,
+                                                                  const float* __restrict__ diameters, const float* __restrict__ boxes,
+                                                                  const float* __restrict__ depth, float max_distance, float min_cos,
+                                                                  double* __restrict__ partial) {
+    const int strip = blockIdx.x;
+    int lo = 0, hi = s.n_views;                                   // view_soff[lo] <= strip < view_soff[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (view_soff[mid] <= strip) lo = mid; else hi = mid;
+    }
+    const int v = lo;
+    if (s.active[v] == 0) return;
+    const int* w = s.windows + 4 * (size_t)v;
+    const int x0 = w[0], y0 = w[1], ww = w[2] - w[0];
+    const int ys = y0 + (strip - view_soff[v]) * ROWS;
+    const int rows = min(ROWS, w[3] - ys);
+    if (ww <= 0 || rows <= 0) return;
+    const int o = s.view_obj[v], img = s.view_img[v];
+    const float* k = s.cams + 4 * (size_t)img;
+    const double fx = (double)k[0], fy = (double)k[1], cx = (double)k[2], cy = (double)k[3];
+    Frame fr;
+    load_frame(s.poses + 16 * (size_t)v, boxes + 6 * (size_t)o, diameters[o], fr);
+    const int v0 = s.vert_off[o], Nv = s.vert_off[o + 1] - v0, f0 = s.face_off[o], Nf = s.face_off[o + 1] - f0;
+    const float* verts = s.verts + 3 * (size_t)v0;
+    const int* faces = s.faces + 3 * (size_t)f0;
+    const unsigned long long* zv = zbuf + s.view_zoff[v] + (size_t)(ys - y0) * ww;
+    const float* dimg = depth + (size_t)img * s.H * s.W;
+    const double mc = (double)min_cos;
+
+    double acc[NS];
+#pragma unroll
+    for (int c = 0; c < NS; ++c) acc[c] = 0.0;
+    const int n = rows * ww;
+    for (int i = threadIdx.x; i < n; i += BLOCK) {
+        const unsigned long long key = zv[i];
+        if (key == ~0ull) continue;
+        const int yy = i / ww, x = x0 + (i - yy * ww), y = ys + yy;
+        const float z_r = __uint_as_float((unsigned)(key >> 32));
+        const unsigned f = (unsigned)key;
+        const float z_t = dimg[(size_t)y * s.W + x];
+        if (!(z_t > 0.f)) continue;                               // missing
+        if (!(fabsf(z_t - z_r) <= max_distance)) continue;        // the gate, float32
+        if (f >= (unsigned)Nf) continue;
+        const unsigned i0 = (unsigned)faces[3 * (size_t)f], i1 = (unsigned)faces[3 * (size_t)f + 1], i2 = (unsigned)faces[3 * (size_t)f + 2];
+        if (i0 >= (unsigned)Nv || i1 >= (unsigned)Nv || i2 >= (unsigned)Nv) continue;
+        double a[3], b[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const double p0 = (double)verts[3 * (size_t)i0 + d];
+            a[d] = (double)verts[3 * (size_t)i1 + d] - p0;
+            b[d] = (double)verts[3 * (size_t)i2 + d] - p0;
+        }
+        const double cr[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+        if (cr[0] == 0.0 && cr[1] == 0.0 && cr[2] == 0.0) continue;   // a degenerate face
+        double nn[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) nn[d] = (fr.R[3 * d] * cr[0] + fr.R[3 * d + 1] * cr[1]) + fr.R[3 * d + 2] * cr[2];
+        const double len = sqrt((nn[0] * nn[0] + nn[1] * nn[1]) + nn[2] * nn[2]);
+        if (!(len > 0.0)) continue;
+        const double xr = ((double)x - cx) / fx, yr = ((double)y - cy) / fy;
+        const double zr = (double)z_r, zt = (double)z_t;
+        const double pm[3] = {zr * xr, zr * yr, zr}, pt[3] = {zt * xr, zt * yr, zt};
+        double dot = 0.0;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            nn[d] = nn[d] / len;
+            dot += nn[d] * pm[d];
+        }
+        if (dot > 0.0) {
+            dot = -dot;
+#pragma unroll
+            for (int d = 0; d < 3; ++d) nn[d] = -nn[d];
+        }
+        const double range = sqrt((pm[0] * pm[0] + pm[1] * pm[1]) + pm[2] * pm[2]);
+        if (-dot / range < mc) continue;                          // grazing
+        double r = 0.0;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) r += nn[d] * (pt[d] - pm[d]);
+        const double q[3] = {pm[0] - fr.c[0], pm[1] - fr.c[1], pm[2] - fr.c[2]};
+        const double J[6] = {(q[1] * nn[2] - q[2] * nn[1]) / fr.rho, (q[2] * nn[0] - q[0] * nn[2]) / fr.rho,
+                             (q[0] * nn[1] - q[1] * nn[0]) / fr.rho, nn[0], nn[1], nn[2]};
+        int c = 0;
+#pragma unroll
+        for (int ja = 0; ja < 6; ++ja)
+#pragma unroll
+            for (int jb = ja; jb < 6; ++jb) acc[c++] += J[ja] * J[jb];
+#pragma unroll
+        for (int ja = 0; ja < 6; ++ja) acc[21 + ja] += J[ja] * r;
+        acc[27] += r * r;
+        acc[28] += 1.0;
+    }
+    __shared__ double sm[WAVES][NS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < NS; ++c) {
+        double val = acc[c];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) val += __shfl_xor(val, d, 64);
+        if (lane == 0) sm[wave][c] = val;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < NS) {
+        double val = sm[0][threadIdx.x];
+#pragma unroll
+        for (int wv = 1; wv < WAVES; ++wv) val += sm[wv][threadIdx.x];
+        partial[(size_t)strip * NS + threadIdx.x] = val;
+    }
+}
+
+struct SolveArgs {
+    int min_points, iteration;
+    double rcond, eps, max_translation, max_rotation;
+};
+
+// eigen-decomposition of the symmetric 6 x 6 matrix A (destroyed: its diagonal becomes the eigenvalues), V: the eigenvectors as columns
+__device__ void jacobi6(double* A, double* V) {
+    for (int i = 0; i < 36; ++i) V[i] = (i % 7 == 0) ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep)
+        for (int p = 0; p < 5; ++p)
+            for (int q = p + 1; q < 6; ++q) {
+                const double apq = A[6 * p + q];
+                if (apq == 0.0) continue;
+                const double theta = (A[6 * q + q] - A[6 * p + p]) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
+                for (int k = 0; k < 6; ++k) {
+                    const double akp = A[6 * k + p], akq = A[6 * k + q];
+                    A[6 * k + p] = c * akp - sn * akq;
+                    A[6 * k + q] = sn * akp + c * akq;
+                }
+                for (int k = 0; k < 6; ++k) {
+                    const double apk = A[6 * p + k], aqk = A[6 * q + k];
+                    A[6 * p + k] = c * apk - sn * aqk;
+                    A[6 * q + k] = sn * apk + c * aqk;
+                }
+                for (int k = 0; k < 6; ++k) {
+                    const double vkp = V[6 * k + p], vkq = V[6 * k + q];
+                    V[6 * k + p] = c * vkp - sn * vkq;
+                    V[6 * k + q] = sn * vkp + c * vkq;
+                }
+            }
+}
+
+// view blockIdx.x: the sums of its strips, the step, the new pose and the status
+__global__ __launch_bounds__(64) void refine_solve_kernel(State st, SolveArgs a, const int* __restrict__ view_obj,
+                                                          const int* __restrict__ view_soff, const float* __restrict__ diameters,
+                                                          const float* __restrict__ boxes, const double* __restrict__ partial) {
+    const int v = blockIdx.x;
+    const int lane = threadIdx.x;
+    const bool act = st.active[v] != 0;
+    __shared__ double S[NS], A[36], V[36];
+    __shared__ float pose_sm[16];
+    float* pose = st.poses + 16 * (size_t)v;
+    if (act && lane < NS) {
+        double val = 0.0;
+        for (int sidx = view_soff[v]; sidx < view_soff[v + 1]; ++sidx) val += partial[(size_t)sidx * NS + lane];
+        S[lane] = val;
+        if (st.sums) st.sums[((size_t)v * st.iterations + a.iteration) * NS + lane] = val;
+    }
+    if (lane < 16) pose_sm[lane] = pose[lane];
+    __syncthreads();
+    if (act && lane == 0) {
+        const float* pin = st.poses_in + 16 * (size_t)v;
+        const int N = (int)S[28];
+        const float rms = N > 0 ? (float)sqrt(S[27] / (double)N) : NAN;
+        if (st.iters[v] == 0) st.rms_before[v] = rms;
+        st.rms_after[v] = rms;
+        st.n_points[v] = N;
+        st.iters[v] += 1;
+        int status = ST_LIMIT, rank = 0;
+        bool restore = false;
+        if (N < a.min_points) {
+            status = ST_FEW;
+            restore = true;
+        } else {
+            const int o = view_obj[v];
+            Frame fr;
+            load_frame(pose, boxes + 6 * (size_t)o, diameters[o], fr);
+            int c = 0;
+            for (int i = 0; i < 6; ++i)
+                for (int j = i; j < 6; ++j) A[6 * i + j] = A[6 * j + i] = S[c++];
+            jacobi6(A, V);
+            double lmax = 0.0;
+            for (int i = 0; i < 6; ++i) lmax = fmax(lmax, A[7 * i]);
+            double x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            for (int i = 0; i < 6; ++i) {
+                const double lam = A[7 * i];
+                if (!(lam > 0.0) || lam < a.rcond * lmax) continue;
+                ++rank;
+                double g = 0.0;
+                for (int kk = 0; kk < 6; ++kk) g += V[6 * kk + i] * S[21 + kk];
+                g = g / lam;
+                for (int kk = 0; kk < 6; ++kk) x[kk] += V[6 * kk + i] * g;
+            }
+            const double th[3] = {x[0] / fr.rho, x[1] / fr.rho, x[2] / fr.rho};
+            const double a2 = (th[0] * th[0] + th[1] * th[1]) + th[2] * th[2], ang = sqrt(a2);
+            double ca, cb;                                        // Exp(th) = I + ca K + cb K K
+            if (a2 < 1e-12) {
+                ca = 1.0 - a2 / 6.0;
+                cb = 0.5 - a2 / 24.0;
+            } else {
+                ca = sin(ang) / ang;
+                cb = (1.0 - cos(ang)) / a2;
+            }
+            const double K[9] = {0.0, -th[2], th[1], th[2], 0.0, -th[0], -th[1], th[0], 0.0};
+            double E[9];
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) {
+                    const double kk2 = (K[3 * i] * K[j] + K[3 * i + 1] * K[3 + j]) + K[3 * i + 2] * K[6 + j];
+                    E[3 * i + j] = ((i == j ? 1.0 : 0.0) + ca * K[3 * i + j]) + cb * kk2;
+                }
+            float Rn[9], tn[3];
+            for (int i = 0; i < 3; ++i) {
+                for (int j = 0; j < 3; ++j)
+                    Rn[3 * i + j] = (float)((E[3 * i] * fr.R[j] + E[3 * i + 1] * fr.R[3 + j]) + E[3 * i + 2] * fr.R[6 + j]);
+                const double d[3] = {fr.t[0] - fr.c[0], fr.t[1] - fr.c[1], fr.t[2] - fr.c[2]};
+                tn[i] = (float)((fr.c[i] + ((E[3 * i] * d[0] + E[3 * i + 1] * d[1]) + E[3 * i + 2] * d[2])) + x[3 + i]);
+            }
+            // the bounds on the whole correction, from the float32 poses
+            double dt2 = 0.0, tr = 0.0;
+            for (int i = 0; i < 3; ++i) {
+                const double d = (double)tn[i] - (double)pin[4 * i + 3];
+                dt2 += d * d;
+                for (int j = 0; j < 3; ++j) tr += (double)Rn[3 * i + j] * (double)pin[4 * i + j];
+            }
+            const double rot = acos(fmin(1.0, fmax(-1.0, 0.5 * (tr - 1.0))));
+            if (!(sqrt(dt2) <= a.max_translation) || !(rot <= a.max_rotation)) {
+                status = ST_DRIFT;
+                restore = true;
+            } else {
+                for (int i = 0; i < 3; ++i) {
+                    for (int j = 0; j < 3; ++j) pose_sm[4 * i + j] = Rn[3 * i + j];
+                    pose_sm[4 * i + 3] = tn[i];
+                }
+                const double sr = sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]), sv = sqrt((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]);
+                if (fmax(sr, sv) < a.eps) status = ST_CONVERGED;
+            }
+        }
+        if (restore)
+            for (int kk = 0; kk < 16; ++kk) pose_sm[kk] = pin[kk];
+        st.rank[v] = rank;
+        st.status[v] = status;
+        if (status != ST_LIMIT) st.active[v] = 0;
+    }
+    __syncthreads();
+    if (lane < 16) {
+        if (act) pose[lane] = pose_sm[lane];
+        if (st.trajectory) st.trajectory[((size_t)v * (st.iterations + 1) + a.iteration + 1) * 16 + lane] = pose_sm[lane];
+    }
+}
+
+inline size_t align256(size_t n) { return (n + 255) / 256 * 256; }
+
+inline bool positive_finite(float v) { return v > 0.f && v <= 3.402823466e38f; }
+inline bool finite_host(float v) { return fabsf(v) <= 3.402823466e38f; }
+
+}  // namespace
+
+extern "C" {
+
+int pp_depth_refine_workspace_bytes(long long window_samples, long long view_faces, long long strips, size_t* bytes) {
+    if (!bytes || window_samples < 0 || view_faces <= 0 || strips < 0 || window_samples > (LLONG_MAX >> 5) ||
+        view_faces > (long long)UINT_MAX || strips > (long long)INT_MAX || strips > window_samples)
+        return PP_EINVAL;
+    *bytes = WS_HEADER + align256((size_t)window_samples * 8) + align256((size_t)view_faces * 8) + (size_t)strips * NS * sizeof(double);
+    return PP_OK;
+}
+
+int pp_depth_refine(const float* vertices, const int* vert_off, const int* faces, const int* face_off, const float* diameters,
+                    const float* boxes, const int* vert_off_host, const int* faces_host, const int* face_off_host,
+                    const float* diameters_host, const float* boxes_host, int n_objects, const float* cams, const float* cams_host,
+                    int n_images, int H, int W, const int* view_obj, const int* view_img, const float* poses_in, const int* windows,
+                    const long long* view_zoff, const int* view_soff, const int* view_obj_host, const int* view_img_host,
+                    const int* windows_host, const long long* view_zoff_host, const int* view_soff_host, int n_views,
+                    const float* depth, int iterations, float max_distance, int min_points, float min_cos, float rcond, float eps,
+                    float max_translation, float max_rotation, float near, void* workspace, size_t workspace_bytes, float* poses_out,
+                    int* active, int* status, int* n_iterations, int* rank, int* n_points, float* rms_before, float* rms_after,
+                    unsigned int* near_count, float* trajectory, double* sums, void* stream) {
+    if (!vertices || !vert_off || !faces || !face_off || !diameters || !boxes || !vert_off_host || !faces_host || !face_off_host ||
+        !diameters_host || !boxes_host || !cams || !cams_host || !view_obj || !view_img || !poses_in || !windows || !view_zoff ||
+        !view_soff || !view_obj_host || !view_img_host || !windows_host || !view_zoff_host || !view_soff_host || !depth || !workspace ||
+        !poses_out || !active || !status || !n_iterations || !rank || !n_points || !rms_before || !rms_after || !near_count)
+        return PP_EINVAL;
+    if (poses_in == poses_out) return PP_EINVAL;
+    if (n_objects <= 0 || n_images <= 0 || n_views <= 0 || H <= 0 || W <= 0 || (long long)H * W > INT_MAX) return PP_EINVAL;
+    if (iterations < 1 || iterations > PP_DEPTH_REFINE_MAX_ITERATIONS || min_points < 1 || !positive_finite(max_distance) ||
+        !(min_cos >= 0.f && min_cos < 1.f) || !(rcond >= 0.f && rcond < 1.f) || !(eps >= 0.f && finite_host(eps)) ||
+        !positive_finite(max_translation) || !positive_finite(max_rotation) || !positive_finite(near))
+        return PP_EINVAL;
+    if (vert_off_host[0] != 0 || face_off_host[0] != 0) return PP_EINVAL;
+    for (int o = 0; o < n_objects; ++o) {
+        if (vert_off_host[o + 1] <= vert_off_host[o] || face_off_host[o + 1] < face_off_host[o]) return PP_EINVAL;
+        if (!positive_finite(diameters_host[o])) return PP_EINVAL;
+        for (int d = 0; d < 3; ++d) {
+            const float lo = boxes_host[6 * (size_t)o + d], hi = boxes_host[6 * (size_t)o + 3 + d];
+            if (!finite_host(lo) || !finite_host(hi) || hi < lo) return PP_EINVAL;
+        }
+        const unsigned nv = (unsigned)(vert_off_host[o + 1] - vert_off_host[o]);
+        for (size_t k = 3 * (size_t)face_off_host[o]; k < 3 * (size_t)face_off_host[o + 1]; ++k)
+            if ((unsigned)faces_host[k] >= nv) return PP_EINVAL;
+    }
+    for (int i = 0; i < n_images; ++i) {
+        const float* k = cams_host + 4 * (size_t)i;
+        if (k[0] == 0.f || k[1] == 0.f || !finite_host(k[0]) || !finite_host(k[1]) || !finite_host(k[2]) || !finite_host(k[3]))
+            return PP_EINVAL;
+    }
+    if (view_zoff_host[0] != 0 || view_soff_host[0] != 0) return PP_EINVAL;
+    long long total_faces = 0;
+    int max_faces = 0;
+    for (int v = 0; v < n_views; ++v) {
+        const int o = view_obj_host[v];
+        if ((unsigned)o >= (unsigned)n_objects || (unsigned)view_img_host[v] >= (unsigned)n_images) return PP_EINVAL;
+        const int nf = face_off_host[o + 1] - face_off_host[o];
+        if (nf <= 0) return PP_EINVAL;                            // an object of the call without faces
+        const int* w = windows_host + 4 * (size_t)v;
+        if (w[0] < 0 || w[1] < 0 || w[2] < w[0] || w[3] < w[1] || w[2] > W || w[3] > H) return PP_EINVAL;
+        const long long ws = (long long)(w[2] - w[0]) * (w[3] - w[1]);
+        if (view_zoff_host[v + 1] - view_zoff_host[v] != ws) return PP_EINVAL;
+        const long long strips_v = ws > 0 ? (w[3] - w[1] + ROWS - 1) / ROWS : 0;
+        if ((long long)view_soff_host[v + 1] - view_soff_host[v] != strips_v) return PP_EINVAL;
+        total_faces += nf;
+        max_faces = nf > max_faces ? nf : max_faces;
+    }
+    if (total_faces > (long long)UINT_MAX) return PP_EINVAL;
+    const long long samples = view_zoff_host[n_views];
+    const int strips = view_soff_host[n_views];
+    size_t need = 0;
+    if (pp_depth_refine_workspace_bytes(samples, total_faces, strips, &need) != PP_OK) return PP_EINVAL;
+    if (((uintptr_t)workspace % 256) != 0 || workspace_bytes < need) return PP_EWORKSPACE;
+
+    hipStream_t st = (hipStream_t)stream;
+    unsigned* qcount = (unsigned*)workspace;
+    unsigned long long* zbuf = (unsigned long long*)((char*)workspace + WS_HEADER);
+    uint2* queue = (uint2*)((char*)zbuf + align256((size_t)samples * 8));
+    double* partial = (double*)((char*)queue + align256((size_t)total_faces * 8));
+    Scene s{vertices, vert_off, faces, face_off, cams, view_obj, view_img, poses_out, windows, view_zoff, n_views, H, W, near};
+    s.active = active;
+    const State state{poses_in, poses_out, active, status, n_iterations, rank, n_points, rms_before, rms_after, trajectory, sums, iterations};
+    PP_CHECK_HIP(hipMemsetAsync(near_count, 0, sizeof(unsigned) * (size_t)n_views, st));
+    if (sums) PP_CHECK_HIP(hipMemsetAsync(sums, 0, sizeof(double) * (size_t)n_views * iterations * NS, st));
+    hipLaunchKernelGGL(refine_init_kernel, dim3((unsigned)((n_views + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, state, windows, n_views);
+    for (int it = 0; it < iterations && strips > 0; ++it) {
+        PP_CHECK_HIP(hipMemsetAsync(qcount, 0, sizeof(unsigned), st));
+        PP_CHECK_HIP(hipMemsetAsync(zbuf, 0xFF, (size_t)samples * 8, st));
+        launch_raster(s, max_faces, total_faces, zbuf, queue, qcount, near_count, st);
+        hipLaunchKernelGGL(refine_accumulate_kernel, dim3((unsigned)strips), dim3(BLOCK), 0, st, s, zbuf, view_soff, diameters, boxes, depth,
+                           max_distance, min_cos, partial);
+        const SolveArgs a{min_points, it, (double)rcond, (double)eps, (double)max_translation, (double)max_rotation};
+        hipLaunchKernelGGL(refine_solve_kernel, dim3((unsigned)n_views), dim3(64), 0, st, state, a, view_obj, view_soff, diameters, boxes,
+                           partial);
+    }
+    return pp_last_launch();
+}
+
+}  // extern "C"

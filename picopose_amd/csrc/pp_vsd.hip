@@ -1,9 +1,7 @@
 // BOP19 VSD of (estimate, ground truth) pairs (picopose_amd/evaluation.py plans every call; the contract is stated in
 // include/picopose_hip.h and restated in numpy by tests/vsd_oracle.py).
 //
-//   vsd_raster_small_kernel  one lane per (view, triangle of the view's object): tri_setup under the view's camera and window; a box
-//                            of at most SMALL_BOX samples is walked by the lane, a larger one goes to the queue
-//   vsd_raster_large_kernel  queue entries -> 16 x 16 tiles, one workgroup step per tile (the template renderer's scheme)
+//   vsd_raster_small_kernel, vsd_raster_large_kernel  the windowed depth raster of pp_vsd_raster_dev.h (shared with pp_depth_refine.hip)
 //   vsd_depth_kernel         optional: the window's z-buffer words -> a dense (n_views, H, W) float32 depth image
 //   vsd_pair_kernel          one workgroup per pair: walks the union box of the two windows, reads Z_est / Z_gt from the z-buffer
 //                            words and the test depth from the image, keeps |union|, |inter| and n_1 .. n_T as per-lane INTEGERS,
@@ -18,7 +16,7 @@
 #include "pp_common.h"
 
 #pragma clang fp contract(off)
-#include "pp_raster_dev.h"
+#include "pp_vsd_raster_dev.h"
 
 namespace {
 
@@ -30,101 +28,6 @@ constexpr int NC = 2 + PP_VSD_MAX_TAUS;   // counters of a pair: union, inter, n
 struct Taus {
     float v[PP_VSD_MAX_TAUS];
 };
-
-// the tables of a call (device pointers)
-struct Scene {
-    const float* verts;
-    const int* vert_off;
-    const int* faces;
-    const int* face_off;
-    const float* cams;         // (n_images, 4) fx, fy, cx, cy
-    const int* view_obj;
-    const int* view_img;
-    const float* poses;        // (n_views, 16)
-    const int* windows;        // (n_views, 4) x0, y0, x1, y1 (exclusive upper corner)
-    const long long* view_zoff;
-    int n_views, H, W;
-    float near;
-};
-
-struct View {
-    const float* verts;
-    const int* faces;
-    const float* pose;
-    int Nv, Nf, x0, y0, ww;
-    Cam cam;
-};
-
-// false: the view's window is empty, nothing is rendered
-__device__ __forceinline__ bool load_view(const Scene& s, int v, View& out) {
-    const int* w = s.windows + 4 * (size_t)v;
-    const int x0 = w[0], y0 = w[1], x1 = w[2], y1 = w[3];
-    if (x1 <= x0 || y1 <= y0) return false;
-    const int o = s.view_obj[v];
-    const float* k = s.cams + 4 * (size_t)s.view_img[v];
-    const int v0 = s.vert_off[o], f0 = s.face_off[o];
-    out.verts = s.verts + 3 * (size_t)v0;
-    out.Nv = s.vert_off[o + 1] - v0;
-    out.faces = s.faces + 3 * (size_t)f0;
-    out.Nf = s.face_off[o + 1] - f0;
-    out.pose = s.poses + 16 * (size_t)v;
-    out.x0 = x0;
-    out.y0 = y0;
-    out.ww = x1 - x0;
-    out.cam = Cam{k[0], k[1], k[2], k[3], s.near, s.H, s.W, x0, y0, x1, y1};
-    return true;
-}
-
-__device__ __forceinline__ unsigned long long* slot_of(unsigned long long* zv, const View& vw, int px, int py) {
-    return zv + (size_t)(py - vw.y0) * vw.ww + (px - vw.x0);
-}
-
-// view blockIdx.y, blockIdx.y + gridDim.y, ...; faces blockIdx.x * 256 + lane of that view's object
-__global__ __launch_bounds__(BLOCK) void vsd_raster_small_kernel(Scene s, unsigned long long* __restrict__ zbuf,
-                                                                 uint2* __restrict__ queue, unsigned* __restrict__ qcount,
-                                                                 unsigned* __restrict__ near_count) {
-    const int f = blockIdx.x * BLOCK + threadIdx.x;
-    for (int v = blockIdx.y; v < s.n_views; v += gridDim.y) {
-        View vw;
-        if (!load_view(s, v, vw) || f >= vw.Nf) continue;
-        Tri t;
-        const int st = tri_setup(vw.verts, vw.faces, vw.Nv, vw.pose, vw.cam, f, t);
-        if (st == TRI_NEAR) atomicAdd(near_count + v, 1u);
-        if (st != TRI_OK) continue;
-        if ((t.bx1 - t.bx0 + 1) * (long long)(t.by1 - t.by0 + 1) > SMALL_BOX) {
-            queue[atomicAdd(qcount, 1u)] = make_uint2((unsigned)v, (unsigned)f);
-            continue;
-        }
-        unsigned long long* zv = zbuf + s.view_zoff[v];
-        for (int py = t.by0; py <= t.by1; ++py)
-            for (int px = t.bx0; px <= t.bx1; ++px) depth_test(t, px, py, f, slot_of(zv, vw, px, py));
-    }
-}
-
-// queue entry blockIdx.y, blockIdx.y + gridDim.y, ...; its tiles blockIdx.x, blockIdx.x + gridDim.x, ...
-__global__ __launch_bounds__(TILE * TILE) void vsd_raster_large_kernel(Scene s, unsigned long long* __restrict__ zbuf,
-                                                                       const uint2* __restrict__ queue,
-                                                                       const unsigned* __restrict__ qcount) {
-    const unsigned n = *qcount;
-    const int ty = threadIdx.x / TILE, tx = threadIdx.x % TILE;
-    for (unsigned e = blockIdx.y; e < n; e += gridDim.y) {
-        const uint2 q = queue[e];
-        if (q.x >= (unsigned)s.n_views) continue;
-        View vw;
-        if (!load_view(s, (int)q.x, vw) || q.y >= (unsigned)vw.Nf) continue;
-        Tri t;
-        if (tri_setup(vw.verts, vw.faces, vw.Nv, vw.pose, vw.cam, (int)q.y, t) != TRI_OK) continue;
-        unsigned long long* zv = zbuf + s.view_zoff[q.x];
-        const int ntx = (t.bx1 - t.bx0) / TILE + 1, nty = (t.by1 - t.by0) / TILE + 1;
-        for (int tile = blockIdx.x; tile < ntx * nty; tile += gridDim.x) {
-            const int x0 = t.bx0 + (tile % ntx) * TILE, y0 = t.by0 + (tile / ntx) * TILE;
-            const int x1 = min(x0 + TILE - 1, t.bx1), y1 = min(y0 + TILE - 1, t.by1);
-            if (tile_outside(t, x0, y0, x1, y1)) continue;
-            const int px = x0 + tx, py = y0 + ty;
-            if (px <= x1 && py <= y1) depth_test(t, px, py, (int)q.y, slot_of(zv, vw, px, py));
-        }
-    }
-}
 
 __device__ __forceinline__ float word_depth(unsigned long long key) {
     return key == ~0ull ? 0.f : __uint_as_float((unsigned)(key >> 32));
@@ -305,16 +208,11 @@ int pp_vsd_errors(const float* vertices, const int* vert_off, const int* faces, 
     unsigned long long* zbuf = (unsigned long long*)((char*)workspace + WS_HEADER);
     uint2* queue = (uint2*)((char*)zbuf + align256((size_t)samples * 8));
     const Scene s{vertices, vert_off, faces, face_off, cams, view_obj, view_img, poses, windows, view_zoff, n_views, H, W, near};
-    const unsigned gv = (unsigned)(n_views < 65535 ? n_views : 65535);
+    const unsigned gv = (unsigned)(n_views < 65535 ? n_views : 65535);   // (the depth kernel's view stride)
     PP_CHECK_HIP(hipMemsetAsync(near_count, 0, sizeof(unsigned) * (size_t)n_views, st));
     PP_CHECK_HIP(hipMemsetAsync(qcount, 0, sizeof(unsigned), st));
     if (samples > 0) PP_CHECK_HIP(hipMemsetAsync(zbuf, 0xFF, (size_t)samples * 8, st));
-    if (samples > 0) {
-        hipLaunchKernelGGL(vsd_raster_small_kernel, dim3((unsigned)((max_faces + BLOCK - 1) / BLOCK), gv), dim3(BLOCK), 0, st, s, zbuf,
-                           queue, qcount, near_count);
-        const unsigned gy = (unsigned)(total_faces < 4096 ? total_faces : 4096);
-        hipLaunchKernelGGL(vsd_raster_large_kernel, dim3(8, gy), dim3(TILE * TILE), 0, st, s, zbuf, queue, qcount);
-    }
+    if (samples > 0) launch_raster(s, max_faces, total_faces, zbuf, queue, qcount, near_count, st);
     if (depth_out) {
         PP_CHECK_HIP(hipMemsetAsync(depth_out, 0, (size_t)n_views * H * W * sizeof(float), st));
         if (samples > 0) {

@@ -251,11 +251,61 @@ def _collect(pending, hyp, net, pnp_refine=None):
     return _rank_hypotheses(s2_host.numpy(), rot, tvec, ratio, ok, hyp)
 
 
-def bop_csv_lines(scene_id, img_id, obj_ids, scores, preds_image, image_time):
-    """The BOP results rows of run_test.py:191-206: one line per instance, best hypothesis, t in millimetres."""
+STAGES = {"stage_3": ("R_stage_3", "t_stage_3"), "depth": ("R_depth", "t_depth")}
+
+
+def bop_csv_lines(scene_id, img_id, obj_ids, scores, preds_image, image_time, stage="stage_3"):
+    """The BOP results rows of run_test.py:191-206: one line per instance, best hypothesis, t in millimetres.
+    stage: "stage_3" (default) writes the network's pose, "depth" the depth-refined one (refine_predictions must have run: an
+    instance whose best hypothesis holds no R_depth is a ValueError)."""
+    if stage not in STAGES:
+        raise ValueError(f"stage must be one of {sorted(STAGES)}, got {stage!r}")
+    kr, kt = STAGES[stage]
     lines = []
     for k, preds in enumerate(preds_image):
+        if kr not in preds[0]:
+            raise ValueError(f"instance {k}: its best hypothesis holds no {kr!r}; run refine_predictions first")
         lines.append(",".join((str(scene_id), str(img_id), str(obj_ids[k]), str(scores[k]),
-                               " ".join(str(v) for v in preds[0]["R_stage_3"]),
-                               " ".join(str(v) for v in preds[0]["t_stage_3"]), f"{image_time}\n")))
+                               " ".join(str(v) for v in preds[0][kr]),
+                               " ".join(str(v) for v in preds[0][kt]), f"{image_time}\n")))
     return lines
+
+
+def refine_predictions(preds_image, models, obj_ids, K, depth, depth_scale=None, hypotheses="best", rank_by="inliers_ratio", **kw):
+    """Depth refinement of one image's predictions (depth_refine.refine_poses_depth, ONE call for the whole image) -> a new
+    preds_image; the input is not modified.  preds_image: infer_image's result; obj_ids: the object id of each instance (ids known
+    to `models`, an evaluation.ObjectModels with faces); K (3, 3); depth (H, W) or (1, H, W), uint16 raw with `depth_scale` or float
+    millimetres; **kw: refine_poses_depth's parameters.
+    hypotheses: "best" refines each instance's first hypothesis, "all" every one.  A refined hypothesis gains 'R_depth' (9,),
+    't_depth' (3,) in mm (float32; the input pose where depth_status >= 2), 'depth_status' and 'depth_rms' (rms_after).
+    rank_by: "inliers_ratio" keeps the order; "depth" (with "all") re-sorts each instance's hypotheses, stably: those with
+    depth_status <= 1 first, in ascending depth_rms, then the others in their order.  ValueError before any device work for another
+    value, rank_by="depth" without "all", or obj_ids that do not match preds_image."""
+    from .depth_refine import refine_poses_depth
+
+    if hypotheses not in ("best", "all"):
+        raise ValueError(f"hypotheses must be 'best' or 'all', got {hypotheses!r}")
+    if rank_by not in ("inliers_ratio", "depth"):
+        raise ValueError(f"rank_by must be 'inliers_ratio' or 'depth', got {rank_by!r}")
+    if rank_by == "depth" and hypotheses != "all":
+        raise ValueError("rank_by='depth' compares an instance's hypotheses: it needs hypotheses='all'")
+    if len(obj_ids) != len(preds_image):
+        raise ValueError(f"obj_ids must hold one id per instance: {len(obj_ids)} ids for {len(preds_image)} instances")
+    if getattr(depth, "ndim", 0) == 2:
+        depth = depth[None]
+    if getattr(depth, "ndim", 0) != 3 or depth.shape[0] != 1:
+        raise ValueError(f"depth must be one (H, W) image, got shape {tuple(getattr(depth, 'shape', ()))}")
+    where = [(i, h) for i, hyps in enumerate(preds_image) for h in range(len(hyps) if hypotheses == "all" else min(1, len(hyps)))]
+    R = np.array([np.asarray(preds_image[i][h]["R_stage_3"], dtype=np.float64).reshape(3, 3) for i, h in where]).reshape(-1, 3, 3)
+    t = np.array([np.asarray(preds_image[i][h]["t_stage_3"], dtype=np.float64).reshape(3) for i, h in where]).reshape(-1, 3)
+    ids = np.array([int(obj_ids[i]) for i, _ in where], dtype=np.int64)
+    res = refine_poses_depth(models, ids, R, t, K, depth, depth_scale=depth_scale, **kw)
+    Rd, td = res["R"].cpu().numpy().reshape(-1, 9), res["t"].cpu().numpy()
+    status, rms = res["status"].cpu().numpy(), res["rms_after"].cpu().numpy()
+    out = [[dict(h) for h in hyps] for hyps in preds_image]
+    for n, (i, h) in enumerate(where):
+        out[i][h].update(R_depth=Rd[n], t_depth=td[n], depth_status=int(status[n]), depth_rms=float(rms[n]))
+    if rank_by == "depth":
+        for hyps in out:
+            hyps.sort(key=lambda h: (0, h["depth_rms"]) if h["depth_status"] <= 1 else (1, 0.0))
+    return out
