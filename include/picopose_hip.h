@@ -854,6 +854,61 @@ int pp_render_views(const float* vertices, int n_vertices, const int* faces, con
                     const unsigned char* colors, const float* poses, int n_views, float fx, float fy, float cx, float cy, int H,
                     int W, float near, void* workspace, size_t workspace_bytes, unsigned char* rgba, unsigned short* depth_mm,
                     float* depth_m, int* face_id, unsigned int* near_count, void* stream);
+/* -------------------------------------------------------------------------
+ * THE TEXTURE CONTRACT: the same render for a UV-textured mesh (BOP's `obj_NNNNNN.ply` with `texture_u texture_v` and a
+ * `comment TextureFile`).  The reference's recipe is textured and unshaded: rendering/src/custom_megapose/panda3d_scene_renderer.py:70-73
+ * sets `texture-minfilter mipmap` and call_panda3d.py:57-62 lights the object with ambient light of colour 1, so a pixel is the
+ * filtered texture colour.  Items 1-5, 7 and 8 of THE RASTER CONTRACT (coverage, depth, alpha, depth_mm, face_id) hold unchanged;
+ * only the colour of item 6 changes, to T3-T5.  tests/texture_oracle.py restates T2-T5 in numpy; the kernels equal it bit for bit.
+ * Float operations are IEEE float32, one rounding each, never contracted, in the order written.
+ *  T1. Inputs.  The texture is (Ht, Wt, 3) uint8 RGB, row 0 the top row of the image file, 1 <= Wt, Ht <= PP_TEXTURE_MAX.  UVs are
+ *      per corner: face_uv (Nf, 3, 2) float32 = (u, v) of corner k of face f, in the order of `faces`; u runs to the right, v runs
+ *      UP (v = 0 is the bottom row of the image: the PLY / OBJ / Panda3D convention).  Per-corner UVs are the only device layout;
+ *      per-vertex UVs are expanded by the caller (uv[faces]).
+ *  T2. Mip pyramid (pp_texture_build_mips, once per texture).  Level 0 is the image.  Level l + 1 has W' = max(1, W_l >> 1) by
+ *      H' = max(1, H_l >> 1) texels; texel (x, y) is (a + b + c + d + 2) >> 2 per channel over the four taps
+ *      (min(2x, W_l - 1) | min(2x + 1, W_l - 1), min(2y, H_l - 1) | min(2y + 1, H_l - 1)) of level l.  Levels go down to 1 x 1.
+ *      Integer arithmetic: the pyramid equals a numpy one bit for bit.  Storage: uchar4 texels {r, g, b, 255}, row-major, the
+ *      levels back to back from level 0 (pp_texture_mips_bytes gives the size and the number of levels), so each of a sample's
+ *      four texels is one 4-byte load.
+ *  T3. Level of detail: one level per (view, face), constant over the triangle, recomputed for the winning face by the resolve pass
+ *      (nothing is stored per triangle).  With the corner UVs in the order item 4 left the corners in,
+ *        A_t = (fabsf(((u1 - u0) (v2 - v0)) - ((v1 - v0) (u2 - u0))) * (float) Wt) * (float) Ht     (twice the texel area)
+ *        A_p = (float) area2 / 65536                                                                (twice the pixel area)
+ *      the level is the smallest l >= 0 with A_t <= (2 A_p) 4^l, capped at the last level; (2 A_p) 4^l is formed by repeated
+ *      multiplication by 4, which is exact — no log2.  A_t that is zero or NaN gives level 0.  A linear footprint (texels per pixel)
+ *      of 1 therefore samples level 0, 2 level 1, 4 level 2: the switch points lie at sqrt(2) 2^k.  Exchanging corners 1 and 2
+ *      negates the determinant exactly, so the level does not depend on the winding.
+ *  T4. Coordinates at a covered sample: u = ((p0 u0 + p1 u1) + p2 u2) / q and v likewise, p_k and q of item 6 (perspective
+ *      correct).  Wrap mode repeat on both axes: u' = u - floorf(u), v' = v - floorf(v).
+ *  T5. Bilinear sample of level l (W_l x H_l): x = u' W_l - 0.5, y = (1 - v') H_l - 0.5 (texel centres at half-integer texture
+ *      coordinates, v flipped); x0 = floorf(x), fx = x - x0, y0 = floorf(y), fy = y - y0; taps x0, x0 + 1 and y0, y0 + 1 reduced by
+ *      a positive modulo of W_l / H_l (u', v' in [0, 1] put x0 in [-1, W_l - 1]: -1 wraps to W_l - 1 and W_l to 0).  Per channel,
+ *      with c_yx the texels as floats: a = c00 + fx (c01 - c00), b = c10 + fx (c11 - c10), val = a + fy (b - a),
+ *      out = min(255, max(0, floorf(val + 0.5))); alpha = 255.  A coordinate that is not finite (UVs that are, or overflow) reads
+ *      texels inside the level and gives an unspecified colour, never a fault.
+ *  T6. OUT OF SCOPE: anisotropic filtering and trilinear blending between levels (one level per face, chosen by area); multisampled
+ *      edges (the reference enables 4x MSAA; silhouettes here are single-sampled as in item 5); clamp and mirror wrap modes;
+ *      texture alpha (a texel's alpha is ignored: convert to RGB first); more than one texture per mesh; shading.  Parity with
+ *      Panda3D's pixels stays UNPINNED, as for the rest of the render.
+ *
+ * pp_texture_mips_bytes: *bytes = 4 * the texels of all levels, *levels (may be NULL) = their number.  PP_EINVAL: bytes NULL, Wt or
+ * Ht outside [1, PP_TEXTURE_MAX].
+ * pp_texture_build_mips: rgb (Ht, Wt, 3) uint8 and mips (4-byte aligned, mips_bytes >= pp_texture_mips_bytes) on the device; packs
+ * level 0 and builds every further level, one launch per level, on `stream`.  PP_EINVAL: null pointer, size out of range, mips
+ * misaligned or too small.
+ * pp_render_views_textured: pp_render_views with `colors` replaced by face_uv (Nf, 3, 2) fp32, the pyramid and the texture's size;
+ * the coverage launches are the same, the resolve pass implements T3-T5.  Everything said of pp_render_views' other arguments,
+ * chunking and errors holds; also PP_EINVAL: face_uv or mips NULL or not 4-byte aligned, Wt or Ht outside [1, PP_TEXTURE_MAX].
+ * ------------------------------------------------------------------------- */
+#define PP_TEXTURE_MAX 16384
+int pp_texture_mips_bytes(int Wt, int Ht, size_t* bytes, int* levels);
+int pp_texture_build_mips(const unsigned char* rgb, int Wt, int Ht, void* mips, size_t mips_bytes, void* stream);
+int pp_render_views_textured(const float* vertices, int n_vertices, const int* faces, const int* faces_host, int n_faces,
+                             const float* face_uv, const void* mips, int Wt, int Ht, const float* poses, int n_views, float fx,
+                             float fy, float cx, float cy, int H, int W, float near, void* workspace, size_t workspace_bytes,
+                             unsigned char* rgba, unsigned short* depth_mm, float* depth_m, int* face_id, unsigned int* near_count,
+                             void* stream);
 /* Per view the first / last row and column with alpha != 0 — the np.any / np.where of get_bbox (utils/data_utils.py:131-137) on
  * rgba[..., 3]: extents (V, 4) int32 = {rmin, rmax, cmin, cmax} (inclusive; -1 each for a view that covers nothing);
  * counts (V) int32 covered samples, may be NULL. */

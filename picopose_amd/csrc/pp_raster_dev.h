@@ -29,6 +29,7 @@ struct Cam {
 struct Tri {
     int x[3], y[3];      // snapped screen coordinates, ordered so that area2 > 0
     int id[3];           // vertex indices in that order
+    int swapped;         // 1 when corners 1 and 2 were exchanged for that: per-corner attributes follow (no arithmetic reads it)
     float iz[3];         // 1 / Zc
     long long area2;
     int bx0, bx1, by0, by1;   // inclusive sample box, clipped to the clip rectangle
@@ -64,6 +65,7 @@ __device__ __forceinline__ int tri_setup(const float* __restrict__ verts, const 
     if (near_hit) return TRI_NEAR;
     long long area2 = (long long)(t.x[1] - t.x[0]) * (t.y[2] - t.y[0]) - (long long)(t.y[1] - t.y[0]) * (t.x[2] - t.x[0]);
     if (area2 == 0) return TRI_SKIP;
+    t.swapped = area2 < 0;
     if (area2 < 0) {
         area2 = -area2;
         int s = t.x[1]; t.x[1] = t.x[2]; t.x[2] = s;

@@ -12,6 +12,10 @@
 // does not depend on the order in which triangles arrive.  A lane walks the box of a triangle of at most SMALL_BOX samples; a
 // larger box goes to a queue and is rasterised by workgroups, one 16 x 16 tile per step, after the tile is tested against the
 // three edges.
+//
+// A UV-textured mesh (pp_render_views_textured) shares the coverage launches; only the colour of the resolve pass differs: THE
+// TEXTURE CONTRACT of include/picopose_hip.h (T1-T5), restated by tests/texture_oracle.py.  The mip pyramid is built once per
+// texture by pp_texture_build_mips, one launch per level, in integer arithmetic.
 #include <stdint.h>
 #include <limits.h>
 #include "pp_common.h"
@@ -73,14 +77,76 @@ __global__ __launch_bounds__(TILE * TILE) void raster_large_kernel(const float* 
     }
 }
 
-__global__ __launch_bounds__(256) void resolve_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
-                                                      const unsigned char* __restrict__ colors, int Nv, int Nf,
-                                                      const float* __restrict__ poses, int n_views, Cam cam,
-                                                      const unsigned long long* __restrict__ zbuf, uchar4* __restrict__ rgba,
-                                                      unsigned short* __restrict__ depth_mm, float* __restrict__ depth_m,
-                                                      int* __restrict__ face_id) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x, hw = (long long)cam.H * cam.W;
-    if (i >= hw * n_views) return;
+// item 6's colour of a covered sample: the perspective blend of the three vertex colours
+struct VertexColour {
+    const unsigned char* __restrict__ colors;
+    __device__ __forceinline__ uchar4 operator()(const Tri& t, int, const float p[3], float q) const {
+        unsigned char c[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float c0 = (float)colors[3 * (size_t)t.id[0] + ch], c1 = (float)colors[3 * (size_t)t.id[1] + ch],
+                        c2 = (float)colors[3 * (size_t)t.id[2] + ch];
+            const float v = floorf((((p[0] * c0 + p[1] * c1) + p[2] * c2) / q) + 0.5f);
+            c[ch] = (unsigned char)fminf(fmaxf(v, 0.f), 255.f);
+        }
+        return make_uchar4(c[0], c[1], c[2], 255);
+    }
+};
+
+// T3-T5 of the texture contract.  The level and the corner UVs are the same for every sample of a face but not for a wave (a wave
+// of the resolve pass holds 64 neighbouring samples of a row, which may belong to as many faces): they are per-lane values, the
+// texel loads are a per-lane gather of four 4-byte words, and nothing of it is forced wave-uniform.
+struct Textured {
+    const float* __restrict__ face_uv;      // (Nf, 3, 2)
+    const uchar4* __restrict__ mips;        // level 0, 1, ... back to back
+    int Wt, Ht;
+    __device__ __forceinline__ uchar4 operator()(const Tri& t, int face, const float p[3], float q) const {
+        const float* uv = face_uv + 6 * (size_t)face;
+        const int k1 = t.swapped ? 2 : 1, k2 = 3 - k1;           // the corner order tri_setup left in t.id
+        const float u0 = uv[0], v0 = uv[1], u1 = uv[2 * k1], v1 = uv[2 * k1 + 1], u2 = uv[2 * k2], v2 = uv[2 * k2 + 1];
+        // T3: the smallest level whose texels are no smaller than half a pixel's area, by exact multiplications by 4
+        const float at = (fabsf(((u1 - u0) * (v2 - v0)) - ((v1 - v0) * (u2 - u0))) * (float)Wt) * (float)Ht;
+        float lim = 2.f * ((float)t.area2 / 65536.f);
+        int W = Wt, H = Ht;
+        size_t off = 0;
+        if (at > 0.f)                                            // (zero or NaN: level 0)
+            while ((W > 1 || H > 1) && !(at <= lim)) {
+                off += (size_t)W * H;
+                W = max(1, W >> 1);
+                H = max(1, H >> 1);
+                lim = lim * 4.f;
+            }
+        // T4
+        float u = ((p[0] * u0 + p[1] * u1) + p[2] * u2) / q, v = ((p[0] * v0 + p[1] * v1) + p[2] * v2) / q;
+        u = u - floorf(u);
+        v = v - floorf(v);
+        // T5.  u, v in [0, 1] put floor(x) in [-1, W - 1], where the positive modulo is a single wrap at either end; the clamp changes
+        // no such value and keeps the taps of a non-finite coordinate inside the level
+        const float x = u * (float)W - 0.5f, y = (1.f - v) * (float)H - 0.5f;
+        const float xf = floorf(x), yf = floorf(y), fx = x - xf, fy = y - yf;
+        const int x0 = (int)fminf(fmaxf(xf, -1.f), (float)(W - 1)), y0 = (int)fminf(fmaxf(yf, -1.f), (float)(H - 1));
+        const int xa = x0 < 0 ? W - 1 : x0, xb = x0 + 1 >= W ? 0 : x0 + 1;
+        const int ya = y0 < 0 ? H - 1 : y0, yb = y0 + 1 >= H ? 0 : y0 + 1;
+        const uchar4* level = mips + off;
+        const uchar4 c00 = level[(size_t)ya * W + xa], c01 = level[(size_t)ya * W + xb], c10 = level[(size_t)yb * W + xa],
+                     c11 = level[(size_t)yb * W + xb];
+        auto blend = [&](unsigned char t00, unsigned char t01, unsigned char t10, unsigned char t11) -> unsigned char {
+            const float f00 = (float)t00, f01 = (float)t01, f10 = (float)t10, f11 = (float)t11;
+            const float a = f00 + fx * (f01 - f00), b = f10 + fx * (f11 - f10);
+            return (unsigned char)fminf(fmaxf(floorf((a + fy * (b - a)) + 0.5f), 0.f), 255.f);
+        };
+        return make_uchar4(blend(c00.x, c01.x, c10.x, c11.x), blend(c00.y, c01.y, c10.y, c11.y), blend(c00.z, c01.z, c10.z, c11.z), 255);
+    }
+};
+
+// items 6-8 for sample i of the chunk: the winning face is set up again and its colour comes from `colour`
+template <class Colour>
+__device__ __forceinline__ void resolve_sample(long long i, const float* __restrict__ verts, const int* __restrict__ faces, int Nv,
+                                               int Nf, const float* __restrict__ poses, const Cam& cam,
+                                               const unsigned long long* __restrict__ zbuf, const Colour& colour,
+                                               uchar4* __restrict__ rgba, unsigned short* __restrict__ depth_mm,
+                                               float* __restrict__ depth_m, int* __restrict__ face_id) {
+    const long long hw = (long long)cam.H * cam.W;
     const unsigned long long key = zbuf[i];
     uchar4 col = make_uchar4(0, 0, 0, 0);
     float z = 0.f;
@@ -95,15 +161,7 @@ __global__ __launch_bounds__(256) void resolve_kernel(const float* __restrict__ 
         float p[3];
         if (face < Nf && tri_setup(verts, faces, Nv, poses + 16 * (size_t)view, cam, face, t) == TRI_OK && covers(t, px, py, w)) {
             const float q = weights(t, w, p);
-            unsigned char c[3];
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const float c0 = (float)colors[3 * (size_t)t.id[0] + ch], c1 = (float)colors[3 * (size_t)t.id[1] + ch],
-                            c2 = (float)colors[3 * (size_t)t.id[2] + ch];
-                const float v = floorf((((p[0] * c0 + p[1] * c1) + p[2] * c2) / q) + 0.5f);
-                c[ch] = (unsigned char)fminf(fmaxf(v, 0.f), 255.f);
-            }
-            col = make_uchar4(c[0], c[1], c[2], 255);
+            col = colour(t, face, p, q);
         }
         mm = (unsigned short)fminf(rintf(1000.f * z), 65535.f);
     }
@@ -111,6 +169,46 @@ __global__ __launch_bounds__(256) void resolve_kernel(const float* __restrict__ 
     depth_mm[i] = mm;
     if (depth_m) depth_m[i] = z;
     if (face_id) face_id[i] = face;
+}
+
+__global__ __launch_bounds__(256) void resolve_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
+                                                      const unsigned char* __restrict__ colors, int Nv, int Nf,
+                                                      const float* __restrict__ poses, int n_views, Cam cam,
+                                                      const unsigned long long* __restrict__ zbuf, uchar4* __restrict__ rgba,
+                                                      unsigned short* __restrict__ depth_mm, float* __restrict__ depth_m,
+                                                      int* __restrict__ face_id) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)cam.H * cam.W * n_views) return;
+    resolve_sample(i, verts, faces, Nv, Nf, poses, cam, zbuf, VertexColour{colors}, rgba, depth_mm, depth_m, face_id);
+}
+
+__global__ __launch_bounds__(256) void resolve_textured_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
+                                                               Textured tex, int Nv, int Nf, const float* __restrict__ poses,
+                                                               int n_views, Cam cam, const unsigned long long* __restrict__ zbuf,
+                                                               uchar4* __restrict__ rgba, unsigned short* __restrict__ depth_mm,
+                                                               float* __restrict__ depth_m, int* __restrict__ face_id) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)cam.H * cam.W * n_views) return;
+    resolve_sample(i, verts, faces, Nv, Nf, poses, cam, zbuf, tex, rgba, depth_mm, depth_m, face_id);
+}
+
+// T2, level 0: RGB bytes to uchar4 texels (alpha 255)
+__global__ __launch_bounds__(256) void texture_pack_kernel(const unsigned char* __restrict__ rgb, long long n, uchar4* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[i] = make_uchar4(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 255);
+}
+
+// T2, level l + 1 (Wd x Hd) from level l (Ws x Hs): the rounded mean of a 2 x 2 block whose taps are clamped to the level
+__global__ __launch_bounds__(256) void texture_down_kernel(const uchar4* __restrict__ src, int Ws, int Hs, uchar4* __restrict__ dst,
+                                                           int Wd, int Hd) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)Wd * Hd) return;
+    const int y = (int)(i / Wd), x = (int)(i - (long long)y * Wd);
+    const int xa = min(2 * x, Ws - 1), xb = min(2 * x + 1, Ws - 1), ya = min(2 * y, Hs - 1), yb = min(2 * y + 1, Hs - 1);
+    const uchar4 a = src[(size_t)ya * Ws + xa], b = src[(size_t)ya * Ws + xb], c = src[(size_t)yb * Ws + xa], d = src[(size_t)yb * Ws + xb];
+    dst[i] = make_uchar4((unsigned char)((a.x + b.x + c.x + d.x + 2) >> 2), (unsigned char)((a.y + b.y + c.y + d.y + 2) >> 2),
+                         (unsigned char)((a.z + b.z + c.z + d.z + 2) >> 2), 255);
 }
 
 // first / last covered row and column of alpha != 0 and the covered count of one view per workgroup
@@ -209,23 +307,15 @@ __global__ __launch_bounds__(256) void templates_crop_kernel(const uchar4* __res
 
 inline size_t per_view_bytes(int H, int W, int Nf) { return ((size_t)H * W + (size_t)Nf) * 8; }
 
-}  // namespace
-
-extern "C" {
-
-int pp_render_workspace_bytes(int H, int W, int n_faces, int chunk_views, size_t* bytes) {
-    if (!bytes || H <= 0 || W <= 0 || n_faces <= 0 || chunk_views <= 0 || (long long)H * W > INT_MAX) return PP_EINVAL;
-    *bytes = WS_HEADER + (size_t)chunk_views * per_view_bytes(H, W, n_faces);
-    return PP_OK;
-}
-
-int pp_render_views(const float* vertices, int n_vertices, const int* faces, const int* faces_host, int n_faces,
-                    const unsigned char* colors, const float* poses, int n_views, float fx, float fy, float cx, float cy, int H,
-                    int W, float near, void* workspace, size_t workspace_bytes, unsigned char* rgba, unsigned short* depth_mm,
-                    float* depth_m, int* face_id, unsigned int* near_count, void* stream) {
-    if (!vertices || !faces || !faces_host || !colors || !poses || !workspace || !rgba || !depth_mm || !near_count ||
-        n_vertices <= 0 || n_faces <= 0 || n_views <= 0 || H <= 0 || W <= 0 || (long long)H * W > INT_MAX || !(near > 0.f) ||
-        !(fx != 0.f) || !(fy != 0.f))
+// The argument checks and the chunk loop of pp_render_views and pp_render_views_textured: z-buffer fill, the two coverage launches,
+// then resolve(blocks, poses of the chunk, its views, cam, zbuf, first output sample) launches the entry's own resolve pass.
+template <class Resolve>
+int render_chunks(const float* vertices, int n_vertices, const int* faces, const int* faces_host, int n_faces, const float* poses,
+                  int n_views, float fx, float fy, float cx, float cy, int H, int W, float near, void* workspace,
+                  size_t workspace_bytes, unsigned char* rgba, unsigned short* depth_mm, float* depth_m, int* face_id,
+                  unsigned int* near_count, hipStream_t st, Resolve resolve) {
+    if (!vertices || !faces || !faces_host || !poses || !workspace || !rgba || !depth_mm || !near_count || n_vertices <= 0 ||
+        n_faces <= 0 || n_views <= 0 || H <= 0 || W <= 0 || (long long)H * W > INT_MAX || !(near > 0.f) || !(fx != 0.f) || !(fy != 0.f))
         return PP_EINVAL;
     if (((uintptr_t)rgba % 4) != 0) return PP_EINVAL;
     for (size_t k = 0; k < (size_t)n_faces * 3; ++k)
@@ -238,7 +328,6 @@ int pp_render_views(const float* vertices, int n_vertices, const int* faces, con
     chunk = chunk < by_faces ? chunk : by_faces;
     chunk = chunk < by_samples ? chunk : by_samples;
     if (chunk < 1) return PP_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
     unsigned* qcount = (unsigned*)workspace;
     unsigned long long* zbuf = (unsigned long long*)((char*)workspace + WS_HEADER);
     uint2* queue = (uint2*)(zbuf + (size_t)chunk * H * W);
@@ -255,14 +344,87 @@ int pp_render_views(const float* vertices, int n_vertices, const int* faces, con
         const unsigned gy = (unsigned)(work < 4096 ? work : 4096);
         hipLaunchKernelGGL(raster_large_kernel, dim3(8, gy), dim3(TILE * TILE), 0, st, vertices, faces, n_vertices,
                            poses + 16 * (size_t)v0, nv, n_faces, cam, zbuf, queue, qcount);
-        hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)(((long long)nv * hw + 255) / 256)), dim3(256), 0, st, vertices, faces,
-                           colors, n_vertices, n_faces, poses + 16 * (size_t)v0, nv, cam, zbuf, (uchar4*)rgba + (size_t)v0 * hw,
-                           depth_mm + (size_t)v0 * hw, depth_m ? depth_m + (size_t)v0 * hw : nullptr,
-                           face_id ? face_id + (size_t)v0 * hw : nullptr);
+        resolve((unsigned)(((long long)nv * hw + 255) / 256), poses + 16 * (size_t)v0, nv, cam, zbuf, (size_t)v0 * hw);
         const int rc = pp_last_launch();
         if (rc != PP_OK) return rc;
     }
     return PP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pp_render_workspace_bytes(int H, int W, int n_faces, int chunk_views, size_t* bytes) {
+    if (!bytes || H <= 0 || W <= 0 || n_faces <= 0 || chunk_views <= 0 || (long long)H * W > INT_MAX) return PP_EINVAL;
+    *bytes = WS_HEADER + (size_t)chunk_views * per_view_bytes(H, W, n_faces);
+    return PP_OK;
+}
+
+int pp_render_views(const float* vertices, int n_vertices, const int* faces, const int* faces_host, int n_faces,
+                    const unsigned char* colors, const float* poses, int n_views, float fx, float fy, float cx, float cy, int H,
+                    int W, float near, void* workspace, size_t workspace_bytes, unsigned char* rgba, unsigned short* depth_mm,
+                    float* depth_m, int* face_id, unsigned int* near_count, void* stream) {
+    if (!colors) return PP_EINVAL;
+    return render_chunks(vertices, n_vertices, faces, faces_host, n_faces, poses, n_views, fx, fy, cx, cy, H, W, near, workspace,
+                         workspace_bytes, rgba, depth_mm, depth_m, face_id, near_count, (hipStream_t)stream,
+                         [&](unsigned blocks, const float* p, int nv, const Cam& cam, const unsigned long long* zbuf, size_t o) {
+                             hipLaunchKernelGGL(resolve_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, vertices, faces, colors,
+                                                n_vertices, n_faces, p, nv, cam, zbuf, (uchar4*)rgba + o, depth_mm + o,
+                                                depth_m ? depth_m + o : nullptr, face_id ? face_id + o : nullptr);
+                         });
+}
+
+int pp_texture_mips_bytes(int Wt, int Ht, size_t* bytes, int* levels) {
+    if (!bytes || Wt < 1 || Ht < 1 || Wt > PP_TEXTURE_MAX || Ht > PP_TEXTURE_MAX) return PP_EINVAL;
+    size_t texels = (size_t)Wt * Ht;
+    int n = 1;
+    for (int w = Wt, h = Ht; w > 1 || h > 1; ++n) {
+        w = w > 1 ? w >> 1 : 1;
+        h = h > 1 ? h >> 1 : 1;
+        texels += (size_t)w * h;
+    }
+    *bytes = texels * 4;
+    if (levels) *levels = n;
+    return PP_OK;
+}
+
+int pp_texture_build_mips(const unsigned char* rgb, int Wt, int Ht, void* mips, size_t mips_bytes, void* stream) {
+    size_t need;
+    if (!rgb || !mips || pp_texture_mips_bytes(Wt, Ht, &need, nullptr) != PP_OK || ((uintptr_t)mips % 4) != 0 || mips_bytes < need)
+        return PP_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    uchar4* level = (uchar4*)mips;
+    const long long n0 = (long long)Wt * Ht;
+    hipLaunchKernelGGL(texture_pack_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, rgb, n0, level);
+    for (int w = Wt, h = Ht; w > 1 || h > 1;) {
+        const int wd = w > 1 ? w >> 1 : 1, hd = h > 1 ? h >> 1 : 1;
+        uchar4* next = level + (size_t)w * h;
+        hipLaunchKernelGGL(texture_down_kernel, dim3((unsigned)(((long long)wd * hd + 255) / 256)), dim3(256), 0, st, level, w, h, next,
+                           wd, hd);
+        level = next;
+        w = wd;
+        h = hd;
+    }
+    return pp_last_launch();
+}
+
+int pp_render_views_textured(const float* vertices, int n_vertices, const int* faces, const int* faces_host, int n_faces,
+                             const float* face_uv, const void* mips, int Wt, int Ht, const float* poses, int n_views, float fx,
+                             float fy, float cx, float cy, int H, int W, float near, void* workspace, size_t workspace_bytes,
+                             unsigned char* rgba, unsigned short* depth_mm, float* depth_m, int* face_id, unsigned int* near_count,
+                             void* stream) {
+    if (!face_uv || !mips || Wt < 1 || Ht < 1 || Wt > PP_TEXTURE_MAX || Ht > PP_TEXTURE_MAX || ((uintptr_t)face_uv % 4) != 0 ||
+        ((uintptr_t)mips % 4) != 0)
+        return PP_EINVAL;
+    const Textured tex{face_uv, (const uchar4*)mips, Wt, Ht};
+    return render_chunks(vertices, n_vertices, faces, faces_host, n_faces, poses, n_views, fx, fy, cx, cy, H, W, near, workspace,
+                         workspace_bytes, rgba, depth_mm, depth_m, face_id, near_count, (hipStream_t)stream,
+                         [&](unsigned blocks, const float* p, int nv, const Cam& cam, const unsigned long long* zbuf, size_t o) {
+                             hipLaunchKernelGGL(resolve_textured_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, vertices, faces,
+                                                tex, n_vertices, n_faces, p, nv, cam, zbuf, (uchar4*)rgba + o, depth_mm + o,
+                                                depth_m ? depth_m + o : nullptr, face_id ? face_id + o : nullptr);
+                         });
 }
 
 int pp_template_extents(const unsigned char* rgba, int n_views, int H, int W, int* extents, int* counts, void* stream) {

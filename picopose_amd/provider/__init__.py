@@ -1,4 +1,4 @@
 """Mirror of the reference's provider/: training-pair assembly on the device (training_batch), a test image's detection
 batch from its RLE records (test_batch) and an object's template bank from its mesh (template_bank)."""
-from .template_bank import (TEMPLATE_K, load_ply, mesh_diameter, onboard_objects, render_templates, render_views,  # noqa: F401
-                            template_object_poses, templates_from_frames)
+from .template_bank import (TEMPLATE_K, load_model, load_ply, load_texture, mesh_diameter, onboard_objects,  # noqa: F401
+                            render_templates, render_views, template_object_poses, templates_from_frames)

@@ -4,18 +4,26 @@ Replaces the reference's offline step rendering/scripts/render_bop_templates.py 
 (Panda3D inside MegaPose's image, 324 PNG files per object) followed by provider/bop_test_dataset.py:212-308 (`_get_template`,
 `get_templates`) and run_test.py:120-134 (the bank features):
 
-    mesh = load_ply(path)                                    # or {"vertices", "faces", "colors"} arrays of your own
+    mesh = load_model(path)                                  # PLY + the texture it names; or arrays of your own: {"vertices",
+                                                             # "faces"} + "colors" or "texture" with "uv" / "face_uv"
     bank = onboard_objects(net, [mesh, ...], view_poses)     # templates_data + template_feature
     pipeline.infer_image(net, data, bank, indexed_bank=True)
 
 The render recipe is the reference's: one ambient light of colour 1 (the pixel is the surface colour, unshaded), TEMPLATE_K at
 480 x 640, object pose = a view rotation with t = (0, 0, diameter), RGBA uint8 with alpha = 255 on the object, depth in whole
 millimetres.  The rasteriser's conventions (pixel centres at integer coordinates, 1/256 px snapping, top-left fill rule, no
-back-face culling, no near-plane clipping, vertex colours only) are stated in include/picopose_hip.h; parity with Panda3D's or
-BlenderProc's pixels is UNPINNED — neither renderer is available to compare against.  Texture maps are not read: a UV-textured
-model must be baked to vertex colours by the caller.  The package reads no fixture: `view_poses` is the caller's array (the
+back-face culling, no near-plane clipping) are stated in include/picopose_hip.h; parity with Panda3D's or BlenderProc's pixels
+is UNPINNED — neither renderer is available to compare against.
+
+A UV-textured model (BOP's `obj_NNNNNN.ply` with `texture_u texture_v` or a per-face `texcoord` list, and `comment TextureFile
+obj_NNNNNN.png`) is rendered from its texture, with no baking step: load_model reads the PLY and the image, a mip pyramid is built on
+the device once per render call, and the resolve pass samples it perspective-correctly — one mip level per (view, face) chosen by
+area, bilinear, wrap mode repeat, v = 0 at the bottom row (THE TEXTURE CONTRACT in include/picopose_hip.h, T1-T5).  Out of scope
+(T6): anisotropic and trilinear filtering, multisampled edges (the reference enables 4x MSAA), clamp / mirror wrap, texture alpha,
+several textures per mesh, shading.  The package reads no fixture: `view_poses` is the caller's array (the
 reference's is rendering/src/lib3d/predefined_poses/obj_poses_level1.npy, 162 views)."""
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -30,19 +38,25 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
 
 
 def load_ply(path):
-    """A BOP model file -> {"vertices" (Nv,3) f32, "faces" (Nf,3) i32, "colors" (Nv,3) u8 or None}.  ASCII and
-    binary_little_endian PLY; element `vertex` with x y z (nx ny nz, red green blue [alpha], texture_u / texture_v and any other
-    scalar property are skipped or, for the colours, returned), element `face` with a `vertex_indices` / `vertex_index` list.
-    ValueError: not a PLY file, big-endian, a missing element or property, a face that is not a triangle, a truncated body."""
+    """A BOP model file -> {"vertices" (Nv,3) f32, "faces" (Nf,3) i32, "colors" (Nv,3) u8 or None, "uv" (Nv,2) f32 or None,
+    "face_uv" (Nf,3,2) f32 or None, "texture_file" str or None}.  ASCII and binary_little_endian PLY; element `vertex` with x y z
+    (red green blue and texture_u texture_v / s t / u v are returned; nx ny nz, alpha and any other scalar property are skipped),
+    element `face` with a `vertex_indices` / `vertex_index` list, optionally a `texcoord` list of 6 floats (u v per corner: MeshLab's
+    wedge UVs) and scalar properties such as `texnumber`, which are skipped.  "texture_file" is the NAME in `comment TextureFile
+    NAME`, as written (load_model resolves and reads it).
+    ValueError: not a PLY file, big-endian, a missing element or property, a face that is not a triangle or whose texcoord list
+    does not hold 6 values (named), a truncated body."""
     with open(path, "rb") as fh:
         raw = fh.read()
     end = raw.find(b"end_header")
     if not raw.startswith(b"ply") or end < 0:
         raise ValueError(f"{path}: not a PLY file (no 'ply' magic / 'end_header')")
     body = raw.find(b"\n", end) + 1
-    fmt, elements = None, []
+    fmt, elements, texture_file = None, [], None
     for line in raw[:end].decode("ascii", "replace").splitlines()[1:]:
         tok = line.split()
+        if len(tok) >= 3 and tok[0] == "comment" and tok[1] == "TextureFile" and texture_file is None:
+            texture_file = line.split(None, 2)[2].strip()
         if not tok or tok[0] in ("comment", "obj_info"):
             continue
         if tok[0] == "format":
@@ -68,7 +82,7 @@ def load_ply(path):
     for need in ("vertex", "face"):
         if need not in names:
             raise ValueError(f"{path}: no '{need}' element")
-    out = {}
+    out = {"uv": None, "face_uv": None, "texture_file": texture_file}
     tokens, pos = (raw[body:].split(), 0) if fmt == "ascii" else (None, body)
     for name, count, props in elements:
         lists = [p for p in props if isinstance(p[1], tuple)]
@@ -95,26 +109,44 @@ def load_ply(path):
             out["vertices"] = np.ascontiguousarray(np.stack([col["x"], col["y"], col["z"]], axis=1).astype(np.float32))
             out["colors"] = (np.ascontiguousarray(np.stack([col["red"], col["green"], col["blue"]], axis=1).astype(np.uint8))
                              if all(c in col for c in ("red", "green", "blue")) else None)
+            for un, vn in (("texture_u", "texture_v"), ("s", "t"), ("u", "v")):
+                if un in col and vn in col:
+                    out["uv"] = np.ascontiguousarray(np.stack([col[un], col[vn]], axis=1).astype(np.float32))
+                    break
         elif name == "face":
-            if len(props) != 1 or not lists or props[0][0] not in ("vertex_indices", "vertex_index"):
-                raise ValueError(f"{path}: face element must hold one 'vertex_indices' / 'vertex_index' list")
-            ct, it = props[0][1]
+            want = {p[0]: 6 if p[0] == "texcoord" else 3 for p in lists}
+            index = [n for n in want if n in ("vertex_indices", "vertex_index")]
+            if len(index) != 1 or len(want) != len(lists) or set(want) - {index[0], "texcoord"}:
+                raise ValueError(f"{path}: face element must hold one 'vertex_indices' / 'vertex_index' list (besides it only a "
+                                 "'texcoord' list and scalar properties are read past)")
+            # every row has the same layout when each list has the length it should: read the table in one piece, and walk the
+            # rows one by one only to name the first that differs
             if fmt == "ascii":
-                if pos + 4 * count > len(tokens):
-                    raise ValueError(f"{path}: truncated face data (or a face that is not a triangle)")
-                tab = np.array(tokens[pos:pos + 4 * count], dtype=np.int64).reshape(count, 4)
-                pos += 4 * count
-                n, idx = tab[:, 0], tab[:, 1:]
+                width = sum(1 + want[n] if isinstance(t, tuple) else 1 for n, t in props)
+                fits = pos + count * width <= len(tokens)
+                if fits:
+                    tab = np.array(tokens[pos:pos + count * width], dtype=np.float64).reshape(count, width)
+                    col, o = {}, 0
+                    for n, t in props:
+                        if isinstance(t, tuple):
+                            col[n] = (tab[:, o], tab[:, o + 1:o + 1 + want[n]])
+                            o += want[n]
+                        o += 1
+                size = count * width
             else:
-                dt = np.dtype([("n", "<" + ct), ("i", "<" + it, (3,))])
-                if pos + count * dt.itemsize > len(raw):
-                    raise ValueError(f"{path}: truncated face data (or a face that is not a triangle)")
-                tab = np.frombuffer(raw, dtype=dt, count=count, offset=pos)
-                pos += count * dt.itemsize
-                n, idx = tab["n"], tab["i"]
-            if np.any(n != 3):
-                raise ValueError(f"{path}: face {int(np.argmax(n != 3))} is not a triangle ({int(n[np.argmax(n != 3)])} vertices)")
-            out["faces"] = np.ascontiguousarray(idx.astype(np.int32))
+                dt = np.dtype([f for n, t in props for f in ([(n + "#", "<" + t[0]), (n, "<" + t[1], (want[n],))]
+                                                             if isinstance(t, tuple) else [(n, "<" + t)])])
+                fits = pos + count * dt.itemsize <= len(raw)
+                if fits:
+                    tab = np.frombuffer(raw, dtype=dt, count=count, offset=pos)
+                    col = {n: (tab[n + "#"], tab[n]) for n in want}
+                size = count * dt.itemsize
+            if not fits or any(np.any(col[n][0] != want[n]) for n in want):
+                _raise_on_face_rows(path, fmt, tokens if fmt == "ascii" else raw, pos, count, props, want)
+            pos += size
+            out["faces"] = np.ascontiguousarray(col[index[0]][1].astype(np.int32))
+            if "texcoord" in want:
+                out["face_uv"] = np.ascontiguousarray(col["texcoord"][1].astype(np.float32).reshape(count, 3, 2))
         else:                                                   # another element: skipped (fixed-size properties only)
             if lists:
                 raise ValueError(f"{path}: cannot skip element '{name}' with a list property")
@@ -123,6 +155,59 @@ def load_ply(path):
             else:
                 pos += count * np.dtype([(n_, "<" + t) for n_, t in props]).itemsize
     return out
+
+
+def _raise_on_face_rows(path, fmt, data, pos, count, props, want):
+    """Walk the face rows one by one and name the first whose list has another length than want[name], or the truncation."""
+    def take(t):                                                 # the next scalar of PLY type t, None past the end
+        nonlocal pos
+        if fmt == "ascii":
+            val = float(data[pos]) if pos < len(data) else None
+            pos += 1
+        else:
+            dt = np.dtype("<" + t)
+            val = np.frombuffer(data, dtype=dt, count=1, offset=pos)[0] if pos + dt.itemsize <= len(data) else None
+            pos += dt.itemsize
+        return val
+
+    for row in range(count):
+        for name, t in props:
+            n = take(t[0] if isinstance(t, tuple) else t)
+            if n is None:
+                raise ValueError(f"{path}: truncated face data (or a face that is not a triangle)")
+            if isinstance(t, tuple):
+                if int(n) != want[name]:
+                    raise ValueError(f"{path}: face {row} holds a texcoord list of {int(n)} values (6 expected: u v per corner)"
+                                     if name == "texcoord" else f"{path}: face {row} is not a triangle ({int(n)} vertices)")
+                for _ in range(want[name]):
+                    take(t[1])
+    raise ValueError(f"{path}: truncated face data (or a face that is not a triangle)")
+
+
+def load_texture(path):
+    """An image file -> (Ht, Wt, 3) uint8 RGB, row 0 the top row (PIL, `convert("RGB")`: alpha is dropped, a palette resolved)."""
+    from PIL import Image
+
+    with Image.open(path) as im:
+        return np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8))
+
+
+def load_model(ply_path, texture=None):
+    """load_ply plus the model's texture under "texture": `texture` (a path or an (Ht, Wt, 3) uint8 array) when given, else the
+    file that `comment TextureFile NAME` names, looked up next to the PLY.  A model without UVs or without a texture comes back as
+    load_ply gives it.  ValueError: the named texture file does not exist (it says which)."""
+    mesh = load_ply(ply_path)
+    if texture is None and mesh["texture_file"] is not None and (mesh["uv"] is not None or mesh["face_uv"] is not None):
+        texture = os.path.join(os.path.dirname(os.path.abspath(ply_path)), mesh["texture_file"])
+        if not os.path.isfile(texture):
+            raise ValueError(f"{ply_path}: its texture file {texture} (comment TextureFile {mesh['texture_file']}) does not exist")
+    if isinstance(texture, (str, bytes)) or hasattr(texture, "__fspath__"):
+        if not os.path.isfile(texture):
+            raise ValueError(f"texture file {texture} does not exist")
+        texture = load_texture(texture)
+    if texture is not None:
+        mesh["texture"] = texture
+    return mesh
 
 
 def mesh_diameter(vertices):
@@ -159,6 +244,45 @@ def _mesh_arrays(mesh):
     return (np.ascontiguousarray(v, dtype=np.float32), np.ascontiguousarray(f, dtype=np.int32), np.ascontiguousarray(c))
 
 
+def _mesh_texture(mesh, n_vertices, f):
+    """The texture (Ht, Wt, 3) uint8 and the per-corner UVs (Nf, 3, 2) f32 of a textured mesh dict, or None when it holds no
+    texture.  "face_uv" wins over "uv", which is expanded to corners here (the only device layout)."""
+    tex = mesh.get("texture")
+    if tex is None:
+        return None
+    tex = np.asarray(tex)
+    if tex.ndim != 3 or tex.shape[2] != 3 or tex.dtype != np.uint8 or not (1 <= tex.shape[0] <= 16384 and 1 <= tex.shape[1] <= 16384):
+        raise ValueError(f"texture must be (Ht, Wt, 3) uint8 with 1 <= Ht, Wt <= 16384, got {tex.dtype} {tex.shape}")
+    if mesh.get("face_uv") is not None:
+        uv = np.asarray(mesh["face_uv"])
+        if uv.shape != (len(f), 3, 2) or not np.issubdtype(uv.dtype, np.floating):
+            raise ValueError(f"face_uv must be a (Nf, 3, 2) float array, got {uv.dtype} {uv.shape}")
+    elif mesh.get("uv") is not None:
+        uv = np.asarray(mesh["uv"])
+        if uv.shape != (n_vertices, 2) or not np.issubdtype(uv.dtype, np.floating):
+            raise ValueError(f"uv must be a (Nv, 2) float array, got {uv.dtype} {uv.shape}")
+        uv = uv[f]
+    else:
+        raise ValueError("a mesh with a texture needs 'face_uv' (Nf, 3, 2) or 'uv' (Nv, 2)")
+    if not np.all(np.isfinite(uv)):
+        raise ValueError("the UVs contain a non-finite value")
+    return np.ascontiguousarray(tex), np.ascontiguousarray(uv, dtype=np.float32)
+
+
+def texture_mips(image):
+    """The mip pyramid of an (Ht, Wt, 3) uint8 device tensor, built on the device (T2 of the texture contract): a flat uint8 tensor
+    of uchar4 texels, level 0 first, as pp_render_views_textured reads it."""
+    if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3 or not image.is_cuda:
+        raise ValueError(f"image must be an (Ht, Wt, 3) uint8 device tensor, got {image.dtype} {tuple(image.shape)} on {image.device}")
+    image, L = image.contiguous(), _lib.lib()
+    Ht, Wt = image.shape[:2]
+    need = ctypes.c_size_t()
+    _lib.check(L.pp_texture_mips_bytes(Wt, Ht, ctypes.byref(need), None), "pp_texture_mips_bytes")
+    mips = torch.empty(need.value, dtype=torch.uint8, device=image.device)
+    _lib.check(L.pp_texture_build_mips(image.data_ptr(), Wt, Ht, mips.data_ptr(), mips.numel(), _lib.stream_ptr()), "pp_texture_build_mips")
+    return mips
+
+
 def _unit_scale(units, vertices):
     if units == "auto":                                          # call_panda3d.py:39-40
         units = "m" if mesh_diameter(vertices) < 10 else "mm"
@@ -169,15 +293,18 @@ def _unit_scale(units, vertices):
 
 def render_views(mesh, poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", near=1e-3, return_depth_m=False, return_face_id=False,
                  workspace_bytes=DEFAULT_WORKSPACE_BYTES, check_near=True, device="cuda"):
-    """Render `mesh` ({"vertices", "faces", "colors" or None}) under the object -> camera poses (V,4,4) whose translation is in
+    """Render `mesh` ({"vertices", "faces", "colors" or None}, or with "texture" (Ht,Wt,3) uint8 and "face_uv" (Nf,3,2) or "uv"
+    (Nv,2): the textured path, which wins over "colors") under the object -> camera poses (V,4,4) whose translation is in
     the mesh's `units` ("mm" as BOP models are, "m", or "auto": the reference's rule, diameter < 10 -> metres).  The kernels work
     in metres: vertices and translations are scaled by 1e-3 in float64 for "mm" and rounded to float32 once.
     -> {"rgba" (V,H,W,4) uint8, "depth_mm" (V,H,W) uint16 [, "depth_m" (V,H,W) f32, "face_id" (V,H,W) int32], "near_count"
-    (1,) int32 device tensor}.  A mesh without colours renders mid-grey (128, 128, 128).  `workspace_bytes` bounds the
+    (1,) int32 device tensor}.  A mesh without colours and without a texture renders mid-grey (128, 128, 128).  A texture's mip
+    pyramid is built on the device once per call, before the views are rendered.  `workspace_bytes` bounds the
     rasteriser's workspace; the views are rendered in as many chunks as that takes (at least one view's worth is allocated).
     check_near: synchronise and raise ValueError when a triangle was dropped at the near plane (`near` metres); False leaves the
     count on the device for the caller."""
     v, f, c = _mesh_arrays(mesh)
+    tex = _mesh_texture(mesh, len(v), f)
     scale = _unit_scale(units, v)
     poses = np.array(poses, dtype=np.float64)
     if poses.ndim != 3 or poses.shape[1:] != (4, 4) or len(poses) == 0 or not np.all(np.isfinite(poses)):
@@ -201,12 +328,18 @@ def render_views(mesh, poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", n
         out["depth_m"] = torch.empty(V, H, W, dtype=torch.float32, device=device)
     if return_face_id:
         out["face_id"] = torch.empty(V, H, W, dtype=torch.int32, device=device)
-    _lib.check(L.pp_render_views(v_d.data_ptr(), len(v), f_d.data_ptr(), f.ctypes.data, len(f), c_d.data_ptr(), p_d.data_ptr(), V,
-                                 float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), H, W, float(near), ws.data_ptr(),
-                                 ws.numel(), out["rgba"].data_ptr(), out["depth_mm"].data_ptr(),
-                                 out["depth_m"].data_ptr() if return_depth_m else None,
-                                 out["face_id"].data_ptr() if return_face_id else None, out["near_count"].data_ptr(),
-                                 _lib.stream_ptr()), "pp_render_views")
+    tail = (p_d.data_ptr(), V, float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), H, W, float(near), ws.data_ptr(), ws.numel(),
+            out["rgba"].data_ptr(), out["depth_mm"].data_ptr(), out["depth_m"].data_ptr() if return_depth_m else None,
+            out["face_id"].data_ptr() if return_face_id else None, out["near_count"].data_ptr(), _lib.stream_ptr())
+    if tex is None:
+        _lib.check(L.pp_render_views(v_d.data_ptr(), len(v), f_d.data_ptr(), f.ctypes.data, len(f), c_d.data_ptr(), *tail), "pp_render_views")
+    else:
+        image, face_uv = tex
+        Ht, Wt = image.shape[:2]
+        mips = texture_mips(torch.from_numpy(image).to(device))           # once per call: the chunk loop is inside the entry
+        uv_d = torch.from_numpy(face_uv).to(device)
+        _lib.check(L.pp_render_views_textured(v_d.data_ptr(), len(v), f_d.data_ptr(), f.ctypes.data, len(f), uv_d.data_ptr(),
+                                              mips.data_ptr(), Wt, Ht, *tail), "pp_render_views_textured")
     if check_near:
         _raise_on_near(int(out["near_count"].item()), near)
     return out

@@ -6,7 +6,10 @@
     for the same job: a loop of utils.preprocess.crop_template over the same 162 frames held as numpy arrays — same process,
     median of --reps after --warmup, synchronised at the ends only;
   * --onboard VIT: onboard_objects for one object split into render / crop / bank features (extended bank with --extended);
-  * --profile: one render_templates per mesh and nothing else, for `rocprofv3 --kernel-trace --stats -- python tools/bench_template_bank.py --profile`.
+  * --profile: one render_templates per mesh and nothing else, for `rocprofv3 --kernel-trace --stats -- python tools/bench_template_bank.py --profile`;
+  * --textured WtxHt: the 20 k-triangle icosphere with per-vertex UVs and a generated Wt x Ht texture instead of the three meshes:
+    render_templates and render_views for the vertex-colour and the textured path alternately, and the mip pyramid build alone (HIP
+    events on the stream); with --profile one textured render_templates and nothing else.
 
 Prints one JSON line per measurement."""
 import argparse
@@ -56,6 +59,33 @@ def events(fn, reps, warmup):
     return statistics.median(out)
 
 
+def textured(a, views):
+    Wt, Ht = (int(x) for x in a.textured.lower().split("x"))
+    m = ro.icosphere(5, 50.0)
+    d = m["vertices"].astype(np.float64) / 50.0
+    uv = np.stack([np.arctan2(d[:, 1], d[:, 0]) / (2 * np.pi) + 0.5, np.arccos(np.clip(d[:, 2], -1, 1)) / np.pi], axis=1).astype(np.float32)
+    tex = np.random.default_rng(0).integers(0, 256, (Ht, Wt, 3)).astype(np.uint8)
+    tm = {"vertices": m["vertices"], "faces": m["faces"], "uv": uv, "texture": tex}
+    if a.profile:
+        tb.render_templates(tm, views)
+        torch.cuda.synchronize()
+        return
+    poses = tb.template_object_poses(views, m["vertices"])
+    tex_d = torch.from_numpy(tex).cuda()
+    for rep in range(2):                                        # the two paths alternately, twice: the spread between the passes is printed
+        for name, mesh in (("vertex_colour", m), ("textured", tm)):
+            print(json.dumps({"what": "render_templates", "path": name, "pass": rep, "mesh": "icosphere_20480", "views": 162,
+                              "texture": a.textured if mesh is tm else None,
+                              "host_ms": round(timed(lambda: tb.render_templates(mesh, views), a.reps, a.warmup), 3),
+                              "render_views_event_ms": round(events(lambda: tb.render_views(mesh, poses, check_near=False), a.reps, a.warmup), 3)}),
+                  flush=True)
+    print(json.dumps({"what": "texture_mips alone", "texture": a.textured, "bytes": int(tb.texture_mips(tex_d).numel()),
+                      "event_ms": round(events(lambda: tb.texture_mips(tex_d), a.reps, a.warmup), 4)}), flush=True)
+    r = tb.render_views(tm, poses, return_face_id=True)
+    print(json.dumps({"what": "covered samples", "views": 162, "covered": int((r["face_id"] >= 0).sum().item()),
+                      "samples": int(r["face_id"].numel())}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -64,8 +94,11 @@ def main():
     ap.add_argument("--onboard", default=None, help="dinov2_vits14 | dinov2_vitb14 | dinov2_vitl14")
     ap.add_argument("--extended", action="store_true")
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--textured", default=None, metavar="WtxHt", help="texture size, e.g. 2048x2048")
     a = ap.parse_args()
     views = np.load(os.path.join(ROOT, "tests", "golden", "template_view_poses_level1.npy"))
+    if a.textured:
+        return textured(a, views)
     meshes = {"cube_12": ro.cube(40.0), "icosphere_20480": ro.icosphere(5, 50.0)}
     big = ro.icosphere(a.big, 50.0)
     meshes[f"icosphere_{len(big['faces'])}"] = big
