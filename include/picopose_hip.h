@@ -889,7 +889,8 @@ int pp_render_views(const float* vertices, int n_vertices, const int* faces, con
  *      texels inside the level and gives an unspecified colour, never a fault.
  *  T6. OUT OF SCOPE: anisotropic filtering and trilinear blending between levels (one level per face, chosen by area); multisampled
  *      edges (the reference enables 4x MSAA; silhouettes here are single-sampled as in item 5); clamp and mirror wrap modes;
- *      texture alpha (a texel's alpha is ignored: convert to RGB first); more than one texture per mesh; shading.  Parity with
+ *      texture alpha (a texel's alpha is ignored: convert to RGB first); more than one texture per mesh.  (Shading is THE SHADING
+ *      CONTRACT below; what it leaves out is S9.)  Parity with
  *      Panda3D's pixels stays UNPINNED, as for the rest of the render.
  *
  * pp_texture_mips_bytes: *bytes = 4 * the texels of all levels, *levels (may be NULL) = their number.  PP_EINVAL: bytes NULL, Wt or
@@ -909,6 +910,70 @@ int pp_render_views_textured(const float* vertices, int n_vertices, const int* f
                              float fy, float cx, float cy, int H, int W, float near, void* workspace, size_t workspace_bytes,
                              unsigned char* rgba, unsigned short* depth_mm, float* depth_m, int* face_id, unsigned int* near_count,
                              void* stream);
+/* -------------------------------------------------------------------------
+ * THE SHADING CONTRACT: the same render, lit.  The reference renders T-LESS and ITODD from their untextured CAD meshes with
+ * BlenderProc under eight point lights (rendering/scripts/render_bop_templates.py:131, rendering/src/lib3d/blenderproc.py:29-39,
+ * :54-57); unlit, such a mesh is a flat silhouette.  pp_render_views_lit multiplies the base colour of a covered sample by
+ * ambient + Lambert diffuse.  tests/shading_oracle.py restates S2-S8 in numpy; the kernels equal it bit for bit.  Float operations
+ * are IEEE float32, one rounding each, never contracted, in the order written; only `/` and sqrtf (both correctly rounded) are
+ * used besides + - *: no reciprocal square root, no fast intrinsic, no powf.
+ *  S1. Inputs.  n_lights in [0, PP_MAX_LIGHTS]; light k is (x, y, z, I_k) float32 in camera space (the frame of item 1: x right,
+ *      y down, z forward) in the vertices' unit, finite, I_k >= 0.  ambient >= 0.  Base colour of a covered sample: the uchar4
+ *      the UNLIT render writes there (vertex colours by item 6, or the texture by T3-T5), or a constant RGB triple when one is
+ *      given (a constant overrides both).  Normal mode flat or smooth.  Optional tone table: T uint8 entries on the device,
+ *      2 <= T <= PP_TONE_MAX.
+ *  S2. Position P = ((p0 C0 + p1 C1) + p2 C2) / q per coordinate: C_k the camera-space corners of item 1 in the order item 4
+ *      left them, p_k and q of item 6.
+ *  S3. Normal.  Flat: e1 = C1 - C0, e2 = C2 - C0, n = e1 x e2 with every component formed as (a b) - (c d):
+ *        nx = (e1y e2z) - (e1z e2y), ny = (e1z e2x) - (e1x e2z), nz = (e1x e2y) - (e1y e2x).
+ *      Exchanging corners 1 and 2 negates n exactly, so the result after the facing step does not depend on the winding.
+ *      Smooth: o = (p0 N0 + p1 N1) + p2 N2 per component, N_k the object-space vertex normals (S8, or the model's own) of those
+ *      corners; rotated by the pose's 3 x 3 block, assumed orthonormal: nx = ((P00 ox + P01 oy) + P02 oz), ny and nz from rows 1, 2.
+ *      Both: len2 = (nx nx + ny ny) + nz nz.  When len2 > 0 is false the sample gets s = 0 (ambient only).  Otherwise
+ *      n = n / sqrtf(len2) per component, then facing (two-sided, matching "no back-face culling"): when
+ *      ((nx Px + ny Py) + nz Pz) > 0, n = -n.
+ *  S4. Lights in index order, s starting at 0: L = L_k - P; d2 = (Lx Lx + Ly Ly) + Lz Lz; ndl = (nx Lx + ny Ly) + nz Lz;
+ *      when ndl > 0 and d2 > 0: s = s + (I_k ndl) / (d2 sqrtf(d2)).  (Inverse-square fall-off times the cosine.)
+ *  S5. m = ambient + s.  Per channel val = (float) base_c * m.
+ *  S6. Output.  Without a table: out = min(255, max(0, floorf(val + 0.5))).  With a table: idx = (int) rintf(fminf(val / 255, 1) * (float)(T - 1))
+ *      (round half to even), clamped to [0, T - 1] (a no-op for the inputs of S1), out = table[idx].  Alpha = 255.
+ *  S7. Coverage, depth, depth_mm, depth_m, face_id and alpha are items 1-5, 7 and 8, unchanged: shading moves colour only.
+ *  S8. Vertex normals (pp_vertex_normals, once per mesh).  For vertex v: the sum, over the entries vf_faces[vf_offsets[v] ..
+ *      vf_offsets[v + 1]) in that order, of the object-space (V1 - V0) x (V2 - V0) of the face (area-weighted, un-normalised,
+ *      the face's own corner order, components as in S3), every component accumulated sequentially in float32 from 0; then
+ *      normalised as in S3 (zeros when len2 > 0 is false: an unreferenced vertex, or faces without area).  The adjacency is a
+ *      CSR pair built on the host: a stable sort of faces.reshape(-1) by vertex, so a vertex's faces come in ascending face
+ *      index (a face that names v twice is listed twice and adds zero).  No float atomics: the bytes do not depend on launch order.
+ *  S9. OUT OF SCOPE: specular terms, shadows, coloured or spot lights, decoding base colours from sRGB, angle-threshold "auto
+ *      smooth", MSAA.  Parity with Cycles / pyrender pixels stays UNPINNED, as for the rest of the render.
+ *
+ * pp_vertex_normals: vertices (Nv, 3) fp32, faces (Nf, 3) int32, vf_offsets (Nv + 1) int32, vf_faces (3 Nf) int32, normals (Nv, 3)
+ * fp32 out: device.  One launch on `stream`, nothing synchronises.  An entry of the lists that is out of range is skipped, never a
+ * fault.  PP_EINVAL: null or misaligned (4 B) pointer, Nv or Nf <= 0, 3 Nf >= 2^31.
+ * pp_render_views_lit: the arguments of pp_render_views and pp_render_views_textured together, then the shading.  Colour source:
+ * `colors`, or face_uv + mips (+ Wt, Ht), or neither (NULL, NULL, NULL, 0, 0) with base_color_host.  lights_host: n_lights x 4 floats
+ * on the HOST, copied into the kernel arguments; base_color_host: 3 bytes on the HOST or NULL; normals (Nv, 3) fp32 on the device
+ * (needed for PP_NORMALS_SMOOTH only); tone_table: tone_entries bytes on the device, or NULL with tone_entries = 0.  The coverage
+ * launches, the workspace (pp_render_workspace_bytes), chunking and everything pp_render_views rejects are unchanged; all work is
+ * enqueued on `stream`, nothing synchronises.  Also PP_EINVAL, before any launch: n_lights outside [0, PP_MAX_LIGHTS] or lights_host
+ * NULL with n_lights > 0; a light that is not finite or has I < 0; ambient negative or not finite; normal_mode not one of the two;
+ * smooth without normals; no colour source (and no constant); both colour sources; face_uv without mips or the reverse; Wt / Ht out
+ * of range with a texture; tone_entries outside [2, PP_TONE_MAX] with a table, or != 0 without; lights_host, normals, face_uv or mips
+ * not 4-byte aligned.
+ * ------------------------------------------------------------------------- */
+#define PP_MAX_LIGHTS 16
+#define PP_TONE_MAX 65536
+#define PP_NORMALS_FLAT 0
+#define PP_NORMALS_SMOOTH 1
+int pp_vertex_normals(const float* vertices, int n_vertices, const int* faces, int n_faces, const int* vf_offsets, const int* vf_faces,
+                      float* normals, void* stream);
+int pp_render_views_lit(const float* vertices, int n_vertices, const int* faces, const int* faces_host, int n_faces,
+                        const unsigned char* colors, const float* face_uv, const void* mips, int Wt, int Ht, const float* poses,
+                        int n_views, float fx, float fy, float cx, float cy, int H, int W, float near, void* workspace,
+                        size_t workspace_bytes, unsigned char* rgba, unsigned short* depth_mm, float* depth_m, int* face_id,
+                        unsigned int* near_count, const float* lights_host, int n_lights, float ambient, int normal_mode,
+                        const float* normals, const unsigned char* base_color_host, const unsigned char* tone_table, int tone_entries,
+                        void* stream);
 /* Per view the first / last row and column with alpha != 0 — the np.any / np.where of get_bbox (utils/data_utils.py:131-137) on
  * rgba[..., 3]: extents (V, 4) int32 = {rmin, rmax, cmin, cmax} (inclusive; -1 each for a view that covers nothing);
  * counts (V) int32 covered samples, may be NULL. */

@@ -220,6 +220,9 @@ def lib():
         L.pp_texture_build_mips.argtypes = [vp, i32, i32, vp, sz, vp]
         L.pp_render_views_textured.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, i32, vp, i32, f32, f32, f32, f32, i32, i32, f32, vp, sz,
                                                vp, vp, vp, vp, vp, vp]
+        L.pp_vertex_normals.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp]
+        L.pp_render_views_lit.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, f32, f32, f32, f32, i32, i32, f32, vp, sz,
+                                          vp, vp, vp, vp, vp, vp, i32, f32, i32, vp, vp, vp, i32, vp]
         L.pp_template_extents.argtypes = [vp, i32, i32, i32, vp, vp, vp]
         L.pp_templates_crop.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, f32, f32, f32, f32, i32, i32, i32,
                                         c.POINTER(c.c_double), c.POINTER(c.c_double), vp, vp, vp, vp]

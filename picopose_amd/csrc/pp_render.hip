@@ -16,6 +16,13 @@
 // A UV-textured mesh (pp_render_views_textured) shares the coverage launches; only the colour of the resolve pass differs: THE
 // TEXTURE CONTRACT of include/picopose_hip.h (T1-T5), restated by tests/texture_oracle.py.  The mip pyramid is built once per
 // texture by pp_texture_build_mips, one launch per level, in integer arithmetic.
+//
+// A lit render (pp_render_views_lit) again shares the coverage launches.  Its resolve pass wraps the sample's colour functor
+// (vertex colours, texture, or a constant) in Lit, which multiplies that base colour by ambient + Lambert diffuse of up to
+// PP_MAX_LIGHTS point lights: THE SHADING CONTRACT of include/picopose_hip.h (S1-S7), restated by tests/shading_oracle.py.  The
+// lights travel by value in the kernel arguments; pp_vertex_normals (S8) makes the smooth normals once per mesh, without float
+// atomics.
+#include <math.h>
 #include <stdint.h>
 #include <limits.h>
 #include "pp_common.h"
@@ -139,6 +146,92 @@ struct Textured {
     }
 };
 
+// S1's constant base colour
+struct ConstantColour {
+    uchar4 c;
+    __device__ __forceinline__ uchar4 operator()(const Tri&, int, const float*, float) const { return c; }
+};
+
+// S1 by value in the kernel arguments: the lights are wave-uniform scalar loads and the light loop has a uniform trip count
+struct Shading {
+    float lights[PP_MAX_LIGHTS][4];         // x, y, z (camera space), intensity
+    int n_lights;
+    float ambient;
+    int smooth;
+    const float* normals;                   // (Nv, 3) object space: smooth mode only
+    const unsigned char* tone;              // T entries, or null
+    int T;
+};
+
+// S2-S6 around the base colour of `base`.  The camera-space corners are recomputed from the vertices with item 1's expressions
+// (the same bits tri_setup had before it projected them) instead of being kept in Tri for every kernel that sets a triangle up.
+template <class Colour>
+struct Lit {
+    Colour base;
+    const Shading& sh;
+    const float* __restrict__ verts;
+    const float* __restrict__ P;            // the view's pose
+    __device__ __forceinline__ uchar4 operator()(const Tri& t, int face, const float p[3], float q) const {
+        const uchar4 b = base(t, face, p, q);
+        float C[3][3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float X = verts[3 * (size_t)t.id[k]], Y = verts[3 * (size_t)t.id[k] + 1], Z = verts[3 * (size_t)t.id[k] + 2];
+            C[k][0] = ((P[0] * X + P[1] * Y) + P[2] * Z) + P[3];
+            C[k][1] = ((P[4] * X + P[5] * Y) + P[6] * Z) + P[7];
+            C[k][2] = ((P[8] * X + P[9] * Y) + P[10] * Z) + P[11];
+        }
+        float pos[3], n[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) pos[c] = ((p[0] * C[0][c] + p[1] * C[1][c]) + p[2] * C[2][c]) / q;       // S2
+        if (sh.smooth) {                                                                                     // S3
+            float o[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                o[c] = (p[0] * sh.normals[3 * (size_t)t.id[0] + c] + p[1] * sh.normals[3 * (size_t)t.id[1] + c]) +
+                       p[2] * sh.normals[3 * (size_t)t.id[2] + c];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) n[c] = (P[4 * c] * o[0] + P[4 * c + 1] * o[1]) + P[4 * c + 2] * o[2];
+        } else {
+            const float e1[3] = {C[1][0] - C[0][0], C[1][1] - C[0][1], C[1][2] - C[0][2]};
+            const float e2[3] = {C[2][0] - C[0][0], C[2][1] - C[0][1], C[2][2] - C[0][2]};
+            n[0] = (e1[1] * e2[2]) - (e1[2] * e2[1]);
+            n[1] = (e1[2] * e2[0]) - (e1[0] * e2[2]);
+            n[2] = (e1[0] * e2[1]) - (e1[1] * e2[0]);
+        }
+        const float len2 = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
+        float s = 0.f;
+        if (len2 > 0.f) {
+            const float len = sqrtf(len2);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) n[c] = n[c] / len;
+            if (((n[0] * pos[0] + n[1] * pos[1]) + n[2] * pos[2]) > 0.f) {                                   // two-sided
+#pragma unroll
+                for (int c = 0; c < 3; ++c) n[c] = -n[c];
+            }
+            for (int k = 0; k < sh.n_lights; ++k) {                                                          // S4
+                const float lx = sh.lights[k][0] - pos[0], ly = sh.lights[k][1] - pos[1], lz = sh.lights[k][2] - pos[2];
+                const float d2 = (lx * lx + ly * ly) + lz * lz;
+                const float ndl = (n[0] * lx + n[1] * ly) + n[2] * lz;
+                if (ndl > 0.f && d2 > 0.f) s = s + (sh.lights[k][3] * ndl) / (d2 * sqrtf(d2));
+            }
+        }
+        const float m = sh.ambient + s;                                                                      // S5
+        const float val[3] = {(float)b.x * m, (float)b.y * m, (float)b.z * m};
+        unsigned char out[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {                                                                        // S6
+            if (sh.tone) {
+                const int idx = (int)rintf(fminf(val[c] / 255.f, 1.f) * (float)(sh.T - 1));
+                out[c] = sh.tone[min(max(idx, 0), sh.T - 1)];
+            } else {
+                out[c] = (unsigned char)fminf(fmaxf(floorf(val[c] + 0.5f), 0.f), 255.f);
+            }
+        }
+        return make_uchar4(out[0], out[1], out[2], 255);
+    }
+};
+
 // items 6-8 for sample i of the chunk: the winning face is set up again and its colour comes from `colour`
 template <class Colour>
 __device__ __forceinline__ void resolve_sample(long long i, const float* __restrict__ verts, const int* __restrict__ faces, int Nv,
@@ -190,6 +283,51 @@ __global__ __launch_bounds__(256) void resolve_textured_kernel(const float* __re
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)cam.H * cam.W * n_views) return;
     resolve_sample(i, verts, faces, Nv, Nf, poses, cam, zbuf, tex, rgba, depth_mm, depth_m, face_id);
+}
+
+// the lit resolve pass: one instance per colour source; flat / smooth and the tone table are wave-uniform branches on `sh`
+template <class Colour>
+__global__ __launch_bounds__(256) void resolve_lit_kernel(const float* __restrict__ verts, const int* __restrict__ faces, Colour base,
+                                                          Shading sh, int Nv, int Nf, const float* __restrict__ poses, int n_views,
+                                                          Cam cam, const unsigned long long* __restrict__ zbuf,
+                                                          uchar4* __restrict__ rgba, unsigned short* __restrict__ depth_mm,
+                                                          float* __restrict__ depth_m, int* __restrict__ face_id) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long hw = (long long)cam.H * cam.W;
+    if (i >= hw * n_views) return;
+    const Lit<Colour> lit{base, sh, verts, poses + 16 * (size_t)(i / hw)};
+    resolve_sample(i, verts, faces, Nv, Nf, poses, cam, zbuf, lit, rgba, depth_mm, depth_m, face_id);
+}
+
+// S8: the normal of vertex blockIdx.x * 256 + threadIdx.x from its incident faces, in the order of the adjacency list
+__global__ __launch_bounds__(256) void vertex_normals_kernel(const float* __restrict__ verts, int Nv, const int* __restrict__ faces,
+                                                             int Nf, const int* __restrict__ vf_offsets,
+                                                             const int* __restrict__ vf_faces, float* __restrict__ normals) {
+    const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (v >= Nv) return;
+    const long long total = 3ll * Nf;
+    const long long b = max((long long)vf_offsets[v], 0ll), e = min((long long)vf_offsets[v + 1], total);
+    float n[3] = {0.f, 0.f, 0.f};
+    for (long long j = b; j < e; ++j) {
+        const int f = vf_faces[j];
+        if ((unsigned)f >= (unsigned)Nf) continue;               // (a malformed list is never a fault)
+        const int i0 = faces[3 * (size_t)f], i1 = faces[3 * (size_t)f + 1], i2 = faces[3 * (size_t)f + 2];
+        if ((unsigned)i0 >= (unsigned)Nv || (unsigned)i1 >= (unsigned)Nv || (unsigned)i2 >= (unsigned)Nv) continue;
+        float e1[3], e2[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            e1[c] = verts[3 * (size_t)i1 + c] - verts[3 * (size_t)i0 + c];
+            e2[c] = verts[3 * (size_t)i2 + c] - verts[3 * (size_t)i0 + c];
+        }
+        n[0] = n[0] + ((e1[1] * e2[2]) - (e1[2] * e2[1]));
+        n[1] = n[1] + ((e1[2] * e2[0]) - (e1[0] * e2[2]));
+        n[2] = n[2] + ((e1[0] * e2[1]) - (e1[1] * e2[0]));
+    }
+    const float len2 = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
+    const bool ok = len2 > 0.f;
+    const float len = sqrtf(len2);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) normals[3 * (size_t)v + c] = ok ? n[c] / len : 0.f;
 }
 
 // T2, level 0: RGB bytes to uchar4 texels (alpha 255)
@@ -425,6 +563,63 @@ int pp_render_views_textured(const float* vertices, int n_vertices, const int* f
                                                 tex, n_vertices, n_faces, p, nv, cam, zbuf, (uchar4*)rgba + o, depth_mm + o,
                                                 depth_m ? depth_m + o : nullptr, face_id ? face_id + o : nullptr);
                          });
+}
+
+int pp_vertex_normals(const float* vertices, int n_vertices, const int* faces, int n_faces, const int* vf_offsets, const int* vf_faces,
+                      float* normals, void* stream) {
+    if (!vertices || !faces || !vf_offsets || !vf_faces || !normals || n_vertices <= 0 || n_faces <= 0 || n_faces > INT_MAX / 3 ||
+        ((uintptr_t)vertices % 4) != 0 || ((uintptr_t)faces % 4) != 0 || ((uintptr_t)vf_offsets % 4) != 0 ||
+        ((uintptr_t)vf_faces % 4) != 0 || ((uintptr_t)normals % 4) != 0)
+        return PP_EINVAL;
+    hipLaunchKernelGGL(vertex_normals_kernel, dim3((unsigned)((n_vertices + 255ll) / 256)), dim3(256), 0, (hipStream_t)stream, vertices,
+                       n_vertices, faces, n_faces, vf_offsets, vf_faces, normals);
+    return pp_last_launch();
+}
+
+int pp_render_views_lit(const float* vertices, int n_vertices, const int* faces, const int* faces_host, int n_faces,
+                        const unsigned char* colors, const float* face_uv, const void* mips, int Wt, int Ht, const float* poses,
+                        int n_views, float fx, float fy, float cx, float cy, int H, int W, float near, void* workspace,
+                        size_t workspace_bytes, unsigned char* rgba, unsigned short* depth_mm, float* depth_m, int* face_id,
+                        unsigned int* near_count, const float* lights_host, int n_lights, float ambient, int normal_mode,
+                        const float* normals, const unsigned char* base_color_host, const unsigned char* tone_table, int tone_entries,
+                        void* stream) {
+    const bool textured = face_uv || mips;
+    if (n_lights < 0 || n_lights > PP_MAX_LIGHTS || (n_lights > 0 && !lights_host) || !(ambient >= 0.f) || !isfinite(ambient) ||
+        (normal_mode != PP_NORMALS_FLAT && normal_mode != PP_NORMALS_SMOOTH) || (normal_mode == PP_NORMALS_SMOOTH && !normals) ||
+        (colors && textured) || (!colors && !textured && !base_color_host) ||
+        (tone_table ? (tone_entries < 2 || tone_entries > PP_TONE_MAX) : tone_entries != 0) || ((uintptr_t)lights_host % 4) != 0 ||
+        ((uintptr_t)normals % 4) != 0)
+        return PP_EINVAL;
+    if (textured && (!face_uv || !mips || Wt < 1 || Ht < 1 || Wt > PP_TEXTURE_MAX || Ht > PP_TEXTURE_MAX || ((uintptr_t)face_uv % 4) != 0 ||
+                     ((uintptr_t)mips % 4) != 0))
+        return PP_EINVAL;
+    Shading sh{};
+    for (int k = 0; k < n_lights; ++k) {
+        for (int c = 0; c < 4; ++c) {
+            if (!isfinite(lights_host[4 * k + c])) return PP_EINVAL;
+            sh.lights[k][c] = lights_host[4 * k + c];
+        }
+        if (sh.lights[k][3] < 0.f) return PP_EINVAL;
+    }
+    sh.n_lights = n_lights;
+    sh.ambient = ambient;
+    sh.smooth = normal_mode == PP_NORMALS_SMOOTH;
+    sh.normals = sh.smooth ? normals : nullptr;
+    sh.tone = tone_table;
+    sh.T = tone_entries;
+    hipStream_t st = (hipStream_t)stream;
+    auto run = [&](auto base) {
+        return render_chunks(vertices, n_vertices, faces, faces_host, n_faces, poses, n_views, fx, fy, cx, cy, H, W, near, workspace,
+                             workspace_bytes, rgba, depth_mm, depth_m, face_id, near_count, st,
+                             [&](unsigned blocks, const float* p, int nv, const Cam& cam, const unsigned long long* zbuf, size_t o) {
+                                 hipLaunchKernelGGL(resolve_lit_kernel<decltype(base)>, dim3(blocks), dim3(256), 0, st, vertices, faces, base,
+                                                    sh, n_vertices, n_faces, p, nv, cam, zbuf, (uchar4*)rgba + o, depth_mm + o,
+                                                    depth_m ? depth_m + o : nullptr, face_id ? face_id + o : nullptr);
+                             });
+    };
+    if (base_color_host) return run(ConstantColour{make_uchar4(base_color_host[0], base_color_host[1], base_color_host[2], 255)});
+    if (textured) return run(Textured{face_uv, (const uchar4*)mips, Wt, Ht});
+    return run(VertexColour{colors});
 }
 
 int pp_template_extents(const unsigned char* rgba, int n_views, int H, int W, int* extents, int* counts, void* stream) {

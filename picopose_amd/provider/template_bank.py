@@ -9,7 +9,8 @@ Replaces the reference's offline step rendering/scripts/render_bop_templates.py 
     bank = onboard_objects(net, [mesh, ...], view_poses)     # templates_data + template_feature
     pipeline.infer_image(net, data, bank, indexed_bank=True)
 
-The render recipe is the reference's: one ambient light of colour 1 (the pixel is the surface colour, unshaded), TEMPLATE_K at
+The default render recipe is the reference's for LM-O, YCB-V, HB, IC-BIN and TUD-L (Panda3D): one ambient light of colour 1 (the
+pixel is the surface colour, unshaded), TEMPLATE_K at
 480 x 640, object pose = a view rotation with t = (0, 0, diameter), RGBA uint8 with alpha = 255 on the object, depth in whole
 millimetres.  The rasteriser's conventions (pixel centres at integer coordinates, 1/256 px snapping, top-left fill rule, no
 back-face culling, no near-plane clipping) are stated in include/picopose_hip.h; parity with Panda3D's or BlenderProc's pixels
@@ -20,9 +21,19 @@ obj_NNNNNN.png`) is rendered from its texture, with no baking step: load_model r
 the device once per render call, and the resolve pass samples it perspective-correctly — one mip level per (view, face) chosen by
 area, bilinear, wrap mode repeat, v = 0 at the bottom row (THE TEXTURE CONTRACT in include/picopose_hip.h, T1-T5).  Out of scope
 (T6): anisotropic and trilinear filtering, multisampled edges (the reference enables 4x MSAA), clamp / mirror wrap, texture alpha,
-several textures per mesh, shading.  The package reads no fixture: `view_poses` is the caller's array (the
-reference's is rendering/src/lib3d/predefined_poses/obj_poses_level1.npy, 162 views)."""
+several textures per mesh.
+
+T-LESS and ITODD need shading: the reference renders their untextured CAD meshes (`models_cad`) with BlenderProc under eight point
+lights (render_bop_templates.py:131, blenderproc.py:29-39) and, for T-LESS, a uniform grey 0.4 material (:54-57); unlit, such a
+mesh — or any untextured CAD part of your own — is a flat silhouette with nothing for the features to match inside the outline.
+`render_views` / `render_templates` / `onboard_objects` take `shading=` (a Shading, a dict of its fields, or "tless"): Lambert
+diffuse plus ambient under up to 16 point lights, flat or smooth normals, an optional tone table, on top of any of the three colour
+sources (THE SHADING CONTRACT in include/picopose_hip.h, S1-S8; out of scope, S9: specular terms, shadows, coloured or spot
+lights, sRGB decoding of base colours, auto-smooth, MSAA).  Shading is opt-in: without it every render is byte for byte what it was.
+The package reads no fixture: `view_poses` is the caller's array (the reference's is
+rendering/src/lib3d/predefined_poses/obj_poses_level1.npy, 162 views)."""
 import ctypes
+import dataclasses
 import os
 
 import numpy as np
@@ -39,8 +50,9 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
 
 def load_ply(path):
     """A BOP model file -> {"vertices" (Nv,3) f32, "faces" (Nf,3) i32, "colors" (Nv,3) u8 or None, "uv" (Nv,2) f32 or None,
-    "face_uv" (Nf,3,2) f32 or None, "texture_file" str or None}.  ASCII and binary_little_endian PLY; element `vertex` with x y z
-    (red green blue and texture_u texture_v / s t / u v are returned; nx ny nz, alpha and any other scalar property are skipped),
+    "face_uv" (Nf,3,2) f32 or None, "normals" (Nv,3) f32 or None, "texture_file" str or None}.  ASCII and binary_little_endian PLY;
+    element `vertex` with x y z (red green blue, nx ny nz and texture_u texture_v / s t / u v are returned; alpha and any other scalar
+    property are skipped),
     element `face` with a `vertex_indices` / `vertex_index` list, optionally a `texcoord` list of 6 floats (u v per corner: MeshLab's
     wedge UVs) and scalar properties such as `texnumber`, which are skipped.  "texture_file" is the NAME in `comment TextureFile
     NAME`, as written (load_model resolves and reads it).
@@ -82,7 +94,7 @@ def load_ply(path):
     for need in ("vertex", "face"):
         if need not in names:
             raise ValueError(f"{path}: no '{need}' element")
-    out = {"uv": None, "face_uv": None, "texture_file": texture_file}
+    out = {"uv": None, "face_uv": None, "normals": None, "texture_file": texture_file}
     tokens, pos = (raw[body:].split(), 0) if fmt == "ascii" else (None, body)
     for name, count, props in elements:
         lists = [p for p in props if isinstance(p[1], tuple)]
@@ -109,6 +121,8 @@ def load_ply(path):
             out["vertices"] = np.ascontiguousarray(np.stack([col["x"], col["y"], col["z"]], axis=1).astype(np.float32))
             out["colors"] = (np.ascontiguousarray(np.stack([col["red"], col["green"], col["blue"]], axis=1).astype(np.uint8))
                              if all(c in col for c in ("red", "green", "blue")) else None)
+            if all(c in col for c in ("nx", "ny", "nz")):
+                out["normals"] = np.ascontiguousarray(np.stack([col["nx"], col["ny"], col["nz"]], axis=1).astype(np.float32))
             for un, vn in (("texture_u", "texture_v"), ("s", "t"), ("u", "v")):
                 if un in col and vn in col:
                     out["uv"] = np.ascontiguousarray(np.stack([col[un], col[vn]], axis=1).astype(np.float32))
@@ -283,6 +297,138 @@ def texture_mips(image):
     return mips
 
 
+@dataclasses.dataclass
+class Shading:
+    """The lit render's description (THE SHADING CONTRACT, S1).  lights (Nl, 3) and intensity (Nl,), Nl <= 16: point lights in METRES
+    in the OpenCV camera frame (x right, y down, z forward) — not scaled by `units`, only vertices and translations are; a light
+    adds intensity * cos / distance^2 to the multiplier of the base colour.  ambient >= 0 is added to it.  normals: "flat" (the
+    face's) or "smooth" (interpolated vertex normals: the mesh's "normals" when present, else vertex_normals(mesh)).  base_color: a
+    uint8 triple that replaces the mesh's colours / texture, or None.  tone: None (the multiplied colour, rounded and clamped to
+    255), "srgb" (srgb_tone_table()) or a uint8 array of 2 ... 65536 entries indexed by the colour / 255."""
+    lights: object = None
+    intensity: object = None
+    ambient: float = 0.0
+    normals: str = "flat"
+    base_color: object = None
+    tone: object = None
+
+
+def template_lights(distance_m, recipe="blenderproc", key=1.0):
+    """Light sets for templates rendered at `distance_m` metres -> {"lights" (Nl, 3), "intensity" (Nl,)} float64, Shading's fields.
+    "blenderproc": the eight point lights of rendering/src/lib3d/blenderproc.py:29-33 at (+-1, +-1, {0, 1}) m around the camera,
+    mapped from Blender's camera frame to ours, (x, -y, -z).  "headlight": one light at the camera (the pyrender recipe's).
+    The intensities are equal and chosen, in float64, so that a point at (0, 0, distance_m) with normal (0, 0, -1) receives a
+    multiplier of `key`: a camera-facing surface at the template distance shows its base colour for key = 1.  This normalisation
+    is this project's own: Blender's absolute exposure (50 W per light through Cycles and its view transform) cannot be reproduced
+    here, only the geometry of the light set is the reference's."""
+    d = float(distance_m)
+    if not (np.isfinite(d) and d > 0) or not (np.isfinite(key) and key >= 0):
+        raise ValueError(f"distance_m must be positive and key non-negative, got {distance_m!r}, {key!r}")
+    if recipe == "blenderproc":
+        L = np.array([[x, -y, -z] for x in (-1.0, 1.0) for y in (-1.0, 1.0) for z in (0.0, 1.0)])
+    elif recipe == "headlight":
+        L = np.zeros((1, 3))
+    else:
+        raise ValueError(f"recipe must be 'blenderproc' or 'headlight', got {recipe!r}")
+    to_light = L - np.array([0.0, 0.0, d])
+    d2 = (to_light ** 2).sum(axis=1)
+    gain = (-to_light[:, 2]) / (d2 * np.sqrt(d2))               # n . L / |L|^3 with n = (0, 0, -1): every light is in front of it
+    return {"lights": L, "intensity": np.full(len(L), float(key) / gain.sum())}
+
+
+def srgb_tone_table(T=4096):
+    """The sRGB OETF as a tone table of T uint8 entries: entry i is 255 * oetf(i / (T - 1)), evaluated in float64 and rounded."""
+    if not 2 <= int(T) <= 65536:
+        raise ValueError(f"T must be in [2, 65536], got {T}")
+    x = np.arange(int(T), dtype=np.float64) / (int(T) - 1)
+    y = np.where(x <= 0.0031308, 12.92 * x, 1.055 * np.power(x, 1.0 / 2.4) - 0.055)
+    return np.floor(255.0 * np.clip(y, 0.0, 1.0) + 0.5).astype(np.uint8)
+
+
+def _parse_shading(shading, distance_m):
+    """Shading / dict / "tless" -> (lights4 (Nl, 4) f32, ambient, smooth, base_color (3,) u8 or None, tone (T,) u8 or None), validated."""
+    if isinstance(shading, str):
+        if shading != "tless":
+            raise ValueError(f"shading must be a Shading, a dict of its fields or 'tless', got {shading!r}")
+        shading = Shading(**template_lights(distance_m), normals="flat", base_color=(102, 102, 102))     # 0.4 * 255
+    elif isinstance(shading, dict):
+        unknown = set(shading) - {f.name for f in dataclasses.fields(Shading)}
+        if unknown:
+            raise ValueError(f"unknown shading field(s) {sorted(unknown)}")
+        shading = Shading(**shading)
+    elif not isinstance(shading, Shading):
+        raise ValueError(f"shading must be a Shading, a dict of its fields or 'tless', got {type(shading).__name__}")
+    try:
+        lights = np.zeros((0, 3)) if shading.lights is None else np.asarray(shading.lights, dtype=np.float64)
+        inten = np.zeros(0) if shading.intensity is None else np.asarray(shading.intensity, dtype=np.float64)
+        ambient = float(shading.ambient)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"shading lights, intensity and ambient must be numeric: {e}") from None
+    if lights.ndim != 2 or lights.shape[1] != 3 or len(lights) > 16 or not np.all(np.isfinite(lights)):
+        raise ValueError(f"shading lights must be a finite (Nl, 3) array with Nl <= 16, got {lights.shape}")
+    if inten.shape != (len(lights),) or not np.all(np.isfinite(inten)) or np.any(inten < 0):
+        raise ValueError(f"shading intensity must be (Nl,) = ({len(lights)},) finite and non-negative, got {inten.shape}")
+    with np.errstate(over="ignore"):
+        lights4 = np.ascontiguousarray(np.concatenate([lights, inten[:, None]], axis=1).astype(np.float32))
+    if not np.all(np.isfinite(lights4)):
+        raise ValueError("a shading light or intensity overflows float32")
+    if not (np.isfinite(ambient) and ambient >= 0 and np.isfinite(np.float32(ambient))):
+        raise ValueError(f"shading ambient must be finite and non-negative, got {shading.ambient!r}")
+    if shading.normals not in ("flat", "smooth"):
+        raise ValueError(f"shading normals must be 'flat' or 'smooth', got {shading.normals!r}")
+    base = shading.base_color
+    if base is not None:
+        b = np.asarray(base)
+        if b.shape != (3,) or not np.issubdtype(b.dtype, np.integer) or b.min() < 0 or b.max() > 255:
+            raise ValueError(f"shading base_color must be three integers in [0, 255], got {base!r}")
+        base = np.ascontiguousarray(b.astype(np.uint8))
+    tone = shading.tone
+    if isinstance(tone, str):
+        if tone != "srgb":
+            raise ValueError(f"shading tone must be None, 'srgb' or a uint8 array, got {tone!r}")
+        tone = srgb_tone_table()
+    elif tone is not None:
+        tone = np.asarray(tone)
+        if tone.ndim != 1 or tone.dtype != np.uint8 or not 2 <= len(tone) <= 65536:
+            raise ValueError(f"shading tone must be a 1-D uint8 array of 2 ... 65536 entries, got {tone.dtype} {tone.shape}")
+        tone = np.ascontiguousarray(tone)
+    return lights4, ambient, shading.normals == "smooth", base, tone
+
+
+def vertex_face_csr(faces, n_vertices):
+    """The vertex -> face adjacency of S8 -> (vf_offsets (Nv + 1,), vf_faces (3 Nf,)) int32: a stable sort of faces.reshape(-1),
+    so the faces of a vertex come in ascending face index."""
+    flat = np.asarray(faces, dtype=np.int64).reshape(-1)
+    order = np.argsort(flat, kind="stable")
+    offsets = np.concatenate([[0], np.cumsum(np.bincount(flat, minlength=n_vertices))])
+    return offsets.astype(np.int32), np.ascontiguousarray((order // 3).astype(np.int32))
+
+
+def vertex_normals(mesh, device="cuda"):
+    """Area-weighted unit vertex normals of `mesh` ({"vertices", "faces"}) on the device (S8 of the shading contract) -> (Nv, 3)
+    float32 device tensor; zeros for a vertex no face with area references.  One launch; the bytes do not depend on launch order."""
+    v, f, _ = _mesh_arrays(mesh)
+    if len(f) > (2 ** 31 - 1) // 3:
+        raise ValueError(f"too many faces for the adjacency list ({len(f)})")
+    off, adj = vertex_face_csr(f, len(v))
+    v_d, f_d, off_d, adj_d = (torch.from_numpy(a).to(device) for a in (v, f, off, adj))
+    out = torch.empty(len(v), 3, dtype=torch.float32, device=device)
+    _lib.check(_lib.lib().pp_vertex_normals(v_d.data_ptr(), len(v), f_d.data_ptr(), len(f), off_d.data_ptr(), adj_d.data_ptr(), out.data_ptr(),
+                                            _lib.stream_ptr()), "pp_vertex_normals")
+    return out
+
+
+def _mesh_normals(mesh, n_vertices):
+    """The mesh's own "normals" as (Nv, 3) float32, or None when it has none."""
+    n = mesh.get("normals")
+    if n is None:
+        return None
+    n = np.asarray(n)
+    if n.shape != (n_vertices, 3) or not np.issubdtype(n.dtype, np.floating) or not np.all(np.isfinite(n)):
+        raise ValueError(f"normals must be a finite (Nv, 3) float array, got {n.dtype} {n.shape}")
+    return np.ascontiguousarray(n, dtype=np.float32)
+
+
 def _unit_scale(units, vertices):
     if units == "auto":                                          # call_panda3d.py:39-40
         units = "m" if mesh_diameter(vertices) < 10 else "mm"
@@ -292,13 +438,16 @@ def _unit_scale(units, vertices):
 
 
 def render_views(mesh, poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", near=1e-3, return_depth_m=False, return_face_id=False,
-                 workspace_bytes=DEFAULT_WORKSPACE_BYTES, check_near=True, device="cuda"):
+                 workspace_bytes=DEFAULT_WORKSPACE_BYTES, check_near=True, device="cuda", shading=None):
     """Render `mesh` ({"vertices", "faces", "colors" or None}, or with "texture" (Ht,Wt,3) uint8 and "face_uv" (Nf,3,2) or "uv"
     (Nv,2): the textured path, which wins over "colors") under the object -> camera poses (V,4,4) whose translation is in
     the mesh's `units` ("mm" as BOP models are, "m", or "auto": the reference's rule, diameter < 10 -> metres).  The kernels work
     in metres: vertices and translations are scaled by 1e-3 in float64 for "mm" and rounded to float32 once.
     -> {"rgba" (V,H,W,4) uint8, "depth_mm" (V,H,W) uint16 [, "depth_m" (V,H,W) f32, "face_id" (V,H,W) int32], "near_count"
-    (1,) int32 device tensor}.  A mesh without colours and without a texture renders mid-grey (128, 128, 128).  A texture's mip
+    (1,) int32 device tensor}.  A mesh without colours and without a texture renders mid-grey (128, 128, 128) (unlit; pass `shading` for an
+    untextured model).  shading: None (unlit, the default), a Shading, a dict of its fields, or "tless" = template_lights at the
+    object's template distance (its diameter), flat normals, base_color (102, 102, 102), no tone table; the base colour of a sample is
+    what the unlit render shows there, or base_color.  ValueError for a malformed shading field, before any device work.  A texture's mip
     pyramid is built on the device once per call, before the views are rendered.  `workspace_bytes` bounds the
     rasteriser's workspace; the views are rendered in as many chunks as that takes (at least one view's worth is allocated).
     check_near: synchronise and raise ValueError when a triangle was dropped at the near plane (`near` metres); False leaves the
@@ -306,6 +455,8 @@ def render_views(mesh, poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", n
     v, f, c = _mesh_arrays(mesh)
     tex = _mesh_texture(mesh, len(v), f)
     scale = _unit_scale(units, v)
+    lit = None if shading is None else _parse_shading(shading, mesh_diameter(v) * scale)
+    own_normals = _mesh_normals(mesh, len(v)) if lit is not None and lit[2] else None
     poses = np.array(poses, dtype=np.float64)
     if poses.ndim != 3 or poses.shape[1:] != (4, 4) or len(poses) == 0 or not np.all(np.isfinite(poses)):
         raise ValueError(f"poses must be a non-empty finite (V, 4, 4) array, got {poses.shape}")
@@ -331,13 +482,29 @@ def render_views(mesh, poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", n
     tail = (p_d.data_ptr(), V, float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), H, W, float(near), ws.data_ptr(), ws.numel(),
             out["rgba"].data_ptr(), out["depth_mm"].data_ptr(), out["depth_m"].data_ptr() if return_depth_m else None,
             out["face_id"].data_ptr() if return_face_id else None, out["near_count"].data_ptr(), _lib.stream_ptr())
-    if tex is None:
-        _lib.check(L.pp_render_views(v_d.data_ptr(), len(v), f_d.data_ptr(), f.ctypes.data, len(f), c_d.data_ptr(), *tail), "pp_render_views")
-    else:
+    Ht = Wt = 0
+    if tex is not None:
         image, face_uv = tex
         Ht, Wt = image.shape[:2]
         mips = texture_mips(torch.from_numpy(image).to(device))           # once per call: the chunk loop is inside the entry
         uv_d = torch.from_numpy(face_uv).to(device)
+    if lit is not None:
+        lights4, ambient, smooth, base, tone = lit
+        n_d = None
+        if smooth:                                                        # direction only: the unit of the vertices does not matter
+            n_d = torch.from_numpy(own_normals).to(device) if own_normals is not None else vertex_normals(mesh, device)
+        tone_d = None if tone is None else torch.from_numpy(tone).to(device)
+        _lib.check(L.pp_render_views_lit(v_d.data_ptr(), len(v), f_d.data_ptr(), f.ctypes.data, len(f),
+                                         c_d.data_ptr() if tex is None and base is None else None,
+                                         uv_d.data_ptr() if tex is not None and base is None else None,
+                                         mips.data_ptr() if tex is not None and base is None else None, Wt, Ht, *tail[:-1],
+                                         lights4.ctypes.data if len(lights4) else None, len(lights4), ambient, int(smooth),
+                                         None if n_d is None else n_d.data_ptr(), None if base is None else base.ctypes.data,
+                                         None if tone_d is None else tone_d.data_ptr(), 0 if tone is None else len(tone), tail[-1]),
+                   "pp_render_views_lit")
+    elif tex is None:
+        _lib.check(L.pp_render_views(v_d.data_ptr(), len(v), f_d.data_ptr(), f.ctypes.data, len(f), c_d.data_ptr(), *tail), "pp_render_views")
+    else:
         _lib.check(L.pp_render_views_textured(v_d.data_ptr(), len(v), f_d.data_ptr(), f.ctypes.data, len(f), uv_d.data_ptr(),
                                               mips.data_ptr(), Wt, Ht, *tail), "pp_render_views_textured")
     if check_near:
@@ -418,13 +585,14 @@ def templates_from_frames(rgba, depth_mm, K, poses_mm, img_size=224, pts_size=64
 
 
 def render_templates(mesh, view_poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", depth="png", img_size=224, pts_size=64,
-                     rgb_mask_flag=False, near=1e-3, workspace_bytes=DEFAULT_WORKSPACE_BYTES, device="cuda"):
+                     rgb_mask_flag=False, near=1e-3, workspace_bytes=DEFAULT_WORKSPACE_BYTES, device="cuda", shading=None):
     """One object's template bank from its mesh: `tem_rgb` (V,3,S,S), `tem_mask` (V,S,S), `tem_pts3d` (V,P,P,3) metres, `tem_bbox`
     (V,4), `tem_M` (V,3,3), `tem_K` (V,3,3), `tem_pose` (V,4,4) (t in metres), float32 device tensors with `_get_template`'s values
     for the rendered frames (bop_test_dataset.py:212-264).  view_poses (V,4,4): only the rotations are used; the object sits at
     (0, 0, diameter) (template_object_poses).  Render, extents, ONE device->host copy (extents + near-plane count), one crop launch.
     depth="png" (default): the lookup points come from the uint16 millimetres a depth file would hold, as the reference's do;
     depth="float": from the float32 depth directly — a deviation from the reference that removes the 0.5 mm quantisation.
+    shading: render_views' (None: unlit; "tless" for T-LESS / ITODD-like untextured CAD models); it changes `tem_rgb` only.
     ValueError: a triangle at the near plane, or a view that covers no pixel (named)."""
     if depth not in ("png", "float"):
         raise ValueError(f"depth must be 'png' or 'float', got {depth!r}")
@@ -432,7 +600,7 @@ def render_templates(mesh, view_poses, K=TEMPLATE_K, resolution=(480, 640), unit
     to_mm = 1.0 / (_unit_scale(units, v) * 1000.0)               # the returned pose follows the file convention: t in mm, then / 1000
     poses = template_object_poses(view_poses, v)
     r = render_views(mesh, poses, K=K, resolution=resolution, units=units, near=near, return_depth_m=depth == "float",
-                     workspace_bytes=workspace_bytes, check_near=False, device=device)
+                     workspace_bytes=workspace_bytes, check_near=False, device=device, shading=shading)
     poses_mm = poses.copy()
     poses_mm[:, :3, 3] *= to_mm
     return _crop_frames(r["rgba"], r["depth_m"] if depth == "float" else r["depth_mm"], depth == "float", K, poses_mm, r["near_count"],

@@ -9,7 +9,10 @@
   * --profile: one render_templates per mesh and nothing else, for `rocprofv3 --kernel-trace --stats -- python tools/bench_template_bank.py --profile`;
   * --textured WtxHt: the 20 k-triangle icosphere with per-vertex UVs and a generated Wt x Ht texture instead of the three meshes:
     render_templates and render_views for the vertex-colour and the textured path alternately, and the mip pyramid build alone (HIP
-    events on the stream); with --profile one textured render_templates and nothing else.
+    events on the stream); with --profile one textured render_templates and nothing else;
+  * --shaded: the 20 k-triangle icosphere's 162 views through render_views unlit, lit flat, lit smooth (precomputed normals), textured
+    and textured lit, alternately, twice (HIP events, uploads included: they are the same for every path), and pp_vertex_normals
+    alone; with --profile one render of each path and nothing else, for the per-kernel times.
 
 Prints one JSON line per measurement."""
 import argparse
@@ -86,6 +89,31 @@ def textured(a, views):
                       "samples": int(r["face_id"].numel())}), flush=True)
 
 
+def shaded(a, views):
+    m = ro.icosphere(5, 50.0)
+    d = m["vertices"].astype(np.float64) / 50.0
+    uv = np.stack([np.arctan2(d[:, 1], d[:, 0]) / (2 * np.pi) + 0.5, np.arccos(np.clip(d[:, 2], -1, 1)) / np.pi], axis=1).astype(np.float32)
+    tm = {"vertices": m["vertices"], "faces": m["faces"], "uv": uv, "texture": np.random.default_rng(0).integers(0, 256, (2048, 2048, 3)).astype(np.uint8)}
+    poses = tb.template_object_poses(views, m["vertices"])
+    lights = tb.template_lights(tb.mesh_diameter(m["vertices"]) * 1e-3)
+    normals = tb.vertex_normals(m).cpu().numpy()                # uploaded per call like the colours: the S8 launch is timed on its own
+    paths = {"unlit": (m, None), "lit_flat": (m, dict(lights, normals="flat")), "lit_smooth": (dict(m, normals=normals), dict(lights, normals="smooth")),
+             "textured_unlit": (tm, None), "textured_lit_flat": (tm, dict(lights, normals="flat"))}
+    if a.profile:
+        for mesh, sh in paths.values():
+            tb.render_views(mesh, poses, check_near=False, shading=sh)
+        tb.vertex_normals(m)
+        torch.cuda.synchronize()
+        return
+    for rep in range(2):
+        for name, (mesh, sh) in paths.items():
+            print(json.dumps({"what": "render_views", "path": name, "pass": rep, "mesh": "icosphere_20480", "views": 162,
+                              "event_ms": round(events(lambda: tb.render_views(mesh, poses, check_near=False, shading=sh), a.reps, a.warmup), 3)}),
+                  flush=True)
+    print(json.dumps({"what": "vertex_normals alone (CSR built on the host, 4 uploads, one launch)", "vertices": len(m["vertices"]),
+                      "event_ms": round(events(lambda: tb.vertex_normals(m), a.reps, a.warmup), 4)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -95,10 +123,13 @@ def main():
     ap.add_argument("--extended", action="store_true")
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--textured", default=None, metavar="WtxHt", help="texture size, e.g. 2048x2048")
+    ap.add_argument("--shaded", action="store_true")
     a = ap.parse_args()
     views = np.load(os.path.join(ROOT, "tests", "golden", "template_view_poses_level1.npy"))
     if a.textured:
         return textured(a, views)
+    if a.shaded:
+        return shaded(a, views)
     meshes = {"cube_12": ro.cube(40.0), "icosphere_20480": ro.icosphere(5, 50.0)}
     big = ro.icosphere(a.big, 50.0)
     meshes[f"icosphere_{len(big['faces'])}"] = big
