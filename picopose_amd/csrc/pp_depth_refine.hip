@@ -2,8 +2,9 @@
 // stated in include/picopose_hip.h, "DEPTH REFINEMENT", and restated in numpy by tests/depth_refine_oracle.py).
 //
 //   refine_init_kernel        one lane per view: the working pose, the active flag and the per-pose state
-//   vsd_raster_small_kernel, vsd_raster_large_kernel  the windowed depth raster of pp_vsd_raster_dev.h (shared with pp_vsd.hip);
-//                             a view whose active flag is 0 renders nothing
+//   vsd_raster_small_kernel, vsd_raster_large_kernel  the windowed depth raster of pp_vsd_raster_dev.h (shared with pp_vsd.hip, as are
+//                             the validation of the object, camera and view tables and the front of the workspace); a view whose
+//                             active flag is 0 renders nothing
 //   refine_accumulate_kernel  one workgroup per STRIP (PP_DEPTH_REFINE_STRIP_ROWS rows of one view's window): associates the strip's
 //                             samples with the test depth and adds J^T J, J^T r, sum r^2 and N as per-lane float64 partial sums,
 //                             reduced by xor-shuffles within a wave and through LDS across waves in wave order -> 29 doubles per strip
@@ -23,7 +24,6 @@
 
 namespace {
 
-constexpr size_t WS_HEADER = 256;
 constexpr int BLOCK = 256;
 constexpr int WAVES = BLOCK / 64;
 constexpr int ROWS = PP_DEPTH_REFINE_STRIP_ROWS;
@@ -47,8 +47,6 @@ struct State {
     double* sums;              // (n_views, iterations, NS) or null
     int iterations;
 };
-
-__device__ __forceinline__ bool finite32(float v) { return fabsf(v) <= 3.402823466e38f; }
 
 __global__ __launch_bounds__(BLOCK) void refine_init_kernel(State st, const int* __restrict__ windows, int n_views) {
     const int v = blockIdx.x * BLOCK + threadIdx.x;
@@ -347,11 +345,6 @@ __global__ __launch_bounds__(64) void refine_solve_kernel(State st, SolveArgs a,
     }
 }
 
-inline size_t align256(size_t n) { return (n + 255) / 256 * 256; }
-
-inline bool positive_finite(float v) { return v > 0.f && v <= 3.402823466e38f; }
-inline bool finite_host(float v) { return fabsf(v) <= 3.402823466e38f; }
-
 }  // namespace
 
 extern "C" {
@@ -380,57 +373,34 @@ int pp_depth_refine(const float* vertices, const int* vert_off, const int* faces
         !poses_out || !active || !status || !n_iterations || !rank || !n_points || !rms_before || !rms_after || !near_count)
         return PP_EINVAL;
     if (poses_in == poses_out) return PP_EINVAL;
-    if (n_objects <= 0 || n_images <= 0 || n_views <= 0 || H <= 0 || W <= 0 || (long long)H * W > INT_MAX) return PP_EINVAL;
     if (iterations < 1 || iterations > PP_DEPTH_REFINE_MAX_ITERATIONS || min_points < 1 || !positive_finite(max_distance) ||
-        !(min_cos >= 0.f && min_cos < 1.f) || !(rcond >= 0.f && rcond < 1.f) || !(eps >= 0.f && finite_host(eps)) ||
+        !(min_cos >= 0.f && min_cos < 1.f) || !(rcond >= 0.f && rcond < 1.f) || !(eps >= 0.f && finite32(eps)) ||
         !positive_finite(max_translation) || !positive_finite(max_rotation) || !positive_finite(near))
         return PP_EINVAL;
-    if (vert_off_host[0] != 0 || face_off_host[0] != 0) return PP_EINVAL;
-    for (int o = 0; o < n_objects; ++o) {
-        if (vert_off_host[o + 1] <= vert_off_host[o] || face_off_host[o + 1] < face_off_host[o]) return PP_EINVAL;
-        if (!positive_finite(diameters_host[o])) return PP_EINVAL;
+    SceneSize n;
+    if (check_scene({vert_off_host, faces_host, face_off_host, diameters_host, n_objects, cams_host, n_images, H, W, view_obj_host,
+                     view_img_host, windows_host, view_zoff_host, n_views}, n) != PP_OK)
+        return PP_EINVAL;
+    // on top of the scene: the objects' vertex boxes and the strips that follow from the windows
+    for (int o = 0; o < n_objects; ++o)
         for (int d = 0; d < 3; ++d) {
             const float lo = boxes_host[6 * (size_t)o + d], hi = boxes_host[6 * (size_t)o + 3 + d];
-            if (!finite_host(lo) || !finite_host(hi) || hi < lo) return PP_EINVAL;
+            if (!finite32(lo) || !finite32(hi) || hi < lo) return PP_EINVAL;
         }
-        const unsigned nv = (unsigned)(vert_off_host[o + 1] - vert_off_host[o]);
-        for (size_t k = 3 * (size_t)face_off_host[o]; k < 3 * (size_t)face_off_host[o + 1]; ++k)
-            if ((unsigned)faces_host[k] >= nv) return PP_EINVAL;
-    }
-    for (int i = 0; i < n_images; ++i) {
-        const float* k = cams_host + 4 * (size_t)i;
-        if (k[0] == 0.f || k[1] == 0.f || !finite_host(k[0]) || !finite_host(k[1]) || !finite_host(k[2]) || !finite_host(k[3]))
-            return PP_EINVAL;
-    }
-    if (view_zoff_host[0] != 0 || view_soff_host[0] != 0) return PP_EINVAL;
-    long long total_faces = 0;
-    int max_faces = 0;
+    if (view_soff_host[0] != 0) return PP_EINVAL;
     for (int v = 0; v < n_views; ++v) {
-        const int o = view_obj_host[v];
-        if ((unsigned)o >= (unsigned)n_objects || (unsigned)view_img_host[v] >= (unsigned)n_images) return PP_EINVAL;
-        const int nf = face_off_host[o + 1] - face_off_host[o];
-        if (nf <= 0) return PP_EINVAL;                            // an object of the call without faces
         const int* w = windows_host + 4 * (size_t)v;
-        if (w[0] < 0 || w[1] < 0 || w[2] < w[0] || w[3] < w[1] || w[2] > W || w[3] > H) return PP_EINVAL;
-        const long long ws = (long long)(w[2] - w[0]) * (w[3] - w[1]);
-        if (view_zoff_host[v + 1] - view_zoff_host[v] != ws) return PP_EINVAL;
-        const long long strips_v = ws > 0 ? (w[3] - w[1] + ROWS - 1) / ROWS : 0;
+        const long long strips_v = w[2] > w[0] && w[3] > w[1] ? (w[3] - w[1] + ROWS - 1) / ROWS : 0;
         if ((long long)view_soff_host[v + 1] - view_soff_host[v] != strips_v) return PP_EINVAL;
-        total_faces += nf;
-        max_faces = nf > max_faces ? nf : max_faces;
     }
-    if (total_faces > (long long)UINT_MAX) return PP_EINVAL;
-    const long long samples = view_zoff_host[n_views];
     const int strips = view_soff_host[n_views];
     size_t need = 0;
-    if (pp_depth_refine_workspace_bytes(samples, total_faces, strips, &need) != PP_OK) return PP_EINVAL;
+    if (pp_depth_refine_workspace_bytes(n.samples, n.total_faces, strips, &need) != PP_OK) return PP_EINVAL;
     if (((uintptr_t)workspace % 256) != 0 || workspace_bytes < need) return PP_EWORKSPACE;
 
     hipStream_t st = (hipStream_t)stream;
-    unsigned* qcount = (unsigned*)workspace;
-    unsigned long long* zbuf = (unsigned long long*)((char*)workspace + WS_HEADER);
-    uint2* queue = (uint2*)((char*)zbuf + align256((size_t)samples * 8));
-    double* partial = (double*)((char*)queue + align256((size_t)total_faces * 8));
+    const RasterWs ws = carve(workspace, n);
+    double* partial = (double*)((char*)ws.queue + align256((size_t)n.total_faces * 8));
     Scene s{vertices, vert_off, faces, face_off, cams, view_obj, view_img, poses_out, windows, view_zoff, n_views, H, W, near};
     s.active = active;
     const State state{poses_in, poses_out, active, status, n_iterations, rank, n_points, rms_before, rms_after, trajectory, sums, iterations};
@@ -438,10 +408,9 @@ int pp_depth_refine(const float* vertices, const int* vert_off, const int* faces
     if (sums) PP_CHECK_HIP(hipMemsetAsync(sums, 0, sizeof(double) * (size_t)n_views * iterations * NS, st));
     hipLaunchKernelGGL(refine_init_kernel, dim3((unsigned)((n_views + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, state, windows, n_views);
     for (int it = 0; it < iterations && strips > 0; ++it) {
-        PP_CHECK_HIP(hipMemsetAsync(qcount, 0, sizeof(unsigned), st));
-        PP_CHECK_HIP(hipMemsetAsync(zbuf, 0xFF, (size_t)samples * 8, st));
-        launch_raster(s, max_faces, total_faces, zbuf, queue, qcount, near_count, st);
-        hipLaunchKernelGGL(refine_accumulate_kernel, dim3((unsigned)strips), dim3(BLOCK), 0, st, s, zbuf, view_soff, diameters, boxes, depth,
+        const int rc = raster_views(s, n, ws, near_count, st);
+        if (rc != PP_OK) return rc;
+        hipLaunchKernelGGL(refine_accumulate_kernel, dim3((unsigned)strips), dim3(BLOCK), 0, st, s, ws.zbuf, view_soff, diameters, boxes, depth,
                            max_distance, min_cos, partial);
         const SolveArgs a{min_points, it, (double)rcond, (double)eps, (double)max_translation, (double)max_rotation};
         hipLaunchKernelGGL(refine_solve_kernel, dim3((unsigned)n_views), dim3(64), 0, st, state, a, view_obj, view_soff, diameters, boxes,

@@ -1,8 +1,9 @@
-// Device functions of the z-buffer rasterisers: items 1-6 of the raster contract (include/picopose_hip.h) for one (view, triangle).
-// One statement of the arithmetic for pp_render_views (pp_render.hip) and the depth raster of pp_vsd_errors (pp_vsd.hip): every float
-// operation is a single float32 operation, coverage is exact integer arithmetic, and nothing is stored per triangle — tri_setup() gives
-// the same bits wherever it is evaluated.  Include it AFTER `#pragma clang fp contract(off)` (it repeats the pragma for the
-// translation unit) and after any header that must be compiled in the build's default mode (pp_crop_dev.h).
+// Device functions of the z-buffer rasterisers: items 1-6 of the raster contract (include/picopose_hip.h) for one (view, triangle) and
+// the coverage pass built from them.  One statement of the arithmetic AND of the traversal for the template renderer (pp_render.hip)
+// and the windowed depth raster (pp_vsd_raster_dev.h): every float operation is a single float32 operation, coverage is exact integer
+// arithmetic, and nothing is stored per triangle — tri_setup() gives the same bits wherever it is evaluated.  A raster kernel is its
+// index mapping and its View; cover_small() and cover_large() are the rest.  Include it AFTER `#pragma clang fp contract(off)` (it
+// repeats the pragma for the translation unit) and after any header that must be compiled in the build's default mode (pp_crop_dev.h).
 #ifndef PP_RASTER_DEV_H
 #define PP_RASTER_DEV_H
 #include <hip/hip_runtime.h>
@@ -16,6 +17,7 @@ constexpr int SUB = 256;                 // sub-pixel units per pixel
 constexpr float SNAP_LIMIT = 268435456.f;   // 2^28 sub-pixel units: the edge functions stay below 2^60
 constexpr int SMALL_BOX = 64;            // samples a single lane walks
 constexpr int TILE = 16;
+constexpr size_t WS_HEADER = 256;        // bytes of a workspace in front of the z-buffer: the queue counter, padded to the alignment
 
 enum : int { TRI_OK = 0, TRI_NEAR = 1, TRI_SKIP = 2 };
 
@@ -132,6 +134,52 @@ __device__ __forceinline__ void depth_test(const Tri& t, int px, int py, int fac
     const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)face;
     // the slot only ever decreases: a (possibly stale) value at or below the key already rules this fragment out
     if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > key) atomicMin(slot, key);
+}
+
+// one view of a coverage launch: its mesh, pose and camera, and where its z-buffer words lie — sample (px, py) is word
+// (py - y0) * ww + (px - x0) of the view (a whole frame: origin (0, 0), row stride W)
+struct View {
+    const float* verts;
+    const int* faces;
+    const float* pose;
+    int Nv, Nf, x0, y0, ww;
+    Cam cam;
+};
+
+__device__ __forceinline__ unsigned long long* slot_of(unsigned long long* zv, const View& vw, int px, int py) {
+    return zv + (size_t)(py - vw.y0) * vw.ww + (px - vw.x0);
+}
+
+// the calling lane's triangle f of view v (z-buffer words at zv): a triangle in front of the near plane is counted, a box of at most
+// SMALL_BOX samples is walked here, a larger one goes to the queue
+__device__ __forceinline__ void cover_small(const View& vw, int v, int f, unsigned long long* zv, uint2* __restrict__ queue,
+                                            unsigned* __restrict__ qcount, unsigned* __restrict__ near_slot) {
+    Tri t;
+    const int st = tri_setup(vw.verts, vw.faces, vw.Nv, vw.pose, vw.cam, f, t);
+    if (st == TRI_NEAR) atomicAdd(near_slot, 1u);
+    if (st != TRI_OK) return;
+    if ((t.bx1 - t.bx0 + 1) * (long long)(t.by1 - t.by0 + 1) > SMALL_BOX) {
+        queue[atomicAdd(qcount, 1u)] = make_uint2((unsigned)v, (unsigned)f);
+        return;
+    }
+    for (int py = t.by0; py <= t.by1; ++py)
+        for (int px = t.bx0; px <= t.bx1; ++px) depth_test(t, px, py, f, slot_of(zv, vw, px, py));
+}
+
+// the queued triangle f of a view for the calling workgroup of TILE * TILE lanes: the tiles blockIdx.x, blockIdx.x + gridDim.x, ...
+// of its box, a lane per sample, after the tile is tested against the three edges
+__device__ __forceinline__ void cover_large(const View& vw, unsigned f, unsigned long long* zv) {
+    Tri t;
+    if (f >= (unsigned)vw.Nf || tri_setup(vw.verts, vw.faces, vw.Nv, vw.pose, vw.cam, (int)f, t) != TRI_OK) return;
+    const int ty = threadIdx.x / TILE, tx = threadIdx.x % TILE;
+    const int ntx = (t.bx1 - t.bx0) / TILE + 1, nty = (t.by1 - t.by0) / TILE + 1;
+    for (int tile = blockIdx.x; tile < ntx * nty; tile += gridDim.x) {
+        const int x0 = t.bx0 + (tile % ntx) * TILE, y0 = t.by0 + (tile / ntx) * TILE;
+        const int x1 = min(x0 + TILE - 1, t.bx1), y1 = min(y0 + TILE - 1, t.by1);
+        if (tile_outside(t, x0, y0, x1, y1)) continue;
+        const int px = x0 + tx, py = y0 + ty;
+        if (px <= x1 && py <= y1) depth_test(t, px, py, (int)f, slot_of(zv, vw, px, py));
+    }
 }
 
 }  // namespace

@@ -1,7 +1,8 @@
 // BOP19 VSD of (estimate, ground truth) pairs (picopose_amd/evaluation.py plans every call; the contract is stated in
 // include/picopose_hip.h and restated in numpy by tests/vsd_oracle.py).
 //
-//   vsd_raster_small_kernel, vsd_raster_large_kernel  the windowed depth raster of pp_vsd_raster_dev.h (shared with pp_depth_refine.hip)
+//   vsd_raster_small_kernel, vsd_raster_large_kernel  the windowed depth raster of pp_vsd_raster_dev.h (shared with pp_depth_refine.hip,
+//                            as are the validation of the object, camera and view tables and the workspace layout)
 //   vsd_depth_kernel         optional: the window's z-buffer words -> a dense (n_views, H, W) float32 depth image
 //   vsd_pair_kernel          one workgroup per pair: walks the union box of the two windows, reads Z_est / Z_gt from the z-buffer
 //                            words and the test depth from the image, keeps |union|, |inter| and n_1 .. n_T as per-lane INTEGERS,
@@ -20,7 +21,6 @@
 
 namespace {
 
-constexpr size_t WS_HEADER = 256;
 constexpr int BLOCK = 256;
 constexpr int WAVES = BLOCK / 64;
 constexpr int NC = 2 + PP_VSD_MAX_TAUS;   // counters of a pair: union, inter, n_1 .. n_16
@@ -130,10 +130,6 @@ __global__ __launch_bounds__(BLOCK) void vsd_pair_kernel(Scene s, const unsigned
     }
 }
 
-inline size_t align256(size_t n) { return (n + 255) / 256 * 256; }
-
-inline bool positive_finite(float v) { return v > 0.f && v <= 3.402823466e38f; }
-
 }  // namespace
 
 extern "C" {
@@ -157,73 +153,42 @@ int pp_vsd_errors(const float* vertices, const int* vert_off, const int* faces, 
         !diameters_host || !cams || !cams_host || !view_obj || !view_img || !poses || !windows || !view_zoff || !view_obj_host ||
         !view_img_host || !windows_host || !view_zoff_host || !taus_host || !workspace || !near_count)
         return PP_EINVAL;
-    if (n_objects <= 0 || n_images <= 0 || n_views <= 0 || n_pairs < 0 || H <= 0 || W <= 0 || (long long)H * W > INT_MAX ||
-        n_taus < 1 || n_taus > PP_VSD_MAX_TAUS || !positive_finite(delta) || !positive_finite(near))
-        return PP_EINVAL;
+    if (n_pairs < 0 || n_taus < 1 || n_taus > PP_VSD_MAX_TAUS || !positive_finite(delta) || !positive_finite(near)) return PP_EINVAL;
     if (n_pairs == 0 && !depth_out) return PP_EINVAL;             // nothing to do
     if (n_pairs > 0 && (!pair_est || !pair_gt || !pair_est_host || !pair_gt_host || !depth || !vsd || !counts)) return PP_EINVAL;
     for (int t = 0; t < n_taus; ++t)
         if (!(taus_host[t] == taus_host[t])) return PP_EINVAL;
-    if (vert_off_host[0] != 0 || face_off_host[0] != 0) return PP_EINVAL;
-    for (int o = 0; o < n_objects; ++o) {
-        if (vert_off_host[o + 1] <= vert_off_host[o] || face_off_host[o + 1] < face_off_host[o]) return PP_EINVAL;
-        if (!positive_finite(diameters_host[o])) return PP_EINVAL;
-        const unsigned nv = (unsigned)(vert_off_host[o + 1] - vert_off_host[o]);
-        for (size_t k = 3 * (size_t)face_off_host[o]; k < 3 * (size_t)face_off_host[o + 1]; ++k)
-            if ((unsigned)faces_host[k] >= nv) return PP_EINVAL;
-    }
-    for (int i = 0; i < n_images; ++i) {
-        const float* k = cams_host + 4 * (size_t)i;
-        if (k[0] == 0.f || k[1] == 0.f || !(fabsf(k[0]) <= 3.402823466e38f) || !(fabsf(k[1]) <= 3.402823466e38f) ||
-            !(fabsf(k[2]) <= 3.402823466e38f) || !(fabsf(k[3]) <= 3.402823466e38f))
-            return PP_EINVAL;
-    }
-    if (view_zoff_host[0] != 0) return PP_EINVAL;
-    long long total_faces = 0;
-    int max_faces = 0;
-    for (int v = 0; v < n_views; ++v) {
-        const int o = view_obj_host[v];
-        if ((unsigned)o >= (unsigned)n_objects || (unsigned)view_img_host[v] >= (unsigned)n_images) return PP_EINVAL;
-        const int nf = face_off_host[o + 1] - face_off_host[o];
-        if (nf <= 0) return PP_EINVAL;                            // an object of the call without faces
-        const int* w = windows_host + 4 * (size_t)v;
-        if (w[0] < 0 || w[1] < 0 || w[2] < w[0] || w[3] < w[1] || w[2] > W || w[3] > H) return PP_EINVAL;
-        if (view_zoff_host[v + 1] - view_zoff_host[v] != (long long)(w[2] - w[0]) * (w[3] - w[1])) return PP_EINVAL;
-        total_faces += nf;
-        max_faces = nf > max_faces ? nf : max_faces;
-    }
-    if (total_faces > (long long)UINT_MAX) return PP_EINVAL;
+    SceneSize n;
+    if (check_scene({vert_off_host, faces_host, face_off_host, diameters_host, n_objects, cams_host, n_images, H, W, view_obj_host,
+                     view_img_host, windows_host, view_zoff_host, n_views}, n) != PP_OK)
+        return PP_EINVAL;
     for (int p = 0; p < n_pairs; ++p) {
         const int e = pair_est_host[p], g = pair_gt_host[p];
         if ((unsigned)e >= (unsigned)n_views || (unsigned)g >= (unsigned)n_views) return PP_EINVAL;
         if (view_obj_host[e] != view_obj_host[g] || view_img_host[e] != view_img_host[g]) return PP_EINVAL;
     }
-    const long long samples = view_zoff_host[n_views];
     size_t need = 0;
-    if (pp_vsd_workspace_bytes(samples, total_faces, &need) != PP_OK) return PP_EINVAL;
+    if (pp_vsd_workspace_bytes(n.samples, n.total_faces, &need) != PP_OK) return PP_EINVAL;
     if (((uintptr_t)workspace % 256) != 0 || workspace_bytes < need) return PP_EWORKSPACE;
 
     hipStream_t st = (hipStream_t)stream;
-    unsigned* qcount = (unsigned*)workspace;
-    unsigned long long* zbuf = (unsigned long long*)((char*)workspace + WS_HEADER);
-    uint2* queue = (uint2*)((char*)zbuf + align256((size_t)samples * 8));
+    const RasterWs ws = carve(workspace, n);
     const Scene s{vertices, vert_off, faces, face_off, cams, view_obj, view_img, poses, windows, view_zoff, n_views, H, W, near};
-    const unsigned gv = (unsigned)(n_views < 65535 ? n_views : 65535);   // (the depth kernel's view stride)
     PP_CHECK_HIP(hipMemsetAsync(near_count, 0, sizeof(unsigned) * (size_t)n_views, st));
-    PP_CHECK_HIP(hipMemsetAsync(qcount, 0, sizeof(unsigned), st));
-    if (samples > 0) PP_CHECK_HIP(hipMemsetAsync(zbuf, 0xFF, (size_t)samples * 8, st));
-    if (samples > 0) launch_raster(s, max_faces, total_faces, zbuf, queue, qcount, near_count, st);
+    const int rc = raster_views(s, n, ws, near_count, st);
+    if (rc != PP_OK) return rc;
     if (depth_out) {
         PP_CHECK_HIP(hipMemsetAsync(depth_out, 0, (size_t)n_views * H * W * sizeof(float), st));
-        if (samples > 0) {
+        if (n.samples > 0) {
             const long long per = ((long long)H * W + BLOCK - 1) / BLOCK;
-            hipLaunchKernelGGL(vsd_depth_kernel, dim3((unsigned)(per < 64 ? per : 64), gv), dim3(BLOCK), 0, st, s, zbuf, depth_out);
+            const unsigned gv = (unsigned)(n_views < 65535 ? n_views : 65535);   // (the kernel's view stride)
+            hipLaunchKernelGGL(vsd_depth_kernel, dim3((unsigned)(per < 64 ? per : 64), gv), dim3(BLOCK), 0, st, s, ws.zbuf, depth_out);
         }
     }
     if (n_pairs > 0) {
         Taus taus;
         for (int t = 0; t < PP_VSD_MAX_TAUS; ++t) taus.v[t] = t < n_taus ? taus_host[t] : INFINITY;
-        hipLaunchKernelGGL(vsd_pair_kernel, dim3((unsigned)n_pairs), dim3(BLOCK), 0, st, s, zbuf, pair_est, pair_gt, diameters, depth,
+        hipLaunchKernelGGL(vsd_pair_kernel, dim3((unsigned)n_pairs), dim3(BLOCK), 0, st, s, ws.zbuf, pair_est, pair_gt, diameters, depth,
                            delta, taus, n_taus, vsd, counts);
     }
     return pp_last_launch();

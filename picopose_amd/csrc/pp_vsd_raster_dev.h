@@ -1,15 +1,18 @@
-// The mixed-object windowed depth raster ("THE DEPTH RASTER" of include/picopose_hip.h): the tables of a call, the view loader and the
-// two raster kernels, shared by pp_vsd.hip (pp_vsd_errors) and pp_depth_refine.hip (pp_depth_refine).  Each translation unit that
-// includes this header gets its own copy of the kernels (internal linkage, no relocatable device code in this build).
+// The mixed-object windowed depth raster ("THE DEPTH RASTER" of include/picopose_hip.h), shared by pp_vsd.hip (pp_vsd_errors) and
+// pp_depth_refine.hip (pp_depth_refine).  Each translation unit that includes this header gets its own copy of the kernels (internal
+// linkage, no relocatable device code in this build).
 //
-//   vsd_raster_small_kernel  one lane per (view, triangle of the view's object): tri_setup under the view's camera and window; a box
-//                            of at most SMALL_BOX samples is walked by the lane, a larger one goes to the queue
-//   vsd_raster_large_kernel  queue entries -> 16 x 16 tiles, one workgroup step per tile (the template renderer's scheme)
+//   vsd_raster_small_kernel  one lane per (view, triangle of the view's object): cover_small under the view's camera and window
+//   vsd_raster_large_kernel  one workgroup row per queue entry: cover_large
+//   check_scene, carve, raster_views (host)  the one validation of the object, camera and view tables, the one layout of
+//                            header | z-buffer | queue, and the clears and launches of a call or of one refinement iteration
 //
-// The z-buffer is ragged: 8 bytes per WINDOW sample, view v at words [view_zoff[v], view_zoff[v + 1]).  Depth is a 64-bit unsigned
-// atomic minimum over (bits of Z) << 32 | face.  Include it AFTER `#pragma clang fp contract(off)`, like pp_raster_dev.h.
+// The kernels are an index mapping and load_view(); the traversal is pp_raster_dev.h's, the template renderer's.  The z-buffer is
+// ragged: 8 bytes per WINDOW sample, view v at words [view_zoff[v], view_zoff[v + 1]).  Include it AFTER `#pragma clang fp
+// contract(off)`, like pp_raster_dev.h.
 #ifndef PP_VSD_RASTER_DEV_H
 #define PP_VSD_RASTER_DEV_H
+#include "pp_common.h"
 #include "pp_raster_dev.h"
 
 namespace {
@@ -33,14 +36,6 @@ struct Scene {
     const int* active = nullptr;   // (n_views) or null: a view with active[v] == 0 renders nothing; null: every view is active
 };
 
-struct View {
-    const float* verts;
-    const int* faces;
-    const float* pose;
-    int Nv, Nf, x0, y0, ww;
-    Cam cam;
-};
-
 // false: the view's window is empty or the view is not active, nothing is rendered
 __device__ __forceinline__ bool load_view(const Scene& s, int v, View& out) {
     if (s.active && s.active[v] == 0) return false;
@@ -50,20 +45,9 @@ __device__ __forceinline__ bool load_view(const Scene& s, int v, View& out) {
     const int o = s.view_obj[v];
     const float* k = s.cams + 4 * (size_t)s.view_img[v];
     const int v0 = s.vert_off[o], f0 = s.face_off[o];
-    out.verts = s.verts + 3 * (size_t)v0;
-    out.Nv = s.vert_off[o + 1] - v0;
-    out.faces = s.faces + 3 * (size_t)f0;
-    out.Nf = s.face_off[o + 1] - f0;
-    out.pose = s.poses + 16 * (size_t)v;
-    out.x0 = x0;
-    out.y0 = y0;
-    out.ww = x1 - x0;
-    out.cam = Cam{k[0], k[1], k[2], k[3], s.near, s.H, s.W, x0, y0, x1, y1};
+    out = View{s.verts + 3 * (size_t)v0, s.faces + 3 * (size_t)f0, s.poses + 16 * (size_t)v, s.vert_off[o + 1] - v0, s.face_off[o + 1] - f0,
+               x0, y0, x1 - x0, Cam{k[0], k[1], k[2], k[3], s.near, s.H, s.W, x0, y0, x1, y1}};
     return true;
-}
-
-__device__ __forceinline__ unsigned long long* slot_of(unsigned long long* zv, const View& vw, int px, int py) {
-    return zv + (size_t)(py - vw.y0) * vw.ww + (px - vw.x0);
 }
 
 // view blockIdx.y, blockIdx.y + gridDim.y, ...; faces blockIdx.x * 256 + lane of that view's object
@@ -73,18 +57,7 @@ __global__ __launch_bounds__(RASTER_BLOCK) void vsd_raster_small_kernel(Scene s,
     const int f = blockIdx.x * RASTER_BLOCK + threadIdx.x;
     for (int v = blockIdx.y; v < s.n_views; v += gridDim.y) {
         View vw;
-        if (!load_view(s, v, vw) || f >= vw.Nf) continue;
-        Tri t;
-        const int st = tri_setup(vw.verts, vw.faces, vw.Nv, vw.pose, vw.cam, f, t);
-        if (st == TRI_NEAR) atomicAdd(near_count + v, 1u);
-        if (st != TRI_OK) continue;
-        if ((t.bx1 - t.bx0 + 1) * (long long)(t.by1 - t.by0 + 1) > SMALL_BOX) {
-            queue[atomicAdd(qcount, 1u)] = make_uint2((unsigned)v, (unsigned)f);
-            continue;
-        }
-        unsigned long long* zv = zbuf + s.view_zoff[v];
-        for (int py = t.by0; py <= t.by1; ++py)
-            for (int px = t.bx0; px <= t.bx1; ++px) depth_test(t, px, py, f, slot_of(zv, vw, px, py));
+        if (load_view(s, v, vw) && f < vw.Nf) cover_small(vw, v, f, zbuf + s.view_zoff[v], queue, qcount, near_count + v);
     }
 }
 
@@ -93,34 +66,97 @@ __global__ __launch_bounds__(TILE * TILE) void vsd_raster_large_kernel(Scene s, 
                                                                        const uint2* __restrict__ queue,
                                                                        const unsigned* __restrict__ qcount) {
     const unsigned n = *qcount;
-    const int ty = threadIdx.x / TILE, tx = threadIdx.x % TILE;
     for (unsigned e = blockIdx.y; e < n; e += gridDim.y) {
         const uint2 q = queue[e];
-        if (q.x >= (unsigned)s.n_views) continue;
         View vw;
-        if (!load_view(s, (int)q.x, vw) || q.y >= (unsigned)vw.Nf) continue;
-        Tri t;
-        if (tri_setup(vw.verts, vw.faces, vw.Nv, vw.pose, vw.cam, (int)q.y, t) != TRI_OK) continue;
-        unsigned long long* zv = zbuf + s.view_zoff[q.x];
-        const int ntx = (t.bx1 - t.bx0) / TILE + 1, nty = (t.by1 - t.by0) / TILE + 1;
-        for (int tile = blockIdx.x; tile < ntx * nty; tile += gridDim.x) {
-            const int x0 = t.bx0 + (tile % ntx) * TILE, y0 = t.by0 + (tile / ntx) * TILE;
-            const int x1 = min(x0 + TILE - 1, t.bx1), y1 = min(y0 + TILE - 1, t.by1);
-            if (tile_outside(t, x0, y0, x1, y1)) continue;
-            const int px = x0 + tx, py = y0 + ty;
-            if (px <= x1 && py <= y1) depth_test(t, px, py, (int)q.y, slot_of(zv, vw, px, py));
-        }
+        if (q.x < (unsigned)s.n_views && load_view(s, (int)q.x, vw)) cover_large(vw, q.y, zbuf + s.view_zoff[q.x]);
     }
 }
 
-// the raster of every view of `s` into the (cleared) z-buffer: the two launches of a call or of one refinement iteration
-inline void launch_raster(const Scene& s, int max_faces, long long total_faces, unsigned long long* zbuf, uint2* queue, unsigned* qcount,
-                          unsigned* near_count, hipStream_t st) {
+inline size_t align256(size_t n) { return (n + 255) / 256 * 256; }
+
+__host__ __device__ inline bool finite32(float v) { return fabsf(v) <= 3.402823466e38f; }
+inline bool positive_finite(float v) { return v > 0.f && finite32(v); }
+
+// the host copies of the tables of a call, as the entries receive them
+struct SceneHost {
+    const int* vert_off;
+    const int* faces;
+    const int* face_off;
+    const float* diameters;
+    int n_objects;
+    const float* cams;
+    int n_images, H, W;
+    const int* view_obj;
+    const int* view_img;
+    const int* windows;
+    const long long* view_zoff;
+    int n_views;
+};
+
+struct SceneSize {
+    long long total_faces;     // over the views: the queue's capacity
+    int max_faces;             // of one view
+    long long samples;         // z-buffer words
+};
+
+// The counts and every table of `h` (no pointer of it is null): offsets, face indices, diameters, cameras, the views' objects and
+// images, windows inside the frame and the z-buffer offsets that follow from them.  PP_OK or PP_EINVAL; nothing touches the device.
+inline int check_scene(const SceneHost& h, SceneSize& out) {
+    if (h.n_objects <= 0 || h.n_images <= 0 || h.n_views <= 0 || h.H <= 0 || h.W <= 0 || (long long)h.H * h.W > INT_MAX) return PP_EINVAL;
+    if (h.vert_off[0] != 0 || h.face_off[0] != 0) return PP_EINVAL;
+    for (int o = 0; o < h.n_objects; ++o) {
+        if (h.vert_off[o + 1] <= h.vert_off[o] || h.face_off[o + 1] < h.face_off[o]) return PP_EINVAL;
+        if (!positive_finite(h.diameters[o])) return PP_EINVAL;
+        const unsigned nv = (unsigned)(h.vert_off[o + 1] - h.vert_off[o]);
+        for (size_t k = 3 * (size_t)h.face_off[o]; k < 3 * (size_t)h.face_off[o + 1]; ++k)
+            if ((unsigned)h.faces[k] >= nv) return PP_EINVAL;
+    }
+    for (int i = 0; i < h.n_images; ++i) {
+        const float* k = h.cams + 4 * (size_t)i;
+        if (k[0] == 0.f || k[1] == 0.f || !finite32(k[0]) || !finite32(k[1]) || !finite32(k[2]) || !finite32(k[3])) return PP_EINVAL;
+    }
+    if (h.view_zoff[0] != 0) return PP_EINVAL;
+    out = SceneSize{0, 0, 0};
+    for (int v = 0; v < h.n_views; ++v) {
+        const int o = h.view_obj[v];
+        if ((unsigned)o >= (unsigned)h.n_objects || (unsigned)h.view_img[v] >= (unsigned)h.n_images) return PP_EINVAL;
+        const int nf = h.face_off[o + 1] - h.face_off[o];
+        if (nf <= 0) return PP_EINVAL;                            // an object of the call without faces
+        const int* w = h.windows + 4 * (size_t)v;
+        if (w[0] < 0 || w[1] < 0 || w[2] < w[0] || w[3] < w[1] || w[2] > h.W || w[3] > h.H) return PP_EINVAL;
+        if (h.view_zoff[v + 1] - h.view_zoff[v] != (long long)(w[2] - w[0]) * (w[3] - w[1])) return PP_EINVAL;
+        out.total_faces += nf;
+        out.max_faces = nf > out.max_faces ? nf : out.max_faces;
+    }
+    if (out.total_faces > (long long)UINT_MAX) return PP_EINVAL;
+    out.samples = h.view_zoff[h.n_views];
+    return PP_OK;
+}
+
+// the front of a workspace: header (the queue counter) | z-buffer, padded to 256 bytes | queue, one slot per (view, triangle)
+struct RasterWs {
+    unsigned* qcount;
+    unsigned long long* zbuf;
+    uint2* queue;
+};
+
+inline RasterWs carve(void* workspace, const SceneSize& n) {
+    char* zbuf = (char*)workspace + WS_HEADER;
+    return RasterWs{(unsigned*)workspace, (unsigned long long*)zbuf, (uint2*)(zbuf + align256((size_t)n.samples * 8))};
+}
+
+// the raster of every view of `s`: queue and z-buffer clears and the two launches of a call or of one refinement iteration
+inline int raster_views(const Scene& s, const SceneSize& n, const RasterWs& ws, unsigned* near_count, hipStream_t st) {
+    PP_CHECK_HIP(hipMemsetAsync(ws.qcount, 0, sizeof(unsigned), st));
+    if (n.samples == 0) return PP_OK;
+    PP_CHECK_HIP(hipMemsetAsync(ws.zbuf, 0xFF, (size_t)n.samples * 8, st));
     const unsigned gv = (unsigned)(s.n_views < 65535 ? s.n_views : 65535);
-    hipLaunchKernelGGL(vsd_raster_small_kernel, dim3((unsigned)((max_faces + RASTER_BLOCK - 1) / RASTER_BLOCK), gv), dim3(RASTER_BLOCK), 0,
-                       st, s, zbuf, queue, qcount, near_count);
-    const unsigned gy = (unsigned)(total_faces < 4096 ? total_faces : 4096);
-    hipLaunchKernelGGL(vsd_raster_large_kernel, dim3(8, gy), dim3(TILE * TILE), 0, st, s, zbuf, queue, qcount);
+    hipLaunchKernelGGL(vsd_raster_small_kernel, dim3((unsigned)((n.max_faces + RASTER_BLOCK - 1) / RASTER_BLOCK), gv), dim3(RASTER_BLOCK),
+                       0, st, s, ws.zbuf, ws.queue, ws.qcount, near_count);
+    const unsigned gy = (unsigned)(n.total_faces < 4096 ? n.total_faces : 4096);
+    hipLaunchKernelGGL(vsd_raster_large_kernel, dim3(8, gy), dim3(TILE * TILE), 0, st, s, ws.zbuf, ws.queue, ws.qcount);
+    return PP_OK;
 }
 
 }  // namespace

@@ -254,3 +254,46 @@ def test_depth_refine_abi_argument_validation_needs_no_gpu():
                {"soff_h": i32(0, 2, 4, 5)}, {"soff_h": i32(0, 1, 3, 3)}, {"soff_h": i32(1, 3, 5, 5)}):
         assert call(**kw) == -1, kw
     assert call(ws_bytes=256 + 1792 + 256 + 4 * 232 - 1) == -2 and call(ws=p + 64) == -2 and call(ws_bytes=0) == -2      # PP_EWORKSPACE
+
+
+def test_scene_tables_get_the_same_code_from_pp_vsd_errors_and_pp_depth_refine_needs_no_gpu():
+    """The object, camera and view tables are validated once for the two entries: each malformed table below, with everything else
+    well formed, gets PP_EINVAL from both, and a workspace one byte short or misaligned PP_EWORKSPACE from both."""
+    from picopose_amd import _lib
+
+    L = _lib.lib()
+    buf = (ctypes.c_char * 16384)()
+    p = ctypes.addressof(buf) + (-ctypes.addressof(buf)) % 256
+    arr = lambda ty, *v: (ty * len(v))(*v)  # noqa: E731
+    i32, f32, i64 = (lambda *v: arr(ctypes.c_int, *v)), (lambda *v: arr(ctypes.c_float, *v)), (lambda *v: arr(ctypes.c_longlong, *v))
+    nan, inf = float("nan"), float("inf")
+    scene = dict(vert_off_h=i32(0, 4, 7), faces_h=i32(0, 1, 2, 0, 2, 3, 0, 1, 2), face_off_h=i32(0, 2, 3), diam_h=f32(100.0, 50.0),
+                 cams_h=f32(100, 100, 32, 24, 90, 95, 30, 20), view_obj_h=i32(0, 0, 1), view_img_h=i32(0, 0, 1),
+                 windows_h=i32(0, 0, 10, 10, 54, 38, 64, 48, 5, 5, 5, 9), zoff_h=i64(0, 100, 200, 200), ws=p, short=0)
+    vsd_ws, refine_ws = 256 + 1792 + 5 * 8, 256 + 1792 + 256 + 4 * 232
+
+    def both(**kw):
+        s = dict(scene, **kw)
+        vsd = L.pp_vsd_errors(p, p, p, p, p, s["vert_off_h"], s["faces_h"], s["face_off_h"], s["diam_h"], 2, p, s["cams_h"], 2, 48, 64, p, p, p, p,
+                              p, s["view_obj_h"], s["view_img_h"], s["windows_h"], s["zoff_h"], 3, p, p, i32(0, 2), i32(1, 2), 2, p, 15.0,
+                              f32(0.1, 0.2), 2, 1.0, s["ws"], vsd_ws - s["short"], p, p, p, None, None)
+        refine = L.pp_depth_refine(p, p, p, p, p, p, s["vert_off_h"], s["faces_h"], s["face_off_h"], s["diam_h"],
+                                   f32(-1, -1, -1, 1, 1, 1, 0, 0, 0, 2, 2, 0), 2, p, s["cams_h"], 2, 48, 64, p, p, p + 4096, p, p, p, s["view_obj_h"],
+                                   s["view_img_h"], s["windows_h"], s["zoff_h"], i32(0, 2, 4, 4), 3, p, 10, 100.0, 1000, 0.1, 1e-6, 1e-2, 100.0,
+                                   0.5, 1.0, s["ws"], refine_ws - s["short"], p, p, p, p, p, p, p, p, p, None, None, None)
+        return vsd, refine
+
+    # (the well-formed call would launch: it is never sent; every call below differs from it in one table or in the workspace)
+    cases = {"vert_off[0] != 0": {"vert_off_h": i32(1, 4, 7)}, "non-increasing vert_off": {"vert_off_h": i32(0, 4, 4)},
+             "face index == vertex count": {"faces_h": i32(0, 1, 2, 0, 2, 4, 0, 1, 2)}, "diameter 0": {"diam_h": f32(100.0, 0.0)},
+             "diameter inf": {"diam_h": f32(inf, 50.0)}, "diameter NaN": {"diam_h": f32(100.0, nan)},
+             "fx == 0": {"cams_h": f32(0, 100, 32, 24, 90, 95, 30, 20)}, "non-finite cx": {"cams_h": f32(100, 100, 32, 24, 90, 95, inf, 20)},
+             "view_obj out of range": {"view_obj_h": i32(0, 2, 1)}, "view_img out of range": {"view_img_h": i32(0, -1, 1)},
+             "an object of the call without faces": {"face_off_h": i32(0, 3, 3)},
+             "x1 > W": {"windows_h": i32(0, 0, 10, 10, 55, 38, 65, 48, 5, 5, 5, 9)},
+             "inverted window": {"windows_h": i32(0, 0, 10, 10, 54, 38, 64, 48, 6, 5, 5, 9)},
+             "view_zoff[0] != 0": {"zoff_h": i64(1, 101, 201, 201)}, "view_zoff step is not the area": {"zoff_h": i64(0, 100, 200, 201)}}
+    assert len(cases) == 15
+    for name, kw in cases.items():
+        assert both(**kw) == (-1, -1), name                                   # PP_EINVAL
+    assert both(short=1) == (-2, -2) and both(ws=p + 8) == (-2, -2)          # PP_EWORKSPACE: one byte short, misaligned by 8
