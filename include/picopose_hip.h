@@ -1181,6 +1181,68 @@ int pp_depth_refine(const float* vertices, const int* vert_off, const int* faces
                     int* active, int* status, int* n_iterations, int* rank, int* n_points, float* rms_before, float* rms_after,
                     unsigned int* near_count, float* trajectory, double* sums, void* stream);
 
+/* -------------------------------------------------------------------------
+ * SCENE GROUND TRUTH: per ground-truth view the pixel counts, boxes and masks of BOP's scene_gt_info.json, mask and mask_visib, and per
+ * image the composite of its views (picopose_amd/scene_gt.py plans every call; tests/scene_gt_oracle.py restates this text in numpy).
+ * This is the BOP toolkit's calc_gt_info / calc_gt_masks WRITTEN FROM MEMORY: the toolkit cannot be run next to this library, so
+ * parity with its pixels is UNPINNED.  Known places where it can differ: its renderer's sampling convention (here pixel centres at
+ * integer coordinates, raster contract item 2), its geometric near-plane clipping (here a triangle with a vertex at Zc <= near is
+ * dropped whole and counted), and its box convention (here boxes are INCLUSIVE corners; scene_gt.format_gt_info turns them into
+ * the file's [x, y, w, h]).  Millimetres throughout.
+ *
+ * THE CANVAS.  A frame is H x W with camera (fx, fy, cx, cy).  Views are rasterised on a canvas of (H + 2 pad_y) x (W + 2 pad_x)
+ * samples whose camera is (fx, fy, f32(cx + pad_x), f32(cy + pad_y)): the sums are taken in float32 and rounded once.  Items 1-5 and 7
+ * of THE RASTER CONTRACT and the Z of item 6 apply with the canvas as the frame (THE DEPTH RASTER of the VSD block); windows are
+ * planned on, and clipped to, the canvas.  Canvas sample (xc, yc) is frame pixel (x, y) = (xc - pad_x, yc - pad_y), IN-FRAME iff
+ * 0 <= x < W and 0 <= y < H.  pad = (0, 0) gives the bits of a pp_vsd_errors depth render.  A padded render does NOT in general:
+ * the principal point changes the float32 projection (shifting cx by W changes one of the twelve ground-truth views of
+ * tests/vsd_oracle.py's mixed scene).  The toolkit's own canvas, from memory, is pad = (W, H).
+ *
+ * PER VIEW, with Z the view's render and Z_test the test depth of its image, "missing" where Z_test > 0 is false:
+ *   px_count_all   = #{canvas samples with Z > 0}
+ *   px_count_valid = #{in-frame samples with Z > 0 and Z_test > 0}
+ *   visible        = in-frame and Z > 0 and (missing or D - D_test <= delta), with D = Z r, D_test = Z_test r,
+ *                    xr = ((float) x - cx) / fx, yr = ((float) y - cy) / fy, r = sqrtf((xr xr + yr yr) + 1) from the FRAME pixel and
+ *                    the FRAME camera; float32, one rounding per operation, never contracted: visib_gt of the VSD block, operation
+ *                    for operation
+ *   px_count_visib = #{visible samples}
+ *   bbox_obj       = inclusive corners {x_min, y_min, x_max, y_max} of the samples with Z > 0, in FRAME coordinates (they may be negative
+ *                    or reach past the frame);  bbox_visib = the same of the visible samples;  an empty set gives {0, 0, -1, -1}.
+ *
+ * THE COMPOSITE.  Per frame pixel the minimum of (bits of Z_v) << 32 | v over the views v of that image that cover it, v the view's
+ * index in the call: scene_depth = that Z (background 0), instance_map = view_label[v] (v itself without the table; background -1);
+ * on equal depth the lower v wins.  Without a test depth (depth = NULL) Z_test := scene_depth: nothing is missing where a model
+ * covers, and an instance is hidden exactly by the other instances of its image; delta = 0 is then exact mutual occlusion.
+ * The composite runs when scene_depth or instance_map is asked for or depth is NULL.
+ *
+ * DETERMINISM.  Counts are integer sums (three counters and eight extrema per lane, xor-shuffles within a wave, LDS across the four
+ * waves, then integer atomicAdd / atomicMin / atomicMax per workgroup of a view), the composite is a 64-bit integer atomic minimum;
+ * there is no floating-point atomic.  Every output is the same bits for any stream, view order, window, and grouping of the views
+ * over calls (the map: up to the tie rule, which is stated on the call's view order).
+ *
+ * Objects, views, windows (on the canvas) and view_zoff are the tables of pp_vsd_errors.  cams (n_images, 4): the FRAME cameras;
+ * canvas_cams (n_images, 4): the canvas cameras, which must be the float32 sums above.  depth (n_images, H, W) fp32 mm or NULL.
+ * view_label (n_views) int32, used when use_view_label != 0.  Outputs (device): counts (n_views, 3) int32 = {all, valid, visib};
+ * boxes (n_views, 8) int32 = bbox_obj, bbox_visib; near_count (n_views) uint32 (zeroed here).  Optional (NULL: off): mask_all,
+ * mask_visib (n_views, H, W) uint8, 0 / 255, in-frame only, mask_all = Z > 0 (zeroed here); scene_depth (n_images, H, W) fp32;
+ * instance_map (n_images, H, W) int32.
+ * Workspace (256-byte aligned): pp_scene_gt_workspace_bytes(window_samples, view_faces, composite_pixels) = the header, z-buffer and
+ * queue of pp_vsd_workspace_bytes, and when composite_pixels = n_images H W > 0 (the composite runs) that rounded up to 256 plus
+ * 8 composite_pixels.  All work is enqueued on `stream`; nothing synchronises.
+ * PP_EINVAL (before any device call): every case of pp_vsd_errors that applies, with the canvas as the frame (so a canvas of 2^31
+ * samples or more); a needed pointer that is null; pad_x or pad_y < 0; delta negative or not finite; near not positive and finite;
+ * a canvas camera that is not the stated sum; use_view_label with view_label NULL.  PP_EWORKSPACE: as pp_vsd_errors.
+ * ------------------------------------------------------------------------- */
+int pp_scene_gt_workspace_bytes(long long window_samples, long long view_faces, long long composite_pixels, size_t* bytes);
+int pp_scene_gt(const float* vertices, const int* vert_off, const int* faces, const int* face_off, const int* vert_off_host,
+                const int* faces_host, const int* face_off_host, const float* diameters_host, int n_objects, const float* cams,
+                const float* cams_host, const float* canvas_cams, const float* canvas_cams_host, int n_images, int H, int W, int pad_x,
+                int pad_y, const int* view_obj, const int* view_img, const float* poses, const int* windows, const long long* view_zoff,
+                const int* view_obj_host, const int* view_img_host, const int* windows_host, const long long* view_zoff_host, int n_views,
+                const float* depth, float delta, float near, const int* view_label, int use_view_label, void* workspace,
+                size_t workspace_bytes, int* counts, int* boxes, unsigned int* near_count, unsigned char* mask_all,
+                unsigned char* mask_visib, float* scene_depth, int* instance_map, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

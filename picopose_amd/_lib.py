@@ -234,6 +234,8 @@ def lib():
         L.pp_depth_refine_workspace_bytes.argtypes = [ll, ll, ll, c.POINTER(sz)]
         L.pp_depth_refine.argtypes = ([vp] * 11 + [i32, vp, vp, i32, i32, i32] + [vp] * 11 + [i32, vp, i32, f32, i32] + [f32] * 6 +
                                       [vp, sz] + [vp] * 12)
+        L.pp_scene_gt_workspace_bytes.argtypes = [ll, ll, ll, c.POINTER(sz)]
+        L.pp_scene_gt.argtypes = ([vp] * 8 + [i32] + [vp] * 4 + [i32] * 5 + [vp] * 9 + [i32, vp, f32, f32, vp, i32, vp, sz] + [vp] * 8)
         _lib = L
     return _lib
 

@@ -322,7 +322,9 @@ def assemble_training_batch(samples, img_size=224, augment_real=True, augment_te
     """Collated training batch of B decoded pairs -> end_points with the reference's keys (training_dataset.py:152-167):
     real_/tem_ full_depth (B,H,W), rgb (B,3,S,S), bbox (B,4), mask (B,S,S), M (B,3,3), K (B,3,3), pose (B,4,4), all fp32
     on `device`.  Each sample is a dict of decoded arrays:
-      rgb (H,W,3) uint8 as load_im gives it, mask (H,W) visible mask, depth (H,W) uint16, depth_scale, K (3,3), cam_R_m2c (9),
+      rgb (H,W,3) uint8 as load_im gives it, mask (H,W) visible mask (a dataset's mask_visib entry, or for a scene that has only
+      scene_gt.json: picopose_amd.scene_gt.scene_gt_info(..., masks="visib")["mask_visib"], whose counts and visib_fract are also
+      the instance filter of training_dataset.py:178), depth (H,W) uint16, depth_scale, K (3,3), cam_R_m2c (9),
       cam_t_m2c (3) in mm; tem_rgba (Ht,Wt,4) uint8, tem_depth (Ht,Wt) uint16 (PNG values), tem_pose (4,4) as stored
       (t in template units), templates_K (optional, the reference's by default).
     All real frames share one shape, all templates another.  `generator` (numpy Generator) draws the box ratios
