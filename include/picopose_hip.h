@@ -1243,6 +1243,59 @@ int pp_scene_gt(const float* vertices, const int* vert_off, const int* faces, co
                 size_t workspace_bytes, int* counts, int* boxes, unsigned int* near_count, unsigned char* mask_all,
                 unsigned char* mask_visib, float* scene_depth, int* instance_map, void* stream);
 
+/* -------------------------------------------------------------------------
+ * MODEL INFO: what a models_info.json entry needs from the vertices alone (picopose_amd/model_info.py plans every call;
+ * tests/model_info_oracle.py restates this text in numpy; every output equals it bit for bit).  Two all-pairs measurements:
+ * the BOP diameter — the largest distance between two vertices, with the pair that attains it — and the directed Hausdorff distance
+ * of a vertex set under candidate rigid transforms, which is what a symmetry search measures.  The search itself (which
+ * transforms to try, what passes) is the host's; these entries only measure.  Millimetres throughout.
+ *
+ * THE ARITHMETIC.  float32, one rounding per operation, never contracted, in the order written:
+ *  1. the squared distance of two points p, q, in difference form: dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z,
+ *     d2 = (dx dx + dy dy) + dz dz.
+ *  2. pp_model_diameter, per object with vertices v_0 .. v_(n-1): d2max = the maximum over the pairs i < j of d2(v_i, v_j); pair =
+ *     the lexicographically lowest (i, j), indices LOCAL to the object, among the pairs that attain it.  One vertex: d2max = 0,
+ *     pair = (0, 0).  The square root is the caller's (model_info.py takes it in float64 from the two vertices of the pair).
+ *  3. a point under a candidate T (12 floats: R row-major, then t — the layout of the composed maps of pp_pose_errors):
+ *     X = ((T0 x + T1 y) + T2 z) + T9, Y = ((T3 x + T4 y) + T5 z) + T10, Z = ((T6 x + T7 y) + T8 z) + T11 (item 2 of that block).
+ *  4. pp_transform_hausdorff, per candidate c of object o: h[c] = sqrtf(max over x in query(o) of min over y in full(o) of
+ *     d2(T_c(x), y)), the minimum by fminf from +inf, the maximum by fmaxf from 0; y is NOT transformed.  The distance is DIRECTED
+ *     (query under T towards the full set): the caller asks for T and for its inverse when it wants the symmetric one.
+ * A maximum, a minimum and an index tie rule do not depend on the order of evaluation: every output is the same bits for any stream,
+ * object order, candidate order and any split of the candidates over calls.  No atomics.
+ *
+ * THE WORK.  Tiles of PP_MODEL_INFO_TILE = 1024 points, 4 per lane of a 256-lane workgroup held in registers (lane l holds points
+ * l, l + 256, l + 512, l + 768 of its tile); the other side goes through LDS 256 points at a time.  Diameter: one workgroup per
+ * (object, i-tile, range of 2 j-tiles at or beyond the i-tile), so only the upper triangle is visited; every lane keeps its best
+ * (d2, i, j), the lanes combine by xor-shuffles 32 .. 1, the waves through LDS, the workgroups of an object in a finalize launch, all
+ * with the tie rule of item 2.  Hausdorff: one workgroup per (candidate, query tile), then one finalize lane per candidate.
+ *
+ * vertices: every object's (Nv, 3) fp32 vertices concatenated, object o at rows [vert_off[o], vert_off[o + 1]), as
+ * evaluation.ObjectModels lays them out; q_vertices / q_off: the query sets alike (e.g. a sub-sample; it may be the same buffers).
+ * The *_off tables (n_objects + 1 ints) are device pointers, *_off_host their HOST copies, validated here.
+ * pp_model_diameter: d2max (n_objects) fp32, pair (n_objects, 2) int32, device.  Workspace (256-byte aligned):
+ * pp_model_diameter_workspace_bytes(vert_off_host, n_objects) = roundup256(4 (n_objects + 1)) + roundup256(16 work items), an object
+ * of T tiles having T ceil(T / 2) work items.
+ * pp_transform_hausdorff: cand_obj (n_candidates) int32 object index per candidate, device, cand_obj_host its HOST copy; cand_T
+ * (n_candidates, 12) fp32, device; h (n_candidates) fp32, device.  Workspace (256-byte aligned):
+ * pp_transform_hausdorff_workspace_bytes(n_candidates, max_query_vertices) = roundup256(4 n_candidates ceil(max_query_vertices /
+ * 1024)), max_query_vertices the largest query set among the objects of the call's candidates; a caller with a bound on its workspace
+ * splits the candidates into consecutive groups, one call each, with identical results.
+ * All work is enqueued on `stream`; nothing synchronises.
+ * PP_EINVAL (before any device call): a null pointer; n_objects <= 0 (pp_model_diameter: or > 65535); n_candidates <= 0; an offset table that does not
+ * start at 0 or does not increase (an object without vertices); a cand_obj_host entry outside [0, n_objects); more than 2^31 - 1
+ * diameter work items; a query set of more than 65535 tiles.  PP_EWORKSPACE: workspace misaligned or smaller than stated.
+ * ------------------------------------------------------------------------- */
+#define PP_MODEL_INFO_TILE 1024
+int pp_model_diameter_workspace_bytes(const int* vert_off_host, int n_objects, size_t* bytes);
+int pp_model_diameter(const float* vertices, const int* vert_off, const int* vert_off_host, int n_objects, void* workspace,
+                      size_t workspace_bytes, float* d2max, int* pair, void* stream);
+int pp_transform_hausdorff_workspace_bytes(int n_candidates, int max_query_vertices, size_t* bytes);
+int pp_transform_hausdorff(const float* vertices, const int* vert_off, const float* q_vertices, const int* q_off,
+                           const int* vert_off_host, const int* q_off_host, int n_objects, const int* cand_obj,
+                           const int* cand_obj_host, const float* cand_T, int n_candidates, void* workspace, size_t workspace_bytes,
+                           float* h, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

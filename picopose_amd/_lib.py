@@ -236,6 +236,10 @@ def lib():
                                       [vp, sz] + [vp] * 12)
         L.pp_scene_gt_workspace_bytes.argtypes = [ll, ll, ll, c.POINTER(sz)]
         L.pp_scene_gt.argtypes = ([vp] * 8 + [i32] + [vp] * 4 + [i32] * 5 + [vp] * 9 + [i32, vp, f32, f32, vp, i32, vp, sz] + [vp] * 8)
+        L.pp_model_diameter_workspace_bytes.argtypes = [vp, i32, c.POINTER(sz)]
+        L.pp_model_diameter.argtypes = [vp, vp, vp, i32, vp, sz, vp, vp, vp]
+        L.pp_transform_hausdorff_workspace_bytes.argtypes = [i32, i32, c.POINTER(sz)]
+        L.pp_transform_hausdorff.argtypes = [vp] * 6 + [i32, vp, vp, vp, i32, vp, sz, vp, vp]
         _lib = L
     return _lib
 

@@ -1,0 +1,364 @@
+// Model metadata from the vertices alone: the BOP diameter (the largest vertex-to-vertex distance, with the pair that attains it) and
+// the directed Hausdorff distance of a vertex set under candidate rigid transforms, the measurement behind a symmetry search
+// (picopose_amd/model_info.py plans every call; the contract is stated in include/picopose_hip.h, "MODEL INFO", and restated in numpy by
+// tests/model_info_oracle.py).  Both are all-pairs problems on pp_eval.hip's adds_kernel pattern: a workgroup owns MI_TILE points
+// (MI_EPT per lane, in registers), the other side streams through LDS as broadcast float4s, squared distances in difference form.
+//
+//   diameter_plan_kernel      one lane: the prefix sums of the objects' work counts (tiles x ranges per object)
+//   diameter_kernel           one workgroup per (object, i-tile, range of DIAM_JR j-tiles at or beyond it): only i < j is visited; per
+//                             lane the best (d2, i, j); xor-shuffles inside a wave, the waves through LDS, with the tie rule
+//   diameter_finalize_kernel  one workgroup per object: the same reduction over the object's partial results
+//   hausdorff_kernel          one workgroup per (candidate, query tile): the transformed query points in registers, the full set through
+//                             LDS untransformed, running minimum per query point, then the maximum over the tile
+//   hausdorff_finalize_kernel one lane per candidate: the maximum over its tiles, one square root
+//
+// Maximum and minimum are exact and order-independent and ties are resolved by index: the results do not depend on launch order,
+// stream, object order, candidate order or the grouping of the candidates.  No atomics.
+#include <stdint.h>
+#include <limits.h>
+#include <math.h>
+#include "pp_common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int BLOCK = 256;
+constexpr int WAVES = BLOCK / 64;
+constexpr int MI_TILE = PP_MODEL_INFO_TILE;
+constexpr int MI_EPT = MI_TILE / BLOCK;           // register-side points per lane
+constexpr int MI_LDS = 256;                       // streamed-side points per LDS tile
+constexpr int DIAM_JR = 2;                        // j-tiles per workgroup of diameter_kernel
+static_assert(MI_TILE % BLOCK == 0 && MI_TILE % MI_LDS == 0 && MI_LDS == BLOCK, "tiles");
+
+// X = ((T0 x + T1 y) + T2 z) + T9, ... : pp_eval.hip's apply, one rounding per operation, in this order
+__device__ __forceinline__ void apply(const float* __restrict__ T, float x, float y, float z, float& X, float& Y, float& Z) {
+    X = ((T[0] * x + T[1] * y) + T[2] * z) + T[9];
+    Y = ((T[3] * x + T[4] * y) + T[5] * z) + T[10];
+    Z = ((T[6] * x + T[7] * y) + T[8] * z) + T[11];
+}
+
+__host__ __device__ inline long long diam_work(int nv) {
+    const long long tiles = ((long long)nv + MI_TILE - 1) / MI_TILE;
+    return tiles * ((tiles + DIAM_JR - 1) / DIAM_JR);
+}
+
+__global__ void diameter_plan_kernel(const int* __restrict__ vert_off, int n_objects, int* __restrict__ work_off) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    int at = 0;
+    work_off[0] = 0;
+    for (int o = 0; o < n_objects; ++o) {
+        at += (int)diam_work(vert_off[o + 1] - vert_off[o]);
+        work_off[o + 1] = at;
+    }
+}
+
+// a beats b: the larger squared distance, on a tie the lexicographically lower (i, j)
+__device__ __forceinline__ bool beats(float ad, int ai, int aj, float bd, int bi, int bj) {
+    return ad > bd || (ad == bd && (ai < bi || (ai == bi && aj < bj)));
+}
+
+// the workgroup's best (d2, i, j) in thread 0; sm: 3 * WAVES words
+__device__ __forceinline__ void block_best(float& d, int& i, int& j, int* sm) {
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        const float od = __shfl_xor(d, s, 64);
+        const int oi = __shfl_xor(i, s, 64), oj = __shfl_xor(j, s, 64);
+        if (beats(od, oi, oj, d, i, j)) {
+            d = od;
+            i = oi;
+            j = oj;
+        }
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        sm[3 * wave] = __float_as_int(d);
+        sm[3 * wave + 1] = i;
+        sm[3 * wave + 2] = j;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) {
+            const float od = __int_as_float(sm[3 * w]);
+            const int oi = sm[3 * w + 1], oj = sm[3 * w + 2];
+            if (beats(od, oi, oj, d, i, j)) {
+                d = od;
+                i = oi;
+                j = oj;
+            }
+        }
+    }
+}
+
+// part[w] = {bits of d2, i, j, 0}; d2 = -1: the work item holds no pair
+__global__ __launch_bounds__(BLOCK) void diameter_kernel(const float* __restrict__ verts, const int* __restrict__ vert_off,
+                                                         const int* __restrict__ work_off, int n_objects, int4* __restrict__ part) {
+    const int w = blockIdx.x;
+    int lo = 0, hi = n_objects;                                  // the object o with work_off[o] <= w < work_off[o + 1]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (work_off[mid] <= w) lo = mid; else hi = mid;
+    }
+    const int o = lo;
+    const int v0 = vert_off[o], nv = vert_off[o + 1] - v0;
+    const int tiles = (nv + MI_TILE - 1) / MI_TILE, ranges = (tiles + DIAM_JR - 1) / DIAM_JR;
+    const int local = w - work_off[o];
+    const int ti = local / ranges, tj0 = ti + (local % ranges) * DIAM_JR;
+    if (tj0 >= tiles) {                                          // (uniform: before any barrier)
+        if (threadIdx.x == 0) part[w] = make_int4(__float_as_int(-1.f), 0, 0, 0);
+        return;
+    }
+    const int tj1 = tj0 + DIAM_JR < tiles ? tj0 + DIAM_JR : tiles;
+    const float* vp = verts + 3 * (size_t)v0;
+    float px[MI_EPT], py[MI_EPT], pz[MI_EPT], bd[MI_EPT];
+    int bj[MI_EPT];
+#pragma unroll
+    for (int k = 0; k < MI_EPT; ++k) {
+        const int i = ti * MI_TILE + k * BLOCK + (int)threadIdx.x;
+        const size_t c = (size_t)(i < nv ? i : nv - 1);
+        px[k] = vp[3 * c];
+        py[k] = vp[3 * c + 1];
+        pz[k] = vp[3 * c + 2];
+        bd[k] = -1.f;
+        bj[k] = 0;
+    }
+    __shared__ float4 sh[MI_LDS];
+    const int j_end = tj1 * MI_TILE < nv ? tj1 * MI_TILE : nv;
+    for (int g0 = tj0 * MI_TILE; g0 < j_end; g0 += MI_LDS) {
+        const int cnt = j_end - g0 < MI_LDS ? j_end - g0 : MI_LDS;
+        __syncthreads();
+        if ((int)threadIdx.x < cnt) {
+            const size_t c = (size_t)(g0 + (int)threadIdx.x);
+            sh[threadIdx.x] = make_float4(vp[3 * c], vp[3 * c + 1], vp[3 * c + 2], 0.f);
+        }
+        __syncthreads();
+        // j ascends and the compare is strict: per register-side point the lowest j that attains its maximum is kept
+        if (g0 >= (ti + 1) * MI_TILE) {                          // every j of this tile lies beyond every i of the workgroup
+            for (int q = 0; q < cnt; ++q) {
+                const float4 g = sh[q];
+#pragma unroll
+                for (int k = 0; k < MI_EPT; ++k) {
+                    const float dx = px[k] - g.x, dy = py[k] - g.y, dz = pz[k] - g.z;
+                    const float d2 = (dx * dx + dy * dy) + dz * dz;
+                    if (d2 > bd[k]) {
+                        bd[k] = d2;
+                        bj[k] = g0 + q;
+                    }
+                }
+            }
+        } else {                                                 // the diagonal tile: only j > i counts
+            for (int q = 0; q < cnt; ++q) {
+                const float4 g = sh[q];
+                const int j = g0 + q;
+#pragma unroll
+                for (int k = 0; k < MI_EPT; ++k) {
+                    const float dx = px[k] - g.x, dy = py[k] - g.y, dz = pz[k] - g.z;
+                    const float d2 = (dx * dx + dy * dy) + dz * dz;
+                    if (j > ti * MI_TILE + k * BLOCK + (int)threadIdx.x && d2 > bd[k]) {
+                        bd[k] = d2;
+                        bj[k] = j;
+                    }
+                }
+            }
+        }
+    }
+    // i ascends with k and the compare is strict: the lane's lowest i on a tie; a lane's point past the object's last one holds nothing
+    float d = -1.f;
+    int bi = 0, bjj = 0;
+#pragma unroll
+    for (int k = 0; k < MI_EPT; ++k) {
+        const int i = ti * MI_TILE + k * BLOCK + (int)threadIdx.x;
+        if (i < nv && bd[k] > d) {
+            d = bd[k];
+            bi = i;
+            bjj = bj[k];
+        }
+    }
+    __shared__ int sm[3 * WAVES];
+    block_best(d, bi, bjj, sm);
+    if (threadIdx.x == 0) part[w] = make_int4(__float_as_int(d), bi, bjj, 0);
+}
+
+__global__ __launch_bounds__(BLOCK) void diameter_finalize_kernel(const int* __restrict__ work_off, const int4* __restrict__ part,
+                                                                  float* __restrict__ d2max, int* __restrict__ pair) {
+    const int o = blockIdx.x;
+    const int w0 = work_off[o], w1 = work_off[o + 1];
+    float d = -1.f;
+    int bi = 0, bj = 0;
+    for (int w = w0 + (int)threadIdx.x; w < w1; w += BLOCK) {
+        const int4 p = part[w];
+        const float od = __int_as_float(p.x);
+        if (beats(od, p.y, p.z, d, bi, bj)) {
+            d = od;
+            bi = p.y;
+            bj = p.z;
+        }
+    }
+    __shared__ int sm[3 * WAVES];
+    block_best(d, bi, bj, sm);
+    if (threadIdx.x == 0) {
+        const bool any = d >= 0.f;                               // an object with one vertex has no pair: 0 and (0, 0)
+        d2max[o] = any ? d : 0.f;
+        pair[2 * (size_t)o] = any ? bi : 0;
+        pair[2 * (size_t)o + 1] = any ? bj : 0;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void hausdorff_kernel(const float* __restrict__ verts, const int* __restrict__ vert_off,
+                                                          const float* __restrict__ q_verts, const int* __restrict__ q_off,
+                                                          const int* __restrict__ cand_obj, const float* __restrict__ cand_T,
+                                                          int tiles_max, float* __restrict__ part) {
+    const int c = blockIdx.x, tile = blockIdx.y;
+    const int o = cand_obj[c];
+    const int q0 = q_off[o], nq = q_off[o + 1] - q0;
+    if ((long long)tile * MI_TILE >= nq) return;                 // (uniform: before any barrier)
+    const int v0 = vert_off[o], nv = vert_off[o + 1] - v0;
+    float T[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) T[k] = cand_T[12 * (size_t)c + k];
+    const float* qp = q_verts + 3 * (size_t)q0;
+    const float* vp = verts + 3 * (size_t)v0;
+    float ex[MI_EPT], ey[MI_EPT], ez[MI_EPT], mn[MI_EPT];
+    bool valid[MI_EPT];
+#pragma unroll
+    for (int k = 0; k < MI_EPT; ++k) {
+        const int i = tile * MI_TILE + k * BLOCK + (int)threadIdx.x;
+        valid[k] = i < nq;
+        const size_t a = (size_t)(valid[k] ? i : nq - 1);
+        apply(T, qp[3 * a], qp[3 * a + 1], qp[3 * a + 2], ex[k], ey[k], ez[k]);
+        mn[k] = INFINITY;
+    }
+    __shared__ float4 sh[MI_LDS];
+    for (int g0 = 0; g0 < nv; g0 += MI_LDS) {
+        const int cnt = nv - g0 < MI_LDS ? nv - g0 : MI_LDS;
+        __syncthreads();
+        if ((int)threadIdx.x < cnt) {
+            const size_t a = (size_t)(g0 + (int)threadIdx.x);
+            sh[threadIdx.x] = make_float4(vp[3 * a], vp[3 * a + 1], vp[3 * a + 2], 0.f);
+        }
+        __syncthreads();
+        for (int q = 0; q < cnt; ++q) {
+            const float4 g = sh[q];
+#pragma unroll
+            for (int k = 0; k < MI_EPT; ++k) {
+                const float dx = ex[k] - g.x, dy = ey[k] - g.y, dz = ez[k] - g.z;
+                mn[k] = fminf(mn[k], (dx * dx + dy * dy) + dz * dz);
+            }
+        }
+    }
+    float m = 0.f;
+#pragma unroll
+    for (int k = 0; k < MI_EPT; ++k)
+        if (valid[k]) m = fmaxf(m, mn[k]);
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) m = fmaxf(m, __shfl_xor(m, s, 64));
+    __shared__ float sm[WAVES];
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) m = fmaxf(m, sm[w]);
+        part[(size_t)c * tiles_max + tile] = m;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void hausdorff_finalize_kernel(const int* __restrict__ q_off, const int* __restrict__ cand_obj,
+                                                                   int n_candidates, int tiles_max, const float* __restrict__ part,
+                                                                   float* __restrict__ h) {
+    const int c = blockIdx.x * BLOCK + threadIdx.x;
+    if (c >= n_candidates) return;
+    const int o = cand_obj[c];
+    const int nq = q_off[o + 1] - q_off[o];
+    const int nt = (nq + MI_TILE - 1) / MI_TILE;
+    float m = 0.f;
+    for (int t = 0; t < nt; ++t) m = fmaxf(m, part[(size_t)c * tiles_max + t]);
+    h[c] = sqrtf(m);
+}
+
+inline size_t align256(size_t n) { return (n + 255) / 256 * 256; }
+
+// -> the total work of the objects, or -1: a table that does not start at 0 or does not increase, or too much work for one grid
+inline long long diameter_total_work(const int* vert_off_host, int n_objects) {
+    if (vert_off_host[0] != 0) return -1;
+    long long total = 0;
+    for (int o = 0; o < n_objects; ++o) {
+        if (vert_off_host[o + 1] <= vert_off_host[o]) return -1;
+        total += diam_work(vert_off_host[o + 1] - vert_off_host[o]);
+        if (total > (long long)INT_MAX) return -1;
+    }
+    return total;
+}
+
+inline bool bad_hausdorff_sizes(int n_candidates, int max_query_vertices) {
+    return n_candidates <= 0 || max_query_vertices <= 0 ||
+           ((long long)max_query_vertices + MI_TILE - 1) / MI_TILE > 65535;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pp_model_diameter_workspace_bytes(const int* vert_off_host, int n_objects, size_t* bytes) {
+    if (!vert_off_host || !bytes || n_objects <= 0 || n_objects > 65535) return PP_EINVAL;
+    const long long total = diameter_total_work(vert_off_host, n_objects);
+    if (total < 0) return PP_EINVAL;
+    *bytes = align256(((size_t)n_objects + 1) * sizeof(int)) + align256((size_t)total * sizeof(int4));
+    return PP_OK;
+}
+
+int pp_model_diameter(const float* vertices, const int* vert_off, const int* vert_off_host, int n_objects, void* workspace,
+                      size_t workspace_bytes, float* d2max, int* pair, void* stream) {
+    if (!vertices || !vert_off || !vert_off_host || !workspace || !d2max || !pair || n_objects <= 0 || n_objects > 65535)
+        return PP_EINVAL;
+    const long long total = diameter_total_work(vert_off_host, n_objects);
+    if (total < 0) return PP_EINVAL;
+    const size_t table = align256(((size_t)n_objects + 1) * sizeof(int));
+    if (((uintptr_t)workspace % 256) != 0 || workspace_bytes < table + align256((size_t)total * sizeof(int4))) return PP_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    int* work_off = (int*)workspace;
+    int4* part = (int4*)((char*)workspace + table);
+    hipLaunchKernelGGL(diameter_plan_kernel, dim3(1), dim3(64), 0, st, vert_off, n_objects, work_off);
+    hipLaunchKernelGGL(diameter_kernel, dim3((unsigned)total), dim3(BLOCK), 0, st, vertices, vert_off, work_off, n_objects, part);
+    hipLaunchKernelGGL(diameter_finalize_kernel, dim3(n_objects), dim3(BLOCK), 0, st, work_off, part, d2max, pair);
+    return pp_last_launch();
+}
+
+int pp_transform_hausdorff_workspace_bytes(int n_candidates, int max_query_vertices, size_t* bytes) {
+    if (!bytes || bad_hausdorff_sizes(n_candidates, max_query_vertices)) return PP_EINVAL;
+    const size_t tiles = ((size_t)max_query_vertices + MI_TILE - 1) / MI_TILE;
+    *bytes = align256((size_t)n_candidates * tiles * sizeof(float));
+    return PP_OK;
+}
+
+int pp_transform_hausdorff(const float* vertices, const int* vert_off, const float* q_vertices, const int* q_off,
+                           const int* vert_off_host, const int* q_off_host, int n_objects, const int* cand_obj,
+                           const int* cand_obj_host, const float* cand_T, int n_candidates, void* workspace, size_t workspace_bytes,
+                           float* h, void* stream) {
+    if (!vertices || !vert_off || !q_vertices || !q_off || !vert_off_host || !q_off_host || !cand_obj || !cand_obj_host || !cand_T ||
+        !workspace || !h || n_objects <= 0 || n_candidates <= 0)
+        return PP_EINVAL;
+    if (vert_off_host[0] != 0 || q_off_host[0] != 0) return PP_EINVAL;
+    for (int o = 0; o < n_objects; ++o)
+        if (vert_off_host[o + 1] <= vert_off_host[o] || q_off_host[o + 1] <= q_off_host[o]) return PP_EINVAL;
+    int nq_max = 0;
+    for (int c = 0; c < n_candidates; ++c) {
+        const int o = cand_obj_host[c];
+        if ((unsigned)o >= (unsigned)n_objects) return PP_EINVAL;
+        const int nq = q_off_host[o + 1] - q_off_host[o];
+        nq_max = nq > nq_max ? nq : nq_max;
+    }
+    if (bad_hausdorff_sizes(n_candidates, nq_max)) return PP_EINVAL;
+    const int tiles = (int)(((long long)nq_max + MI_TILE - 1) / MI_TILE);
+    if (((uintptr_t)workspace % 256) != 0 || workspace_bytes < align256((size_t)n_candidates * tiles * sizeof(float)))
+        return PP_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    float* part = (float*)workspace;
+    hipLaunchKernelGGL(hausdorff_kernel, dim3(n_candidates, tiles), dim3(BLOCK), 0, st, vertices, vert_off, q_vertices, q_off, cand_obj,
+                       cand_T, tiles, part);
+    hipLaunchKernelGGL(hausdorff_finalize_kernel, dim3((unsigned)((n_candidates + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, q_off,
+                       cand_obj, n_candidates, tiles, part, h);
+    return pp_last_launch();
+}
+
+}  // extern "C"
