@@ -1296,6 +1296,71 @@ int pp_transform_hausdorff(const float* vertices, const int* vert_off, const flo
                            const int* cand_obj_host, const float* cand_T, int n_candidates, void* workspace, size_t workspace_bytes,
                            float* h, void* stream);
 
+/* -------------------------------------------------------------------------
+ * THE SCENE COMPOSITE: rendered object layers over a background -> the colour frame, 16-bit depth, instance map and per-instance
+ * visibility of a synthetic training scene (csrc/pp_synth.hip; picopose_amd/provider/synth_scenes.py plans every call;
+ * tests/synth_oracle.py restates this text in numpy; every output equals it bit for bit).  A LAYER is one object instance rendered
+ * into a full frame by pp_render_views*: layers_rgba (L, H, W, 4) uint8 and layers_depth (L, H, W) fp32 metres (that entry's
+ * depth_m: 0 on its background).  layer_off (n_images + 1 int32, non-decreasing, device; layer_off_host its HOST copy): the layers of
+ * image i are [layer_off[i], layer_off[i + 1]); an image may have none.
+ *
+ * PER FRAME PIXEL of image i.  Layer l COVERS the pixel when its depth Z_l > 0 is true (a NaN, a negative value and +-0 do not
+ * cover; +inf does).  The coverage test is on depth alone: alpha is never read.  The WINNER is the l of the minimum of
+ * (bits of Z_l) << 32 | l over the covering layers of the image, l the layer's index in the call: the nearest layer, on equal depth
+ * the lower l.  Then
+ *   rgb      (n_images, H, W, 3) uint8  = bytes 0..2 of the winner's layers_rgba pixel, or the background pixel (below);
+ *   depth    (n_images, H, W) uint16    = min(65535, rintf((1000.0f * Z) / depth_scale[i])) of the winner's Z — float32, one rounding
+ *                                         per operation in the order written, never contracted, rintf = round half to even (the
+ *                                         value a depth PNG with the camera's depth_scale would hold) — or 0 on background;
+ *   instance (n_images, H, W) int32     = the winner l, or -1.
+ * PER LAYER l:
+ *   counts (L, 2) int32 = {px_all, px_visib}: the pixels l covers, and the pixels l wins;
+ *   boxes  (L, 4) int32 = inclusive {x_min, y_min, x_max, y_max} of the pixels l wins; none: {0, 0, -1, -1} (as pp_scene_gt);
+ *   mask_visib (L, H, W) uint8 (optional, NULL: off) = 255 where l wins, else 0 (every byte is written).
+ *
+ * THE BACKGROUND.  background (n_images, PP_SYNTH_BG_WORDS) int32 descriptors {mode, a, b, 0} (device; background_host the HOST copy):
+ *   mode 0  a constant: R = a & 255, G = (a >> 8) & 255, B = (a >> 16) & 255;
+ *   mode 1  the pixel of bg_images (n_images, H, W, 3) uint8, image i of the CALL;
+ *   mode 2  a lattice in integer arithmetic: seed = a (its uint32 bits), s = b in 2..7, S = 2^s the cell.  Pixel (x, y):
+ *           gx = x >> s, fx = x & (S - 1), gy = y >> s, fy = y & (S - 1); node (u, v) has the colour bytes 0..2 (channel c = byte c,
+ *           (h >> 8 c) & 255) of h(seed, u, v), h the counter hash of the training-pair assembly block above (one device function,
+ *           csrc/pp_hash_dev.h); channel c of the pixel =
+ *           (n00 (S - fx)(S - fy) + n10 fx (S - fy) + n01 (S - fx) fy + n11 fx fy + 2^(2s-1)) >> 2s, n_uv the byte of node
+ *           (gx + u, gy + v).  At a node (fx = fy = 0) it is the node's colour; elsewhere it lies within the four.
+ * depth_scale (n_images) fp32 (device; depth_scale_host the HOST copy): the camera's depth_scale, millimetres per depth unit.
+ *
+ * DETERMINISM.  The composite is a loop over the image's layers per pixel: no atomics.  counts and boxes are integer sums and integer
+ * extrema: per workgroup (PP_SYNTH_TILE consecutive pixels of one image) ballots and xor-shuffles within a wave and LDS across the four
+ * waves give one record of six integers per layer of the image, written to the workspace; a second launch reduces the records of a
+ * layer in a fixed order.  There is no atomic and no floating-point reduction anywhere.  Every output is the same bits for any
+ * stream, any split of the images over calls and any order of the images (instance and the layer order of the per-layer outputs:
+ * up to the call's layer indices, which the tie rule is stated on).
+ *
+ * Workspace (256-byte aligned; may be NULL when 0 bytes are needed): pp_scene_composite_workspace_bytes(n_layers, H, W) =
+ * roundup256(24 n_layers ceil(H W / PP_SYNTH_TILE)).  All work is enqueued on `stream`; nothing synchronises.
+ * The layers are read with 16-byte loads and the outputs written four pixels per lane when W % 4 == 0 and every buffer is 16-byte
+ * aligned, one pixel per access otherwise; the results do not depend on which.
+ * PP_EINVAL (before any device call): a needed pointer that is null (layers_* with n_layers > 0, layer_off*, background*,
+ * depth_scale*, rgb, depth, instance; counts and boxes with n_layers > 0); n_images, H or W <= 0; n_layers < 0; n_layers H W or
+ * n_images H W >= 2^31; layer_off_host decreasing, not starting at 0 or not ending at n_layers; a depth_scale_host entry that is not
+ * positive and finite; a mode outside 0..2; mode 2 with s outside 2..7; mode 1 with bg_images NULL.  PP_EWORKSPACE: workspace
+ * misaligned or smaller than stated.  n_layers = 0 is legal: every image is its background.
+ *
+ * pp_depth_quantize_u16: out[k] = Z > 0 ? min(65535, rintf(units_per_metre * Z)) : 0 for k < n, Z = depth_m[k] (float32, rintf = round
+ * half to even; not (Z > 0) — background, NaN, negative — gives 0).  The template frames use it with 10000: the 0.1 mm unit of the
+ * template depth files that pp_depth_u16_template reads back.  PP_EINVAL: a null pointer, n < 0, units_per_metre not positive and
+ * finite.  n = 0 launches nothing.
+ * ------------------------------------------------------------------------- */
+#define PP_SYNTH_BG_WORDS 4
+#define PP_SYNTH_TILE 1024
+int pp_scene_composite_workspace_bytes(int n_layers, int H, int W, size_t* bytes);
+int pp_scene_composite(const unsigned char* layers_rgba, const float* layers_depth, const int* layer_off, const int* layer_off_host,
+                       int n_layers, int n_images, int H, int W, const int* background, const int* background_host,
+                       const unsigned char* bg_images, const float* depth_scale, const float* depth_scale_host, void* workspace,
+                       size_t workspace_bytes, unsigned char* rgb, unsigned short* depth, int* instance, int* counts, int* boxes,
+                       unsigned char* mask_visib, void* stream);
+int pp_depth_quantize_u16(const float* depth_m, long long n, float units_per_metre, unsigned short* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -240,6 +240,9 @@ def lib():
         L.pp_model_diameter.argtypes = [vp, vp, vp, i32, vp, sz, vp, vp, vp]
         L.pp_transform_hausdorff_workspace_bytes.argtypes = [i32, i32, c.POINTER(sz)]
         L.pp_transform_hausdorff.argtypes = [vp] * 6 + [i32, vp, vp, vp, i32, vp, sz, vp, vp]
+        L.pp_scene_composite_workspace_bytes.argtypes = [i32, i32, i32, c.POINTER(sz)]
+        L.pp_scene_composite.argtypes = [vp] * 4 + [i32] * 4 + [vp] * 6 + [sz] + [vp] * 7
+        L.pp_depth_quantize_u16.argtypes = [vp, ll, f32, vp, vp]
         _lib = L
     return _lib
 

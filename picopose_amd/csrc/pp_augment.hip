@@ -7,6 +7,7 @@
 // only execute them.  Every op is integer, LUT-free fixed point or float32 with contraction off, so
 // tests/train_batch_oracle.py restates each one bit for bit.
 #include "pp_common.h"
+#include "pp_hash_dev.h"             // aug_mix, aug_hash: the counter-based hash, shared with pp_synth.hip
 
 #pragma clang fp contract(off)
 
@@ -17,19 +18,6 @@ enum : int {
     OP_DROPOUT = 1, OP_BLUR = 2, OP_SHARPNESS = 3, OP_CONTRAST = 4, OP_BRIGHTNESS = 5, OP_COLOR = 6, OP_ADD = 7, OP_INVERT = 8,
     OP_MULTIPLY_PC = 9, OP_MULTIPLY = 10, OP_NOISE = 11, OP_LINEAR_CONTRAST = 12, OP_GRAYSCALE = 13
 };
-
-// counter-based hash (include/picopose_hip.h): keyed by (image seed, pixel or cell, stream), never by thread
-__device__ __forceinline__ unsigned aug_mix(unsigned x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ unsigned aug_hash(unsigned seed, unsigned a, unsigned b) {
-    return aug_mix(seed ^ aug_mix(a ^ aug_mix(b + 0x9e3779b9u)));
-}
 
 __device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 // PIL Image.blend on uint8 (and the LinearContrast LUT): clip(trunc(d + f (v - d))) in float32, one rounding per operation
