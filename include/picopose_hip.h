@@ -590,6 +590,52 @@ int pp_pnp_refine_lm(const double* object_points, const double* image_points, co
                      double* tvec, double* rms_before, double* rms_after, int32_t* lm_iterations, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * RGB-D POSE RECOVERY (picopose_amd/csrc/pp_rgbd_pose.hip; restated in numpy by tests/rgbd_pose_oracle.py)
+ * The correspondences of pp_pnp_ransac, each lifted to a 3D-3D pair by the test depth image, RANSAC over three-point rigid
+ * fits, a rigid refit on the consensus set: a metric pose from one launch, one 512-thread workgroup per problem, no host wait.
+ * This is the project's own algorithm — the project it was modelled on recovers poses from RGB alone — so it is defined by the
+ * contract below, not by parity with anything.
+ *   The first ten arguments are pp_pnp_ransac's (same layouts, N <= 4096).  depth (n_images, dH, dW) fp32 in the length unit
+ *   of src_pts_3d; image_index (P) int32: the depth image each problem reads; inlier_dist (P) fp32: the inlier radius in the
+ *   same unit.  out: rot (P,3,3) f64, tvec (P,3) f64, inlier_ratio (P) f64, success, num_points, num_listed (P) int32,
+ *   rms (P) f64, inlier_mask (P, N) uint8 or null.
+ * Gather.  The entries of tar_pts / src_pts with no -1, in list order, and the object-frame source point (X - t_tem) @ R_tem
+ *   in fp32, exactly as pp_pnp_ransac walks and forms them; num_listed is their count (at most 4096).  For each, (u, v) is the
+ *   fp32 pair of tar_pts_2d and the pixel is (xi, yi) = (floor(u + 0.5), floor(v + 0.5)), evaluated in fp32.  The entry is
+ *   dropped if the pixel lies outside [0, dW) x [0, dH) (a NaN coordinate does) or if z = depth[image, yi, xi] is not finite or
+ *   is <= 0.  Otherwise the camera point is q = ((u - cx) z / fx, (v - cy) z / fy, z), evaluated in fp64 from the fp32 values in
+ *   that order, with fx, fy, cx, cy = K[0], K[4], K[2], K[5].  num_points is the number kept.  Kept pairs are STORED AS FP32:
+ *   the source point as formed, q rounded once from its fp64 value (z is exact); everything below reads those fp32 values and
+ *   works in fp64.  An image_index outside [0, n_images) reads no depth: every entry is dropped (num_points 0).
+ *   Fewer than 3 kept pairs, or an inlier_dist that is not > 0 (a NaN is not), give the failure outputs of pp_pnp_ransac:
+ *   rot = I, tvec = (0, 0, 1), inlier_ratio 0, success 0, rms 0, an all-zero mask; num_listed and num_points are still reported.
+ * Hypotheses.  nh = min(iterations, 256).  Hypothesis h of problem p draws 3 distinct indices in [0, num_points) by
+ *   pp_pnp_ransac's rule with a sample of 3: s = mix(0x9E3779B9 (p + 1) ^ (h 7919 + 17)), then per index s = mix(s + 0x6D2B79F5),
+ *   c = s % num_points, drawn again while c repeats an earlier index (mix: the 32-bit finaliser x ^= x >> 16, x *= 0x7feb352d,
+ *   x ^= x >> 15, x *= 0x846ca68b, x ^= x >> 16; uint32 arithmetic).  A sample is degenerate if, in its source or its target
+ *   triangle, |a x b|^2 <= 1e-6 |a|^2 |b|^2 for the two edges a, b from its first point; a degenerate sample scores 0.
+ *   Otherwise its pose is the least-squares rigid fit q ~ R p + t of the 3 pairs (Horn's quaternion form: the 4x4 symmetric
+ *   matrix of the centred cross-covariance, its largest eigenvector by cyclic Jacobi in fp64, t = qm - R pm: a proper rotation
+ *   by construction).  Its score is the number of kept pairs with |R p + t - q|^2 <= inlier_dist^2 (fp64; a non-finite residual
+ *   is no inlier).  The winner has the highest score, the lowest h among equals; a winning score below 3 is a failure.
+ * Refit.  The same rigid fit over the winner's consensus set, its sums (centroids first, then the centred cross-covariance and
+ *   the source scatter) reduced in a fixed order: two launches give the same bits.  The refit is returned unless it is not
+ *   finite or the set's source points are collinear: l2 <= 1e-6 l1 for the two largest eigenvalues l1 >= l2 of their centred
+ *   3x3 scatter matrix; then the winner's pose is returned.  inlier_ratio = winner's score / num_points; rms = sqrt of the mean
+ *   squared 3-D residual of the consensus set at the returned pose; inlier_mask = membership of the winner's consensus set in
+ *   the order of the listed entries (0 for dropped entries, for the N - num_listed padding slots and for failed problems).
+ * PP_EINVAL (before any launch): what pp_pnp_ransac rejects, a null pointer other than inlier_mask, n_images <= 0, dH or
+ * dW <= 0, iterations <= 0.  image_index and inlier_dist are device data: a bad value fails its problem (above), nothing is
+ * read out of bounds.
+ * ------------------------------------------------------------------------- */
+int pp_rgbd_ransac(const float* tar_pts_2d, const float* src_pts_3d, const float* K, const float* tem_pose,
+                   const int64_t* tar_pts, const int64_t* src_pts, int P, int H, int W, int N,
+                   const float* depth, int n_images, int dH, int dW, const int32_t* image_index,
+                   const float* inlier_dist, int iterations,
+                   double* rot, double* tvec, double* inlier_ratio, int32_t* success,
+                   int32_t* num_points, int32_t* num_listed, double* rms, uint8_t* inlier_mask, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Training forward (model/picopose.py:114-137 — losses only, no gradients; csrc/pp_train.hip)
  * ------------------------------------------------------------------------- */
 /* KeyPointSampler.sample_pts (utils/keypoints.py:120-205, Keypoint :47-92, torch_utils.py unproject_points :138-151,

@@ -161,6 +161,7 @@ def lib():
         L.pp_pnp_ransac_debug.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]
         L.pp_pnp_ransac_refine.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, c.c_double] + [vp] * 10
         L.pp_pnp_refine_lm.argtypes = [vp] * 6 + [i32, i32, i32, c.c_double] + [vp] * 6
+        L.pp_rgbd_ransac.argtypes = [vp] * 6 + [i32] * 4 + [vp, i32, i32, i32, vp, vp, i32] + [vp] * 9
         L.pp_train_keypoints_workspace_bytes.restype = sz
         L.pp_train_keypoints_workspace_bytes.argtypes = [i32]
         L.pp_train_keypoints.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32] + [vp] * 10 + [i32, vp, vp, vp, sz, vp]

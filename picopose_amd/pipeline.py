@@ -12,7 +12,11 @@ tests have one GPU).
 
 pnp_refine: None (default) | "lm" — the batched PnP refines each pose by Levenberg-Marquardt on its RANSAC consensus set
 (utils/pose_recovery.py, refine="lm").  Only R and t move: the inlier ratios, the success flags and therefore the order of the
-hypotheses are those of pnp_refine=None."""
+hypotheses are those of pnp_refine=None.
+
+depth / depth_scale / depth_unit / rgbd_inlier_dist: with the test depth image every hypothesis also carries the pose of the batched
+3D-3D RANSAC (rgbd_pose.py, pp_rgbd_ransac) on the same correspondences: 'R_rgbd', 't_rgbd', 'rgbd_inliers_ratio', 'rgbd_success'.
+The PnP results, the ranking and the order of the hypotheses are those of a call without depth."""
 import numpy as np
 import torch
 
@@ -58,8 +62,64 @@ def pnp_collect(handle, hyp, B):
     return rot.reshape(hyp, B, 3, 3), tvec.reshape(hyp, B, 3, 1), ratio.reshape(hyp, B), ok.reshape(hyp, B)
 
 
-def _rank_hypotheses(stage2, rot, tvec, ratio, ok, hyp):
-    """run_test.py:168-186 for one mini-batch: per instance the hypotheses sorted by inlier ratio, stage-2 pose where PnP failed."""
+def _rgbd_args(outputs, real_K, inlier_dist, image_index):
+    """inlier_dist / image_index per instance (B,) (or a number / None) -> per problem (hyp * B,), hypothesis-major like pnp_inputs."""
+    hyp, B = len(outputs), outputs[0]["pred_poses"].shape[0]
+    per_problem = lambda x: x if x is None or np.ndim(x) == 0 or tuple(np.shape(x)) != (B,) else (  # noqa: E731
+        x.repeat(hyp) if isinstance(x, torch.Tensor) else np.tile(np.asarray(x), hyp))
+    return hyp, B, per_problem(inlier_dist), per_problem(image_index)
+
+
+def _rgbd_shaped(res, hyp, B):
+    rot, tvec, ratio, ok, npts, st = res[:6]
+    out = (rot.reshape(hyp, B, 3, 3), tvec.reshape(hyp, B, 3, 1), ratio.reshape(hyp, B), ok.reshape(hyp, B), npts.reshape(hyp, B),
+           {k: v.reshape(hyp, B) for k, v in st.items()})
+    return out + (res[6].reshape(hyp, B, -1),) if len(res) > 6 else out
+
+
+def rgbd_for_outputs(outputs, real_K, depth, inlier_dist, image_index=None, **kw):
+    """The RGB-D pose of every (hypothesis, instance) of a forward (rgbd_pose.pose_recovery_ransac_rgbd_batched over pnp_inputs):
+    outputs: list (hyp) of Net.forward dicts; real_K (B,3,3); depth (dH, dW) or (n_images, dH, dW); inlier_dist a number or one per
+    instance (B,) (or per problem (hyp * B,)), in the unit of the network's 3-D points; image_index (B,) (or (hyp * B,)): the depth
+    image of each instance (default 0); **kw: iterations, return_inliers, depth_scale, depth_unit.
+    -> rot (hyp,B,3,3), tvec (hyp,B,3,1), ratio, ok, npts (hyp,B), stats dict of (hyp,B) arrays [+ inliers (hyp,B,N)]."""
+    from .rgbd_pose import pose_recovery_ransac_rgbd_batched
+
+    hyp, B, dist, img = _rgbd_args(outputs, real_K, inlier_dist, image_index)
+    return _rgbd_shaped(pose_recovery_ransac_rgbd_batched(*pnp_inputs(outputs, real_K), depth, dist, img, **kw), hyp, B)
+
+
+def rgbd_for_outputs_async(outputs, real_K, depth, inlier_dist, image_index=None, **kw):
+    """rgbd_for_outputs without the host wait -> handle; `rgbd_collect(handle, hyp, B)` reads it.  **kw also takes `host` and
+    `stream` (rgbd_pose.pose_recovery_ransac_rgbd_batched_async)."""
+    from .rgbd_pose import pose_recovery_ransac_rgbd_batched_async
+
+    hyp, B, dist, img = _rgbd_args(outputs, real_K, inlier_dist, image_index)
+    return pose_recovery_ransac_rgbd_batched_async(*pnp_inputs(outputs, real_K), depth, dist, img, **kw)
+
+
+def rgbd_collect(handle, hyp, B):
+    return _rgbd_shaped(handle.result(), hyp, B)
+
+
+def _check_rgbd(depth, depth_scale, rgbd_inlier_dist):
+    """The depth arguments of infer_batch / infer_image, before any device work -> True when the RGB-D solver runs."""
+    if depth is None:
+        if depth_scale is not None or rgbd_inlier_dist is not None:
+            raise ValueError("depth_scale and rgbd_inlier_dist go with a depth image: depth is None")
+        return False
+    if rgbd_inlier_dist is None:
+        raise ValueError("depth needs rgbd_inlier_dist: the inlier radius of the RGB-D solver, in the unit of the network's 3-D points "
+                         "(it has no default)")
+    if getattr(depth, "ndim", 0) not in (2, 3) or (depth.ndim == 3 and depth.shape[0] != 1):
+        raise ValueError(f"depth must be one (dH, dW) image, got shape {tuple(getattr(depth, 'shape', ()))}")
+    return True
+
+
+def _rank_hypotheses(stage2, rot, tvec, ratio, ok, hyp, rgbd=None):
+    """run_test.py:168-186 for one mini-batch: per instance the hypotheses sorted by inlier ratio, stage-2 pose where PnP failed.
+    rgbd: rgbd_for_outputs' result; every hypothesis then also carries R_rgbd (9,), t_rgbd (3,) (its R, t where the RGB-D solver
+    failed), rgbd_inliers_ratio and rgbd_success.  The sort key is the PnP's inlier ratio either way."""
     B = stage2.shape[1]
     results = []
     for b in range(B):
@@ -70,6 +130,11 @@ def _rank_hypotheses(stage2, rot, tvec, ratio, ok, hyp):
             else:  # run_test.py:177-179: fall back to the stage-2 pose — float32 as the network returned it (the csv row of
                 # such an instance prints float32 values), with the inlier ratio PnP reported
                 hyps.append(dict(R=stage2[k, b, :3, :3], t=stage2[k, b, :3, 3], inliers_ratio=float(ratio[k, b]), pnp_success=False))
+            if rgbd is not None:
+                good = bool(rgbd[3][k, b])
+                hyps[-1].update(R_rgbd=(rgbd[0][k, b] if good else np.asarray(hyps[-1]["R"])).reshape(9),
+                                t_rgbd=(rgbd[1][k, b, :, 0] if good else np.asarray(hyps[-1]["t"])).reshape(3),
+                                rgbd_inliers_ratio=float(rgbd[2][k, b]), rgbd_success=good)
         hyps.sort(key=lambda h: h["inliers_ratio"], reverse=True)                   # run_test.py:186 (stable, like sorted())
         results.append(hyps)
     return results
@@ -116,15 +181,22 @@ def _forward_exact(net, end_points, hyp, pnp_fn=None, pnp_refine=None):
     return outputs, pnp
 
 
-def infer_batch(net, end_points, hyp=5, pnp_fn=None, on_saturation="raise", pnp_refine=None):
+def infer_batch(net, end_points, hyp=5, pnp_fn=None, on_saturation="raise", pnp_refine=None, depth=None, depth_scale=None,
+                rgbd_inlier_dist=None, depth_unit="m"):
     """-> per-instance pose hypotheses sorted by inlier ratio (run_test.py:168-186):
     list over instances of list over hypotheses of dict(R (3,3), t (3,), inliers_ratio, pnp_success).
     pnp_fn(outputs, real_K) -> (rot (hyp,B,3,3), tvec (hyp,B,3,1), ratio (hyp,B), ok (hyp,B)) replaces the batched HIP
     PnP (tests of the loop semantics inject canned answers).
     on_saturation: "raise" | "exact" (module docstring): with "exact" a forward that clamped an operand is run again in strict fp32.
     pnp_refine: None | "lm" (module docstring): the poses are refined on their consensus sets; the hypothesis order stays the inlier
-    ratio's of pnp_refine=None.  ValueError, before any device work, for another value or with pnp_fn."""
+    ratio's of pnp_refine=None.  ValueError, before any device work, for another value or with pnp_fn.
+    depth: the test depth image (dH, dW) of the batch's instances — float in the network's unit (metres; depth_unit="mm" for float
+    millimetres) or uint16 raw with depth_scale (millimetres per unit) — with rgbd_inlier_dist, the inlier radius of the RGB-D
+    solver in the network's unit (a number or one per instance; no default: ValueError without it).  Every hypothesis then also
+    carries R_rgbd (9,), t_rgbd (3,) (the unit of t; equal to R, t where rgbd_success is false), rgbd_inliers_ratio and
+    rgbd_success; everything else, the order included, is the result of a call without depth."""
     _check_pnp_refine(pnp_refine, pnp_fn)
+    with_depth = _check_rgbd(depth, depth_scale, rgbd_inlier_dist)
     if not _check_on_saturation(on_saturation):
         outputs = net(end_points, hyp)
         if pnp_fn is not None:
@@ -140,12 +212,15 @@ def infer_batch(net, end_points, hyp=5, pnp_fn=None, on_saturation="raise", pnp_
                                                          pnp_refine)
         if saturated:
             outputs, (rot, tvec, ratio, ok) = _forward_exact(net, end_points, hyp, pnp_fn, pnp_refine)
+    rgbd = None
+    if with_depth:
+        rgbd = rgbd_for_outputs(outputs, end_points["real_K"], depth, rgbd_inlier_dist, depth_scale=depth_scale, depth_unit=depth_unit)
     stage2 = np.stack([o["pred_poses"].cpu().numpy() for o in outputs])            # (hyp,B,4,4) float32
-    return _rank_hypotheses(stage2, rot, tvec, ratio, ok, hyp)
+    return _rank_hypotheses(stage2, rot, tvec, ratio, ok, hyp, rgbd)
 
 
 def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=True, next_data=None, on_saturation="raise",
-                indexed_bank=False, pnp_refine=None):
+                indexed_bank=False, pnp_refine=None, depth=None, depth_scale=None, rgbd_inlier_dist=None, depth_unit="m"):
     """One test image exactly as run_test.py:141-188 walks it: `data` holds the image's instances on dim 1
     (data[key][0] = (n_instance, ...), plus 'obj_idx'), `templates_data[key]` the per-object template bank
     ((n_objects, N, ...), including 'template_feature' and, optionally, an extended bank under 'template_cache').
@@ -164,11 +239,22 @@ def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=
     indexed_bank: the per-object tensors of `templates_data` go to the network as they are, and each instance names its object
     (end_points["template_index"] = its obj_idx): no copy of the bank per instance (run_test.py:159-162 makes one: ~308 MB per detection at
     ViT-L, 162 views), and a template shared by several instances is streamed once by stage 1.  Same results as the default.
-    pnp_refine: None | "lm" (module docstring), for both walks and for the strict-fp32 re-runs; the hypothesis order does not change."""
+    pnp_refine: None | "lm" (module docstring), for both walks and for the strict-fp32 re-runs; the hypothesis order does not change.
+    depth, depth_scale, depth_unit, rgbd_inlier_dist: the image's depth image and the RGB-D solver's inlier radius, as infer_batch
+    (rgbd_inlier_dist a number or one per instance); every hypothesis then also holds 'R_rgbd' (9,), 't_rgbd' (3,) in mm,
+    'rgbd_inliers_ratio' and 'rgbd_success'.  The depth is converted on the device once per image."""
     _check_pnp_refine(pnp_refine, pnp_fn)
     exact = _check_on_saturation(on_saturation)
+    with_depth = _check_rgbd(depth, depth_scale, rgbd_inlier_dist)
     n_instance = data["score"].shape[1]
     preds_image = []
+    if with_depth and n_instance > 0:
+        from .rgbd_pose import depth_on_device
+
+        if np.ndim(rgbd_inlier_dist) != 0 and tuple(np.shape(rgbd_inlier_dist)) != (n_instance,):
+            raise ValueError(f"rgbd_inlier_dist must be a number or one per instance ({n_instance},), got shape {tuple(np.shape(rgbd_inlier_dist))}")
+        depth = depth_on_device(depth, data["real_rgb"].device, depth_scale, depth_unit)     # float32 metres from here on
+    dist_of = lambda start, end: rgbd_inlier_dist if np.ndim(rgbd_inlier_dist) == 0 else rgbd_inlier_dist[start:end]  # noqa: E731
 
     def inputs_of(start, end):
         obj_idx = data["obj_idx"][0][start:end].reshape(-1)
@@ -187,11 +273,16 @@ def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=
         for hyps in batch_results:
             preds_image.append([{"R_stage_3": np.asarray(h["R"]).reshape(9), "t_stage_3": np.asarray(h["t"]).reshape(3) * 1000,
                                  "inliers_ratio": h["inliers_ratio"]} for h in hyps])
+            if with_depth:
+                for out, h in zip(preds_image[-1], hyps):
+                    out.update(R_rgbd=h["R_rgbd"], t_rgbd=h["t_rgbd"] * 1000, rgbd_inliers_ratio=h["rgbd_inliers_ratio"],
+                               rgbd_success=h["rgbd_success"])
 
     if pnp_fn is not None or not pipelined:
         for start in range(0, n_instance, bs):
-            emit(infer_batch(net, inputs_of(start, min(start + bs, n_instance)), hyp, pnp_fn=pnp_fn, on_saturation=on_saturation,
-                             pnp_refine=pnp_refine))
+            end = min(start + bs, n_instance)
+            rgbd_kw = dict(depth=depth, rgbd_inlier_dist=dist_of(start, end)) if with_depth else {}
+            emit(infer_batch(net, inputs_of(start, end), hyp, pnp_fn=pnp_fn, on_saturation=on_saturation, pnp_refine=pnp_refine, **rgbd_kw))
         return preds_image
     pending = None      # (PnP handle, pinned stage-2 poses, their event, batch size, inputs) of the mini-batch in flight
     starts = list(range(0, n_instance, bs))
@@ -213,6 +304,10 @@ def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=
         outputs = net(inputs, hyp, next_real_rgb=nxt) if nxt is not None else net(inputs, hyp)
         slot = ops.saturation_take(dev, _new_slot(dev)) if exact else None       # this forward's verdict, in stream order
         handle = pnp_for_outputs_async(outputs, inputs["real_K"], sat_slot=slot, pnp_refine=pnp_refine)
+        rgbd = None     # (RGB-D handle, depth, inlier radius): the launch rides behind the PnP's, read when the PnP is
+        if with_depth:
+            dist = dist_of(start, min(start + bs, n_instance))
+            rgbd = (rgbd_for_outputs_async(outputs, inputs["real_K"], depth, dist), depth, dist)
         s2 = torch.stack([o["pred_poses"] for o in outputs])                        # (hyp,B,4,4) float32
         s2_host = torch.empty(s2.shape, dtype=s2.dtype, pin_memory=True)
         s2_host.copy_(s2, non_blocking=True)
@@ -220,7 +315,7 @@ def infer_image(net, data, templates_data, hyp=5, bs=16, pnp_fn=None, pipelined=
         ev.record()
         if pending is not None:
             emit(_collect(pending, hyp, net, pnp_refine))
-        pending = (handle, s2_host, ev, s2.shape[1], inputs if exact else None)
+        pending = (handle, s2_host, ev, s2.shape[1], inputs if exact else None, rgbd)
     if pending is not None:
         emit(_collect(pending, hyp, net, pnp_refine))
     return preds_image
@@ -242,36 +337,42 @@ def infer_detections(net, image_u8, detections, K, templates_data, obj_idxs, **k
 
 
 def _collect(pending, hyp, net, pnp_refine=None):
-    handle, s2_host, ev, B, inputs = pending
+    handle, s2_host, ev, B, inputs, rgbd = pending
     rot, tvec, ratio, ok = pnp_collect(handle, hyp, B)
     ev.synchronize()
     if handle.saturated:    # (on_saturation="exact" only: the snapshot of this mini-batch's forward was set)
         outputs, (rot, tvec, ratio, ok) = _forward_exact(net, inputs, hyp, pnp_refine=pnp_refine)
-        return _rank_hypotheses(np.stack([o["pred_poses"].cpu().numpy() for o in outputs]), rot, tvec, ratio, ok, hyp)
-    return _rank_hypotheses(s2_host.numpy(), rot, tvec, ratio, ok, hyp)
+        if rgbd is not None:    # (the RGB-D poses of the re-run's correspondences)
+            rgbd = rgbd_for_outputs(outputs, inputs["real_K"], rgbd[1], rgbd[2])
+        return _rank_hypotheses(np.stack([o["pred_poses"].cpu().numpy() for o in outputs]), rot, tvec, ratio, ok, hyp, rgbd)
+    return _rank_hypotheses(s2_host.numpy(), rot, tvec, ratio, ok, hyp, rgbd_collect(rgbd[0], hyp, B) if rgbd is not None else None)
 
 
-STAGES = {"stage_3": ("R_stage_3", "t_stage_3"), "depth": ("R_depth", "t_depth")}
+STAGES = {"stage_3": ("R_stage_3", "t_stage_3"), "depth": ("R_depth", "t_depth"), "rgbd": ("R_rgbd", "t_rgbd")}
+REFINE_STARTS = ("stage_3", "rgbd")
 
 
 def bop_csv_lines(scene_id, img_id, obj_ids, scores, preds_image, image_time, stage="stage_3"):
     """The BOP results rows of run_test.py:191-206: one line per instance, best hypothesis, t in millimetres.
     stage: "stage_3" (default) writes the network's pose, "depth" the depth-refined one (refine_predictions must have run: an
-    instance whose best hypothesis holds no R_depth is a ValueError)."""
+    instance whose best hypothesis holds no R_depth is a ValueError), "rgbd" the RGB-D solver's (infer_image with a depth image;
+    the same error when the hypothesis holds no R_rgbd)."""
     if stage not in STAGES:
         raise ValueError(f"stage must be one of {sorted(STAGES)}, got {stage!r}")
     kr, kt = STAGES[stage]
     lines = []
     for k, preds in enumerate(preds_image):
         if kr not in preds[0]:
-            raise ValueError(f"instance {k}: its best hypothesis holds no {kr!r}; run refine_predictions first")
+            raise ValueError(f"instance {k}: its best hypothesis holds no {kr!r}; run refine_predictions first"
+                             if stage != "rgbd" else f"instance {k}: its best hypothesis holds no {kr!r}; run infer_image with depth first")
         lines.append(",".join((str(scene_id), str(img_id), str(obj_ids[k]), str(scores[k]),
                                " ".join(str(v) for v in preds[0][kr]),
                                " ".join(str(v) for v in preds[0][kt]), f"{image_time}\n")))
     return lines
 
 
-def refine_predictions(preds_image, models, obj_ids, K, depth, depth_scale=None, hypotheses="best", rank_by="inliers_ratio", **kw):
+def refine_predictions(preds_image, models, obj_ids, K, depth, depth_scale=None, hypotheses="best", rank_by="inliers_ratio",
+                       start="stage_3", **kw):
     """Depth refinement of one image's predictions (depth_refine.refine_poses_depth, ONE call for the whole image) -> a new
     preds_image; the input is not modified.  preds_image: infer_image's result; obj_ids: the object id of each instance (ids known
     to `models`, an evaluation.ObjectModels with faces); K (3, 3); depth (H, W) or (1, H, W), uint16 raw with `depth_scale` or float
@@ -280,8 +381,15 @@ def refine_predictions(preds_image, models, obj_ids, K, depth, depth_scale=None,
     't_depth' (3,) in mm (float32; the input pose where depth_status >= 2), 'depth_status' and 'depth_rms' (rms_after).
     rank_by: "inliers_ratio" keeps the order; "depth" (with "all") re-sorts each instance's hypotheses, stably: those with
     depth_status <= 1 first, in ascending depth_rms, then the others in their order.  ValueError before any device work for another
-    value, rank_by="depth" without "all", or obj_ids that do not match preds_image."""
+    value, rank_by="depth" without "all", or obj_ids that do not match preds_image.
+    start: "stage_3" (default) refines the network's pose, "rgbd" the RGB-D solver's ('R_rgbd', 't_rgbd' of infer_image with a depth
+    image: a start whose translation is already metric).  ValueError for another value, or for "rgbd" when a hypothesis to refine
+    holds no 'R_rgbd'."""
     from .depth_refine import refine_poses_depth
+
+    if not (isinstance(start, str) and start in REFINE_STARTS):
+        raise ValueError(f"start must be one of {REFINE_STARTS}, got {start!r}")
+    kr, kt = STAGES[start]
 
     if hypotheses not in ("best", "all"):
         raise ValueError(f"hypotheses must be 'best' or 'all', got {hypotheses!r}")
@@ -296,8 +404,11 @@ def refine_predictions(preds_image, models, obj_ids, K, depth, depth_scale=None,
     if getattr(depth, "ndim", 0) != 3 or depth.shape[0] != 1:
         raise ValueError(f"depth must be one (H, W) image, got shape {tuple(getattr(depth, 'shape', ()))}")
     where = [(i, h) for i, hyps in enumerate(preds_image) for h in range(len(hyps) if hypotheses == "all" else min(1, len(hyps)))]
-    R = np.array([np.asarray(preds_image[i][h]["R_stage_3"], dtype=np.float64).reshape(3, 3) for i, h in where]).reshape(-1, 3, 3)
-    t = np.array([np.asarray(preds_image[i][h]["t_stage_3"], dtype=np.float64).reshape(3) for i, h in where]).reshape(-1, 3)
+    for i, h in where:
+        if kr not in preds_image[i][h]:
+            raise ValueError(f"instance {i}, hypothesis {h} holds no {kr!r}: start={start!r} needs infer_image with a depth image")
+    R = np.array([np.asarray(preds_image[i][h][kr], dtype=np.float64).reshape(3, 3) for i, h in where]).reshape(-1, 3, 3)
+    t = np.array([np.asarray(preds_image[i][h][kt], dtype=np.float64).reshape(3) for i, h in where]).reshape(-1, 3)
     ids = np.array([int(obj_ids[i]) for i, _ in where], dtype=np.int64)
     res = refine_poses_depth(models, ids, R, t, K, depth, depth_scale=depth_scale, **kw)
     Rd, td = res["R"].cpu().numpy().reshape(-1, 9), res["t"].cpu().numpy()
