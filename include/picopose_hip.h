@@ -1117,13 +1117,23 @@ int pp_pose_errors(const float* vertices, const int* vert_off, const float* adds
  *   e_t = f32((double)(n_t + union - inter) / (double) union), or 1 when union = 0.
  * Integers make the result independent of order, stream, pair order and of how the caller splits the pairs over calls.
  *
+ * THE SCENE (PpScene, below) is what pp_vsd_errors, pp_depth_refine and pp_scene_gt share: the objects, cameras and views of a call.
  * Objects: vertices (millimetres) and faces (indices LOCAL to their object) of every object concatenated, object o at rows
  * [vert_off[o], vert_off[o + 1]) / [face_off[o], face_off[o + 1]); diameters (n_objects) fp32.  cams (n_images, 4) fp32 = fx, fy, cx, cy.
  * Views: view_obj, view_img (n_views) int32, poses (n_views, 4, 4) fp32 row-major object -> camera, windows (n_views, 4) int32,
  * view_zoff (n_views + 1) int64: the prefix sums of the windows' sample counts — view v owns z-buffer words
- * [view_zoff[v], view_zoff[v + 1]).  Pairs: pair_est, pair_gt (n_pairs) int32 view indices.  depth (n_images, H, W) fp32 millimetres.
- * Every table is a device pointer; the *_host arguments are HOST copies of the offset, window and index tables (and of faces,
- * diameters, cams), validated here before any launch.  taus_host: n_taus floats on the host (they travel as kernel arguments).
+ * [view_zoff[v], view_zoff[v + 1]).  H, W: the frame the windows lie in; near: the near plane (mm).
+ * Every table is a device pointer; the *_host members are HOST copies of the offset, window and index tables (and of faces,
+ * diameters, cams), validated by every entry before any launch.  A device table an entry does not read may be NULL (pp_scene_gt:
+ * diameters); every other member pointer is needed.  The struct is read during the call only: the caller may reuse or free it after.
+ * THE SCENE CHECKS, PP_EINVAL (before any launch) from every entry: a NULL scene or a needed member pointer that is null; n_objects /
+ * n_images / n_views / H / W <= 0, H W >= 2^31; near or a diameter not positive and finite; fx or fy = 0, a camera entry that is not
+ * finite; an offset table that does not start at 0, an object without vertices, a view whose object has no faces; a face index
+ * outside its object; a view's object or image index out of range; a window outside the frame or with x1 < x0 / y1 < y0; view_zoff
+ * not the prefix sums of the windows; view_faces (the sum over the views of their object's face count) >= 2^32.
+ *
+ * pp_vsd_errors.  Pairs: pair_est, pair_gt (n_pairs) int32 view indices, device pointers with *_host copies validated here.
+ * depth (n_images, H, W) fp32 millimetres.  taus_host: n_taus floats on the host (they travel as kernel arguments).
  * Outputs: vsd (n_pairs, n_taus) fp32, counts (n_pairs, 2 + n_taus) int32 = {union, inter, n_1 .. n_T}, near_count (n_views) uint32
  * (zeroed here): the triangles of each view dropped at the near plane; depth_out (n_views, H, W) fp32 (0 = background) or NULL.
  * n_pairs = 0 with depth_out renders only (the pair tables, depth, vsd and counts may then be NULL).
@@ -1132,22 +1142,41 @@ int pp_pose_errors(const float* vertices, const int* vert_off, const float* adds
  * (view, triangle)).  One call is one launch sequence over all its views: the caller (evaluation.vsd_errors) splits the PAIRS into
  * groups whose views fit its workspace bound, one call per group, with identical results.  All work is enqueued on `stream`;
  * nothing synchronises.
- * PP_EINVAL (before any launch): a null pointer that is needed; n_objects / n_images / n_views / H / W <= 0, n_pairs < 0, n_pairs = 0
- * without depth_out, H W >= 2^31; n_taus outside 1..PP_VSD_MAX_TAUS, a NaN tau; delta, near or a diameter not positive and finite;
- * fx or fy = 0, a camera entry that is not finite; an offset table that does not start at 0, an object without vertices, a view whose object has no faces; a
- * face index outside its object; a view's object or image index out of range; a window outside the frame or with x1 < x0 / y1 < y0;
- * view_zoff not the prefix sums of the windows; a pair index out of range; a pair whose two views differ in image or object;
- * view_faces >= 2^32.  PP_EWORKSPACE: workspace misaligned or smaller than pp_vsd_workspace_bytes says.
+ * PP_EINVAL (before any launch): THE SCENE CHECKS; a null pointer that is needed; n_pairs < 0, n_pairs = 0 without depth_out; n_taus
+ * outside 1..PP_VSD_MAX_TAUS, a NaN tau; delta not positive and finite; a pair index out of range; a pair whose two views differ in
+ * image or object.  PP_EWORKSPACE: workspace misaligned or smaller than pp_vsd_workspace_bytes says.
  * ------------------------------------------------------------------------- */
+typedef struct PpScene {
+    /* device tables */
+    const float* vertices;
+    const int* vert_off;
+    const int* faces;
+    const int* face_off;
+    const float* diameters;
+    const float* cams;
+    const int* view_obj;
+    const int* view_img;
+    const float* poses;
+    const int* windows;
+    const long long* view_zoff;
+    /* host copies, validated before any launch */
+    const int* vert_off_host;
+    const int* faces_host;
+    const int* face_off_host;
+    const float* diameters_host;
+    const float* cams_host;
+    const int* view_obj_host;
+    const int* view_img_host;
+    const int* windows_host;
+    const long long* view_zoff_host;
+    int n_objects, n_images, H, W, n_views;
+    float near;
+} PpScene;
+
 #define PP_VSD_MAX_TAUS 16
 int pp_vsd_workspace_bytes(long long window_samples, long long view_faces, size_t* bytes);
-int pp_vsd_errors(const float* vertices, const int* vert_off, const int* faces, const int* face_off, const float* diameters,
-                  const int* vert_off_host, const int* faces_host, const int* face_off_host, const float* diameters_host,
-                  int n_objects, const float* cams, const float* cams_host, int n_images, int H, int W, const int* view_obj,
-                  const int* view_img, const float* poses, const int* windows, const long long* view_zoff, const int* view_obj_host,
-                  const int* view_img_host, const int* windows_host, const long long* view_zoff_host, int n_views,
-                  const int* pair_est, const int* pair_gt, const int* pair_est_host, const int* pair_gt_host, int n_pairs,
-                  const float* depth, float delta, const float* taus_host, int n_taus, float near, void* workspace,
+int pp_vsd_errors(const PpScene* scene, const int* pair_est, const int* pair_gt, const int* pair_est_host, const int* pair_gt_host,
+                  int n_pairs, const float* depth, float delta, const float* taus_host, int n_taus, void* workspace,
                   size_t workspace_bytes, float* vsd, int* counts, unsigned int* near_count, float* depth_out, void* stream);
 
 /* -------------------------------------------------------------------------
@@ -1160,7 +1189,7 @@ int pp_vsd_errors(const float* vertices, const int* vert_off, const int* faces, 
  * THE ALGORITHM.  Per pose, at most `iterations` times:
  *  1. Render.  THE DEPTH RASTER of the VSD block, unchanged: the object under the CURRENT float32 pose into the view's window of the
  *     ragged z-buffer, word = (bits of Z) << 32 | face, 64-bit unsigned atomic minimum.  The window is fixed for the whole call (the
- *     caller plans it once from the input pose: evaluation.plan_window grown by a margin and clipped to the frame); a sample that
+ *     caller plans it once from the input pose: scene.plan_window grown by a margin and clipped to the frame); a sample that
  *     leaves it is not rendered and therefore not associated.
  *  2. Associate and accumulate.  For every window sample (x, y) with a z-buffer hit (Z_r, face f):
  *       Z_t = the test depth at (x, y); the sample is skipped unless Z_t > 0 (zero, negative, NaN: missing);
@@ -1193,10 +1222,11 @@ int pp_vsd_errors(const float* vertices, const int* vert_off, const int* faces, 
  *       4  (before the first) an input pose whose first three rows hold a NaN or an infinity, or an empty window -> the input pose
  *     A stopped pose is frozen: later launches neither render it nor move it, and nothing of another pose depends on it.
  *
- * Objects, cams, views, windows and view_zoff are the tables of pp_vsd_errors (device pointers, with *_host copies validated here);
- * boxes (n_objects, 6) fp32 = the lower and the upper corner of each object's vertex box.  view_soff (n_views + 1) int32: the prefix
- * sums of the views' strip counts, ceil(window height / PP_DEPTH_REFINE_STRIP_ROWS), 0 for an empty window.  poses_in (n_views, 4, 4)
- * fp32 row-major object -> camera; depth (n_images, H, W) fp32 millimetres.  max_distance, min_cos, rcond, eps, max_translation
+ * Objects, cams, views, windows and view_zoff are THE SCENE (PpScene, the VSD block); scene->poses are the INPUT poses ("poses_in"
+ * below), (n_views, 4, 4) fp32 row-major object -> camera.  boxes (n_objects, 6) fp32 = the lower and the upper corner of each
+ * object's vertex box, view_soff (n_views + 1) int32: the prefix sums of the views' strip counts, ceil(window height /
+ * PP_DEPTH_REFINE_STRIP_ROWS), 0 for an empty window; both are device pointers with *_host copies validated here.
+ * depth (n_images, H, W) fp32 millimetres.  max_distance, min_cos, rcond, eps, max_translation
  * (mm), max_rotation (rad) are float32 arguments, converted to float64 where they are compared with float64.
  * Outputs (device): poses_out (n_views, 4, 4) fp32 (also the working poses; it must not be poses_in); active (n_views) int32 work
  * table; status, n_iterations (linearisations performed), rank and n_points (of the last linearisation; rank 0 when it stopped with
@@ -1207,23 +1237,18 @@ int pp_vsd_errors(const float* vertices, const int* vert_off, const int* faces, 
  * Workspace (256-byte aligned): pp_depth_refine_workspace_bytes(window_samples, view_faces, strips) = 256 + roundup256(8
  * window_samples) + roundup256(8 view_faces) + 232 strips.  All `iterations` rounds (clear, two raster launches, accumulate, solve)
  * are enqueued on `stream`; nothing synchronises with the host.
- * PP_EINVAL (before any launch): every case of pp_vsd_errors that applies; poses_out = poses_in; a box that is not finite or has
- * hi < lo; view_soff not the prefix sums of the strip counts; iterations outside 1..PP_DEPTH_REFINE_MAX_ITERATIONS; min_points < 1;
- * max_distance, max_translation, max_rotation or near not positive and finite; min_cos or rcond outside [0, 1); eps negative or not
- * finite.  PP_EWORKSPACE: workspace misaligned or smaller than pp_depth_refine_workspace_bytes says.
+ * PP_EINVAL (before any launch): THE SCENE CHECKS; a null pointer that is needed; poses_out = scene->poses; a box that is not finite
+ * or has hi < lo; view_soff not the prefix sums of the strip counts; iterations outside 1..PP_DEPTH_REFINE_MAX_ITERATIONS;
+ * min_points < 1; max_distance, max_translation or max_rotation not positive and finite; min_cos or rcond outside [0, 1); eps
+ * negative or not finite.  PP_EWORKSPACE: workspace misaligned or smaller than pp_depth_refine_workspace_bytes says.
  * ------------------------------------------------------------------------- */
 #define PP_DEPTH_REFINE_STRIP_ROWS 8
 #define PP_DEPTH_REFINE_SUMS 29
 #define PP_DEPTH_REFINE_MAX_ITERATIONS 1000
 int pp_depth_refine_workspace_bytes(long long window_samples, long long view_faces, long long strips, size_t* bytes);
-int pp_depth_refine(const float* vertices, const int* vert_off, const int* faces, const int* face_off, const float* diameters,
-                    const float* boxes, const int* vert_off_host, const int* faces_host, const int* face_off_host,
-                    const float* diameters_host, const float* boxes_host, int n_objects, const float* cams, const float* cams_host,
-                    int n_images, int H, int W, const int* view_obj, const int* view_img, const float* poses_in, const int* windows,
-                    const long long* view_zoff, const int* view_soff, const int* view_obj_host, const int* view_img_host,
-                    const int* windows_host, const long long* view_zoff_host, const int* view_soff_host, int n_views,
+int pp_depth_refine(const PpScene* scene, const float* boxes, const float* boxes_host, const int* view_soff, const int* view_soff_host,
                     const float* depth, int iterations, float max_distance, int min_points, float min_cos, float rcond, float eps,
-                    float max_translation, float max_rotation, float near, void* workspace, size_t workspace_bytes, float* poses_out,
+                    float max_translation, float max_rotation, void* workspace, size_t workspace_bytes, float* poses_out,
                     int* active, int* status, int* n_iterations, int* rank, int* n_points, float* rms_before, float* rms_after,
                     unsigned int* near_count, float* trajectory, double* sums, void* stream);
 
@@ -1266,8 +1291,10 @@ int pp_depth_refine(const float* vertices, const int* vert_off, const int* faces
  * there is no floating-point atomic.  Every output is the same bits for any stream, view order, window, and grouping of the views
  * over calls (the map: up to the tie rule, which is stated on the call's view order).
  *
- * Objects, views, windows (on the canvas) and view_zoff are the tables of pp_vsd_errors.  cams (n_images, 4): the FRAME cameras;
- * canvas_cams (n_images, 4): the canvas cameras, which must be the float32 sums above.  depth (n_images, H, W) fp32 mm or NULL.
+ * Objects, views, windows (on the canvas) and view_zoff are THE SCENE (PpScene, the VSD block); the device table `diameters` is not
+ * read and may be NULL.  scene->cams, H and W are the FRAME cameras and the frame size; the canvas is derived here, and THE SCENE
+ * CHECKS run on a copy of the scene with the canvas cameras and the canvas size in their place.  canvas_cams (n_images, 4), device
+ * pointer with a host copy: the canvas cameras, which must be the float32 sums above.  depth (n_images, H, W) fp32 mm or NULL.
  * view_label (n_views) int32, used when use_view_label != 0.  Outputs (device): counts (n_views, 3) int32 = {all, valid, visib};
  * boxes (n_views, 8) int32 = bbox_obj, bbox_visib; near_count (n_views) uint32 (zeroed here).  Optional (NULL: off): mask_all,
  * mask_visib (n_views, H, W) uint8, 0 / 255, in-frame only, mask_all = Z > 0 (zeroed here); scene_depth (n_images, H, W) fp32;
@@ -1275,19 +1302,15 @@ int pp_depth_refine(const float* vertices, const int* vert_off, const int* faces
  * Workspace (256-byte aligned): pp_scene_gt_workspace_bytes(window_samples, view_faces, composite_pixels) = the header, z-buffer and
  * queue of pp_vsd_workspace_bytes, and when composite_pixels = n_images H W > 0 (the composite runs) that rounded up to 256 plus
  * 8 composite_pixels.  All work is enqueued on `stream`; nothing synchronises.
- * PP_EINVAL (before any device call): every case of pp_vsd_errors that applies, with the canvas as the frame (so a canvas of 2^31
- * samples or more); a needed pointer that is null; pad_x or pad_y < 0; delta negative or not finite; near not positive and finite;
- * a canvas camera that is not the stated sum; use_view_label with view_label NULL.  PP_EWORKSPACE: as pp_vsd_errors.
+ * PP_EINVAL (before any device call): THE SCENE CHECKS, with the canvas as the frame (so a canvas of 2^31 samples or more); a needed
+ * pointer that is null; pad_x or pad_y < 0; delta negative or not finite; a canvas camera that is not the stated sum;
+ * use_view_label with view_label NULL.  PP_EWORKSPACE: as pp_vsd_errors.
  * ------------------------------------------------------------------------- */
 int pp_scene_gt_workspace_bytes(long long window_samples, long long view_faces, long long composite_pixels, size_t* bytes);
-int pp_scene_gt(const float* vertices, const int* vert_off, const int* faces, const int* face_off, const int* vert_off_host,
-                const int* faces_host, const int* face_off_host, const float* diameters_host, int n_objects, const float* cams,
-                const float* cams_host, const float* canvas_cams, const float* canvas_cams_host, int n_images, int H, int W, int pad_x,
-                int pad_y, const int* view_obj, const int* view_img, const float* poses, const int* windows, const long long* view_zoff,
-                const int* view_obj_host, const int* view_img_host, const int* windows_host, const long long* view_zoff_host, int n_views,
-                const float* depth, float delta, float near, const int* view_label, int use_view_label, void* workspace,
-                size_t workspace_bytes, int* counts, int* boxes, unsigned int* near_count, unsigned char* mask_all,
-                unsigned char* mask_visib, float* scene_depth, int* instance_map, void* stream);
+int pp_scene_gt(const PpScene* scene, const float* canvas_cams, const float* canvas_cams_host, int pad_x, int pad_y, const float* depth,
+                float delta, const int* view_label, int use_view_label, void* workspace, size_t workspace_bytes, int* counts, int* boxes,
+                unsigned int* near_count, unsigned char* mask_all, unsigned char* mask_visib, float* scene_depth, int* instance_map,
+                void* stream);
 
 /* -------------------------------------------------------------------------
  * MODEL INFO: what a models_info.json entry needs from the vertices alone (picopose_amd/model_info.py plans every call;

@@ -43,6 +43,14 @@ class PpGemmDesc(ctypes.Structure):
     ]
 
 
+class PpScene(ctypes.Structure):
+    """The objects, cameras and views of one pp_vsd_errors / pp_depth_refine / pp_scene_gt call (scene.PackedScene fills it)."""
+    _fields_ = ([(name, ctypes.c_void_p) for name in (
+        "vertices", "vert_off", "faces", "face_off", "diameters", "cams", "view_obj", "view_img", "poses", "windows", "view_zoff",
+        "vert_off_host", "faces_host", "face_off_host", "diameters_host", "cams_host", "view_obj_host", "view_img_host", "windows_host",
+        "view_zoff_host")] + [(name, ctypes.c_int) for name in ("n_objects", "n_images", "H", "W", "n_views")] + [("near", ctypes.c_float)])
+
+
 class PpAdamTensor(ctypes.Structure):
     _fields_ = [("p", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("hl", ctypes.c_void_p),
                 ("scale2", ctypes.c_void_p), ("n", ctypes.c_longlong)]
@@ -230,13 +238,13 @@ def lib():
         L.pp_pose_errors_workspace_bytes.argtypes = [i32, i32, i32, i32, c.POINTER(sz)]
         L.pp_pose_errors.argtypes = [vp] * 10 + [i32] + [vp] * 7 + [i32, i32, vp, sz] + [vp] * 7
         L.pp_vsd_workspace_bytes.argtypes = [ll, ll, c.POINTER(sz)]
-        L.pp_vsd_errors.argtypes = ([vp] * 9 + [i32, vp, vp, i32, i32, i32] + [vp] * 9 + [i32] + [vp] * 4 + [i32, vp, f32, vp, i32, f32,
-                                    vp, sz] + [vp] * 5)
+        scene = c.POINTER(PpScene)
+        L.pp_vsd_errors.argtypes = [scene, vp, vp, vp, vp, i32, vp, f32, vp, i32, vp, sz, vp, vp, vp, vp, vp]
         L.pp_depth_refine_workspace_bytes.argtypes = [ll, ll, ll, c.POINTER(sz)]
-        L.pp_depth_refine.argtypes = ([vp] * 11 + [i32, vp, vp, i32, i32, i32] + [vp] * 11 + [i32, vp, i32, f32, i32] + [f32] * 6 +
-                                      [vp, sz] + [vp] * 12)
+        L.pp_depth_refine.argtypes = [scene, vp, vp, vp, vp, vp, i32, f32, i32, f32, f32, f32, f32, f32, vp, sz,
+                                      vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.pp_scene_gt_workspace_bytes.argtypes = [ll, ll, ll, c.POINTER(sz)]
-        L.pp_scene_gt.argtypes = ([vp] * 8 + [i32] + [vp] * 4 + [i32] * 5 + [vp] * 9 + [i32, vp, f32, f32, vp, i32, vp, sz] + [vp] * 8)
+        L.pp_scene_gt.argtypes = [scene, vp, vp, i32, i32, vp, f32, vp, i32, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
         L.pp_model_diameter_workspace_bytes.argtypes = [vp, i32, c.POINTER(sz)]
         L.pp_model_diameter.argtypes = [vp, vp, vp, i32, vp, sz, vp, vp, vp]
         L.pp_transform_hausdorff_workspace_bytes.argtypes = [i32, i32, c.POINTER(sz)]

@@ -357,39 +357,32 @@ int pp_depth_refine_workspace_bytes(long long window_samples, long long view_fac
     return PP_OK;
 }
 
-int pp_depth_refine(const float* vertices, const int* vert_off, const int* faces, const int* face_off, const float* diameters,
-                    const float* boxes, const int* vert_off_host, const int* faces_host, const int* face_off_host,
-                    const float* diameters_host, const float* boxes_host, int n_objects, const float* cams, const float* cams_host,
-                    int n_images, int H, int W, const int* view_obj, const int* view_img, const float* poses_in, const int* windows,
-                    const long long* view_zoff, const int* view_soff, const int* view_obj_host, const int* view_img_host,
-                    const int* windows_host, const long long* view_zoff_host, const int* view_soff_host, int n_views,
+int pp_depth_refine(const PpScene* scene, const float* boxes, const float* boxes_host, const int* view_soff, const int* view_soff_host,
                     const float* depth, int iterations, float max_distance, int min_points, float min_cos, float rcond, float eps,
-                    float max_translation, float max_rotation, float near, void* workspace, size_t workspace_bytes, float* poses_out,
+                    float max_translation, float max_rotation, void* workspace, size_t workspace_bytes, float* poses_out,
                     int* active, int* status, int* n_iterations, int* rank, int* n_points, float* rms_before, float* rms_after,
                     unsigned int* near_count, float* trajectory, double* sums, void* stream) {
-    if (!vertices || !vert_off || !faces || !face_off || !diameters || !boxes || !vert_off_host || !faces_host || !face_off_host ||
-        !diameters_host || !boxes_host || !cams || !cams_host || !view_obj || !view_img || !poses_in || !windows || !view_zoff ||
-        !view_soff || !view_obj_host || !view_img_host || !windows_host || !view_zoff_host || !view_soff_host || !depth || !workspace ||
-        !poses_out || !active || !status || !n_iterations || !rank || !n_points || !rms_before || !rms_after || !near_count)
+    if (!boxes || !boxes_host || !view_soff || !view_soff_host || !depth || !workspace || !poses_out || !active || !status ||
+        !n_iterations || !rank || !n_points || !rms_before || !rms_after || !near_count)
         return PP_EINVAL;
-    if (poses_in == poses_out) return PP_EINVAL;
     if (iterations < 1 || iterations > PP_DEPTH_REFINE_MAX_ITERATIONS || min_points < 1 || !positive_finite(max_distance) ||
         !(min_cos >= 0.f && min_cos < 1.f) || !(rcond >= 0.f && rcond < 1.f) || !(eps >= 0.f && finite32(eps)) ||
-        !positive_finite(max_translation) || !positive_finite(max_rotation) || !positive_finite(near))
+        !positive_finite(max_translation) || !positive_finite(max_rotation))
         return PP_EINVAL;
     SceneSize n;
-    if (check_scene({vert_off_host, faces_host, face_off_host, diameters_host, n_objects, cams_host, n_images, H, W, view_obj_host,
-                     view_img_host, windows_host, view_zoff_host, n_views}, n) != PP_OK)
-        return PP_EINVAL;
+    if (check_scene(scene, true, n) != PP_OK) return PP_EINVAL;
+    const float* poses_in = scene->poses;
+    if (poses_in == poses_out) return PP_EINVAL;
+    const int n_views = scene->n_views;
     // on top of the scene: the objects' vertex boxes and the strips that follow from the windows
-    for (int o = 0; o < n_objects; ++o)
+    for (int o = 0; o < scene->n_objects; ++o)
         for (int d = 0; d < 3; ++d) {
             const float lo = boxes_host[6 * (size_t)o + d], hi = boxes_host[6 * (size_t)o + 3 + d];
             if (!finite32(lo) || !finite32(hi) || hi < lo) return PP_EINVAL;
         }
     if (view_soff_host[0] != 0) return PP_EINVAL;
     for (int v = 0; v < n_views; ++v) {
-        const int* w = windows_host + 4 * (size_t)v;
+        const int* w = scene->windows_host + 4 * (size_t)v;
         const long long strips_v = w[2] > w[0] && w[3] > w[1] ? (w[3] - w[1] + ROWS - 1) / ROWS : 0;
         if ((long long)view_soff_host[v + 1] - view_soff_host[v] != strips_v) return PP_EINVAL;
     }
@@ -401,20 +394,21 @@ int pp_depth_refine(const float* vertices, const int* vert_off, const int* faces
     hipStream_t st = (hipStream_t)stream;
     const RasterWs ws = carve(workspace, n);
     double* partial = (double*)((char*)ws.queue + align256((size_t)n.total_faces * 8));
-    Scene s{vertices, vert_off, faces, face_off, cams, view_obj, view_img, poses_out, windows, view_zoff, n_views, H, W, near};
+    Scene s = device_scene(*scene);                               // (the raster reads the working poses and skips a stopped view)
+    s.poses = poses_out;
     s.active = active;
     const State state{poses_in, poses_out, active, status, n_iterations, rank, n_points, rms_before, rms_after, trajectory, sums, iterations};
     PP_CHECK_HIP(hipMemsetAsync(near_count, 0, sizeof(unsigned) * (size_t)n_views, st));
     if (sums) PP_CHECK_HIP(hipMemsetAsync(sums, 0, sizeof(double) * (size_t)n_views * iterations * NS, st));
-    hipLaunchKernelGGL(refine_init_kernel, dim3((unsigned)((n_views + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, state, windows, n_views);
+    hipLaunchKernelGGL(refine_init_kernel, dim3((unsigned)((n_views + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, state, scene->windows, n_views);
     for (int it = 0; it < iterations && strips > 0; ++it) {
         const int rc = raster_views(s, n, ws, near_count, st);
         if (rc != PP_OK) return rc;
-        hipLaunchKernelGGL(refine_accumulate_kernel, dim3((unsigned)strips), dim3(BLOCK), 0, st, s, ws.zbuf, view_soff, diameters, boxes, depth,
-                           max_distance, min_cos, partial);
+        hipLaunchKernelGGL(refine_accumulate_kernel, dim3((unsigned)strips), dim3(BLOCK), 0, st, s, ws.zbuf, view_soff, scene->diameters, boxes,
+                           depth, max_distance, min_cos, partial);
         const SolveArgs a{min_points, it, (double)rcond, (double)eps, (double)max_translation, (double)max_rotation};
-        hipLaunchKernelGGL(refine_solve_kernel, dim3((unsigned)n_views), dim3(64), 0, st, state, a, view_obj, view_soff, diameters, boxes,
-                           partial);
+        hipLaunchKernelGGL(refine_solve_kernel, dim3((unsigned)n_views), dim3(64), 0, st, state, a, scene->view_obj, view_soff,
+                           scene->diameters, boxes, partial);
     }
     return pp_last_launch();
 }

@@ -180,32 +180,26 @@ int pp_scene_gt_workspace_bytes(long long window_samples, long long view_faces, 
     return PP_OK;
 }
 
-int pp_scene_gt(const float* vertices, const int* vert_off, const int* faces, const int* face_off, const int* vert_off_host,
-                const int* faces_host, const int* face_off_host, const float* diameters_host, int n_objects, const float* cams,
-                const float* cams_host, const float* canvas_cams, const float* canvas_cams_host, int n_images, int H, int W, int pad_x,
-                int pad_y, const int* view_obj, const int* view_img, const float* poses, const int* windows, const long long* view_zoff,
-                const int* view_obj_host, const int* view_img_host, const int* windows_host, const long long* view_zoff_host, int n_views,
-                const float* depth, float delta, float near, const int* view_label, int use_view_label, void* workspace,
-                size_t workspace_bytes, int* counts, int* boxes, unsigned int* near_count, unsigned char* mask_all,
-                unsigned char* mask_visib, float* scene_depth, int* instance_map, void* stream) {
-    if (!vertices || !vert_off || !faces || !face_off || !vert_off_host || !faces_host || !face_off_host || !diameters_host || !cams ||
-        !cams_host || !canvas_cams || !canvas_cams_host || !view_obj || !view_img || !poses || !windows || !view_zoff || !view_obj_host ||
-        !view_img_host || !windows_host || !view_zoff_host || !workspace || !counts || !boxes || !near_count)
-        return PP_EINVAL;
+int pp_scene_gt(const PpScene* scene, const float* canvas_cams, const float* canvas_cams_host, int pad_x, int pad_y, const float* depth,
+                float delta, const int* view_label, int use_view_label, void* workspace, size_t workspace_bytes, int* counts, int* boxes,
+                unsigned int* near_count, unsigned char* mask_all, unsigned char* mask_visib, float* scene_depth, int* instance_map,
+                void* stream) {
+    if (!scene_tables(scene, false) || !canvas_cams || !canvas_cams_host || !workspace || !counts || !boxes || !near_count) return PP_EINVAL;
     if (use_view_label && !view_label) return PP_EINVAL;
-    if (!(delta >= 0.f) || !finite32(delta) || !positive_finite(near)) return PP_EINVAL;
-    int Hc = 0, Wc = 0;
-    if (!canvas_dims(H, W, pad_x, pad_y, Hc, Wc) || n_images <= 0) return PP_EINVAL;
+    if (!(delta >= 0.f) || !finite32(delta)) return PP_EINVAL;
+    // the scene as the raster sees it: the canvas cameras and the canvas size in the place of the frame's
+    PpScene canvas = *scene;
+    canvas.cams = canvas_cams, canvas.cams_host = canvas_cams_host;
+    const int n_images = scene->n_images, n_views = scene->n_views, H = scene->H, W = scene->W;
+    if (!canvas_dims(H, W, pad_x, pad_y, canvas.H, canvas.W) || n_images <= 0) return PP_EINVAL;
     for (int i = 0; i < n_images; ++i) {
-        const float* k = cams_host + 4 * (size_t)i;
+        const float* k = scene->cams_host + 4 * (size_t)i;
         const float* c = canvas_cams_host + 4 * (size_t)i;
         const float sx = k[2] + (float)pad_x, sy = k[3] + (float)pad_y;
         if (!(c[0] == k[0] && c[1] == k[1] && c[2] == sx && c[3] == sy)) return PP_EINVAL;      // (a NaN entry fails here too)
     }
     SceneSize n;
-    if (check_scene({vert_off_host, faces_host, face_off_host, diameters_host, n_objects, canvas_cams_host, n_images, Hc, Wc,
-                     view_obj_host, view_img_host, windows_host, view_zoff_host, n_views}, n) != PP_OK)
-        return PP_EINVAL;
+    if (check_scene(&canvas, false, n) != PP_OK) return PP_EINVAL;
     const bool composite = scene_depth || instance_map || !depth;
     const long long comp_pixels = composite ? (long long)n_images * H * W : 0;
     size_t need = 0, front = 0;
@@ -215,15 +209,15 @@ int pp_scene_gt(const float* vertices, const int* vert_off, const int* faces, co
     if (((uintptr_t)workspace % 256) != 0 || workspace_bytes < need) return PP_EWORKSPACE;
     long long max_window = 0;
     for (int v = 0; v < n_views; ++v) {
-        const long long m = view_zoff_host[v + 1] - view_zoff_host[v];
+        const long long m = scene->view_zoff_host[v + 1] - scene->view_zoff_host[v];
         max_window = m > max_window ? m : max_window;
     }
 
     hipStream_t st = (hipStream_t)stream;
     const RasterWs ws = carve(workspace, n);
     unsigned long long* comp = composite ? (unsigned long long*)((char*)workspace + align256(front)) : nullptr;
-    const Scene s{vertices, vert_off, faces, face_off, canvas_cams, view_obj, view_img, poses, windows, view_zoff, n_views, Hc, Wc, near};
-    const Frame f{cams, H, W, pad_x, pad_y};
+    const Scene s = device_scene(canvas);
+    const Frame f{scene->cams, H, W, pad_x, pad_y};
     PP_CHECK_HIP(hipMemsetAsync(near_count, 0, sizeof(unsigned) * (size_t)n_views, st));
     const int rc = raster_views(s, n, ws, near_count, st);
     if (rc != PP_OK) return rc;

@@ -141,31 +141,22 @@ int pp_vsd_workspace_bytes(long long window_samples, long long view_faces, size_
     return PP_OK;
 }
 
-int pp_vsd_errors(const float* vertices, const int* vert_off, const int* faces, const int* face_off, const float* diameters,
-                  const int* vert_off_host, const int* faces_host, const int* face_off_host, const float* diameters_host,
-                  int n_objects, const float* cams, const float* cams_host, int n_images, int H, int W, const int* view_obj,
-                  const int* view_img, const float* poses, const int* windows, const long long* view_zoff, const int* view_obj_host,
-                  const int* view_img_host, const int* windows_host, const long long* view_zoff_host, int n_views,
-                  const int* pair_est, const int* pair_gt, const int* pair_est_host, const int* pair_gt_host, int n_pairs,
-                  const float* depth, float delta, const float* taus_host, int n_taus, float near, void* workspace,
+int pp_vsd_errors(const PpScene* scene, const int* pair_est, const int* pair_gt, const int* pair_est_host, const int* pair_gt_host,
+                  int n_pairs, const float* depth, float delta, const float* taus_host, int n_taus, void* workspace,
                   size_t workspace_bytes, float* vsd, int* counts, unsigned int* near_count, float* depth_out, void* stream) {
-    if (!vertices || !vert_off || !faces || !face_off || !diameters || !vert_off_host || !faces_host || !face_off_host ||
-        !diameters_host || !cams || !cams_host || !view_obj || !view_img || !poses || !windows || !view_zoff || !view_obj_host ||
-        !view_img_host || !windows_host || !view_zoff_host || !taus_host || !workspace || !near_count)
-        return PP_EINVAL;
-    if (n_pairs < 0 || n_taus < 1 || n_taus > PP_VSD_MAX_TAUS || !positive_finite(delta) || !positive_finite(near)) return PP_EINVAL;
+    if (!taus_host || !workspace || !near_count) return PP_EINVAL;
+    if (n_pairs < 0 || n_taus < 1 || n_taus > PP_VSD_MAX_TAUS || !positive_finite(delta)) return PP_EINVAL;
     if (n_pairs == 0 && !depth_out) return PP_EINVAL;             // nothing to do
     if (n_pairs > 0 && (!pair_est || !pair_gt || !pair_est_host || !pair_gt_host || !depth || !vsd || !counts)) return PP_EINVAL;
     for (int t = 0; t < n_taus; ++t)
         if (!(taus_host[t] == taus_host[t])) return PP_EINVAL;
     SceneSize n;
-    if (check_scene({vert_off_host, faces_host, face_off_host, diameters_host, n_objects, cams_host, n_images, H, W, view_obj_host,
-                     view_img_host, windows_host, view_zoff_host, n_views}, n) != PP_OK)
-        return PP_EINVAL;
+    if (check_scene(scene, true, n) != PP_OK) return PP_EINVAL;
+    const int n_views = scene->n_views, H = scene->H, W = scene->W;
     for (int p = 0; p < n_pairs; ++p) {
         const int e = pair_est_host[p], g = pair_gt_host[p];
         if ((unsigned)e >= (unsigned)n_views || (unsigned)g >= (unsigned)n_views) return PP_EINVAL;
-        if (view_obj_host[e] != view_obj_host[g] || view_img_host[e] != view_img_host[g]) return PP_EINVAL;
+        if (scene->view_obj_host[e] != scene->view_obj_host[g] || scene->view_img_host[e] != scene->view_img_host[g]) return PP_EINVAL;
     }
     size_t need = 0;
     if (pp_vsd_workspace_bytes(n.samples, n.total_faces, &need) != PP_OK) return PP_EINVAL;
@@ -173,7 +164,7 @@ int pp_vsd_errors(const float* vertices, const int* vert_off, const int* faces, 
 
     hipStream_t st = (hipStream_t)stream;
     const RasterWs ws = carve(workspace, n);
-    const Scene s{vertices, vert_off, faces, face_off, cams, view_obj, view_img, poses, windows, view_zoff, n_views, H, W, near};
+    const Scene s = device_scene(*scene);
     PP_CHECK_HIP(hipMemsetAsync(near_count, 0, sizeof(unsigned) * (size_t)n_views, st));
     const int rc = raster_views(s, n, ws, near_count, st);
     if (rc != PP_OK) return rc;
@@ -188,7 +179,7 @@ int pp_vsd_errors(const float* vertices, const int* vert_off, const int* faces, 
     if (n_pairs > 0) {
         Taus taus;
         for (int t = 0; t < PP_VSD_MAX_TAUS; ++t) taus.v[t] = t < n_taus ? taus_host[t] : INFINITY;
-        hipLaunchKernelGGL(vsd_pair_kernel, dim3((unsigned)n_pairs), dim3(BLOCK), 0, st, s, ws.zbuf, pair_est, pair_gt, diameters, depth,
+        hipLaunchKernelGGL(vsd_pair_kernel, dim3((unsigned)n_pairs), dim3(BLOCK), 0, st, s, ws.zbuf, pair_est, pair_gt, scene->diameters, depth,
                            delta, taus, n_taus, vsd, counts);
     }
     return pp_last_launch();

@@ -1,11 +1,12 @@
-// The mixed-object windowed depth raster ("THE DEPTH RASTER" of include/picopose_hip.h), shared by pp_vsd.hip (pp_vsd_errors) and
-// pp_depth_refine.hip (pp_depth_refine).  Each translation unit that includes this header gets its own copy of the kernels (internal
-// linkage, no relocatable device code in this build).
+// The mixed-object windowed depth raster ("THE DEPTH RASTER" of include/picopose_hip.h), shared by pp_vsd.hip (pp_vsd_errors),
+// pp_depth_refine.hip (pp_depth_refine) and pp_scene_gt.hip (pp_scene_gt).  Each translation unit that includes this header gets its
+// own copy of the kernels (internal linkage, no relocatable device code in this build).
 //
 //   vsd_raster_small_kernel  one lane per (view, triangle of the view's object): cover_small under the view's camera and window
 //   vsd_raster_large_kernel  one workgroup row per queue entry: cover_large
-//   check_scene, carve, raster_views (host)  the one validation of the object, camera and view tables, the one layout of
-//                            header | z-buffer | queue, and the clears and launches of a call or of one refinement iteration
+//   check_scene, device_scene, carve, raster_views (host)  the one validation of a PpScene (null checks included), its tables as the
+//                            kernels take them, the one layout of header | z-buffer | queue, and the clears and launches of a call
+//                            or of one refinement iteration
 //
 // The kernels are an index mapping and load_view(); the traversal is pp_raster_dev.h's, the template renderer's.  The z-buffer is
 // ragged: 8 bytes per WINDOW sample, view v at words [view_zoff[v], view_zoff[v + 1]).  Include it AFTER `#pragma clang fp
@@ -78,60 +79,63 @@ inline size_t align256(size_t n) { return (n + 255) / 256 * 256; }
 __host__ __device__ inline bool finite32(float v) { return fabsf(v) <= 3.402823466e38f; }
 inline bool positive_finite(float v) { return v > 0.f && finite32(v); }
 
-// the host copies of the tables of a call, as the entries receive them
-struct SceneHost {
-    const int* vert_off;
-    const int* faces;
-    const int* face_off;
-    const float* diameters;
-    int n_objects;
-    const float* cams;
-    int n_images, H, W;
-    const int* view_obj;
-    const int* view_img;
-    const int* windows;
-    const long long* view_zoff;
-    int n_views;
-};
-
 struct SceneSize {
     long long total_faces;     // over the views: the queue's capacity
     int max_faces;             // of one view
     long long samples;         // z-buffer words
 };
 
-// The counts and every table of `h` (no pointer of it is null): offsets, face indices, diameters, cameras, the views' objects and
-// images, windows inside the frame and the z-buffer offsets that follow from them.  PP_OK or PP_EINVAL; nothing touches the device.
-inline int check_scene(const SceneHost& h, SceneSize& out) {
-    if (h.n_objects <= 0 || h.n_images <= 0 || h.n_views <= 0 || h.H <= 0 || h.W <= 0 || (long long)h.H * h.W > INT_MAX) return PP_EINVAL;
-    if (h.vert_off[0] != 0 || h.face_off[0] != 0) return PP_EINVAL;
-    for (int o = 0; o < h.n_objects; ++o) {
-        if (h.vert_off[o + 1] <= h.vert_off[o] || h.face_off[o + 1] < h.face_off[o]) return PP_EINVAL;
-        if (!positive_finite(h.diameters[o])) return PP_EINVAL;
-        const unsigned nv = (unsigned)(h.vert_off[o + 1] - h.vert_off[o]);
-        for (size_t k = 3 * (size_t)h.face_off[o]; k < 3 * (size_t)h.face_off[o + 1]; ++k)
-            if ((unsigned)h.faces[k] >= nv) return PP_EINVAL;
+// The one null check of the scene's tables.  device_diameters: whether the entry reads the device table `diameters`.
+inline bool scene_tables(const PpScene* h, bool device_diameters) {
+    return h && h->vertices && h->vert_off && h->faces && h->face_off && (h->diameters || !device_diameters) && h->cams && h->view_obj &&
+           h->view_img && h->poses && h->windows && h->view_zoff && h->vert_off_host && h->faces_host && h->face_off_host &&
+           h->diameters_host && h->cams_host && h->view_obj_host && h->view_img_host && h->windows_host && h->view_zoff_host;
+}
+
+// THE SCENE CHECKS of include/picopose_hip.h: the pointers (scene_tables), the counts, near, and every host table of `h`: offsets,
+// face indices, diameters, cameras, the views' objects and images, windows inside the frame and the z-buffer offsets that follow
+// from them.  PP_OK or PP_EINVAL; nothing touches the device.
+inline int check_scene(const PpScene* h, bool device_diameters, SceneSize& out) {
+    if (!scene_tables(h, device_diameters)) return PP_EINVAL;
+    if (h->n_objects <= 0 || h->n_images <= 0 || h->n_views <= 0 || h->H <= 0 || h->W <= 0 || (long long)h->H * h->W > INT_MAX) return PP_EINVAL;
+    if (!positive_finite(h->near)) return PP_EINVAL;
+    const int* vert_off = h->vert_off_host;
+    const int* face_off = h->face_off_host;
+    if (vert_off[0] != 0 || face_off[0] != 0) return PP_EINVAL;
+    for (int o = 0; o < h->n_objects; ++o) {
+        if (vert_off[o + 1] <= vert_off[o] || face_off[o + 1] < face_off[o]) return PP_EINVAL;
+        if (!positive_finite(h->diameters_host[o])) return PP_EINVAL;
+        const unsigned nv = (unsigned)(vert_off[o + 1] - vert_off[o]);
+        for (size_t k = 3 * (size_t)face_off[o]; k < 3 * (size_t)face_off[o + 1]; ++k)
+            if ((unsigned)h->faces_host[k] >= nv) return PP_EINVAL;
     }
-    for (int i = 0; i < h.n_images; ++i) {
-        const float* k = h.cams + 4 * (size_t)i;
+    for (int i = 0; i < h->n_images; ++i) {
+        const float* k = h->cams_host + 4 * (size_t)i;
         if (k[0] == 0.f || k[1] == 0.f || !finite32(k[0]) || !finite32(k[1]) || !finite32(k[2]) || !finite32(k[3])) return PP_EINVAL;
     }
-    if (h.view_zoff[0] != 0) return PP_EINVAL;
+    const long long* view_zoff = h->view_zoff_host;
+    if (view_zoff[0] != 0) return PP_EINVAL;
     out = SceneSize{0, 0, 0};
-    for (int v = 0; v < h.n_views; ++v) {
-        const int o = h.view_obj[v];
-        if ((unsigned)o >= (unsigned)h.n_objects || (unsigned)h.view_img[v] >= (unsigned)h.n_images) return PP_EINVAL;
-        const int nf = h.face_off[o + 1] - h.face_off[o];
+    for (int v = 0; v < h->n_views; ++v) {
+        const int o = h->view_obj_host[v];
+        if ((unsigned)o >= (unsigned)h->n_objects || (unsigned)h->view_img_host[v] >= (unsigned)h->n_images) return PP_EINVAL;
+        const int nf = face_off[o + 1] - face_off[o];
         if (nf <= 0) return PP_EINVAL;                            // an object of the call without faces
-        const int* w = h.windows + 4 * (size_t)v;
-        if (w[0] < 0 || w[1] < 0 || w[2] < w[0] || w[3] < w[1] || w[2] > h.W || w[3] > h.H) return PP_EINVAL;
-        if (h.view_zoff[v + 1] - h.view_zoff[v] != (long long)(w[2] - w[0]) * (w[3] - w[1])) return PP_EINVAL;
+        const int* w = h->windows_host + 4 * (size_t)v;
+        if (w[0] < 0 || w[1] < 0 || w[2] < w[0] || w[3] < w[1] || w[2] > h->W || w[3] > h->H) return PP_EINVAL;
+        if (view_zoff[v + 1] - view_zoff[v] != (long long)(w[2] - w[0]) * (w[3] - w[1])) return PP_EINVAL;
         out.total_faces += nf;
         out.max_faces = nf > out.max_faces ? nf : out.max_faces;
     }
     if (out.total_faces > (long long)UINT_MAX) return PP_EINVAL;
-    out.samples = h.view_zoff[h.n_views];
+    out.samples = view_zoff[h->n_views];
     return PP_OK;
+}
+
+// the tables of a checked scene as the kernels take them
+inline Scene device_scene(const PpScene& h) {
+    return Scene{h.vertices, h.vert_off, h.faces, h.face_off, h.cams, h.view_obj, h.view_img, h.poses, h.windows, h.view_zoff, h.n_views, h.H, h.W,
+                 h.near};
 }
 
 // the front of a workspace: header (the queue counter) | z-buffer, padded to 256 bytes | queue, one slot per (view, triangle)

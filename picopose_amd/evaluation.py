@@ -22,7 +22,8 @@ hold them.
 VSD, the third term of the BOP average recall, needs the test depth images and two depth renders per pair, so it has its own entry
 point: vsd_errors renders every distinct (image, object, pose) view once into a ragged z-buffer (a host-planned window per view)
 and reduces every pair on the device (csrc/pp_vsd.hip; the definition and the arithmetic are stated in include/picopose_hip.h and
-restated by tests/vsd_oracle.py).  It is the BOP toolkit's VSD (visib_mode "bop19", step cost) written from memory: parity with
+restated by tests/vsd_oracle.py; the windows, the view groups and the packing of a call's tables into the PpScene of the ABI are
+scene.py's, shared with depth_refine.py and scene_gt.py).  It is the BOP toolkit's VSD (visib_mode "bop19", step cost) written from memory: parity with
 the toolkit's pixels is unpinned, and a triangle that reaches the near plane is dropped whole where the toolkit's renderer clips it.
 match_and_score computes it when it is given the depth images, and then also returns AR = (AR_VSD + AR_MSSD + AR_MSPD) / 3."""
 import ctypes
@@ -34,9 +35,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import scene as scn
+from .scene import DEFAULT_WORKSPACE_BYTES, plan_window  # noqa: F401  (documented names of this module)
 
 KINDS = {"mssd": 1, "mspd": 2, "add": 4, "adds": 8}             # PP_EVAL_* of include/picopose_hip.h
-DEFAULT_WORKSPACE_BYTES = 256 << 20
 MSSD_THRESHOLDS = np.arange(1, 11) / 20.0                       # 0.05 .. 0.5 of the object diameter
 MSPD_THRESHOLDS = np.arange(1, 11) * 5.0                        # 5 r .. 50 r pixels, r = image_width / 640
 VSD_TAUS = np.arange(1, 11) / 20.0                              # misalignment tolerances, 0.05 .. 0.5 of the object diameter
@@ -149,6 +151,7 @@ class ObjectModels:
         self.sym_off = self._offsets(syms)
         self.face_off = self._offsets(faces)
         self.faces_host = np.concatenate(faces)
+        self.face_counts = (self.face_off[1:] - self.face_off[:-1]).astype(np.int64)
         self.has_faces = all(len(f) for f in faces)
         self.diameters_f32 = self.diameters.astype(np.float32)
         self.aabb_corners = [np.array([[x, y, z] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])], dtype=np.float64)
@@ -185,30 +188,6 @@ class ObjectModels:
     def n_faces(self, obj_id):
         k = self.index[int(obj_id)]
         return int(self.face_off[k + 1] - self.face_off[k])
-
-
-def _pose_tensor(name, a, P, tail, device):
-    """One rule for R_*, t_* and K: a numpy array or a torch tensor must have a float dtype; a plain (nested) list or tuple of numbers,
-    as json.load gives it, is read as float64.  tail: the shape after P, or a list of whole shapes to choose from."""
-    if isinstance(a, (list, tuple)):
-        try:
-            a = np.asarray(a, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError(f"{name} must be a rectangular nested list of numbers") from None
-    if isinstance(a, np.ndarray):
-        if not np.issubdtype(a.dtype, np.floating):
-            raise ValueError(f"{name} must be a float array, got {a.dtype}")
-        t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
-    elif isinstance(a, torch.Tensor):
-        if not a.dtype.is_floating_point:
-            raise ValueError(f"{name} must be a float tensor, got {a.dtype}")
-        t = a
-    else:
-        raise ValueError(f"{name} must be a numpy array, a torch tensor or a nested list, got {type(a).__name__}")
-    shapes = [(P,) + tail] if isinstance(tail, tuple) else list(tail)
-    if tuple(t.shape) not in shapes:
-        raise ValueError(f"{name} must have shape {' or '.join(str(s) for s in shapes)}, got {tuple(t.shape)}")
-    return t.to(device=device, dtype=torch.float32).contiguous()
 
 
 def _plan_chunks(models, pair_obj, mask, workspace_bytes):
@@ -264,13 +243,13 @@ def pose_errors(models, obj_ids, R_est, t_est, R_gt, t_gt, K=None, kinds=("mssd"
         if int(o) not in models.index:
             raise ValueError(f"unknown obj_id {int(o)}: the models hold {models.obj_ids}")
     pair_obj = np.array([models.index[int(o)] for o in ids], dtype=np.int32)
-    Re, te = _pose_tensor("R_est", R_est, P, (3, 3), dev), _pose_tensor("t_est", t_est, P, (3,), dev)
-    Rg, tg = _pose_tensor("R_gt", R_gt, P, (3, 3), dev), _pose_tensor("t_gt", t_gt, P, (3,), dev)
+    Re, te = scn.pose_tensor("R_est", R_est, P, (3, 3), dev), scn.pose_tensor("t_est", t_est, P, (3,), dev)
+    Rg, tg = scn.pose_tensor("R_gt", R_gt, P, (3, 3), dev), scn.pose_tensor("t_gt", t_gt, P, (3,), dev)
     focal = None
     if "mspd" in kinds:
         if K is None:
             raise ValueError("kind 'mspd' needs the camera matrix K")
-        Kt = _pose_tensor("K", K, P, [(3, 3), (P, 3, 3)], dev)
+        Kt = scn.pose_tensor("K", K, P, [(3, 3), (P, 3, 3)], dev)
         if Kt.dim() == 2:
             Kt = Kt[None].expand(P, 3, 3)
         focal = torch.stack([Kt[:, 0, 0], Kt[:, 1, 1]], dim=1).contiguous()
@@ -283,8 +262,7 @@ def pose_errors(models, obj_ids, R_est, t_est, R_gt, t_gt, K=None, kinds=("mssd"
         out["adds_max_points"] = models.max_points
     if P == 0:
         return out
-    if dev.type != "cuda":
-        raise _lib.PicoPoseHipError("picopose_amd runs on the GPU only: build the ObjectModels on a CUDA(HIP) device")
+    scn.require_gpu(dev)
     L = _lib.lib()
     mask = sum(KINDS[k] for k in set(kinds))
     chunk, need = _plan_chunks(models, pair_obj, mask, workspace_bytes)
@@ -308,175 +286,39 @@ def pose_errors(models, obj_ids, R_est, t_est, R_gt, t_gt, K=None, kinds=("mssd"
 
 
 # ---- VSD: depth renders and visibility ---------------------------------------------------------------------------------------------
-def plan_window(corners, pose, K4, H, W, near):
-    """The sampling window {x0, y0, x1, y1} (x1, y1 exclusive) of one view, planned on the host in float64: the 8 corners (8, 3) of the
-    object's vertex box under `pose` (4, 4); when all have Zc > near the window is the box of their pixels grown by one pixel and
-    clipped to the frame ((0, 0, 0, 0) when that is empty: the object is off-frame), otherwise the whole frame.  The projection of the
-    box contains the projection of every vertex, and one pixel exceeds the float32 error of the kernel's own projection by orders
-    of magnitude, so the window holds every sample the full-frame render covers.  A pose with a NaN or an infinity: (0, 0, 0, 0)."""
-    P = np.asarray(pose, dtype=np.float64)
-    if not np.all(np.isfinite(P[:3])):
-        return (0, 0, 0, 0)
-    c = np.asarray(corners, dtype=np.float64) @ P[:3, :3].T + P[:3, 3]
-    if not np.all(c[:, 2] > near):
-        return (0, 0, W, H)
-    fx, fy, cx, cy = K4
-    u, v = fx * c[:, 0] / c[:, 2] + cx, fy * c[:, 1] / c[:, 2] + cy
-    if not (np.all(np.isfinite(u)) and np.all(np.isfinite(v))):
-        return (0, 0, W, H)
-    x0, x1 = int(np.clip(np.floor(u.min()) - 1, 0, W)), int(np.clip(np.ceil(u.max()) + 2, 0, W))
-    y0, y1 = int(np.clip(np.floor(v.min()) - 1, 0, H)), int(np.clip(np.ceil(v.max()) + 2, 0, H))
-    return (x0, y0, x1, y1) if x1 > x0 and y1 > y0 else (0, 0, 0, 0)
-
-
-def _host_f32(name, a, P, tail):
-    """_pose_tensor's rules, result on the host: (P,) + tail float32 numpy (the views are planned on the host)."""
-    return _pose_tensor(name, a, P, tail, "cpu").numpy()
-
-
-def _obj_index(models, obj_ids, need_faces=True):
-    if not isinstance(models, ObjectModels):
-        raise ValueError("models must be an ObjectModels")
-    if isinstance(obj_ids, torch.Tensor):
-        obj_ids = obj_ids.cpu().numpy()
-    ids = np.asarray(obj_ids)
-    if ids.ndim != 1 or (len(ids) and not np.issubdtype(ids.dtype, np.integer)):
-        raise ValueError(f"obj_ids must be a 1-D integer sequence, got {ids.dtype} {ids.shape}")
-    for o in ids:
-        if int(o) not in models.index:
-            raise ValueError(f"unknown obj_id {int(o)}: the models hold {models.obj_ids}")
-        if need_faces and models.n_faces(o) == 0:
-            raise ValueError(f"object {int(o)} has no faces: give ObjectModels its 'faces' to render it")
-    return np.array([models.index[int(o)] for o in ids], dtype=np.int32)
-
-
-def _cams(K, n_images):
-    """K (3, 3) or (n_images, 3, 3) -> (n_images, 4) float32 {fx, fy, cx, cy} on the host (no skew)."""
-    Kt = _pose_tensor("K", K, n_images, [(3, 3), (n_images, 3, 3)], "cpu").numpy()
-    if Kt.ndim == 2:
-        Kt = np.broadcast_to(Kt, (n_images, 3, 3))
-    cams = np.ascontiguousarray(np.stack([Kt[:, 0, 0], Kt[:, 1, 1], Kt[:, 0, 2], Kt[:, 1, 2]], axis=1), dtype=np.float32)
-    if not (np.all(np.isfinite(cams)) and np.all(cams[:, :2] != 0)):
-        raise ValueError("K must be finite with fx and fy non-zero")
-    return cams
-
-
-def _image_index(image_index, P, n_images):
-    if image_index is None:
-        return np.zeros(P, dtype=np.int32)
-    if isinstance(image_index, torch.Tensor):
-        image_index = image_index.cpu().numpy()
-    idx = np.asarray(image_index)
-    if idx.shape != (P,) or (P and not np.issubdtype(idx.dtype, np.integer)):
-        raise ValueError(f"image_index must be {P} integers, got {idx.dtype} {idx.shape}")
-    if P and (idx.min() < 0 or idx.max() >= n_images):
-        raise ValueError(f"image_index must lie in [0, {n_images})")
-    return idx.astype(np.int32)
-
-
-def _pose44(R, t):
-    P = np.zeros((len(R), 4, 4), dtype=np.float32)
-    P[:, :3, :3], P[:, :3, 3], P[:, 3, 3] = R, t, 1.0
-    return P
-
-
-def _check_scalars(near, window, workspace_bytes):
-    if not (isinstance(near, (int, float)) and math.isfinite(near) and near > 0):
-        raise ValueError(f"near must be a positive number, got {near!r}")
-    if window not in ("auto", "full"):
-        raise ValueError(f"window must be 'auto' or 'full', got {window!r}")
-    if not (isinstance(workspace_bytes, int) and workspace_bytes > 0):
-        raise ValueError(f"workspace_bytes must be a positive int, got {workspace_bytes!r}")
-
-
-def _windows(models, view_obj, view_img, poses, cams, H, W, near, window):
-    out = np.zeros((len(view_obj), 4), dtype=np.int32)
-    for v, (o, i, P) in enumerate(zip(view_obj, view_img, poses)):
-        if window == "full":
-            out[v] = (0, 0, W, H) if np.all(np.isfinite(P[:3])) else (0, 0, 0, 0)
-        else:
-            out[v] = plan_window(models.aabb_corners[o], P, cams[i].astype(np.float64), H, W, float(np.float32(near)))
-    return out
-
-
-def _view_groups(models, view_obj, windows, pair_est, pair_gt, workspace_bytes):
-    """Consecutive pairs (or, without pairs, consecutive views) whose distinct views fit `workspace_bytes`: 8 bytes per window sample and
-    per triangle of a view.  At least one pair (view) per group.  -> [(view ids in order of first use, pair ids or None)]."""
-    nf = (models.face_off[1:] - models.face_off[:-1]).astype(np.int64)
-    cost = 8 * ((windows[:, 2] - windows[:, 0]).astype(np.int64) * (windows[:, 3] - windows[:, 1]) + nf[view_obj]) + 256
-    budget = max(int(workspace_bytes) - 512, 0)
-    groups, views, seen, used, first = [], [], set(), 0, 0
-    if pair_est is None:
-        for v in range(len(view_obj)):
-            if views and used + cost[v] > budget:
-                groups.append((np.array(views, dtype=np.int64), None))
-                views, used = [], 0
-            views.append(v)
-            used += int(cost[v])
-        groups.append((np.array(views, dtype=np.int64), None))
-        return groups
-    for p, (e, g) in enumerate(zip(pair_est.tolist(), pair_gt.tolist())):
-        new = [v for v in dict.fromkeys((e, g)) if v not in seen]
-        add = sum(int(cost[v]) for v in new)
-        if p > first and used + add > budget:
-            groups.append((np.array(views, dtype=np.int64), np.arange(first, p)))
-            views, seen, used, first = [], set(), 0, p
-            new = list(dict.fromkeys((e, g)))
-            add = sum(int(cost[v]) for v in new)
-        views += new
-        seen.update(new)
-        used += add
-    groups.append((np.array(views, dtype=np.int64), np.arange(first, len(pair_est))))
-    return groups
-
-
 def _vsd_launch(models, cams, H, W, view_obj, view_img, poses, windows, groups, near, pair_est=None, pair_gt=None, depth=None,
                 delta=15.0, taus=None, want_depth=False):
     """One pp_vsd_errors call per group -> (vsd, counts, per-view near counts, dense depth or None), device tensors."""
     dev, L = models.device, _lib.lib()
-    if dev.type != "cuda":
-        raise _lib.PicoPoseHipError("picopose_amd runs on the GPU only: build the ObjectModels on a CUDA(HIP) device")
+    scn.require_gpu(dev)
     U, P = len(view_obj), 0 if pair_est is None else len(pair_est)
     T = 1 if taus is None else len(taus)
     taus_h = np.ascontiguousarray(np.zeros(1) if taus is None else taus, dtype=np.float32)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
-    cams_d = up(cams)
     vsd = torch.empty((P, T), dtype=torch.float32, device=dev)
     counts = torch.empty((P, 2 + T), dtype=torch.int32, device=dev)
     near_all = torch.zeros(U, dtype=torch.int32, device=dev)
     dense = torch.empty((U, H, W), dtype=torch.float32, device=dev) if want_depth else None
     need = ctypes.c_size_t()
-    nf = (models.face_off[1:] - models.face_off[:-1]).astype(np.int64)
     for views, pairs in groups:
-        vo, vi = np.ascontiguousarray(view_obj[views]), np.ascontiguousarray(view_img[views])
-        win, pose = np.ascontiguousarray(windows[views]), np.ascontiguousarray(poses[views])
-        zoff = np.zeros(len(views) + 1, dtype=np.int64)
-        np.cumsum((win[:, 2] - win[:, 0]).astype(np.int64) * (win[:, 3] - win[:, 1]), out=zoff[1:])
-        _lib.check(L.pp_vsd_workspace_bytes(int(zoff[-1]), int(nf[vo].sum()), ctypes.byref(need)), "pp_vsd_workspace_bytes")
+        packed = scn.PackedScene(models, cams, H, W, near, view_obj[views], view_img[views], poses[views], windows[views])
+        _lib.check(L.pp_vsd_workspace_bytes(packed.samples, packed.faces, ctypes.byref(need)), "pp_vsd_workspace_bytes")
         ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-        vo_d, vi_d, win_d, pose_d, zoff_d = up(vo), up(vi), up(win), up(pose), up(zoff)
         near_d = torch.empty(len(views), dtype=torch.int32, device=dev)
-        pe = pg = pe_d = pg_d = None
+        pe = pg = pe_d = pg_d = vsd_ptr = counts_ptr = dense_ptr = None
         n_pairs = 0
         if pairs is not None:
             local = {int(v): k for k, v in enumerate(views.tolist())}
             pe = np.array([local[int(v)] for v in pair_est[pairs]], dtype=np.int32)
             pg = np.array([local[int(v)] for v in pair_gt[pairs]], dtype=np.int32)
-            pe_d, pg_d, n_pairs = up(pe), up(pg), len(pairs)
-        p0 = 0 if pairs is None else int(pairs[0])
+            pe_d, pg_d, n_pairs, p0 = torch.from_numpy(pe).to(dev), torch.from_numpy(pg).to(dev), len(pairs), int(pairs[0])
+            vsd_ptr, counts_ptr = vsd.data_ptr() + p0 * T * 4, counts.data_ptr() + p0 * (2 + T) * 4
         ptr = lambda a: None if a is None else a.ctypes.data             # noqa: E731
         dptr = lambda a: None if a is None else a.data_ptr()             # noqa: E731
-        dense_ptr = None
         if want_depth:                                            # (render_depth: the groups are consecutive views)
             dense_ptr = dense.data_ptr() + int(views[0]) * H * W * 4
-        _lib.check(L.pp_vsd_errors(
-            models.vertices.data_ptr(), models.vert_off_d.data_ptr(), models.faces.data_ptr(), models.face_off_d.data_ptr(),
-            models.diameters_d.data_ptr(), models.vert_off.ctypes.data, models.faces_host.ctypes.data, models.face_off.ctypes.data,
-            models.diameters_f32.ctypes.data, len(models.obj_ids), cams_d.data_ptr(), cams.ctypes.data, len(cams), H, W,
-            vo_d.data_ptr(), vi_d.data_ptr(), pose_d.data_ptr(), win_d.data_ptr(), zoff_d.data_ptr(), vo.ctypes.data, vi.ctypes.data,
-            win.ctypes.data, zoff.ctypes.data, len(views), dptr(pe_d), dptr(pg_d), ptr(pe), ptr(pg), n_pairs, dptr(depth), float(delta),
-            taus_h.ctypes.data, T, float(near), ws.data_ptr(), ws.numel(), vsd.data_ptr() + p0 * T * 4 if n_pairs else None,
-            counts.data_ptr() + p0 * (2 + T) * 4 if n_pairs else None, near_d.data_ptr(), dense_ptr, _lib.stream_ptr()), "pp_vsd_errors")
+        _lib.check(L.pp_vsd_errors(ctypes.byref(packed.scene), dptr(pe_d), dptr(pg_d), ptr(pe), ptr(pg), n_pairs, dptr(depth), float(delta),
+                                   taus_h.ctypes.data, T, ws.data_ptr(), ws.numel(), vsd_ptr, counts_ptr, near_d.data_ptr(), dense_ptr,
+                                   _lib.stream_ptr()), "pp_vsd_errors")
         near_all[torch.from_numpy(views).to(dev)] = near_d
     return vsd, counts, near_all, dense
 
@@ -488,71 +330,26 @@ def render_depth(models, obj_ids, R, t, K, resolution, image_index=None, near=1.
     image_index (U,) choosing the camera of each view (default: image 0); R (U, 3, 3), t (U, 3) millimetres; near in millimetres.
     window: "auto" samples the host-planned window of each view (plan_window), "full" the whole frame — the same bits.  The views are
     rendered in as many launch sequences as `workspace_bytes` needs.  U = 0: an empty tensor, no launch.  ValueError as vsd_errors."""
-    obj = _obj_index(models, obj_ids)
+    obj = scn.obj_index(models, obj_ids)
     U = len(obj)
-    _check_scalars(near, window, workspace_bytes)
-    try:
-        H, W = (int(v) for v in resolution)
-    except (TypeError, ValueError):
-        raise ValueError(f"resolution must be (H, W), got {resolution!r}") from None
-    if H <= 0 or W <= 0 or H * W >= 2 ** 31:
+    scn.check_scalars(near, window, workspace_bytes)
+    res = scn.resolution_hw(resolution)
+    if res is None:
+        raise ValueError(f"resolution must be (H, W), got {resolution!r}")
+    H, W = res
+    if not scn.frame_in_range(H, W):
         raise ValueError(f"resolution must be positive with H W < 2^31, got {(H, W)}")
-    Rh, th = _host_f32("R", R, U, (3, 3)), _host_f32("t", t, U, (3,))
-    n_images = 1
-    if not isinstance(K, (list, tuple)) and getattr(K, "ndim", 2) == 3:
-        n_images = int(K.shape[0])
-    cams = _cams(K, n_images)
-    img = _image_index(image_index, U, n_images)
+    Rh, th = scn.host_f32("R", R, U, (3, 3)), scn.host_f32("t", t, U, (3,))
+    n_images = scn.n_images_of(K)
+    cams = scn.cameras(K, n_images)
+    img = scn.image_index(image_index, U, n_images)
     if U == 0:
         return {"depth": torch.empty((0, H, W), dtype=torch.float32, device=models.device), "near_count": 0}
-    poses = _pose44(Rh, th)
-    windows = _windows(models, obj, img, poses, cams, H, W, near, window)
-    groups = _view_groups(models, obj, windows, None, None, workspace_bytes)
+    poses = scn.pose44(Rh, th)
+    windows = scn.view_windows(models, obj, img, poses, cams, H, W, near, window)
+    groups = scn.view_groups(models, obj, windows, None, None, workspace_bytes)
     _, _, near_all, dense = _vsd_launch(models, cams, H, W, obj, img, poses, windows, groups, near, want_depth=True)
     return {"depth": dense, "near_count": int(near_all.sum().item())}
-
-
-def _check_depth(depth, depth_scale):
-    """-> (n_images, H, W, per-image scale float64 or None for float millimetres); ValueError for anything else."""
-    is_t = isinstance(depth, torch.Tensor)
-    if not is_t and not isinstance(depth, np.ndarray):
-        raise ValueError(f"depth must be a numpy array or a torch tensor, got {type(depth).__name__}")
-    if depth.ndim != 3 or 0 in tuple(depth.shape):
-        raise ValueError(f"depth must have shape (n_images, H, W), got {tuple(depth.shape)}")
-    n, H, W = (int(v) for v in depth.shape)
-    if H * W >= 2 ** 31:
-        raise ValueError("depth frames must hold fewer than 2^31 samples")
-    if depth.dtype == (getattr(torch, "uint16", None) if is_t else np.uint16):
-        if depth_scale is None:
-            raise ValueError("uint16 depth is raw: depth_scale (millimetres per unit) is required")
-        try:
-            sc = np.asarray(depth_scale, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError(f"depth_scale must be a number or one per image, got {depth_scale!r}") from None
-        if sc.shape not in ((), (n,)) or not np.all(np.isfinite(sc)) or not np.all(sc > 0):
-            raise ValueError(f"depth_scale must be a positive number or one per image, got {depth_scale!r}")
-        return n, H, W, np.broadcast_to(sc, (n,))
-    if not (depth.dtype.is_floating_point if is_t else np.issubdtype(depth.dtype, np.floating)):
-        raise ValueError(f"depth must be uint16 (raw, with depth_scale) or float millimetres, got {depth.dtype}")
-    if depth_scale is not None:
-        raise ValueError("float depth is millimetres already: depth_scale must be None")
-    return n, H, W, None
-
-
-def _depth_mm(depth, scale, dev):
-    """(n_images, H, W) uint16 raw with its per-image scale, or float millimetres (scale None) -> float32 mm on the device."""
-    is_t = isinstance(depth, torch.Tensor)
-    if scale is None:
-        d = depth if is_t else torch.from_numpy(np.ascontiguousarray(depth, dtype=np.float32))
-        return d.to(device=dev, dtype=torch.float32).contiguous()
-    n, H, W = (int(v) for v in depth.shape)
-    # pp_depth_u16_scaled writes (f32(d) * s) / 1000 in float32: s = f32(1000 depth_scale) gives millimetres
-    s = torch.from_numpy((scale * 1000.0).astype(np.float32)).to(dev)
-    raw = (depth.contiguous().view(torch.int16) if is_t else torch.from_numpy(np.ascontiguousarray(depth).view(np.int16))).to(dev)
-    out = torch.empty((n, H, W), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().pp_depth_u16_scaled(raw.data_ptr(), H * W, n, s.data_ptr(), out.data_ptr(), _lib.stream_ptr()),
-               "pp_depth_u16_scaled")
-    return out
 
 
 def vsd_errors(models, obj_ids, R_est, t_est, R_gt, t_gt, K, depth, image_index=None, depth_scale=None, delta=15.0, taus=VSD_TAUS,
@@ -570,29 +367,28 @@ def vsd_errors(models, obj_ids, R_est, t_est, R_gt, t_gt, K, depth, image_index=
     same bits.  A pose holding a NaN or an infinity gets an empty window: it renders nothing and e = 1 for every tau.  When the views of
     all pairs need more than `workspace_bytes` the pairs are processed in groups, with identical results.  P = 0: empty tensors, no launch.
     ValueError: an object without faces, an unknown obj_id, shape or dtype mismatches, image_index out of range, T outside 1..16."""
-    obj = _obj_index(models, obj_ids)
+    obj = scn.obj_index(models, obj_ids)
     P, dev = len(obj), models.device
-    _check_scalars(near, window, workspace_bytes)
+    scn.check_scalars(near, window, workspace_bytes)
     if not (isinstance(delta, (int, float)) and math.isfinite(delta) and delta > 0):
         raise ValueError(f"delta must be a positive number, got {delta!r}")
     tau = np.asarray(taus, dtype=np.float64)
     if tau.ndim != 1 or not 1 <= len(tau) <= VSD_MAX_TAUS or not np.all(np.isfinite(tau)):
         raise ValueError(f"taus must be 1 .. {VSD_MAX_TAUS} finite numbers, got shape {tau.shape}")
     T = len(tau)
-    Re, te = _host_f32("R_est", R_est, P, (3, 3)), _host_f32("t_est", t_est, P, (3,))
-    Rg, tg = _host_f32("R_gt", R_gt, P, (3, 3)), _host_f32("t_gt", t_gt, P, (3,))
-    n_images, H, W, scale = _check_depth(depth, depth_scale)
-    cams = _cams(K, n_images)
-    img = _image_index(image_index, P, n_images)
+    Re, te = scn.host_f32("R_est", R_est, P, (3, 3)), scn.host_f32("t_est", t_est, P, (3,))
+    Rg, tg = scn.host_f32("R_gt", R_gt, P, (3, 3)), scn.host_f32("t_gt", t_gt, P, (3,))
+    n_images, H, W, scale = scn.check_depth(depth, depth_scale)
+    cams = scn.cameras(K, n_images)
+    img = scn.image_index(image_index, P, n_images)
     if P == 0:
         z = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)     # noqa: E731
         return {"vsd": torch.empty((0, T), dtype=torch.float32, device=dev), "visib_union": z(0), "visib_inter": z(0), "n_far": z(0, T),
                 "n_views": 0, "near_count": 0}
-    if dev.type != "cuda":
-        raise _lib.PicoPoseHipError("picopose_amd runs on the GPU only: build the ObjectModels on a CUDA(HIP) device")
-    depth_d = _depth_mm(depth, scale, dev)
+    scn.require_gpu(dev)
+    depth_d = scn.depth_mm(depth, scale, dev)
     # the distinct views: (image, object, bytes of the float32 pose)
-    Pe, Pg = _pose44(Re, te), _pose44(Rg, tg)
+    Pe, Pg = scn.pose44(Re, te), scn.pose44(Rg, tg)
     index, view_obj, view_img, poses = {}, [], [], []
     pair_est, pair_gt = np.zeros(P, dtype=np.int32), np.zeros(P, dtype=np.int32)
     for p in range(P):
@@ -606,8 +402,8 @@ def vsd_errors(models, obj_ids, R_est, t_est, R_gt, t_gt, K, depth, image_index=
                 poses.append(pose)
             dst[p] = v
     view_obj, view_img, poses = np.array(view_obj, dtype=np.int32), np.array(view_img, dtype=np.int32), np.stack(poses)
-    windows = _windows(models, view_obj, view_img, poses, cams, H, W, near, window)
-    groups = _view_groups(models, view_obj, windows, pair_est, pair_gt, workspace_bytes)
+    windows = scn.view_windows(models, view_obj, view_img, poses, cams, H, W, near, window)
+    groups = scn.view_groups(models, view_obj, windows, pair_est, pair_gt, workspace_bytes)
     vsd, counts, near_all, _ = _vsd_launch(models, cams, H, W, view_obj, view_img, poses, windows, groups, near, pair_est, pair_gt,
                                            depth_d, delta, tau, want_depth=False)
     return {"vsd": vsd, "visib_union": counts[:, 0], "visib_inter": counts[:, 1], "n_far": counts[:, 2:], "n_views": len(poses),

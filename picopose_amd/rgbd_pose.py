@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .scene import depth_u16_scaled
 
 MAX_POINTS = 4096                # correspondences per problem (include/picopose_hip.h)
 DEPTH_UNITS = {"m": 1.0, "mm": 1e-3}
@@ -99,13 +100,7 @@ def depth_on_device(depth, dev, depth_scale=None, depth_unit="m"):
         d = depth if is_t else torch.from_numpy(np.ascontiguousarray(depth))
         d = d.to(device=dev, dtype=torch.float32).contiguous()
         return d if depth_unit == "m" else d * DEPTH_UNITS[depth_unit]
-    n, dH, dW = (int(v) for v in depth.shape)
-    s = torch.from_numpy(np.broadcast_to(np.asarray(depth_scale, dtype=np.float64), (n,)).astype(np.float32)).to(dev)
-    raw = (depth.contiguous().view(torch.int16) if is_t else torch.from_numpy(np.ascontiguousarray(depth).view(np.int16))).to(dev)
-    out = torch.empty((n, dH, dW), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().pp_depth_u16_scaled(raw.data_ptr(), dH * dW, n, s.data_ptr(), out.data_ptr(), _lib.stream_ptr()),
-               "pp_depth_u16_scaled")
-    return out
+    return depth_u16_scaled(depth, np.broadcast_to(np.asarray(depth_scale, dtype=np.float64), (len(depth),)).astype(np.float32), dev)
 
 
 def rgbd_launch(tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts, depth, inlier_dist, image_index=None, iterations=150,

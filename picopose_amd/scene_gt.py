@@ -6,7 +6,7 @@ truth (rle_from_mask, gt_detections).
 The contract is "SCENE GROUND TRUTH" of include/picopose_hip.h (csrc/pp_scene_gt.hip; tests/scene_gt_oracle.py restates it in numpy).
 It is the BOP toolkit's calc_gt_info / calc_gt_masks written from memory: the toolkit cannot be run next to this library, parity
 with its pixels is UNPINNED, and the header lists the known differences (sampling convention, near-plane rule, box convention).
-The planners (windows, view groups, depth conversion, cameras) are evaluation.py's."""
+The planners (windows, view groups, depth conversion, cameras) and the packing of a call's tables are scene.py's."""
 import ctypes
 import math
 
@@ -14,8 +14,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .evaluation import (DEFAULT_WORKSPACE_BYTES, _cams, _check_depth, _check_scalars, _depth_mm, _host_f32, _image_index, _obj_index,
-                         _pose44, _view_groups, _windows)
+from . import scene as scn
+from .scene import DEFAULT_WORKSPACE_BYTES
 
 MASKS = (None, "visib", "all", "both")
 
@@ -41,11 +41,6 @@ def canvas_cams(cams, pad_x, pad_y):
     out[:, 2] = out[:, 2] + np.float32(pad_x)
     out[:, 3] = out[:, 3] + np.float32(pad_y)
     return out
-
-
-def _view_cost(models, view_obj, windows):
-    nf = (models.face_off[1:] - models.face_off[:-1]).astype(np.int64)
-    return 8 * ((windows[:, 2] - windows[:, 0]).astype(np.int64) * (windows[:, 3] - windows[:, 1]) + nf[view_obj]) + 256
 
 
 def image_groups(cost, view_img, frame_bytes, workspace_bytes):
@@ -99,9 +94,9 @@ def scene_gt_info(models, obj_ids, R, t, K, depth=None, resolution=None, image_i
     None or composite=True) a call holds whole images, and ValueError is raised when one image's views alone exceed the bound.
     A pose with a NaN or an infinity renders nothing: zero counts, empty boxes.  U = 0: empty tensors, no launch.
     ValueError as vsd_errors, and for pad, delta (negative or not finite), masks, composite, a missing or mismatching resolution."""
-    obj = _obj_index(models, obj_ids)
+    obj = scn.obj_index(models, obj_ids)
     U, dev = len(obj), models.device
-    _check_scalars(near, window, workspace_bytes)
+    scn.check_scalars(near, window, workspace_bytes)
     if not (isinstance(delta, (int, float)) and not isinstance(delta, bool) and math.isfinite(delta) and delta >= 0):
         raise ValueError(f"delta must be a non-negative number, got {delta!r}")
     if masks not in MASKS:
@@ -110,11 +105,8 @@ def scene_gt_info(models, obj_ids, R, t, K, depth=None, resolution=None, image_i
         raise ValueError(f"composite must be a bool, got {composite!r}")
     res = None
     if resolution is not None:
-        try:
-            res = tuple(int(v) for v in resolution)
-        except (TypeError, ValueError):
-            res = ()
-        if len(res) != 2 or res[0] <= 0 or res[1] <= 0 or res[0] * res[1] >= 2 ** 31:
+        res = scn.resolution_hw(resolution)
+        if res is None or not scn.frame_in_range(*res):
             raise ValueError(f"resolution must be (H, W), positive with H W < 2^31, got {resolution!r}")
     if depth is None:
         if res is None:
@@ -122,20 +114,18 @@ def scene_gt_info(models, obj_ids, R, t, K, depth=None, resolution=None, image_i
         if depth_scale is not None:
             raise ValueError("depth_scale without depth")
         H, W = res
-        n_images, scale = 1, None
-        if not isinstance(K, (list, tuple)) and getattr(K, "ndim", 2) == 3:
-            n_images = int(K.shape[0])
+        n_images, scale = scn.n_images_of(K), None
     else:
-        n_images, H, W, scale = _check_depth(depth, depth_scale)
+        n_images, H, W, scale = scn.check_depth(depth, depth_scale)
         if res is not None and res != (H, W):
             raise ValueError(f"resolution {res} is not the depth images' {(H, W)}")
     pad_x, pad_y = _pad(pad, H, W)
     Hc, Wc = H + 2 * pad_y, W + 2 * pad_x
     if Hc * Wc >= 2 ** 31:
         raise ValueError(f"the padded canvas {Hc} x {Wc} must hold fewer than 2^31 samples")
-    Rh, th = _host_f32("R", R, U, (3, 3)), _host_f32("t", t, U, (3,))
-    cams = _cams(K, n_images)
-    img = _image_index(image_index, U, n_images)
+    Rh, th = scn.host_f32("R", R, U, (3, 3)), scn.host_f32("t", t, U, (3,))
+    cams = scn.cameras(K, n_images)
+    img = scn.image_index(image_index, U, n_images)
     want_all, want_visib = masks in ("all", "both"), masks in ("visib", "both")
     run_composite = bool(composite) or depth is None
 
@@ -156,48 +146,38 @@ def scene_gt_info(models, obj_ids, R, t, K, depth=None, resolution=None, image_i
     ccams = canvas_cams(cams, pad_x, pad_y)
     if not np.all(np.isfinite(ccams)):
         raise ValueError("K plus the pad is not finite in float32")
-    poses = _pose44(Rh, th)
-    windows = _windows(models, obj, img, poses, ccams, Hc, Wc, near, window)
+    poses = scn.pose44(Rh, th)
+    windows = scn.view_windows(models, obj, img, poses, ccams, Hc, Wc, near, window)
     # the order of the calls: as given, or (composite) stably by image, so that a call holds whole images
     if run_composite:
         order = np.argsort(img, kind="stable")
-        groups = image_groups(_view_cost(models, obj[order], windows[order]), img[order], 8 * H * W, workspace_bytes)
+        groups = image_groups(scn.view_cost(models, obj[order], windows[order]), img[order], 8 * H * W, workspace_bytes)
     else:
         order = np.arange(U)
-        groups = [(int(g[0][0]), int(g[0][-1]) + 1, 0, n_images) for g in _view_groups(models, obj, windows, None, None, workspace_bytes)]
-    if dev.type != "cuda":
-        raise _lib.PicoPoseHipError("picopose_amd runs on the GPU only: build the ObjectModels on a CUDA(HIP) device")
+        groups = [(int(g[0][0]), int(g[0][-1]) + 1, 0, n_images) for g in scn.view_groups(models, obj, windows, None, None, workspace_bytes)]
+    scn.require_gpu(dev)
     L = _lib.lib()
-    depth_d = None if depth is None else _depth_mm(depth, scale, dev)
+    depth_d = None if depth is None else scn.depth_mm(depth, scale, dev)
     s_obj, s_img, s_pose, s_win = obj[order], img[order], poses[order], windows[order]
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)     # noqa: E731
     counts, boxes, near_d = i32(U, 3), i32(U, 8), i32(U)
     m_all = u8(U, H, W) if want_all else None
     m_vis = u8(U, H, W) if want_visib else None
     scene_depth = torch.zeros((n_images, H, W), dtype=torch.float32, device=dev) if composite else None
     inst_map = torch.full((n_images, H, W), -1, dtype=torch.int32, device=dev) if composite else None
-    nf = (models.face_off[1:] - models.face_off[:-1]).astype(np.int64)
     need = ctypes.c_size_t()
     off = lambda a, n, size: None if a is None else a.data_ptr() + n * size      # noqa: E731
     for v0, v1, i0, i1 in groups:
-        vo_, vi_ = np.ascontiguousarray(s_obj[v0:v1]), np.ascontiguousarray(s_img[v0:v1] - i0).astype(np.int32)
-        win, pose = np.ascontiguousarray(s_win[v0:v1]), np.ascontiguousarray(s_pose[v0:v1])
-        label = np.ascontiguousarray(order[v0:v1].astype(np.int32))
-        cam, ccam = np.ascontiguousarray(cams[i0:i1]), np.ascontiguousarray(ccams[i0:i1])
-        zoff = np.zeros(v1 - v0 + 1, dtype=np.int64)
-        np.cumsum((win[:, 2] - win[:, 0]).astype(np.int64) * (win[:, 3] - win[:, 1]), out=zoff[1:])
-        _lib.check(L.pp_scene_gt_workspace_bytes(int(zoff[-1]), int(nf[vo_].sum()), (i1 - i0) * H * W if run_composite else 0,
+        packed = scn.PackedScene(models, cams[i0:i1], H, W, near, s_obj[v0:v1], s_img[v0:v1] - i0, s_pose[v0:v1], s_win[v0:v1])
+        ccam = np.ascontiguousarray(ccams[i0:i1])
+        _lib.check(L.pp_scene_gt_workspace_bytes(packed.samples, packed.faces, (i1 - i0) * H * W if run_composite else 0,
                                                  ctypes.byref(need)), "pp_scene_gt_workspace_bytes")
         ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-        vo_d, vi_d, win_d, pose_d, zoff_d, label_d, cam_d, ccam_d = (up(a) for a in (vo_, vi_, win, pose, zoff, label, cam, ccam))
+        label_d, ccam_d = torch.from_numpy(order[v0:v1].astype(np.int32)).to(dev), torch.from_numpy(ccam).to(dev)
         _lib.check(L.pp_scene_gt(
-            models.vertices.data_ptr(), models.vert_off_d.data_ptr(), models.faces.data_ptr(), models.face_off_d.data_ptr(),
-            models.vert_off.ctypes.data, models.faces_host.ctypes.data, models.face_off.ctypes.data, models.diameters_f32.ctypes.data,
-            len(models.obj_ids), cam_d.data_ptr(), cam.ctypes.data, ccam_d.data_ptr(), ccam.ctypes.data, i1 - i0, H, W, pad_x, pad_y,
-            vo_d.data_ptr(), vi_d.data_ptr(), pose_d.data_ptr(), win_d.data_ptr(), zoff_d.data_ptr(), vo_.ctypes.data, vi_.ctypes.data,
-            win.ctypes.data, zoff.ctypes.data, v1 - v0, off(depth_d, i0 * H * W, 4), float(delta), float(near), label_d.data_ptr(), 1,
-            ws.data_ptr(), ws.numel(), off(counts, v0 * 3, 4), off(boxes, v0 * 8, 4), off(near_d, v0, 4), off(m_all, v0 * H * W, 1),
-            off(m_vis, v0 * H * W, 1), off(scene_depth, i0 * H * W, 4), off(inst_map, i0 * H * W, 4), _lib.stream_ptr()), "pp_scene_gt")
+            ctypes.byref(packed.scene), ccam_d.data_ptr(), ccam.ctypes.data, pad_x, pad_y, off(depth_d, i0 * H * W, 4), float(delta),
+            label_d.data_ptr(), 1, ws.data_ptr(), ws.numel(), off(counts, v0 * 3, 4), off(boxes, v0 * 8, 4), off(near_d, v0, 4),
+            off(m_all, v0 * H * W, 1), off(m_vis, v0 * H * W, 1), off(scene_depth, i0 * H * W, 4), off(inst_map, i0 * H * W, 4),
+            _lib.stream_ptr()), "pp_scene_gt")
     if run_composite and not np.array_equal(order, np.arange(U)):  # back to the caller's order
         inv = torch.from_numpy(np.argsort(order, kind="stable")).to(dev)
         counts, boxes, near_d = counts[inv], boxes[inv], near_d[inv]

@@ -12,11 +12,13 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import depth_refine_oracle as do  # noqa: E402
+import scene_tables as st  # noqa: E402
 import vsd_oracle as vo  # noqa: E402
 
 from picopose_amd import depth_refine as dr  # noqa: E402  (absent before the feature: every test here fails without it)
 from picopose_amd import evaluation as ev  # noqa: E402
 from picopose_amd import pipeline  # noqa: E402
+from picopose_amd import scene as scn  # noqa: E402
 
 F = np.float32
 
@@ -132,7 +134,7 @@ def test_window_margin_strips_and_grouping_plan():
     assert dr.grow_window((2, 3, 118, 88), 32, 90, 120) == (0, 0, 120, 90)
     assert dr.grow_window((0, 0, 0, 0), 32, 90, 120) == (0, 0, 0, 0) and dr.grow_window((5, 5, 5, 9), 4, 90, 120) == (0, 0, 0, 0)
     scene, _, poses, wins = do.mixed()
-    obj = ev._obj_index(m, scene["obj_ids"])
+    obj = scn.obj_index(m, scene["obj_ids"])
     nan_pose = np.stack(poses).copy()
     nan_pose[3, 0, 0] = np.nan
     nan_pose[4, :3, 3] = (5000.0, 0, 500.0)                       # off-frame
@@ -217,83 +219,73 @@ def test_depth_refine_abi_argument_validation_needs_no_gpu():
     for args in ((-1, 24, 0), (10, 0, 1), (10, 2 ** 32, 1), (2 ** 62, 1, 1), (10, 5, -1), (10, 5, 11), (2 ** 40, 5, 2 ** 31)):
         assert L.pp_depth_refine_workspace_bytes(*args, ctypes.byref(need)) == -1, args
     assert L.pp_depth_refine_workspace_bytes(10, 10, 1, None) == -1
-    buf = (ctypes.c_char * 16384)()
-    p = ctypes.addressof(buf) + (-ctypes.addressof(buf)) % 256
-    arr = lambda ty, *v: (ty * len(v))(*v)  # noqa: E731
-    i32, f32, i64 = (lambda *v: arr(ctypes.c_int, *v)), (lambda *v: arr(ctypes.c_float, *v)), (lambda *v: arr(ctypes.c_longlong, *v))
-    H, W = 48, 64
-    base = dict(verts=p, vert_off=p, faces=p, face_off=p, diam=p, boxes=p, vert_off_h=i32(0, 4, 7), faces_h=i32(0, 1, 2, 0, 2, 3, 0, 1, 2),
-                face_off_h=i32(0, 2, 3), diam_h=f32(100.0, 50.0), boxes_h=f32(-1, -1, -1, 1, 1, 1, 0, 0, 0, 2, 2, 0), n_obj=2, cams=p,
-                cams_h=f32(100, 100, 32, 24, 90, 95, 30, 20), n_img=2, H=H, W=W, view_obj=p, view_img=p, poses_in=p + 4096, windows=p, zoff=p,
-                soff=p, view_obj_h=i32(0, 0, 1), view_img_h=i32(0, 0, 1), windows_h=i32(0, 0, 10, 10, 54, 38, 64, 48, 5, 5, 5, 9),
-                zoff_h=i64(0, 100, 200, 200), soff_h=i32(0, 2, 4, 4), n_views=3, depth=p, iterations=10, max_distance=100.0, min_points=1000,
-                min_cos=0.1, rcond=1e-6, eps=1e-2, max_translation=100.0, max_rotation=0.5, near=1.0, ws=p, ws_bytes=256 + 1792 + 256 + 4 * 232,
-                poses_out=p, active=p, status=p, n_iterations=p, rank=p, n_points=p, rms_before=p, rms_after=p, near_count=p, trajectory=None,
-                sums=None)
-
-    def call(**kw):
-        a = dict(base, **kw)
-        return L.pp_depth_refine(*[a[k] for k in base], None)
+    buf, p = st.aligned_buffer()
+    i32, f32, i64 = st.i32, st.f32, st.i64
+    scene = dict(st.fields(p), poses=p + 4096)                     # (the input poses must not be poses_out)
+    ws_bytes = 256 + 1792 + 256 + 4 * 232
+    own = dict(boxes=p, boxes_host=f32(-1, -1, -1, 1, 1, 1, 0, 0, 0, 2, 2, 0), view_soff=p, view_soff_host=i32(0, 2, 4, 4), depth=p, iterations=10,
+               max_distance=100.0, min_points=1000, min_cos=0.1, rcond=1e-6, eps=1e-2, max_translation=100.0, max_rotation=0.5, workspace=p,
+               workspace_bytes=ws_bytes, poses_out=p, active=p, status=p, n_iterations=p, rank=p, n_points=p, rms_before=p, rms_after=p,
+               near_count=p, trajectory=None, sums=None)
+    call = st.caller(L.pp_depth_refine, scene, own)
 
     # (a valid argument list would launch: it is never sent here; every call below differs from it in one invalid argument)
-    pointers = [k for k in base if (base[k] is p or k == "poses_in") and k != "ws"]
+    assert call(scene=None) == -1
+    pointers = list(st.DEVICE_TABLES) + [k for k in own if own[k] is p and k != "workspace"]
     assert len(pointers) == 23
     for k in pointers:
         assert call(**{k: None}) == -1, k
-    for k in ("vert_off_h", "faces_h", "face_off_h", "diam_h", "boxes_h", "cams_h", "view_obj_h", "view_img_h", "windows_h", "zoff_h", "soff_h", "ws"):
+    for k in st.HOST_TABLES + ("boxes_host", "view_soff_host", "workspace"):
         assert call(**{k: None}) == -1, k
     nan, inf = float("nan"), float("inf")
-    for kw in ({"poses_in": p}, {"n_obj": 0}, {"n_img": 0}, {"n_views": 0}, {"H": 0}, {"W": -3}, {"H": 50000, "W": 50000}, {"iterations": 0},
+    for kw in ({"poses": p}, {"n_objects": 0}, {"n_images": 0}, {"n_views": 0}, {"H": 0}, {"W": -3}, {"H": 50000, "W": 50000}, {"iterations": 0},
                {"iterations": 1001}, {"max_distance": 0.0}, {"max_distance": inf}, {"max_distance": nan}, {"min_points": 0}, {"min_points": -5},
                {"min_cos": -0.5}, {"min_cos": 1.0}, {"min_cos": nan}, {"rcond": -1.0}, {"rcond": 1.0}, {"rcond": nan}, {"eps": -1.0}, {"eps": inf},
                {"eps": nan}, {"max_translation": 0.0}, {"max_translation": nan}, {"max_rotation": -0.5}, {"max_rotation": inf}, {"near": 0.0},
-               {"near": inf}, {"diam_h": f32(100.0, 0.0)}, {"boxes_h": f32(-1, -1, -1, 1, 1, 1, 0, 0, 0, 2, 2, -1)},
-               {"boxes_h": f32(-1, nan, -1, 1, 1, 1, 0, 0, 0, 2, 2, 0)}, {"cams_h": f32(0, 100, 32, 24, 90, 95, 30, 20)},
-               {"vert_off_h": i32(1, 4, 7)}, {"face_off_h": i32(0, 3, 3)}, {"faces_h": i32(0, 1, 2, 0, 2, 4, 0, 1, 2)}, {"view_obj_h": i32(0, 2, 1)},
-               {"view_img_h": i32(0, -1, 1)}, {"windows_h": i32(0, 0, 10, 10, 55, 38, 65, 48, 5, 5, 5, 9)}, {"zoff_h": i64(0, 100, 200, 201)},
-               {"soff_h": i32(0, 2, 4, 5)}, {"soff_h": i32(0, 1, 3, 3)}, {"soff_h": i32(1, 3, 5, 5)}):
+               {"near": inf}, {"diameters_host": f32(100.0, 0.0)}, {"boxes_host": f32(-1, -1, -1, 1, 1, 1, 0, 0, 0, 2, 2, -1)},
+               {"boxes_host": f32(-1, nan, -1, 1, 1, 1, 0, 0, 0, 2, 2, 0)}, {"cams_host": f32(0, 100, 32, 24, 90, 95, 30, 20)},
+               {"vert_off_host": i32(1, 4, 7)}, {"face_off_host": i32(0, 3, 3)}, {"faces_host": i32(0, 1, 2, 0, 2, 4, 0, 1, 2)},
+               {"view_obj_host": i32(0, 2, 1)}, {"view_img_host": i32(0, -1, 1)}, {"windows_host": i32(0, 0, 10, 10, 55, 38, 65, 48, 5, 5, 5, 9)},
+               {"view_zoff_host": i64(0, 100, 200, 201)}, {"view_soff_host": i32(0, 2, 4, 5)}, {"view_soff_host": i32(0, 1, 3, 3)},
+               {"view_soff_host": i32(1, 3, 5, 5)}):
         assert call(**kw) == -1, kw
-    assert call(ws_bytes=256 + 1792 + 256 + 4 * 232 - 1) == -2 and call(ws=p + 64) == -2 and call(ws_bytes=0) == -2      # PP_EWORKSPACE
+    # PP_EWORKSPACE.  These calls pass every check of the scene before they fail on the workspace, so they are also the guard that the
+    # ctypes layout of _lib.PpScene is the C struct's.
+    assert call(workspace_bytes=ws_bytes - 1) == -2 and call(workspace=p + 64) == -2 and call(workspace_bytes=0) == -2
 
 
 def test_scene_tables_get_the_same_code_from_pp_vsd_errors_and_pp_depth_refine_needs_no_gpu():
-    """The object, camera and view tables are validated once for the two entries: each malformed table below, with everything else
-    well formed, gets PP_EINVAL from both, and a workspace one byte short or misaligned PP_EWORKSPACE from both."""
+    """The object, camera and view tables are validated once for the three entries that take a PpScene: each malformed table below, with
+    everything else well formed, gets PP_EINVAL from pp_vsd_errors, pp_depth_refine and pp_scene_gt (pad (0, 0): the canvas is the
+    frame), all three reading ONE struct instance, and a workspace one byte short or misaligned PP_EWORKSPACE from all three."""
     from picopose_amd import _lib
 
     L = _lib.lib()
-    buf = (ctypes.c_char * 16384)()
-    p = ctypes.addressof(buf) + (-ctypes.addressof(buf)) % 256
-    arr = lambda ty, *v: (ty * len(v))(*v)  # noqa: E731
-    i32, f32, i64 = (lambda *v: arr(ctypes.c_int, *v)), (lambda *v: arr(ctypes.c_float, *v)), (lambda *v: arr(ctypes.c_longlong, *v))
+    buf, p = st.aligned_buffer()
+    i32, f32, i64 = st.i32, st.f32, st.i64
     nan, inf = float("nan"), float("inf")
-    scene = dict(vert_off_h=i32(0, 4, 7), faces_h=i32(0, 1, 2, 0, 2, 3, 0, 1, 2), face_off_h=i32(0, 2, 3), diam_h=f32(100.0, 50.0),
-                 cams_h=f32(100, 100, 32, 24, 90, 95, 30, 20), view_obj_h=i32(0, 0, 1), view_img_h=i32(0, 0, 1),
-                 windows_h=i32(0, 0, 10, 10, 54, 38, 64, 48, 5, 5, 5, 9), zoff_h=i64(0, 100, 200, 200), ws=p, short=0)
     vsd_ws, refine_ws = 256 + 1792 + 5 * 8, 256 + 1792 + 256 + 4 * 232
 
-    def both(**kw):
-        s = dict(scene, **kw)
-        vsd = L.pp_vsd_errors(p, p, p, p, p, s["vert_off_h"], s["faces_h"], s["face_off_h"], s["diam_h"], 2, p, s["cams_h"], 2, 48, 64, p, p, p, p,
-                              p, s["view_obj_h"], s["view_img_h"], s["windows_h"], s["zoff_h"], 3, p, p, i32(0, 2), i32(1, 2), 2, p, 15.0,
-                              f32(0.1, 0.2), 2, 1.0, s["ws"], vsd_ws - s["short"], p, p, p, None, None)
-        refine = L.pp_depth_refine(p, p, p, p, p, p, s["vert_off_h"], s["faces_h"], s["face_off_h"], s["diam_h"],
-                                   f32(-1, -1, -1, 1, 1, 1, 0, 0, 0, 2, 2, 0), 2, p, s["cams_h"], 2, 48, 64, p, p, p + 4096, p, p, p, s["view_obj_h"],
-                                   s["view_img_h"], s["windows_h"], s["zoff_h"], i32(0, 2, 4, 4), 3, p, 10, 100.0, 1000, 0.1, 1e-6, 1e-2, 100.0,
-                                   0.5, 1.0, s["ws"], refine_ws - s["short"], p, p, p, p, p, p, p, p, p, None, None, None)
-        return vsd, refine
+    def three(ws=p, short=0, **kw):
+        s = st.pack(dict(st.fields(p), poses=p + 4096, **kw))
+        sc = ctypes.byref(s)
+        vsd = L.pp_vsd_errors(sc, p, p, i32(0, 2), i32(1, 2), 2, p, 15.0, f32(0.1, 0.2), 2, ws, vsd_ws - short, p, p, p, None, None)
+        refine = L.pp_depth_refine(sc, p, f32(-1, -1, -1, 1, 1, 1, 0, 0, 0, 2, 2, 0), p, i32(0, 2, 4, 4), p, 10, 100.0, 1000, 0.1, 1e-6, 1e-2,
+                                   100.0, 0.5, ws, refine_ws - short, p, p, p, p, p, p, p, p, p, None, None, None)
+        gt = L.pp_scene_gt(sc, p, s.keep["cams_host"], 0, 0, p, 15.0, None, 0, ws, vsd_ws - short, p, p, p, None, None, None, None, None)
+        return vsd, refine, gt
 
     # (the well-formed call would launch: it is never sent; every call below differs from it in one table or in the workspace)
-    cases = {"vert_off[0] != 0": {"vert_off_h": i32(1, 4, 7)}, "non-increasing vert_off": {"vert_off_h": i32(0, 4, 4)},
-             "face index == vertex count": {"faces_h": i32(0, 1, 2, 0, 2, 4, 0, 1, 2)}, "diameter 0": {"diam_h": f32(100.0, 0.0)},
-             "diameter inf": {"diam_h": f32(inf, 50.0)}, "diameter NaN": {"diam_h": f32(100.0, nan)},
-             "fx == 0": {"cams_h": f32(0, 100, 32, 24, 90, 95, 30, 20)}, "non-finite cx": {"cams_h": f32(100, 100, 32, 24, 90, 95, inf, 20)},
-             "view_obj out of range": {"view_obj_h": i32(0, 2, 1)}, "view_img out of range": {"view_img_h": i32(0, -1, 1)},
-             "an object of the call without faces": {"face_off_h": i32(0, 3, 3)},
-             "x1 > W": {"windows_h": i32(0, 0, 10, 10, 55, 38, 65, 48, 5, 5, 5, 9)},
-             "inverted window": {"windows_h": i32(0, 0, 10, 10, 54, 38, 64, 48, 6, 5, 5, 9)},
-             "view_zoff[0] != 0": {"zoff_h": i64(1, 101, 201, 201)}, "view_zoff step is not the area": {"zoff_h": i64(0, 100, 200, 201)}}
+    cases = {"vert_off[0] != 0": {"vert_off_host": i32(1, 4, 7)}, "non-increasing vert_off": {"vert_off_host": i32(0, 4, 4)},
+             "face index == vertex count": {"faces_host": i32(0, 1, 2, 0, 2, 4, 0, 1, 2)}, "diameter 0": {"diameters_host": f32(100.0, 0.0)},
+             "diameter inf": {"diameters_host": f32(inf, 50.0)}, "diameter NaN": {"diameters_host": f32(100.0, nan)},
+             "fx == 0": {"cams_host": f32(0, 100, 32, 24, 90, 95, 30, 20)}, "non-finite cx": {"cams_host": f32(100, 100, 32, 24, 90, 95, inf, 20)},
+             "view_obj out of range": {"view_obj_host": i32(0, 2, 1)}, "view_img out of range": {"view_img_host": i32(0, -1, 1)},
+             "an object of the call without faces": {"face_off_host": i32(0, 3, 3)},
+             "x1 > W": {"windows_host": i32(0, 0, 10, 10, 55, 38, 65, 48, 5, 5, 5, 9)},
+             "inverted window": {"windows_host": i32(0, 0, 10, 10, 54, 38, 64, 48, 6, 5, 5, 9)},
+             "view_zoff[0] != 0": {"view_zoff_host": i64(1, 101, 201, 201)}, "view_zoff step is not the area": {"view_zoff_host": i64(0, 100, 200, 201)}}
     assert len(cases) == 15
     for name, kw in cases.items():
-        assert both(**kw) == (-1, -1), name                                   # PP_EINVAL
-    assert both(short=1) == (-2, -2) and both(ws=p + 8) == (-2, -2)          # PP_EWORKSPACE: one byte short, misaligned by 8
+        assert three(**kw) == (-1, -1, -1), name                             # PP_EINVAL
+    assert three(short=1) == (-2, -2, -2) and three(ws=p + 8) == (-2, -2, -2)      # PP_EWORKSPACE: one byte short, misaligned by 8

@@ -12,6 +12,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import scene_gt_oracle as so  # noqa: E402
+import scene_tables as st  # noqa: E402
 import vsd_oracle as vo  # noqa: E402
 
 from picopose_amd import evaluation as ev  # noqa: E402
@@ -263,43 +264,39 @@ def test_scene_gt_abi_argument_validation_needs_no_gpu():
     for args in ((-1, 24, 0), (10, 0, 0), (10, 2 ** 32, 0), (2 ** 62, 1, 0), (10, 10, -1), (10, 10, 2 ** 62)):
         assert L.pp_scene_gt_workspace_bytes(*args, ctypes.byref(need)) == -1, args
     assert L.pp_scene_gt_workspace_bytes(10, 10, 10, None) == -1
-    buf = (ctypes.c_char * 8192)()
-    p = ctypes.addressof(buf) + (-ctypes.addressof(buf)) % 256
-    arr = lambda ty, *v: (ty * len(v))(*v)  # noqa: E731
-    i32, f32, i64 = (lambda *v: arr(ctypes.c_int, *v)), (lambda *v: arr(ctypes.c_float, *v)), (lambda *v: arr(ctypes.c_longlong, *v))
+    buf, p = st.aligned_buffer()
+    i32, f32, i64 = st.i32, st.f32, st.i64
     H, W = 28, 44                                                  # pad (10, 10): the canvas is 48 x 64
     front = 256 + 1792 + 5 * 8                                     # 200 window samples, 2 + 2 + 1 faces
-    base = dict(verts=p, vert_off=p, faces=p, face_off=p, vert_off_h=i32(0, 4, 7), faces_h=i32(0, 1, 2, 0, 2, 3, 0, 1, 2), face_off_h=i32(0, 2, 3),
-                diam_h=f32(100.0, 50.0), n_obj=2, cams=p, cams_h=f32(100, 100, 22, 14, 90, 95, 20.5, 10), ccams=p,
-                ccams_h=f32(100, 100, 32, 24, 90, 95, 30.5, 20), n_img=2, H=H, W=W, pad_x=10, pad_y=10, view_obj=p, view_img=p, poses=p, windows=p,
-                zoff=p, view_obj_h=i32(0, 0, 1), view_img_h=i32(0, 0, 1), windows_h=i32(0, 0, 10, 10, 54, 38, 64, 48, 5, 5, 5, 9),
-                zoff_h=i64(0, 100, 200, 200), n_views=3, depth=p, delta=15.0, near=1.0, label=p, use_label=1, ws=p, ws_bytes=front, counts=p,
-                boxes=p, near_count=p, mask_all=None, mask_visib=None, scene_depth=None, inst=None)
-
-    def call(**kw):
-        a = dict(base, **kw)
-        return L.pp_scene_gt(*[a[k] for k in base], None)
+    # the FRAME cameras and frame size in the scene; the windows lie on the canvas; the device table `diameters` is not read: null
+    scene = dict(st.fields(p, H, W), cams_host=f32(100, 100, 22, 14, 90, 95, 20.5, 10), diameters=None)
+    own = dict(canvas_cams=p, canvas_cams_host=f32(100, 100, 32, 24, 90, 95, 30.5, 20), pad_x=10, pad_y=10, depth=p, delta=15.0, view_label=p,
+               use_view_label=1, workspace=p, workspace_bytes=front, counts=p, boxes=p, near_count=p, mask_all=None, mask_visib=None,
+               scene_depth=None, instance_map=None)
+    call = st.caller(L.pp_scene_gt, scene, own)
 
     comp = 2304 + 2 * H * W * 8                                    # the front rounded up to 256, then the words of two images
-    for k in [k for k in base if base[k] is p and k not in ("ws", "depth")]:
+    assert call(scene=None) == -1
+    for k in [k for k in st.DEVICE_TABLES if k != "diameters"] + [k for k in own if own[k] is p and k != "depth"] + list(st.HOST_TABLES) + ["canvas_cams_host"]:
         assert call(**{k: None}) == -1, k
-    for k in ("vert_off_h", "faces_h", "face_off_h", "diam_h", "cams_h", "ccams_h", "view_obj_h", "view_img_h", "windows_h", "zoff_h", "ws"):
-        assert call(**{k: None}) == -1, k
-    for kw in ({"n_obj": 0}, {"n_img": 0}, {"n_views": 0}, {"H": 0}, {"W": -3}, {"pad_x": -1, "ccams_h": f32(100, 100, 21, 24, 90, 95, 19.5, 20)},
-               {"pad_y": -1}, {"H": 50000, "W": 50000, "pad_x": 0, "pad_y": 0, "ccams_h": f32(100, 100, 22, 14, 90, 95, 20.5, 10)},
+    for kw in ({"n_objects": 0}, {"n_images": 0}, {"n_views": 0}, {"H": 0}, {"W": -3},
+               {"pad_x": -1, "canvas_cams_host": f32(100, 100, 21, 24, 90, 95, 19.5, 20)}, {"pad_y": -1},
+               {"H": 50000, "W": 50000, "pad_x": 0, "pad_y": 0, "canvas_cams_host": f32(100, 100, 22, 14, 90, 95, 20.5, 10)},
                {"pad_x": 2 ** 30}, {"pad_y": 25000, "pad_x": 25000},
                {"delta": -1.0}, {"delta": float("inf")}, {"delta": float("nan")}, {"near": 0.0}, {"near": float("inf")}, {"near": float("nan")},
-               {"ccams_h": f32(100, 100, 32, 24, 90, 95, 30.5, 20.5)}, {"ccams_h": f32(100, 100, 32, 24, 91, 95, 30.5, 20)},
-               {"ccams_h": f32(100, 100, 22, 14, 90, 95, 20.5, 10)}, {"cams_h": f32(100, 100, 22, 14, 90, float("nan"), 20.5, 10)},
-               {"cams_h": f32(0, 100, 22, 14, 90, 95, 20.5, 10), "ccams_h": f32(0, 100, 32, 24, 90, 95, 30.5, 20)},
-               {"diam_h": f32(100.0, 0.0)}, {"vert_off_h": i32(1, 4, 7)}, {"vert_off_h": i32(0, 4, 4)}, {"face_off_h": i32(0, 2, 1)},
-               {"face_off_h": i32(0, 3, 3)}, {"faces_h": i32(0, 1, 2, 0, 2, 4, 0, 1, 2)}, {"faces_h": i32(0, -1, 2, 0, 2, 3, 0, 1, 2)},
-               {"view_obj_h": i32(0, 2, 1)}, {"view_img_h": i32(0, -1, 1)}, {"windows_h": i32(0, 0, 10, 10, 55, 38, 65, 48, 5, 5, 5, 9)},
-               {"windows_h": i32(0, 0, 10, 10, 54, 39, 64, 49, 5, 5, 5, 9)}, {"windows_h": i32(-1, 0, 9, 10, 54, 38, 64, 48, 5, 5, 5, 9)},
-               {"windows_h": i32(0, 0, 10, 10, 54, 38, 64, 48, 6, 5, 5, 9)}, {"zoff_h": i64(0, 100, 200, 201)}, {"zoff_h": i64(1, 101, 201, 201)}):
+               {"canvas_cams_host": f32(100, 100, 32, 24, 90, 95, 30.5, 20.5)}, {"canvas_cams_host": f32(100, 100, 32, 24, 91, 95, 30.5, 20)},
+               {"canvas_cams_host": f32(100, 100, 22, 14, 90, 95, 20.5, 10)}, {"cams_host": f32(100, 100, 22, 14, 90, float("nan"), 20.5, 10)},
+               {"cams_host": f32(0, 100, 22, 14, 90, 95, 20.5, 10), "canvas_cams_host": f32(0, 100, 32, 24, 90, 95, 30.5, 20)},
+               {"diameters_host": f32(100.0, 0.0)}, {"vert_off_host": i32(1, 4, 7)}, {"vert_off_host": i32(0, 4, 4)}, {"face_off_host": i32(0, 2, 1)},
+               {"face_off_host": i32(0, 3, 3)}, {"faces_host": i32(0, 1, 2, 0, 2, 4, 0, 1, 2)}, {"faces_host": i32(0, -1, 2, 0, 2, 3, 0, 1, 2)},
+               {"view_obj_host": i32(0, 2, 1)}, {"view_img_host": i32(0, -1, 1)}, {"windows_host": i32(0, 0, 10, 10, 55, 38, 65, 48, 5, 5, 5, 9)},
+               {"windows_host": i32(0, 0, 10, 10, 54, 39, 64, 49, 5, 5, 5, 9)}, {"windows_host": i32(-1, 0, 9, 10, 54, 38, 64, 48, 5, 5, 5, 9)},
+               {"windows_host": i32(0, 0, 10, 10, 54, 38, 64, 48, 6, 5, 5, 9)}, {"view_zoff_host": i64(0, 100, 200, 201)},
+               {"view_zoff_host": i64(1, 101, 201, 201)}):
         assert call(**kw) == -1, kw
-    # PP_EWORKSPACE: the front alone with a depth image; the composite's words when it runs (no depth, or an output asked for)
-    assert call(ws_bytes=front - 1) == -2 and call(ws=p + 64) == -2 and call(ws_bytes=0) == -2
-    assert call(depth=None) == -2 and call(depth=None, ws_bytes=comp - 1) == -2
-    assert call(scene_depth=p, ws_bytes=comp - 1) == -2 and call(inst=p, ws_bytes=comp - 1) == -2
-    assert call(mask_all=p, mask_visib=p, ws_bytes=front - 1) == -2
+    # PP_EWORKSPACE: the front alone with a depth image; the composite's words when it runs (no depth, or an output asked for).  These
+    # calls pass every check of the scene first (with `diameters` null), so they also guard the ctypes layout of _lib.PpScene.
+    assert call(workspace_bytes=front - 1) == -2 and call(workspace=p + 64) == -2 and call(workspace_bytes=0) == -2
+    assert call(depth=None) == -2 and call(depth=None, workspace_bytes=comp - 1) == -2
+    assert call(scene_depth=p, workspace_bytes=comp - 1) == -2 and call(instance_map=p, workspace_bytes=comp - 1) == -2
+    assert call(mask_all=p, mask_visib=p, workspace_bytes=front - 1) == -2

@@ -2,6 +2,7 @@
 for both canvases and both windows and under a workspace bound that forces several calls; tied to the existing kernels (vsd_errors'
 visible count, render_depth's coverage); the edge scene, the plate rows and a NaN pose; composite visibility, scene_depth and
 instance_map with the tie rule; determinism across view order, stream and grouping; U = 0; and the three uses end to end."""
+import ctypes
 import functools
 import os
 import sys
@@ -12,10 +13,13 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import detections_oracle as do  # noqa: E402
+import render_oracle as ro  # noqa: E402
 import scene_gt_oracle as so  # noqa: E402
 import vsd_oracle as vo  # noqa: E402
 
+from picopose_amd import _lib  # noqa: E402
 from picopose_amd import evaluation as ev  # noqa: E402
+from picopose_amd import scene as scn  # noqa: E402
 from picopose_amd import scene_gt as sg  # noqa: E402  (absent before the feature: every test here fails without it)
 from picopose_amd.provider import test_batch as tb  # noqa: E402
 from picopose_amd.utils.preprocess import get_bbox  # noqa: E402
@@ -89,6 +93,54 @@ def test_mixed_scene_equals_the_oracle_for_both_canvases_windows_and_groupings()
     assert np.array_equal(vsd["visib_union"].cpu().numpy(), got["px_count_visib"])
     z = ev.render_depth(models, ms["obj_ids"], ms["R_gt"], ms["t_gt"], ms["K"], (vo.H, vo.W), image_index=ms["image_index"])["depth"]
     assert np.array_equal((z > 0).cpu().numpy(), got["mask_all"] == 255)
+    _one_packed_scene_through_both_entries()
+
+
+def _one_packed_scene_through_both_entries():
+    """The same equality without the public functions between the two kernels: ONE scene.PackedScene, and the SAME PpScene instance,
+    goes to pp_vsd_errors (depth_out only) and to pp_scene_gt (pad (0, 0), mask_all, a float depth of zeros).  48 x 64 frame; the
+    12-triangle box and a tetrahedron (made here: the oracles' scenes hold none); four views: the box centred, the tetrahedron cut by
+    the right frame edge (its window is clipped there), the box off-frame (an empty window) and a pose with a NaN (an empty window)."""
+    H, W, K4 = 48, 64, (100.0, 100.0, 31.5, 23.5)
+    box = ro.cube(40.0)
+    tetra = {"vertices": np.array([[30, 30, 30], [30, -30, -30], [-30, 30, -30], [-30, -30, 30]], dtype=F),
+             "faces": np.array([[0, 1, 2], [0, 3, 1], [0, 2, 3], [1, 3, 2]], dtype=np.int32)}
+    objects = {1: {"vertices": box["vertices"], "faces": box["faces"], "info": {"diameter": 140.0}},
+               2: {"vertices": tetra["vertices"], "faces": tetra["faces"], "info": {"diameter": 85.0}}}
+    models = ev.ObjectModels(objects)
+    rng = np.random.default_rng(11)
+    poses = np.stack([vo.pose(vo.random_rotation(rng), t) for t in ((0, 0, 400.0), (120.0, 10.0, 400.0), (2000.0, 0, 400.0), (0, 0, 400.0))]).astype(F)
+    poses[3, 1, 1] = np.nan
+    obj, img = np.array([0, 1, 0, 1], dtype=np.int32), np.zeros(4, dtype=np.int32)
+    cams = np.array([K4], dtype=F)
+    windows = scn.view_windows(models, obj, img, poses, cams, H, W, 1.0, "auto")
+    assert 0 < windows[0, 0] and windows[0, 2] < W and windows[1, 2] == W and 0 < windows[1, 0] and not windows[2:].any()
+    want = np.zeros((4, H, W), dtype=F)
+    for v in (0, 1, 2):
+        want[v] = vo.depth32(objects[int(obj[v]) + 1]["vertices"], objects[int(obj[v]) + 1]["faces"], poses[v], cams[0], H, W)[0]
+    assert (want[0] > 0).sum() > 300 and (want[1][:, -1] > 0).any() and not (want[1][:, 0] > 0).any() and not want[2].any()
+
+    packed = scn.PackedScene(models, cams, H, W, 1.0, obj, img, poses, windows)
+    L, dev, need = _lib.lib(), models.device, ctypes.c_size_t()
+    _lib.check(L.pp_vsd_workspace_bytes(packed.samples, packed.faces, ctypes.byref(need)), "pp_vsd_workspace_bytes")
+    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)  # noqa: E731
+    dense, near_vsd, near_gt, counts, boxes = torch.empty((4, H, W), dtype=torch.float32, device=dev), i32(4), i32(4), i32(4, 3), i32(4, 8)
+    mask_all, zeros = torch.empty((4, H, W), dtype=torch.uint8, device=dev), torch.zeros((1, H, W), dtype=torch.float32, device=dev)
+    tau = np.zeros(1, dtype=F)
+    sc = ctypes.byref(packed.scene)
+    _lib.check(L.pp_vsd_errors(sc, None, None, None, None, 0, None, 15.0, tau.ctypes.data, 1, ws.data_ptr(), ws.numel(), None, None,
+                               near_vsd.data_ptr(), dense.data_ptr(), _lib.stream_ptr()), "pp_vsd_errors")
+    # pad (0, 0): the canvas cameras are the frame cameras, so the scene's own tables serve as both
+    _lib.check(L.pp_scene_gt(sc, packed.scene.cams, packed.scene.cams_host, 0, 0, zeros.data_ptr(), 15.0, None, 0, ws.data_ptr(), ws.numel(),
+                             counts.data_ptr(), boxes.data_ptr(), near_gt.data_ptr(), mask_all.data_ptr(), None, None, None,
+                             _lib.stream_ptr()), "pp_scene_gt")
+    torch.cuda.synchronize()
+    z, m, c = dense.cpu().numpy(), mask_all.cpu().numpy(), counts.cpu().numpy()
+    assert np.array_equal(z.view(np.int32), want.view(np.int32))
+    assert m.dtype == np.uint8 and np.array_equal(m, 255 * (z > 0).astype(np.uint8)) and np.array_equal(m, 255 * (want > 0).astype(np.uint8))
+    assert np.array_equal(c[:, 0], (z > 0).reshape(4, -1).sum(axis=1)) and np.array_equal(c[:, 0], (want > 0).reshape(4, -1).sum(axis=1))
+    assert c[2:].tolist() == [[0, 0, 0]] * 2 and not near_vsd.cpu().numpy().any() and not near_gt.cpu().numpy().any()
 
 
 @gpu

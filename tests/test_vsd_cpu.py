@@ -10,9 +10,11 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import render_oracle as ro  # noqa: E402
+import scene_tables as st  # noqa: E402
 import vsd_oracle as vo  # noqa: E402
 
 from picopose_amd import evaluation as ev  # noqa: E402
+from picopose_amd import scene as scn  # noqa: E402
 from picopose_amd.evaluation import vsd_errors  # noqa: E402,F401  (absent before the feature: every test here fails without it)
 
 F = np.float32
@@ -247,11 +249,11 @@ def test_view_groups_split_the_pairs_under_the_workspace_bound():
     view_obj = np.array([0, 0, 1, 1, 1], dtype=np.int32)
     windows = np.array([[0, 0, 10, 10]] * 5, dtype=np.int32)
     pe, pg = np.array([0, 2, 3], dtype=np.int32), np.array([1, 4, 4], dtype=np.int32)
-    one = ev._view_groups(m, view_obj, windows, pe, pg, 1 << 30)
+    one = scn.view_groups(m, view_obj, windows, pe, pg, 1 << 30)
     assert len(one) == 1 and one[0][0].tolist() == [0, 1, 2, 4, 3] and one[0][1].tolist() == [0, 1, 2]
-    tiny = ev._view_groups(m, view_obj, windows, pe, pg, 1)
+    tiny = scn.view_groups(m, view_obj, windows, pe, pg, 1)
     assert [g[0].tolist() for g in tiny] == [[0, 1], [2, 4], [3, 4]] and [g[1].tolist() for g in tiny] == [[0], [1], [2]]
-    assert [g[0].tolist() for g in ev._view_groups(m, view_obj, windows, None, None, 1)] == [[0], [1], [2], [3], [4]]
+    assert [g[0].tolist() for g in scn.view_groups(m, view_obj, windows, None, None, 1)] == [[0], [1], [2], [3], [4]]
 
 
 def test_vsd_abi_argument_validation_needs_no_gpu():
@@ -265,36 +267,33 @@ def test_vsd_abi_argument_validation_needs_no_gpu():
     for args in ((-1, 24), (10, 0), (10, 2 ** 32), (2 ** 62, 1)):
         assert L.pp_vsd_workspace_bytes(*args, ctypes.byref(need)) == -1, args
     assert L.pp_vsd_workspace_bytes(10, 10, None) == -1
-    buf = (ctypes.c_char * 8192)()
-    p = ctypes.addressof(buf) + (-ctypes.addressof(buf)) % 256
-    arr = lambda ty, *v: (ty * len(v))(*v)  # noqa: E731
-    i32, f32, i64 = (lambda *v: arr(ctypes.c_int, *v)), (lambda *v: arr(ctypes.c_float, *v)), (lambda *v: arr(ctypes.c_longlong, *v))
-    H, W = 48, 64
-    base = dict(verts=p, vert_off=p, faces=p, face_off=p, diam=p, vert_off_h=i32(0, 4, 7), faces_h=i32(0, 1, 2, 0, 2, 3, 0, 1, 2),
-                face_off_h=i32(0, 2, 3), diam_h=f32(100.0, 50.0), n_obj=2, cams=p, cams_h=f32(100, 100, 32, 24, 90, 95, 30, 20), n_img=2, H=H, W=W,
-                view_obj=p, view_img=p, poses=p, windows=p, zoff=p, view_obj_h=i32(0, 0, 1), view_img_h=i32(0, 0, 1),
-                windows_h=i32(0, 0, 10, 10, 54, 38, 64, 48, 5, 5, 5, 9), zoff_h=i64(0, 100, 200, 200), n_views=3, pe=p, pg=p, pe_h=i32(0, 2),
-                pg_h=i32(1, 2), n_pairs=2, depth=p, delta=15.0, taus_h=f32(0.1, 0.2), T=2, near=1.0, ws=p, ws_bytes=256 + 1792 + 5 * 8, vsd=p,
-                counts=p, near_count=p, depth_out=None)
+    buf, p = st.aligned_buffer()
+    i32, f32, i64 = st.i32, st.f32, st.i64
+    scene = st.fields(p)
+    ws_bytes = 256 + 8 * st.WINDOW_SAMPLES + 192 + 8 * st.VIEW_FACES          # 1600 z-buffer bytes rounded up to 1792
+    own = dict(pair_est=p, pair_gt=p, pair_est_host=i32(0, 2), pair_gt_host=i32(1, 2), n_pairs=2, depth=p, delta=15.0, taus_host=f32(0.1, 0.2),
+               n_taus=2, workspace=p, workspace_bytes=ws_bytes, vsd=p, counts=p, near_count=p, depth_out=None)
+    call = st.caller(L.pp_vsd_errors, scene, own)
 
-    def call(**kw):
-        a = dict(base, **kw)
-        return L.pp_vsd_errors(*[a[k] for k in base], None)
-
-    nulls = [k for k in base if base[k] is p and k not in ("ws",)]
-    for k in nulls:
+    # (a valid argument list would launch: it is never sent here; every call below differs from it in one invalid argument)
+    assert call(scene=None) == -1
+    for k in st.DEVICE_TABLES + st.HOST_TABLES + tuple(k for k, v in own.items() if v is p or isinstance(v, ctypes.Array)):
         assert call(**{k: None}) == -1, k
-    for k in ("vert_off_h", "faces_h", "face_off_h", "diam_h", "cams_h", "view_obj_h", "view_img_h", "windows_h", "zoff_h", "pe_h", "pg_h", "taus_h", "ws"):
-        assert call(**{k: None}) == -1, k
-    for kw in ({"n_obj": 0}, {"n_img": 0}, {"n_views": 0}, {"n_pairs": -1}, {"n_pairs": 0}, {"H": 0}, {"W": -3}, {"H": 50000, "W": 50000}, {"T": 0}, {"T": 17},
-               {"delta": 0.0}, {"delta": float("inf")}, {"delta": float("nan")}, {"near": 0.0}, {"near": float("inf")}, {"taus_h": f32(0.1, float("nan"))},
-               {"diam_h": f32(100.0, 0.0)}, {"diam_h": f32(float("inf"), 50.0)}, {"cams_h": f32(0, 100, 32, 24, 90, 95, 30, 20)},
-               {"cams_h": f32(100, 100, 32, 24, 90, float("nan"), 30, 20)}, {"vert_off_h": i32(1, 4, 7)}, {"vert_off_h": i32(0, 4, 4)},
-               {"face_off_h": i32(0, 2, 1)}, {"face_off_h": i32(0, 3, 3)},                                   # (object 1 of view 2 has no faces)
-               {"faces_h": i32(0, 1, 2, 0, 2, 4, 0, 1, 2)}, {"faces_h": i32(0, 1, 2, 0, 2, 3, 0, 1, 3)}, {"faces_h": i32(0, -1, 2, 0, 2, 3, 0, 1, 2)},
-               {"view_obj_h": i32(0, 2, 1)}, {"view_img_h": i32(0, -1, 1)}, {"windows_h": i32(0, 0, 10, 10, 55, 38, 65, 48, 5, 5, 5, 9)},
-               {"windows_h": i32(0, 0, 10, 10, 54, 39, 64, 49, 5, 5, 5, 9)}, {"windows_h": i32(-1, 0, 9, 10, 54, 38, 64, 48, 5, 5, 5, 9)},
-               {"windows_h": i32(0, 0, 10, 10, 54, 38, 64, 48, 6, 5, 5, 9)}, {"zoff_h": i64(0, 100, 200, 201)}, {"zoff_h": i64(1, 101, 201, 201)},
-               {"pe_h": i32(0, 3)}, {"pg_h": i32(-1, 2)}, {"pg_h": i32(1, 0)}, {"pe_h": i32(2, 2), "pg_h": i32(0, 2)}):
+    for kw in ({"n_objects": 0}, {"n_images": 0}, {"n_views": 0}, {"n_pairs": -1}, {"n_pairs": 0}, {"H": 0}, {"W": -3}, {"H": 50000, "W": 50000},
+               {"n_taus": 0}, {"n_taus": 17},
+               {"delta": 0.0}, {"delta": float("inf")}, {"delta": float("nan")}, {"near": 0.0}, {"near": float("inf")}, {"taus_host": f32(0.1, float("nan"))},
+               {"diameters_host": f32(100.0, 0.0)}, {"diameters_host": f32(float("inf"), 50.0)}, {"cams_host": f32(0, 100, 32, 24, 90, 95, 30, 20)},
+               {"cams_host": f32(100, 100, 32, 24, 90, float("nan"), 30, 20)}, {"vert_off_host": i32(1, 4, 7)}, {"vert_off_host": i32(0, 4, 4)},
+               {"face_off_host": i32(0, 2, 1)}, {"face_off_host": i32(0, 3, 3)},                             # (object 1 of view 2 has no faces)
+               {"faces_host": i32(0, 1, 2, 0, 2, 4, 0, 1, 2)}, {"faces_host": i32(0, 1, 2, 0, 2, 3, 0, 1, 3)},
+               {"faces_host": i32(0, -1, 2, 0, 2, 3, 0, 1, 2)},
+               {"view_obj_host": i32(0, 2, 1)}, {"view_img_host": i32(0, -1, 1)}, {"windows_host": i32(0, 0, 10, 10, 55, 38, 65, 48, 5, 5, 5, 9)},
+               {"windows_host": i32(0, 0, 10, 10, 54, 39, 64, 49, 5, 5, 5, 9)}, {"windows_host": i32(-1, 0, 9, 10, 54, 38, 64, 48, 5, 5, 5, 9)},
+               {"windows_host": i32(0, 0, 10, 10, 54, 38, 64, 48, 6, 5, 5, 9)}, {"view_zoff_host": i64(0, 100, 200, 201)},
+               {"view_zoff_host": i64(1, 101, 201, 201)},
+               {"pair_est_host": i32(0, 3)}, {"pair_gt_host": i32(-1, 2)}, {"pair_gt_host": i32(1, 0)},
+               {"pair_est_host": i32(2, 2), "pair_gt_host": i32(0, 2)}):
         assert call(**kw) == -1, kw
-    assert call(ws_bytes=256 + 1792 + 5 * 8 - 1) == -2 and call(ws=p + 64) == -2 and call(ws_bytes=0) == -2      # PP_EWORKSPACE
+    # PP_EWORKSPACE.  These calls pass every check of the scene before they fail on the workspace, so they are also the guard that the
+    # ctypes layout of _lib.PpScene is the C struct's: a shifted member would fail a scene check with -1 instead.
+    assert call(workspace_bytes=ws_bytes - 1) == -2 and call(workspace=p + 64) == -2 and call(workspace_bytes=0) == -2

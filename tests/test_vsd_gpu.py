@@ -16,6 +16,7 @@ import render_oracle as ro  # noqa: E402
 import vsd_oracle as vo  # noqa: E402
 
 from picopose_amd import evaluation as ev  # noqa: E402
+from picopose_amd import scene as scn  # noqa: E402
 from picopose_amd.evaluation import vsd_errors  # noqa: E402,F401  (absent before the feature)
 
 gpu = pytest.mark.gpu
@@ -188,7 +189,7 @@ def test_one_by_one_and_empty_windows(monkeypatch):
             out[v] = wins[int(p)]
         return out
 
-    monkeypatch.setattr(ev, "_windows", windows)
+    monkeypatch.setattr(scn, "view_windows", windows)
     got = _run(models, scene, rows=rows)
     for k, p in enumerate(rows.tolist()):
         o = int(scene["obj_ids"][p])
