@@ -1430,6 +1430,56 @@ int pp_scene_composite(const unsigned char* layers_rgba, const float* layers_dep
                        unsigned char* mask_visib, void* stream);
 int pp_depth_quantize_u16(const float* depth_m, long long n, float units_per_metre, unsigned short* out, void* stream);
 
+/* -------------------------------------------------------------------------
+ * PROPOSAL LABELLING: which onboarded object a class-agnostic mask proposal is, and how sure (csrc/pp_proposals.hip;
+ * picopose_amd/proposals.py plans every call; tests/proposal_oracle.py restates this text in numpy float64).  CNOS's matching stage,
+ * written from its published description: cls-token descriptors, cosine similarity to every template of every object, the mean of
+ * the top-k templates per object, arg-max over objects, then mask NMS on the host from the intersection table below.  Parity with
+ * CNOS's own code is unpinned.  All pointers are device pointers unless named *_host; all work is enqueued on `stream`, nothing
+ * synchronises; no entry uses atomics.  Finite inputs are the caller's contract everywhere: a NaN or an infinity in a descriptor
+ * gives unspecified scores, labels and views (never an access outside the buffers).
+ *
+ * pp_descriptor_normalize: y[r] = x[r] / max(||x[r]||_2, eps) for the n rows of x (n, C) fp32 (y is another buffer).  The sum of squares of a
+ * row is accumulated in THE ROW ORDER: lane l of the row's wave adds the elements l, l + 64, ... in ascending order with one fma
+ * each, and the 64 lane sums are folded by a butterfly over the lane masks 32, 16, 8, 4, 2, 1; then one sqrtf, one maximum and one
+ * division per element.  A zero row gives a zero row.  PP_EINVAL: a null pointer, n or C <= 0, eps not positive.
+ *
+ * pp_proposal_match: query (P, C) and bank (sum T, C) hold unit rows (pp_descriptor_normalize's); offsets (O + 1 int32): the
+ * templates of object o are the bank rows [offsets[o], offsets[o + 1]), T_o >= 1 of them; offsets_host is the HOST copy, validated
+ * before the launch.  cos(p, t) = the dot product of query row p and a template row in THE DOT ORDER: lane l adds the products of
+ * the elements 4 c .. 4 c + 3 of its 16-byte chunks c = l, l + 64, ... in ascending element order, one fma each, starting from 0;
+ * the 64 lane sums are folded by the butterfly above.  The order depends on C alone — not on P, O, T, the proposal's place in its
+ * tile or the wave that computes it — so bit-equal rows give bit-equal cosines.  With k = min(topk, T_o):
+ *   score (P, O) fp32  = (the k largest cos(p, t) of object o, added largest first) / k   (one division);
+ *   view  (P, O) int32 = the t - offsets[o] of the largest cos(p, t); among equal ones the lowest;
+ *   label (P) int32    = the o of the largest score[p][o]; among equal ones the lowest;
+ *   best  (P) fp32     = score[p][label[p]].
+ * One workgroup of four waves per (tile of PP_MATCH_TILE proposals, object) stages the tile's rows in LDS (PP_MATCH_TILE * C * 4
+ * bytes: 64 KB at PP_MATCH_MAX_C, the largest C the staging holds); a second small launch takes the arg-max over objects.
+ * PP_EINVAL (before any launch): a null pointer; P, O or C <= 0; O > 65535; C not a multiple of 4 or above PP_MATCH_MAX_C; topk < 1
+ * or > PP_MATCH_MAX_TOPK; query or bank not 16-byte aligned; offsets_host not starting at 0, decreasing or leaving an object empty.
+ *
+ * pp_rle_pack_bits: the run-end tables of pp_detections_crop (run_ends, run_offset, run_offset_host: cumulative COCO run ends over
+ * the column-major mask of hw = H * W pixels) -> bits (n, words) uint32, words = ceil(hw / 32): bit i of word w of mask d is pixel
+ * 32 w + i in column-major order (x * H + y), the bits past hw in the last word are 0; area (n) int32 = the mask's pixel count.
+ * PP_EINVAL: a null pointer, n <= 0 or > PP_MASK_MAX_N, n_runs <= 0, hw <= 0, words != ceil(hw / 32), run_offset_host decreasing,
+ * negative or past n_runs.
+ *
+ * pp_mask_intersections: bits (n, words) -> inter (n, n) int32, inter[i][j] = the sum over the words of popcount(bits[i][w] &
+ * bits[j][w]): symmetric, its diagonal is the area.  A workgroup owns 8 x 8 pairs, four threads per pair, and stages 64 words of its 16 rows
+ * per step in LDS, the rows 68 words apart (conflict-free 4-byte reads).  PP_EINVAL: a null pointer, n <= 0 or > PP_MASK_MAX_N, words <= 0.
+ * ------------------------------------------------------------------------- */
+#define PP_MATCH_TILE 16
+#define PP_MATCH_MAX_C 1024
+#define PP_MATCH_MAX_TOPK 8
+#define PP_MASK_MAX_N 4096
+int pp_descriptor_normalize(const float* x, int n, int C, float eps, float* y, void* stream);
+int pp_proposal_match(const float* query, int P, const float* bank, const int* offsets, const int* offsets_host, int O, int C,
+                      int topk, float* score, int* view, int* label, float* best, void* stream);
+int pp_rle_pack_bits(const int* run_ends, int n_runs, const int* run_offset, const int* run_offset_host, int n, int hw, int words,
+                     unsigned* bits, int* area, void* stream);
+int pp_mask_intersections(const unsigned* bits, int n, int words, int* inter, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

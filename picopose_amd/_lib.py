@@ -252,6 +252,10 @@ def lib():
         L.pp_scene_composite_workspace_bytes.argtypes = [i32, i32, i32, c.POINTER(sz)]
         L.pp_scene_composite.argtypes = [vp] * 4 + [i32] * 4 + [vp] * 6 + [sz] + [vp] * 7
         L.pp_depth_quantize_u16.argtypes = [vp, ll, f32, vp, vp]
+        L.pp_descriptor_normalize.argtypes = [vp, i32, i32, f32, vp, vp]
+        L.pp_proposal_match.argtypes = [vp, i32, vp, vp, c.POINTER(i32), i32, i32, i32, vp, vp, vp, vp, vp]
+        L.pp_rle_pack_bits.argtypes = [vp, i32, vp, c.POINTER(i32), i32, i32, i32, vp, vp, vp]
+        L.pp_mask_intersections.argtypes = [vp, i32, i32, vp, vp]
         _lib = L
     return _lib
 

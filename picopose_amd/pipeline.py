@@ -336,6 +336,33 @@ def infer_detections(net, image_u8, detections, K, templates_data, obj_idxs, **k
     return infer_image(net, data, templates_data, **kw), data
 
 
+LABEL_KEYS = ("topk", "min_score", "max_detections", "nms_iou", "min_area_px", "time")       # label_proposals' own
+LABEL_SHARED_KEYS = ("scene_id", "img_id", "img_size", "minimum_n_point", "bs", "device")       # ... and those both steps read
+
+
+def infer_proposals(net, image_u8, proposals, K, templates_data, bank, **kw):
+    """One decoded test image and a class-agnostic segmenter's mask proposals -> (preds_image, data, detections):
+    proposals.label_proposals against `bank` (proposals.describe_templates of the same `templates_data`, in the same object order:
+    object id bank.obj_ids[o] is bank row o of `templates_data`), then infer_detections on the labelled records.  The keywords of
+    LABEL_KEYS go to label_proposals, those of LABEL_SHARED_KEYS to both steps, every other one to infer_detections —
+    `rgb_mask_flag` among them, which is the pose network's there (the labelling keeps its own default: masked crops).
+    detections: the records, best first, one per entry of preds_image.  ([], None, []) when no proposal survives the labelling or
+    the score filter."""
+    from .proposals import label_proposals
+
+    lkw = {k: kw.pop(k) for k in LABEL_KEYS if k in kw}
+    lkw.update({k: kw[k] for k in LABEL_SHARED_KEYS if k in kw})
+    detections = label_proposals(net, image_u8, proposals, bank, **lkw)
+    if not detections:
+        return [], None, []
+    obj_idxs = {obj_id: o for o, obj_id in enumerate(bank.obj_ids)}
+    preds_image, data = infer_detections(net, image_u8, detections, K, templates_data, obj_idxs, **kw)
+    if data is None:
+        return [], None, []
+    kept = [d for d in detections if d["score"] > kw.get("seg_filter_score", 0.0)]
+    return preds_image, data, kept
+
+
 def _collect(pending, hyp, net, pnp_refine=None):
     handle, s2_host, ev, B, inputs, rgbd = pending
     rot, tvec, ratio, ok = pnp_collect(handle, hyp, B)
