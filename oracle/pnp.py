@@ -30,7 +30,7 @@ _M32 = 0xFFFFFFFF
 
 
 def hash32(x):
-    """The sampling hash of csrc/pp_pnp.hip (lowbias32)."""
+    """The sampling hash of the RANSAC kernels (lowbias32: aug_mix of csrc/pp_hash_dev.h)."""
     x &= _M32
     x ^= x >> 16
     x = (x * 0x7FEB352D) & _M32
@@ -40,11 +40,12 @@ def hash32(x):
     return x
 
 
-def sample_indices(prob, h, npts):
-    """5 distinct indices of hypothesis h of problem `prob` (same sequence as the HIP kernel)."""
+def sample_indices(prob, h, npts, sample=SAMPLE):
+    """The `sample` distinct indices of hypothesis h of problem `prob` (its index in the batch): ransac_sample of
+    csrc/pp_ransac_dev.h, the sequence of both RANSAC kernels (5 for the PnP, 3 for the RGB-D solver)."""
     s = hash32(((0x9E3779B9 * (prob + 1)) & _M32) ^ ((h * 7919 + 17) & _M32))
     idx = []
-    while len(idx) < SAMPLE:
+    while len(idx) < sample:
         s = hash32((s + 0x6D2B79F5) & _M32)
         c = s % npts
         if c not in idx:

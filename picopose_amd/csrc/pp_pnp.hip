@@ -11,20 +11,22 @@
 // test, EPnP refit on the inlier set.  Sampling uses a counter-based hash, not OpenCV's RNG, and
 // all 150 iterations are run (OpenCV stops early at 99 % confidence): parity with cv2 is
 // "unpinned"  and is defined by known-answer tests instead.  fp64 throughout.
+//
+// The rules this solver shares with the RGB-D solver (pp_rgbd_pose.hip) are stated once, in pp_ransac_dev.h: the workgroup
+// shape and the capacities (NT, NW, MAXP, MAXH), the cyclic Jacobi (jacobi_sym), the fixed-order block sum, the sampling
+// sequence (ransac_sample), the winner's tie rule (ransac_winner), the failure outputs and the object-frame source point.
+// What stays here is the PnP's own: EPnP with its 12x12 one-sided Jacobi, the scoring pass, the refit and the LM tail.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/picopose_hip.h"
 #include "pp_common.h"
+#include "pp_ransac_dev.h"           // NT, NW, MAXP, MAXH and the rules shared with pp_rgbd_pose.hip
 
 namespace {
 
-constexpr int NT = 512;           // 8 waves, one workgroup per CU (the correspondences of a problem fill most of the LDS)
-constexpr int NW = NT / 64;
 constexpr int GL = 16;            // lanes of a solver group (12 of them own a column of the 12x12 system)
 constexpr int NG = NT / GL;       // solver groups per workgroup: RANSAC hypotheses are solved NG at a time
-constexpr int MAXP = 4096;
-constexpr int MAXH = 256;         // RANSAC hypotheses kept per problem
 constexpr int HB = 128;           // hypotheses per batch (their null-space vectors wait in LDS between the two phases)
 constexpr int SAMPLE = 5;         // minimal sample size of solvePnPRansac for EPNP
 
@@ -33,57 +35,29 @@ constexpr int SAMPLE = 5;         // minimal sample size of solvePnPRansac for E
 // (a per-lane matrix with run-time indices lives in scratch memory, whose latency made the first version of this kernel
 // spend 9 ms on 160 problems).
 
-#define PP_JROT3(A, V, p, q)                                                                   \
-    {                                                                                          \
-        const double apq = A[p][q];                                                            \
-        if (fabs(apq) >= 1e-300) {                                                             \
-            const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);                            \
-            const double t_ = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0)); \
-            const double c_ = 1.0 / sqrt(t_ * t_ + 1.0), s_ = t_ * c_;                         \
-            _Pragma("unroll") for (int k_ = 0; k_ < 3; ++k_) {                                 \
-                const double akp = A[k_][p], akq = A[k_][q];                                   \
-                A[k_][p] = c_ * akp - s_ * akq;                                                \
-                A[k_][q] = s_ * akp + c_ * akq;                                                \
-            }                                                                                  \
-            _Pragma("unroll") for (int k_ = 0; k_ < 3; ++k_) {                                 \
-                const double apk = A[p][k_], aqk = A[q][k_];                                   \
-                A[p][k_] = c_ * apk - s_ * aqk;                                                \
-                A[q][k_] = s_ * apk + c_ * aqk;                                                \
-            }                                                                                  \
-            _Pragma("unroll") for (int k_ = 0; k_ < 3; ++k_) {                                 \
-                const double vpk = V[p][k_], vqk = V[q][k_];                                   \
-                V[p][k_] = c_ * vpk - s_ * vqk;                                                \
-                V[q][k_] = s_ * vpk + c_ * vqk;                                                \
-            }                                                                                  \
-        }                                                                                      \
+// exchanges eigenpairs I and J (I < J) when w[J] < w[I]
+template <int I, int J>
+__device__ __forceinline__ void cswap3(double (&w)[3], double (&V)[3][3]) {
+    if (w[J] < w[I]) {
+        const double tw = w[I]; w[I] = w[J]; w[J] = tw;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double tv = V[I][k]; V[I][k] = V[J][k]; V[J][k] = tv;
+        }
     }
+}
 
-#define PP_CSWAP3(w, V, i, j)                                   \
-    if (w[j] < w[i]) {                                          \
-        const double tw_ = w[i]; w[i] = w[j]; w[j] = tw_;       \
-        _Pragma("unroll") for (int k_ = 0; k_ < 3; ++k_) {      \
-            const double tv_ = V[i][k_]; V[i][k_] = V[j][k_]; V[j][k_] = tv_; \
-        }                                                       \
-    }
-
-// cyclic Jacobi eigen-decomposition of a symmetric 3x3 matrix: w ascending, V[k] = eigenvector k (rows)
+// eigen-decomposition of a symmetric 3x3 matrix (cyclic Jacobi): w ascending, V[k] = eigenvector k (rows)
 __device__ inline void eig3_sym(double (&A)[3][3], double (&w)[3], double (&V)[3][3]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
-        const double diag = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
-        if (off <= 1e-30 * (diag + 1e-300)) break;
-        PP_JROT3(A, V, 0, 1)
-        PP_JROT3(A, V, 0, 2)
-        PP_JROT3(A, V, 1, 2)
-    }
+    jacobi_sym<3>(A, V);
     w[0] = A[0][0]; w[1] = A[1][1]; w[2] = A[2][2];
     // selection sort order of the first version (min to slot 0, then min of the rest to slot 1)
-    if (w[1] < w[0] && w[1] <= w[2]) { PP_CSWAP3(w, V, 0, 1) } else if (w[2] < w[0] && w[2] < w[1]) { PP_CSWAP3(w, V, 0, 2) }
-    PP_CSWAP3(w, V, 1, 2)
+    // (two plain ifs, not if / else if: the stores of two sibling branches to different rows are merged into one store through
+    // a run-time pointer, and those rows of V then live in scratch memory)
+    const bool first = w[1] < w[0] && w[1] <= w[2], second = !first && w[2] < w[0] && w[2] < w[1];
+    if (first) cswap3<0, 1>(w, V);
+    if (second) cswap3<0, 2>(w, V);
+    cswap3<1, 2>(w, V);
 }
 
 // least squares  min |A x - b|  for A (6 x C), via normal equations + Gaussian elimination with partial pivoting
@@ -261,31 +235,11 @@ struct PointSet {
     double* vn;       // MODE 0, PHASE 1 / 2: the hypothesis' four null-space vectors [4][12] in LDS
 };
 
-// sum of vals[0..CNT) over the workgroup, result in every thread (MODE 0: every lane already holds the full sums)
+// sum of vals[0..CNT) over the point set, result in every thread (MODE 0: every lane already holds the full sums)
 template <int MODE, int CNT>
-__device__ inline void block_sum(const PointSet<MODE>& ps, double (&vals)[CNT]) {
+__device__ inline void set_sum(const PointSet<MODE>& ps, double (&vals)[CNT]) {
     if (MODE == 0) return;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < CNT; ++c) {
-        double x = vals[c];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-        vals[c] = x;
-    }
-    __syncthreads();   // (the previous use of `red` has been read by everyone)
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < CNT; ++c) ps.red[wv * CNT + c] = vals[c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < CNT; ++c) {
-        double x = 0.0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) x += ps.red[w * CNT + c];
-        vals[c] = x;
-    }
+    block_sum<NW, CNT>(vals, ps.red);
 }
 
 #define PP_FOR_POINTS(ps, i, ...)                                                          \
@@ -315,7 +269,7 @@ __device__ double epnp(const PointSet<MODE>& ps, const Cam& cam, double (&R)[9],
     // ---- control points: centroid + principal directions
     double a4[4] = {0.0, 0.0, 0.0, 0.0};
     PP_FOR_POINTS(ps, i, { a4[0] += ps.p3[3 * i]; a4[1] += ps.p3[3 * i + 1]; a4[2] += ps.p3[3 * i + 2]; a4[3] += 1.0; })
-    block_sum<MODE, 4>(ps, a4);
+    set_sum<MODE, 4>(ps, a4);
     const double n = a4[3];
     double cws[4][3];
 _Pragma("unroll")
@@ -325,7 +279,7 @@ _Pragma("unroll")
         const double x = ps.p3[3 * i] - cws[0][0], y = ps.p3[3 * i + 1] - cws[0][1], z = ps.p3[3 * i + 2] - cws[0][2];
         a6[0] += x * x; a6[1] += x * y; a6[2] += x * z; a6[3] += y * y; a6[4] += y * z; a6[5] += z * z;
     })
-    block_sum<MODE, 6>(ps, a6);
+    set_sum<MODE, 6>(ps, a6);
     {
         double c3[3][3] = {{a6[0], a6[1], a6[2]}, {a6[1], a6[3], a6[4]}, {a6[2], a6[4], a6[5]}}, w[3], v[3][3];
         eig3_sym(c3, w, v);
@@ -542,7 +496,7 @@ _Pragma("unroll")
             for (int c = 0; c < 3; ++c) s6[c] += a[0] * ccs[0][c] + a[1] * ccs[1][c] + a[2] * ccs[2][c] + a[3] * ccs[3][c];
             s6[3] += ps.p3[3 * i]; s6[4] += ps.p3[3 * i + 1]; s6[5] += ps.p3[3 * i + 2];
         })
-        block_sum<MODE, 6>(ps, s6);
+        set_sum<MODE, 6>(ps, s6);
         if (s6[2] < 0) {  // solve_for_sign (mean depth must be positive)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
@@ -564,7 +518,7 @@ _Pragma("unroll")
 _Pragma("unroll")
             for (int r = 0; r < 3; ++r) { H[r * 3] += pc[r] * w0; H[r * 3 + 1] += pc[r] * w1; H[r * 3 + 2] += pc[r] * w2; }
         })
-        block_sum<MODE, 9>(ps, H);
+        set_sum<MODE, 9>(ps, H);
         double Rc[9], tc[3];
         horn_rotation(H, Rc);
 #pragma unroll
@@ -578,7 +532,7 @@ _Pragma("unroll")
             const double du = cam.uc + cam.fu * xc * iz - ps.p2[2 * i], dvv = cam.vc + cam.fv * yc * iz - ps.p2[2 * i + 1];
             er[0] += sqrt(du * du + dvv * dvv);
         })
-        block_sum<MODE, 1>(ps, er);
+        set_sum<MODE, 1>(ps, er);
         const double err = er[0] / n;
         if (MODE == 1 && dbg && threadIdx.x == 0) {
             for (int k = 0; k < 9; ++k) dbg[approx * 13 + k] = Rc[k];
@@ -807,11 +761,6 @@ __device__ void lm_refine(const PTS& pts, const Cam& cam, double* red, int max_i
     rms1 = sqrt(cost / n);
 }
 
-__device__ inline unsigned hash32(unsigned x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
-
 // the outputs and settings of the refining instantiation (unused by pnp_ransac_kernel<false>)
 struct RefineArgs {
     int max_iters;
@@ -872,11 +821,7 @@ __global__ __launch_bounds__(NT) void pnp_ransac_kernel(const float* __restrict_
             if (r < MAXP) {
                 p2[2 * r] = f2[ty * W + tx];
                 p2[2 * r + 1] = f2[(size_t)H * W + ty * W + tx];
-                const float X = f3[sy * W + sx] - P[3], Y = f3[(size_t)H * W + sy * W + sx] - P[7], Z = f3[(size_t)2 * H * W + sy * W + sx] - P[11];
-                // (X - t) @ R_tem  (pose_recovery.py:84): component j = sum_i d_i R[i][j]
-                p3[3 * r] = X * P[0] + Y * P[4] + Z * P[8];
-                p3[3 * r + 1] = X * P[1] + Y * P[5] + Z * P[9];
-                p3[3 * r + 2] = X * P[2] + Y * P[6] + Z * P[10];
+                object_frame_point(f3, P, H, W, sx, sy, p3 + 3 * r);
             }
         }
         __syncthreads();
@@ -889,10 +834,7 @@ __global__ __launch_bounds__(NT) void pnp_ransac_kernel(const float* __restrict_
         if (tid == 0) {
             if (dbg)
                 for (int k = 0; k < 40; ++k) dbg[(size_t)prob * 40 + k] = k == 39 ? -1.0 : k % 13 == 12 ? 1e300 : 0.0;
-            for (int k = 0; k < 9; ++k) rot[(size_t)prob * 9 + k] = (k % 4 == 0) ? 1.0 : 0.0;
-            tvec[(size_t)prob * 3] = 0.0; tvec[(size_t)prob * 3 + 1] = 0.0; tvec[(size_t)prob * 3 + 2] = 1.0;
-            ratio[prob] = 0.0;
-            ok[prob] = 0;
+            ransac_fail_outputs(prob, rot, tvec, ratio, ok);
             if constexpr (REFINE) {
                 ra.rms_before[prob] = 0.0; ra.rms_after[prob] = 0.0; ra.iters[prob] = 0;
             }
@@ -908,27 +850,13 @@ __global__ __launch_bounds__(NT) void pnp_ransac_kernel(const float* __restrict_
     // eigen-solve of hypotheses g, g + NG, ... and leaves their null-space vectors in LDS; phase 2 — thread h finishes
     // hypothesis h (64 hypotheses per wave instead of 4)
     const int nh = iters < MAXH ? iters : MAXH;
-    auto sample = [&](int h, int (&idx)[SAMPLE]) __attribute__((always_inline)) {
-        unsigned s = hash32(0x9E3779B9u * (unsigned)(prob + 1) ^ (unsigned)(h * 7919 + 17));
-#pragma unroll
-        for (int k = 0; k < SAMPLE; ++k) {
-            for (;;) {
-                s = hash32(s + 0x6D2B79F5u);
-                const int c = (int)(s % (unsigned)np);
-                bool dup = false;
-#pragma unroll
-                for (int j = 0; j < SAMPLE; ++j) dup |= j < k && idx[j] == c;
-                if (!dup) { idx[k] = c; break; }
-            }
-        }
-    };
     for (int hb = 0; hb < nh; hb += HB) {
         const int hend = hb + HB < nh ? hb + HB : nh;
         for (int h0 = hb; h0 < hend; h0 += NG) {
             const int h = h0 + tid / GL;
             if (h < hend) {      // (uniform over the 16 lanes of a group; the shuffles inside stay within the group)
                 int idx[SAMPLE];
-                sample(h, idx);
+                ransac_sample<SAMPLE>(prob, h, np, idx);
                 PointSet<0> ps = {p3, p2, idx, nullptr, SAMPLE, nullptr, vnb + (h - hb) * 48};
                 double R[9], t[3];
                 (void)epnp<0, 1>(ps, cam, R, t);
@@ -938,7 +866,7 @@ __global__ __launch_bounds__(NT) void pnp_ransac_kernel(const float* __restrict_
         if (tid < HB && hb + tid < hend) {
             const int h = hb + tid;
             int idx[SAMPLE];
-            sample(h, idx);
+            ransac_sample<SAMPLE>(prob, h, np, idx);
             PointSet<0> ps = {p3, p2, idx, nullptr, SAMPLE, nullptr, vnb + tid * 48};
             double R[9], t[3];
             const double e = epnp<0, 2>(ps, cam, R, t);
@@ -983,17 +911,7 @@ __global__ __launch_bounds__(NT) void pnp_ransac_kernel(const float* __restrict_
         }
     }
     __syncthreads();
-    if (tid < 64) {   // arg-max of the consensus, lowest hypothesis index among equals
-        int bc = -1, bh = 0;
-        for (int h = tid; h < nh; h += 64)
-            if (cnt[h] > bc) { bc = cnt[h]; bh = h; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const int oc = __shfl_xor(bc, o), oh = __shfl_xor(bh, o);
-            if (oc > bc || (oc == bc && oh < bh)) { bc = oc; bh = oh; }
-        }
-        if (tid == 0) { best_h = bh; best_c = bc; }
-    }
+    if (tid < 64) ransac_winner(cnt, nh, &best_h, &best_c);
     __syncthreads();
     if (best_c < SAMPLE) { fail(); return; }
     {

@@ -13,91 +13,29 @@
 // Phase 1: thread h fits hypothesis h.  Phase 2: wave w scores hypotheses w, w + 8, ...; its lanes walk the points, one ballot /
 // popcount per 64 points.  No atomics.  Phase 3: the whole workgroup refits on the winner's consensus set, sums reduced in a fixed
 // order (xor-butterfly within a wave, then the 8 wave partials in order), every thread solving the same small system.
+//
+// The rules shared with pp_pnp_ransac — workgroup shape and capacities, the cyclic Jacobi behind horn_fit and eig3_top2, the block
+// sum, the sampling sequence, the winner's tie rule, the failure outputs, the object-frame source point — are the functions of
+// pp_ransac_dev.h, the ones pp_pnp.hip calls.  The kernel keeps 224 VGPRs, no spills and no scratch.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/picopose_hip.h"
 #include "pp_common.h"
-#include "pp_hash_dev.h"
+#include "pp_ransac_dev.h"           // NT, NW, MAXP, MAXH and the rules shared with pp_pnp.hip
 
 namespace {
 
-constexpr int NT = 512;           // 8 waves, one workgroup per CU
-constexpr int NW = NT / 64;
-constexpr int MAXP = 4096;        // pairs per problem
-constexpr int MAXH = 256;         // RANSAC hypotheses kept per problem
 constexpr int SAMPLE = 3;
-constexpr int NRED = 16;          // widest block sum (15 used)
+constexpr int NRED = 16;          // doubles of reduction scratch per wave: block_sum<NW, CNT> needs CNT <= NRED (15 is the widest)
 constexpr double DEGENERATE = 1e-6;
 
-// ------------------------------------------------------------------ small dense helpers (double, everything in registers:
-// every array index is a compile-time constant after unrolling)
-
-// one Jacobi rotation of the symmetric A (full storage) annihilating A[P][Q]; the rows of V accumulate the eigenvectors
-template <int N, int P, int Q>
-__device__ __forceinline__ void jrot(double (&A)[N][N], double (&V)[N][N]) {
-    const double apq = A[P][Q];
-    if (fabs(apq) >= 1e-300) {
-        const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            const double akp = A[k][P], akq = A[k][Q];
-            A[k][P] = c * akp - s * akq;
-            A[k][Q] = s * akp + c * akq;
-        }
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            const double apk = A[P][k], aqk = A[Q][k];
-            A[P][k] = c * apk - s * aqk;
-            A[Q][k] = s * apk + c * aqk;
-        }
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            const double vpk = V[P][k], vqk = V[Q][k];
-            V[P][k] = c * vpk - s * vqk;
-            V[Q][k] = s * vpk + c * vqk;
-        }
-    }
-}
-
-template <int N>
-__device__ __forceinline__ bool jacobi_converged(const double (&A)[N][N]) {
-    double off = 0.0, diag = 0.0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        diag += A[i][i] * A[i][i];
-#pragma unroll
-        for (int j = i + 1; j < N; ++j) off += A[i][j] * A[i][j];
-    }
-    return !(off > 1e-30 * (diag + 1e-300));      // (a NaN ends the sweeps as well)
-}
-
-// cyclic Jacobi on a symmetric 4x4: eigenvalues on the diagonal of A, eigenvector k in row k of V
-__device__ inline void eig4_sym(double (&A)[4][4], double (&V)[4][4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        if (jacobi_converged(A)) break;
-        jrot<4, 0, 1>(A, V); jrot<4, 0, 2>(A, V); jrot<4, 0, 3>(A, V);
-        jrot<4, 1, 2>(A, V); jrot<4, 1, 3>(A, V); jrot<4, 2, 3>(A, V);
-    }
-}
+// ------------------------------------------------------------------ small dense helpers (double, everything in registers)
 
 // the two largest eigenvalues of a symmetric 3x3 (cyclic Jacobi)
 __device__ inline void eig3_top2(double (&A)[3][3], double& l1, double& l2) {
     double V[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        if (jacobi_converged(A)) break;
-        jrot<3, 0, 1>(A, V); jrot<3, 0, 2>(A, V); jrot<3, 1, 2>(A, V);
-    }
+    jacobi_sym<3>(A, V);
     const double a = A[0][0], b = A[1][1], c = A[2][2];
     l1 = fmax(a, fmax(b, c));
     l2 = fmax(fmin(a, b), fmin(fmax(a, b), c));   // the median
@@ -113,7 +51,7 @@ __device__ inline void horn_fit(const double (&S)[9], const double (&pm)[3], con
                       {Szx - Sxz, Sxy + Syx, -Sxx + Syy - Szz, Syz + Szy},
                       {Sxy - Syx, Szx + Sxz, Syz + Szy, -Sxx - Syy + Szz}};
     double V[4][4];
-    eig4_sym(A, V);
+    jacobi_sym<4>(A, V);
     int best = 0;
     double lam = A[0][0];
 #pragma unroll
@@ -147,33 +85,6 @@ __device__ __forceinline__ double residual2(const double* M, const float* ps, co
     const double dy = fma(M[3], X, fma(M[4], Y, fma(M[5], Z, M[10]))) - (double)pq[3 * i + 1];
     const double dz = fma(M[6], X, fma(M[7], Y, fma(M[8], Z, M[11]))) - (double)pq[3 * i + 2];
     return fma(dx, dx, fma(dy, dy, dz * dz));
-}
-
-// sum of vals[0..CNT) over the workgroup in a fixed order, result in every thread (the same bits in every thread)
-template <int CNT>
-__device__ inline void block_sum(double (&vals)[CNT], double* red) {
-    static_assert(CNT <= NRED, "reduction scratch");
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < CNT; ++c) {
-        double x = vals[c];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-        vals[c] = x;
-    }
-    __syncthreads();   // (the previous use of `red` has been read by everyone)
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < CNT; ++c) red[wv * NRED + c] = vals[c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < CNT; ++c) {
-        double x = 0.0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) x += red[w * NRED + c];
-        vals[c] = x;
-    }
 }
 
 __device__ __forceinline__ bool finite12(const double (&R)[9], const double (&t)[3]) {
@@ -259,11 +170,7 @@ __global__ __launch_bounds__(NT) void rgbd_ransac_kernel(const float* __restrict
             const unsigned long long below = (1ull << lane) - 1ull;
             const int rl = offl + __popcll(bl & below), rk = offk + __popcll(bk & below);
             if (rl < MAXP) {     // (N <= MAXP: always)
-                const float X = f3[sy * W + sx] - P[3], Y = f3[(size_t)H * W + sy * W + sx] - P[7], Z = f3[(size_t)2 * H * W + sy * W + sx] - P[11];
-                // (X - t) @ R_tem: component j = sum_i d_i R[i][j]
-                ps[3 * rk] = X * P[0] + Y * P[4] + Z * P[8];
-                ps[3 * rk + 1] = X * P[1] + Y * P[5] + Z * P[9];
-                ps[3 * rk + 2] = X * P[2] + Y * P[6] + Z * P[10];
+                object_frame_point(f3, P, H, W, sx, sy, ps + 3 * rk);
                 const double zd = z;
                 pq[3 * rk] = (float)(((double)u - cx) * zd / fx);
                 pq[3 * rk + 1] = (float)(((double)vv - cy) * zd / fy);
@@ -280,10 +187,7 @@ __global__ __launch_bounds__(NT) void rgbd_ransac_kernel(const float* __restrict
     if (tid == 0) { nlisted[prob] = nl; npts[prob] = np; }
     auto fail = [&]() {
         if (tid == 0) {
-            for (int k = 0; k < 9; ++k) rot[(size_t)prob * 9 + k] = (k % 4 == 0) ? 1.0 : 0.0;
-            tvec[(size_t)prob * 3] = 0.0; tvec[(size_t)prob * 3 + 1] = 0.0; tvec[(size_t)prob * 3 + 2] = 1.0;
-            ratio[prob] = 0.0;
-            ok[prob] = 0;
+            ransac_fail_outputs(prob, rot, tvec, ratio, ok);
             rms[prob] = 0.0;
         }
         if (mask)
@@ -298,18 +202,7 @@ __global__ __launch_bounds__(NT) void rgbd_ransac_kernel(const float* __restrict
     if (tid < nh) {
         const int h = tid;
         int idx[SAMPLE];
-        unsigned s = aug_mix(0x9E3779B9u * (unsigned)(prob + 1) ^ (unsigned)(h * 7919 + 17));
-#pragma unroll
-        for (int k = 0; k < SAMPLE; ++k) {
-            for (;;) {
-                s = aug_mix(s + 0x6D2B79F5u);
-                const int c = (int)(s % (unsigned)np);
-                bool dup = false;
-#pragma unroll
-                for (int j = 0; j < SAMPLE; ++j) dup |= j < k && idx[j] == c;
-                if (!dup) { idx[k] = c; break; }
-            }
-        }
+        ransac_sample<SAMPLE>(prob, h, np, idx);
         double a[3][3], b[3][3];
 #pragma unroll
         for (int k = 0; k < 3; ++k)
@@ -350,17 +243,7 @@ __global__ __launch_bounds__(NT) void rgbd_ransac_kernel(const float* __restrict
         if (lane == 0) cnt[h] = c;
     }
     __syncthreads();
-    if (tid < 64) {   // arg-max of the consensus, lowest hypothesis index among equals
-        int bc = -1, bh = 0;
-        for (int h = tid; h < nh; h += 64)
-            if (cnt[h] > bc) { bc = cnt[h]; bh = h; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const int oc = __shfl_xor(bc, o), oh = __shfl_xor(bh, o);
-            if (oc > bc || (oc == bc && oh < bh)) { bc = oc; bh = oh; }
-        }
-        if (tid == 0) { best_h = bh; best_c = bc; }
-    }
+    if (tid < 64) ransac_winner(cnt, nh, &best_h, &best_c);
     for (int i = tid; i < MAXP; i += NT) lmask[i] = 0;
     __syncthreads();
     if (best_c < SAMPLE) { fail(); return; }
@@ -382,7 +265,7 @@ __global__ __launch_bounds__(NT) void rgbd_ransac_kernel(const float* __restrict
         for (int c = 0; c < 3; ++c) { s7[c] += ps[3 * i + c]; s7[3 + c] += pq[3 * i + c]; }
         s7[6] += 1.0;
     }
-    block_sum<7>(s7, red);
+    block_sum<NW, 7>(s7, red);
     const double n = s7[6];
     double pm[3], qm[3];
 #pragma unroll
@@ -399,7 +282,7 @@ __global__ __launch_bounds__(NT) void rgbd_ransac_kernel(const float* __restrict
         s15[6] += a2 * b0; s15[7] += a2 * b1; s15[8] += a2 * b2;
         s15[9] += a0 * a0; s15[10] += a0 * a1; s15[11] += a0 * a2; s15[12] += a1 * a1; s15[13] += a1 * a2; s15[14] += a2 * a2;
     }
-    block_sum<15>(s15, red);
+    block_sum<NW, 15>(s15, red);
     double M[12];
     {
         double S[9], R[9], t[3];
@@ -417,7 +300,7 @@ __global__ __launch_bounds__(NT) void rgbd_ransac_kernel(const float* __restrict
     double e[1] = {0.0};
     for (int i = tid; i < np; i += NT)
         if (use[i]) e[0] += residual2(M, ps, pq, i);
-    block_sum<1>(e, red);
+    block_sum<NW, 1>(e, red);
     if (tid == 0) {
         for (int k = 0; k < 9; ++k) rot[(size_t)prob * 9 + k] = M[k];
         for (int k = 0; k < 3; ++k) tvec[(size_t)prob * 3 + k] = M[9 + k];

@@ -18,8 +18,8 @@ import torch
 
 from . import _lib
 from .scene import depth_u16_scaled
+from .utils.pose_recovery import MAX_POINTS, alloc_pose_outputs, launch_and_copy_async
 
-MAX_POINTS = 4096                # correspondences per problem (include/picopose_hip.h)
 DEPTH_UNITS = {"m": 1.0, "mm": 1e-3}
 
 
@@ -122,11 +122,7 @@ def rgbd_launch(tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts, depth, in
         img = torch.zeros(P, dtype=torch.int32, device=dev)
     else:
         img = torch.as_tensor(image_index).to(device=dev, dtype=torch.int32).contiguous()
-    rot = torch.empty(P, 3, 3, dtype=torch.float64, device=dev)
-    tvec = torch.empty(P, 3, dtype=torch.float64, device=dev)
-    ratio = torch.empty(P, dtype=torch.float64, device=dev)
-    ok = torch.empty(P, dtype=torch.int32, device=dev)
-    npts = torch.empty(P, dtype=torch.int32, device=dev)
+    rot, tvec, ratio, ok, npts = alloc_pose_outputs(P, dev)
     nlisted = torch.empty(P, dtype=torch.int32, device=dev)
     rms = torch.empty(P, dtype=torch.float64, device=dev)
     mask = torch.empty(P, N, dtype=torch.uint8, device=dev) if return_inliers else None
@@ -202,24 +198,10 @@ def pose_recovery_ransac_rgbd_batched_async(tar_pts_2d, src_pts_3d, K, tem_pose,
     check_rgbd_args(tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts, depth, inlier_dist, image_index, iterations, depth_scale,
                     depth_unit)
     inputs = (tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts)
-    if stream is not None:
-        stream.wait_stream(torch.cuda.current_stream())
-        for t in inputs + (depth, inlier_dist, image_index):
-            if isinstance(t, torch.Tensor) and t.is_cuda:
-                t.record_stream(stream)  # (the caching allocator must not hand these blocks out while the side stream reads them)
-    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
-        launched = rgbd_launch(*inputs, depth, inlier_dist, image_index, iterations, return_inliers, depth_scale, depth_unit)
-        P = launched[0].shape[0]
-        packed = _packed(launched)
-        if host is None or tuple(host.shape) != tuple(packed.shape):
-            host = torch.empty(tuple(packed.shape), dtype=torch.float64, pin_memory=True)
-        host.copy_(packed, non_blocking=True)
-        mask = None
-        if return_inliers:
-            mask = torch.empty(tuple(launched[7].shape), dtype=torch.uint8, pin_memory=True)
-            mask.copy_(launched[7], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
+    on_device = [t for t in inputs + (depth, inlier_dist, image_index) if isinstance(t, torch.Tensor) and t.is_cuda]
+    host, ev, P, mask = launch_and_copy_async(
+        lambda: rgbd_launch(*inputs, depth, inlier_dist, image_index, iterations, return_inliers, depth_scale, depth_unit),
+        _packed, stream, on_device, host, 7 if return_inliers else None)
     return RgbdHandle(host, ev, P, mask=mask)
 
 

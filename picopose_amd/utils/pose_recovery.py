@@ -49,6 +49,39 @@ def pose_recovery_2d_prediction(query_M, query_K, pred_Ms, template_K, template_
     return out
 
 
+def alloc_pose_outputs(P, dev):
+    """The outputs every batched RANSAC launch (PnP, RGB-D) writes -> rot (P,3,3) f64, tvec (P,3) f64, ratio (P) f64, ok (P) i32,
+    npts (P) i32, uninitialised on `dev`."""
+    f64 = dict(dtype=torch.float64, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    return torch.empty(P, 3, 3, **f64), torch.empty(P, 3, **f64), torch.empty(P, **f64), torch.empty(P, **i32), torch.empty(P, **i32)
+
+
+def launch_and_copy_async(launch, pack, stream=None, stream_inputs=(), host=None, mask_at=None):
+    """The asynchronous tail of a batched RANSAC launch (PnP, RGB-D) -> (host, event, P, mask).  launch() enqueues the kernel and
+    returns its device tensors, pack(launched) makes the ONE (P [+ 1], columns) f64 device tensor that travels: it is copied into a
+    pinned buffer (`host`, reused when its shape fits) without a host wait, launched[mask_at] (uint8, if asked for) into a second
+    one, and the event is recorded behind both.  stream: a side stream for all of it; it first waits for the current stream, and
+    the caching allocator must not hand out the blocks of `stream_inputs` while the side stream reads them."""
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream())
+        for t in stream_inputs:
+            t.record_stream(stream)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        launched = launch()
+        packed = pack(launched)
+        if host is None or tuple(host.shape) != tuple(packed.shape):
+            host = torch.empty(tuple(packed.shape), dtype=torch.float64, pin_memory=True)
+        host.copy_(packed, non_blocking=True)
+        mask = None
+        if mask_at is not None:
+            mask = torch.empty(tuple(launched[mask_at].shape), dtype=torch.uint8, pin_memory=True)
+            mask.copy_(launched[mask_at], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+    return host, ev, launched[0].shape[0], mask
+
+
 def pnp_launch(tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts, iterations=150, reproj_error=2.0, branches=False, refine=None,
                refine_iters=20, refine_eps=REFINE_EPS, return_inliers=False):
     """Enqueue the batched PnP/RANSAC kernel; returns DEVICE tensors (rot (P,3,3) f64, tvec (P,3) f64, ratio (P) f64,
@@ -66,11 +99,7 @@ def pnp_launch(tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts, iterations
     P, _, H, W = t2.shape
     N = tp.shape[1]
     dev = t2.device
-    rot = torch.empty(P, 3, 3, dtype=torch.float64, device=dev)
-    tvec = torch.empty(P, 3, dtype=torch.float64, device=dev)
-    ratio = torch.empty(P, dtype=torch.float64, device=dev)
-    ok = torch.empty(P, dtype=torch.int32, device=dev)
-    npts = torch.empty(P, dtype=torch.int32, device=dev)
+    rot, tvec, ratio, ok, npts = alloc_pose_outputs(P, dev)
     if branches:
         dbg = torch.empty(P, 40, dtype=torch.float64, device=dev)
         rc = _lib.lib().pp_pnp_ransac_debug(t2.data_ptr(), s3.data_ptr(), Kd.data_ptr(), pose.data_ptr(), tp.data_ptr(), sp.data_ptr(),
@@ -223,26 +252,11 @@ def pose_recovery_ransac_pnp_batched_async(tar_pts_2d, src_pts_3d, K, tem_pose, 
     the mask is a second asynchronous copy)."""
     check_refine(refine, refine_iters, refine_eps, return_inliers)
     inputs = (tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts)
-    if stream is not None:
-        stream.wait_stream(torch.cuda.current_stream())
-        for t in inputs:
-            t.record_stream(stream)      # (the caching allocator must not hand these blocks out while the side stream reads them)
-    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
-        launched = pnp_launch(*inputs, iterations, reproj_error, refine=refine, refine_iters=refine_iters, refine_eps=refine_eps,
-                              return_inliers=return_inliers)
-        P = launched[0].shape[0]
-        if sat_slot is not None and stream is not None:
-            sat_slot.record_stream(stream)
-        packed = _with_sat_row(_packed(launched), sat_slot)
-        if host is None or tuple(host.shape) != tuple(packed.shape):
-            host = torch.empty(tuple(packed.shape), dtype=torch.float64, pin_memory=True)
-        host.copy_(packed, non_blocking=True)
-        mask = None
-        if return_inliers:
-            mask = torch.empty(tuple(launched[8].shape), dtype=torch.uint8, pin_memory=True)
-            mask.copy_(launched[8], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
+    host, ev, P, mask = launch_and_copy_async(
+        lambda: pnp_launch(*inputs, iterations, reproj_error, refine=refine, refine_iters=refine_iters, refine_eps=refine_eps,
+                           return_inliers=return_inliers),
+        lambda launched: _with_sat_row(_packed(launched), sat_slot), stream,
+        inputs + ((sat_slot,) if sat_slot is not None else ()), host, 8 if return_inliers else None)
     return PnPHandle(host, ev, P, slot=sat_slot is not None, mask=mask)
 
 

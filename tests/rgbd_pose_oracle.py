@@ -9,33 +9,17 @@ kernel's quaternion form: where the two agree, they agree on the least-squares f
 cannot move a pair in or out of a consensus set, so kernel and oracle must report the same masks."""
 import numpy as np
 
+from oracle.pnp import hash32 as mix, sample_indices  # noqa: F401  (pp_pnp_ransac's rule: one mixer, one sampler)
+
 MAXP, MAXH = 4096, 256
 DEGENERATE = 1e-6
 K0 = np.array([[572.4114, 0, 325.2611], [0, 573.57043, 242.04899], [0, 0, 1.0]], dtype=np.float32)
 H = W = 64
-M32 = 0xFFFFFFFF
-
-
-def mix(x):
-    x &= M32
-    x ^= x >> 16
-    x = (x * 0x7FEB352D) & M32
-    x ^= x >> 15
-    x = (x * 0x846CA68B) & M32
-    x ^= x >> 16
-    return x
 
 
 def draw(prob, h, npts):
     """The 3 distinct indices of hypothesis h of problem `prob` (its index in the batch)."""
-    s = mix(((0x9E3779B9 * (prob + 1)) & M32) ^ ((h * 7919 + 17) & M32))
-    idx = []
-    while len(idx) < 3:
-        s = mix((s + 0x6D2B79F5) & M32)
-        c = s % npts
-        if c not in idx:
-            idx.append(c)
-    return idx
+    return sample_indices(prob, h, npts, 3)
 
 
 def gather(p, depth):

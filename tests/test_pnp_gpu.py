@@ -53,6 +53,60 @@ def test_planted_outliers_are_rejected():
         assert np.abs(rot[i] - p["R"]).max() < tol and np.abs(tvec[i, :, 0] - p["t"]).max() < tol
 
 
+INTERLEAVED_COUNTS = (0, 4, 5, 6, 63, 64, 65, 511, 512, 513, 4096)   # around the sample (5), a wave (64) and a workgroup (512)
+INTERLEAVED_OUTLIERS = (513, 4096)                                    # two more problems, 30 % planted outliers each
+
+
+def interleaved_problems(seed=5):
+    """The batch of test_interleaved_empty_rows_keep_the_gather_order: noise-free problems with INTERLEAVED_COUNTS listed entries,
+    then INTERLEAVED_OUTLIERS with 30 % outliers, each in lists of N = 4096 whose listed rows are shuffled among themselves
+    (outliers anywhere) and then dealt, in that order, to random rows: -1 rows anywhere, none necessarily trailing.
+    -> (problems, flags): flags[i] (count,) bool, the planted inlier flags of problem i in list order."""
+    rng = np.random.default_rng(seed)
+    probs, flags = [], []
+    for n, frac in [(n, 0.0) for n in INTERLEAVED_COUNTS] + [(n, 0.3) for n in INTERLEAVED_OUTLIERS]:
+        p = _problem(rng, n, n_out=int(round(frac * n)))
+        N = p["tar_pts"].shape[0]
+        listed = np.flatnonzero(p["tar_pts"][:, 0] != -1)               # make_batch: entry j is its j-th listed row, outliers first
+        assert len(listed) == n and N == 4096
+        order = rng.permutation(n)
+        rows = np.sort(rng.permutation(N)[:n])
+        for k in ("tar_pts", "src_pts"):
+            moved = -np.ones_like(p[k])
+            moved[rows] = p[k][listed[order]]
+            p[k] = moved
+        probs.append(p)
+        flags.append(order >= n - p["n_in"])
+    return probs, flags
+
+
+@gpu
+def test_interleaved_empty_rows_keep_the_gather_order():
+    """The gather compacts the listed entries in list order wherever the -1 rows lie: npts is the listed count, the pose is the
+    planted one and the consensus mask (refine="lm", return_inliers) is in list order — all of it set and nothing behind it on
+    noise-free data, the planted flags (one entry per problem may differ, as in test_planted_outliers_are_rejected) with outliers."""
+    from picopose_amd.utils.pose_recovery import pose_recovery_ransac_pnp_batched
+
+    probs, flags = interleaved_problems()
+    st = lambda k: torch.from_numpy(np.stack([p[k] for p in probs])).cuda()  # noqa: E731
+    rot, tvec, ratio, ok, npts, stats, inliers = pose_recovery_ransac_pnp_batched(
+        st("tar2d"), st("src3d"), st("K"), st("pose"), st("tar_pts"), st("src_pts"), return_npts=True, refine="lm", return_inliers=True)
+    counts = INTERLEAVED_COUNTS + INTERLEAVED_OUTLIERS
+    assert inliers.shape == (len(counts), 4096) and inliers.dtype == bool
+    for i, (n, p) in enumerate(zip(counts, probs)):
+        assert npts[i] == n, (i, npts[i], n)
+        if n < 5:
+            assert not ok[i], i
+        if n < 6:
+            continue
+        assert ok[i] and not inliers[i, n:].any(), i
+        if i < len(INTERLEAVED_COUNTS):
+            assert np.abs(rot[i] - p["R"]).max() < 1e-4 and np.abs(tvec[i, :, 0] - p["t"]).max() < 1e-4, (i, np.abs(rot[i] - p["R"]).max())
+            assert inliers[i, :n].all(), (i, int(inliers[i, :n].sum()))
+        else:
+            assert int((inliers[i, :n] != flags[i]).sum()) <= 1, (i, int((inliers[i, :n] != flags[i]).sum()))
+
+
 @gpu
 def test_failure_outputs_and_single_problem_api():
     from picopose_amd.utils.pose_recovery import pose_recovery_ransac_pnp
