@@ -404,6 +404,14 @@ int pp_avgpool2_nhwc(const float* in, int B, int H, int W, int C, float* out, vo
  * (model/picopose.py:55-62). */
 int pp_gather_rows(const float* src, const long long* index, long long n_src_rows, long long row_floats, int n, float* dst,
                    void* stream);
+/* Rows of the feature bank as token rows: tokens[(j T + skip + p) ld + c] = bank[(index[j] C + c) P + p] for j < n, p < P, c < C.
+ * bank: n_bank_rows rows of (C, P) fp32 — `template_feature.flatten(0, 1)`, which run_test.py:120-134 builds as
+ * feature_extractor(tem_rgb)[-1] and run_test.py:161-162 gathers per crop; index: int64 on the device (an index outside
+ * [0, n_bank_rows) leaves its image untouched, as in pp_gather_rows); tokens: the (rows, ld) fp32 buffer of a ViT level with T rows per
+ * image (ld >= C, skip + P <= T).  The `skip` leading rows of every image (the cls row) are written as zeros; rows past skip + P and
+ * columns past C are not written.  One launch: the gather fused with the (C, P) -> (P, C) transpose through an LDS tile. */
+int pp_bank_rows_to_tokens(const float* bank, long long n_bank_rows, int C, int P, const long long* index, int n, float* tokens, int ld,
+                           int T, int skip, void* stream);
 
 /* -------------------------------------------------------------------------
  * Crop preprocessing of one detection (provider/bop_test_dataset.py:162-177, utils/data_utils.py:231-250):

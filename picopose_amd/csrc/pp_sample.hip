@@ -525,6 +525,35 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) d4[i] = s4[i];
 }
 
+// Bank rows to token rows: tokens[(j T + skip + p) ld + c] = bank[(index[j] C + c) P + p] — the gather above fused with the
+// (C, P) -> (P, C) transpose of transpose_kernel (32x33 LDS tile; p runs along the lanes on the load, c on the store), so the last-level
+// patch tokens of the selected templates come out of the feature bank (run_test.py:130-134, 161-162) as rows of the level buffer.
+// The `skip` leading rows of every image (the cls row, which nothing reads) are zeroed by the blocks of the first tile row.
+__global__ __launch_bounds__(256) void bank_rows_to_tokens_kernel(const float* __restrict__ bank, const long long* __restrict__ index,
+                                                                  long long nsrc, int C, int P, float* __restrict__ tokens, int ld, int T,
+                                                                  int skip) {
+    __shared__ float t[32][33];
+    const long long r = index[blockIdx.z];
+    if (r < 0 || r >= nsrc) return;  // (as gather_rows_kernel; uniform over the block, before the barrier)
+    const int c0 = blockIdx.x * 32, p0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+    const float* src = bank + (size_t)r * C * P;
+    float* dst = tokens + (size_t)blockIdx.z * T * ld;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = c0 + ty + 8 * i, p = p0 + tx;
+        if (c < C && p < P) t[ty + 8 * i][tx] = src[(size_t)c * P + p];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int p = p0 + ty + 8 * i, c = c0 + tx;
+        if (p < P && c < C) dst[(size_t)(skip + p) * ld + c] = t[tx][ty + 8 * i];
+    }
+    if (blockIdx.y == 0 && c0 + tx < C)
+        for (int s = ty; s < skip; s += 8) dst[(size_t)s * ld + c0 + tx] = 0.f;
+}
+
 // Stream-ordered snapshot of the sticky saturation word (pp_saturation_take): one lane moves the word into the caller's slot and clears it,
 // so the slot covers exactly the producers enqueued on this stream since the previous take.
 __global__ __launch_bounds__(64) void saturation_take_kernel(unsigned* __restrict__ word, unsigned* __restrict__ slot) {
@@ -858,6 +887,17 @@ int pp_gather_rows(const float* src, const long long* index, long long n_src_row
     const int gx = (int)((n4 + 255) / 256 < 64 ? (n4 + 255) / 256 : 64);
     hipLaunchKernelGGL(gather_rows_kernel, dim3(gx, n), dim3(256), 0, (hipStream_t)stream, src, index, row_floats, n_src_rows,
                        dst);
+    return pp_last_launch();
+}
+
+int pp_bank_rows_to_tokens(const float* bank, long long n_bank_rows, int C, int P, const long long* index, int n, float* tokens, int ld,
+                           int T, int skip, void* stream) {
+    if (!bank || !index || !tokens || n_bank_rows <= 0 || C <= 0 || P <= 0 || n <= 0 || ld < C || skip < 0 || T <= 0 ||
+        (long long)skip + P > T)
+        return PP_EINVAL;
+    if (n > 65535 || (P + 31) / 32 > 65535) return PP_EINVAL;   // grid.z / grid.y
+    hipLaunchKernelGGL(bank_rows_to_tokens_kernel, dim3((C + 31) / 32, (P + 31) / 32, n), dim3(256), 0, (hipStream_t)stream, bank, index,
+                       n_bank_rows, C, P, tokens, ld, T, skip);
     return pp_last_launch();
 }
 

@@ -135,8 +135,11 @@ class FeatureExtractor(Packed):
         return pk["pos"][key]
 
     # ---- forward -------------------------------------------------------------------------
-    def forward_tokens(self, x, last_block_fn=None, all_blocks=False, embed_fn=None, level_out=None):
+    def forward_tokens(self, x, last_block_fn=None, all_blocks=False, embed_fn=None, level_out=None, full_depth=None):
         """(B,3,H,W) -> list of token tensors (B, 1+hw, C) at the taken blocks (cls row first).
+        full_depth = n: the blocks after the second-to-last taken one run on the first n images only (rows xs[:n * T]; n = 0: they are
+        skipped) — the last entry of the result, and the last level written through `level_out`, then cover n images; the caller has the
+        other images' last level from elsewhere (Net.forward_test_hyp: the feature bank).  Inference only.
         level_out = (buffers, row0): the taken blocks' outputs are written as images row0 .. row0 + B of the caller's
         (Btot * T, C) fp32 buffers (one per taken level) — the query pass and the template pass of a forward then leave their
         levels in ONE tensor per level, which the DPT head reads as one batch (Net.forward_test).
@@ -160,7 +163,15 @@ class FeatureExtractor(Packed):
             tok = ops.assemble_tokens(patches.view(B, h0 * w0, C), v.cls_token.reshape(C), self._pos(h0, w0))
             xs = tok.view(B * T, C)
         outs = []
+        if full_depth is not None:
+            assert last_block_fn is None and embed_fn is None, "full_depth is an inference shortcut: not under the training hooks"
+            assert len(self.blocks_to_take) >= 2 and 0 <= full_depth <= B
         for i, blk in enumerate(v.blocks):
+            if full_depth is not None and i == self.blocks_to_take[-2] + 1:
+                xs, B = xs[:full_depth * T], full_depth
+                if B == 0:
+                    outs.append(xs.view(0, T, C))
+                    break
             if last_block_fn is not None and (all_blocks or i == len(v.blocks) - 1):
                 xs = last_block_fn(blk, xs, B, T, heads, hd)
                 if i in self.blocks_to_take:

@@ -1289,3 +1289,20 @@ def gather_rows(src, index):
     _lib.check(_lib.lib().pp_gather_rows(_p(src), _p(index), R, row, index.numel(), _p(dst), _lib.stream_ptr()),
                "pp_gather_rows")
     return dst
+
+
+def bank_rows_to_tokens(bank, index, T, skip=1, out=None):
+    """Rows `index` (n,) int64 of a feature bank (R, C, h, w) contiguous fp32 as token rows: image j of the result holds `skip` zero rows
+    (the cls row), then the h*w patch rows bank[index[j]].flatten(1).t() — what FeatureExtractor.forward_tokens leaves in its last level for
+    the templates the bank was built from (run_test.py:130-134).  out: (n*T, ld) fp32 rows of a level buffer (ld >= C, unit column stride)
+    written in place; None: a fresh (n*T, C) tensor."""
+    R, C = bank.shape[:2]
+    P = bank[0, 0].numel()
+    n = index.numel()
+    assert bank.is_contiguous() and bank.dtype == torch.float32 and index.dtype == torch.int64 and index.device == bank.device
+    if out is None:
+        out = torch.empty(n * T, C, dtype=torch.float32, device=bank.device)
+    assert out.dim() == 2 and out.dtype == torch.float32 and out.shape[0] == n * T and out.shape[1] >= C and out.stride(1) == 1 and out.device == bank.device
+    _lib.check(_lib.lib().pp_bank_rows_to_tokens(_p(bank), R, C, P, _p(index.contiguous()), n, _p(out), out.stride(0), T, skip,
+                                                 _lib.stream_ptr()), "pp_bank_rows_to_tokens")
+    return out

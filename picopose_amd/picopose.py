@@ -30,6 +30,9 @@ BATCH_VIT_TRAIN = os.environ.get("PP_BATCH_VIT_TRAIN", "1") != "0"
 BATCH_DPT = os.environ.get("PP_BATCH_DPT", "1") != "0"
 # The NEXT batch's query ViT inside this batch's template-side ViT pass (Net.forward(..., next_real_rgb=...); PP_PREFETCH_QUERY=0: off, A/B)
 PREFETCH_QUERY = os.environ.get("PP_PREFETCH_QUERY", "1") != "0"
+# The selected templates' last ViT level read from the feature bank instead of running its blocks again (Net.template_last_from_bank;
+# PP_TEMPLATE_LAST_FROM_BANK=0 / 1 overrides the attribute's auto rule, A/B)
+TEMPLATE_LAST_FROM_BANK = {"0": False, "1": True}.get(os.environ.get("PP_TEMPLATE_LAST_FROM_BANK"))
 
 
 def _tensor_key(t, fe=None):
@@ -73,6 +76,11 @@ class Net(nn.Module):
         # arithmetic of this network's forwards: None follows the global ops.PRECISION; "f32" / "f16x3" / "f16" holds for every call of this
         # model (ops.precision_scope, per thread), whatever the global says — two models of one process can run in different modes
         self.precision = None
+        # The templates' last ViT level from end_points["template_feature"] instead of the blocks after the second-to-last taken one (DESIGN.md
+        # section 0): None — auto, on when the forward runs in "f16x3" / "f16" and off in "f32" (the re-run of a clamped batch must not read a
+        # bank built by the arithmetic that clamped); True — in every mode (the caller's bank was built in the mode the forward runs in);
+        # False — always recompute (a bank that is not feature_extractor(tem_rgb)[-1] of THIS network: INTEGRATION.md)
+        self.template_last_from_bank = None
         self.range_fallbacks = 0     # mini-batches re-run in strict fp32 after a clamped operand (pipeline.py, on_saturation="exact")
 
     @property
@@ -94,12 +102,31 @@ class Net(nn.Module):
                 m.invalidate_packed()
         self._query_stash = None
 
+    def _last_from_bank(self, end_points):
+        """Whether this forward takes the selected templates' last-level patch tokens from end_points["template_feature"] — which
+        run_test.py:120-134 builds as feature_extractor(tem_rgb)[-1] with this model on these renders, so the rows are the ones blocks
+        9-11 (ViT-L: 18-23) would compute again — instead of recomputing them.  Everything else recomputes: training, a bank stored in
+        fp16 or on another grid, the extended bank (template_cache: no template ViT at all), end_points without a bank (dist.py)."""
+        on = self.template_last_from_bank
+        on = TEMPLATE_LAST_FROM_BANK if on is None else on
+        on = ops.precision() in ("f16x3", "f16") if on is None else on
+        bank = end_points.get("template_feature")
+        if not on or self.training or bank is None or end_points.get("template_cache") is not None:
+            return False
+        fe = self.feature_extractor
+        H, W = end_points["tem_rgb"].shape[-2:]
+        grid = (fe.num_features, H // fe.patch_size, W // fe.patch_size)
+        return (bank.dtype == torch.float32 and bank.dim() == 5 and tuple(bank.shape[2:]) == grid and bank.is_contiguous()
+                and tuple(bank.shape[:2]) == tuple(end_points["tem_rgb"].shape[:2]) and len(fe.blocks_to_take) >= 2)
+
     # model/picopose.py:52-70 — pick hypothesis k's template for every crop (pure indexing)
     def select_template_data(self, end_points, pred_id_src, k):
         idx = pred_id_src[:, k]
         rows = end_points.get("template_index")       # per-object banks: crop b's templates are row template_index[b]
         rows = torch.arange(idx.shape[0], device=idx.device) if rows is None else rows
         sel = {key: end_points[key][rows, idx] for key in ("tem_pose", "tem_K", "tem_M", "tem_mask", "tem_rgb", "tem_pts3d")}
+        if self._last_from_bank(end_points):          # (the flattened bank, the selected rows): forward_test_hyp
+            sel["tem_bank"] = (end_points["template_feature"].flatten(0, 1), rows * end_points["template_feature"].shape[1] + idx)
         for key in ("real_pts2d", "real_K", "real_M", "real_mask", "real_pose"):
             sel[key] = end_points[key]
         return sel
@@ -139,23 +166,35 @@ class Net(nn.Module):
         output["src_pts_3d"] = end_points["tem_pts3d"].permute(0, 3, 1, 2)
         # stage 1: template features
         pre = real[4] if len(real) > 4 else None        # (level buffers with room in front, the NEXT batch's query crops): forward_test
+        # (flattened feature bank, selected rows): the templates' last level is there already (_last_from_bank) — their ViT pass stops after
+        # the second-to-last taken block, pp_bank_rows_to_tokens writes the bank rows as the patch rows of the last level (cls row: zeros,
+        # nothing reads it) and stage 2 reads the bank rows as they are
+        bank = end_points.get("tem_bank") if tem_cached is None else None
+        T = h0 * w0 + 1
         if tem_cached is None and pre is not None and levels is not None:
             # the next batch's query ViT rides in this batch's template pass: rows [next queries ; templates] of one launch per layer
             # (a GEMM row does not depend on the other rows: every token keeps its bits); its four levels stay behind as the stash
             alloc, nxt = pre
-            Bn, T = nxt.shape[0], h0 * w0 + 1
-            both, _ = fe.forward_tokens(torch.cat([nxt, end_points["tem_rgb"]]), level_out=(alloc, 0))
+            Bn = nxt.shape[0]
+            both, _ = fe.forward_tokens(torch.cat([nxt, end_points["tem_rgb"]]), level_out=(alloc, 0), full_depth=None if bank is None else Bn)
             tem_tok = [t[Bn:] for t in both]
+            if bank is not None:
+                nT = tem_tok[0].shape[0]
+                tem_tok[-1] = ops.bank_rows_to_tokens(*bank, T, out=alloc[-1][Bn * T:(Bn + nT) * T]).view(nT, T, -1)
             # the stash: the key of the crops it was computed FROM, copies of its Bn * T rows per level (views would pin the whole `alloc` of
             # this batch until the next call), and `nxt` itself — held so that its storage cannot be freed and its address handed to another
             # batch of the same shape, whose key would then match
             self._query_stash = (_tensor_key(nxt, fe), [a[:Bn * T].clone() for a in alloc], (h0, w0), nxt)
-            tem_last = ops.tokens_to_nchw(tem_tok[-1], 1, h0, w0)
         elif tem_cached is None:
-            tem_tok, _ = fe.forward_tokens(end_points["tem_rgb"], level_out=None if levels is None else (levels, 0))
-            tem_last = ops.tokens_to_nchw(tem_tok[-1], 1, h0, w0)
+            tem_tok, _ = fe.forward_tokens(end_points["tem_rgb"], level_out=None if levels is None else (levels, 0),
+                                           full_depth=None if bank is None else 0)
+            if bank is not None:
+                nT = tem_tok[0].shape[0]
+                tem_tok[-1] = ops.bank_rows_to_tokens(*bank, T, out=None if levels is None else levels[-1][:nT * T]).view(nT, T, -1)
         else:
             tem_last, tem_dpt = tem_cached
+        if tem_cached is None:
+            tem_last = ops.tokens_to_nchw(tem_tok[-1], 1, h0, w0) if bank is None else ops.gather_rows(*bank)
         # stage 2
         sim = matching_features_similarity(tem_last, ops.tokens_to_nchw(real_tok[-1], 1, h0, w0),
                                            end_points["tem_mask"], end_points["real_mask"])
@@ -171,7 +210,6 @@ class Net(nn.Module):
         if levels is not None and real_dpt is None and tem_cached is None:
             # ONE pass of the DPT head over [templates ; query crops] (the same weights; a row of a GEMM does not depend on the
             # other rows, so every map keeps the bits two passes give it): larger launches, half as many of them
-            T = h0 * w0 + 1
             nT, nR = tem_tok[0].shape[0], levels[0].shape[0] // T - tem_tok[0].shape[0]
             both = orr.dpt_head.forward_nhwc([as_img(lv.view(-1, T, lv.shape[1])) for lv in levels])
             tem_dpt, real_dpt = [_image_rows(p_, 0, nT) for p_ in both], [_image_rows(p_, nT, nT + nR) for p_ in both]
@@ -220,6 +258,8 @@ class Net(nn.Module):
         sel = {key: (ops.gather_rows(end_points[key].flatten(0, 1), flat) if end_points[key].is_contiguous()
                      else end_points[key][trow, idx])
                for key in ("tem_pose", "tem_K", "tem_M", "tem_mask", "tem_rgb", "tem_pts3d")}
+        if self._last_from_bank(end_points):
+            sel["tem_bank"] = (end_points["template_feature"].flatten(0, 1), flat)
         for key in ("real_pts2d", "real_K", "real_M", "real_mask", "real_pose"):
             sel[key] = rep(end_points[key])
         # (with the query-side DPT maps at hand only the last token level is read again: for the stage-2 similarity)
