@@ -412,6 +412,19 @@ int pp_gather_rows(const float* src, const long long* index, long long n_src_row
  * columns past C are not written.  One launch: the gather fused with the (C, P) -> (P, C) transpose through an LDS tile. */
 int pp_bank_rows_to_tokens(const float* bank, long long n_bank_rows, int C, int P, const long long* index, int n, float* tokens, int ld,
                            int T, int skip, void* stream);
+/* The patch-embed operand straight from the image bank: image j < n_front of the result is front[j] ((n_front, 3, H, W) contiguous fp32;
+ * NULL with n_front = 0), image n_front + i is bank[index[i]] (bank: n_bank_rows rows of (3, H, W) fp32 — `tem_rgb.flatten(0, 1)`; index:
+ * n int64 on the device).  out: ((n_front + n) H W, 8) operand rows in the format pp_split_activation_t writes (terms = 2: hl, 1: h),
+ * channels 0..2 = the pixel's three planes, 3..7 zero; a value beyond the operand range sets the saturation word as there.  The bits are
+ * those of pp_gather_rows -> concatenation -> NCHW to NHWC-8 (pp_transpose_batched into a zeroed map) -> pp_split_activation_t, in one pass
+ * (NCHW -> pixel-major through an LDS tile).  bank, front and out 16-byte aligned; an index outside [0, n_bank_rows) leaves its image's
+ * rows unwritten and the call returns PP_OK, as in pp_gather_rows. */
+int pp_patch_operand(const float* bank, long long n_bank_rows, const long long* index, int n, const float* front, int n_front, int H, int W,
+                     void* out, int terms, void* stream);
+/* A flow map as the operand of flow_net[0] (raft_decoder.py:141-147): flow (rows, ld_flow >= 2) fp32, x and y first; out8: (rows, 8)
+ * operand (16-byte aligned) with channels 0, 1 = the flow and 2..7 zero.  One launch for a zeroed 8-channel map, the copy of the flow
+ * into it and its pp_split_activation_t — the same bits and the same saturation report. */
+int pp_flow_operand(const float* flow, int ld_flow, long long rows, void* out8, int terms, void* stream);
 
 /* -------------------------------------------------------------------------
  * Crop preprocessing of one detection (provider/bop_test_dataset.py:162-177, utils/data_utils.py:231-250):
@@ -432,7 +445,8 @@ int pp_depth_points_nearest(const float* depth_m, int H, int W, int y1, int y2, 
  * (B*HW, HW) volume: f1 (B,H,W,C) with rows of ld_f1 floats, f2_l{0,1,2} = f2 and its 2x2 average pools holding
  * f2_batch images (image b reads f2[b % f2_batch]), flow (B,H,W,ld_flow);
  * out (B,H,W,ld_out) with channel l*(2r+1)^2 + a*(2r+1) + b = corr_l sampled at x offset a-r,
- * y offset b-r around (p + flow)/2^l.
+ * y offset b-r around (p + flow)/2^l; ld_out is the channel count of the result: the channels from levels*(2r+1)^2 up to ld_out
+ * (padding to the next layer's multiple of 8) are written as zeros by these entries and by pp_corr_lookup_nhwc_hl.
  * When H, W are multiples of 8 and C of 32 the local correlations of an 8x8 pixel tile against a 16x16 region of f2
  * are computed on the matrix cores in the engine's f16x3 arithmetic (22 operand bits, fp32 accumulation; values with
  * |x| >= 16376 saturate); otherwise (and with PP_CORR_TILED=0 in the environment) by exact fp32 fmas, one lane per

@@ -160,6 +160,8 @@ def lib():
         L.pp_avgpool2_nhwc.argtypes = [vp, i32, i32, i32, i32, vp, vp]
         L.pp_gather_rows.argtypes = [vp, vp, c.c_longlong, c.c_longlong, i32, vp, vp]
         L.pp_bank_rows_to_tokens.argtypes = [vp, c.c_longlong, i32, i32, vp, i32, vp, i32, i32, i32, vp]
+        L.pp_patch_operand.argtypes = [vp, c.c_longlong, vp, i32, vp, i32, i32, i32, vp, i32, vp]
+        L.pp_flow_operand.argtypes = [vp, i32, c.c_longlong, vp, i32, vp]
         L.pp_depth_points_nearest.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, f32, f32, vp, vp]
         L.pp_crop_resize_normalize.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, c.POINTER(c.c_double),
                                                c.POINTER(c.c_double), vp, vp, vp]

@@ -1267,7 +1267,8 @@ struct GemmPlan {
 // is one tile per workgroup) and bit-identical in their results.  fp32 operands (split on the fly, or fp32 MFMA): 0 / 1 = 128x128 at
 // 2 / 3 workgroups per CU, 2 = 128x64.  fp32 operands on aligned shapes: the fp32 engine (pp_gemm_f.hip; configurations 3 = 128x128,
 // 4 = 256x128, 5 = 256x256, 6 = 128x64, 7 = 256x192 — every one of them accumulates in the same order).  The round-1 gemm_kernel
-// keeps batched products, B [K][N], unaligned rows.  9 / 10: the tail split (tail_rows) of 5 / 4.
+// keeps batched products, B [K][N], unaligned rows.  9 / 10: the tail split (tail_rows) of 5 / 4.  11: the pre-split engine's 256x192
+// tile (vector epilogue, modes 0 - 2; the same accumulation order, the same bits) — for the fp32 engine 11 is not a configuration.
 static GemmPlan gemm_plan(const GemmView& v, int cfg, int cus) {
     const PpGemmDesc& d = v.d;
     GemmPlan p{};
@@ -1281,8 +1282,9 @@ static GemmPlan gemm_plan(const GemmView& v, int cfg, int cus) {
         if (cfg == 5 && d.N <= 128) cfg = 4;
         if (!v.u_vec && cfg != 2) cfg = 0;   // the element-wise epilogue exists for the two 128-row tiles
         p.engine = cfg == 6 ? GE_UH : GE_U;
-        p.tile = cfg == 5 ? PP_U_256x256 : cfg == 4 ? PP_U_256x128 : cfg == 2 ? PP_U_128x64 : PP_U_128x128;
         p.amode = cfg == 6 ? 1 : pp_gemm_u_mode(d, v.terms);
+        if (cfg == 11 && p.amode == 3) cfg = 4;   // (K slices: no 256x192 instantiation)
+        p.tile = cfg == 11 ? PP_U_256x192 : cfg == 5 ? PP_U_256x256 : cfg == 4 ? PP_U_256x128 : cfg == 2 ? PP_U_128x64 : PP_U_128x128;
         p.vec = v.u_vec;
     } else if (v.fvec && (cfg >= 3 || d.grp_rows != 0)) {
         if (cfg < 3) cfg = 3;   // a grouped batch exists on the engine only (the round-1 kernel would read group 0's weights for every row)
@@ -1358,6 +1360,9 @@ static int tune_candidates(const GemmView& v, int cus, int* c) {
         if (t4 >= cus / 2) c[n++] = 4;
         if (t5 >= cus / 2 && d.N > 128) c[n++] = 5;
         if (t5 >= cus / 2 && d.N > 128 && v.h_shape) c[n++] = 6;
+        // 256x192: the last 256-wide tile column would be more than a quarter empty (N = 192: corr_net[1] of the flow decoder)
+        static const bool tile192 = [] { const char* e = getenv("PP_GEMM_TILE_192"); return !(e && e[0] == '0'); }();   // (A/B switch)
+        if (tile192 && d.N % 256 > 128 && d.N % 256 <= 192 && v.u_vec && (long long)((d.M + 255) / 256) * ((d.N + 191) / 192) >= cus / 2) c[n++] = 11;
         if (tail_on && d.N > 128 && tail_rows(v, 256, cus)) c[n++] = 9;
         if (tail_on && tail_rows(v, 128, cus)) c[n++] = 10;
     } else if (v.fvec) {
@@ -1435,7 +1440,7 @@ int pp_gemm(const PpGemmDesc* desc, void* stream) {
     bool pinned = false;
     if (const char* f = getenv("PP_GEMM_FORCE_CFG")) {  // tests: pin one kernel configuration (recorded like any other launch)
         const int fc = atoi(f);
-        if (((fc == 9 || fc == 10) && (v.asplit || v.fvec)) || (fc >= 0 && fc <= 8 && (v.asplit || fc <= 2 || (v.fvec && fc <= 7)))) {
+        if (((fc == 9 || fc == 10) && (v.asplit || v.fvec)) || (fc == 11 && v.asplit) || (fc >= 0 && fc <= 8 && (v.asplit || fc <= 2 || (v.fvec && fc <= 7)))) {
             cfg = fc;
             pinned = true;
         }

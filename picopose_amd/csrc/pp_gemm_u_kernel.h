@@ -985,6 +985,9 @@ typedef TileCfg<256, 256, 2, 4, 2, 1, 0, 1> T256x256;   // 8 waves, 128x64 each,
 typedef TileCfg<256, 128, 4, 2, 3, 1, 1> T256x128;   // 8 waves, 64x64 each, 3 x 48 KB ring, prefetching schedule
 typedef TileCfg<128, 128, 2, 2, 2, 2> T128x128;   // 4 waves, 64x64 each, 2 x 32 KB ring: two workgroups per CU
 typedef TileCfg<128, 64, 2, 2, 3, 2> T128x64;     // 4 waves, 64x32 each, 3 x 24 KB ring: two workgroups per CU
+// 8 waves, 64x96 each (three pp_wperm blocks of 32 weight rows per wave), 2 x 56 KB ring, the unit schedule of the 128x128 tile: layers
+// whose N leaves a 256-wide tile column more than a quarter empty (the decoder's 192-channel corr_net[1])
+typedef TileCfg<256, 192, 4, 2, 2, 1> T256x192;
 
 template <class T, int MODE, int TERMS, bool VEC, int EPI = PP_EPI_GENERIC>
 static int pp_u_launch_one(const PpGemmDesc& d, int persistent_slots, hipStream_t st) {
@@ -1018,7 +1021,7 @@ static int pp_u_launch_tile(const PpGemmDesc& d, int mode, int slots, hipStream_
     if (mode == 0) return pp_u_launch_one<T, 0, TERMS, VEC>(d, slots, st);
     if (mode == 1) return pp_u_launch_one<T, 1, TERMS, VEC>(d, slots, st);
     if (mode == 3) {   // K slices: the hl format with the vector epilogue only (weight gradients of the training step)
-        if constexpr (TERMS == 2 && VEC) return pp_u_launch_one<T, 3, TERMS, VEC>(d, slots, st);
+        if constexpr (TERMS == 2 && VEC && !std::is_same<T, T256x192>::value) return pp_u_launch_one<T, 3, TERMS, VEC>(d, slots, st);
         else return PP_EINVAL;
     }
     return pp_u_launch_one<T, 2, TERMS, VEC>(d, slots, st);
@@ -1035,6 +1038,7 @@ static int pp_u_launch_terms(const PpGemmDesc& d, int tile, int mode, bool vec, 
     switch (tile) {
         case PP_U_256x256: return pp_u_launch_tile<T256x256, TERMS, true>(d, mode, cus, st);
         case PP_U_256x128: return pp_u_launch_tile<T256x128, TERMS, true>(d, mode, cus, st);
+        case PP_U_256x192: return pp_u_launch_tile<T256x192, TERMS, true>(d, mode, cus, st);
         case PP_U_128x128: return pp_u_launch_tile<T128x128, TERMS, true>(d, mode, 2 * cus, st);
         case PP_U_128x64: return pp_u_launch_tile<T128x64, TERMS, true>(d, mode, 2 * cus, st);
         default: return PP_EINVAL;

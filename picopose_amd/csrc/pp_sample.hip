@@ -260,6 +260,7 @@ __global__ __launch_bounds__(256) void corr_lookup_kernel(const float* __restric
             const float* t = tab + l * tw * tw + bi * tw + ai;  // x offset a-r -> dx = ai, y offset b-r -> dy = bi
             o[i] = t[0] * (wx0 * wy0) + t[1] * (wx1 * wy0) + t[tw] * (wx0 * wy1) + t[tw + 1] * (wx1 * wy1);
         }
+        for (int i = nout + lane; i < ld_out; i += 64) o[i] = 0.f;   // the pad channels of the row (the caller allocates without a fill)
     }
 }
 
@@ -320,6 +321,11 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_mfma_kernel(const void* __
         const float* fl = flow + ((size_t)b * H * W + (size_t)(y0 + my) * W + x0 + mx) * ld_flow;
         gx = (float)(x0 + mx) + fl[0];
         gy = (float)(y0 + my) + fl[1];
+    }
+    // the pad channels [L win^2, ld_out) of the tile's 64 rows: zeros (the caller allocates without a fill)
+    for (int npad = ld_out - L * win * win, idx = tid; idx < CM * npad; idx += 256) {
+        const int m = idx / npad, o = idx - m * npad;
+        out[((size_t)b * H * W + (size_t)(y0 + (m >> 3)) * W + x0 + (m & 7)) * ld_out + L * win * win + o] = 0.f;
     }
     for (int l = 0; l < L; ++l) {
         const int Hl = H >> l, Wl = W >> l;
@@ -703,6 +709,76 @@ __global__ __launch_bounds__(256) void conv_narrow_kernel(const _Float16* __rest
     }
 }
 
+// The flow of a decoder level as the operand of flow_net[0] (raft_decoder.py:141-147): row p of `op8` <- 8 channels, 0 and 1 = the flow,
+// 2..7 zero.  One thread per pixel; the split of pp_split_f16_chk, so the bits and the saturation report are those of a zero-padded
+// fp32 map going through split_act_kernel.
+__global__ __launch_bounds__(256) void flow_operand_kernel(const float* __restrict__ flow, int ld_flow, long long rows, _Float16* __restrict__ op8,
+                                                           int terms) {
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= rows) return;
+    const float* f = flow + p * ld_flow;
+    _Float16 h0, l0, h1, l1;
+    pp_split_f16_chk(f[0], h0, l0);
+    pp_split_f16_chk(f[1], h1, l1);
+    const _Float16 z = (_Float16)0.f;
+    const h8_t hi = {h0, h1, z, z, z, z, z, z}, lo = {l0, l1, z, z, z, z, z, z};
+    h8_t* o = (h8_t*)(op8 + p * 8 * terms);
+    o[0] = hi;
+    if (terms == 2) o[1] = lo;
+}
+
+// Patch-embed operand straight from the image bank: image j < n_front is front[j], image n_front + i is bank[index[i]] ((3, HW) fp32
+// planes); row (j HW + p) of `out` <- the 8-channel operand of pixel p (channels 0..2 = the planes' values, 3..7 zero) — what the row
+// gather, the concatenation, the NCHW -> NHWC-8 transpose and split_act_kernel leave, in one pass.  A workgroup stages PO_TILE pixels of
+// the three planes in LDS (16-byte loads along the plane where HW % 4 == 0) and writes the operand rows as consecutive 16-byte pieces
+// (terms = 2: piece 2 q = the hi terms of pixel q, 2 q + 1 its lo terms; terms = 1: piece q).  A bank row outside [0, n_rows) leaves its
+// image's rows unwritten, as gather_rows_kernel does.
+constexpr int PO_TILE = 1024;
+__global__ __launch_bounds__(256) void patch_operand_kernel(const float* __restrict__ bank, const long long* __restrict__ index, long long n_rows,
+                                                            const float* __restrict__ front, int n_front, int HW, _Float16* __restrict__ out,
+                                                            int terms) {
+    __shared__ __attribute__((aligned(16))) float t[3][PO_TILE];
+    const int j = blockIdx.y, tid = threadIdx.x;
+    const float* src;
+    if (j < n_front) {
+        src = front + (size_t)j * 3 * HW;
+    } else {
+        const long long r = index[j - n_front];
+        if (r < 0 || r >= n_rows) return;   // (uniform over the block, before the barrier)
+        src = bank + (size_t)r * 3 * HW;
+    }
+    const int p0 = blockIdx.x * PO_TILE, np = min(PO_TILE, HW - p0);
+    if ((HW & 3) == 0) {      // planes and tiles start on 16 bytes, np % 4 == 0
+        for (int i = tid; i < 3 * (np >> 2); i += 256) {
+            const int c = i / (np >> 2), q = i - c * (np >> 2);
+            *(f4*)&t[c][4 * q] = *(const f4*)(src + (size_t)c * HW + p0 + 4 * q);
+        }
+    } else {
+        for (int i = tid; i < 3 * np; i += 256) {
+            const int c = i / np, q = i - c * np;
+            t[c][q] = src[(size_t)c * HW + p0 + q];
+        }
+    }
+    __syncthreads();
+    h8_t* o = (h8_t*)(out + ((size_t)j * HW + p0) * 8 * terms);
+    const _Float16 z = (_Float16)0.f;
+    for (int i = tid; i < np * terms; i += 256) {
+        const int q = terms == 2 ? i >> 1 : i;
+        _Float16 h0, l0, h1, l1, h2, l2;
+        if (terms == 1 || (i & 1) == 0) {   // (one report per pixel)
+            pp_split_f16_chk(t[0][q], h0, l0);
+            pp_split_f16_chk(t[1][q], h1, l1);
+            pp_split_f16_chk(t[2][q], h2, l2);
+            o[i] = h8_t{h0, h1, h2, z, z, z, z, z};
+        } else {
+            pp_split_f16(t[0][q], h0, l0);
+            pp_split_f16(t[1][q], h1, l1);
+            pp_split_f16(t[2][q], h2, l2);
+            o[i] = h8_t{l0, l1, l2, z, z, z, z, z};
+        }
+    }
+}
+
 }  // namespace
 
 PP_SAT_SETTER(pp_sat_set_sample)
@@ -898,6 +974,26 @@ int pp_bank_rows_to_tokens(const float* bank, long long n_bank_rows, int C, int 
     if (n > 65535 || (P + 31) / 32 > 65535) return PP_EINVAL;   // grid.z / grid.y
     hipLaunchKernelGGL(bank_rows_to_tokens_kernel, dim3((C + 31) / 32, (P + 31) / 32, n), dim3(256), 0, (hipStream_t)stream, bank, index,
                        n_bank_rows, C, P, tokens, ld, T, skip);
+    return pp_last_launch();
+}
+
+int pp_patch_operand(const float* bank, long long n_bank_rows, const long long* index, int n, const float* front, int n_front, int H, int W,
+                     void* out, int terms, void* stream) {
+    if (!out || n < 0 || n_front < 0 || n + n_front <= 0 || H <= 0 || W <= 0 || (terms != 1 && terms != 2)) return PP_EINVAL;
+    if ((n > 0 && (!bank || !index || n_bank_rows <= 0)) || (n_front > 0 && !front)) return PP_EINVAL;
+    if (((uintptr_t)out | (n > 0 ? (uintptr_t)bank : 0) | (n_front > 0 ? (uintptr_t)front : 0)) % 16 != 0) return PP_EINVAL;
+    const long long hw = (long long)H * W, tiles = (hw + PO_TILE - 1) / PO_TILE;
+    if (n + n_front > 65535 || hw > 0x7fffffff || tiles > 0x7fffffff) return PP_EINVAL;   // grid.y; 32-bit pixel indices
+    hipLaunchKernelGGL(patch_operand_kernel, dim3((unsigned)tiles, n + n_front), dim3(256), 0, (hipStream_t)stream, bank, index, n_bank_rows,
+                       front, n_front, (int)hw, (_Float16*)out, terms);
+    return pp_last_launch();
+}
+
+int pp_flow_operand(const float* flow, int ld_flow, long long rows, void* out8, int terms, void* stream) {
+    if (!flow || !out8 || rows <= 0 || ld_flow < 2 || ((uintptr_t)out8 % 16) != 0 || (terms != 1 && terms != 2)) return PP_EINVAL;
+    if ((rows + 255) / 256 > 0x7fffffff) return PP_EINVAL;
+    hipLaunchKernelGGL(flow_operand_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, flow, ld_flow, rows,
+                       (_Float16*)out8, terms);
     return pp_last_launch();
 }
 

@@ -147,7 +147,8 @@ class FeatureExtractor(Packed):
         engine path — the training slices run them under autograd (picopose_amd/autograd.last_block_forward); embed_fn(self, x) ->
         token rows (B*T, C): the embedding under autograd (autograd.embed_tokens)."""
         v = self.dinov2
-        B, _, H, W = x.shape
+        # (x may be the patch embedding's prepared operand: a Split over (B*H*W, 8) with .image = (B, H, W) — ops.patch_operand)
+        B, H, W = x.image if isinstance(x, ops.Split) else (x.shape[0],) + tuple(x.shape[2:])
         p = v.patch_size
         assert H % p == 0 and W % p == 0  # patch_embed.py:73-74
         h0, w0 = H // p, W // p
@@ -158,7 +159,7 @@ class FeatureExtractor(Packed):
         if embed_fn is not None:
             xs = embed_fn(self, x)
         else:
-            img = ops.to_nhwc(x, c_pad=8)
+            img = x if isinstance(x, ops.Split) else ops.to_nhwc(x, c_pad=8)
             patches = ops.conv2d(img, pk["patch_w"], v.patch_embed.proj.bias, p, stride=p)        # (B,h0,w0,C)
             tok = ops.assemble_tokens(patches.view(B, h0 * w0, C), v.cls_token.reshape(C), self._pos(h0, w0))
             xs = tok.view(B * T, C)

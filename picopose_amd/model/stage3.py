@@ -106,8 +106,9 @@ class DPTHead(Packed):
         return ops.conv2d(h, pk[key + "_c2"], pk[key + "_b2"], 3, pad=1, relu_in=not isinstance(h, (ops.Split, ops.WinoInput)), residual=x,
                           residual2=extra, also_split="relu" if more else None, out_split=operand_only)
 
-    def _fuse(self, pk, i, size, x0, x1=None, train=False):
-        """FeatureFusionBlock (dpt.py:129-156)."""
+    def _fuse(self, pk, i, size, x0, x1=None, train=False, operand_only=False):
+        """FeatureFusionBlock (dpt.py:129-156).  operand_only: nothing reads the block's path map as fp32 (the finest map on its way to the
+        flow decoder's 1x1 projection) — it leaves the interpolation as a Split with .image, the fp32 copy is not stored."""
         if train:
             out = x0 if x1 is None else self._rcu_train(i, 1, x1, extra=x0)
             out = self._rcu_train(i, 2, out)
@@ -118,15 +119,17 @@ class DPTHead(Packed):
                 # the path map leaves the resize as fp32 and as the operand of the flow decoder's 1x1 projection
                 out = self._rcu(pk, f"f{i}_u2", out, operand_only=True)
                 out = ops.conv2d(out, pk[f"f{i}_out"], getattr(self.scratch, f"refinenet{i}").out_conv.bias, 1)
-                return ops.resize_bilinear(out, size[0], size[1], also_split=True)
+                return ops.resize_bilinear(out, size[0], size[1], **(dict(out_split=True) if operand_only else dict(also_split=True)))
             out = self._rcu(pk, f"f{i}_u2", out)
         out = ops.resize_bilinear(out, size[0], size[1], out_split=True)   # feeds only the 1x1 out_conv
         # the path map is an output (fp32) AND the input of the flow decoder's 1x1 projection: its operand form rides along
         return ops.conv2d(out, pk[f"f{i}_out"], getattr(self.scratch, f"refinenet{i}").out_conv.bias, 1, also_split="plain")
 
-    def forward_nhwc(self, feats, train=False):
+    def forward_nhwc(self, feats, train=False, finest_operand_only=False):
         """feats: 4 NHWC maps (B,16,16,C) (may be views with a free batch stride) -> [path_4, path_3, path_2] NHWC.
-        train: the ResidualConvUnits' BatchNorms run in training mode (one statistics update per call)."""
+        train: the ResidualConvUnits' BatchNorms run in training mode (one statistics update per call).
+        finest_operand_only: the caller reads path_2 only as the operand of the flow decoder's projection (Net's batched eval path): on a
+        pre-split engine it comes back as a Split with .image instead of an fp32 map with `._hl` (PP_DECODER_LEAN=0: never)."""
         pk, r = self.packed(for_training=train), self.resize_layers
         # (the projected maps feed only their resize layer, the resized maps only their layerK_rn convolution: operand-only
         # outputs on the f16x3 engine — no fp32 store, no split pass)
@@ -151,7 +154,7 @@ class DPTHead(Packed):
             assert tuple(rn[0].shape[1:3]) == size1
         p4 = self._fuse(pk, 4, rn[2].shape[1:3], rn[3], train=train)
         p3 = self._fuse(pk, 3, rn[1].shape[1:3], p4, rn[2], train)
-        p2 = self._fuse(pk, 2, size1, p3, rn[1], train)
+        p2 = self._fuse(pk, 2, size1, p3, rn[1], train, operand_only=finest_operand_only and not train and ops.decoder_lean())
         if train:
             self.bn_moved()              # eval re-folds the running buffers on its next call
         return [p4, p3, p2]
@@ -242,13 +245,15 @@ class FlowDecoder(Packed):
         pkt = self.packed_train() if train else None
         pk = self.packed(for_training=train)
         flows, certs = [], []
+        lean = ops.decoder_lean() and not train       # PP_DECODER_LEAN=0: every fp32 map and the torch glue of the flow operands, as before
         for l in range(self.num_levels):
             fr_in, fq_in = feat_render_list[l], feat_real_list[l]
-            B, H, W, _ = fr_in.shape
+            # (a path map may arrive as an operand only — a Split with .image: DPTHead.forward_nhwc(finest_operand_only=True))
+            B, H, W = fr_in.image if isinstance(fr_in, ops.Split) else fr_in.shape[:3]
             # decoder input [render | warped real | motion] (640 channels).  f32 engine: an fp32 NHWC buffer X the producers
             # write their slices of.  f16x3 engine: X never exists — the producers write their columns of the OPERAND Xs the
-            # two heads read (the 1x1 projection also keeps its fp32 map for the correlation lookup), which removes the
-            # read + write of the whole concat by a separate split pass.
+            # two heads read (the 1x1 projection keeps its fp32 map only where the correlation lookup reads it), which removes
+            # the read + write of the whole concat by a separate split pass.
             opcat = ops.presplit()
             dev = fr_in.device
             if opcat:
@@ -271,15 +276,18 @@ class FlowDecoder(Packed):
                     X[..., 0:256] = fr
             else:
                 fq = ops.conv2d(getattr(fq_in, "_hl", fq_in), pk[f"proj{l}"], pk[f"proj{l}_b"], 1, also_split="plain" if opcat else None)
-                if opcat:
-                    fr = ops.conv2d(fr_src, pk[f"proj{l}"], pk[f"proj{l}_b"], 1, hl_into=(Xs, 0),
-                                    out=torch.empty(B, H, W, 256, dtype=torch.float32, device=dev))
-                else:
-                    fr = ops.conv2d(fr_src, pk[f"proj{l}"], pk[f"proj{l}_b"], 1, out=X[..., 0:256])   # straight into its slice of X
-            ncorr = (l + 1) * (2 * self.r + 1) ** 2
             # (f16x3 engine: both maps already exist as operands — the render map as columns 0..255 of Xs, the real map from
             # its projection's epilogue — so the lookup stages copies instead of splitting every chunk)
             hl_maps = dict(f1_hl=(Xs, 0), f2_hl=getattr(fq, "_hl", None)) if opcat and not train and ops.terms() == 2 else {}
+            if not train and opcat:
+                # the lookup is the only reader of the render projection as fp32, and on its operand branch it reads the columns of Xs
+                # instead (ops.corr_takes_operands — the lookup's own test): the projection then stores operand columns alone
+                fr_dead = lean and bool(hl_maps) and ops.corr_takes_operands(hl_maps["f1_hl"], hl_maps["f2_hl"], H, W, 256)
+                fr = ops.conv2d(fr_src, pk[f"proj{l}"], pk[f"proj{l}_b"], 1, hl_into=(Xs, 0),
+                                out=None if fr_dead else torch.empty(B, H, W, 256, dtype=torch.float32, device=dev))
+            elif not train:
+                fr = ops.conv2d(fr_src, pk[f"proj{l}"], pk[f"proj{l}_b"], 1, out=X[..., 0:256])   # straight into its slice of X
+            ncorr = (l + 1) * (2 * self.r + 1) ** 2
             corr = ops.corr_lookup(fr, fq, flow, l + 1, self.r, c_pad=-(-ncorr // 8) * 8, **hl_maps)
             # [corr feat 192 | flow feat 64]: on the f16x3 engine the concat exists only as the operand of out_net
             hl_cat = opcat
@@ -291,15 +299,19 @@ class FlowDecoder(Packed):
             c1 = ops.conv2d(corr, pk[f"e{l}_corr0"], getattr(e.corr_net, "0").conv.bias, 1, act="relu", out_split=True)
             ops.conv2d(c1, pk[f"e{l}_corr1"], getattr(e.corr_net, "1").conv.bias, 3, pad=1, act="relu",
                        **(dict(hl_into=(cf, 0)) if hl_cat else dict(out=cf[..., 0:192])))
-            flow8 = torch.zeros(B, H, W, 8, dtype=torch.float32, device=dev)
-            flow8[..., 0:2] = flow
-            f1 = ops.conv2d(flow8, pk[f"e{l}_flow0"], getattr(e.flow_net, "0").conv.bias, 7, pad=3, act="relu", out_split=True)
+            if lean and opcat:
+                flow8 = ops.flow_operand(flow)      # the zero-padded 8-channel operand in one launch: no fp32 map, no fill, no split pass
+            else:
+                flow8 = torch.zeros(B, H, W, 8, dtype=torch.float32, device=dev)
+                flow8[..., 0:2] = flow
+            f1 =ops.conv2d(flow8, pk[f"e{l}_flow0"], getattr(e.flow_net, "0").conv.bias, 7, pad=3, act="relu", out_split=True)
             ops.conv2d(f1, pk[f"e{l}_flow1"], getattr(e.flow_net, "1").conv.bias, 3, pad=1, act="relu",
                        **(dict(hl_into=(cf, 192)) if hl_cat else dict(out=cf[..., 192:256])))
             if opcat:
                 # motion = cat([out_net (126), flow (2)]) (raft_decoder.py:161), written straight into its operand columns
                 ops.conv2d(cf, pk[f"e{l}_out0_128"], pk[f"e{l}_out0_b128"], 3, pad=1, act="relu", hl_into=(Xs, 512))
-                ops.hl_patch_columns(flow[..., 0:2].contiguous() if flow.shape[-1] != 2 else flow, Xs, 638)
+                # (after out_net: its 128-column epilogue has just written zeros there.  The kernel takes the flow's pixel stride)
+                ops.hl_patch_columns(flow[..., 0:2] if lean else (flow[..., 0:2].contiguous() if flow.shape[-1] != 2 else flow), Xs, 638)
                 ops.warp(fq, flow, hl_into=(Xs, 256))               # feature_sample (flow_decoder.py:49-56)
             else:
                 ops.conv2d(cf, pk[f"e{l}_out0"], getattr(e.out_net, "0").conv.bias, 3, pad=1, act="relu", out=X[..., 512:638])

@@ -319,14 +319,59 @@ def split_activation(x, B, P, C, batch_stride, row_stride, relu=False, into=None
 
 
 def hl_patch_columns(x, tgt, col0):
-    """Columns col0 .. col0 + c - 1 of the Split `tgt` <- x (..., c) fp32 (contiguous): the narrow member of an operand concat."""
+    """Columns col0 .. col0 + c - 1 of the Split `tgt` <- x (..., c) fp32 (contiguous, or the leading channels of contiguous wider
+    rows: a channel slice): the narrow member of an operand concat."""
     c = x.shape[-1]
     rows = x.numel() // c
-    assert x.is_contiguous() and rows == tgt.shape[0] and col0 + c <= tgt.shape[1]
-    _lib.check(_lib.lib().pp_hl_patch_columns_t(_p(x), c, c, rows, _p(tgt.hl), tgt.shape[1], col0, tgt.terms, _lib.stream_ptr()),
+    ld = c if x.is_contiguous() else x.stride(-2)
+    assert rows == tgt.shape[0] and col0 + c <= tgt.shape[1]
+    assert x.is_contiguous() or (x.dim() >= 2 and x.stride(-1) == 1 and ld >= c
+                                 and all(x.stride(i) == x.stride(i + 1) * x.shape[i + 1] for i in range(x.dim() - 2)))
+    _lib.check(_lib.lib().pp_hl_patch_columns_t(_p(x), ld, c, rows, _p(tgt.hl), tgt.shape[1], col0, tgt.terms, _lib.stream_ptr()),
                "pp_hl_patch_columns_t")
     if CHECK_SATURATION:   # (the 8-channel groups holding the patched columns; their other members are already written)
         _chk(tgt.cols(col0 // 8 * 8, -(-(col0 + c) // 8) * 8 - col0 // 8 * 8), "pp_hl_patch_columns_t")
+
+
+def flow_operand(flow):
+    """flow (B,H,W,>=2) fp32 (x, y first; channel-contiguous pixels with any pixel stride) -> Split (B*H*W, 8) with .image: the operand
+    of flow_net[0], channels 2..7 zero — the bits of zeros + slice copy + split_activation, in one launch (pp_flow_operand)."""
+    B, H, W = flow.shape[:3]
+    assert presplit() and flow.dtype == torch.float32 and flow.shape[3] >= 2 and flow.stride(3) == 1
+    assert flow.stride(1) == W * flow.stride(2) and flow.stride(0) == H * flow.stride(1)
+    sp = Split.empty(B * H * W, 8, flow.device)
+    sp.image = (B, H, W)
+    _lib.check(_lib.lib().pp_flow_operand(_p(flow), flow.stride(2), B * H * W, _p(sp.hl), sp.terms, _lib.stream_ptr()), "pp_flow_operand")
+    _chk(sp.hl, "pp_flow_operand")
+    return sp
+
+
+def patch_operand_on():
+    """PP_PATCH_OPERAND (default on; read per call): the selected templates' patch-embed operand is written straight from the image bank
+    (patch_operand); "0": gather_rows -> cat -> to_nhwc -> split_activation — the same bits."""
+    return os.environ.get("PP_PATCH_OPERAND", "1") != "0"
+
+
+def patch_operand_ok(bank, front=None):
+    """The shapes / layouts `patch_operand` takes: a contiguous fp32 (R, 3, H, W) bank (and such a `front`), a pre-split mode."""
+    ok = lambda t: (t.dim() == 4 and t.shape[1] == 3 and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0)  # noqa: E731
+    return (presplit() and ok(bank) and bank.shape[0] > 0
+            and (front is None or (ok(front) and front.shape[2:] == bank.shape[2:] and front.device == bank.device)))
+
+
+def patch_operand(bank, index, front=None):
+    """bank (R,3,H,W) contiguous fp32, index (n,) int64, front (Bn,3,H,W) or None -> Split ((Bn + n)*H*W, 8) with .image =
+    (Bn + n, H, W): the patch-embed convolution's operand of [front ; bank[index]] (channels 3..7 zero), one pass (pp_patch_operand)
+    instead of gather_rows, torch.cat, to_nhwc(c_pad=8) and split_activation."""
+    assert patch_operand_ok(bank, front) and index.dtype == torch.int64 and index.device == bank.device
+    R, _, H, W = bank.shape
+    n, nf = index.numel(), 0 if front is None else front.shape[0]
+    sp = Split.empty((nf + n) * H * W, 8, bank.device)
+    sp.image = (nf + n, H, W)
+    _lib.check(_lib.lib().pp_patch_operand(_p(bank), R, _p(index.contiguous()), n, _p(front), nf, H, W, _p(sp.hl), sp.terms,
+                                           _lib.stream_ptr()), "pp_patch_operand")
+    _chk(sp.hl, "pp_patch_operand")
+    return sp
 
 
 def _can_presplit(x, K, C, *strides):
@@ -1217,23 +1262,41 @@ def avgpool2(x):
     return out
 
 
+def decoder_lean():
+    """PP_DECODER_LEAN (default on; read per call): the flow decoder and the DPT head store no fp32 map that nothing reads and build the
+    flow's operands in one launch (model/stage3.py); "0" restores the fp32 maps and the torch glue — the same bits either way."""
+    return os.environ.get("PP_DECODER_LEAN", "1") != "0"
+
+
+def corr_takes_operands(f1_hl, f2_hl, H, W, C):
+    """Whether corr_lookup reads the two maps as the operands f1_hl / f2_hl (pp_corr_lookup_nhwc_hl) — then nothing reads the fp32 form of
+    f1, and its producer need not store it (FlowDecoder.forward_nhwc asks this same function before it decides)."""
+    return (f1_hl is not None and f2_hl is not None and precision() == "f16x3" and f2_hl.terms == 2 and H % 8 == 0 and W % 8 == 0 and C % 32 == 0
+            and os.environ.get("PP_CORR_TILED", "1") != "0" and os.environ.get("PP_CORR_HL", "1") != "0")
+
+
 def corr_lookup(f1, f2, flow, levels, radius, c_pad=None, f1_hl=None, f2_hl=None):
     """Correlation pyramid + lookup, NHWC: (B,H,W,C) x2, flow (B,H,W,>=2) -> (B,H,W,levels*(2r+1)^2)
     (c_pad: channel count of the result, zero-filled beyond the levels*(2r+1)^2 real channels).
     f1 may be a channel slice of a wider buffer; f2 may hold B / k images (image b reads f2[b % (B / k)]).
     f1_hl = (Split over (B*H*W, Ctot), col0), f2_hl = Split over (Bf*H*W, C): the same maps as operands the producers have
-    already written (f16x3 engine, tileable shapes): the kernel then stages 16-byte copies instead of splitting every chunk."""
-    B, H, W, C = f1.shape
-    assert f2.is_contiguous() and flow.stride(3) == 1 and B % f2.shape[0] == 0 and tuple(f2.shape[1:]) == (H, W, C)
-    assert f1.stride(3) == 1 and f1.stride(1) == W * f1.stride(2) and f1.stride(0) == H * f1.stride(1)
+    already written (f16x3 engine, tileable shapes): the kernel then stages 16-byte copies instead of splitting every chunk.
+    f1 = None: the map exists only as f1_hl (allowed exactly where `corr_takes_operands` holds)."""
+    (H, W, C), B = f2.shape[1:], flow.shape[0]
+    assert f2.is_contiguous() and flow.stride(3) == 1 and B % f2.shape[0] == 0 and tuple(flow.shape[1:3]) == (H, W)
+    operands = corr_takes_operands(f1_hl, f2_hl, H, W, C)
+    if f1 is None:
+        assert operands, "corr_lookup without the fp32 map f1 needs the operand form of both maps (corr_takes_operands)"
+    else:
+        assert tuple(f1.shape) == (B, H, W, C) and f1.stride(3) == 1 and f1.stride(1) == W * f1.stride(2) and f1.stride(0) == H * f1.stride(1)
     pyr = [f2]
     for _ in range(levels - 1):
         pyr.append(avgpool2(pyr[-1]))
     n = levels * (2 * radius + 1) ** 2
     np_ = c_pad if c_pad and c_pad > n else n
-    out = (torch.zeros if np_ > n else torch.empty)(B, H, W, np_, dtype=torch.float32, device=f1.device)
-    if (f1_hl is not None and f2_hl is not None and precision() == "f16x3" and f2_hl.terms == 2 and H % 8 == 0 and W % 8 == 0 and C % 32 == 0
-            and os.environ.get("PP_CORR_TILED", "1") != "0" and os.environ.get("PP_CORR_HL", "1") != "0"):
+    # (the kernels write the pad channels of their rows themselves; PP_DECODER_LEAN=0: the separate fill of the whole map, as before)
+    out = (torch.zeros if np_ > n and not decoder_lean() else torch.empty)(B, H, W, np_, dtype=torch.float32, device=f2.device)
+    if operands:
         tgt, col0 = f1_hl
         assert tgt.shape[0] == B * H * W and col0 % 8 == 0 and col0 + C <= tgt.shape[1] and f2_hl.shape == (f2.shape[0] * H * W, C)
         hls = [f2_hl.hl] + [split_activation(p, p.shape[0], p.shape[1] * p.shape[2], C, p.shape[1] * p.shape[2] * C, C) for p in pyr[1:]]

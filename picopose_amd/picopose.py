@@ -47,7 +47,13 @@ def _tensor_key(t, fe=None):
 
 
 def _image_rows(p, b0, b1):
-    """Images b0 .. b1 of an NHWC map, with its attached operand form (`._hl`, model/stage3.py) cut the same way."""
+    """Images b0 .. b1 of an NHWC map, with its attached operand form (`._hl`, model/stage3.py) cut the same way; a map that exists
+    as an operand only (a Split with .image) is cut as one."""
+    if isinstance(p, ops.Split):
+        hw = p.image[1] * p.image[2]
+        s = ops.Split(p.hl[b0 * hw:b1 * hw], p.terms)
+        s.image = (b1 - b0,) + tuple(p.image[1:])
+        return s
     q = p[b0:b1]
     hl = getattr(p, "_hl", None)
     if hl is not None:
@@ -171,12 +177,21 @@ class Net(nn.Module):
         # nothing reads it) and stage 2 reads the bank rows as they are
         bank = end_points.get("tem_bank") if tem_cached is None else None
         T = h0 * w0 + 1
+        rgb_rows = end_points.get("tem_rgb_rows")      # (flattened image bank, selected rows) instead of "tem_rgb": forward_hypotheses
+
+        def tem_images(front=None):
+            """The template-side input of the ViT, [front ; selected renders]: the images, or the patch embedding's operand."""
+            if rgb_rows is not None and ops.patch_operand_ok(rgb_rows[0], front):
+                return ops.patch_operand(*rgb_rows, front=front)
+            tem = end_points["tem_rgb"] if rgb_rows is None else ops.gather_rows(*rgb_rows)
+            return tem if front is None else torch.cat([front, tem])
+
         if tem_cached is None and pre is not None and levels is not None:
             # the next batch's query ViT rides in this batch's template pass: rows [next queries ; templates] of one launch per layer
             # (a GEMM row does not depend on the other rows: every token keeps its bits); its four levels stay behind as the stash
             alloc, nxt = pre
             Bn = nxt.shape[0]
-            both, _ = fe.forward_tokens(torch.cat([nxt, end_points["tem_rgb"]]), level_out=(alloc, 0), full_depth=None if bank is None else Bn)
+            both, _ = fe.forward_tokens(tem_images(nxt), level_out=(alloc, 0), full_depth=None if bank is None else Bn)
             tem_tok = [t[Bn:] for t in both]
             if bank is not None:
                 nT = tem_tok[0].shape[0]
@@ -186,7 +201,7 @@ class Net(nn.Module):
             # batch of the same shape, whose key would then match
             self._query_stash = (_tensor_key(nxt, fe), [a[:Bn * T].clone() for a in alloc], (h0, w0), nxt)
         elif tem_cached is None:
-            tem_tok, _ = fe.forward_tokens(end_points["tem_rgb"], level_out=None if levels is None else (levels, 0),
+            tem_tok, _ = fe.forward_tokens(tem_images(), level_out=None if levels is None else (levels, 0),
                                            full_depth=None if bank is None else 0)
             if bank is not None:
                 nT = tem_tok[0].shape[0]
@@ -211,7 +226,8 @@ class Net(nn.Module):
             # ONE pass of the DPT head over [templates ; query crops] (the same weights; a row of a GEMM does not depend on the
             # other rows, so every map keeps the bits two passes give it): larger launches, half as many of them
             nT, nR = tem_tok[0].shape[0], levels[0].shape[0] // T - tem_tok[0].shape[0]
-            both = orr.dpt_head.forward_nhwc([as_img(lv.view(-1, T, lv.shape[1])) for lv in levels])
+            # (the finest path map feeds only the flow decoder's projection: no fp32 copy of it — DPTHead.forward_nhwc)
+            both = orr.dpt_head.forward_nhwc([as_img(lv.view(-1, T, lv.shape[1])) for lv in levels], finest_operand_only=True)
             tem_dpt, real_dpt = [_image_rows(p_, 0, nT) for p_ in both], [_image_rows(p_, nT, nT + nR) for p_ in both]
         else:
             if real_dpt is None:
@@ -255,9 +271,18 @@ class Net(nn.Module):
         N = end_points["tem_pose"].shape[1]
         trow = rows if tidx is None else tidx[rows]                      # bank row of every sample: its crop, or the crop's object
         flat = trow * N + idx                                            # row of (b, template) in the (B*N, ...) / (O*N, ...) view
+        # the selected renders are read once, by the patch embedding: where its operand can be written straight from the bank
+        # (ops.patch_operand: forward_test's batched eval path, a pre-split mode, a contiguous fp32 bank, no template_cache) they are
+        # neither gathered here nor concatenated there — forward_test_hyp gets (flattened bank, rows) instead of the images
+        rgb_rows = None
+        if (ops.patch_operand_on() and not self.training and cache is None and levels is not None and end_points["tem_rgb"].dim() == 5
+                and end_points["tem_rgb"].is_contiguous() and flat.dtype == torch.int64 and ops.patch_operand_ok(end_points["tem_rgb"].flatten(0, 1))):
+            rgb_rows = (end_points["tem_rgb"].flatten(0, 1), flat)
         sel = {key: (ops.gather_rows(end_points[key].flatten(0, 1), flat) if end_points[key].is_contiguous()
                      else end_points[key][trow, idx])
-               for key in ("tem_pose", "tem_K", "tem_M", "tem_mask", "tem_rgb", "tem_pts3d")}
+               for key in ("tem_pose", "tem_K", "tem_M", "tem_mask", "tem_rgb", "tem_pts3d") if not (key == "tem_rgb" and rgb_rows is not None)}
+        if rgb_rows is not None:
+            sel["tem_rgb_rows"] = rgb_rows
         if self._last_from_bank(end_points):
             sel["tem_bank"] = (end_points["template_feature"].flatten(0, 1), flat)
         for key in ("real_pts2d", "real_K", "real_M", "real_mask", "real_pose"):
