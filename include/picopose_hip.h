@@ -541,6 +541,18 @@ int pp_saturation_take(unsigned int* word, unsigned int* slot, void* stream);
 int pp_corr_lookup_nhwc_hl(const void* f1_hl, int ld_f1, const void* f2_hl_l0, const void* f2_hl_l1, const void* f2_hl_l2,
                            int f2_batch, const float* flow, int B, int H, int W, int C, int levels, int radius, int ld_flow,
                            float* out, int ld_out, void* stream);
+/* The same lookup with the choice of output: exactly one of `out` (the fp32 map, rows of ld_out floats) and `out_hl` (the result
+ * as an hl operand with rows of ld_out_h channels, ld_out_h % 8 == 0 and >= levels (2 radius + 1)^2: the operand of the 1x1
+ * convolution that reads the map, pad channels zero — the bits and the saturation report of the fp32 map going through
+ * pp_split_activation, with no fp32 map stored).  Both entries take the ring-staged kernel (per-level regions of the query map,
+ * chunks moved into LDS by LDS-DMA) unless PP_CORR_RING=0 (read per call), which keeps the register-staged kernel: the same bits. */
+int pp_corr_lookup_nhwc_hl_op(const void* f1_hl, int ld_f1, const void* f2_hl_l0, const void* f2_hl_l1, const void* f2_hl_l2,
+                              int f2_batch, const float* flow, int B, int H, int W, int C, int levels, int radius, int ld_flow,
+                              float* out, int ld_out, void* out_hl, int ld_out_h, void* stream);
+/* pp_avgpool2_nhwc with the pooled map's hl operand written by the same kernel (C % 8 == 0; in and out 16-byte aligned): out_hl
+ * (B (H/2) (W/2), 2 C) holds the bits of pp_split_activation on the pooled map (same sum order, same saturation report); out may be
+ * null (a pyramid level whose fp32 form nothing reads). */
+int pp_avgpool2_hl(const float* in, int B, int H, int W, int C, float* out, void* out_hl, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * utils/pose_recovery.py:68-105 pose_recovery_ransac_pnp, batched over P = instances x hypotheses

@@ -181,6 +181,37 @@ __global__ __launch_bounds__(256) void avgpool2_kernel(const float* __restrict__
     }
 }
 
+// The same pool with the pooled map's hl operand written alongside (C % 8 == 0; a thread takes 4 channels: half of a group of 8 — 4 hi and
+// 4 lo terms): the sum order and the factor of avgpool2_kernel, the split of pp_split_f16_chk — the bits and the saturation report of
+// avgpool2_kernel followed by split_act_kernel.  out may be null (the last pyramid level: only its operand is read).
+__global__ __launch_bounds__(256) void avgpool2_hl_kernel(const float* __restrict__ in, int H, int W, int C, float* __restrict__ out,
+                                                          _Float16* __restrict__ out_hl) {
+    const int Ho = H / 2, Wo = W / 2, b = blockIdx.y, C4 = C >> 2;
+    const size_t n4 = (size_t)Ho * Wo * C4;
+    const float* ib = in + (size_t)b * H * W * C;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const int c = (int)(i % C4) * 4;
+        const size_t q = i / C4;
+        const int ox = (int)(q % Wo), oy = (int)(q / Wo);
+        const float* p = ib + ((size_t)(2 * oy) * W + 2 * ox) * C + c;
+        const f4 p0 = *(const f4*)p, p1 = *(const f4*)(p + C), p2 = *(const f4*)(p + (size_t)W * C), p3 = *(const f4*)(p + (size_t)W * C + C);
+        f4 v;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = ((p0[k] + p1[k]) + (p2[k] + p3[k])) * 0.25f;
+        const size_t row = (size_t)b * Ho * Wo + q;
+        if (out) *(f4*)(out + row * C + c) = v;
+        _Float16 h0, h1, h2, h3, l0, l1, l2, l3;
+        pp_split_f16_chk(v[0], h0, l0);
+        pp_split_f16_chk(v[1], h1, l1);
+        pp_split_f16_chk(v[2], h2, l2);
+        pp_split_f16_chk(v[3], h3, l3);
+        _Float16* o = out_hl + row * 2 * (size_t)C + pp_hl_col(c, 0);
+        typedef _Float16 h4w __attribute__((ext_vector_type(4)));
+        *(h4w*)o = h4w{h0, h1, h2, h3};
+        *(h4w*)(o + 8) = h4w{l0, l1, l2, l3};
+    }
+}
+
 // CorrelationPyramid + CorrLookup fused — raft_decoder.py:30-53, corr_lookup.py:100-134.
 // corr_l[p, q] = <f1[p], pool_l(f2)[q]> / sqrt(C); for every pixel p and level l the (2r+1)^2
 // window around (p + flow[p]) / 2^l is bilinearly sampled (zeros padding).  Output channel
@@ -286,6 +317,21 @@ typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
 constexpr int CSP = CN + 4;                    // row pitch of S
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
+// One result element of the tiled lookups: channel ch of pixel row `row`, into the fp32 map (rows of ld_out floats) or, out_hl given, into
+// the hl operand of the 1x1 convolution that reads the map (rows of ld_out channels = 2 ld_out halfs) — the split of pp_split_f16_chk, so
+// the bits and the saturation report are those of the fp32 map going through split_act_kernel.
+__device__ __forceinline__ void corr_put(float* __restrict__ out, _Float16* __restrict__ out_hl, size_t row, int ld_out, int ch, float v) {
+    if (out_hl) {
+        _Float16 h, l;
+        pp_split_f16_chk(v, h, l);
+        _Float16* q = out_hl + row * 2 * (size_t)ld_out + pp_hl_col(ch, 0);
+        q[0] = h;
+        q[8] = l;
+    } else {
+        out[row * ld_out + ch] = v;
+    }
+}
+
 // HLIN: f1 / f2 arrive as the engine's hl operand (fp16 [rows][2 ld]: per 8 channels 8 hi then 8 lo terms — what the
 // producing convolution's epilogue writes): staging is 16-byte copies, no split arithmetic (it was as long as the MFMAs of a
 // chunk).  Same bits either way: the split of a value does not depend on who performs it.
@@ -300,7 +346,8 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_mfma_kernel(const void* __
                                                                   const void* __restrict__ f2l0, const void* __restrict__ f2l1,
                                                                   const void* __restrict__ f2l2, const float* __restrict__ flow,
                                                                   int B, int H, int W, int C, int L, int r, int ld_flow,
-                                                                  float inv_sqrt_c, float* __restrict__ out, int ld_out) {
+                                                                  float inv_sqrt_c, float* __restrict__ out, int ld_out,
+                                                                  _Float16* __restrict__ out_hl) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* As = sm;                        // [CM][CKP]
     float* Bs = sm + CM * CKP;             // [CN][CKP]
@@ -325,7 +372,7 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_mfma_kernel(const void* __
     // the pad channels [L win^2, ld_out) of the tile's 64 rows: zeros (the caller allocates without a fill)
     for (int npad = ld_out - L * win * win, idx = tid; idx < CM * npad; idx += 256) {
         const int m = idx / npad, o = idx - m * npad;
-        out[((size_t)b * H * W + (size_t)(y0 + (m >> 3)) * W + x0 + (m & 7)) * ld_out + L * win * win + o] = 0.f;
+        corr_put(out, out_hl, (size_t)b * H * W + (size_t)(y0 + (m >> 3)) * W + x0 + (m & 7), ld_out, L * win * win + o, 0.f);
     }
     for (int l = 0; l < L; ++l) {
         const int Hl = H >> l, Wl = W >> l;
@@ -351,7 +398,7 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_mfma_kernel(const void* __
         for (int idx = tid; idx < CM * win * win; idx += 256) {   // neighbourhoods outside the image: zeros
             const int m = idx / (win * win), o = idx - m * (win * win);
             if (s_state[m] == 2)
-                out[((size_t)b * H * W + (size_t)(y0 + (m >> 3)) * W + x0 + (m & 7)) * ld_out + l * win * win + o] = 0.f;
+                corr_put(out, out_hl, (size_t)b * H * W + (size_t)(y0 + (m >> 3)) * W + x0 + (m & 7), ld_out, l * win * win + o, 0.f);
         }
         while (s_todo > 0) {                                // (uniform: read after a barrier, written before the next)
             // ---- region of this pass: origin = smallest bx still to do, then the smallest by among its column band
@@ -501,8 +548,8 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_mfma_kernel(const void* __
                     const float cx = s_cx[m], cy = s_cy[m];
                     const float wx1 = cx - floorf(cx), wy1 = cy - floorf(cy), wx0 = 1.f - wx1, wy0 = 1.f - wy1;
                     const float* t = S + m * CSP + (dy + bi) * CRW + dx + ai;   // x offset a-r -> +ai, y offset b-r -> +bi
-                    out[((size_t)b * H * W + (size_t)(y0 + (m >> 3)) * W + x0 + (m & 7)) * ld_out + l * win * win + o] =
-                        t[0] * (wx0 * wy0) + t[1] * (wx1 * wy0) + t[CRW] * (wx0 * wy1) + t[CRW + 1] * (wx1 * wy1);
+                    corr_put(out, out_hl, (size_t)b * H * W + (size_t)(y0 + (m >> 3)) * W + x0 + (m & 7), ld_out, l * win * win + o,
+                             t[0] * (wx0 * wy0) + t[1] * (wx1 * wy0) + t[CRW] * (wx0 * wy1) + t[CRW + 1] * (wx1 * wy1));
                 }
             }
             __syncthreads();
@@ -517,6 +564,240 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_mfma_kernel(const void* __
         }
         __syncthreads();
     }
+}
+
+// ---- the operand-input lookup again: a region per pyramid level, chunks staged by LDS-DMA into a ring ------------------------------
+// Same tiles, same pass loop and same arithmetic as corr_lookup_mfma_kernel<true> (an entry of S is accumulated over the channels in
+// ascending order, per 16 channels hi.hi, hi.lo, lo.hi; it does not depend on the region or the pass that produced it: the same bits),
+// but
+//   * every level has its own compile-time region: 16 x 16 at level 0 as before; the footprint of an 8 x 8 tile shrinks to 4 + 6 positions
+//     at the once-pooled level and 2 + 6 at the twice-pooled one, and both take 11 x 11 (slack for flow divergence inside the tile: 2 and
+//     12 source pixels, against 3 at level 0; one pass per tile on the benchmark's flows down to 10 x 10, profiles/r13) — 128 columns of S
+//     instead of 256, half the rows fetched and multiplied;
+//   * a K step is 16 channels, one 64-byte segment per row, moved global -> LDS by LDS-DMA (pp_gemm_u_kernel.h): no staging registers,
+//     no ds_write.  A wave instruction fills 16 rows; the 16-byte chunk c of row r sits at position c ^ (r >> 2 & 3) — conflict-free
+//     ds_read_b128 for the 32x32x16 fragment pattern (lane l: row l & 31, chunk 2 (l >> 5) + term) — applied to the per-lane SOURCE
+//     address.  Ring of two stages, one wait and one barrier per step;
+//   * S holds one half of the tile's pixels at a time (32 rows: 33 KB), so ring and S fit in 40 KB and THREE workgroups share a CU: the
+//     kernel is bound by its serial phases (setup, barriers, the blend), not by the matrix cores or the staging — with one workgroup per CU
+//     and a deep ring it took 2.2 ms where two take 1.27 and three 1.04 (profiles/r13/corr_lookup.md);
+//   * region rows outside the image, rows past the level's region and steps past the K loop are out-of-range buffer offsets: the DMA
+//     writes zeros, no traffic, no branch, no lane mask held across a load.
+constexpr int RK = 16, RROW = 2 * RK;      // channels per K step; halfs per staged row
+constexpr int RP = 512 / RROW, LPR = 64 / RP;   // rows per DMA piece (1 KB per wave instruction); lanes per row
+constexpr int RST = 2;                     // ring stages
+// region edge and staged region rows (whole DMA pieces for each of the 4 waves: a multiple of 64) per pyramid level
+constexpr int RG0_W = 16, RG0_N = 256, RG1_W = 11, RG1_N = 128, RG2_W = 11, RG2_N = 128;
+constexpr int corr_ring_nb(int rw) { return (rw * rw + 31) / 32; }      // 32-column blocks of S that hold region positions
+constexpr size_t corr_ring_bytes(int rw, int nrp) {
+    const size_t ring = (size_t)RST * (CM + nrp) * RROW * 2, s = (size_t)(CM / 2) * (corr_ring_nb(rw) * 32 + 4) * 4;
+    return ring > s ? ring : s;
+}
+constexpr size_t CORR_RING_LDS = corr_ring_bytes(RG0_W, RG0_N);
+static_assert(corr_ring_bytes(RG1_W, RG1_N) <= CORR_RING_LDS && corr_ring_bytes(RG2_W, RG2_N) <= CORR_RING_LDS, "level 0 sizes the LDS");
+static_assert(corr_ring_nb(RG0_W) * 32 <= RG0_N && corr_ring_nb(RG1_W) * 32 <= RG1_N && corr_ring_nb(RG2_W) * 32 <= RG2_N, "S columns are staged rows");
+static_assert(RG0_N % (4 * RP) == 0 && RG1_N % (4 * RP) == 0 && RG2_N % (4 * RP) == 0 && CM % (4 * RP) == 0, "whole DMA pieces per wave");
+
+#if defined(__HIP_DEVICE_COMPILE__)   // (the host pass only needs the launch stub: it cannot instantiate the LDS-DMA builtin)
+typedef __attribute__((address_space(3))) void* corr_lds_ptr_t;
+
+// one pyramid level of one tile.  f1b: image b of the render operand; f2b: image b % f2_batch of the level's query operand (Hl x Wl);
+// s_org = {region origin x, y, pixels still to do}
+template <int RW, int NRP>
+__device__ __forceinline__ void corr_ring_level(float* sm, float* s_cx, float* s_cy, int* s_bx, int* s_by, int* s_state, int* s_org, int l,
+                                                const _Float16* f1b, int ld_f1, int f1_bytes, const _Float16* f2b, int Hl, int Wl, int C,
+                                                float gx, float gy, int r, float inv_sqrt_c, size_t row0, int y0, int x0, int W,
+                                                float* __restrict__ out, _Float16* __restrict__ out_hl, int ld_out) {
+    constexpr int NB = corr_ring_nb(RW), NT = (2 * NB + 3) / 4;   // column blocks of S; 32 x 32 tiles of S per wave (tile t = wave + 4 i)
+    constexpr int PA = CM / RP / 4, PB = NRP / RP / 4, NP = PA + PB;   // DMA pieces per wave and step: tile rows, region rows
+    constexpr int STG = (CM + NRP) * RROW;                        // halfs per stage: [64 tile rows | NRP region rows]
+    constexpr int SP = NB * 32 + 4;                               // row pitch of S
+    _Float16* ring = (_Float16*)sm;
+    float* S = sm;                                                // [32][SP]: aliases the ring once the K loop is over
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, lh = lane >> 5;
+    const int tw = 2 * r + 2, win = 2 * r + 1, fit = RW - tw;
+    if (tid == 0) s_org[2] = 0;
+    __syncthreads();
+    if (tid < CM) {
+        const float sc = (float)(1 << l);
+        // centre sample (offset 0): its integer corner anchors the neighbourhood (clamped far outside: no overflow)
+        const float cx = fminf(fmaxf(roundtrip(gx / sc, Wl), -1.0e6f), 1.0e6f);
+        const float cy = fminf(fmaxf(roundtrip(gy / sc, Hl), -1.0e6f), 1.0e6f);
+        const int bx = (int)floorf(cx) - r, by = (int)floorf(cy) - r;
+        s_cx[tid] = cx; s_cy[tid] = cy; s_bx[tid] = bx; s_by[tid] = by;
+        const bool outside = bx >= Wl || by >= Hl || bx + tw <= 0 || by + tw <= 0;
+        s_state[tid] = outside ? 2 : 0;                // 0 = to do, 1 = done, 2 = all zeros
+        if (!outside) atomicAdd(&s_org[2], 1);
+    }
+    __syncthreads();
+    for (int idx = tid; idx < CM * win * win; idx += 256) {   // neighbourhoods outside the image: zeros
+        const int m = idx / (win * win), o = idx - m * (win * win);
+        if (s_state[m] == 2) corr_put(out, out_hl, row0 + (size_t)(y0 + (m >> 3)) * W + x0 + (m & 7), ld_out, l * win * win + o, 0.f);
+    }
+    // DMA slot of this lane: a piece fills 16 rows, lane -> row lane >> 2, chunk position lane & 3, which holds source chunk sc (the key
+    // reads bits 2, 3 of the row = of lane >> 2: the same for every piece)
+    const int lr = lane / LPR, sc = (lane % LPR) ^ ((lr >> 2) & 3);
+    const __amdgpu_buffer_rsrc_t Ar = __builtin_amdgcn_make_buffer_rsrc((void*)f1b, 0, f1_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t Br = __builtin_amdgcn_make_buffer_rsrc((void*)f2b, 0, Hl * Wl * C * 4, 0x00020000);
+    unsigned abyte[PA];                                       // tile pixels of this lane's pieces of the render operand
+#pragma unroll
+    for (int j = 0; j < PA; ++j) {
+        const int ma = (j * 4 + wv) * RP + lr;
+        abyte[j] = (unsigned)(((y0 + (ma >> 3)) * W + x0 + (ma & 7)) * ld_f1) * 4u + (unsigned)sc * 16u;
+    }
+    const int ns = C / RK;
+    // fragment reads: lane (l31, lh) feeds row / column l31 with channels 8 lh .. + 7 of the step: chunk 2 lh (hi terms), 2 lh + 1 (lo)
+    const int ph = ((2 * lh) ^ ((l31 >> 2) & 3)) * 8, pl = ph ^ 8;
+    while (s_org[2] > 0) {                                  // (uniform: read after a barrier, written before the next)
+        // ---- region of this pass: origin = smallest bx still to do, then the smallest by among its column band
+        if (tid == 0) { s_org[0] = 0x7fffffff; s_org[1] = 0x7fffffff; }
+        __syncthreads();
+        if (tid < CM && s_state[tid] == 0) atomicMin(&s_org[0], s_bx[tid]);
+        __syncthreads();
+        if (tid < CM && s_state[tid] == 0 && s_bx[tid] - s_org[0] <= fit) atomicMin(&s_org[1], s_by[tid]);
+        __syncthreads();
+        const int ox = s_org[0], oy = s_org[1];
+        unsigned bbyte[PB];                                 // region rows of this lane's pieces: byte offset of channel 0 (+ its chunk)
+#pragma unroll
+        for (int j = 0; j < PB; ++j) {
+            const int n = (j * 4 + wv) * RP + lr, ry = n / RW, qy = oy + ry, qx = ox + n - ry * RW;
+            const bool in = n < RW * RW && qx >= 0 && qx < Wl && qy >= 0 && qy < Hl;
+            bbyte[j] = in ? (unsigned)((qy * Wl + qx) * C) * 4u + (unsigned)sc * 16u : 0xFFFFFFFFu;
+        }
+        // the pieces of K step STEP into stage STAGE (a macro, not a lambda: pp_gemm_u_kernel.h).  A step past the K loop is all
+        // out-of-range offsets, so every wave issues NP pieces per step and the counted wait below holds to the end.
+#define CORR_RING_ISSUE(STEP, STAGE)                                                                                                \
+        {                                                                                                                               \
+            const unsigned dead_ = (STEP) < ns ? 0u : 0xFFFFFFFFu;                                                                      \
+            const int so_ = (STEP) * (RK * 4);                                                                                          \
+            _Float16* st_ = ring + (STAGE) * STG;                                                                                       \
+            _Pragma("unroll") for (int j = 0; j < PA; ++j)                                                                              \
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(Ar, (corr_lds_ptr_t)(st_ + (j * 4 + wv) * RP * RROW), 16, abyte[j] | dead_,    \
+                                                         so_, 0, 0);                                                                    \
+            _Pragma("unroll") for (int j = 0; j < PB; ++j)                                                                              \
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(Br, (corr_lds_ptr_t)(st_ + (CM + (j * 4 + wv) * RP) * RROW), 16,               \
+                                                         bbyte[j] | dead_, so_, 0, 0);                                                  \
+        }
+        // ---- S = F1_tile . F2_region^T
+        f32x16_t acc[NT];
+#pragma unroll
+        for (int i = 0; i < NT; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // this wave's result stores have left: the counted waits count DMA pieces alone
+#pragma unroll
+        for (int s = 0; s < RST - 1; ++s) CORR_RING_ISSUE(s, s)
+        int cur = 0;
+        for (int s = 0; s < ns; ++s) {
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"((RST - 2) * NP) : "memory");   // this wave's pieces of step s have landed
+            __builtin_amdgcn_s_barrier();                   // ... and everybody's; every wave is done reading the stage of step s - 1
+            const int nxt = cur == 0 ? RST - 1 : cur - 1;
+            CORR_RING_ISSUE(s + RST - 1, nxt)
+            const _Float16* sa = ring + cur * STG;
+            const _Float16* sb = sa + CM * RROW;
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+                const int t = wv + 4 * i;
+                if ((2 * NB) % 4 == 0 || t < 2 * NB) {      // (wave-uniform)
+                    const int m = t / NB, n = t - m * NB;
+                    const _Float16* ar = sa + (m * 32 + l31) * RROW;
+                    const _Float16* br = sb + (n * 32 + l31) * RROW;
+                    const h8_t ah = *(const h8_t*)(ar + ph), al = *(const h8_t*)(ar + pl);
+                    const h8_t bh = *(const h8_t*)(br + ph), bl = *(const h8_t*)(br + pl);
+                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[i], 0, 0, 0);
+                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[i], 0, 0, 0);
+                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[i], 0, 0, 0);
+                }
+            }
+            cur = cur == RST - 1 ? 0 : cur + 1;
+        }
+#undef CORR_RING_ISSUE
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the zero pieces past the loop have landed too: S overwrites the ring
+        __syncthreads();                                    // every wave is done reading the ring
+        // S holds one half of the tile's pixels (a 32-row block of the accumulators) at a time
+        for (int half = 0; half < 2; ++half) {
+            if (half) __syncthreads();                      // the first half's samples have been read
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+                const int t = wv + 4 * i;
+                if (((2 * NB) % 4 == 0 || t < 2 * NB) && t / NB == half) {
+                    const int n = t - half * NB;
+#pragma unroll
+                    for (int e = 0; e < 16; ++e)            // accumulator (e, lane): row (e/4)*8 + lh*4 + e%4 of the half, column l31
+                        S[((e >> 2) * 8 + lh * 4 + (e & 3)) * SP + n * 32 + l31] =
+                            acc[i][e] * (inv_sqrt_c / (PP_A_SCALE * PP_A_SCALE));
+                }
+            }
+            __syncthreads();
+            // ---- blend the 25 samples of every pixel whose neighbourhood lies in the region
+            for (int idx = tid; idx < CM / 2 * win * win; idx += 256) {
+                const int ms = idx / (win * win), o = idx - ms * (win * win), ai = o / win, bi = o - ai * win, m = ms + 32 * half;
+                const int dx = s_bx[m] - ox, dy = s_by[m] - oy;
+                if (s_state[m] == 0 && dx >= 0 && dx <= fit && dy >= 0 && dy <= fit) {
+                    const float cx = s_cx[m], cy = s_cy[m];
+                    const float wx1 = cx - floorf(cx), wy1 = cy - floorf(cy), wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+                    const float* t = S + ms * SP + (dy + bi) * RW + dx + ai;   // x offset a-r -> +ai, y offset b-r -> +bi
+                    corr_put(out, out_hl, row0 + (size_t)(y0 + (m >> 3)) * W + x0 + (m & 7), ld_out, l * win * win + o,
+                             t[0] * (wx0 * wy0) + t[1] * (wx1 * wy0) + t[RW] * (wx0 * wy1) + t[RW + 1] * (wx1 * wy1));
+                }
+            }
+        }
+        __syncthreads();
+        if (tid < CM && s_state[tid] == 0) {
+            const int dx = s_bx[tid] - ox, dy = s_by[tid] - oy;
+            if (dx >= 0 && dx <= fit && dy >= 0 && dy <= fit) {
+                s_state[tid] = 1;
+                atomicSub(&s_org[2], 1);
+            }
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+}
+#endif
+
+__global__ __launch_bounds__(256, 3) void corr_lookup_ring_kernel(const _Float16* __restrict__ f1h, int ld_f1, int f2_batch,
+                                                                  const _Float16* __restrict__ f2l0, const _Float16* __restrict__ f2l1,
+                                                                  const _Float16* __restrict__ f2l2, const float* __restrict__ flow, int B,
+                                                                  int H, int W, int C, int L, int r, int ld_flow, float inv_sqrt_c,
+                                                                  float* __restrict__ out, int ld_out, _Float16* __restrict__ out_hl) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    __shared__ float s_cx[CM], s_cy[CM];
+    __shared__ int s_bx[CM], s_by[CM], s_state[CM], s_org[3];
+    const int tid = threadIdx.x;
+    const int tiles_x = W / CT, tiles = tiles_x * (H / CT), total = tiles * B;
+    // workgroups are dealt round-robin to the 8 XCDs: make consecutive tiles (same image, overlapping regions) share an L2
+    int g = blockIdx.x;
+    if (total % 8 == 0) g = (g % 8) * (total / 8) + g / 8;
+    const int b = g / tiles, tile = g - b * tiles;
+    const int y0 = (tile / tiles_x) * CT, x0 = (tile % tiles_x) * CT;
+    const int win = 2 * r + 1;
+    const int my = tid >> 3, mx = tid & 7;                  // tid < 64: the pixel this thread describes
+    const size_t row0 = (size_t)b * H * W;
+    float gx = 0.f, gy = 0.f;
+    if (tid < CM) {
+        const float* fl = flow + (row0 + (size_t)(y0 + my) * W + x0 + mx) * ld_flow;
+        gx = (float)(x0 + mx) + fl[0];
+        gy = (float)(y0 + my) + fl[1];
+    }
+    // the pad channels [L win^2, ld_out) of the tile's 64 rows: zeros (the caller allocates without a fill)
+    for (int npad = ld_out - L * win * win, idx = tid; idx < CM * npad; idx += 256) {
+        const int m = idx / npad, o = idx - m * npad;
+        corr_put(out, out_hl, row0 + (size_t)(y0 + (m >> 3)) * W + x0 + (m & 7), ld_out, L * win * win + o, 0.f);
+    }
+    const _Float16* f1b = f1h + row0 * ld_f1 * 2;
+    const int f1_bytes = ((H * W - 1) * ld_f1 + C) * 4;
+    const size_t q = (size_t)(b % f2_batch);
+    corr_ring_level<RG0_W, RG0_N>(sm, s_cx, s_cy, s_bx, s_by, s_state, s_org, 0, f1b, ld_f1, f1_bytes, f2l0 + q * H * W * C * 2, H, W, C, gx, gy,
+                                  r, inv_sqrt_c, row0, y0, x0, W, out, out_hl, ld_out);
+    if (L > 1)
+        corr_ring_level<RG1_W, RG1_N>(sm, s_cx, s_cy, s_bx, s_by, s_state, s_org, 1, f1b, ld_f1, f1_bytes, f2l1 + q * (H >> 1) * (W >> 1) * C * 2,
+                                      H >> 1, W >> 1, C, gx, gy, r, inv_sqrt_c, row0, y0, x0, W, out, out_hl, ld_out);
+    if (L > 2)
+        corr_ring_level<RG2_W, RG2_N>(sm, s_cx, s_cy, s_bx, s_by, s_state, s_org, 2, f1b, ld_f1, f1_bytes, f2l2 + q * (H >> 2) * (W >> 2) * C * 2,
+                                      H >> 2, W >> 2, C, gx, gy, r, inv_sqrt_c, row0, y0, x0, W, out, out_hl, ld_out);
+#endif
 }
 
 // Row gather: dst[i] = src[index[i]] for rows of `row` floats (row % 4 == 0, 16-byte aligned): the selection of the
@@ -856,9 +1137,18 @@ int pp_avgpool2_nhwc(const float* in, int B, int H, int W, int C, float* out, vo
     return pp_last_launch();
 }
 
+int pp_avgpool2_hl(const float* in, int B, int H, int W, int C, float* out, void* out_hl, void* stream) {
+    if (!in || !out_hl || B <= 0 || H < 2 || W < 2 || C <= 0 || H % 2 != 0 || W % 2 != 0 || C % 8 != 0) return PP_EINVAL;
+    if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)out_hl) % 16 != 0) return PP_EINVAL;
+    const size_t n = (size_t)(H / 2) * (W / 2) * (C / 4);
+    const int gx = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
+    hipLaunchKernelGGL(avgpool2_hl_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, in, H, W, C, out, (_Float16*)out_hl);
+    return pp_last_launch();
+}
+
 static int corr_tiled_launch(bool hl, const void* f1, int ld_f1, const void* f2_l0, const void* f2_l1, const void* f2_l2, int f2_batch,
                              const float* flow, int B, int H, int W, int C, int levels, int radius, int ld_flow, float* out, int ld_out,
-                             void* stream, bool exact = false, bool one = false) {
+                             void* stream, bool exact = false, bool one = false, void* out_hl = nullptr) {
     // matrix-core version: one workgroup per 8 x 8 pixel tile
     const size_t lds = (size_t)(CM * CSP > (CM + CN) * CKP ? CM * CSP : (CM + CN) * CKP) * sizeof(float);
     static signed char attr[PP_MAX_DEVICES];
@@ -867,22 +1157,32 @@ static int corr_tiled_launch(bool hl, const void* f1, int ld_f1, const void* f2_
         ok = hipFuncSetAttribute((const void*)corr_lookup_mfma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
                      hipFuncSetAttribute((const void*)corr_lookup_mfma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
                      hipFuncSetAttribute((const void*)corr_lookup_mfma_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-                     hipFuncSetAttribute((const void*)corr_lookup_mfma_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess
+                     hipFuncSetAttribute((const void*)corr_lookup_mfma_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
+                     hipFuncSetAttribute((const void*)corr_lookup_ring_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CORR_RING_LDS) == hipSuccess
                  ? 1 : -1;
     if (ok < 0) return PP_ELAUNCH;
     const dim3 grid((unsigned)((H / CT) * (W / CT) * B));
-    if (exact)
+    _Float16* oh = (_Float16*)out_hl;
+    // operand input: the ring-staged kernel (PP_CORR_RING=0, read per call, keeps the register-staged one: the tests run both in one process).
+    // Its DMA offsets are 32-bit and signed on the way: an image of either operand beyond 2 GiB stays with the register-staged kernel.
+    const char* re = getenv("PP_CORR_RING");
+    const bool ring = hl && !(re && re[0] == '0') && (long long)H * W * ld_f1 * 4 < 0x7FFFFFFFLL && (long long)H * W * C * 4 < 0x7FFFFFFFLL;
+    if (ring)
+        hipLaunchKernelGGL(corr_lookup_ring_kernel, grid, dim3(256), CORR_RING_LDS, (hipStream_t)stream, (const _Float16*)f1, ld_f1, f2_batch,
+                           (const _Float16*)f2_l0, (const _Float16*)f2_l1, (const _Float16*)f2_l2, flow, B, H, W, C, levels, radius, ld_flow,
+                           1.0f / sqrtf((float)C), out, ld_out, oh);
+    else if (exact)
         hipLaunchKernelGGL((corr_lookup_mfma_kernel<false, true>), grid, dim3(256), lds, (hipStream_t)stream, f1, ld_f1, f2_batch, f2_l0, f2_l1, f2_l2,
-                           flow, B, H, W, C, levels, radius, ld_flow, 1.0f / sqrtf((float)C), out, ld_out);
+                           flow, B, H, W, C, levels, radius, ld_flow, 1.0f / sqrtf((float)C), out, ld_out, oh);
     else if (one)
         hipLaunchKernelGGL((corr_lookup_mfma_kernel<false, false, true>), grid, dim3(256), lds, (hipStream_t)stream, f1, ld_f1, f2_batch, f2_l0, f2_l1,
-                           f2_l2, flow, B, H, W, C, levels, radius, ld_flow, 1.0f / sqrtf((float)C), out, ld_out);
+                           f2_l2, flow, B, H, W, C, levels, radius, ld_flow, 1.0f / sqrtf((float)C), out, ld_out, oh);
     else if (hl)
         hipLaunchKernelGGL(corr_lookup_mfma_kernel<true>, grid, dim3(256), lds, (hipStream_t)stream, f1, ld_f1, f2_batch, f2_l0, f2_l1, f2_l2,
-                           flow, B, H, W, C, levels, radius, ld_flow, 1.0f / sqrtf((float)C), out, ld_out);
+                           flow, B, H, W, C, levels, radius, ld_flow, 1.0f / sqrtf((float)C), out, ld_out, oh);
     else
         hipLaunchKernelGGL(corr_lookup_mfma_kernel<false>, grid, dim3(256), lds, (hipStream_t)stream, f1, ld_f1, f2_batch, f2_l0, f2_l1, f2_l2,
-                           flow, B, H, W, C, levels, radius, ld_flow, 1.0f / sqrtf((float)C), out, ld_out);
+                           flow, B, H, W, C, levels, radius, ld_flow, 1.0f / sqrtf((float)C), out, ld_out, oh);
     return pp_last_launch();
 }
 
@@ -932,19 +1232,28 @@ int pp_corr_lookup_nhwc_ex(const float* f1, int ld_f1, const float* f2_l0, const
     return pp_last_launch();
 }
 
-int pp_corr_lookup_nhwc_hl(const void* f1_hl, int ld_f1, const void* f2_hl_l0, const void* f2_hl_l1, const void* f2_hl_l2,
-                           int f2_batch, const float* flow, int B, int H, int W, int C, int levels, int radius, int ld_flow,
-                           float* out, int ld_out, void* stream) {
-    if (!f1_hl || !f2_hl_l0 || !flow || !out || B <= 0 || H <= 0 || W <= 0 || C <= 0 || f2_batch <= 0) return PP_EINVAL;
+int pp_corr_lookup_nhwc_hl_op(const void* f1_hl, int ld_f1, const void* f2_hl_l0, const void* f2_hl_l1, const void* f2_hl_l2,
+                              int f2_batch, const float* flow, int B, int H, int W, int C, int levels, int radius, int ld_flow,
+                              float* out, int ld_out, void* out_hl, int ld_out_h, void* stream) {
+    if (!f1_hl || !f2_hl_l0 || !flow || (out != nullptr) == (out_hl != nullptr) || B <= 0 || H <= 0 || W <= 0 || C <= 0 || f2_batch <= 0)
+        return PP_EINVAL;
     if (H % CT != 0 || W % CT != 0 || C % CK != 0 || ld_f1 < C || ld_f1 % 8 != 0) return PP_EINVAL;   // tiled shapes only
     if (((uintptr_t)f1_hl | (uintptr_t)f2_hl_l0 | (uintptr_t)f2_hl_l1 | (uintptr_t)f2_hl_l2) % 16 != 0) return PP_EINVAL;
     if (levels < 1 || levels > MAXL || radius < 1 || radius > MAXR) return PP_EINVAL;
     if ((levels > 1 && !f2_hl_l1) || (levels > 2 && !f2_hl_l2)) return PP_EINVAL;
     if ((H >> (levels - 1)) < 1 || (W >> (levels - 1)) < 1 || ld_flow < 2) return PP_EINVAL;
-    const int win = 2 * radius + 1;
-    if (ld_out < levels * win * win) return PP_EINVAL;
-    return corr_tiled_launch(true, f1_hl, ld_f1, f2_hl_l0, f2_hl_l1, f2_hl_l2, f2_batch, flow, B, H, W, C, levels, radius, ld_flow, out, ld_out,
-                             stream);
+    const int win = 2 * radius + 1, ld = out_hl ? ld_out_h : ld_out;
+    if (ld < levels * win * win) return PP_EINVAL;
+    if (out_hl && (ld_out_h % 8 != 0 || ((uintptr_t)out_hl % 16) != 0)) return PP_EINVAL;   // whole groups of 8 channels
+    return corr_tiled_launch(true, f1_hl, ld_f1, f2_hl_l0, f2_hl_l1, f2_hl_l2, f2_batch, flow, B, H, W, C, levels, radius, ld_flow, out, ld,
+                             stream, false, false, out_hl);
+}
+
+int pp_corr_lookup_nhwc_hl(const void* f1_hl, int ld_f1, const void* f2_hl_l0, const void* f2_hl_l1, const void* f2_hl_l2,
+                           int f2_batch, const float* flow, int B, int H, int W, int C, int levels, int radius, int ld_flow,
+                           float* out, int ld_out, void* stream) {
+    return pp_corr_lookup_nhwc_hl_op(f1_hl, ld_f1, f2_hl_l0, f2_hl_l1, f2_hl_l2, f2_batch, flow, B, H, W, C, levels, radius, ld_flow, out, ld_out,
+                                     nullptr, 0, stream);
 }
 
 int pp_corr_lookup_nhwc(const float* f1, int ld_f1, const float* f2_l0, const float* f2_l1, const float* f2_l2,

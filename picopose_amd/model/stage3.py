@@ -288,7 +288,9 @@ class FlowDecoder(Packed):
             elif not train:
                 fr = ops.conv2d(fr_src, pk[f"proj{l}"], pk[f"proj{l}_b"], 1, out=X[..., 0:256])   # straight into its slice of X
             ncorr = (l + 1) * (2 * self.r + 1) ** 2
-            corr = ops.corr_lookup(fr, fq, flow, l + 1, self.r, c_pad=-(-ncorr // 8) * 8, **hl_maps)
+            # (the lookup's only reader is corr_net[0], a 1x1 convolution: on the operand branch the lookup writes that operand itself)
+            corr_op = lean and bool(hl_maps) and ops.corr_takes_operands(hl_maps["f1_hl"], hl_maps["f2_hl"], H, W, 256)
+            corr = ops.corr_lookup(fr, fq, flow, l + 1, self.r, c_pad=-(-ncorr // 8) * 8, out_split=corr_op, **hl_maps)
             # [corr feat 192 | flow feat 64]: on the f16x3 engine the concat exists only as the operand of out_net
             hl_cat = opcat
             if hl_cat:

@@ -1262,6 +1262,26 @@ def avgpool2(x):
     return out
 
 
+def avgpool2_hl(x, keep_f32=True):
+    """avgpool2 with the pooled map's operand written by the same kernel (pp_avgpool2_hl): (fp32 pool or None, Split with .image) — the bits
+    of avgpool2 followed by split_activation.  keep_f32=False: the last pyramid level, whose fp32 form nothing reads."""
+    B, H, W, C = x.shape
+    assert x.is_contiguous() and C % 8 == 0 and terms() == 2
+    out = torch.empty(B, H // 2, W // 2, C, dtype=torch.float32, device=x.device) if keep_f32 else None
+    sp = Split.empty(B * (H // 2) * (W // 2), C, x.device)
+    sp.image = (B, H // 2, W // 2)
+    _lib.check(_lib.lib().pp_avgpool2_hl(_p(x), B, H, W, C, _p(out) if keep_f32 else None, _p(sp.hl), _lib.stream_ptr()), "pp_avgpool2_hl")
+    _chk(sp.hl, "pp_avgpool2_hl")
+    return out, sp
+
+
+def corr_operand_out():
+    """PP_CORR_OPERAND_OUT (default on; read per call): on its operand branch the correlation lookup pools the query map and writes the pooled
+    operand in one launch per level (avgpool2_hl) and, asked with out_split, writes its result as the operand of corr_net[0] instead of an
+    fp32 map; "0": avgpool2 -> split_activation and fp32 map -> split_activation — the same bits."""
+    return os.environ.get("PP_CORR_OPERAND_OUT", "1") != "0"
+
+
 def decoder_lean():
     """PP_DECODER_LEAN (default on; read per call): the flow decoder and the DPT head store no fp32 map that nothing reads and build the
     flow's operands in one launch (model/stage3.py); "0" restores the fp32 maps and the torch glue — the same bits either way."""
@@ -1275,13 +1295,15 @@ def corr_takes_operands(f1_hl, f2_hl, H, W, C):
             and os.environ.get("PP_CORR_TILED", "1") != "0" and os.environ.get("PP_CORR_HL", "1") != "0")
 
 
-def corr_lookup(f1, f2, flow, levels, radius, c_pad=None, f1_hl=None, f2_hl=None):
+def corr_lookup(f1, f2, flow, levels, radius, c_pad=None, f1_hl=None, f2_hl=None, out_split=False):
     """Correlation pyramid + lookup, NHWC: (B,H,W,C) x2, flow (B,H,W,>=2) -> (B,H,W,levels*(2r+1)^2)
     (c_pad: channel count of the result, zero-filled beyond the levels*(2r+1)^2 real channels).
     f1 may be a channel slice of a wider buffer; f2 may hold B / k images (image b reads f2[b % (B / k)]).
     f1_hl = (Split over (B*H*W, Ctot), col0), f2_hl = Split over (Bf*H*W, C): the same maps as operands the producers have
     already written (f16x3 engine, tileable shapes): the kernel then stages 16-byte copies instead of splitting every chunk.
-    f1 = None: the map exists only as f1_hl (allowed exactly where `corr_takes_operands` holds)."""
+    f1 = None: the map exists only as f1_hl (allowed exactly where `corr_takes_operands` holds).
+    out_split (where `corr_takes_operands` holds, c_pad % 8 == 0): the result as a Split with .image — the operand of the 1x1 convolution
+    that reads it, written by the lookup itself (corr_operand_out) — instead of the fp32 map."""
     (H, W, C), B = f2.shape[1:], flow.shape[0]
     assert f2.is_contiguous() and flow.stride(3) == 1 and B % f2.shape[0] == 0 and tuple(flow.shape[1:3]) == (H, W)
     operands = corr_takes_operands(f1_hl, f2_hl, H, W, C)
@@ -1289,20 +1311,40 @@ def corr_lookup(f1, f2, flow, levels, radius, c_pad=None, f1_hl=None, f2_hl=None
         assert operands, "corr_lookup without the fp32 map f1 needs the operand form of both maps (corr_takes_operands)"
     else:
         assert tuple(f1.shape) == (B, H, W, C) and f1.stride(3) == 1 and f1.stride(1) == W * f1.stride(2) and f1.stride(0) == H * f1.stride(1)
-    pyr = [f2]
-    for _ in range(levels - 1):
-        pyr.append(avgpool2(pyr[-1]))
     n = levels * (2 * radius + 1) ** 2
     np_ = c_pad if c_pad and c_pad > n else n
-    # (the kernels write the pad channels of their rows themselves; PP_DECODER_LEAN=0: the separate fill of the whole map, as before)
-    out = (torch.zeros if np_ > n and not decoder_lean() else torch.empty)(B, H, W, np_, dtype=torch.float32, device=f2.device)
+    assert not out_split or (operands and np_ % 8 == 0), "corr_lookup(out_split=True) needs the operand branch and a padded channel count"
+    fused = operands and corr_operand_out()
+    pyr, hls = [f2], [f2_hl.hl if operands else None]
+    for i in range(levels - 1):
+        if fused:      # pool and operand in one launch; the last level's fp32 pool has no reader
+            p, sp = avgpool2_hl(pyr[-1], keep_f32=i < levels - 2)
+            pyr.append(p)
+            hls.append(sp.hl)
+        else:
+            pyr.append(avgpool2(pyr[-1]))
+            if operands:
+                p = pyr[-1]
+                hls.append(split_activation(p, p.shape[0], p.shape[1] * p.shape[2], C, p.shape[1] * p.shape[2] * C, C))
     if operands:
         tgt, col0 = f1_hl
         assert tgt.shape[0] == B * H * W and col0 % 8 == 0 and col0 + C <= tgt.shape[1] and f2_hl.shape == (f2.shape[0] * H * W, C)
-        hls = [f2_hl.hl] + [split_activation(p, p.shape[0], p.shape[1] * p.shape[2], C, p.shape[1] * p.shape[2] * C, C) for p in pyr[1:]]
-        _lib.check(_lib.lib().pp_corr_lookup_nhwc_hl(tgt.hl.data_ptr() + 4 * col0, tgt.shape[1], _p(hls[0]), _p(hls[1]) if levels > 1 else None,
-                                                     _p(hls[2]) if levels > 2 else None, f2.shape[0], _p(flow), B, H, W, C, levels, radius,
-                                                     flow.stride(2), _p(out), np_, _lib.stream_ptr()), "pp_corr_lookup_nhwc_hl")
+        args = (tgt.hl.data_ptr() + 4 * col0, tgt.shape[1], _p(hls[0]), _p(hls[1]) if levels > 1 else None, _p(hls[2]) if levels > 2 else None,
+                f2.shape[0], _p(flow), B, H, W, C, levels, radius, flow.stride(2))
+        if out_split and fused:
+            sp = Split.empty(B * H * W, np_, f2.device)
+            sp.image = (B, H, W)
+            _lib.check(_lib.lib().pp_corr_lookup_nhwc_hl_op(*args, None, np_, _p(sp.hl), np_, _lib.stream_ptr()), "pp_corr_lookup_nhwc_hl_op")
+            _chk(sp.hl, "pp_corr_lookup_nhwc_hl_op")
+            return sp
+    # (the kernels write the pad channels of their rows themselves; PP_DECODER_LEAN=0: the separate fill of the whole map, as before)
+    out = (torch.zeros if np_ > n and not decoder_lean() else torch.empty)(B, H, W, np_, dtype=torch.float32, device=f2.device)
+    if operands:
+        _lib.check(_lib.lib().pp_corr_lookup_nhwc_hl(*args, _p(out), np_, _lib.stream_ptr()), "pp_corr_lookup_nhwc_hl")
+        if out_split:
+            sp = Split(split_activation(out, B, H * W, np_, H * W * np_, np_))
+            sp.image = (B, H, W)
+            return sp
         return out
     _lib.check(_lib.lib().pp_corr_lookup_nhwc_ex(_p(f1), f1.stride(2), _p(pyr[0]), _p(pyr[1]) if levels > 1 else None,
                                                  _p(pyr[2]) if levels > 2 else None, f2.shape[0], _p(flow), B, H, W, C,
