@@ -24,13 +24,15 @@ int pp_sat_set_gemm_u2(unsigned*);
 int pp_sat_set_gemm_uh(unsigned*);
 int pp_sat_set_attn(unsigned*);
 int pp_sat_set_sample(unsigned*);
+int pp_sat_set_corr(unsigned*);
 static unsigned* g_sat_word[PP_MAX_DEVICES];
 unsigned* pp_saturation_word() { return g_sat_word[pp_cur_device()]; }
 extern "C" {
 
 int pp_set_saturation_word(unsigned int* word) {
     // every translation unit with a producer kernel holds its own device-side copy of the pointer (pp_common.h)
-    int (*const setters[])(unsigned*) = {pp_sat_set_gemm, pp_sat_set_gemm_u1, pp_sat_set_gemm_u2, pp_sat_set_gemm_uh, pp_sat_set_attn, pp_sat_set_sample};
+    int (*const setters[])(unsigned*) = {pp_sat_set_gemm, pp_sat_set_gemm_u1, pp_sat_set_gemm_u2, pp_sat_set_gemm_uh,
+                                         pp_sat_set_attn, pp_sat_set_sample, pp_sat_set_corr};
     for (auto f : setters) {
         const int rc = f(word);
         if (rc != PP_OK) return rc;

@@ -1,13 +1,14 @@
 // Adjoint kernels of stage 3's training path (picopose_amd/autograd.py: offset_regressor_forward): BatchNorm in training mode,
 // bilinear resize (align_corners=True), the feature warp, the fused correlation pyramid + lookup, 2x2 average pooling and the
 // flow / certainty losses.  Convolutions go through pp_im2col_nhwc / pp_col2im_nhwc + pp_gemm (pp_backward.hip).  Every kernel
-// restates the FORWARD kernel's own coordinate arithmetic (pp_sample.hip, pp_train.hip) so that value and gradient describe the
-// same function; reductions over rows run in double in a fixed order, scatters (warp / lookup into the sampled maps) are fp32
-// atomic adds.
+// restates the FORWARD kernel's own coordinate arithmetic (pp_sample.hip, pp_corr.hip, pp_train.hip; the round trip is the forward
+// kernels' pp_roundtrip itself) so that value and gradient describe the same function; reductions over rows run in double in a
+// fixed order, scatters (warp / lookup into the sampled maps) are fp32 atomic adds.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/picopose_hip.h"
 #include "pp_common.h"
+#include "pp_corr_dev.h"
 
 namespace {
 
@@ -242,12 +243,6 @@ __global__ __launch_bounds__(256) void avgpool2_backward_kernel(const float* __r
     }
 }
 
-// coordinate round trip of the forward kernels (pp_sample.hip: roundtrip)
-__device__ __forceinline__ float roundtrip(float x, int size) {
-    const float n = x * 2.f / (float)(size - 1 > 1 ? size - 1 : 1) - 1.f;
-    return ((n + 1.f) / 2.f) * (float)(size - 1);
-}
-
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -281,7 +276,7 @@ __global__ __launch_bounds__(256) void warp_backward_kernel(const float* __restr
     if (p >= H * W) return;
     const int y = p / W, x = p - y * W;
     const float* fl = flow + ((size_t)b * H * W + p) * ld_flow;
-    const float rx = roundtrip((float)x + fl[0], W), ry = roundtrip((float)y + fl[1], H);
+    const float rx = pp_roundtrip((float)x + fl[0], W), ry = pp_roundtrip((float)y + fl[1], H);
     const float ix = fminf(fmaxf(rx, -2.f), (float)W + 1.f), iy = fminf(fmaxf(ry, -2.f), (float)H + 1.f);
     const float x0f = floorf(ix), y0f = floorf(iy);
     const int x0 = (int)x0f, y0 = (int)y0f;
@@ -314,7 +309,7 @@ __global__ __launch_bounds__(256) void warp_backward_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------------------- correlation lookup
-// adjoint of corr_lookup_kernel (pp_sample.hip): corr_l[p, q] = <f1[p], pool_l(f2)[q]> / sqrt(C), output channel
+// adjoint of corr_lookup_kernel (pp_corr.hip): corr_l[p, q] = <f1[p], pool_l(f2)[q]> / sqrt(C), output channel
 // l win^2 + a win + b = bilinear sample of corr_l[p, .] at ((p + flow[p]) / 2^l) + (a - r, b - r), zeros padding.
 // One wave per pixel: the (2r+2)^2 table positions per level are visited one after the other, lanes over channels.
 constexpr int CLB_MAXL = 3, CLB_TW = 8;   // levels, table width for r <= 3
@@ -344,7 +339,7 @@ __global__ __launch_bounds__(256) void corr_lookup_backward_kernel(const float* 
     for (int l = 0; l < L; ++l) {
         const int Hl = H >> l, Wl = W >> l;
         const float sc = (float)(1 << l);
-        const float rx = roundtrip(gx0 / sc, Wl), ry = roundtrip(gy0 / sc, Hl);
+        const float rx = pp_roundtrip(gx0 / sc, Wl), ry = pp_roundtrip(gy0 / sc, Hl);
         const float cx = fminf(fmaxf(rx, -(float)(r + 2)), (float)(Wl + r + 1)), cy = fminf(fmaxf(ry, -(float)(r + 2)), (float)(Hl + r + 1));
         const int bx = (int)floorf(cx) - r, by = (int)floorf(cy) - r;
         const float wx1 = cx - floorf(cx), wy1 = cy - floorf(cy), wx0 = 1.f - wx1, wy0 = 1.f - wy1;
@@ -460,14 +455,14 @@ __global__ __launch_bounds__(1024) void corr_lookup_scatter_kernel(const float* 
         for (int i = threadIdx.x; i < ncell * 16; i += 1024) (&D[0][0])[i] = 0.f;
         int ax, ay;   // anchor: the window base of pixel (px0 + 1, py0 + 1), two positions up and left
         {
-            const float rx = roundtrip(agx / sc, Wl), ry = roundtrip(agy / sc, Hl);
+            const float rx = pp_roundtrip(agx / sc, Wl), ry = pp_roundtrip(agy / sc, Hl);
             const float cx = fminf(fmaxf(rx, -(float)(r + 2)), (float)(Wl + r + 1)), cy = fminf(fmaxf(ry, -(float)(r + 2)), (float)(Hl + r + 1));
             ax = (int)floorf(cx) - r - 2;
             ay = (int)floorf(cy) - r - 2;
         }
         __syncthreads();
         {
-            const float rx = roundtrip(gx0 / sc, Wl), ry = roundtrip(gy0 / sc, Hl);
+            const float rx = pp_roundtrip(gx0 / sc, Wl), ry = pp_roundtrip(gy0 / sc, Hl);
             const float cx = fminf(fmaxf(rx, -(float)(r + 2)), (float)(Wl + r + 1)), cy = fminf(fmaxf(ry, -(float)(r + 2)), (float)(Hl + r + 1));
             const int bx = (int)floorf(cx) - r, by = (int)floorf(cy) - r;
             const float wx1 = cx - floorf(cx), wy1 = cy - floorf(cy), wx0 = 1.f - wx1, wy0 = 1.f - wy1;

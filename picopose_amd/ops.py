@@ -1,4 +1,4 @@
-"""Thin host wrappers over the network engine of libpicopose_hip.so (pp_gemm.hip, pp_sample.hip).
+"""Thin host wrappers over the network engine of libpicopose_hip.so (pp_gemm.hip, pp_sample.hip, pp_corr.hip).
 
 All activations are token-major / NHWC fp32 device tensors: (rows, C) or (B, H, W, C).  Nothing
 here computes with torch ops — torch only allocates the outputs."""
@@ -1295,6 +1295,24 @@ def corr_takes_operands(f1_hl, f2_hl, H, W, C):
             and os.environ.get("PP_CORR_TILED", "1") != "0" and os.environ.get("PP_CORR_HL", "1") != "0")
 
 
+def _corr_pyramid(f2, hl0, levels, fused):
+    """The query pyramid of corr_lookup: (fp32 levels, their operands), each padded with None to three entries.  hl0: the operand of f2 on
+    the operand branch (None: fp32 levels alone).  fused (corr_operand_out): pool and operand in one launch per level, and the last
+    level's fp32 pool, which has no reader, is None; otherwise avgpool2, then split_activation on the operand branch."""
+    C = f2.shape[3]
+    pyr, hls = [f2], [hl0]
+    for i in range(levels - 1):
+        if fused:
+            p, sp = avgpool2_hl(pyr[-1], keep_f32=i < levels - 2)
+            hls.append(sp.hl)
+        else:
+            p = avgpool2(pyr[-1])
+            if hl0 is not None:
+                hls.append(split_activation(p, p.shape[0], p.shape[1] * p.shape[2], C, p.shape[1] * p.shape[2] * C, C))
+        pyr.append(p)
+    return pyr + [None, None], hls + [None, None]
+
+
 def corr_lookup(f1, f2, flow, levels, radius, c_pad=None, f1_hl=None, f2_hl=None, out_split=False):
     """Correlation pyramid + lookup, NHWC: (B,H,W,C) x2, flow (B,H,W,>=2) -> (B,H,W,levels*(2r+1)^2)
     (c_pad: channel count of the result, zero-filled beyond the levels*(2r+1)^2 real channels).
@@ -1315,41 +1333,34 @@ def corr_lookup(f1, f2, flow, levels, radius, c_pad=None, f1_hl=None, f2_hl=None
     np_ = c_pad if c_pad and c_pad > n else n
     assert not out_split or (operands and np_ % 8 == 0), "corr_lookup(out_split=True) needs the operand branch and a padded channel count"
     fused = operands and corr_operand_out()
-    pyr, hls = [f2], [f2_hl.hl if operands else None]
-    for i in range(levels - 1):
-        if fused:      # pool and operand in one launch; the last level's fp32 pool has no reader
-            p, sp = avgpool2_hl(pyr[-1], keep_f32=i < levels - 2)
-            pyr.append(p)
-            hls.append(sp.hl)
-        else:
-            pyr.append(avgpool2(pyr[-1]))
-            if operands:
-                p = pyr[-1]
-                hls.append(split_activation(p, p.shape[0], p.shape[1] * p.shape[2], C, p.shape[1] * p.shape[2] * C, C))
+    pyr, hls = _corr_pyramid(f2, f2_hl.hl if operands else None, levels, fused)
     if operands:
         tgt, col0 = f1_hl
         assert tgt.shape[0] == B * H * W and col0 % 8 == 0 and col0 + C <= tgt.shape[1] and f2_hl.shape == (f2.shape[0] * H * W, C)
-        args = (tgt.hl.data_ptr() + 4 * col0, tgt.shape[1], _p(hls[0]), _p(hls[1]) if levels > 1 else None, _p(hls[2]) if levels > 2 else None,
-                f2.shape[0], _p(flow), B, H, W, C, levels, radius, flow.stride(2))
-        if out_split and fused:
-            sp = Split.empty(B * H * W, np_, f2.device)
-            sp.image = (B, H, W)
-            _lib.check(_lib.lib().pp_corr_lookup_nhwc_hl_op(*args, None, np_, _p(sp.hl), np_, _lib.stream_ptr()), "pp_corr_lookup_nhwc_hl_op")
-            _chk(sp.hl, "pp_corr_lookup_nhwc_hl_op")
-            return sp
-    # (the kernels write the pad channels of their rows themselves; PP_DECODER_LEAN=0: the separate fill of the whole map, as before)
-    out = (torch.zeros if np_ > n and not decoder_lean() else torch.empty)(B, H, W, np_, dtype=torch.float32, device=f2.device)
-    if operands:
-        _lib.check(_lib.lib().pp_corr_lookup_nhwc_hl(*args, _p(out), np_, _lib.stream_ptr()), "pp_corr_lookup_nhwc_hl")
+        maps = (tgt.hl.data_ptr() + 4 * col0, tgt.shape[1], _p(hls[0]), _p(hls[1]), _p(hls[2]))
+    else:
+        maps = (_p(f1), f1.stride(2), _p(pyr[0]), _p(pyr[1]), _p(pyr[2]))
+    args = maps + (f2.shape[0], _p(flow), B, H, W, C, levels, radius, flow.stride(2))   # the arguments the three entry points share
+
+    def fp32_map():   # (the kernels write the pad channels of their rows themselves; PP_DECODER_LEAN=0: the separate fill of the whole map, as before)
+        return (torch.zeros if np_ > n and not decoder_lean() else torch.empty)(B, H, W, np_, dtype=torch.float32, device=f2.device)
+
+    L = _lib.lib()
+    if operands and out_split and fused:   # operands in, the operand of the reading convolution out
+        out = Split.empty(B * H * W, np_, f2.device)
+        out.image = (B, H, W)
+        _lib.check(L.pp_corr_lookup_nhwc_hl_op(*args, None, np_, _p(out.hl), np_, _lib.stream_ptr()), "pp_corr_lookup_nhwc_hl_op")
+        _chk(out.hl, "pp_corr_lookup_nhwc_hl_op")
+    elif operands:                         # operands in, fp32 map out (split afterwards where the caller wants the operand)
+        out = fp32_map()
+        _lib.check(L.pp_corr_lookup_nhwc_hl(*args, _p(out), np_, _lib.stream_ptr()), "pp_corr_lookup_nhwc_hl")
         if out_split:
-            sp = Split(split_activation(out, B, H * W, np_, H * W * np_, np_))
-            sp.image = (B, H, W)
-            return sp
-        return out
-    _lib.check(_lib.lib().pp_corr_lookup_nhwc_ex(_p(f1), f1.stride(2), _p(pyr[0]), _p(pyr[1]) if levels > 1 else None,
-                                                 _p(pyr[2]) if levels > 2 else None, f2.shape[0], _p(flow), B, H, W, C,
-                                                 levels, radius, flow.stride(2), 2 if precision() == "f16" else _fly_prec(), _p(out), np_,
-                                                 _lib.stream_ptr()), "pp_corr_lookup_nhwc_ex")
+            out = Split(split_activation(out, B, H * W, np_, H * W * np_, np_))
+            out.image = (B, H, W)
+    else:                                  # fp32 maps in and out
+        out = fp32_map()
+        _lib.check(L.pp_corr_lookup_nhwc_ex(*args, 2 if precision() == "f16" else _fly_prec(), _p(out), np_, _lib.stream_ptr()),
+                   "pp_corr_lookup_nhwc_ex")
     return out
 
 
