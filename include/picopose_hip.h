@@ -1514,6 +1514,48 @@ int pp_rle_pack_bits(const int* run_ends, int n_runs, const int* run_offset, con
                      unsigned* bits, int* area, void* stream);
 int pp_mask_intersections(const unsigned* bits, int n, int words, int* inter, void* stream);
 
+/* -------------------------------------------------------------------------
+ * POSE VERIFICATION: per pose hypothesis, how well its depth render explains the image: eight integer counts of the render held
+ * against the detection's mask and, when there is one, the test depth image (csrc/pp_verify.hip; picopose_amd/verify.py plans every
+ * call and turns the counts into scores; tests/verify_oracle.py restates this text in numpy; counts equal it bit for bit).  This is
+ * the project's own rule, not a published protocol's.  Millimetres throughout.
+ *
+ * Objects, views, windows and view_zoff are THE SCENE (PpScene, the VSD block): one view per hypothesis, rendered by THE DEPTH RASTER
+ * inside its window; the device table `diameters` is not read and may be NULL.  mask_bits (n_masks, words) uint32 is what
+ * pp_rle_pack_bits writes for the frame: words = ceil(H W / 32), bit x * H + y (word (x H + y) / 32, bit (x H + y) % 32) is pixel
+ * (x, y).  view_mask (n_views) int32, device pointer with a host copy: the mask of each view, so that the hypotheses of one detection
+ * share one mask.  depth (n_images, H, W) fp32 or NULL (RGB only).
+ *
+ * PER VIEW, over the window samples (x, y) with a rendered depth (z-buffer word != all ones, Z > 0), with in_mask the sample's mask
+ * bit and Z_test = depth[view_img][y][x]:
+ *   counts[0] render     every such sample
+ *   counts[1] inter      in_mask
+ *   counts[2] valid      depth given and Z_test > 0 (a NaN or a non-positive Z_test is missing)
+ *   counts[3] agree      valid, not front, not behind
+ *   counts[4] front      valid and e > delta    (the scene is closer: the model is occluded here)
+ *   counts[5] behind     valid and -e > delta   (the sensor sees through the model)
+ *   counts[6] vis        not front              (a missing depth counts as visible: the rule of SCENE GROUND TRUTH)
+ *   counts[7] vis_inter  not front and in_mask
+ * e = D - D_test with xr = ((float) x - cx) / fx, yr = ((float) y - cy) / fy, r = sqrtf((xr xr + yr yr) + 1), D = Z r,
+ * D_test = Z_test r: float32, one rounding per operation, never contracted — the operations of SCENE GROUND TRUTH's `visible`.
+ * With depth = NULL the counts are {render, inter, 0, 0, 0, 0, render, inter}.  A view with an empty window has all-zero counts.
+ *
+ * DETERMINISM.  Only integers are summed (eight counters per lane, xor-shuffles within a wave, LDS across the four waves, one integer
+ * atomicAdd per counter and workgroup into the cleared counts); there is no floating-point atomic.  Every output is the same bits
+ * for any stream, view order, window and grouping of the views over calls.
+ *
+ * Outputs (device): counts (n_views, PP_VERIFY_COUNTS) int32 and near_count (n_views) uint32, both zeroed here.  Workspace (256-byte
+ * aligned): pp_vsd_workspace_bytes(window_samples, view_faces), nothing added.  All work is enqueued on `stream` (two clears, the
+ * raster, one reduction launch); nothing synchronises.
+ * PP_EINVAL (before any launch): THE SCENE CHECKS; a null mask_bits, view_mask, view_mask_host, workspace, counts or near_count;
+ * n_masks <= 0; words != ceil(H W / 32); a view_mask_host entry outside [0, n_masks); delta negative, NaN or infinite.
+ * PP_EWORKSPACE: a workspace that is misaligned or short.
+ * ------------------------------------------------------------------------- */
+#define PP_VERIFY_COUNTS 8
+int pp_pose_verify(const PpScene* scene, const unsigned* mask_bits, int n_masks, int words, const int* view_mask,
+                   const int* view_mask_host, const float* depth, float delta, void* workspace, size_t workspace_bytes, int* counts,
+                   unsigned int* near_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

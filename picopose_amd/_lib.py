@@ -44,7 +44,7 @@ class PpGemmDesc(ctypes.Structure):
 
 
 class PpScene(ctypes.Structure):
-    """The objects, cameras and views of one pp_vsd_errors / pp_depth_refine / pp_scene_gt call (scene.PackedScene fills it)."""
+    """The objects, cameras and views of one pp_vsd_errors / pp_depth_refine / pp_scene_gt / pp_pose_verify call (scene.PackedScene fills it)."""
     _fields_ = ([(name, ctypes.c_void_p) for name in (
         "vertices", "vert_off", "faces", "face_off", "diameters", "cams", "view_obj", "view_img", "poses", "windows", "view_zoff",
         "vert_off_host", "faces_host", "face_off_host", "diameters_host", "cams_host", "view_obj_host", "view_img_host", "windows_host",
@@ -261,6 +261,7 @@ def lib():
         L.pp_proposal_match.argtypes = [vp, i32, vp, vp, c.POINTER(i32), i32, i32, i32, vp, vp, vp, vp, vp]
         L.pp_rle_pack_bits.argtypes = [vp, i32, vp, c.POINTER(i32), i32, i32, i32, vp, vp, vp]
         L.pp_mask_intersections.argtypes = [vp, i32, i32, vp, vp]
+        L.pp_pose_verify.argtypes = [scene, vp, i32, i32, vp, c.POINTER(i32), vp, f32, vp, sz, vp, vp, vp]
         _lib = L
     return _lib
 

@@ -1,0 +1,146 @@
+// Pose verification ("POSE VERIFICATION" of include/picopose_hip.h; picopose_amd/verify.py plans every call and tests/verify_oracle.py
+// restates the contract in numpy): per pose hypothesis eight integer counts of its depth render held against the detection's
+// bit-packed mask and, when there is one, the test depth image.
+//
+//   vsd_raster_small_kernel, vsd_raster_large_kernel  the windowed depth raster of pp_vsd_raster_dev.h (shared with pp_vsd.hip,
+//                            pp_depth_refine.hip and pp_scene_gt.hip, as are the validation of the tables and the workspace's layout)
+//   pose_verify_reduce_kernel  workgroups (chunk, view): walks its share of the view's window, reads Z from the z-buffer words, the
+//                            sample's bit of the view's mask and the test depth; eight INTEGER counters per lane, reduced by
+//                            xor-shuffles and through LDS, then one integer atomicAdd per counter and workgroup
+//
+// The z-buffer is row-major within the window and the mask's bits are column-major over the frame.  A wave takes 64 consecutive
+// samples of the window: one 512-byte z segment, and a gather of 64 mask words H / 32 words apart, which stay in cache (a mask is
+// 38 KB at 640 x 480).  A wave tile of 8 x by 8 y — eight 64-byte z segments, eight mask words — was built and measured slower on
+// the MI355X in every case (profiles/r15/pose_verify.md, which states the tile's index mapping), and was removed.
+//
+// Counts are integer sums: no output depends on launch order, stream, view order, the window or on how the caller groups the views.
+// No floating-point atomics.
+#include <stdint.h>
+#include <limits.h>
+#include <math.h>
+#include "pp_common.h"
+
+#pragma clang fp contract(off)
+#include "pp_vsd_raster_dev.h"
+
+namespace {
+
+constexpr int BLOCK = 256;
+constexpr int WAVES = BLOCK / 64;
+constexpr int NC = PP_VERIFY_COUNTS;   // render, inter, valid, agree, front, behind, vis, vis_inter
+constexpr int MAX_CHUNKS = 128;        // workgroups over one view's window
+constexpr int CHUNK_SAMPLES = BLOCK * 16;
+
+struct Evidence {
+    const unsigned* mask_bits;         // (n_masks, words)
+    const int* view_mask;              // (n_views)
+    const float* depth;                // (n_images, H, W) or null
+    int words;
+    float delta;
+};
+
+__device__ __forceinline__ float word_depth(unsigned long long key) {
+    return key == ~0ull ? 0.f : __uint_as_float((unsigned)(key >> 32));
+}
+
+__global__ __launch_bounds__(BLOCK) void pose_verify_reduce_kernel(Scene s, Evidence ev, const unsigned long long* __restrict__ zbuf,
+                                                                   int* __restrict__ counts) {
+    __shared__ int sm[WAVES][NC];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int v = blockIdx.y; v < s.n_views; v += gridDim.y) {
+        const int* w = s.windows + 4 * (size_t)v;
+        const int x0 = w[0], y0 = w[1], ww = w[2] - w[0], wh = w[3] - w[1];
+        if (ww <= 0 || wh <= 0) continue;
+        const long long n = (long long)ww * wh;
+        if ((long long)blockIdx.x * BLOCK >= n) continue;         // (uniform over the workgroup)
+        const int img = s.view_img[v];
+        const float* k = s.cams + 4 * (size_t)img;
+        const float fx = k[0], fy = k[1], cx = k[2], cy = k[3];
+        const unsigned long long* zv = zbuf + s.view_zoff[v];
+        const unsigned* mask = ev.mask_bits + (size_t)ev.view_mask[v] * ev.words;
+        const float* depth = ev.depth ? ev.depth + (size_t)img * s.H * s.W : nullptr;
+        int val[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) val[c] = 0;
+        for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * BLOCK) {
+            const float z = word_depth(zv[i]);
+            if (!(z > 0.f)) continue;
+            const int yy = (int)(i / ww), x = x0 + (int)(i - (long long)yy * ww), y = y0 + yy;      // in the frame: THE SCENE CHECKS
+            const unsigned bit = (unsigned)x * (unsigned)s.H + (unsigned)y;
+            const int in_mask = (int)((mask[bit >> 5] >> (bit & 31u)) & 1u);
+            int valid = 0, front = 0, behind = 0;
+            if (depth) {
+                const float z_test = depth[(size_t)y * s.W + x];
+                if (z_test > 0.f) {                                // (a NaN is missing)
+                    const float xr = ((float)x - cx) / fx, yr = ((float)y - cy) / fy;
+                    const float r = sqrtf((xr * xr + yr * yr) + 1.f);
+                    const float d = z * r, d_test = z_test * r;
+                    const float e = d - d_test;
+                    valid = 1, front = e > ev.delta ? 1 : 0, behind = -e > ev.delta ? 1 : 0;
+                }
+            }
+            const int vis = 1 - front;
+            val[0] += 1, val[1] += in_mask, val[2] += valid, val[3] += valid & ~(front | behind), val[4] += front, val[5] += behind;
+            val[6] += vis, val[7] += vis & in_mask;
+        }
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            int a = val[c];
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) a += __shfl_xor(a, d, 64);
+            if (lane == 0) sm[wave][c] = a;
+        }
+        __syncthreads();
+        if (threadIdx.x < NC) {
+            int a = sm[0][threadIdx.x];
+            for (int q = 1; q < WAVES; ++q) a += sm[q][threadIdx.x];
+            if (a != 0) atomicAdd(counts + NC * (size_t)v + threadIdx.x, a);
+        }
+        __syncthreads();                                          // sm is reused by the workgroup's next view
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int pp_pose_verify(const PpScene* scene, const unsigned* mask_bits, int n_masks, int words, const int* view_mask, const int* view_mask_host,
+                   const float* depth, float delta, void* workspace, size_t workspace_bytes, int* counts, unsigned int* near_count,
+                   void* stream) {
+    SceneSize n;
+    if (check_scene(scene, false, n) != PP_OK) return PP_EINVAL;
+    if (!mask_bits || !view_mask || !view_mask_host || !workspace || !counts || !near_count) return PP_EINVAL;
+    if (n_masks <= 0 || (long long)words != ((long long)scene->H * scene->W + 31) / 32) return PP_EINVAL;
+    if (!(delta >= 0.f) || !finite32(delta)) return PP_EINVAL;
+    const int n_views = scene->n_views;
+    for (int v = 0; v < n_views; ++v)
+        if ((unsigned)view_mask_host[v] >= (unsigned)n_masks) return PP_EINVAL;
+    size_t need = 0;
+    if (pp_vsd_workspace_bytes(n.samples, n.total_faces, &need) != PP_OK) return PP_EINVAL;
+    if (((uintptr_t)workspace % 256) != 0 || workspace_bytes < need) return PP_EWORKSPACE;
+    long long max_window = 0;
+    for (int v = 0; v < n_views; ++v) {
+        const long long m = scene->view_zoff_host[v + 1] - scene->view_zoff_host[v];
+        max_window = m > max_window ? m : max_window;
+    }
+
+    hipStream_t st = (hipStream_t)stream;
+    const RasterWs ws = carve(workspace, n);
+    const Scene s = device_scene(*scene);
+    const Evidence ev{mask_bits, view_mask, depth, words, delta};
+    PP_CHECK_HIP(hipMemsetAsync(near_count, 0, sizeof(unsigned) * (size_t)n_views, st));
+    PP_CHECK_HIP(hipMemsetAsync(counts, 0, sizeof(int) * NC * (size_t)n_views, st));
+    const int rc = raster_views(s, n, ws, near_count, st);
+    if (rc != PP_OK) return rc;
+    if (n.samples > 0) {
+        const unsigned gv = (unsigned)(n_views < 65535 ? n_views : 65535);                      // (the kernel's view stride)
+        long long chunks = (max_window + CHUNK_SAMPLES - 1) / CHUNK_SAMPLES;
+        const long long cap = 8192 / gv > 1 ? 8192 / gv : 1;                                    // bound the grid of a call with many views
+        chunks = chunks < 1 ? 1 : (chunks > MAX_CHUNKS ? MAX_CHUNKS : chunks);
+        chunks = chunks > cap ? cap : chunks;
+        hipLaunchKernelGGL(pose_verify_reduce_kernel, dim3((unsigned)chunks, gv), dim3(BLOCK), 0, st, s, ev, ws.zbuf, counts);
+    }
+    return pp_last_launch();
+}
+
+}  // extern "C"

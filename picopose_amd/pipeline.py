@@ -447,3 +447,66 @@ def refine_predictions(preds_image, models, obj_ids, K, depth, depth_scale=None,
         for hyps in out:
             hyps.sort(key=lambda h: (0, h["depth_rms"]) if h["depth_status"] <= 1 else (1, 0.0))
     return out
+
+
+VERIFY_KEYS = ("verify_score", "verify_iou", "verify_visible_iou", "verify_agreement", "verify_counts")
+
+
+def verify_predictions(preds_image, models, obj_ids, K, segmentations, size, depth=None, depth_scale=None, stage="stage_3",
+                       hypotheses="all", rank=True, **kw):
+    """Render-and-compare verification of one image's predictions (verify.verify_poses, ONE call for the whole image, mask_index =
+    the instance) -> a new preds_image; the input is not modified.  preds_image: infer_image's result; obj_ids: the object id of
+    each instance (ids known to `models`, an evaluation.ObjectModels with faces); K (3, 3); segmentations: the COCO-RLE mask of each
+    instance, in instance order, each of size = (H, W) — for infer_detections these are the `segmentation`s of the records
+    provider.test_batch.select_detections keeps (score > seg_filter_score), in their order; depth: None (RGB only) or one (H, W) or
+    (1, H, W) image, uint16 raw with `depth_scale` or float millimetres; **kw: verify_poses' parameters (delta, near, window,
+    workspace_bytes).
+    stage: the pose that is verified, read through STAGES as refine_predictions reads it (millimetres): "stage_3" (default), "depth"
+    or "rgbd"; ValueError when a hypothesis to verify holds no such key.  hypotheses: "all" (default) verifies every hypothesis,
+    "best" each instance's first.  A verified hypothesis gains the VERIFY_KEYS: 'verify_score', 'verify_iou', 'verify_visible_iou',
+    'verify_agreement' (floats) and 'verify_counts' (8 ints, verify.COUNTS).
+    rank=True (needs hypotheses="all") re-sorts each instance's hypotheses by descending verify_score; the sort is stable, so ties
+    keep the inlier-ratio order, and bop_csv_lines then prints the verified best hypothesis without change.
+    The score is the project's own rule (verify.py's docstring): with modal masks the RGB-only value ranks the hypotheses of one
+    instance but is not comparable across instances, and accuracy on real data is unmeasured and not claimed.
+    ValueError before any device work: another stage or hypotheses value, rank=True without "all", obj_ids or segmentations that do
+    not match preds_image, a depth that is not one image, and verify_poses' own."""
+    from .verify import verify_poses
+
+    if not (isinstance(stage, str) and stage in STAGES):
+        raise ValueError(f"stage must be one of {sorted(STAGES)}, got {stage!r}")
+    kr, kt = STAGES[stage]
+    if hypotheses not in ("best", "all"):
+        raise ValueError(f"hypotheses must be 'best' or 'all', got {hypotheses!r}")
+    if not isinstance(rank, (bool, np.bool_)):
+        raise ValueError(f"rank must be a bool, got {rank!r}")
+    if rank and hypotheses != "all":
+        raise ValueError("rank=True compares an instance's hypotheses: it needs hypotheses='all'")
+    if len(obj_ids) != len(preds_image):
+        raise ValueError(f"obj_ids must hold one id per instance: {len(obj_ids)} ids for {len(preds_image)} instances")
+    if len(segmentations) != len(preds_image):
+        raise ValueError(f"segmentations must hold one mask per instance: {len(segmentations)} masks for {len(preds_image)} instances")
+    if depth is not None:
+        if getattr(depth, "ndim", 0) == 2:
+            depth = depth[None]
+        if getattr(depth, "ndim", 0) != 3 or depth.shape[0] != 1:
+            raise ValueError(f"depth must be one (H, W) image, got shape {tuple(getattr(depth, 'shape', ()))}")
+    where = [(i, h) for i, hyps in enumerate(preds_image) for h in range(len(hyps) if hypotheses == "all" else min(1, len(hyps)))]
+    for i, h in where:
+        if kr not in preds_image[i][h]:
+            raise ValueError(f"instance {i}, hypothesis {h} holds no {kr!r}: stage={stage!r} has not run for it")
+    R = np.array([np.asarray(preds_image[i][h][kr], dtype=np.float64).reshape(3, 3) for i, h in where]).reshape(-1, 3, 3)
+    t = np.array([np.asarray(preds_image[i][h][kt], dtype=np.float64).reshape(3) for i, h in where]).reshape(-1, 3)
+    ids = np.array([int(obj_ids[i]) for i, _ in where], dtype=np.int64)
+    res = verify_poses(models, ids, R, t, K, segmentations, size, mask_index=np.array([i for i, _ in where], dtype=np.int64),
+                       depth=depth, depth_scale=depth_scale, **kw)
+    host = {k: res[k].cpu().numpy() for k in ("score", "iou", "visible_iou", "agreement", "counts")}
+    out = [[dict(h) for h in hyps] for hyps in preds_image]
+    for n, (i, h) in enumerate(where):
+        out[i][h].update(verify_score=float(host["score"][n]), verify_iou=float(host["iou"][n]),
+                         verify_visible_iou=float(host["visible_iou"][n]), verify_agreement=float(host["agreement"][n]),
+                         verify_counts=[int(c) for c in host["counts"][n]])
+    if rank:
+        for hyps in out:
+            hyps.sort(key=lambda h: -h["verify_score"])
+    return out
