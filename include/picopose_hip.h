@@ -1556,6 +1556,87 @@ int pp_pose_verify(const PpScene* scene, const unsigned* mask_bits, int n_masks,
                    const int* view_mask_host, const float* depth, float delta, void* workspace, size_t workspace_bytes, int* counts,
                    unsigned int* near_count, void* stream);
 
+/* -------------------------------------------------------------------------
+ * DEPTH PROPOSALS: class-agnostic mask proposals from the depth image alone: the dominant plane of each image by consensus, the pixels
+ * that stand off it labelled into 4-connected components, per-component records, and the COCO run lengths of the kept components
+ * (csrc/pp_depth_proposals.hip; picopose_amd/depth_proposals.py plans every call; tests/depth_proposals_oracle.py restates this text in
+ * numpy).  THIS IS THE PROJECT'S OWN ALGORITHM, as POSE VERIFICATION, RGB-D POSE RECOVERY and the depth refinement are; it claims parity
+ * with no published segmenter, and its accuracy on real depth images is unmeasured.  What is exact: given a depth image, every
+ * integer output (scores, winner, labels, records, run ends) equals the restatement bit for bit; the refit plane is a float64 fit.
+ * All pointers are device pointers unless named *_host; all work is enqueued on `stream`, nothing synchronises; only integers meet
+ * in atomics, so every output is the same bits for any stream and launch order.  Millimetres throughout.
+ *
+ * depth (B, H, W) fp32; cams (B, 4) fp32 {fx, fy, cx, cy}, fx and fy non-zero.  A pixel is VALID when 0 < z < infinity (a NaN is
+ * not).  THE POINT of pixel (u, v), float32, one rounding per operation, never contracted:
+ *   X = ((float(u) - cx) * z) / fx,  Y = ((float(v) - cy) * z) / fy,  Z = z.
+ * THE HEIGHT of a point over the plane (nx, ny, nz, d):  s = ((nx * X + ny * Y) + nz * Z) + d, float32 in exactly this order.
+ *
+ * pp_depth_plane.  Hypothesis h < n_hyp (<= PP_PLANE_MAX_HYP) of image b samples the pixels i_k = (aug_hash(seed, b, 3 h + k) * H W)
+ * >> 32 (64-bit product; aug_hash as in "Training-pair assembly"), k = 0, 1, 2, row-major (v = i / W, u = i % W), with points p_k.
+ * With a = p_1 - p_0, e = p_2 - p_0 (componentwise float32), c = (ay ez - az ey, az ex - ax ez, ax ey - ay ex) (each product rounded,
+ * then the difference), len2 = (cx cx + cy cy) + cz cz: the hypothesis is DEAD — it scores 0 and cannot win over a live one —
+ * if any i_k is invalid, or len2 <= PP_PLANE_MIN_CROSS2 (mm^4) or is not finite.  Otherwise inv = 1 / sqrtf(len2) (both correctly
+ * rounded), n = c * inv, d = -((nx p0x + ny p0y) + nz p0z).  Its score is the INTEGER count of valid pixels with |s| <= tau.  The
+ * winner is the highest score, the lowest h among equals.  An image whose best score is below min_inliers has NO PLANE.
+ * Refit: over the winner's consensus set (the same pixels), with q = p - p_0 in float64, the sums of q and of q q^T and the count are
+ * accumulated per strip of PP_PLANE_STRIP pixels (per lane in pixel order, a butterfly over the lane masks 32 .. 1, the four waves in
+ * order) and the strips added in a fixed order (lane l of one wave takes strips l, l + 64, ... ascending, then the same butterfly).
+ * The normal is the eigenvector of the smallest eigenvalue of sum(q q^T) / N - m m^T, m = sum(q) / N, by the cyclic Jacobi of the pose
+ * solvers, normalised; d = -n . (p_0 + m); the sign is chosen so that d >= 0 (the camera is on the positive side).
+ * Outputs: plane64 (B, 4) float64, plane (B, 4) fp32 = its cast, info (B, 4) int32 = {has_plane, winner, its score, the refit's
+ * consensus count}; an image with no plane has a zero plane row and refit count 0 (winner and score are still reported).
+ * Workspace (256-byte aligned): pp_depth_plane_workspace_bytes = roundup256(4 B n_hyp) + roundup256(80 B ceil(H W / PP_PLANE_STRIP)).
+ * PP_EINVAL (before any launch): a null pointer; B, H or W <= 0; B > 65535; H W >= 2^31; n_hyp outside [1, PP_PLANE_MAX_HYP]; tau
+ * negative, NaN or infinite; min_inliers < 3.  PP_EWORKSPACE: a workspace that is misaligned or short.
+ *
+ * pp_depth_components.  plane (B, 4) fp32 and has_plane (B) int32 as above (any plane may be given).  A valid pixel is FOREGROUND when
+ * Z <= max_range and, where has_plane[b] != 0, min_height < s < max_height (both strict).  Two 4-neighbours that are both foreground
+ * are CONNECTED when |z_p - z_q| <= max_step: one float32 subtraction, equality connects.  labels (B, H, W) int32: -1 for background,
+ * otherwise the smallest row-major pixel index (y W + x, within the image) of the pixel's component.  Union by smaller index: the
+ * result does not depend on the order of the unions.  One workgroup per 32 x 128 tile (labels and depth in LDS), then the pairs
+ * across tile edges in global memory, then a pass that replaces every label by its root.  pp_depth_components_workspace_bytes is 0
+ * today (the labels are the parent array); workspace may be NULL.
+ * PP_EINVAL: a null depth, cams, plane, has_plane or labels; the frame limits above; H > 32 * 65535; a NaN height bound; max_range not
+ * positive; max_step negative, NaN or infinite.
+ *
+ * pp_component_stats.  Per root (a pixel whose label is its own index): area, the inclusive box xmin, ymin, xmax, ymax, and border = 1
+ * when a pixel of the component lies in the first or last row or column.  The roots with min_area <= area <= max_area (and border = 0
+ * when drop_border) QUALIFY: n_qualified (B) int32 counts them all; the first min(n_qualified[b], cap) rows of comps (B, cap,
+ * PP_COMPONENT_FIELDS) int32 = {root, area, xmin, ymin, xmax, ymax, border} hold qualifiers in an UNSPECIFIED order (which ones when
+ * n_qualified > cap is unspecified too); the other rows are not written.  Lanes of a wave that share a root are reduced by ballots
+ * and shuffles before one integer atomic per value (at most four roots per wave this way, the rest lane by lane).
+ * Workspace (256-byte aligned): pp_component_stats_workspace_bytes = roundup256(24 B H W); it is not cleared.
+ * PP_EINVAL: a null pointer; the frame limits; min_area < 1; max_area < min_area; cap < 1.  PP_EWORKSPACE as above.
+ *
+ * pp_components_rle.  sel (n, PP_RLE_SEL_FIELDS) int32 with a host copy = {image, root, xmin, ymin, xmax, ymax}: the mask of entry k
+ * is labels[image] == root inside the box (a box that holds the whole component gives the component).  With run_ends NULL (the COUNT
+ * pass): n_runs[k] = the number of cumulative run ends of the mask in COCO's column-major order (position x H + y): a leading 0 when
+ * pixel 0 is set, every position f >= 1 whose pixel differs from pixel f - 1, and H W.  With run_ends (the EMIT pass): those ends,
+ * ascending, at run_ends[run_offset[k] ..]; run_offset (n + 1) with its host copy is the exclusive sum of the counts, ending in
+ * n_runs_total — the tables pp_rle_pack_bits and pp_detections_crop read.  Nothing is written at or past run_offset[k + 1].
+ * One workgroup per entry walks the columns of the box; no dense mask is built.
+ * PP_EINVAL: a null labels, sel or sel_host; the frame limits; n <= 0 or > PP_MASK_MAX_N; a sel_host row with an image outside [0, B), a
+ * root outside [0, H W) or a box that is empty or leaves the frame; count pass: n_runs NULL; emit pass: a null run_offset or
+ * run_offset_host, n_runs_total <= 0, run_offset_host not starting at 0, decreasing or not ending in n_runs_total.
+ * ------------------------------------------------------------------------- */
+#define PP_PLANE_MAX_HYP 1024
+#define PP_PLANE_STRIP 1024
+#define PP_PLANE_MIN_CROSS2 1.0f
+#define PP_COMPONENT_FIELDS 7
+#define PP_RLE_SEL_FIELDS 6
+int pp_depth_plane_workspace_bytes(int B, int H, int W, int n_hyp, size_t* bytes);
+int pp_depth_plane(const float* depth, const float* cams, int B, int H, int W, int n_hyp, unsigned seed, float tau, int min_inliers,
+                   void* workspace, size_t workspace_bytes, float* plane, double* plane64, int* info, void* stream);
+int pp_depth_components_workspace_bytes(int B, int H, int W, size_t* bytes);
+int pp_depth_components(const float* depth, const float* cams, const float* plane, const int* has_plane, int B, int H, int W,
+                        float min_height, float max_height, float max_range, float max_step, void* workspace, size_t workspace_bytes,
+                        int* labels, void* stream);
+int pp_component_stats_workspace_bytes(int B, int H, int W, size_t* bytes);
+int pp_component_stats(const int* labels, int B, int H, int W, int min_area, int max_area, int drop_border, int cap, void* workspace,
+                       size_t workspace_bytes, int* n_qualified, int* comps, void* stream);
+int pp_components_rle(const int* labels, int B, int H, int W, const int* sel, const int* sel_host, int n, const int* run_offset,
+                      const int* run_offset_host, int n_runs_total, int* n_runs, int* run_ends, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -262,6 +262,13 @@ def lib():
         L.pp_rle_pack_bits.argtypes = [vp, i32, vp, c.POINTER(i32), i32, i32, i32, vp, vp, vp]
         L.pp_mask_intersections.argtypes = [vp, i32, i32, vp, vp]
         L.pp_pose_verify.argtypes = [scene, vp, i32, i32, vp, c.POINTER(i32), vp, f32, vp, sz, vp, vp, vp]
+        L.pp_depth_plane_workspace_bytes.argtypes = [i32, i32, i32, i32, c.POINTER(sz)]
+        L.pp_depth_plane.argtypes = [vp, vp, i32, i32, i32, i32, c.c_uint, f32, i32, vp, sz, vp, vp, vp, vp]
+        L.pp_depth_components_workspace_bytes.argtypes = [i32, i32, i32, c.POINTER(sz)]
+        L.pp_depth_components.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, vp, sz, vp, vp]
+        L.pp_component_stats_workspace_bytes.argtypes = [i32, i32, i32, c.POINTER(sz)]
+        L.pp_component_stats.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, vp, vp]
+        L.pp_components_rle.argtypes = [vp, i32, i32, i32, vp, c.POINTER(i32), i32, vp, c.POINTER(i32), i32, vp, vp, vp]
         _lib = L
     return _lib
 

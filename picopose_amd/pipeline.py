@@ -363,6 +363,40 @@ def infer_proposals(net, image_u8, proposals, K, templates_data, bank, **kw):
     return preds_image, data, kept
 
 
+DEPTH_PROPOSAL_KEYS = ("tau", "n_hyp", "seed", "min_inliers", "min_height", "max_height", "max_range", "max_step", "max_area_frac",
+                       "drop_border", "max_proposals")       # depth_proposals' own (min_area_px stays label_proposals', see below)
+
+
+def infer_depth_proposals(net, image_u8, depth, K, templates_data, bank, **kw):
+    """One decoded test image and its depth image (H, W) -> (preds_image, data, detections, proposals): depth_proposals.depth_proposals
+    segments the depth image (the project's own depth clusterer; the keywords of DEPTH_PROPOSAL_KEYS go there, `proposal_min_area_px`
+    as its min_area_px, `device` to both), then infer_proposals labels the masks against `bank` and estimates the poses.  depth: uint16
+    raw with `depth_scale`, or float millimetres.  With `rgbd_inlier_dist` the depth image and `depth_scale` are forwarded too (float
+    depth as depth_unit "mm"), so the RGB-D keywords of infer_image keep working; without it the poses are RGB only.  Every other
+    keyword is infer_proposals'.  proposals: the segmenter's list, largest first; ([], None, [], proposals) when none survives."""
+    from .depth_proposals import depth_proposals
+
+    dkw = {k: kw.pop(k) for k in DEPTH_PROPOSAL_KEYS if k in kw}
+    if "proposal_min_area_px" in kw:
+        dkw["min_area_px"] = kw.pop("proposal_min_area_px")
+    if "device" in kw:
+        dkw["device"] = kw["device"]
+    if getattr(depth, "ndim", 0) != 2:
+        raise ValueError(f"depth must be one (H, W) image, got shape {tuple(getattr(depth, 'shape', ()))}")
+    depth_scale = kw.pop("depth_scale", None)
+    if depth_scale is None and kw.get("depth_unit", "mm") != "mm":
+        raise ValueError("float depth is millimetres here: depth_unit must be 'mm'")
+    K33 = np.asarray(K.cpu() if isinstance(K, torch.Tensor) else K, dtype=np.float64).reshape(3, 3)      # (a flat list of 9, as BOP stores it)
+    proposals = depth_proposals(depth, K33, depth_scale=depth_scale, **dkw)
+    if kw.get("rgbd_inlier_dist") is not None:
+        kw.update(depth=depth, depth_scale=depth_scale)
+        if depth_scale is None:
+            kw["depth_unit"] = "mm"
+    else:
+        kw.pop("depth_unit", None)
+    return (*infer_proposals(net, image_u8, proposals, K, templates_data, bank, **kw), proposals)
+
+
 def _collect(pending, hyp, net, pnp_refine=None):
     handle, s2_host, ev, B, inputs, rgbd = pending
     rot, tvec, ratio, ok = pnp_collect(handle, hyp, B)

@@ -1,6 +1,6 @@
 """Label class-agnostic mask proposals against the template banks: which onboarded object a mask is, and how sure.
 
-A segmenter (SAM, FastSAM, a depth clusterer: anything that emits COCO-RLE masks; none is part of this project) gives the
+A segmenter (SAM, FastSAM, a depth clusterer: anything that emits COCO-RLE masks; the depth clusterer of `depth_proposals` is the project's own) gives the
 proposals; `label_proposals` turns them into the CNOS-shaped detection records that `pipeline.infer_detections` and
 `provider.test_batch.assemble_test_image` read, from the `tem_rgb` that `onboard_objects` already produced.
 
