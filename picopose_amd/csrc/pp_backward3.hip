@@ -314,7 +314,44 @@ __global__ __launch_bounds__(256) void warp_backward_kernel(const float* __restr
 // One wave per pixel: the (2r+2)^2 table positions per level are visited one after the other, lanes over channels.
 constexpr int CLB_MAXL = 3, CLB_TW = 8;   // levels, table width for r <= 3
 
-template <bool FIXED, bool SCATTER = true>
+// The adjoint weights of table position (dy_, dx_) of one level: over the outputs (ai, bi) that have the position as their corner (cy_, cx_),
+//   s = sum go w_x w_y (the table's gradient),  sx = sum go (+-1) w_y,  sy = sum go (+-1) w_x (the coordinate's gradient; +1 for the upper corner).
+// Output (ai, bi) = (dx_ - cx_, dy_ - cy_) — except on a pooled axis of size 1 (FLAT; flat_x / flat_y), where the reference's round trip
+// multiplies by size - 1 = 0 and EVERY offset samples coordinate 0: there all `win` offsets read the position of offset 0 (index r) and no other.
+// FLAT = false is the code of every level the production shapes have: one guarded fma per corner.  FLAT is a template argument of the two
+// kernels, chosen at the launch (the coarsest level decides), so that those shapes run the code they ran before the case existed.
+template <bool FLAT>
+__device__ __forceinline__ void corr_corner_sums(const float* __restrict__ gl, int win, int r, int dy_, int dx_, float wx0, float wx1, float wy0,
+                                                 float wy1, bool flat_x, bool flat_y, float& s, float& sx, float& sy) {
+    s = sx = sy = 0.f;
+#pragma unroll
+    for (int cy_ = 0; cy_ < 2; ++cy_)
+#pragma unroll
+        for (int cx_ = 0; cx_ < 2; ++cx_) {
+            const int bi = dy_ - cy_, ai = dx_ - cx_;
+            const float wx = cx_ ? wx1 : wx0, wy = cy_ ? wy1 : wy0, gx = (cx_ ? 1.f : -1.f) * wy, gy = (cy_ ? 1.f : -1.f) * wx;
+            if (!FLAT) {
+                if (ai >= 0 && ai < win && bi >= 0 && bi < win) {
+                    const float go = gl[ai * win + bi];
+                    s = fmaf(go, wx * wy, s);
+                    sx = fmaf(go, gx, sx);
+                    sy = fmaf(go, gy, sy);
+                }
+            } else {
+                const int a0 = flat_x ? 0 : ai, a1 = flat_x ? (ai == r ? win : 0) : (ai >= 0 && ai < win ? ai + 1 : ai);
+                const int b0 = flat_y ? 0 : bi, b1 = flat_y ? (bi == r ? win : 0) : (bi >= 0 && bi < win ? bi + 1 : bi);
+                for (int a = a0; a < a1; ++a)
+                    for (int b = b0; b < b1; ++b) {
+                        const float go = gl[a * win + b];
+                        s = fmaf(go, wx * wy, s);
+                        sx = fmaf(go, gx, sx);
+                        sy = fmaf(go, gy, sy);
+                    }
+            }
+        }
+}
+
+template <bool FIXED, bool SCATTER = true, bool FLAT = false>
 __global__ __launch_bounds__(256) void corr_lookup_backward_kernel(const float* __restrict__ f1, const float* __restrict__ f2l0,
                                                                    const float* __restrict__ f2l1, const float* __restrict__ f2l2,
                                                                    const float* __restrict__ flow, const float* __restrict__ dout, int H,
@@ -349,15 +386,8 @@ __global__ __launch_bounds__(256) void corr_lookup_backward_kernel(const float* 
         // dtab[dy][dx] = sum over the outputs (a, b) whose four corners include (dy, dx)
         for (int i = lane; i < tw * tw; i += 64) {
             const int dy_ = i / tw, dx_ = i - dy_ * tw;
-            float s = 0.f;
-#pragma unroll
-            for (int cy_ = 0; cy_ < 2; ++cy_)
-#pragma unroll
-                for (int cx_ = 0; cx_ < 2; ++cx_) {
-                    const int bi = dy_ - cy_, ai = dx_ - cx_;      // output (ai, bi) has this position as corner (cy_, cx_)
-                    if (ai >= 0 && ai < win && bi >= 0 && bi < win)
-                        s = fmaf(g[l * win * win + ai * win + bi], (cx_ ? wx1 : wx0) * (cy_ ? wy1 : wy0), s);
-                }
+            float s, sx_, sy_;
+            corr_corner_sums<FLAT>(g + l * win * win, win, r, dy_, dx_, wx0, wx1, wy0, wy1, Wl == 1, Hl == 1, s, sx_, sy_);
             dtab[l * CLB_TW * CLB_TW + i] = s;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -385,23 +415,14 @@ __global__ __launch_bounds__(256) void corr_lookup_backward_kernel(const float* 
             }
             const float val = wave_sum(dot) * inv_sqrt_c;
             // d out(ai, bi) / d wx1 for the outputs that use this position: corner (cy_, cx_) carries sign (cx_ ? +1 : -1) wy
-            float sx = 0.f, sy = 0.f;
-#pragma unroll
-            for (int cy_ = 0; cy_ < 2; ++cy_)
-#pragma unroll
-                for (int cx_ = 0; cx_ < 2; ++cx_) {
-                    const int bi = dy_ - cy_, ai = dx_ - cx_;
-                    if (ai >= 0 && ai < win && bi >= 0 && bi < win) {
-                        const float go = g[l * win * win + ai * win + bi];
-                        sx = fmaf(go, (cx_ ? 1.f : -1.f) * (cy_ ? wy1 : wy0), sx);
-                        sy = fmaf(go, (cy_ ? 1.f : -1.f) * (cx_ ? wx1 : wx0), sy);
-                    }
-                }
+            float s_, sx, sy;
+            corr_corner_sums<FLAT>(g + l * win * win, win, r, dy_, dx_, wx0, wx1, wy0, wy1, Wl == 1, Hl == 1, s_, sx, sy);
             gcx = fmaf(val, sx, gcx);
             gcy = fmaf(val, sy, gcy);
         }
-        if (rx == cx) dfx += gcx / sc;   // (every lane holds the same sums)
-        if (ry == cy) dfy += gcy / sc;
+        // (every lane holds the same sums; a pooled axis of size 1: the coordinate does not depend on the flow, as in warp_backward_kernel)
+        if (rx == cx && (!FLAT || Wl > 1)) dfx += gcx / sc;
+        if (ry == cy && (!FLAT || Hl > 1)) dfy += gcy / sc;
         __builtin_amdgcn_wave_barrier();
     }
 #pragma unroll
@@ -427,7 +448,7 @@ __global__ __launch_bounds__(256) void corr_lookup_backward_kernel(const float* 
 // with integer atomics — the same bits on every run (the deterministic option).
 constexpr int CS_CH = 128, CS_CELLS = (CLB_TW + 4) * (CLB_TW + 4);
 
-template <bool FIXED>
+template <bool FIXED, bool FLAT = false>
 __global__ __launch_bounds__(1024) void corr_lookup_scatter_kernel(const float* __restrict__ f1, const float* __restrict__ flow,
                                                                    const float* __restrict__ dout, int H, int W, int C, int L, int r, int ld_flow,
                                                                    int ld_dout, float inv_sqrt_c, void* __restrict__ df2l0,
@@ -471,15 +492,8 @@ __global__ __launch_bounds__(1024) void corr_lookup_scatter_kernel(const float* 
             bool far = false;
             if (lane < tw * tw) {      // lane = table position; dt as in corr_lookup_backward_kernel
                 const int dy_ = lane / tw, dx_ = lane - dy_ * tw;
-                float s = 0.f;
-#pragma unroll
-                for (int cy_ = 0; cy_ < 2; ++cy_)
-#pragma unroll
-                    for (int cx_ = 0; cx_ < 2; ++cx_) {
-                        const int bi = dy_ - cy_, ai = dx_ - cx_;
-                        if (ai >= 0 && ai < win && bi >= 0 && bi < win)
-                            s = fmaf(g[l * win * win + ai * win + bi], (cx_ ? wx1 : wx0) * (cy_ ? wy1 : wy0), s);
-                    }
+                float s, sx_, sy_;
+                corr_corner_sums<FLAT>(g + l * win * win, win, r, dy_, dx_, wx0, wx1, wy0, wy1, Wl == 1, Hl == 1, s, sx_, sy_);
                 qx = bx + dx_;
                 qy = by + dy_;
                 dt = (qx >= 0 && qx < Wl && qy >= 0 && qy < Hl) ? s * inv_sqrt_c : 0.f;
@@ -647,27 +661,24 @@ static int corr_lookup_backward(const float* f1, const float* const* f2_levels, 
     const float *f20 = f2_levels[0], *f21 = levels > 1 ? f2_levels[1] : nullptr, *f22 = levels > 2 ? f2_levels[2] : nullptr;
     void *d0 = df2_levels[0], *d1 = levels > 1 ? df2_levels[1] : nullptr, *d2 = levels > 2 ? df2_levels[2] : nullptr;
     hipStream_t st = (hipStream_t)stream;
-    if (H % 4 == 0 && W % 4 == 0 && C % CS_CH == 0 && !getenv("PP_CORR_SCATTER_PER_PIXEL")) {
-        // values / df1 / dflow per pixel without the scatter, df2 by patches (corr_lookup_scatter_kernel)
-        const dim3 sgrid((H / 4) * (W / 4), B, C / CS_CH);
-        if (fixed) {
-            hipLaunchKernelGGL((corr_lookup_backward_kernel<true, false>), pgrid, dim3(256), 0, st, f1, f20, f21, f22, flow, dout, H, W, C, levels, radius,
-                               ld_flow, ld_dout, isc, df1, d0, d1, d2, dflow);
-            hipLaunchKernelGGL(corr_lookup_scatter_kernel<true>, sgrid, dim3(1024), 0, st, f1, flow, dout, H, W, C, levels, radius, ld_flow, ld_dout, isc, d0,
-                               d1, d2);
-        } else {
-            hipLaunchKernelGGL((corr_lookup_backward_kernel<false, false>), pgrid, dim3(256), 0, st, f1, f20, f21, f22, flow, dout, H, W, C, levels, radius,
-                               ld_flow, ld_dout, isc, df1, d0, d1, d2, dflow);
-            hipLaunchKernelGGL(corr_lookup_scatter_kernel<false>, sgrid, dim3(1024), 0, st, f1, flow, dout, H, W, C, levels, radius, ld_flow, ld_dout, isc, d0,
-                               d1, d2);
-        }
-    } else if (fixed) {
-        hipLaunchKernelGGL(corr_lookup_backward_kernel<true>, pgrid, dim3(256), 0, st, f1, f20, f21, f22, flow, dout, H, W, C, levels, radius, ld_flow, ld_dout,
-                           isc, df1, d0, d1, d2, dflow);
-    } else {
-        hipLaunchKernelGGL(corr_lookup_backward_kernel<false>, pgrid, dim3(256), 0, st, f1, f20, f21, f22, flow, dout, H, W, C, levels, radius, ld_flow, ld_dout,
-                           isc, df1, d0, d1, d2, dflow);
-    }
+    // [FIXED][SCATTER][FLAT] / [FIXED][FLAT].  FLAT: the coarsest level has a pooled axis of size 1 (corr_corner_sums); every other shape runs
+    // the kernels without that case
+    static const decltype(&corr_lookup_backward_kernel<false, true, false>) pixel[2][2][2] = {
+        {{corr_lookup_backward_kernel<false, false, false>, corr_lookup_backward_kernel<false, false, true>},
+         {corr_lookup_backward_kernel<false, true, false>, corr_lookup_backward_kernel<false, true, true>}},
+        {{corr_lookup_backward_kernel<true, false, false>, corr_lookup_backward_kernel<true, false, true>},
+         {corr_lookup_backward_kernel<true, true, false>, corr_lookup_backward_kernel<true, true, true>}}};
+    static const decltype(&corr_lookup_scatter_kernel<false, false>) patch[2][2] = {
+        {corr_lookup_scatter_kernel<false, false>, corr_lookup_scatter_kernel<false, true>},
+        {corr_lookup_scatter_kernel<true, false>, corr_lookup_scatter_kernel<true, true>}};
+    const bool flat = (H >> (levels - 1)) == 1 || (W >> (levels - 1)) == 1;
+    // values / df1 / dflow per pixel; df2 by that kernel's own scatter, or by patches (corr_lookup_scatter_kernel)
+    const bool by_patch = H % 4 == 0 && W % 4 == 0 && C % CS_CH == 0 && !getenv("PP_CORR_SCATTER_PER_PIXEL");
+    hipLaunchKernelGGL(pixel[fixed][!by_patch][flat], pgrid, dim3(256), 0, st, f1, f20, f21, f22, flow, dout, H, W, C, levels, radius, ld_flow, ld_dout, isc,
+                       df1, d0, d1, d2, dflow);
+    if (by_patch)
+        hipLaunchKernelGGL(patch[fixed][flat], dim3((H / 4) * (W / 4), B, C / CS_CH), dim3(1024), 0, st, f1, flow, dout, H, W, C, levels, radius, ld_flow,
+                           ld_dout, isc, d0, d1, d2);
     return pp_last_launch();
 }
 

@@ -79,7 +79,10 @@ __global__ __launch_bounds__(256) void corr_lookup_kernel(const float* __restric
             const int l = i / (win * win), rem = i - l * win * win, ai = rem / win, bi = rem - ai * win;
             const float wx1 = cx[l] - floorf(cx[l]), wy1 = cy[l] - floorf(cy[l]);
             const float wx0 = 1.f - wx1, wy0 = 1.f - wy1;
-            const float* t = tab + l * tw * tw + bi * tw + ai;  // x offset a-r -> dx = ai, y offset b-r -> dy = bi
+            // x offset a-r -> dx = ai, y offset b-r -> dy = bi.  A pooled axis of size 1: the reference's round trip multiplies by size - 1 = 0,
+            // so every offset along it samples coordinate 0 — all of them read the column (row) of offset 0 (c = 0 there: weights 1 and 0)
+            const int di = (W >> l) == 1 ? r : ai, dj = (H >> l) == 1 ? r : bi;
+            const float* t = tab + l * tw * tw + dj * tw + di;
             o[i] = t[0] * (wx0 * wy0) + t[1] * (wx1 * wy0) + t[tw] * (wx0 * wy1) + t[tw + 1] * (wx1 * wy1);
         }
         for (int i = nout + lane; i < ld_out; i += 64) o[i] = 0.f;   // the pad channels of the row (the caller allocates without a fill)
@@ -494,6 +497,7 @@ int pp_corr_lookup_nhwc_ex(const float* f1, int ld_f1, const float* f2_l0, const
     // every pyramid level the tiled kernel reads goes through 16-byte vector loads: a misaligned one falls back (as the hl entry
     // point below rejects it) instead of faulting
     const bool aligned = (((uintptr_t)f2_l0 | (levels > 1 ? (uintptr_t)f2_l1 : 0) | (levels > 2 ? (uintptr_t)f2_l2 : 0)) % 16) == 0;
+    // (H, W % 8 == 0 and at most three levels: a tiled kernel never sees a pooled axis shorter than 2, the case corr_lookup_kernel treats apart)
     if (tiled && H % CT == 0 && W % CT == 0 && C % CK == 0 && aligned)   // (PP_CORR_TILED=0 keeps the lane-per-position kernel)
         return corr_tiled_launch(false, f1, ld_f1, f2_l0, f2_l1, f2_l2, f2_batch, flow, B, H, W, C, levels, radius, ld_flow, out, ld_out, stream,
                                  prec == PP_PREC_F32, prec == PP_PREC_F16);

@@ -1317,6 +1317,8 @@ def corr_lookup(f1, f2, flow, levels, radius, c_pad=None, f1_hl=None, f2_hl=None
     """Correlation pyramid + lookup, NHWC: (B,H,W,C) x2, flow (B,H,W,>=2) -> (B,H,W,levels*(2r+1)^2)
     (c_pad: channel count of the result, zero-filled beyond the levels*(2r+1)^2 real channels).
     f1 may be a channel slice of a wider buffer; f2 may hold B / k images (image b reads f2[b % (B / k)]).
+    A level whose pooled map is one pixel wide (high): every window offset along that axis samples coordinate 0, as the reference's
+    normalise / de-normalise round trip has it (x (size - 1) = 0), and the flow gets no gradient along it.
     f1_hl = (Split over (B*H*W, Ctot), col0), f2_hl = Split over (Bf*H*W, C): the same maps as operands the producers have
     already written (f16x3 engine, tileable shapes): the kernel then stages 16-byte copies instead of splitting every chunk.
     f1 = None: the map exists only as f1_hl (allowed exactly where `corr_takes_operands` holds).
