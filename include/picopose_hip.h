@@ -872,6 +872,8 @@ int pp_depth_u16_template(const unsigned short* depth, long long n, float* out, 
 /* -------------------------------------------------------------------------
  * Detection batch of one test image (provider/bop_test_dataset.py:112-207; picopose_amd/provider/test_batch.py plans the call):
  * pp_crop_resize_normalize for n detections of one frame in one launch, the masks given as COCO run lengths instead of frames.
+ * THE RUN TABLES (run_ends, run_offset, run_offset_host) are stated here once; pp_rle_pack_bits reads and pp_components_rle writes the
+ * same tables.  picopose_amd/masks.py builds them; csrc/pp_runs_dev.h holds the checks and the search that their readers share.
  *
  * image (H, W, 3) uint8 as loaded (H * W < 2^31).  run_ends: the detections' cumulative run ends, concatenated — detection d owns
  * run_ends[run_offset[d] .. run_offset[d + 1]), the inclusive prefix sums of its COCO counts (column-major over (H, W), runs

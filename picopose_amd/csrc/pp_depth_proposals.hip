@@ -27,6 +27,7 @@
 #include <limits.h>
 #include <math.h>
 #include "pp_common.h"
+#include "pp_runs_dev.h"
 
 #pragma clang fp contract(off)
 #include "pp_ransac_dev.h"
@@ -599,9 +600,8 @@ int pp_components_rle(const int* labels, int B, int H, int W, const int* sel, co
         if (s[2] < 0 || s[2] > s[4] || s[4] >= W || s[3] < 0 || s[3] > s[5] || s[5] >= H) return PP_EINVAL;
     }
     if (emit) {
-        if (run_offset_host[0] != 0 || run_offset_host[n] != n_runs_total) return PP_EINVAL;
-        for (int k = 0; k < n; ++k)
-            if (run_offset_host[k + 1] < run_offset_host[k]) return PP_EINVAL;
+        if (!pp_run_offsets_ok(run_offset_host, n, n_runs_total) || run_offset_host[0] != 0 || run_offset_host[n] != n_runs_total)
+            return PP_EINVAL;
     }
     hipLaunchKernelGGL(rle_kernel, dim3((unsigned)n), dim3(BLOCK), 0, (hipStream_t)stream, labels, H, W, sel, run_offset, n_runs, run_ends);
     return pp_last_launch();

@@ -8,6 +8,7 @@
 #include <stdint.h>
 #include <limits.h>
 #include "pp_common.h"
+#include "pp_runs_dev.h"
 
 namespace {
 
@@ -34,17 +35,6 @@ __device__ __forceinline__ int wave_bound(const int* __restrict__ ends, int a, i
     return a;
 }
 
-// ends[0..m) sorted: how many are <= key
-__device__ __forceinline__ int count_le(const int* ends, int m, int key) {
-    int lo = 0, hi = m;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (ends[mid] <= key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(TILE * TILE) void detections_crop_kernel(
     const unsigned char* __restrict__ img, int H, int W, const int* __restrict__ run_ends, int n_runs,
     const int* __restrict__ run_offset, const int* __restrict__ window, int S, int mask_rgb, double m0, double m1, double m2,
@@ -55,9 +45,9 @@ __global__ __launch_bounds__(TILE * TILE) void detections_crop_kernel(
     const int ntx = (S + TILE - 1) / TILE;
     const int tx0 = (blockIdx.x % ntx) * TILE, ty0 = (blockIdx.x / ntx) * TILE;
     const int y1 = window[det * 4], y2 = window[det * 4 + 1], x1 = window[det * 4 + 2], x2 = window[det * 4 + 3];
-    const int r0 = run_offset[det], r1 = run_offset[det + 1];
+    int r0, r1;
     // the host entry validated its copies of both tables; a device copy that disagrees must not lead outside the buffers
-    if (y1 < 0 || x1 < 0 || y2 > H || x2 > W || y2 <= y1 || x2 <= x1 || r0 < 0 || r1 < r0 || r1 > n_runs) return;
+    if (!pp_run_slice(run_offset, det, n_runs, r0, r1) || y1 < 0 || x1 < 0 || y2 > H || x2 > W || y2 <= y1 || x2 <= x1) return;
     const int h = y2 - y1, w = x2 - x1;
     auto taps = [](int o, int n, int S_, int& i0, int& i1, double& fr) {
         const double f = ((double)o + 0.5) * ((double)n / (double)S_) - 0.5;
@@ -102,7 +92,7 @@ __global__ __launch_bounds__(TILE * TILE) void detections_crop_kernel(
     __syncthreads();
     const int* ends = staged ? slice : run_ends + lo;
     const int par0 = (lo - r0) & 1;                                           // runs wholly before the tile's columns
-    auto inside = [&](int yy, int xx) -> bool { return ((par0 + count_le(ends, m, (x1 + xx) * H + (y1 + yy))) & 1) != 0; };
+    auto inside = [&](int yy, int xx) -> bool { return ((par0 + pp_count_le(ends, m, (x1 + xx) * H + (y1 + yy))) & 1) != 0; };
 
     const int oy = ty0 + tid / TILE, ox = tx0 + tid % TILE;
     if (oy >= S || ox >= S) return;
@@ -146,10 +136,9 @@ int pp_detections_crop(const unsigned char* image, int H, int W, const int* run_
     if (!image || !run_ends || !run_offset || !window || !run_offset_host || !window_host || !mean3 || !std3 || !out_rgb ||
         !out_mask || H <= 0 || W <= 0 || (long long)H * W > INT_MAX || n_runs <= 0 || n <= 0 || n > 65535 || S <= 0 || S > 4096)
         return PP_EINVAL;
-    if (run_offset_host[0] < 0 || run_offset_host[n] > n_runs) return PP_EINVAL;
+    if (!pp_run_offsets_ok(run_offset_host, n, n_runs)) return PP_EINVAL;
     for (int d = 0; d < n; ++d) {
         const int* wd = window_host + 4 * d;
-        if (run_offset_host[d + 1] < run_offset_host[d]) return PP_EINVAL;
         if (wd[0] < 0 || wd[2] < 0 || wd[1] > H || wd[3] > W || wd[1] <= wd[0] || wd[3] <= wd[2]) return PP_EINVAL;
     }
     const int nt = (S + TILE - 1) / TILE;

@@ -6,6 +6,7 @@
 #include <limits.h>
 #include <math.h>
 #include "pp_common.h"
+#include "pp_runs_dev.h"
 
 namespace {
 
@@ -228,20 +229,15 @@ __global__ __launch_bounds__(256) void rle_pack_bits_kernel(const int* __restric
                                                             unsigned* __restrict__ bits, int* __restrict__ area) {
     __shared__ int part[4];
     const int d = blockIdx.y, tid = threadIdx.x;
-    int r0 = run_offset[d], r1 = run_offset[d + 1];
-    if (r0 < 0 || r1 < r0 || r1 > n_runs) r0 = r1 = 0;                      // (a device table that disagrees with the validated copy)
+    int r0, r1;
+    pp_run_slice(run_offset, d, n_runs, r0, r1);                            // (an empty mask for a device table that disagrees with the validated copy)
     const int* ends = run_ends + r0;
     const int m = r1 - r0;
     const int w = blockIdx.x * 256 + tid;
     if (w < words) {
         const long long first = (long long)w * 32;
         const int last = (int)(first + 32 < (long long)hw ? first + 32 : (long long)hw);      // one past the word's last pixel
-        int lo = 0, hi = m;                                                   // ends[0 .. lo) <= first
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (ends[mid] <= (int)first) lo = mid + 1;
-            else hi = mid;
-        }
+        const int lo = pp_count_le(ends, m, (int)first);                      // ends[0 .. lo) <= first
         unsigned word = 0;
         int pos = (int)first;
         for (int k = lo; k < m && pos < last; ++k) {                          // run k covers [pos, ends[k]); odd k: a run of ones
@@ -345,9 +341,7 @@ int pp_rle_pack_bits(const int* run_ends, int n_runs, const int* run_offset, con
     if (!run_ends || !run_offset || !run_offset_host || !bits || !area || n_runs <= 0 || n <= 0 || n > PP_MASK_MAX_N || hw <= 0 ||
         words != (int)(((long long)hw + 31) / 32))
         return PP_EINVAL;
-    if (run_offset_host[0] < 0 || run_offset_host[n] > n_runs) return PP_EINVAL;
-    for (int d = 0; d < n; ++d)
-        if (run_offset_host[d + 1] < run_offset_host[d]) return PP_EINVAL;
+    if (!pp_run_offsets_ok(run_offset_host, n, n_runs)) return PP_EINVAL;
     hipLaunchKernelGGL(rle_pack_bits_kernel, dim3((words + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, run_ends, n_runs,
                        run_offset, hw, words, bits, area);
     return pp_last_launch();

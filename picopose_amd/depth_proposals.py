@@ -20,9 +20,9 @@ import torch
 
 from . import _lib
 from . import scene as scn
+from .masks import MAX_MASKS, RunTable, counts_of_ends
 
 MAX_HYP = 1024          # PP_PLANE_MAX_HYP
-MAX_MASKS = 4096        # PP_MASK_MAX_N
 FIELDS = ("root", "area", "xmin", "ymin", "xmax", "ymax", "border")        # the columns of component_stats' records
 _I32P = ctypes.POINTER(ctypes.c_int)
 
@@ -141,9 +141,9 @@ def component_stats(labels, *, min_area=1, max_area=None, drop_border=False, cap
 
 def component_rle(labels, selection):
     """labels (B, H, W) int32 and selection (n, 6) integers on the host = image, root, xmin, ymin, xmax, ymax (the box must hold the
-    component: component_stats' is) -> (run_ends on the device, run_offset on the device, run_offset on the host, n_runs): each
-    component's cumulative COCO run ends, laid out as proposals._run_tables lays them out, so they feed pp_rle_pack_bits and
-    pp_detections_crop unchanged (pp_components_rle: a count pass, one host read of the counts, an emit pass).
+    component: component_stats' is) -> the masks.RunTable (ends, offset, offset_host, n_runs) of the components' cumulative COCO run
+    ends, so they feed pp_rle_pack_bits and pp_detections_crop unchanged (pp_components_rle: a count pass, one host read of the
+    counts, an emit pass).
     ValueError before any device work: shapes, n outside [1, 4096], an image, root or box outside the frame."""
     B, H, W = _frames("labels", labels, torch.int32)
     sel = np.asarray(selection)
@@ -161,13 +161,11 @@ def component_rle(labels, selection):
                                    counts.data_ptr(), None, _lib.stream_ptr()), "pp_components_rle")
     off = np.zeros(n + 1, np.int32)
     np.cumsum(counts.cpu().numpy(), out=off[1:])
-    n_runs = int(off[-1])
-    words = torch.empty((n_runs + n + 1,), dtype=torch.int32, device=dev)       # ends, then the offsets: one buffer, as _run_tables
-    ends, off_d = words[:n_runs], words[n_runs:]
-    off_d.copy_(torch.from_numpy(off))
-    _lib.check(L.pp_components_rle(labels.data_ptr(), B, H, W, sel_d.data_ptr(), sel.ctypes.data_as(_I32P), n, off_d.data_ptr(),
-                                   off.ctypes.data_as(_I32P), n_runs, None, ends.data_ptr(), _lib.stream_ptr()), "pp_components_rle")
-    return ends, off_d, off, n_runs
+    table = RunTable.from_words(torch.empty((int(off[-1]) + n + 1,), dtype=torch.int32, device=dev), off)
+    table.offset.copy_(torch.from_numpy(off))
+    _lib.check(L.pp_components_rle(labels.data_ptr(), B, H, W, sel_d.data_ptr(), sel.ctypes.data_as(_I32P), n, table.offset.data_ptr(),
+                                   off.ctypes.data_as(_I32P), table.n_runs, None, table.ends.data_ptr(), _lib.stream_ptr()), "pp_components_rle")
+    return table
 
 
 def sort_records(records, max_proposals):
@@ -234,10 +232,9 @@ def depth_proposals(depth, K, *, depth_scale=None, tau=5.0, n_hyp=256, seed=0, m
     for s in range(0, len(flat), MAX_MASKS):                                   # one count and one emit launch per MAX_MASKS components
         part = flat[s:s + MAX_MASKS]
         sel = np.array([[b, r[0], r[2], r[3], r[4], r[5]] for b, r in part], dtype=np.int32)
-        ends, _, off, _ = component_rle(labels, sel)
-        ends = ends.cpu().numpy()
+        table = component_rle(labels, sel)
+        ends, off = table.ends.cpu().numpy(), table.offset_host
         for k, (b, r) in enumerate(part):
-            e = ends[off[k]:off[k + 1]].astype(np.int64)
-            out[b].append({"segmentation": {"size": [H, W], "counts": np.diff(np.concatenate(([0], e))).tolist()},
+            out[b].append({"segmentation": {"size": [H, W], "counts": counts_of_ends(ends[off[k]:off[k + 1]]).tolist()},
                            "bbox": [int(r[2]), int(r[3]), int(r[4] - r[2] + 1), int(r[5] - r[3] + 1)], "area": int(r[1])})
     return out[0] if single else out

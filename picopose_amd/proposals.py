@@ -19,27 +19,12 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .provider.test_batch import _frame_u8, detection_window, rle_area_extent, rle_counts
-from .utils.preprocess import CLIP_MEAN, CLIP_STD
+from .masks import RunTable, check_frame, check_window, rle_area_extent, rle_counts, run_ends
+from .provider.test_batch import _frame_u8, detection_window
 
 NORM_EPS = 1e-12        # pp_descriptor_normalize's floor on the norm
 LN_EPS = 1e-6           # DINOv2's LayerNorm
 _I32P = ctypes.POINTER(ctypes.c_int)
-
-
-def _bad(what, index, msg):
-    raise ValueError(f"{what} {index}: {msg}")
-
-
-def _counts(what, index, segmentation, size):
-    """rle_counts of a mask that must have the frame's size; a ValueError names the mask."""
-    try:
-        counts = rle_counts(segmentation)
-    except ValueError as e:
-        _bad(what, index, str(e))
-    if tuple(int(v) for v in segmentation["size"]) != tuple(size):
-        _bad(what, index, f"mask size {tuple(segmentation['size'])} is not the frame's {tuple(size)}")
-    return counts
 
 
 def _call(name, *args):
@@ -124,25 +109,18 @@ def match_descriptors(query, bank, topk=5):
     return score, view, label, best
 
 
-def _run_tables(runs, device):
-    """Per-mask cumulative run ends -> (ends on the device, run_offset on the device, run_offset on the host, n_runs)."""
-    off = np.zeros(len(runs) + 1, np.int32)
-    np.cumsum([len(r) for r in runs], out=off[1:])
-    words = torch.from_numpy(np.concatenate(list(runs) + [off]).astype(np.int32)).to(device)
-    n_runs = int(off[-1])
-    return words[:n_runs], words[n_runs:], off, n_runs
+def mask_intersections(bits):
+    """bits (n, words) int32 as `masks.RunTable.pack` writes them -> inter (n, n) int32 on the device, inter[i][j] the pixels masks i
+    and j share (pp_mask_intersections)."""
+    n, words = bits.shape
+    inter = torch.empty((n, n), dtype=torch.int32, device=bits.device)
+    _call("pp_mask_intersections", bits.data_ptr(), n, words, inter.data_ptr())
+    return inter
 
 
 def _overlaps_of_runs(runs, hw, device):
-    n, words = len(runs), (hw + 31) // 32
-    ends, off_d, off, n_runs = _run_tables(runs, device)
-    bits = torch.empty((n, words), dtype=torch.int32, device=device)
-    area = torch.empty((n,), dtype=torch.int32, device=device)
-    inter = torch.empty((n, n), dtype=torch.int32, device=device)
-    _call("pp_rle_pack_bits", ends.data_ptr(), n_runs, off_d.data_ptr(), off.ctypes.data_as(_I32P), n, hw, words, bits.data_ptr(),
-          area.data_ptr())
-    _call("pp_mask_intersections", bits.data_ptr(), n, words, inter.data_ptr())
-    return inter, area, bits
+    bits, area = RunTable.upload(runs, device).pack(hw)
+    return mask_intersections(bits), area, bits
 
 
 def mask_overlaps(segmentations, size, device="cuda"):
@@ -152,11 +130,10 @@ def mask_overlaps(segmentations, size, device="cuda"):
     H, W = (int(v) for v in size)
     runs = []
     for i, seg in enumerate(segmentations):
-        runs.append(np.cumsum(_counts("mask", i, seg, (H, W))))
+        runs.append(run_ends(rle_counts(seg, i, "mask", (H, W))))
     if not runs:
         raise ValueError("no masks")
-    if H * W >= 2 ** 31:
-        raise ValueError("frame too large for 32-bit pixel indices")
+    check_frame(H, W)
     return _overlaps_of_runs(runs, H * W, device)[:2]
 
 
@@ -181,16 +158,14 @@ def nms_masks(scores, labels, inter, area, iou, per_object=True):
 
 def _crop(frame, runs, windows, S, rgb_mask_flag, device):
     """One pp_detections_crop launch: the proposals' crops (n, 3, S, S), resized and CLIP-normalised."""
-    n, (H, W) = len(runs), frame.shape[:2]
-    ends, off_d, off, n_runs = _run_tables(runs, device)
+    n = len(runs)
+    table = RunTable.upload(runs, device)
     window = np.ascontiguousarray(windows, dtype=np.int32)
     frame_d = torch.from_numpy(np.ascontiguousarray(frame)).to(device)
     win_d = torch.from_numpy(window.ravel()).to(device)
     rgb = torch.empty((n, 3, S, S), dtype=torch.float32, device=device)
     mask = torch.empty((n, S, S), dtype=torch.float32, device=device)
-    mean, std = (ctypes.c_double * 3)(*CLIP_MEAN), (ctypes.c_double * 3)(*CLIP_STD)
-    _call("pp_detections_crop", frame_d.data_ptr(), H, W, ends.data_ptr(), n_runs, off_d.data_ptr(), win_d.data_ptr(),
-          off.ctypes.data_as(_I32P), window.ctypes.data_as(_I32P), n, S, int(rgb_mask_flag), mean, std, rgb.data_ptr(), mask.data_ptr())
+    table.crop(frame_d, win_d, window, S, rgb_mask_flag, rgb, mask)
     return rgb
 
 
@@ -213,8 +188,7 @@ def label_proposals(net, image_u8, proposals, bank, *, scene_id, img_id, topk=5,
 
     frame = _frame_u8(image_u8)
     H, W = frame.shape[:2]
-    if H * W >= 2 ** 31:
-        raise ValueError("frame too large for 32-bit pixel indices")
+    check_frame(H, W)
     tick = [_time.perf_counter()]
 
     def lap(name):
@@ -229,19 +203,17 @@ def label_proposals(net, image_u8, proposals, bank, *, scene_id, img_id, topk=5,
         try:
             seg = prop["segmentation"]
         except (KeyError, TypeError):
-            _bad("proposal", i, "a proposal is a dict with a 'segmentation'")
-        counts = _counts("proposal", i, seg, (H, W))
+            raise ValueError(f"proposal {i}: a proposal is a dict with a 'segmentation'") from None
+        counts = rle_counts(seg, i, "proposal", (H, W))
         area, extent = rle_area_extent(counts, H)
         if area <= min_area_px or extent is None:
             continue
         rmin, rmax, cmin, cmax = extent
         box = [cmin, rmin, cmax - cmin + 1, rmax - rmin + 1]
         _, win = detection_window(counts, (H, W), prop.get("bbox", box), minimum_n_point)
-        y1, y2, x1, x2 = win
-        if y2 <= y1 or x2 <= x1 or y1 < 0 or x1 < 0 or y2 > H or x2 > W:
-            _bad("proposal", i, f"crop window {win} is empty or leaves the {H}x{W} frame")
+        check_window(win, H, W, i, "proposal")
         idx.append(i)
-        runs.append(np.cumsum(counts))
+        runs.append(run_ends(counts))
         boxes.append(box)
         windows.append(win)
     lap("host")

@@ -4,15 +4,10 @@
 
 File reading (JSON, PNG/JPEG) stays with the caller.  The masks stay run lengths from the record to the kernel: the host
 reads pixel count and extent off the runs, the device tests membership by a search over the cumulative run ends
-(csrc/pp_detect.hip, `pp_detections_crop`); no frame-sized mask is built on either side.  The frame goes up once, the
+(csrc/pp_detect.hip, `pp_detections_crop`); no frame-sized mask is built on either side.  The encoding, its decoder and the
+run tables are masks.py's, and so is the `pp_detections_crop` launch (`RunTable.crop`).  The frame goes up once, the
 small arrays (runs, windows, ids, scores, `M`, `pts2d`, boxes, `K`, poses) in one pinned buffer and one copy; one launch
 crops, resizes and normalises every kept detection into the collated tensors.  Nothing in the call waits for the device.
-
-COCO run-length encoding (pycocotools' `maskApi.c`, restated; pycocotools is not available to pin it): the (h, w) mask is
-walked column by column (Fortran order); `counts` alternate a run of 0s and a run of 1s, starting with a run of 0s that
-may be empty.  The compressed string stores each count as little-endian groups of five bits, one character `chr(48 + c)`
-per group with `c & 0x20` = "another group follows" and bit `0x10` of the last group sign-extending; from the fourth count
-on the stored value is the difference to the count two places before.
 
 Stated differences from the reference:
 - an image whose detections are all at or below `seg_filter_score` gives `None` (the reference raises IndexError at
@@ -20,83 +15,12 @@ Stated differences from the reference:
 - the two `cv2.resize` legs follow OpenCV's published definitions, as for `utils.preprocess.crop_instance`, whose outputs
   this call reproduces bit for bit."""
 import contextlib
-import ctypes
 
 import numpy as np
 import torch
 
-from .. import _lib
-from ..utils.preprocess import CLIP_MEAN, CLIP_STD, _square, get_square_bbox
-
-
-def _fail(index, msg):
-    raise ValueError(f"detection {index}: {msg}" if index is not None else msg)
-
-
-def _counts_from_string(s, index=None):
-    c = np.frombuffer(s.encode("ascii") if isinstance(s, str) else bytes(s), np.uint8).astype(np.int64) - 48
-    if c.size == 0:
-        return np.zeros(0, np.int64)
-    if c.min() < 0 or c.max() > 63:
-        _fail(index, "RLE string holds a character outside chr(48) .. chr(111)")
-    last = (c & 0x20) == 0                                 # the closing group of each count
-    if not last[-1]:
-        _fail(index, "truncated RLE string (the last count announces another group)")
-    ends = np.nonzero(last)[0]
-    start = np.concatenate(([0], ends[:-1] + 1))
-    k = np.arange(c.size) - np.repeat(start, ends - start + 1)
-    if k.max() > 6:
-        _fail(index, "RLE count beyond 32 bits")
-    d = np.add.reduceat((c & 0x1f) << (5 * k), start)
-    neg = (c[ends] & 0x10) != 0
-    d[neg] -= np.int64(1) << (5 * (k[ends][neg] + 1))      # sign extension of the closing group
-    counts = d.copy()                                      # count[m] = d[m] + count[m - 2] for m > 2
-    counts[1::2] = np.cumsum(d[1::2])
-    counts[2::2] = np.cumsum(d[2::2])
-    return counts
-
-
-def rle_counts(segmentation, index=None):
-    """COCO RLE of a CNOS record -> the run lengths as int64: `{"size": [h, w], "counts": ...}` with `counts` a list of ints
-    (uncompressed) or a str / bytes (compressed, module docstring).  ValueError (naming `index` when given) for a negative
-    count, a truncated string or counts that do not sum to h * w."""
-    try:
-        h, w = (int(v) for v in segmentation["size"])
-        raw = segmentation["counts"]
-    except (KeyError, TypeError, ValueError):
-        _fail(index, "segmentation must be {'size': [h, w], 'counts': ...}")
-    if h <= 0 or w <= 0:
-        _fail(index, f"bad mask size {(h, w)}")
-    if isinstance(raw, (str, bytes, bytearray)):
-        counts = _counts_from_string(raw, index)
-    else:
-        counts = np.asarray(raw, dtype=np.int64).reshape(-1)
-    if counts.size and counts.min() < 0:
-        _fail(index, "negative run length")
-    if int(counts.sum()) != h * w:
-        _fail(index, f"run lengths sum to {int(counts.sum())}, the mask has {h} x {w} = {h * w} pixels")
-    return counts
-
-
-def rle_area_extent(counts, h):
-    """From the runs alone, in O(runs): (pixel count, (rmin, rmax, cmin, cmax)) of the mask, the extent inclusive as
-    np.where(np.any(mask, axis))[0][[0, -1]] gives it, None for an empty mask.  A 1-run [s, e] (inclusive column-major
-    indices) covers columns s // h .. e // h, and rows s % h .. e % h if it stays in one column, else all of them."""
-    counts = np.asarray(counts, np.int64)
-    ends = np.cumsum(counts)
-    ones = counts[1::2]
-    keep = ones > 0
-    area = int(ones.sum())
-    if area == 0:
-        return 0, None
-    s = ends[0::2][:ones.size][keep]
-    e = ends[1::2][keep] - 1
-    cs, ce = s // h, e // h
-    if np.any(cs != ce):
-        rmin, rmax = 0, h - 1
-    else:
-        rmin, rmax = int((s - cs * h).min()), int((e - ce * h).max())
-    return area, (rmin, rmax, int(cs[0]), int(ce[-1]))
+from ..masks import RunTable, check_frame, check_window, rle_area_extent, rle_counts, run_ends, run_words
+from ..utils.preprocess import _square, get_square_bbox
 
 
 def detection_window(counts, size, det_bbox_xywh, minimum_n_point=8):
@@ -172,8 +96,7 @@ def assemble_test_image(image_u8, detections, K, obj_idxs, *, scene_id, img_id, 
     malformed, whose mask size is not the image's, or whose crop window is empty."""
     frame = _frame_u8(image_u8)
     H, W = frame.shape[:2]
-    if H * W >= 2 ** 31:
-        raise ValueError("frame too large for 32-bit pixel indices")
+    check_frame(H, W)
     kept, seg_time = select_detections(detections, seg_filter_score)
     if not kept:
         return None
@@ -182,24 +105,20 @@ def assemble_test_image(image_u8, detections, K, obj_idxs, *, scene_id, img_id, 
     runs, bboxes, windows = [], [], []
     for i in kept:
         det = detections[i]
-        counts = rle_counts(det["segmentation"], i)
-        if tuple(int(v) for v in det["segmentation"]["size"]) != (H, W):
-            _fail(i, f"mask size {tuple(det['segmentation']['size'])} is not the image's {(H, W)}")
+        counts = rle_counts(det["segmentation"], i, "detection", (H, W))
         bbox, win = detection_window(counts, (H, W), det["bbox"], minimum_n_point)
-        y1, y2, x1, x2 = win
-        if y2 <= y1 or x2 <= x1 or y1 < 0 or x1 < 0 or y2 > H or x2 > W:
-            _fail(i, f"crop window {win} is empty or leaves the {H}x{W} frame")
-        runs.append(np.cumsum(counts))
+        check_window(win, H, W, i, "detection")
+        runs.append(run_ends(counts))
         bboxes.append(bbox)
         windows.append(win)
     M, pts2d = crop_affines(bboxes, windows, S, P)
-    run_offset = np.zeros(n + 1, np.int32)
-    np.cumsum([len(r) for r in runs], out=run_offset[1:])
+    run_words_h, run_offset = run_words(runs)
     window = np.asarray(windows, np.int32)
-    n_runs = int(run_offset[-1])
+    n_tab = len(run_words_h)
 
-    # ---- one staging buffer of 4-byte words: the int32 tables, then the float32 tensors as torch.FloatTensor(...) rounds them
-    ints = [np.concatenate(runs), run_offset, window.ravel(),
+    # ---- one staging buffer of 4-byte words: the run tables and the other int32 arrays, then the float32 tensors as
+    # torch.FloatTensor(...) rounds them
+    ints = [run_words_h, window.ravel(),
             [int(detections[i]["category_id"]) for i in kept], [int(obj_idxs[detections[i]["category_id"]]) for i in kept],
             [int(scene_id)], [int(img_id)]]
     floats = [np.asarray([detections[i]["score"] for i in kept], np.float32), pts2d.astype(np.float32).ravel(),
@@ -218,14 +137,9 @@ def assemble_test_image(image_u8, detections, K, obj_idxs, *, scene_id, img_id, 
         words = words_h.to(device, non_blocking=True)
         rgb = torch.empty((1, n, 3, S, S), dtype=torch.float32, device=device)
         mask = torch.empty((1, n, S, S), dtype=torch.float32, device=device)
-        d_ends, d_off, d_win = words[:n_runs], words[n_runs:n_runs + n + 1], words[n_runs + n + 1:n_runs + 5 * n + 1]
-        mean, std = (ctypes.c_double * 3)(*CLIP_MEAN), (ctypes.c_double * 3)(*CLIP_STD)
-        i32p = ctypes.POINTER(ctypes.c_int)
-        _lib.check(_lib.lib().pp_detections_crop(frame_d.data_ptr(), H, W, d_ends.data_ptr(), n_runs, d_off.data_ptr(), d_win.data_ptr(),
-                                                 run_offset.ctypes.data_as(i32p), window.ctypes.data_as(i32p), n, S, int(rgb_mask_flag),
-                                                 mean, std, rgb.data_ptr(), mask.data_ptr(), _lib.stream_ptr()), "pp_detections_crop")
+        RunTable.from_words(words, run_offset).crop(frame_d, words[n_tab:n_tab + 4 * n], window, S, rgb_mask_flag, rgb, mask)
     data = {"real_rgb": rgb, "real_mask": mask}
-    o = n_runs + 5 * n + 1
+    o = n_tab + 4 * n
     for k, shape in (("obj_id", (1, n, 1)), ("obj_idx", (1, n, 1)), ("scene_id", (1, 1)), ("img_id", (1, 1))):
         m = int(np.prod(shape))
         data[k] = words[o:o + m].view(shape)

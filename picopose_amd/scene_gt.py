@@ -1,7 +1,7 @@
 """Scene ground truth on the GPU: what BOP's scene_gt_info.json, mask and mask_visib hold, from scene_gt.json, the models and
 (optionally) the test depth images — the per-instance pixel counts, visible fraction, boxes and masks (scene_gt_info), the files'
 schema (format_gt_info, dataset_gt_info), BOP19 targets (targets_from_gt_info) and CNOS-shaped detection records of the ground
-truth (rle_from_mask, gt_detections).
+truth (gt_detections, with masks.rle_from_mask).
 
 The contract is "SCENE GROUND TRUTH" of include/picopose_hip.h (csrc/pp_scene_gt.hip; tests/scene_gt_oracle.py restates it in numpy).
 It is the BOP toolkit's calc_gt_info / calc_gt_masks written from memory: the toolkit cannot be run next to this library, parity
@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from . import scene as scn
+from .masks import rle_from_mask
 from .scene import DEFAULT_WORKSPACE_BYTES
 
 MASKS = (None, "visib", "all", "both")
@@ -273,20 +274,6 @@ def targets_from_gt_info(ground_truth, gt_info, min_visib_fract=0.1):
                     key = (int(s), int(im), int(o))
                     rows[key] = rows.get(key, 0) + 1
     return np.array([k + (n,) for k, n in sorted(rows.items())], dtype=np.int64).reshape(-1, 4)
-
-
-def rle_from_mask(mask):
-    """(H, W) mask (non-zero = set) -> {"size": [H, W], "counts": [...]}: UNCOMPRESSED COCO run lengths, column-major, the first run
-    zeros (0 when the first pixel is set) — what provider.test_batch.rle_counts decodes.  numpy on the host."""
-    m = _np(mask)
-    if m.ndim != 2 or 0 in m.shape:
-        raise ValueError(f"mask must be a non-empty (H, W) array, got shape {m.shape}")
-    flat = (m != 0).ravel(order="F")
-    change = np.flatnonzero(flat[1:] != flat[:-1]) + 1
-    runs = np.diff(np.concatenate(([0], change, [flat.size])))
-    if flat[0]:
-        runs = np.concatenate(([0], runs))
-    return {"size": [int(m.shape[0]), int(m.shape[1])], "counts": [int(r) for r in runs]}
 
 
 def gt_detections(obj_ids, result, scene_id, im_id, score=1.0, time=0.0):

@@ -2,7 +2,7 @@
 the detection's mask and, when there is one, the test depth image.  One raster call and one reduction per group of views.
 
 The contract is "POSE VERIFICATION" of include/picopose_hip.h (csrc/pp_verify.hip; tests/verify_oracle.py restates it in numpy).  The
-masks are bit-packed once per call by pp_rle_pack_bits from the run tables of proposals._run_tables; poses, cameras, windows, groups
+masks are bit-packed once per call by pp_rle_pack_bits from the run tables of masks.py (RunTable.pack); poses, cameras, windows, groups
 and the depth conversion are scene.py's, as for evaluation.render_depth.
 
 THIS IS THE PROJECT'S OWN RULE, not a published protocol's and not the reference's (which ranks hypotheses by the PnP inlier ratio
@@ -17,10 +17,10 @@ import torch
 
 from . import _lib
 from . import scene as scn
+from .masks import MAX_MASKS, RunTable, area_of_ends, rle_counts, run_ends
 from .scene import DEFAULT_WORKSPACE_BYTES
 
 COUNTS = ("render", "inter", "valid", "agree", "front", "behind", "vis", "vis_inter")       # the columns of `counts`
-MAX_MASKS = 4096        # PP_MASK_MAX_N of pp_rle_pack_bits
 _I32P = ctypes.POINTER(ctypes.c_int)
 
 
@@ -65,26 +65,10 @@ def _mask_index(mask_index, P, M):
 
 def _mask_runs(segmentations, H, W):
     """The cumulative run ends of every mask, each checked against the frame; ValueError names the mask."""
-    from .proposals import _counts
-
-    runs = [np.cumsum(_counts("mask", i, seg, (H, W))) for i, seg in enumerate(segmentations)]
+    runs = [run_ends(rle_counts(seg, i, "mask", (H, W))) for i, seg in enumerate(segmentations)]
     if len(runs) > MAX_MASKS:
         raise ValueError(f"at most {MAX_MASKS} masks per call, got {len(runs)}")
     return runs
-
-
-def pack_masks(runs, H, W, device):
-    """_mask_runs' tables (at least one mask) -> (bits (M, words) int32, area (M,) int32) on the device: ONE pp_rle_pack_bits launch,
-    the layout pp_pose_verify reads (bit x * H + y is pixel (x, y))."""
-    from .proposals import _run_tables
-
-    M, words = len(runs), (H * W + 31) // 32
-    ends, off_d, off, n_runs = _run_tables(runs, device)
-    bits = torch.empty((M, words), dtype=torch.int32, device=device)
-    area = torch.empty((M,), dtype=torch.int32, device=device)
-    _lib.check(_lib.lib().pp_rle_pack_bits(ends.data_ptr(), n_runs, off_d.data_ptr(), off.ctypes.data_as(_I32P), M, H * W, words,
-                                           bits.data_ptr(), area.data_ptr(), _lib.stream_ptr()), "pp_rle_pack_bits")
-    return bits, area
 
 
 def verify_poses(models, obj_ids, R, t, K, segmentations, size, mask_index=None, depth=None, image_index=None, depth_scale=None,
@@ -94,7 +78,7 @@ def verify_poses(models, obj_ids, R, t, K, segmentations, size, mask_index=None,
        POSE VERIFICATION), "mask_area": (M,) int32, "iou", "visible_iou", "agreement", "score": (P,) float64 (see `scores`) — device
        tensors; "near_count": the triangles dropped at the near plane, "n_groups": the pp_pose_verify calls made}.
 
-    segmentations: M COCO-RLE masks in any form provider.test_batch.rle_counts accepts, each of `size`; mask_index (P,): the mask of
+    segmentations: M COCO-RLE masks in any form masks.rle_counts accepts, each of `size`; mask_index (P,): the mask of
     each pose, so that the hypotheses of one detection share one mask (default: pose p has mask p, which needs M = P).
     R (P, 3, 3), t (P, 3) millimetres; K (3, 3) or (n_images, 3, 3) with image_index (P,) as evaluation.render_depth.
     depth: None (RGB only: score = iou) or (n_images, H, W) uint16 raw with `depth_scale` or float millimetres, as
@@ -134,7 +118,7 @@ def verify_poses(models, obj_ids, R, t, K, segmentations, size, mask_index=None,
 
     counts = torch.zeros((P, len(COUNTS)), dtype=torch.int32, device=dev)
     if P == 0:                                                    # (the areas from the runs: no launch)
-        area = torch.tensor([int(np.diff(np.concatenate(([0], r)))[1::2].sum()) for r in runs], dtype=torch.int32, device=dev)
+        area = torch.tensor([area_of_ends(r) for r in runs], dtype=torch.int32, device=dev)
         iou, viou, agree, score = scores(counts, area[:0], depth is not None)
         return {"counts": counts, "mask_area": area, "iou": iou, "visible_iou": viou, "agreement": agree, "score": score,
                 "near_count": 0, "n_groups": 0}
@@ -143,7 +127,7 @@ def verify_poses(models, obj_ids, R, t, K, segmentations, size, mask_index=None,
     groups = scn.view_groups(models, obj, windows, None, None, workspace_bytes)
     scn.require_gpu(dev)
     L = _lib.lib()
-    bits, area = pack_masks(runs, H, W, dev)
+    bits, area = RunTable.upload(runs, dev).pack(H * W)
     words = bits.shape[1]
     depth_d = None if depth is None else scn.depth_mm(depth, scale, dev)
     near_d = torch.empty((P,), dtype=torch.int32, device=dev)

@@ -182,21 +182,14 @@ def test_records_and_run_lengths_equal_the_oracle():
         rows = dp.sort_records(recs[b, :n_q[b]], 4096)
         assert [tuple(r) for r in rows.tolist()] == do.qualifying(st[b], 1, H * W, False)           # area descending, then root
         sel = np.concatenate([np.full((len(rows), 1), b, np.int32), rows[:, [0, 2, 3, 4, 5]]], axis=1)
-        ends, off_d, off, n_runs = dp.component_rle(labels, sel)
+        table = dp.component_rle(labels, sel)
+        ends, off_d, off, n_runs = table
         ends_h = ends.cpu().numpy()
         assert off[-1] == n_runs == len(ends_h) and np.array_equal(off_d.cpu().numpy(), off)
         for k, r in enumerate(rows):
             assert np.array_equal(ends_h[off[k]:off[k + 1]], do.run_ends(want_lab[b], int(r[0]))), (names[b], r.tolist())
-        # the device's tables feed pp_rle_pack_bits as proposals._run_tables' do: the packed areas are the records'
-        import ctypes
-
-        from picopose_amd import _lib
-
-        words = (H * W + 31) // 32
-        bits = torch.empty((len(rows), words), dtype=torch.int32, device="cuda")
-        area = torch.empty((len(rows),), dtype=torch.int32, device="cuda")
-        _lib.check(_lib.lib().pp_rle_pack_bits(ends.data_ptr(), n_runs, off_d.data_ptr(), off.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(rows),
-                                               H * W, words, bits.data_ptr(), area.data_ptr(), _lib.stream_ptr()), "pp_rle_pack_bits")
+        # the device's tables feed pp_rle_pack_bits as uploaded ones do: the packed areas are the records'
+        bits, area = table.pack(H * W)
         assert np.array_equal(area.cpu().numpy(), rows[:, 1])
 
 

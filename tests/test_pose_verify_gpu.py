@@ -22,6 +22,7 @@ from picopose_amd import pipeline as pl  # noqa: E402
 from picopose_amd import scene as scn  # noqa: E402
 from picopose_amd import scene_gt as sg  # noqa: E402
 from picopose_amd import verify as vf  # noqa: E402  (absent before the feature: every test here fails without it)
+from picopose_amd.masks import RunTable, rle_counts, run_ends  # noqa: E402
 
 gpu = pytest.mark.gpu
 F = np.float32
@@ -176,7 +177,7 @@ def test_the_entry_through_the_abi_clears_its_outputs_and_equals_the_oracle(name
     L, need = _lib.lib(), ctypes.c_size_t()
     _lib.check(L.pp_vsd_workspace_bytes(packed.samples, packed.faces, ctypes.byref(need)), "pp_vsd_workspace_bytes")
     ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-    bits, area = vf.pack_masks(vf._mask_runs(s["segs"], H, W), H, W, dev)
+    bits, area = RunTable.upload([run_ends(rle_counts(seg, size=(H, W))) for seg in s["segs"]], dev).pack(H * W)
     vm = np.ascontiguousarray(s["mask_index"], dtype=np.int32)
     vm_d = torch.from_numpy(vm).to(dev)
     depth = torch.from_numpy(np.ascontiguousarray(s["depth"], dtype=F)).to(dev)

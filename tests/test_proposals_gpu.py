@@ -13,6 +13,7 @@ import proposal_oracle as po  # noqa: E402
 from netcfg import make_end_points, small_cfg  # noqa: E402
 
 from picopose_amd import proposals as pr  # noqa: E402
+from picopose_amd.masks import RunTable  # noqa: E402
 
 gpu = pytest.mark.gpu
 
@@ -99,7 +100,8 @@ def test_mask_bits_and_intersections_equal_the_oracle(size, n):
     H, W = size
     segs = [po.rle_of(m) for m in po.mask_set(H, W, n)]
     runs = [np.cumsum(np.asarray(s["counts"], np.int64)) for s in segs]
-    inter, area, bits = pr._overlaps_of_runs(runs, H * W, "cuda")
+    bits, area = RunTable.upload(runs, "cuda").pack(H * W)
+    inter = pr.mask_intersections(bits)
     want_bits, want_area = po.pack_bits(segs)
     assert np.array_equal(bits.cpu().numpy().view(np.uint32), want_bits)
     assert np.array_equal(area.cpu().numpy(), want_area)

@@ -22,6 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import detections_oracle as do  # noqa: E402
 
+from picopose_amd import masks  # noqa: E402
 from picopose_amd import proposals as pr  # noqa: E402
 
 
@@ -77,14 +78,11 @@ def bench_overlaps(iters, burst, n=100, H=480, W=640):
     rng = np.random.default_rng(2)
     recs = [do.record(do.blob(rng, H, W, holes=0.1 if j % 10 == 9 else 0.0), 0.5, 1) for j in range(n)]
     segs = [r["segmentation"] for r in recs]
-    runs = [np.cumsum(pr.rle_counts(s)) for s in segs]
-    ends, off_d, off, n_runs = pr._run_tables(runs, "cuda")
-    words = (H * W + 31) // 32
-    bits = torch.empty((n, words), dtype=torch.int32, device="cuda")
-    area = torch.empty((n,), dtype=torch.int32, device="cuda")
+    table = masks.RunTable.upload([masks.run_ends(masks.rle_counts(s)) for s in segs], "cuda")
+    pack = lambda: table.pack(H * W)  # noqa: E731  (the launch and its two output allocations, as every caller has it)
+    bits, _ = pack()
+    words, n_runs = bits.shape[1], table.n_runs
     inter = torch.empty((n, n), dtype=torch.int32, device="cuda")
-    offp = off.ctypes.data_as(pr._I32P)
-    pack = lambda: pr._call("pp_rle_pack_bits", ends.data_ptr(), n_runs, off_d.data_ptr(), offp, n, H * W, words, bits.data_ptr(), area.data_ptr())  # noqa: E731
     sect = lambda: pr._call("pp_mask_intersections", bits.data_ptr(), n, words, inter.data_ptr())  # noqa: E731
     for _ in range(3):
         burst_ms(pack, burst), burst_ms(sect, burst)

@@ -27,6 +27,7 @@ import render_oracle as ro  # noqa: E402  (mesh generator only)
 
 from picopose_amd import _lib  # noqa: E402
 from picopose_amd import evaluation as ev  # noqa: E402
+from picopose_amd import masks  # noqa: E402
 from picopose_amd import scene as scn  # noqa: E402
 from picopose_amd import scene_gt as sg  # noqa: E402
 from picopose_amd import verify as vf  # noqa: E402
@@ -94,7 +95,7 @@ def abi_calls(models, U, window, a):
     L, need = _lib.lib(), ctypes.c_size_t()
     _lib.check(L.pp_vsd_workspace_bytes(packed.samples, packed.faces, ctypes.byref(need)), "pp_vsd_workspace_bytes")
     ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-    bits, _ = vf.pack_masks(vf._mask_runs(segs, H, W), H, W, dev)
+    bits, _ = masks.RunTable.upload([masks.run_ends(masks.rle_counts(s, size=(H, W))) for s in segs], dev).pack(H * W)
     words, i32p = bits.shape[1], ctypes.POINTER(ctypes.c_int)
     vm = np.arange(U, dtype=np.int32)
     vm_d = torch.from_numpy(vm).to(dev)
