@@ -1639,6 +1639,91 @@ int pp_component_stats(const int* labels, int B, int H, int W, int min_area, int
 int pp_components_rle(const int* labels, int B, int H, int W, const int* sel, const int* sel_host, int n, const int* run_offset,
                       const int* run_offset_host, int n_runs_total, int* n_runs, int* run_ends, void* stream);
 
+/* -------------------------------------------------------------------------
+ * DETECTION SCORING: COCO-style average precision and recall of 2D detections and masks — what BOP's detection and segmentation
+ * tasks are scored by (csrc/pp_det_eval.hip; picopose_amd/detection_eval.py plans every call and accumulates on the host;
+ * tests/detection_eval_oracle.py restates this text in numpy loops; every device output equals it bit for bit).  The protocol is
+ * COCOeval AS REMEMBERED: neither pycocotools nor the BOP toolkit's eval_bop22_coco.py can be run next to this library, so parity
+ * with both is UNPINNED.  All pointers are device pointers unless named *_host; all work is enqueued on `stream`, nothing
+ * synchronises; no entry uses atomics or accumulates in floating point.
+ *
+ * RECORDS.  A detection is a CNOS record: scene_id, image_id, category_id, bbox [x, y, w, h], score, segmentation (COCO RLE).  A
+ * ground-truth annotation is the same record without a score, plus ignore (bool) and iscrowd (bool, default false); its area is the
+ * pixel count of its mask.  A crowd annotation is ignored as well (COCOeval's _prepare as remembered; the Python layer sets the flag,
+ * the kernels take the two flags as given).  iou_type is "segm" or "bbox".  An image is one (scene_id, image_id); a GROUP is one
+ * (image, category).
+ *
+ * ORDER WITHIN A GROUP.  Detections are sorted by descending score, stably (the lower input index first among equal scores), and cut
+ * to the largest max_dets (default (1, 10, 100)).  For each area range [lo, hi] a ground truth is IGNORED if its ignore flag is set
+ * or its area is < lo or > hi; the ground truths are ordered with the non-ignored ones first, stably.
+ *
+ * OVERLAP.  segm, from pixel counts: iou = inter / (area_d + area_g - inter); for a crowd ground truth inter / area_d.  bbox, in
+ * float64, one rounding per operation, never contracted: iw = max(0, min(xd + wd, xg + wg) - max(xd, xg)), ih likewise,
+ * iou = (iw ih) / ((wd hd + wg hg) - iw ih); for a crowd ground truth the denominator is wd hd.  Every IoU is ONE IEEE float64
+ * division; a denominator that is not positive gives 0.
+ *
+ * MATCHING, per group, area range and threshold t of iou_thrs (default np.linspace(.5, .95, 10)), the detections visited in order:
+ * best = min(t, 1 - 1e-10), m = -1; the ground truths are scanned in group order: one that is already matched at this t is skipped
+ * unless it is a crowd; the scan stops if m >= 0, m is not ignored and this ground truth is ignored; one with iou < best is skipped;
+ * otherwise best = iou, m = this.  If m >= 0 the detection is matched, takes m's ignore flag, and m is marked matched.  An unmatched
+ * detection whose own area (the mask area for segm, w h for bbox) lies outside [lo, hi] is ignored.
+ * THE CLOSED FORM (what pp_det_match computes): the winner is the largest IoU >= min(t, 1 - 1e-10) among the eligible (unmatched, or
+ * crowd) NON-IGNORED ground truths, on equal IoU the LAST one in group order; only if no non-ignored one qualifies does the same
+ * rule apply among the ignored ones.  Inside each class the group order is the input order, so "last" is the highest input index:
+ * the group order is computed in the wave, implicitly — it is never materialised and the host hands none in.
+ *
+ * ACCUMULATION is the host's, numpy float64 (detection_eval.accumulate states it): per category, area range and max_dets value the
+ * first max_det detections of every image are concatenated and sorted by descending score (mergesort); tp / fp are cumulative sums
+ * of (matched / unmatched) and not ignored; rc = tp / npig, pr = tp / (tp + fp + spacing(1)); recall = rc[-1]; pr is made
+ * non-increasing from the right and sampled at the 101 recalls np.linspace(0, 1, 101) by searchsorted(rc, r, "left").  A cell
+ * without a non-ignored ground truth stays -1; a summary is the mean of the cells > -1.
+ *
+ * THE TABLES OF A CALL.  n_det detections and n_gt ground truths, each side with its groups contiguous: the detections in group-sorted
+ * order (sorted and cut by the host), the ground truths in the order the annotations were given.  groups (n_groups,
+ * PP_DET_GROUP_FIELDS) int32 with a host copy = {first detection, D_g, first ground truth, G_g, offset of the group's block}: the
+ * block is D_g x G_g row-major (detection-major) inside the ragged arrays of n_pairs entries.  An empty side (D_g = 0 or G_g = 0) is
+ * legal.  gt_flags (n_gt) uint8: PP_DET_GT_IGNORE | PP_DET_GT_CROWD.
+ *
+ * pp_det_overlaps.  segm: bits (n_det + n_gt, words) uint32 and area (n_det + n_gt) int32 as pp_rle_pack_bits writes them for the
+ * chunk's frame, the detections' rows first; boxes NULL.  bbox: boxes (n_det + n_gt, 4) float64 {x, y, w, h}, the detections' rows
+ * first, finite with w, h >= 0 (the caller's contract); bits, area and inter NULL.  tiles (n_tiles, 3) int32 with a host copy =
+ * {group, first detection of the tile within the group, first ground truth within the group}, both multiples of PP_DET_TILE and
+ * inside the group: the host lists the tiles that hold a pair, one workgroup each.  Outputs: inter (n_pairs) int32 (segm) and iou
+ * (n_pairs) float64.  segm stages 64 words of the tile's 8 + 8 rows per step in LDS, the rows 68 words apart, four threads per pair
+ * (pp_mask_intersections' staging).  No pair outside a group is computed, and there is no cap on the pairs or the masks: only the
+ * pp_rle_pack_bits call that produced `bits` is capped, and the Python layer chunks for it.  n_tiles = 0: no launch.
+ * PP_EINVAL (before any launch, no GPU needed): a null groups, groups_host, gt_flags or iou; both or neither of bits and boxes;
+ * segm with a null area or inter or words <= 0; n_det, n_gt, n_tiles or n_pairs negative; n_groups <= 0; tiles without both copies;
+ * a groups_host row with a negative field, a range past n_det / n_gt or a block past n_pairs; a tiles_host row with a group outside
+ * [0, n_groups), a start that is negative, no multiple of PP_DET_TILE or outside the group.
+ *
+ * pp_det_match.  iou as above; det_area (n_det) and gt_area (n_gt) float64; area_ranges (A, 2) and iou_thrs (T) float64, each
+ * with a host copy.  One wave per (group, area range, threshold): the detections are walked in order, the group's ground truths are
+ * spread over the lanes (j = lane + 64 k), the matched, ignore and crowd flags of a lane's ground truths are bits of three 64-bit
+ * registers (hence G_g <= PP_DET_MAX_GT), and the winner under THE CLOSED FORM is found by two wave reductions (the largest IoU bit
+ * pattern, then the highest index that holds it), the non-ignored class first.  Outputs, the detection axis in the call's (group-
+ * sorted) order and the ground-truth axis in the call's (input) order:
+ *   dt_match  (A, T, n_det) int32  the call-wide index of the matched ground truth, or -1;
+ *   dt_ignore (A, T, n_det) uint8  the matched ground truth's ignore flag; unmatched: area outside [lo, hi];
+ *   gt_match  (A, T, n_gt)  int32  the call-wide index of the detection matched to it (the last one, for a crowd), or -1;
+ *   gt_ignore (A, n_gt)     uint8.
+ * Every element of a group of the table is written; detections and ground truths outside every group are not.
+ * PP_EINVAL (before the launch, no GPU needed): a null pointer; n_pairs, n_det or n_gt negative; n_groups, A or T <= 0; a
+ * threshold outside (0, 1] or NaN; an area range with lo > hi or a NaN; the groups_host checks above; G_g > PP_DET_MAX_GT.
+ * ------------------------------------------------------------------------- */
+#define PP_DET_GROUP_FIELDS 5
+#define PP_DET_TILE 8
+#define PP_DET_MAX_GT 4096
+#define PP_DET_GT_IGNORE 1
+#define PP_DET_GT_CROWD 2
+int pp_det_overlaps(const unsigned* bits, const int* area, int words, const double* boxes, int n_det, int n_gt, const int* groups,
+                    const int* groups_host, int n_groups, const int* tiles, const int* tiles_host, int n_tiles,
+                    const unsigned char* gt_flags, int n_pairs, int* inter, double* iou, void* stream);
+int pp_det_match(const double* iou, int n_pairs, const int* groups, const int* groups_host, int n_groups, int n_det, int n_gt,
+                 const double* det_area, const double* gt_area, const unsigned char* gt_flags, const double* area_ranges,
+                 const double* area_ranges_host, int A, const double* iou_thrs, const double* iou_thrs_host, int T, int* dt_match,
+                 unsigned char* dt_ignore, int* gt_match, unsigned char* gt_ignore, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

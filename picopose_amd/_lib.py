@@ -269,6 +269,9 @@ def lib():
         L.pp_component_stats_workspace_bytes.argtypes = [i32, i32, i32, c.POINTER(sz)]
         L.pp_component_stats.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, vp, vp]
         L.pp_components_rle.argtypes = [vp, i32, i32, i32, vp, c.POINTER(i32), i32, vp, c.POINTER(i32), i32, vp, vp, vp]
+        f64p = c.POINTER(c.c_double)
+        L.pp_det_overlaps.argtypes = [vp, vp, i32, vp, i32, i32, vp, c.POINTER(i32), i32, vp, c.POINTER(i32), i32, vp, i32, vp, vp, vp]
+        L.pp_det_match.argtypes = [vp, i32, vp, c.POINTER(i32), i32, i32, i32, vp, vp, vp, vp, f64p, i32, vp, f64p, i32, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 

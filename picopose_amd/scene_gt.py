@@ -219,15 +219,13 @@ def format_gt_info(result):
              "px_count_visib": int(ns[k]), "visib_fract": float(fr[k])} for k in range(len(fr))]
 
 
-def dataset_gt_info(ground_truth, cameras, models, resolution, depth_images=None, images_per_call=64, **kw):
-    """scene_gt_info.json for whole scenes.  ground_truth / cameras: {scene_id: read_scene_gt(...) / read_scene_camera(...)} and
-    depth_images as evaluation.match_and_score takes them ({scene_id: {im_id: (H, W) array}} or a callable (scene_id, im_id) -> array;
-    raw values scaled by the camera's depth_scale; None: composite visibility).  One scene_gt_info call per `images_per_call` images
-    (kw goes to it) -> {scene_id: {im_id: [info dicts in instance order]}} (format_gt_info's dicts)."""
+def dataset_gt_batches(ground_truth, cameras, models, resolution, depth_images=None, images_per_call=64, **kw):
+    """The batching of `dataset_gt_info`: one scene_gt_info call (kw goes to it) per `images_per_call` images -> yields (batch, obj,
+    result): batch = the [(scene_id, im_id)] of the call, obj = the object ids of each image's instances (one array per image), result =
+    scene_gt_info's for the concatenated instances, image after image."""
     if not (isinstance(images_per_call, int) and images_per_call > 0):
         raise ValueError(f"images_per_call must be a positive int, got {images_per_call!r}")
     images = [(int(s), int(im)) for s, per in ground_truth.items() for im in per]
-    out = {int(s): {} for s in ground_truth}
     for b0 in range(0, len(images), images_per_call):
         batch = images[b0:b0 + images_per_call]
         obj, R, t, idx, Kb = [], [], [], [], []
@@ -250,8 +248,17 @@ def dataset_gt_info(ground_truth, cameras, models, resolution, depth_images=None
                 depth, depth_scale = np.stack(frames), scale
             else:
                 depth = np.stack([f.astype(np.float32) * np.float32(sc) for f, sc in zip(frames, scale)])
-        r = scene_gt_info(models, np.concatenate(obj), np.concatenate(R), np.concatenate(t), np.stack(Kb), depth=depth,
-                          resolution=resolution, image_index=np.concatenate(idx), depth_scale=depth_scale, **kw)
+        yield batch, obj, scene_gt_info(models, np.concatenate(obj), np.concatenate(R), np.concatenate(t), np.stack(Kb), depth=depth,
+                                        resolution=resolution, image_index=np.concatenate(idx), depth_scale=depth_scale, **kw)
+
+
+def dataset_gt_info(ground_truth, cameras, models, resolution, depth_images=None, images_per_call=64, **kw):
+    """scene_gt_info.json for whole scenes.  ground_truth / cameras: {scene_id: read_scene_gt(...) / read_scene_camera(...)} and
+    depth_images as evaluation.match_and_score takes them ({scene_id: {im_id: (H, W) array}} or a callable (scene_id, im_id) -> array;
+    raw values scaled by the camera's depth_scale; None: composite visibility).  One scene_gt_info call per `images_per_call` images
+    (kw goes to it) -> {scene_id: {im_id: [info dicts in instance order]}} (format_gt_info's dicts)."""
+    out = {int(s): {} for s in ground_truth}
+    for batch, obj, r in dataset_gt_batches(ground_truth, cameras, models, resolution, depth_images, images_per_call, **kw):
         info, k = format_gt_info(r), 0
         for (s, im), o in zip(batch, obj):
             out[s][im] = info[k:k + len(o)]
