@@ -808,6 +808,8 @@ typedef struct PpAdamTensor {
     float* scale2;     /* [2^e, 2^-e] of that split (NULL when hl is NULL)                                       */
     long long n;
 } PpAdamTensor;
+/* PpAdamStep arrays live in DEVICE memory: the Python binding passes `steps` as a raw address (picopose_amd/_lib.py _DEVICE_STRUCTS
+ * names the struct; a further device-resident struct is added there). */
 typedef struct PpAdamStep {
     const float* g;    /* gradient (n,) contiguous fp32 (may move between steps)                                 */
     float neg_step_size, inv_bc2_sqrt, decay, lerp_w, beta2, one_minus_beta2, eps;

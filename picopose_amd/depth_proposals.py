@@ -22,7 +22,7 @@ from . import _lib
 from . import scene as scn
 from .masks import MAX_MASKS, RunTable, counts_of_ends
 
-MAX_HYP = 1024          # PP_PLANE_MAX_HYP
+MAX_HYP = _lib.PP_PLANE_MAX_HYP
 FIELDS = ("root", "area", "xmin", "ymin", "xmax", "ymax", "border")        # the columns of component_stats' records
 _I32P = ctypes.POINTER(ctypes.c_int)
 
@@ -64,12 +64,6 @@ def _device_tensors(*tensors):
     return [t.contiguous() for t in tensors]
 
 
-def _workspace(query, *args):
-    need = ctypes.c_size_t()
-    _lib.check(getattr(_lib.lib(), query)(*args, ctypes.byref(need)), query)
-    return need.value
-
-
 def plane_fit(depth, cams, *, tau=5.0, n_hyp=256, seed=0, min_inliers=1000):
     """depth (B, H, W) float32 millimetres and cams (B, 4) float32 {fx, fy, cx, cy}, both on the device -> {"plane": (B, 4) float32
     (n, d) with n . p + d = 0 and the camera on the positive side, "plane64": the float64 fit it is the cast of, "info": (B, 4) int32 =
@@ -83,7 +77,7 @@ def plane_fit(depth, cams, *, tau=5.0, n_hyp=256, seed=0, min_inliers=1000):
     n_hyp, seed, min_inliers = _integer("n_hyp", n_hyp, 1, MAX_HYP), _integer("seed", seed, 0, 2 ** 32 - 1), _integer("min_inliers", min_inliers, 3, 2 ** 31 - 1)
     depth, cams = _device_tensors(depth, cams)
     dev = depth.device
-    ws = torch.empty(_workspace("pp_depth_plane_workspace_bytes", B, H, W, n_hyp), dtype=torch.uint8, device=dev)
+    ws = torch.empty(_lib.workspace_bytes("pp_depth_plane_workspace_bytes", B, H, W, n_hyp), dtype=torch.uint8, device=dev)
     plane = torch.empty((B, 4), dtype=torch.float32, device=dev)
     plane64 = torch.empty((B, 4), dtype=torch.float64, device=dev)
     info = torch.empty((B, 4), dtype=torch.int32, device=dev)
@@ -110,7 +104,7 @@ def components(depth, cams, plane, has_plane, *, min_height=10.0, max_height=400
     if H > 32 * 65535:
         raise ValueError("frames of more than 32 * 65535 rows are not supported")
     depth, cams, plane, has_plane = _device_tensors(depth, cams, plane, has_plane)
-    nbytes = _workspace("pp_depth_components_workspace_bytes", B, H, W)
+    nbytes = _lib.workspace_bytes("pp_depth_components_workspace_bytes", B, H, W)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=depth.device) if nbytes else None
     labels = torch.empty((B, H, W), dtype=torch.int32, device=depth.device)
     _lib.check(_lib.lib().pp_depth_components(depth.data_ptr(), cams.data_ptr(), plane.data_ptr(), has_plane.data_ptr(), B, H, W, lo, hi,
@@ -131,7 +125,7 @@ def component_stats(labels, *, min_area=1, max_area=None, drop_border=False, cap
     cap = _integer("cap", cap, 1, 2 ** 24)
     (labels,) = _device_tensors(labels)
     dev = labels.device
-    ws = torch.empty(_workspace("pp_component_stats_workspace_bytes", B, H, W), dtype=torch.uint8, device=dev)
+    ws = torch.empty(_lib.workspace_bytes("pp_component_stats_workspace_bytes", B, H, W), dtype=torch.uint8, device=dev)
     n_q = torch.empty((B,), dtype=torch.int32, device=dev)
     recs = torch.empty((B, cap, len(FIELDS)), dtype=torch.int32, device=dev)
     _lib.check(_lib.lib().pp_component_stats(labels.data_ptr(), B, H, W, min_area, max_area, int(bool(drop_border)), cap, ws.data_ptr(),

@@ -22,9 +22,9 @@ from . import _lib
 from . import scene as scn
 from .scene import DEFAULT_WORKSPACE_BYTES
 
-STRIP_ROWS = 8                                                    # PP_DEPTH_REFINE_STRIP_ROWS
-N_SUMS = 29                                                       # PP_DEPTH_REFINE_SUMS
-MAX_ITERATIONS = 1000                                             # PP_DEPTH_REFINE_MAX_ITERATIONS
+STRIP_ROWS = _lib.PP_DEPTH_REFINE_STRIP_ROWS
+N_SUMS = _lib.PP_DEPTH_REFINE_SUMS
+MAX_ITERATIONS = _lib.PP_DEPTH_REFINE_MAX_ITERATIONS
 STATUS = {0: "converged", 1: "iteration limit", 2: "too few points", 3: "correction out of bounds", 4: "invalid pose or empty window"}
 
 
@@ -139,14 +139,12 @@ def refine_poses_depth(models, obj_ids, R, t, K, depth, image_index=None, depth_
     boxes = _boxes(models)
     boxes_d = torch.from_numpy(boxes).to(dev)
     near_all, active = i32(P), i32(P)
-    need = ctypes.c_size_t()
     for views in groups:
         v0 = int(views[0])                                        # (consecutive poses)
         packed = scn.PackedScene(models, cams, H, W, near, obj[views], img[views], poses[views], windows[views])
         soff = strip_offsets(packed.windows)
-        _lib.check(L.pp_depth_refine_workspace_bytes(packed.samples, packed.faces, int(soff[-1]), ctypes.byref(need)),
-                   "pp_depth_refine_workspace_bytes")
-        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        need = _lib.workspace_bytes("pp_depth_refine_workspace_bytes", packed.samples, packed.faces, int(soff[-1]))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
         soff_d = torch.from_numpy(soff).to(dev)
         at = lambda a, width: a.data_ptr() + v0 * width              # noqa: E731
         opt = lambda key, width: at(out[key], width) if debug else None    # noqa: E731

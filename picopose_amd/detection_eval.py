@@ -28,8 +28,8 @@ MAX_DETS = (1, 10, 100)
 REC_THRS = np.linspace(0, 1, 101)
 NAMES = ("AP", "AP50", "AP75", "APs", "APm", "APl", "AR1", "AR10", "AR100", "ARs", "ARm", "ARl")
 DEFAULT_WORKSPACE_BYTES = 256 << 20
-TILE = 8                # PP_DET_TILE
-MAX_GT = 4096           # PP_DET_MAX_GT
+TILE = _lib.PP_DET_TILE
+MAX_GT = _lib.PP_DET_MAX_GT
 GT_IGNORE, GT_CROWD = 1, 2
 _I32P = ctypes.POINTER(ctypes.c_int)
 _F64P = ctypes.POINTER(ctypes.c_double)

@@ -38,12 +38,12 @@ from . import _lib
 from . import scene as scn
 from .scene import DEFAULT_WORKSPACE_BYTES, plan_window  # noqa: F401  (documented names of this module)
 
-KINDS = {"mssd": 1, "mspd": 2, "add": 4, "adds": 8}             # PP_EVAL_* of include/picopose_hip.h
+KINDS = {"mssd": _lib.PP_EVAL_MSSD, "mspd": _lib.PP_EVAL_MSPD, "add": _lib.PP_EVAL_ADD, "adds": _lib.PP_EVAL_ADDS}
 MSSD_THRESHOLDS = np.arange(1, 11) / 20.0                       # 0.05 .. 0.5 of the object diameter
 MSPD_THRESHOLDS = np.arange(1, 11) * 5.0                        # 5 r .. 50 r pixels, r = image_width / 640
 VSD_TAUS = np.arange(1, 11) / 20.0                              # misalignment tolerances, 0.05 .. 0.5 of the object diameter
 VSD_THRESHOLDS = np.arange(1, 11) / 20.0                        # a pair is correct at (tau, theta) when e_tau < theta
-VSD_MAX_TAUS = 16                                               # PP_VSD_MAX_TAUS
+VSD_MAX_TAUS = _lib.PP_VSD_MAX_TAUS
 
 
 def _rotation(axis, angle):
@@ -192,15 +192,12 @@ class ObjectModels:
 
 def _plan_chunks(models, pair_obj, mask, workspace_bytes):
     """-> (pairs per launch sequence, bytes of the workspace for that many) under the bound `workspace_bytes` (at least one pair)."""
-    L = _lib.lib()
     ns = (models.sym_off[1:] - models.sym_off[:-1])[pair_obj]
     na = (models.adds_off[1:] - models.adds_off[:-1])[pair_obj]
     S_max, A_max = int(ns.max()), int(na.max())
-    need = ctypes.c_size_t()
-    _lib.check(L.pp_pose_errors_workspace_bytes(1, S_max, A_max, mask, ctypes.byref(need)), "pp_pose_errors_workspace_bytes")
-    chunk = max(1, min(len(pair_obj), int(workspace_bytes) // need.value, (2 ** 31 - 1) // S_max))
-    _lib.check(L.pp_pose_errors_workspace_bytes(chunk, S_max, A_max, mask, ctypes.byref(need)), "pp_pose_errors_workspace_bytes")
-    return chunk, int(need.value)
+    one = _lib.workspace_bytes("pp_pose_errors_workspace_bytes", 1, S_max, A_max, mask)
+    chunk = max(1, min(len(pair_obj), int(workspace_bytes) // one, (2 ** 31 - 1) // S_max))
+    return chunk, _lib.workspace_bytes("pp_pose_errors_workspace_bytes", chunk, S_max, A_max, mask)
 
 
 def pose_error_chunks(models, obj_ids, kinds=("mssd", "mspd"), workspace_bytes=DEFAULT_WORKSPACE_BYTES):
@@ -298,11 +295,9 @@ def _vsd_launch(models, cams, H, W, view_obj, view_img, poses, windows, groups, 
     counts = torch.empty((P, 2 + T), dtype=torch.int32, device=dev)
     near_all = torch.zeros(U, dtype=torch.int32, device=dev)
     dense = torch.empty((U, H, W), dtype=torch.float32, device=dev) if want_depth else None
-    need = ctypes.c_size_t()
     for views, pairs in groups:
         packed = scn.PackedScene(models, cams, H, W, near, view_obj[views], view_img[views], poses[views], windows[views])
-        _lib.check(L.pp_vsd_workspace_bytes(packed.samples, packed.faces, ctypes.byref(need)), "pp_vsd_workspace_bytes")
-        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        ws = torch.empty(_lib.workspace_bytes("pp_vsd_workspace_bytes", packed.samples, packed.faces), dtype=torch.uint8, device=dev)
         near_d = torch.empty(len(views), dtype=torch.int32, device=dev)
         pe = pg = pe_d = pg_d = vsd_ptr = counts_ptr = dense_ptr = None
         n_pairs = 0

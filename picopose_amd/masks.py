@@ -21,7 +21,7 @@ import torch
 from . import _lib
 from .utils.preprocess import CLIP_MEAN, CLIP_STD
 
-MAX_MASKS = 4096        # PP_MASK_MAX_N: the masks of one pp_rle_pack_bits, pp_mask_intersections or pp_components_rle call
+MAX_MASKS = _lib.PP_MASK_MAX_N       # the masks of one pp_rle_pack_bits, pp_mask_intersections or pp_components_rle call
 _I32P = ctypes.POINTER(ctypes.c_int)
 
 

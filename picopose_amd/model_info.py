@@ -16,7 +16,6 @@ The symmetry search (find_symmetries) is a deterministic rule planned on the hos
 CANDIDATES UNDER A TOLERANCE, in models_info.json's shapes.  Two limits: only rotations are searched, so a mirror symmetry is not
 found; and only the geometry is looked at, so a part whose symmetry is broken by its texture is reported symmetric.  It replaces
 what the BOP toolkit's calc_models_info.py computes (diameter and bounds); parity with the toolkit is unpinned.  Millimetres."""
-import ctypes
 import json
 import math
 from fractions import Fraction
@@ -111,11 +110,10 @@ def _diameters(verts, device="cuda"):
 
     dev, L = _device(device), _lib.lib()
     off = _offsets(verts)
-    need = ctypes.c_size_t()
-    _lib.check(L.pp_model_diameter_workspace_bytes(off.ctypes.data, len(verts), ctypes.byref(need)), "pp_model_diameter_workspace_bytes")
+    need = _lib.workspace_bytes("pp_model_diameter_workspace_bytes", off.ctypes.data, len(verts))
     with torch.cuda.device(dev):
         v_d, off_d = torch.from_numpy(np.concatenate(verts)).to(dev), torch.from_numpy(off).to(dev)
-        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
         d2 = torch.empty(len(verts), dtype=torch.float32, device=dev)
         pair = torch.empty((len(verts), 2), dtype=torch.int32, device=dev)
         _lib.check(L.pp_model_diameter(v_d.data_ptr(), off_d.data_ptr(), off.ctypes.data, len(verts), ws.data_ptr(), ws.numel(),
@@ -150,14 +148,13 @@ def _hausdorff(verts, queries, cand_obj, T12, workspace_bytes=DEFAULT_WORKSPACE_
     v_off, q_off = _offsets(verts), _offsets(queries)
     nq_max = int((q_off[1:] - q_off[:-1])[cand_obj].max())
     group = hausdorff_group_size(C, nq_max, workspace_bytes)
-    need = ctypes.c_size_t()
-    _lib.check(L.pp_transform_hausdorff_workspace_bytes(group, nq_max, ctypes.byref(need)), "pp_transform_hausdorff_workspace_bytes")
+    need = _lib.workspace_bytes("pp_transform_hausdorff_workspace_bytes", group, nq_max)
     with torch.cuda.device(dev):
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
         v_d, v_off_d = up(np.concatenate(verts)), up(v_off)
         q_d, q_off_d = (v_d, v_off_d) if same else (up(np.concatenate(queries)), up(q_off))
         obj_d, T_d = up(cand_obj), up(T12)
-        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
         h = torch.empty(C, dtype=torch.float32, device=dev)
         for c0 in range(0, C, group):
             n = min(group, C - c0)

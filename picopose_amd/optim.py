@@ -15,9 +15,7 @@ import torch
 
 from . import _lib, ops
 
-# one PpAdamStep (include/picopose_hip.h) per tensor and step
-_STEP_DTYPE = np.dtype([("g", "<u8"), ("neg_step_size", "<f4"), ("inv_bc2_sqrt", "<f4"), ("decay", "<f4"), ("lerp_w", "<f4"),
-                        ("beta2", "<f4"), ("one_minus_beta2", "<f4"), ("eps", "<f4"), ("mode", "<i4")], align=True)
+_STEP_DTYPE = np.dtype(_lib.PpAdamStep)     # one record per tensor and step, filled in field order (`recs` of step())
 assert _STEP_DTYPE.itemsize == 40
 
 
@@ -161,10 +159,9 @@ class _FusedAdam(torch.optim.Optimizer):
         L = _lib.lib()
         rebuild = key != self._table_key
         if rebuild:
-            need = _lib.ctypes.c_size_t()
-            _lib.check(L.pp_adam_workspace_bytes(tensors, n, _lib.ctypes.byref(need)), "pp_adam_workspace_bytes")
-            if self._workspace is None or self._workspace.numel() < need.value or self._workspace.device != params[0].device:
-                self._workspace = torch.empty(need.value, dtype=torch.uint8, device=params[0].device)
+            need = _lib.workspace_bytes("pp_adam_workspace_bytes", tensors, n)
+            if self._workspace is None or self._workspace.numel() < need or self._workspace.device != params[0].device:
+                self._workspace = torch.empty(need, dtype=torch.uint8, device=params[0].device)
         # the per-step records: pinned, uploaded on the current stream (two slots: the host never overwrites a copy in flight)
         nbytes = n * _STEP_DTYPE.itemsize
         host, ev = self._pinned_slot(nbytes)

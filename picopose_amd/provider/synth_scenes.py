@@ -16,8 +16,6 @@ frames.  Silhouettes are not anti-aliased and there are no shadows or inter-refl
 the backgrounds and training_batch.ColorAugmentor.  Whether a network fine-tuned on them improves on real images is not measured
 here and is not claimed.  The samples go to the host because assemble_training_batch takes host arrays; a device-resident hand-off
 is out of scope."""
-import ctypes
-
 import numpy as np
 import torch
 
@@ -26,7 +24,7 @@ from .template_bank import (DEFAULT_WORKSPACE_BYTES, TEMPLATE_K, _mesh_arrays, _
                             template_object_poses)
 from .training_batch import nearest_template_views
 
-BG_WORDS, TILE = 4, 1024                 # PP_SYNTH_BG_WORDS, PP_SYNTH_TILE
+BG_WORDS, TILE = _lib.PP_SYNTH_BG_WORDS, _lib.PP_SYNTH_TILE
 MIN_VISIB_PX, MIN_VISIB_FRACT = 1024, 0.3    # config/base.yaml: min_px_count_visib, min_visib_fract
 TEMPLATE_UNITS_PER_METRE = 10000.0       # the template depth files' 0.1 mm unit (training_dataset.py:294)
 
@@ -106,9 +104,7 @@ def _composite_call(rgba, depth_m, off, desc, bg_images, scales, H, W, out, l0, 
     """One pp_scene_composite call: layers [l0, l0 + L) (sorted by image) onto images [i0, i0 + n) of the output tensors."""
     L_, n = int(off[-1]), len(off) - 1
     dev, lib = out["rgb"].device, _lib.lib()
-    need = ctypes.c_size_t()
-    _lib.check(lib.pp_scene_composite_workspace_bytes(L_, H, W, ctypes.byref(need)), "pp_scene_composite_workspace_bytes")
-    ws = torch.empty(max(need.value, 256), dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(_lib.workspace_bytes("pp_scene_composite_workspace_bytes", L_, H, W), 256), dtype=torch.uint8, device=dev)
     off = np.ascontiguousarray(off, dtype=np.int32)
     desc = np.ascontiguousarray(desc, dtype=np.int32)
     scales = np.ascontiguousarray(scales, dtype=np.float32)

@@ -467,9 +467,7 @@ def render_views(mesh, poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", n
     v_m = np.ascontiguousarray((v.astype(np.float64) * scale).astype(np.float32))
     v_d, f_d, c_d = (torch.from_numpy(a).to(device) for a in (v_m, f, c))
     p_d = torch.from_numpy(np.ascontiguousarray(poses.astype(np.float32))).to(device)
-    need = ctypes.c_size_t()
-    _lib.check(L.pp_render_workspace_bytes(H, W, len(f), 1, ctypes.byref(need)), "pp_render_workspace_bytes")
-    per_view = need.value - 256
+    per_view = _lib.workspace_bytes("pp_render_workspace_bytes", H, W, len(f), 1) - 256
     chunk = max(1, min(V, (int(workspace_bytes) - 256) // per_view))
     ws = torch.empty(256 + chunk * per_view, dtype=torch.uint8, device=device)
     out = {"rgba": torch.empty(V, H, W, 4, dtype=torch.uint8, device=device),

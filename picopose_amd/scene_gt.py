@@ -165,14 +165,12 @@ def scene_gt_info(models, obj_ids, R, t, K, depth=None, resolution=None, image_i
     m_vis = u8(U, H, W) if want_visib else None
     scene_depth = torch.zeros((n_images, H, W), dtype=torch.float32, device=dev) if composite else None
     inst_map = torch.full((n_images, H, W), -1, dtype=torch.int32, device=dev) if composite else None
-    need = ctypes.c_size_t()
     off = lambda a, n, size: None if a is None else a.data_ptr() + n * size      # noqa: E731
     for v0, v1, i0, i1 in groups:
         packed = scn.PackedScene(models, cams[i0:i1], H, W, near, s_obj[v0:v1], s_img[v0:v1] - i0, s_pose[v0:v1], s_win[v0:v1])
         ccam = np.ascontiguousarray(ccams[i0:i1])
-        _lib.check(L.pp_scene_gt_workspace_bytes(packed.samples, packed.faces, (i1 - i0) * H * W if run_composite else 0,
-                                                 ctypes.byref(need)), "pp_scene_gt_workspace_bytes")
-        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        need = _lib.workspace_bytes("pp_scene_gt_workspace_bytes", packed.samples, packed.faces, (i1 - i0) * H * W if run_composite else 0)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
         label_d, ccam_d = torch.from_numpy(order[v0:v1].astype(np.int32)).to(dev), torch.from_numpy(ccam).to(dev)
         _lib.check(L.pp_scene_gt(
             ctypes.byref(packed.scene), ccam_d.data_ptr(), ccam.ctypes.data, pad_x, pad_y, off(depth_d, i0 * H * W, 4), float(delta),

@@ -24,14 +24,13 @@ def _stream_ptr():
 
 
 def _workspace(B, N, C, device, query="pp_stage1_workspace_bytes"):
-    need = ctypes.c_size_t()
-    _lib.check(getattr(_lib.lib(), query)(B, N, C, ctypes.byref(need)), query)
+    need = _lib.workspace_bytes(query, B, N, C)
     key = (device.index, torch.cuda.current_stream().cuda_stream)
     ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < need.value:
-        ws = torch.empty(need.value, dtype=torch.uint8, device=device)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
         _ws_cache[key] = ws
-    return ws, need.value
+    return ws, need
 
 
 def _check_inputs(src_feats, tar_feat, tar_mask):

@@ -132,12 +132,10 @@ def verify_poses(models, obj_ids, R, t, K, segmentations, size, mask_index=None,
     depth_d = None if depth is None else scn.depth_mm(depth, scale, dev)
     near_d = torch.empty((P,), dtype=torch.int32, device=dev)
     midx_d = torch.from_numpy(midx).to(dev)
-    need = ctypes.c_size_t()
     for views, _ in groups:
         v0, v1 = int(views[0]), int(views[-1]) + 1                # (consecutive views)
         packed = scn.PackedScene(models, cams, H, W, near, obj[v0:v1], img[v0:v1], poses[v0:v1], windows[v0:v1])
-        _lib.check(L.pp_vsd_workspace_bytes(packed.samples, packed.faces, ctypes.byref(need)), "pp_vsd_workspace_bytes")
-        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        ws = torch.empty(_lib.workspace_bytes("pp_vsd_workspace_bytes", packed.samples, packed.faces), dtype=torch.uint8, device=dev)
         vm = np.ascontiguousarray(midx[v0:v1])
         _lib.check(L.pp_pose_verify(ctypes.byref(packed.scene), bits.data_ptr(), M, words, midx_d.data_ptr() + 4 * v0, vm.ctypes.data_as(_I32P),
                                     None if depth_d is None else depth_d.data_ptr(), float(delta), ws.data_ptr(), ws.numel(),

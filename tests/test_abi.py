@@ -17,6 +17,116 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, n), f"{n} declared in include/picopose_hip.h but not exported"
 
 
+_MINI_HEADER = r'''
+/* one prototype per form include/picopose_hip.h uses */
+#ifndef MINI_H
+#define MINI_H
+#include <stddef.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define PP_PLAIN 7
+#define PP_NEGATIVE (-3) /* parenthesised */
+#define PP_FLOAT 1.0f
+#define PP_CONTINUED \
+    12 /* a trailing comment that itself runs over the line \
+          break, as PP_MATCH_FAST's does */
+typedef struct PpX {
+    int a, b, c;      /* a declarator list */
+    const float* p;
+    long long s;
+    float x, y;
+} PpX;
+const char* pp_text(int code);
+size_t pp_size(long long n, int c);
+int pp_none(void);
+int pp_empty();
+int pp_ints(int32_t* a, const int64_t* b, const float* const* c, unsigned seed, double d, float f);
+int pp_voids(const void* in, void* stream, size_t n, size_t* bytes);
+int pp_structs(const PpX* in, PpX* out, long long n);
+int pp_Spread(const float* a, /* first */
+              int n,          /* second */
+              /* a line of its own */
+              float* out,
+              void* stream);
+#ifdef __cplusplus
+}
+#endif
+#endif
+'''
+
+
+def test_header_parser_on_every_form_the_header_uses():
+    c = ctypes
+    protos, structs, consts = _lib.parse_header(_MINI_HEADER)
+    X = structs["PpX"]
+    assert list(structs) == ["PpX"] and issubclass(X, c.Structure) and X.__name__ == "PpX"
+    assert X._fields_ == [("a", c.c_int), ("b", c.c_int), ("c", c.c_int), ("p", c.c_void_p), ("s", c.c_longlong),
+                          ("x", c.c_float), ("y", c.c_float)]
+    assert c.sizeof(X) == 40 and X.p.offset == 16 and X.s.offset == 24 and X.y.offset == 36
+    vp, i32 = c.c_void_p, c.c_int
+    assert protos == {
+        "pp_text": (c.c_char_p, [i32]),
+        "pp_size": (c.c_size_t, [c.c_longlong, i32]),
+        "pp_none": (i32, []),
+        "pp_empty": (i32, []),
+        "pp_ints": (i32, [vp, vp, vp, c.c_uint, c.c_double, c.c_float]),
+        "pp_voids": (i32, [vp, vp, c.c_size_t, vp]),
+        "pp_structs": (i32, [c.POINTER(X), c.POINTER(X), c.c_longlong]),
+        "pp_Spread": (i32, [vp, i32, vp, vp]),
+    }
+    assert consts == {"PP_PLAIN": 7, "PP_NEGATIVE": -3, "PP_CONTINUED": 12}
+    # a type the parser does not know raises and names the function; it never falls back to int
+    # (nor, for a type of several words, back to its first word: `unsigned short` is not `unsigned`)
+    for bad in ("int pp_bad(short n);", "int pp_bad(const float* a, uint16_t n);", "wchar_t pp_bad(int n);", "unsigned long pp_bad(int);",
+                "int pp_bad(unsigned char);", "int pp_bad(unsigned long);", "int pp_bad(unsigned short n);", "unsigned char pp_bad(int n);"):
+        with pytest.raises(ValueError, match="pp_bad"):
+            _lib.parse_header(_MINI_HEADER + bad)
+    for bad in ("short a;", "unsigned short a;", "unsigned char a; int b;", "long a;"):
+        with pytest.raises(ValueError, match="PpY"):
+            _lib.parse_header("typedef struct PpY { %s } PpY;" % bad)
+    # unnamed parameters of known types still bind
+    assert _lib.parse_header("int pp_f(unsigned, long long, unsigned int, const float*);")[0]["pp_f"][1] == [c.c_uint, c.c_longlong, c.c_uint, vp]
+
+
+def test_declared_symbols_are_the_headers_prototypes():
+    import os
+    import re
+
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "picopose_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    counted = re.findall(r"\bpp_[A-Za-z0-9_]+\s*\(", text)         # (letters of either case: pp_calc_pred_Ms; not the PP_E* (-n) macros)
+    names = _lib.declared_symbols()
+    assert "pp_calc_pred_Ms" in names and "pp_version" in names
+    assert names == sorted(names) and len(names) == len(counted) == len(set(counted))
+
+
+def test_structs_and_constants_of_the_real_header():
+    c = ctypes
+    assert c.sizeof(_lib.PpAdamStep) == 40 and c.sizeof(_lib.PpAdamTensor) == 48
+    assert len(_lib.PpScene._fields_) == 26 and len(_lib.PpGemmDesc._fields_) == 53
+    for cls in (_lib.PpGemmDesc, _lib.PpScene, _lib.PpAdamTensor, _lib.PpAdamStep):
+        assert cls.__module__ == "picopose_amd._lib" and issubclass(cls, c.Structure)
+    assert [n for n, _ in _lib.PpAdamTensor._fields_] == ["p", "m", "v", "hl", "scale2", "n"]
+    assert (_lib.PpGemmDesc.M.offset, _lib.PpGemmDesc.a_bs0.offset, _lib.PpScene.n_objects.offset, _lib.PpScene.near.offset) == (56, 96, 160, 180)
+    # the values the Python modules used to restate by hand: this list is the test's own statement of them
+    old = dict(PP_OK=0, PP_EINVAL=-1, PP_EWORKSPACE=-2, PP_ELAUNCH=-3, PP_MATCH_EXACT=0, PP_MATCH_FAST=1, PP_BANK_F32=0, PP_BANK_F16=1,
+               PP_EVAL_MSSD=1, PP_EVAL_MSPD=2, PP_EVAL_ADD=4, PP_EVAL_ADDS=8, PP_VSD_MAX_TAUS=16, PP_DEPTH_REFINE_STRIP_ROWS=8,
+               PP_DEPTH_REFINE_SUMS=29, PP_DEPTH_REFINE_MAX_ITERATIONS=1000, PP_MASK_MAX_N=4096, PP_DET_TILE=8, PP_DET_MAX_GT=4096,
+               PP_PLANE_MAX_HYP=1024, PP_SYNTH_BG_WORDS=4, PP_SYNTH_TILE=1024)
+    for name, value in old.items():
+        assert getattr(_lib, name) == value, name
+    assert not hasattr(_lib, "PP_PLANE_MIN_CROSS2")                  # a float-valued macro is no constant of the binding
+    # ... and the module-level names that read them
+    from picopose_amd import depth_proposals, depth_refine, detection_eval, evaluation, masks
+    from picopose_amd.provider import synth_scenes
+
+    assert evaluation.KINDS == {"mssd": 1, "mspd": 2, "add": 4, "adds": 8} and evaluation.VSD_MAX_TAUS == 16
+    assert (depth_refine.STRIP_ROWS, depth_refine.N_SUMS, depth_refine.MAX_ITERATIONS) == (8, 29, 1000)
+    assert (masks.MAX_MASKS, detection_eval.TILE, detection_eval.MAX_GT, depth_proposals.MAX_HYP) == (4096, 8, 4096, 1024)
+    assert (synth_scenes.BG_WORDS, synth_scenes.TILE) == (4, 1024)
+
+
 def test_error_strings_and_workspace_query():
     L = _lib.lib()
     assert L.pp_version() >= 100
