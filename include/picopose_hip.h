@@ -521,7 +521,9 @@ int pp_winograd4_chain(const float* Y, int ld_y, int B, int H, int W, int C, con
 int pp_winograd_chain_f32(const float* Y, int B, int H, int W, int C, const float* bias, int act, int relu_next, float* U, void* stream);
 
 /* Sticky operand-saturation word.  The f16x3 / f16 operand formats clamp at the fp16 range (|4 x| >= 65504): a clamped term is finite but
- * WRONG.  With a device word registered here, every kernel that writes operand terms ORs bit 0 into it when a term hit the clamp (one
+ * WRONG.  The Winograd F(4x4, 3x3) transforms (pp_winograd4_input_hl, pp_winograd4_output, pp_winograd4_chain) do NOT clamp: there a value
+ * beyond the fp16 range is stored as +-inf in the hi term and NaN in the lo term, and everything computed from it is +-inf / NaN.  Either
+ * way the result is wrong and is reported the same way.  With a device word registered here, every kernel that writes operand terms ORs bit 0 into it when a term hit the clamp (one
  * atomic per wave that saw one; nothing when none did) — the host reads the word together with its results (no extra synchronisation)
  * and raises.  word = NULL switches the reporting off.  Per device (the current one).  block.py:104-106 / layer_scale.py:27-28: trained
  * DINOv2 residual streams hold a few very large channels. */

@@ -27,7 +27,8 @@ __device__ __forceinline__ void pp_split_f16(float v, _Float16& hi, _Float16& lo
 // plain-fp16 operand ("h" format, PP_PREC_F16): v -> f16(4 v), saturated like the hi term above
 __device__ __forceinline__ _Float16 pp_to_f16(float v) { return (_Float16)fminf(fmaxf(v * PP_A_SCALE, -65504.f), 65504.f); }
 
-// Sticky saturation word (include/picopose_hip.h pp_set_saturation_word).  A clamped operand term is finite but WRONG; the kernels that
+// Sticky saturation word (include/picopose_hip.h pp_set_saturation_word).  A clamped operand term is finite but WRONG (the Winograd F(4x4) transforms
+// do not clamp: wino_split4 in pp_winograd.hip stores +-inf / NaN terms there, wrong as well and reported the same way); the kernels that
 // WRITE operand buffers (the producers of the inference path: split passes, LayerNorm, attention output, GEMM epilogues, resize, warp,
 // Winograd transforms) report it by OR-ing bit 0 into a device word — an atomic only from a lane that actually saw a clamped term.
 // Every translation unit holds its own copy of the registered pointer (no relocatable device code in this build);

@@ -104,7 +104,8 @@ def saturation_word(device=None):
 def saturation_error(what="a forward since the last check"):
     return _lib.PicoPoseHipError(
         f"an f16x3 / f16 operand saturated in {what}: an activation reached the fp16 range of the engine's operand format (|x| >= 16376; "
-        "Winograd-transformed maps: >= 10480) and was clamped — the results of this batch are wrong.  Run this network with "
+        "Winograd-transformed maps: >= 10480) and was clamped (by the Winograd F(4x4) transforms: stored as +-inf / NaN) — the results of this "
+        "batch are wrong.  Run this network with "
         "ops.PRECISION = 'f32' (bench.py --mode exact); ops.CHECK_SATURATION = True names the layer")
 
 
@@ -666,6 +667,9 @@ def conv2d(x, wp, bias, ksize, stride=1, pad=0, act=None, relu_in=False, residua
         B, H, W, Cx = x.geom
         assert ksize == 3 and stride == 1 and pad == 1 and cin in (None, Cx) and wp.shape[1] == 9 * Cx and hl_into is None
         assert not (relu_in and not x.relu), "the shared / chained Winograd input was made without the input ReLU this layer asks for"
+        # (a chained input carries its consumer's ReLU because the producer was told so (wino_next="relu"): the consumer need not repeat it.
+        # A shared one serves several consumers: each must ask for exactly the ReLU it was made with)
+        assert x.chained or x.relu == bool(relu_in), "the shared Winograd input was made with an input ReLU this layer does not ask for"
         return _conv3x3_winograd(x, wp, bias, B, H, W, Cx, Cx, wp.shape[0], act, x.relu, residual, residual2, out, chain_next=wino_next)
     if isinstance(x, WinoInput4):     # the shared F(4x4, 3x3) input of several 3x3 convolutions (f16x3 engine)
         B, H, W, Cx = x.geom
@@ -812,11 +816,12 @@ def winograd_weight(wp, cin):
 class WinoInput:
     """The Winograd input transform U (16, P, C) of an fp32 NHWC map, made once for SEVERAL 3x3 convolutions that read the same map (the
     two heads of the flow decoder read one 640-channel input: raft_decoder.py:251-289) — `ops.winograd_shared(x)`; `conv2d` takes it in
-    place of `x`.  The caller guarantees that the map is not rewritten between the transform and its last use."""
-    __slots__ = ("U", "geom", "relu")
+    place of `x`.  The caller guarantees that the map is not rewritten between the transform and its last use.  `chained`: made by the
+    previous layer's chained output transform (conv2d(..., wino_next=)) for ONE consumer, whose input ReLU it already holds if `relu`."""
+    __slots__ = ("U", "geom", "relu", "chained")
 
-    def __init__(self, U, geom, relu):
-        self.U, self.geom, self.relu = U, geom, relu
+    def __init__(self, U, geom, relu, chained=False):
+        self.U, self.geom, self.relu, self.chained = U, geom, relu, chained
 
 
 def _winograd_ok(B, H, W, cin, ld_in, x):
@@ -876,7 +881,7 @@ def _conv3x3_winograd(x, wp, bias, B, H, W, cin, ld_in, Cout, act, relu_in, resi
         U1 = torch.empty(16, P, Cout, dtype=torch.float32, device=dev)
         _lib.check(L.pp_winograd_chain_f32(_p(Y), B, H, W, Cout, _p(bias), ACT[act], int(chain_next == "relu"), _p(U1), _lib.stream_ptr()),
                    "pp_winograd_chain_f32")
-        return WinoInput(U1, (B, H, W, Cout), chain_next == "relu")
+        return WinoInput(U1, (B, H, W, Cout), chain_next == "relu", chained=True)
     if out is None:
         out = torch.empty(B, H, W, Cout, dtype=torch.float32, device=dev)
     ldc = out.stride(2)
@@ -971,6 +976,7 @@ def _wino4_finish(Y, col0, ldy, bias, B, H, W, Cout, act, residual, residual2, o
     Pp, dev, L = _wino4_rows(P), Y.device, _lib.lib()
     yp = Y.data_ptr() + 4 * col0
     ret, hl_t, ldc = None, None, 0
+    split_relu = bool(split_relu) or chain_next == "relu"     # wino_next="relu": the consumer's input ReLU, folded into the operand either way
     # (W = 16: the chain's one workgroup per (image, slice) is four tile rows long and loses to the two separate kernels, 0.144 vs 0.108 ms)
     if (chain_next and WINO4_CHAIN and out_split and out is None and residual is None and residual2 is None and W in WINO4_CHAIN_WIDTHS and Cout % 32 == 0
             and _winograd4_ok(B, H, W, Cout, Cout)):
