@@ -12,6 +12,12 @@ import ctypes
 import os
 import re
 
+import numpy as np
+# torch before the library is opened: PyTorch-ROCm bundles its own libamdhip64, and this library must bind to THAT runtime (it
+# launches on torch's streams and takes torch's device pointers).  Loaded before torch, it would pull in /opt/rocm's copy — two
+# HIP runtimes in one process, and every launch fails (seen on the GPU box with build() followed by smoke()).
+import torch
+
 from .build import LIB
 
 _HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "picopose_hip.h")
@@ -71,7 +77,8 @@ def _struct(name, body, structs):
 
 
 def parse_header(text):
-    """C header text -> (prototypes {name: (restype, argtypes)}, structs {name: ctypes.Structure}, constants {PP_X: int})."""
+    """C header text -> (prototypes {name: (restype, argtypes)}, structs {name: ctypes.Structure}, constants {PP_X: int},
+    streamed: the names of the prototypes whose last parameter is `void* stream`)."""
     text = re.sub(r"/\*.*?\*/", " ", text.replace("\\\n", ""), flags=re.S)
     constants = {}
     for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(PP_\w+)[ \t]+(.+?)[ \t]*$", text, flags=re.M):
@@ -89,7 +96,7 @@ def parse_header(text):
         return ""
 
     text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;", take_struct, text)
-    prototypes = {}
+    prototypes, streamed = {}, set()
     for stmt in filter(None, (s.strip() for s in text.split(";"))):
         m = re.fullmatch(r"(.*[\s*])(\w+)\s*\(([^()]*)\)", stmt, flags=re.S)
         if m is None:
@@ -100,11 +107,13 @@ def parse_header(text):
         if None in argtypes or name in prototypes:
             raise ValueError(f"{name}: void parameter or second declaration")
         prototypes[name] = (restype, argtypes)
-    return prototypes, structs, constants
+        if re.fullmatch(r"void\s*\*\s*stream", params.split(",")[-1].strip()):
+            streamed.add(name)
+    return prototypes, structs, constants, streamed
 
 
 with open(_HEADER) as _f:
-    _PROTOTYPES, _STRUCTS, _CONSTANTS = parse_header(_f.read())
+    _PROTOTYPES, _STRUCTS, _CONSTANTS, _STREAMED = parse_header(_f.read())
 globals().update(_STRUCTS)       # PpGemmDesc, PpScene, PpAdamTensor, PpAdamStep
 globals().update(_CONSTANTS)     # PP_OK, PP_EINVAL, PP_MATCH_FAST, ...
 PP_OK = _CONSTANTS["PP_OK"]      # (named for check() below)
@@ -123,11 +132,6 @@ def lib():
                 f"{LIB} not found: build it with `python -m picopose_amd.build` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback."
             )
-        # torch first: PyTorch-ROCm bundles its own libamdhip64, and this library must bind to THAT runtime (it launches on
-        # torch's streams and takes torch's device pointers).  Loaded before torch, it would pull in /opt/rocm's copy — two
-        # HIP runtimes in one process, and every launch fails (seen on the GPU box with build() followed by smoke()).
-        import torch  # noqa: F401
-
         L = ctypes.CDLL(LIB)
         for name, (restype, argtypes) in _PROTOTYPES.items():
             try:
@@ -140,8 +144,6 @@ def lib():
 
 
 def stream_ptr():
-    import torch
-
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
@@ -160,8 +162,61 @@ def check(rc, what):
         raise PicoPoseHipError(f"{what} failed: {lib().pp_strerror(rc).decode()} (code {rc})")
 
 
+def address(v):
+    """What a `void*` parameter or struct member takes for `v`: a tensor's data_ptr() (a view's own address), a numpy array's
+    buffer; everything else — None (null), an int address, a ctypes array or pointer — as it is.  Nothing is validated here."""
+    kind = _KINDS.get(type(v))
+    if kind is None:         # (isinstance against torch.Tensor runs a metaclass hook: asked once per type, not per argument)
+        kind = _KINDS[type(v)] = 1 if isinstance(v, torch.Tensor) else 2 if isinstance(v, np.ndarray) else 0
+    return v.data_ptr() if kind == 1 else v.ctypes.data if kind == 2 else v
+
+
+_KINDS = {}              # type of a pointer argument -> 1 tensor (and subclasses: Parameter), 2 numpy array, 0 passed as it is
+
+
+_CURRENT = object()      # call()'s default stream: torch's current one
+_PLANS = {}              # entry name -> (function, the `void*` parameters' positions, takes a stream, parameter count)
+
+
+def _plan(name):
+    restype, argtypes = _PROTOTYPES[name]
+    if restype is not ctypes.c_int:
+        raise TypeError(f"{name} does not return a status (its return type is {restype.__name__}): call lib().{name}(...) directly")
+    # the conversion is chosen by the bound argtype: `void*` parameters (bar the appended stream, a handle already) go through
+    # address(); POINTER(struct) takes an instance or an array by reference and scalars convert, both inside ctypes
+    streamed = name in _STREAMED
+    pointers = tuple(i for i, t in enumerate(argtypes[:len(argtypes) - streamed]) if t is ctypes.c_void_p)
+    _PLANS[name] = plan = (getattr(lib(), name), pointers, streamed, len(argtypes))
+    return plan
+
+
+def call(name, *args, stream=_CURRENT, what=None):
+    """Launch the status-returning entry `name` of include/picopose_hip.h: tensors and numpy arrays go in as themselves
+    (see address()), an entry whose last parameter is `void* stream` gets torch's current stream appended (`stream=None`: the
+    null stream, `stream=<int>`: that handle), and a status other than PP_OK raises PicoPoseHipError labelled `what` or `name`."""
+    fn, pointers, streamed, count = _PLANS.get(name) or _plan(name)
+    args = list(args)
+    if streamed:
+        args.append(torch.cuda.current_stream().cuda_stream if stream is _CURRENT else stream)
+    elif stream is not _CURRENT:
+        raise TypeError(f"{name} takes no stream")
+    if len(args) != count:
+        raise TypeError(f"{name} takes {count - streamed} arguments{' and a stream' if streamed else ''}, {len(args) - streamed} given")
+    kinds = _KINDS
+    for i in pointers:       # (address(), with the two frequent cases — a tensor, None or an int — decided here without a call)
+        v = args[i]
+        kind = kinds.get(type(v))
+        if kind == 1:
+            args[i] = v.data_ptr()
+        elif kind != 0:
+            args[i] = address(v)
+    rc = fn(*args)
+    if rc != PP_OK:
+        check(rc, what or name)
+
+
 def workspace_bytes(query, *args):
     """What the size query named `query` — an `int pp_*_workspace_bytes(args..., size_t* bytes)` entry — reports for `args`."""
     need = ctypes.c_size_t()
-    check(getattr(lib(), query)(*args, ctypes.byref(need)), query)
+    call(query, *args, ctypes.byref(need))
     return need.value

@@ -35,10 +35,6 @@ ACT = ops.ACT
 DETERMINISTIC = False
 
 
-def _p(t):
-    return t.data_ptr() if t is not None else None
-
-
 def _f32c(t):
     return t.contiguous().float()
 
@@ -46,17 +42,16 @@ def _f32c(t):
 def colsum(x2d):
     """Column sums of a contiguous (rows, cols) matrix (fixed summation order)."""
     rows, cols = x2d.shape
-    L = _lib.lib()
-    nbytes = L.pp_colsum_workspace_bytes(rows, cols)
+    nbytes = _lib.lib().pp_colsum_workspace_bytes(rows, cols)
     ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=x2d.device)
     out = torch.empty(cols, dtype=torch.float32, device=x2d.device)
-    _lib.check(L.pp_colsum(_p(x2d), rows, cols, x2d.stride(0), _p(out), _p(ws), nbytes, _lib.stream_ptr()), "pp_colsum")
+    _lib.call("pp_colsum", x2d, rows, cols, x2d.stride(0), out, ws, nbytes)
     return out
 
 
 def _ew(op, a, b, cols=0):
     out = torch.empty_like(a)
-    _lib.check(_lib.lib().pp_elementwise(op, _p(a), _p(b), a.numel(), cols, _p(out), _lib.stream_ptr()), "pp_elementwise")
+    _lib.call("pp_elementwise", op, a, b, a.numel(), cols, out)
     return out
 
 
@@ -66,7 +61,7 @@ def _pow2_scale(t):
     back, exactly (powers of two).  One reduction on the device (pp_pow2_scale), no host sync; the scale never enters a value
     except through rounding."""
     buf = torch.empty(2 + 1024, dtype=torch.float32, device=t.device)      # (scale, inverse | per-workgroup maxima)
-    _lib.check(_lib.lib().pp_pow2_scale_ws(_p(t), t.numel(), _p(buf), _p(buf[2:]), _lib.stream_ptr()), "pp_pow2_scale_ws")
+    _lib.call("pp_pow2_scale_ws", t, t.numel(), buf, buf[2:])
     return buf[:2]
 
 
@@ -158,7 +153,7 @@ def _mm(a, b, alpha=1.0, out=None, ra=True, rb=True):
         part = torch.empty(1, S, M, N, dtype=torch.float32, device=a.device)
         ops.bmm_nn(a2.contiguous().view(M, S, kc).permute(1, 0, 2)[None], b2.contiguous().view(S, kc, N)[None], part)
         r = torch.empty(M, N, dtype=torch.float32, device=a.device)
-        _lib.check(_lib.lib().pp_sum_slices(_p(part), S, M, N, None, 0, _p(r), _lib.stream_ptr()), "pp_sum_slices")
+        _lib.call("pp_sum_slices", part, S, M, N, None, 0, r)
         return _unscale(r, sa, sb, out)
     if alpha == 1.0 and ops.operands_ok(M, N, K) and M * N * K >= 1 << 24 and a.stride(1) == 1 and b.stride(1) == 1:
         # both operands split with their range scale applied (b: transposed in the same pass), the inverse scales in the launch
@@ -185,7 +180,7 @@ class _Linear(torch.autograd.Function):
         ctx.act = ACT[act]
         if ctx.act:
             y = torch.empty_like(z)
-            _lib.check(_lib.lib().pp_act_forward(_p(z), z.numel(), ctx.act, _p(y), _lib.stream_ptr()), "pp_act_forward")
+            _lib.call("pp_act_forward", z, z.numel(), ctx.act, y)
         else:
             y = z
         ctx.save_for_backward(x, w, z if ctx.act else None)
@@ -198,7 +193,7 @@ class _Linear(torch.autograd.Function):
         dy = _f32c(dy)
         if ctx.act:
             dz = torch.empty_like(dy)
-            _lib.check(_lib.lib().pp_act_backward(_p(z), _p(dy), dy.numel(), ctx.act, _p(dz), _lib.stream_ptr()), "pp_act_backward")
+            _lib.call("pp_act_backward", z, dy, dy.numel(), ctx.act, dz)
         else:
             dz = dy
         dx = _mm(dz, w, rb=False) if ctx.needs_input_grad[0] else None                       # (weights / activations: forward quantities)
@@ -224,8 +219,7 @@ class _LayerNorm(torch.autograd.Function):
         x, w = ctx.saved_tensors
         dy = _f32c(dy)
         dx, gx = torch.empty_like(x), torch.empty_like(x)
-        _lib.check(_lib.lib().pp_layernorm_backward(_p(x), _p(w), _p(dy), x.shape[0], x.shape[1], float(ctx.eps), _p(dx), _p(gx), _lib.stream_ptr()),
-                   "pp_layernorm_backward")
+        _lib.call("pp_layernorm_backward", x, w, dy, x.shape[0], x.shape[1], float(ctx.eps), dx, gx)
         return dx, colsum(gx), colsum(dy), None
 
 
@@ -269,8 +263,7 @@ class _Attention(torch.autograd.Function):
         if ctx.fused:
             out = torch.empty(B * T, heads * hd, dtype=torch.float32, device=qkv.device)
             lse = torch.empty(B * heads, T, dtype=torch.float32, device=qkv.device)
-            _lib.check(_lib.lib().pp_attention_train(_p(qkv), B, T, heads, hd, float(hd) ** -0.5, _p(out), _p(lse), _lib.stream_ptr()),
-                       "pp_attention_train")
+            _lib.call("pp_attention_train", qkv, B, T, heads, hd, float(hd) ** -0.5, out, lse)
             ctx.save_for_backward(qkv, out, lse)
             return out
         v5 = qkv.view(B, T, 3, heads, hd)
@@ -290,8 +283,7 @@ class _Attention(torch.autograd.Function):
             g = _pow2_scale(dout)
             dqkv = torch.empty_like(qkv)
             ws = torch.empty(B * heads * T, dtype=torch.float32, device=qkv.device)
-            _lib.check(_lib.lib().pp_attention_backward(_p(qkv), _p(out), _p(dout), _p(lse), _p(g), B, T, heads, hd, float(hd) ** -0.5,
-                                                        _p(ws), _p(dqkv), _lib.stream_ptr()), "pp_attention_backward")
+            _lib.call("pp_attention_backward", qkv, out, dout, lse, g, B, T, heads, hd, float(hd) ** -0.5, ws, dqkv)
             return dqkv, None, None, None, None
         qkv, P = ctx.saved_tensors
         v5 = qkv.view(B, T, 3, heads, hd)
@@ -299,7 +291,7 @@ class _Attention(torch.autograd.Function):
         dO = _f32c(dout).view(B, T, heads, hd).permute(0, 2, 1, 3)
         dP = bmm_nt_b(dO, v, rb=False)                                                # dO v^T
         dS = torch.empty_like(P)
-        _lib.check(_lib.lib().pp_softmax_backward_rows(_p(P), _p(dP), B * heads * T, T, _p(dS), _lib.stream_ptr()), "pp_softmax_backward_rows")
+        _lib.call("pp_softmax_backward_rows", P, dP, B * heads * T, T, dS)
         dqkv = torch.empty_like(qkv)
         d5 = dqkv.view(B, T, 3, heads, hd)
         s = float(hd) ** -0.5
@@ -323,8 +315,7 @@ class _GroupNormRelu(torch.autograd.Function):
         B, H, W, C = x.shape
         dy = _f32c(dy)
         dx, gx, gy = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
-        _lib.check(_lib.lib().pp_groupnorm_backward_nhwc(_p(x), _p(w), _p(b), _p(dy), B, H * W, C, ctx.groups, 1e-5, int(ctx.relu), _p(dx), _p(gx),
-                                                         _p(gy), _lib.stream_ptr()), "pp_groupnorm_backward_nhwc")
+        _lib.call("pp_groupnorm_backward_nhwc", x, w, b, dy, B, H * W, C, ctx.groups, 1e-5, int(ctx.relu), dx, gx, gy)
         return dx, colsum(gx.view(-1, C)), colsum(gy.view(-1, C)), None, None
 
 
@@ -335,7 +326,7 @@ class _Im2col(torch.autograd.Function):
         B, H, W, C = x.shape
         Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
         col = torch.empty(B * Ho * Wo, k * k * C, dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().pp_im2col_nhwc(_p(x), B, H, W, C, k, s, p, _p(col), _lib.stream_ptr()), "pp_im2col_nhwc")
+        _lib.call("pp_im2col_nhwc", x, B, H, W, C, k, s, p, col)
         ctx.geom = (B, H, W, C, k, s, p)
         return col
 
@@ -343,7 +334,7 @@ class _Im2col(torch.autograd.Function):
     def backward(ctx, dcol):
         B, H, W, C, k, s, p = ctx.geom
         dx = torch.empty(B, H, W, C, dtype=torch.float32, device=dcol.device)
-        _lib.check(_lib.lib().pp_col2im_nhwc(_p(_f32c(dcol)), B, H, W, C, k, s, p, _p(dx), _lib.stream_ptr()), "pp_col2im_nhwc")
+        _lib.call("pp_col2im_nhwc", _f32c(dcol), B, H, W, C, k, s, p, dx)
         return dx, None, None, None
 
 
@@ -359,8 +350,7 @@ class _NormalizeRows(torch.autograd.Function):
     def backward(ctx, dq):
         (x,) = ctx.saved_tensors
         dx = torch.empty_like(x)
-        _lib.check(_lib.lib().pp_normalize_rows_backward(_p(x), x.shape[1], None, _p(_f32c(dq)), x.shape[0], x.shape[1], float(ctx.eps), _p(dx),
-                                                         _lib.stream_ptr()), "pp_normalize_rows_backward")
+        _lib.call("pp_normalize_rows_backward", x, x.shape[1], None, _f32c(dq), x.shape[0], x.shape[1], float(ctx.eps), dx)
         return dx, None
 
 
@@ -371,15 +361,14 @@ class _InfoNCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tok_s, tok_t, s_rows, t_rows, tau):
         ts, tt = _f32c(tok_s), _f32c(tok_t)
-        L = _lib.lib()
         n, C = s_rows.numel(), ts.shape[-1]
         q = torch.empty(n, C, dtype=torch.float32, device=ts.device)
         r = torch.empty_like(q)
-        _lib.check(L.pp_gather_normalize_rows(_p(ts), C, _p(s_rows), n, C, 1e-12, _p(q), _lib.stream_ptr()), "pp_gather_normalize_rows")
-        _lib.check(L.pp_gather_normalize_rows(_p(tt), C, _p(t_rows), n, C, 1e-12, _p(r), _lib.stream_ptr()), "pp_gather_normalize_rows")
+        _lib.call("pp_gather_normalize_rows", ts, C, s_rows, n, C, 1e-12, q)
+        _lib.call("pp_gather_normalize_rows", tt, C, t_rows, n, C, 1e-12, r)
         logits = ops.bmm_nt(q[None, None], r[None, None])[0, 0]
         rows = torch.empty(n, dtype=torch.float32, device=ts.device)
-        _lib.check(L.pp_xent_diag_rows(_p(logits), n, logits.stride(0), 1.0 / tau, _p(rows), _lib.stream_ptr()), "pp_xent_diag_rows")
+        _lib.call("pp_xent_diag_rows", logits, n, logits.stride(0), 1.0 / tau, rows)
         ctx.save_for_backward(ts, tt, s_rows, t_rows, q, r, logits)
         ctx.tau = tau
         return rows.mean()
@@ -387,22 +376,19 @@ class _InfoNCE(torch.autograd.Function):
     @staticmethod
     def backward(ctx, up):
         ts, tt, s_rows, t_rows, q, r, logits = ctx.saved_tensors
-        L = _lib.lib()
         n, C = q.shape
         dl = torch.empty(n, n, dtype=torch.float32, device=q.device)
-        _lib.check(L.pp_xent_diag_backward(_p(logits), n, logits.stride(0), 1.0 / ctx.tau, _p(_f32c(up).reshape(1)), _p(dl), _lib.stream_ptr()),
-                   "pp_xent_diag_backward")
+        _lib.call("pp_xent_diag_backward", logits, n, logits.stride(0), 1.0 / ctx.tau, _f32c(up).reshape(1), dl)
         dq, dr = _mm(dl, r, rb=False), _mm(dl.t().contiguous(), q, rb=False)
         out = []
         for tok, rows_, dn in ((ts, s_rows, dq), (tt, t_rows, dr)):
             dx = torch.empty(n, C, dtype=torch.float32, device=q.device)
-            _lib.check(L.pp_normalize_rows_backward(_p(tok), C, _p(rows_), _p(dn), n, C, 1e-12, _p(dx), _lib.stream_ptr()),
-                       "pp_normalize_rows_backward")
+            _lib.call("pp_normalize_rows_backward", tok, C, rows_, dn, n, C, 1e-12, dx)
             # the backward of the row gather is a scatter-ADD: the template-side rows are distinct grid cells, but the real-image
             # rows are re-projected points quantised to the 16x16 feature grid (utils/loss_utils.py:150-160) and several key-points
             # can share a cell (more than half of them when the real crop is the smaller view).  Fixed summation order, no atomics.
             g = torch.zeros(tok.numel() // C, C, dtype=torch.float32, device=q.device)
-            _lib.check(L.pp_scatter_add_rows(_p(dx), _p(rows_), n, C, _p(g), _lib.stream_ptr()), "pp_scatter_add_rows")
+            _lib.call("pp_scatter_add_rows", dx, rows_, n, C, g)
             out.append(g.view_as(tok))
         return out[0], out[1], None, None, None
 
@@ -469,18 +455,16 @@ class _SimilarityVolume(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         ts, tt, mask, out = ctx.saved_tensors
-        L = _lib.lib()
         B, T, C = ts.shape
         P = T - 1
         rows = (torch.arange(B, device=ts.device)[:, None] * T + 1 + torch.arange(P, device=ts.device)[None]).reshape(-1)
         q = torch.empty(B * P, C, dtype=torch.float32, device=ts.device)
         r = torch.empty_like(q)
-        _lib.check(L.pp_gather_normalize_rows(_p(ts), C, _p(rows), B * P, C, 1e-12, _p(q), _lib.stream_ptr()), "pp_gather_normalize_rows")
-        _lib.check(L.pp_gather_normalize_rows(_p(tt), C, _p(rows), B * P, C, 1e-12, _p(r), _lib.stream_ptr()), "pp_gather_normalize_rows")
+        _lib.call("pp_gather_normalize_rows", ts, C, rows, B * P, C, 1e-12, q)
+        _lib.call("pp_gather_normalize_rows", tt, C, rows, B * P, C, 1e-12, r)
         mask = _f32c(mask)
         dS = torch.empty(B, P, P, dtype=torch.float32, device=ts.device)           # [b][t][s]
-        _lib.check(L.pp_simvol_backward(_p(out), _p(_f32c(dout)), _p(mask), mask.shape[1], mask.shape[2], B, _p(dS), _lib.stream_ptr()),
-                   "pp_simvol_backward")
+        _lib.call("pp_simvol_backward", out, _f32c(dout), mask, mask.shape[1], mask.shape[2], B, dS)
         dr = torch.empty(1, B, P, C, dtype=torch.float32, device=ts.device)
         dq = torch.empty_like(dr)
         bmm_nn_b(dS[None], q.view(1, B, P, C), dr, rb=False)                        # d tar_hat[t] = sum_s dS[t][s] src_hat[s]
@@ -488,8 +472,7 @@ class _SimilarityVolume(torch.autograd.Function):
         grads = []
         for tok, dn in ((ts, dq), (tt, dr)):
             dx = torch.empty(B * P, C, dtype=torch.float32, device=ts.device)
-            _lib.check(L.pp_normalize_rows_backward(_p(tok), C, _p(rows), _p(dn), B * P, C, 1e-12, _p(dx), _lib.stream_ptr()),
-                       "pp_normalize_rows_backward")
+            _lib.call("pp_normalize_rows_backward", tok, C, rows, dn, B * P, C, 1e-12, dx)
             g = torch.zeros(B * T, C, dtype=torch.float32, device=ts.device)
             g.index_copy_(0, rows, dx)
             grads.append(g.view(B, T, C))
@@ -509,7 +492,7 @@ def embed_tokens(fe, x):
     h0, w0 = H // p, W // p
     img = ops.to_nhwc(x, c_pad=8)
     col = torch.empty(B * h0 * w0, p * p * 8, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().pp_im2col_nhwc(_p(img), B, H, W, 8, p, p, 0, _p(col), _lib.stream_ptr()), "pp_im2col_nhwc")
+    _lib.call("pp_im2col_nhwc", img, B, H, W, 8, p, p, 0, col)
     wp = ops.pack_conv_weight(v.patch_embed.proj.weight.float(), cin_pad=8)            # views + a zero pad: torch differentiates them
     patches = linear(col, wp, v.patch_embed.proj.bias)
     pos = _InterpPos.apply(v.pos_embed, fe._pos(h0, w0), fe._pos_wt(h0, w0))
@@ -570,14 +553,14 @@ class _Act(torch.autograd.Function):
         ctx.act = ACT[act]
         ctx.save_for_backward(x)
         y = torch.empty_like(x)
-        _lib.check(_lib.lib().pp_act_forward(_p(x), x.numel(), ctx.act, _p(y), _lib.stream_ptr()), "pp_act_forward")
+        _lib.call("pp_act_forward", x, x.numel(), ctx.act, y)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
         dx = torch.empty_like(x)
-        _lib.check(_lib.lib().pp_act_backward(_p(x), _p(_f32c(dy)), x.numel(), ctx.act, _p(dx), _lib.stream_ptr()), "pp_act_backward")
+        _lib.call("pp_act_backward", x, _f32c(dy), x.numel(), ctx.act, dx)
         return dx, None
 
 
@@ -610,13 +593,11 @@ class _BatchNormTrain(torch.autograd.Function):
         x, gamma, beta = ctx.saved_tensors
         C = x.shape[-1]
         rows = x.numel() // C
-        L = _lib.lib()
-        nbytes = L.pp_batchnorm_train_backward_workspace_bytes(rows, C)
+        nbytes = _lib.lib().pp_batchnorm_train_backward_workspace_bytes(rows, C)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         dx = torch.empty_like(x)
         dg, db = torch.empty(C, dtype=torch.float32, device=x.device), torch.empty(C, dtype=torch.float32, device=x.device)
-        _lib.check(L.pp_batchnorm_train_backward(_p(x), _p(gamma), _p(beta), _p(_f32c(dy)), rows, C, 1e-5, int(ctx.relu), _p(dx), _p(dg), _p(db),
-                                                 _p(ws), nbytes, _lib.stream_ptr()), "pp_batchnorm_train_backward")
+        _lib.call("pp_batchnorm_train_backward", x, gamma, beta, _f32c(dy), rows, C, 1e-5, int(ctx.relu), dx, dg, db, ws, nbytes)
         return dx, dg, db, None, None
 
 
@@ -635,8 +616,7 @@ class _Resize(torch.autograd.Function):
     def backward(ctx, dy):
         (B, H, W, C), Ho, Wo, mul = ctx.geom
         dx = torch.empty(B, H, W, C, dtype=torch.float32, device=dy.device)
-        _lib.check(_lib.lib().pp_resize_bilinear_backward_nhwc(_p(_f32c(dy)), B, H, W, C, Ho, Wo, float(mul), _p(dx), _lib.stream_ptr()),
-                   "pp_resize_bilinear_backward_nhwc")
+        _lib.call("pp_resize_bilinear_backward_nhwc", _f32c(dy), B, H, W, C, Ho, Wo, float(mul), dx)
         return dx, None, None, None
 
 
@@ -646,7 +626,7 @@ def resize(x, Ho, Wo, mul=1.0):
 
 def _fixed_to_float(acc):
     out = torch.empty(acc.shape, dtype=torch.float32, device=acc.device)
-    _lib.check(_lib.lib().pp_fixed_to_float(_p(acc), acc.numel(), _p(out), _lib.stream_ptr()), "pp_fixed_to_float")
+    _lib.call("pp_fixed_to_float", acc, acc.numel(), out)
     return out
 
 
@@ -664,12 +644,10 @@ class _Warp(torch.autograd.Function):
         dflow = torch.empty(B, H, W, 2, dtype=torch.float32, device=feat.device)
         if DETERMINISTIC:
             acc = torch.zeros(feat.shape, dtype=torch.int64, device=feat.device)
-            _lib.check(_lib.lib().pp_warp_backward_nhwc_fixed(_p(feat), _p(flow), _p(_f32c(dy)), B, H, W, C, flow.shape[-1], _p(acc), _p(dflow),
-                                                              _lib.stream_ptr()), "pp_warp_backward_nhwc_fixed")
+            _lib.call("pp_warp_backward_nhwc_fixed", feat, flow, _f32c(dy), B, H, W, C, flow.shape[-1], acc, dflow)
             return _fixed_to_float(acc), dflow
         dfeat = torch.zeros_like(feat)
-        _lib.check(_lib.lib().pp_warp_backward_nhwc(_p(feat), _p(flow), _p(_f32c(dy)), B, H, W, C, flow.shape[-1], _p(dfeat), _p(dflow),
-                                                    _lib.stream_ptr()), "pp_warp_backward_nhwc")
+        _lib.call("pp_warp_backward_nhwc", feat, flow, _f32c(dy), B, H, W, C, flow.shape[-1], dfeat, dflow)
         return dfeat, dflow
 
 
@@ -698,23 +676,21 @@ class _CorrLookup(torch.autograd.Function):
         df1 = torch.empty_like(f1)
         dflow = torch.empty(B, H, W, 2, dtype=torch.float32, device=f1.device)
         arr = ctypes.c_void_p * 3
-        fl = arr(*[_p(t) for t in pyr] + [None] * (3 - levels))
+        fl = arr(*[t.data_ptr() for t in pyr] + [None] * (3 - levels))
         if DETERMINISTIC:
             accs = [torch.zeros(t.shape, dtype=torch.int64, device=t.device) for t in pyr]
-            dl = arr(*[_p(t) for t in accs] + [None] * (3 - levels))
-            _lib.check(_lib.lib().pp_corr_lookup_backward_nhwc_fixed(_p(f1), fl, _p(flow), _p(dout), B, H, W, C, levels, r, flow.shape[-1],
-                                                                     dout.shape[-1], _p(df1), dl, _p(dflow), _lib.stream_ptr()),
-                       "pp_corr_lookup_backward_nhwc_fixed")
+            dl = arr(*[t.data_ptr() for t in accs] + [None] * (3 - levels))
+            _lib.call("pp_corr_lookup_backward_nhwc_fixed", f1, fl, flow, dout, B, H, W, C, levels, r, flow.shape[-1], dout.shape[-1],
+                      df1, dl, dflow)
             dpyr = [_fixed_to_float(a) for a in accs]
         else:
             dpyr = [torch.zeros_like(t) for t in pyr]
-            dl = arr(*[_p(t) for t in dpyr] + [None] * (3 - levels))
-            _lib.check(_lib.lib().pp_corr_lookup_backward_nhwc(_p(f1), fl, _p(flow), _p(dout), B, H, W, C, levels, r, flow.shape[-1], dout.shape[-1],
-                                                               _p(df1), dl, _p(dflow), _lib.stream_ptr()), "pp_corr_lookup_backward_nhwc")
+            dl = arr(*[t.data_ptr() for t in dpyr] + [None] * (3 - levels))
+            _lib.call("pp_corr_lookup_backward_nhwc", f1, fl, flow, dout, B, H, W, C, levels, r, flow.shape[-1], dout.shape[-1],
+                      df1, dl, dflow)
         for l in range(levels - 1, 0, -1):       # the pooling chain's adjoint, coarse to fine
             t = dpyr[l - 1]
-            _lib.check(_lib.lib().pp_avgpool2_backward_nhwc(_p(dpyr[l]), B, t.shape[1], t.shape[2], C, 1, _p(t), _lib.stream_ptr()),
-                       "pp_avgpool2_backward_nhwc")
+            _lib.call("pp_avgpool2_backward_nhwc", dpyr[l], B, t.shape[1], t.shape[2], C, 1, t)
         return df1, dpyr[0], dflow, None, None, None
 
 
@@ -750,9 +726,8 @@ class _FlowLoss(torch.autograd.Function):
     def forward(ctx, flow, cert, tar_pts, flow_weight, mask_weight, max_flow, eps):
         fl, ce, tp = _f32c(flow), _f32c(cert), _f32c(tar_pts)
         B, H, W, _ = fl.shape
-        L = _lib.lib()
-        part = torch.empty(L.pp_flow_loss_blocks(), 3, dtype=torch.float64, device=fl.device)
-        _lib.check(L.pp_flow_loss_sums(_p(fl), _p(ce), _p(tp), B, H, W, float(max_flow), _p(part), _lib.stream_ptr()), "pp_flow_loss_sums")
+        part = torch.empty(_lib.lib().pp_flow_loss_blocks(), 3, dtype=torch.float64, device=fl.device)
+        _lib.call("pp_flow_loss_sums", fl, ce, tp, B, H, W, float(max_flow), part)
         bce, l1, cnt = part.sum(0)
         ctx.save_for_backward(fl, ce, tp, cnt)
         ctx.cfg = (flow_weight, mask_weight, max_flow, eps)
@@ -766,8 +741,7 @@ class _FlowLoss(torch.autograd.Function):
         gf = (up_f.double() * fw / (cnt + eps)).float().reshape(1).contiguous()      # two device scalars (no host sync)
         gc = (up_c.double() * mw / (B * H * W)).float().reshape(1).contiguous()
         dfl, dce = torch.empty_like(fl), torch.empty_like(ce)
-        _lib.check(_lib.lib().pp_flow_loss_backward(_p(fl), _p(ce), _p(tp), B, H, W, float(max_flow), _p(gf), _p(gc), _p(dfl), _p(dce),
-                                                    _lib.stream_ptr()), "pp_flow_loss_backward")
+        _lib.call("pp_flow_loss_backward", fl, ce, tp, B, H, W, float(max_flow), gf, gc, dfl, dce)
         return dfl, dce, None, None, None, None, None
 
 
@@ -801,7 +775,7 @@ class _Conv2d(torch.autograd.Function):
         dz = _f32c(dy)
         if act:
             g = torch.empty_like(dz)
-            _lib.check(_lib.lib().pp_act_backward(_p(y), _p(dz), dz.numel(), ACT[act], _p(g), _lib.stream_ptr()), "pp_act_backward")
+            _lib.call("pp_act_backward", y, dz, dz.numel(), ACT[act], g)
             dz = g                                                        # relu'(z) = [y > 0]
         rows = B * H * W
         db = colsum(dz.view(-1, Cout)) if has_bias and ctx.needs_input_grad[2] else None
@@ -841,14 +815,14 @@ class _Conv2d(torch.autograd.Function):
                 # operand (x is a forward activation: in range as it is) — no fp32 im2col matrix, no split pass over it
                 A = ops.split_transposed(dz.view(rows, Cout), s)
                 Bt = ops.Split.empty(kk, rows, x.device)
-                _lib.check(_lib.lib().pp_im2col_t_operand(_p(x), B, H, W, Cx, k, 1, k // 2, _p(Bt.hl), Bt.terms, _lib.stream_ptr()), "pp_im2col_t_operand")
+                _lib.call("pp_im2col_t_operand", x, B, H, W, Cx, k, 1, k // 2, Bt.hl, Bt.terms)
                 if swap:
                     dwp = ops.matmul_operands(Bt, A, alpha_dev=_inv(s), ksplit=S).t().contiguous()
                 else:
                     dwp = ops.matmul_operands(A, Bt, alpha_dev=_inv(s), ksplit=S)
             else:
                 colT = torch.empty(k * k * Cx, rows, dtype=torch.float32, device=x.device)
-                _lib.check(_lib.lib().pp_im2col_t_nhwc(_p(x), B, H, W, Cx, k, 1, k // 2, _p(colT), _lib.stream_ptr()), "pp_im2col_t_nhwc")
+                _lib.call("pp_im2col_t_nhwc", x, B, H, W, Cx, k, 1, k // 2, colT)
                 if dzs is None:
                     dzs = _ew(1, dz, s[0:1], 1)
                 dzt = dzs.view(rows, Cout).t().contiguous()                   # (Cout, rows)
@@ -872,7 +846,7 @@ def _mm_kmajor(a, bt):
     kc = K // S
     part = ops.bmm_nt(a.view(M, S, kc).permute(1, 0, 2)[None], bt.view(N, S, kc).permute(1, 0, 2)[None])     # (1,S,M,N)
     r = torch.empty(M, N, dtype=torch.float32, device=a.device)
-    _lib.check(_lib.lib().pp_sum_slices(_p(part), S, M, N, None, 0, _p(r), _lib.stream_ptr()), "pp_sum_slices")
+    _lib.call("pp_sum_slices", part, S, M, N, None, 0, r)
     return r
 
 

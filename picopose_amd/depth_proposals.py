@@ -12,7 +12,6 @@ that touch at equal depth come out as one proposal, and the defaults below are s
 
 `plane_fit`, `components`, `component_stats` and `component_rle` wrap one ABI entry each; `depth_proposals` composes them with two
 host reads (the compact records, then the run counts)."""
-import ctypes
 import math
 
 import numpy as np
@@ -24,7 +23,6 @@ from .masks import MAX_MASKS, RunTable, counts_of_ends
 
 MAX_HYP = _lib.PP_PLANE_MAX_HYP
 FIELDS = ("root", "area", "xmin", "ymin", "xmax", "ymax", "border")        # the columns of component_stats' records
-_I32P = ctypes.POINTER(ctypes.c_int)
 
 
 def _number(name, v, lo=None, strict=False):
@@ -81,8 +79,7 @@ def plane_fit(depth, cams, *, tau=5.0, n_hyp=256, seed=0, min_inliers=1000):
     plane = torch.empty((B, 4), dtype=torch.float32, device=dev)
     plane64 = torch.empty((B, 4), dtype=torch.float64, device=dev)
     info = torch.empty((B, 4), dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().pp_depth_plane(depth.data_ptr(), cams.data_ptr(), B, H, W, n_hyp, seed, tau, min_inliers, ws.data_ptr(), ws.numel(),
-                                         plane.data_ptr(), plane64.data_ptr(), info.data_ptr(), _lib.stream_ptr()), "pp_depth_plane")
+    _lib.call("pp_depth_plane", depth, cams, B, H, W, n_hyp, seed, tau, min_inliers, ws, ws.numel(), plane, plane64, info)
     return {"plane": plane, "plane64": plane64, "info": info}
 
 
@@ -107,9 +104,7 @@ def components(depth, cams, plane, has_plane, *, min_height=10.0, max_height=400
     nbytes = _lib.workspace_bytes("pp_depth_components_workspace_bytes", B, H, W)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=depth.device) if nbytes else None
     labels = torch.empty((B, H, W), dtype=torch.int32, device=depth.device)
-    _lib.check(_lib.lib().pp_depth_components(depth.data_ptr(), cams.data_ptr(), plane.data_ptr(), has_plane.data_ptr(), B, H, W, lo, hi,
-                                              max_range, max_step, None if ws is None else ws.data_ptr(), nbytes, labels.data_ptr(),
-                                              _lib.stream_ptr()), "pp_depth_components")
+    _lib.call("pp_depth_components", depth, cams, plane, has_plane, B, H, W, lo, hi, max_range, max_step, ws, nbytes, labels)
     return labels
 
 
@@ -128,8 +123,7 @@ def component_stats(labels, *, min_area=1, max_area=None, drop_border=False, cap
     ws = torch.empty(_lib.workspace_bytes("pp_component_stats_workspace_bytes", B, H, W), dtype=torch.uint8, device=dev)
     n_q = torch.empty((B,), dtype=torch.int32, device=dev)
     recs = torch.empty((B, cap, len(FIELDS)), dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().pp_component_stats(labels.data_ptr(), B, H, W, min_area, max_area, int(bool(drop_border)), cap, ws.data_ptr(),
-                                             ws.numel(), n_q.data_ptr(), recs.data_ptr(), _lib.stream_ptr()), "pp_component_stats")
+    _lib.call("pp_component_stats", labels, B, H, W, min_area, max_area, int(bool(drop_border)), cap, ws, ws.numel(), n_q, recs)
     return n_q, recs
 
 
@@ -148,17 +142,15 @@ def component_rle(labels, selection):
     if ((b < 0) | (b >= B) | (root < 0) | (root >= H * W) | (x0 < 0) | (x0 > x1) | (x1 >= W) | (y0 < 0) | (y0 > y1) | (y1 >= H)).any():
         raise ValueError("selection: an image, root or box outside the frame")
     (labels,) = _device_tensors(labels)
-    dev, n, L = labels.device, len(sel), _lib.lib()
+    dev, n = labels.device, len(sel)
     sel_d = torch.from_numpy(sel).to(dev)
     counts = torch.empty((n,), dtype=torch.int32, device=dev)
-    _lib.check(L.pp_components_rle(labels.data_ptr(), B, H, W, sel_d.data_ptr(), sel.ctypes.data_as(_I32P), n, None, None, 0,
-                                   counts.data_ptr(), None, _lib.stream_ptr()), "pp_components_rle")
+    _lib.call("pp_components_rle", labels, B, H, W, sel_d, sel, n, None, None, 0, counts, None)
     off = np.zeros(n + 1, np.int32)
     np.cumsum(counts.cpu().numpy(), out=off[1:])
     table = RunTable.from_words(torch.empty((int(off[-1]) + n + 1,), dtype=torch.int32, device=dev), off)
     table.offset.copy_(torch.from_numpy(off))
-    _lib.check(L.pp_components_rle(labels.data_ptr(), B, H, W, sel_d.data_ptr(), sel.ctypes.data_as(_I32P), n, table.offset.data_ptr(),
-                                   off.ctypes.data_as(_I32P), table.n_runs, None, table.ends.data_ptr(), _lib.stream_ptr()), "pp_components_rle")
+    _lib.call("pp_components_rle", labels, B, H, W, sel_d, sel, n, table.offset, off, table.n_runs, None, table.ends)
     return table
 
 

@@ -12,7 +12,6 @@ sphere's rotation) stay where the input pose put them.  All iterations of all po
 
 This is the project's own algorithm.  The project it was modelled on refines with OpenCV's ppf_match_3d ICP after a centroid shift;
 parity with that ICP is unpinned and not attempted (OpenCV cannot run next to this library, and its sub-sampling makes it no oracle)."""
-import ctypes
 import math
 
 import numpy as np
@@ -132,7 +131,6 @@ def refine_poses_depth(models, obj_ids, R, t, K, depth, image_index=None, depth_
         out.update(R=f32(0, 3, 3), t=f32(0, 3), n_groups=0, near_count=i32(0))
         return out
     scn.require_gpu(dev)
-    L = _lib.lib()
     depth_d = scn.depth_mm(depth, scale, dev)
     poses = scn.pose44(Rh, th)
     windows, groups = plan_views(models, obj, img, poses, cams, H, W, near, margin, workspace_bytes)
@@ -146,14 +144,10 @@ def refine_poses_depth(models, obj_ids, R, t, K, depth, image_index=None, depth_
         need = _lib.workspace_bytes("pp_depth_refine_workspace_bytes", packed.samples, packed.faces, int(soff[-1]))
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         soff_d = torch.from_numpy(soff).to(dev)
-        at = lambda a, width: a.data_ptr() + v0 * width              # noqa: E731
-        opt = lambda key, width: at(out[key], width) if debug else None    # noqa: E731
-        _lib.check(L.pp_depth_refine(
-            ctypes.byref(packed.scene), boxes_d.data_ptr(), boxes.ctypes.data, soff_d.data_ptr(), soff.ctypes.data, depth_d.data_ptr(),
-            iterations, float(max_distance), min_points, float(min_cos), float(rcond), float(eps), float(max_translation),
-            float(max_rotation), ws.data_ptr(), ws.numel(), at(poses_out, 64), at(active, 4), at(out["status"], 4),
-            at(out["iterations"], 4), at(out["rank"], 4), at(out["n_points"], 4), at(out["rms_before"], 4), at(out["rms_after"], 4),
-            at(near_all, 4), opt("trajectory", (iterations + 1) * 64), opt("sums", iterations * N_SUMS * 8), _lib.stream_ptr()),
-            "pp_depth_refine")
+        opt = lambda key: out[key][v0:] if debug else None           # noqa: E731
+        _lib.call("pp_depth_refine", packed.scene, boxes_d, boxes, soff_d, soff, depth_d, iterations, float(max_distance), min_points,
+                  float(min_cos), float(rcond), float(eps), float(max_translation), float(max_rotation), ws, ws.numel(), poses_out[v0:],
+                  active[v0:], out["status"][v0:], out["iterations"][v0:], out["rank"][v0:], out["n_points"][v0:], out["rms_before"][v0:],
+                  out["rms_after"][v0:], near_all[v0:], opt("trajectory"), opt("sums"))
     out.update(R=poses_out[:, :3, :3].contiguous(), t=poses_out[:, :3, 3].contiguous(), n_groups=len(groups), near_count=near_all)
     return out

@@ -8,7 +8,6 @@ library, so parity with both is UNPINNED.  What is exact: the overlaps and the m
 
 The device computes the overlaps inside each (image, category) group (pp_rle_pack_bits, pp_det_overlaps) and the greedy matching per
 (group, area range, threshold) (pp_det_match); grouping, sorting and chunking before, and the accumulation after, are numpy on the host."""
-import ctypes
 import json
 import math
 import os
@@ -31,8 +30,6 @@ DEFAULT_WORKSPACE_BYTES = 256 << 20
 TILE = _lib.PP_DET_TILE
 MAX_GT = _lib.PP_DET_MAX_GT
 GT_IGNORE, GT_CROWD = 1, 2
-_I32P = ctypes.POINTER(ctypes.c_int)
-_F64P = ctypes.POINTER(ctypes.c_double)
 _KEYS = ("scene_id", "image_id", "category_id", "bbox")
 
 
@@ -186,7 +183,7 @@ def _tiles(groups):
     return np.ascontiguousarray(np.stack([g, (k // tj[g]) * TILE, (k % tj[g]) * TILE], axis=1), dtype=np.int32)
 
 
-def _run_chunk(L, dev, segm, hw, runs, boxes, groups, flags, det_area, gt_area, ranges, thrs, timings=None):
+def _run_chunk(dev, segm, hw, runs, boxes, groups, flags, det_area, gt_area, ranges, thrs, timings=None):
     """One chunk on the device: (pack,) overlaps, match -> (inter or None, iou, dt_match, dt_ignore, gt_match, gt_ignore) as numpy.
     timings: a dict that receives the device seconds of the pack, overlaps and match launches (event pairs on the current stream)."""
     marks = {}
@@ -218,12 +215,9 @@ def _run_chunk(L, dev, segm, hw, runs, boxes, groups, flags, det_area, gt_area, 
         inter = torch.zeros(max(n_pairs, 1), dtype=torch.int32, device=dev)
     else:
         boxes_d = up(boxes.ravel())
-    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-    gh = groups.ctypes.data_as(_I32P)
     mark("overlaps")
-    _lib.check(L.pp_det_overlaps(ptr(bits), ptr(area), words, ptr(boxes_d), n_det, n_gt, groups_d.data_ptr(), gh, n_groups, ptr(tiles_d),
-                                 tiles.ctypes.data_as(_I32P), len(tiles), flags_d.data_ptr(), n_pairs, ptr(inter), iou.data_ptr(),
-                                 _lib.stream_ptr()), "pp_det_overlaps")
+    _lib.call("pp_det_overlaps", bits, area, words, boxes_d, n_det, n_gt, groups_d, groups, n_groups, tiles_d, tiles, len(tiles), flags_d,
+              n_pairs, inter, iou)
     mark("overlaps")
     da_d, ga_d = up(det_area if n_det else np.zeros(1)), up(gt_area if n_gt else np.zeros(1))
     ranges_d, thrs_d = up(ranges.ravel()), up(thrs)
@@ -234,10 +228,8 @@ def _run_chunk(L, dev, segm, hw, runs, boxes, groups, flags, det_area, gt_area, 
     mark("match")
     # (the kernel indexes the tables with n_det and n_gt: they are allocated with exactly that width unless a side is empty,
     # and an empty side is never indexed)
-    _lib.check(L.pp_det_match(iou.data_ptr(), n_pairs, groups_d.data_ptr(), gh, n_groups, n_det, n_gt, da_d.data_ptr(), ga_d.data_ptr(),
-                              flags_d.data_ptr(), ranges_d.data_ptr(), ranges.ctypes.data_as(_F64P), A, thrs_d.data_ptr(),
-                              thrs.ctypes.data_as(_F64P), T, dt_match.data_ptr(), dt_ignore.data_ptr(), gt_match.data_ptr(),
-                              gt_ignore.data_ptr(), _lib.stream_ptr()), "pp_det_match")
+    _lib.call("pp_det_match", iou, n_pairs, groups_d, groups, n_groups, n_det, n_gt, da_d, ga_d, flags_d, ranges_d, ranges, A, thrs_d, thrs, T,
+              dt_match, dt_ignore, gt_match, gt_ignore)
     mark("match")
     host = lambda t: t.cpu().numpy()      # noqa: E731
     result = (host(inter)[:n_pairs] if segm else None, host(iou)[:n_pairs], host(dt_match)[:, :, :n_det], host(dt_ignore)[:, :, :n_det],
@@ -332,7 +324,6 @@ def match_detections(detections, annotations, iou_type="segm", iou_thrs=None, ar
     chunks += [(size, c[0]) for size, c in cur.items()]
     if torch.device(device).type != "cuda":
         raise _lib.PicoPoseHipError("picopose_amd runs on the GPU only: match_detections needs a CUDA(HIP) device")
-    L = _lib.lib()
     for size, qs in chunks:
         qs = np.array(qs, np.int64)
         cd, cg = nd[qs], ng[qs]
@@ -342,7 +333,7 @@ def match_detections(detections, annotations, iou_type="segm", iou_thrs=None, ar
         di, gi = det_index[dpos], gt_index[gpos]
         runs = [D.runs[n] for n in di] + [G.runs[n] for n in gi] if segm else None
         boxes = None if segm else np.concatenate([D.box[di], G.box[gi]])
-        inter, iou, dtm, dtig, gtm, gtig = _run_chunk(L, torch.device(device), segm, size[0] * size[1] if segm else 0, runs, boxes, groups,
+        inter, iou, dtm, dtig, gtm, gtig = _run_chunk(torch.device(device), segm, size[0] * size[1] if segm else 0, runs, boxes, groups,
                                                       G.flags[gi], det_area[dpos], G.area[gi], ranges, thrs, timings)
         if segm:
             out["inter"][ppos] = inter

@@ -26,7 +26,6 @@ restated by tests/vsd_oracle.py; the windows, the view groups and the packing of
 scene.py's, shared with depth_refine.py and scene_gt.py).  It is the BOP toolkit's VSD (visib_mode "bop19", step cost) written from memory: parity with
 the toolkit's pixels is unpinned, and a triangle that reaches the near plane is dropped whole where the toolkit's renderer clips it.
 match_and_score computes it when it is given the depth images, and then also returns AR = (AR_VSD + AR_MSSD + AR_MSPD) / 3."""
-import ctypes
 import json
 import math
 import os
@@ -260,25 +259,18 @@ def pose_errors(models, obj_ids, R_est, t_est, R_gt, t_gt, K=None, kinds=("mssd"
     if P == 0:
         return out
     scn.require_gpu(dev)
-    L = _lib.lib()
     mask = sum(KINDS[k] for k in set(kinds))
     chunk, need = _plan_chunks(models, pair_obj, mask, workspace_bytes)
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     pair_obj_d = torch.from_numpy(pair_obj).to(dev)
 
-    def ptr(t, p0, width):
-        return None if t is None else t.data_ptr() + p0 * width
-
     for p0 in range(0, P, chunk):
         n = min(chunk, P - p0)
-        _lib.check(L.pp_pose_errors(
-            models.vertices.data_ptr(), models.vert_off_d.data_ptr(), models.adds_vertices.data_ptr(), models.adds_off_d.data_ptr(),
-            models.sym_R.data_ptr(), models.sym_t.data_ptr(), models.sym_off_d.data_ptr(), models.vert_off.ctypes.data,
-            models.adds_off.ctypes.data, models.sym_off.ctypes.data, len(models.obj_ids), ptr(pair_obj_d, p0, 4),
-            pair_obj.ctypes.data + 4 * p0, ptr(Re, p0, 36), ptr(te, p0, 12), ptr(Rg, p0, 36), ptr(tg, p0, 12), ptr(focal, p0, 8), n,
-            mask, ws.data_ptr(), ws.numel(), ptr(out.get("mssd"), p0, 4), ptr(out.get("mssd_sym"), p0, 4), ptr(out.get("mspd"), p0, 4),
-            ptr(out.get("mspd_sym"), p0, 4), ptr(out.get("add"), p0, 4), ptr(out.get("adds"), p0, 4), _lib.stream_ptr()),
-            "pp_pose_errors")
+        at = lambda t: None if t is None else t[p0:]             # noqa: E731  (an optional per-pair table from pair p0 on)
+        _lib.call("pp_pose_errors", models.vertices, models.vert_off_d, models.adds_vertices, models.adds_off_d, models.sym_R, models.sym_t,
+                  models.sym_off_d, models.vert_off, models.adds_off, models.sym_off, len(models.obj_ids), pair_obj_d[p0:], pair_obj[p0:],
+                  Re[p0:], te[p0:], Rg[p0:], tg[p0:], at(focal), n, mask, ws, ws.numel(), at(out.get("mssd")), at(out.get("mssd_sym")),
+                  at(out.get("mspd")), at(out.get("mspd_sym")), at(out.get("add")), at(out.get("adds")))
     return out
 
 
@@ -286,7 +278,7 @@ def pose_errors(models, obj_ids, R_est, t_est, R_gt, t_gt, K=None, kinds=("mssd"
 def _vsd_launch(models, cams, H, W, view_obj, view_img, poses, windows, groups, near, pair_est=None, pair_gt=None, depth=None,
                 delta=15.0, taus=None, want_depth=False):
     """One pp_vsd_errors call per group -> (vsd, counts, per-view near counts, dense depth or None), device tensors."""
-    dev, L = models.device, _lib.lib()
+    dev = models.device
     scn.require_gpu(dev)
     U, P = len(view_obj), 0 if pair_est is None else len(pair_est)
     T = 1 if taus is None else len(taus)
@@ -299,21 +291,18 @@ def _vsd_launch(models, cams, H, W, view_obj, view_img, poses, windows, groups, 
         packed = scn.PackedScene(models, cams, H, W, near, view_obj[views], view_img[views], poses[views], windows[views])
         ws = torch.empty(_lib.workspace_bytes("pp_vsd_workspace_bytes", packed.samples, packed.faces), dtype=torch.uint8, device=dev)
         near_d = torch.empty(len(views), dtype=torch.int32, device=dev)
-        pe = pg = pe_d = pg_d = vsd_ptr = counts_ptr = dense_ptr = None
+        pe = pg = pe_d = pg_d = vsd_at = counts_at = dense_at = None
         n_pairs = 0
         if pairs is not None:
             local = {int(v): k for k, v in enumerate(views.tolist())}
             pe = np.array([local[int(v)] for v in pair_est[pairs]], dtype=np.int32)
             pg = np.array([local[int(v)] for v in pair_gt[pairs]], dtype=np.int32)
             pe_d, pg_d, n_pairs, p0 = torch.from_numpy(pe).to(dev), torch.from_numpy(pg).to(dev), len(pairs), int(pairs[0])
-            vsd_ptr, counts_ptr = vsd.data_ptr() + p0 * T * 4, counts.data_ptr() + p0 * (2 + T) * 4
-        ptr = lambda a: None if a is None else a.ctypes.data             # noqa: E731
-        dptr = lambda a: None if a is None else a.data_ptr()             # noqa: E731
+            vsd_at, counts_at = vsd[p0:], counts[p0:]
         if want_depth:                                            # (render_depth: the groups are consecutive views)
-            dense_ptr = dense.data_ptr() + int(views[0]) * H * W * 4
-        _lib.check(L.pp_vsd_errors(ctypes.byref(packed.scene), dptr(pe_d), dptr(pg_d), ptr(pe), ptr(pg), n_pairs, dptr(depth), float(delta),
-                                   taus_h.ctypes.data, T, ws.data_ptr(), ws.numel(), vsd_ptr, counts_ptr, near_d.data_ptr(), dense_ptr,
-                                   _lib.stream_ptr()), "pp_vsd_errors")
+            dense_at = dense[int(views[0]):]
+        _lib.call("pp_vsd_errors", packed.scene, pe_d, pg_d, pe, pg, n_pairs, depth, float(delta), taus_h, T, ws, ws.numel(),
+                  vsd_at, counts_at, near_d, dense_at)
         near_all[torch.from_numpy(views).to(dev)] = near_d
     return vsd, counts, near_all, dense
 

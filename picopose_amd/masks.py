@@ -22,7 +22,6 @@ from . import _lib
 from .utils.preprocess import CLIP_MEAN, CLIP_STD
 
 MAX_MASKS = _lib.PP_MASK_MAX_N       # the masks of one pp_rle_pack_bits, pp_mask_intersections or pp_components_rle call
-_I32P = ctypes.POINTER(ctypes.c_int)
 
 
 def _fail(what, index, msg):
@@ -174,8 +173,7 @@ class RunTable(NamedTuple):
         n, words, dev = len(self.offset_host) - 1, (hw + 31) // 32, self.ends.device
         bits = torch.empty((n, words), dtype=torch.int32, device=dev)
         area = torch.empty((n,), dtype=torch.int32, device=dev)
-        _lib.check(_lib.lib().pp_rle_pack_bits(self.ends.data_ptr(), self.n_runs, self.offset.data_ptr(), self.offset_host.ctypes.data_as(_I32P),
-                                               n, hw, words, bits.data_ptr(), area.data_ptr(), _lib.stream_ptr()), "pp_rle_pack_bits")
+        _lib.call("pp_rle_pack_bits", self.ends, self.n_runs, self.offset, self.offset_host, n, hw, words, bits, area)
         return bits, area
 
     def crop(self, frame_d, window_d, window, S, rgb_mask_flag, out_rgb, out_mask):
@@ -184,7 +182,5 @@ class RunTable(NamedTuple):
         float32 (any leading 1), resized and CLIP-normalised, on the current stream."""
         H, W = frame_d.shape[:2]
         mean, std = (ctypes.c_double * 3)(*CLIP_MEAN), (ctypes.c_double * 3)(*CLIP_STD)
-        _lib.check(_lib.lib().pp_detections_crop(frame_d.data_ptr(), H, W, self.ends.data_ptr(), self.n_runs, self.offset.data_ptr(),
-                                                 window_d.data_ptr(), self.offset_host.ctypes.data_as(_I32P), window.ctypes.data_as(_I32P),
-                                                 len(window), S, int(rgb_mask_flag), mean, std, out_rgb.data_ptr(), out_mask.data_ptr(),
-                                                 _lib.stream_ptr()), "pp_detections_crop")
+        _lib.call("pp_detections_crop", frame_d, H, W, self.ends, self.n_runs, self.offset, window_d, self.offset_host, window,
+                  len(window), S, int(rgb_mask_flag), mean, std, out_rgb, out_mask)

@@ -108,16 +108,15 @@ def _diameters(verts, device="cuda"):
     """ONE pp_model_diameter call over a list of float32 vertex arrays -> [(diameter float64, (i, j), d2max float32), ...]."""
     import torch
 
-    dev, L = _device(device), _lib.lib()
+    dev = _device(device)
     off = _offsets(verts)
-    need = _lib.workspace_bytes("pp_model_diameter_workspace_bytes", off.ctypes.data, len(verts))
+    need = _lib.workspace_bytes("pp_model_diameter_workspace_bytes", off, len(verts))
     with torch.cuda.device(dev):
         v_d, off_d = torch.from_numpy(np.concatenate(verts)).to(dev), torch.from_numpy(off).to(dev)
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         d2 = torch.empty(len(verts), dtype=torch.float32, device=dev)
         pair = torch.empty((len(verts), 2), dtype=torch.int32, device=dev)
-        _lib.check(L.pp_model_diameter(v_d.data_ptr(), off_d.data_ptr(), off.ctypes.data, len(verts), ws.data_ptr(), ws.numel(),
-                                       d2.data_ptr(), pair.data_ptr(), _lib.stream_ptr()), "pp_model_diameter")
+        _lib.call("pp_model_diameter", v_d, off_d, off, len(verts), ws, ws.numel(), d2, pair)
         d2, pair = d2.cpu().numpy(), pair.cpu().numpy()
     out = []
     for v, (i, j), d in zip(verts, pair.tolist(), d2):
@@ -143,7 +142,7 @@ def _hausdorff(verts, queries, cand_obj, T12, workspace_bytes=DEFAULT_WORKSPACE_
         return np.zeros(0, dtype=np.float32)
     if not (isinstance(workspace_bytes, (int, np.integer)) and workspace_bytes > 0):
         raise ValueError(f"workspace_bytes must be a positive int, got {workspace_bytes!r}")
-    dev, L = _device(device), _lib.lib()
+    dev = _device(device)
     same = all(q is v for q, v in zip(queries, verts))
     v_off, q_off = _offsets(verts), _offsets(queries)
     nq_max = int((q_off[1:] - q_off[:-1])[cand_obj].max())
@@ -158,10 +157,8 @@ def _hausdorff(verts, queries, cand_obj, T12, workspace_bytes=DEFAULT_WORKSPACE_
         h = torch.empty(C, dtype=torch.float32, device=dev)
         for c0 in range(0, C, group):
             n = min(group, C - c0)
-            _lib.check(L.pp_transform_hausdorff(v_d.data_ptr(), v_off_d.data_ptr(), q_d.data_ptr(), q_off_d.data_ptr(), v_off.ctypes.data,
-                                                q_off.ctypes.data, len(verts), obj_d.data_ptr() + 4 * c0, cand_obj.ctypes.data + 4 * c0,
-                                                T_d.data_ptr() + 48 * c0, n, ws.data_ptr(), ws.numel(), h.data_ptr() + 4 * c0,
-                                                _lib.stream_ptr()), "pp_transform_hausdorff")
+            _lib.call("pp_transform_hausdorff", v_d, v_off_d, q_d, q_off_d, v_off, q_off, len(verts), obj_d[c0:], cand_obj[c0:], T_d[c0:], n,
+                      ws, ws.numel(), h[c0:])
         return h.cpu().numpy()
 
 

@@ -96,7 +96,7 @@ def saturation_word(device=None):
         with torch.cuda.device(idx):
             w = torch.zeros(1, dtype=torch.int32, device=dev)
             torch.cuda.synchronize()      # (the zero is in place before the library's kernels may write the word from another stream)
-            _lib.check(_lib.lib().pp_set_saturation_word(_p(w)), "pp_set_saturation_word")
+            _lib.call("pp_set_saturation_word", w)
         _sat_words[idx] = w
     return w
 
@@ -130,7 +130,7 @@ def saturation_take(device, slot):
         if w is None:
             slot.zero_()
         else:
-            _lib.check(_lib.lib().pp_saturation_take(_p(w), _p(slot), _lib.stream_ptr()), "pp_saturation_take")
+            _lib.call("pp_saturation_take", w, slot)
     return slot
 
 
@@ -156,7 +156,7 @@ def split_weight(w, cache=True, t=None):
     if not cache:
         hl = torch.empty(w.shape[0], t * w.shape[1], dtype=torch.float16, device=w.device)
         scale = torch.empty(1, dtype=torch.float32, device=w.device)
-        _lib.check(_lib.lib().pp_split_weights_t(_p(w), w.numel(), t, _p(hl), _p(scale), _lib.stream_ptr()), "pp_split_weights_t")
+        _lib.call("pp_split_weights_t", w, w.numel(), t, hl, scale)
         return hl, float(scale.item())
     # keyed by the tensor's ADDRESS (+ shape, format); the version lives in the value: an optimizer step bumps the version, and the entry
     # of the old version — which can never be hit again — is overwritten in place instead of piling up (~4 bytes per
@@ -168,7 +168,7 @@ def split_weight(w, cache=True, t=None):
         hl = hit[0] if hit is not None and hit[0].shape == (w.shape[0], t * w.shape[1]) else \
             torch.empty(w.shape[0], t * w.shape[1], dtype=torch.float16, device=w.device)
         scale = torch.empty(1, dtype=torch.float32, device=w.device)
-        _lib.check(_lib.lib().pp_split_weights_t(_p(w), w.numel(), t, _p(hl), _p(scale), _lib.stream_ptr()), "pp_split_weights_t")
+        _lib.call("pp_split_weights_t", w, w.numel(), t, hl, scale)
         if len(_split_cache) > 4096:       # (last resort: thousands of distinct live weight tensors)
             _split_cache.clear()
         hit = _split_cache[key] = (hl, float(scale.item()), w, w._version)  # keep w alive so its address is not reused
@@ -190,7 +190,7 @@ def split_weight_dev(w):
         else:
             hl = torch.empty(w.shape[0], t * w.shape[1], dtype=torch.float16, device=w.device)
             buf = torch.empty(2 + 1024, dtype=torch.float32, device=w.device)
-        _lib.check(_lib.lib().pp_split_weights_ws(_p(w), w.numel(), t, _p(hl), _p(buf), _p(buf[2:]), _lib.stream_ptr()), "pp_split_weights_ws")
+        _lib.call("pp_split_weights_ws", w, w.numel(), t, hl, buf, buf[2:])
         if len(_split_cache) > 4096:
             _split_cache.clear()
         hit = _split_cache[key] = (hl, buf[:2], w, w._version, buf)
@@ -252,10 +252,10 @@ def split_weight_tracked(w, owner, tag=""):
     t = terms()
     hl = torch.empty(w.shape[0], t * w.shape[1], dtype=torch.float16, device=w.device)
     sdev = torch.full((1,), ent[0], dtype=torch.float32, device=w.device)
-    _lib.check(_lib.lib().pp_split_with_scale_t(_p(w), w.numel(), t, _p(sdev), _p(hl), _lib.stream_ptr()), "pp_split_with_scale_t")
+    _lib.call("pp_split_with_scale_t", w, w.numel(), t, sdev, hl)
     if ent[1] is None:
         s2 = torch.empty(2, dtype=torch.float32, device=w.device)
-        _lib.check(_lib.lib().pp_pow2_scale(_p(w), w.numel(), _p(s2), _lib.stream_ptr()), "pp_pow2_scale")
+        _lib.call("pp_pow2_scale", w, w.numel(), s2)
         host = torch.empty(2, dtype=torch.float32, pin_memory=True)
         host.copy_(s2, non_blocking=True)
         ev = torch.cuda.Event()
@@ -308,14 +308,12 @@ def split_activation(x, B, P, C, batch_stride, row_stride, relu=False, into=None
         tgt, col0 = into
         ctot = tgt.shape[1]
         assert tgt.shape[0] == B * P and col0 % 8 == 0 and col0 + C <= ctot
-        _lib.check(_lib.lib().pp_split_activation_t(_p(x), batch_stride, B, P, row_stride, C, int(relu),
-                                                    tgt.col_ptr(col0), ctot, t, _lib.stream_ptr()), "pp_split_activation_t")
+        _lib.call("pp_split_activation_t", x, batch_stride, B, P, row_stride, C, int(relu), tgt.col_ptr(col0), ctot, t)
         if CHECK_SATURATION:
             _chk(tgt.cols(col0, C), "pp_split_activation_t")
         return None
     hl = torch.empty(B * P, t * C, dtype=torch.float16, device=x.device)
-    _lib.check(_lib.lib().pp_split_activation_t(_p(x), batch_stride, B, P, row_stride, C, int(relu), _p(hl), C, t,
-                                                _lib.stream_ptr()), "pp_split_activation_t")
+    _lib.call("pp_split_activation_t", x, batch_stride, B, P, row_stride, C, int(relu), hl, C, t)
     return _chk(hl, "pp_split_activation_t")
 
 
@@ -328,8 +326,7 @@ def hl_patch_columns(x, tgt, col0):
     assert rows == tgt.shape[0] and col0 + c <= tgt.shape[1]
     assert x.is_contiguous() or (x.dim() >= 2 and x.stride(-1) == 1 and ld >= c
                                  and all(x.stride(i) == x.stride(i + 1) * x.shape[i + 1] for i in range(x.dim() - 2)))
-    _lib.check(_lib.lib().pp_hl_patch_columns_t(_p(x), ld, c, rows, _p(tgt.hl), tgt.shape[1], col0, tgt.terms, _lib.stream_ptr()),
-               "pp_hl_patch_columns_t")
+    _lib.call("pp_hl_patch_columns_t", x, ld, c, rows, tgt.hl, tgt.shape[1], col0, tgt.terms)
     if CHECK_SATURATION:   # (the 8-channel groups holding the patched columns; their other members are already written)
         _chk(tgt.cols(col0 // 8 * 8, -(-(col0 + c) // 8) * 8 - col0 // 8 * 8), "pp_hl_patch_columns_t")
 
@@ -342,7 +339,7 @@ def flow_operand(flow):
     assert flow.stride(1) == W * flow.stride(2) and flow.stride(0) == H * flow.stride(1)
     sp = Split.empty(B * H * W, 8, flow.device)
     sp.image = (B, H, W)
-    _lib.check(_lib.lib().pp_flow_operand(_p(flow), flow.stride(2), B * H * W, _p(sp.hl), sp.terms, _lib.stream_ptr()), "pp_flow_operand")
+    _lib.call("pp_flow_operand", flow, flow.stride(2), B * H * W, sp.hl, sp.terms)
     _chk(sp.hl, "pp_flow_operand")
     return sp
 
@@ -369,8 +366,7 @@ def patch_operand(bank, index, front=None):
     n, nf = index.numel(), 0 if front is None else front.shape[0]
     sp = Split.empty((nf + n) * H * W, 8, bank.device)
     sp.image = (nf + n, H, W)
-    _lib.check(_lib.lib().pp_patch_operand(_p(bank), R, _p(index.contiguous()), n, _p(front), nf, H, W, _p(sp.hl), sp.terms,
-                                           _lib.stream_ptr()), "pp_patch_operand")
+    _lib.call("pp_patch_operand", bank, R, index.contiguous(), n, front, nf, H, W, sp.hl, sp.terms)
     _chk(sp.hl, "pp_patch_operand")
     return sp
 
@@ -390,9 +386,9 @@ def _weight_args(w, K, cache=True):
     if presplit() and K % 8 == 0 and w.data_ptr() % 16 == 0:
         if cache == "dev":                 # a trained parameter: scale on the device, taken by the launch through alpha_dev
             hl, s2 = split_weight_dev(w)
-            return dict(prec=_PREC[precision()], B_hl=_p(hl), b_scale=1.0, alpha_dev=_p(s2[1:2]), _hl=(hl, s2))
+            return dict(prec=_PREC[precision()], B_hl=hl, b_scale=1.0, alpha_dev=s2[1:2], _hl=(hl, s2))
         hl, scale = split_weight_tracked(w, *cache) if isinstance(cache, tuple) else split_weight(w, cache)
-        return dict(prec=_PREC[precision()], B_hl=_p(hl), b_scale=scale, _hl=hl)
+        return dict(prec=_PREC[precision()], B_hl=hl, b_scale=scale, _hl=hl)
     return dict(prec=_fly_prec())
 
 
@@ -409,31 +405,32 @@ def _fly_args(wargs, w=None, cache=True):
     if precision() == "f16":
         if w is not None and cache is True and "B_hl" in wargs:
             hl, scale = split_weight(w, True, t=2)
-            return dict(prec=1, B_hl=_p(hl), b_scale=scale, _hl=hl)
+            return dict(prec=1, B_hl=hl, b_scale=scale, _hl=hl)
         return dict(prec=1)
     if "alpha_dev" in wargs:     # device-scaled weights (cache="dev") belong to the pre-split kernels: these launches read the fp32 weights
         return dict(prec=_fly_prec())
     return wargs
 
 
-def _p(t):
-    return t.data_ptr() if t is not None else None
-
-
 def _run(d, what="pp_gemm", written=None):
     """written: the Split this launch writes operand columns of (verified under CHECK_SATURATION)."""
-    _lib.check(_lib.lib().pp_gemm(ctypes.byref(d), _lib.stream_ptr()), what)
+    _lib.call("pp_gemm", d, what=what)
     if written is not None:
         _chk(written.hl, f"{what} epilogue (M={d.M}, N={d.N}, K={d.K})")
 
 
+_p = _lib.address        # the engine tests build descriptors from raw addresses under this name; no launch in the package spells it
+_DESC_POINTERS = frozenset(name for name, ctype in PpGemmDesc._fields_ if ctype is ctypes.c_void_p)
+
+
 def _desc(**kw):
+    """Pointer members take what a `void*` parameter of _lib.call takes: a tensor (its address), None (null) or a raw address."""
     d = PpGemmDesc()
     d.batch0 = d.batch1 = 1
     d.alpha = 1.0
     for k, v in kw.items():
         if not k.startswith("_"):     # (_hl: the operand tensor itself, carried so that it outlives the enqueue)
-            setattr(d, k, v)
+            setattr(d, k, _lib.address(v) if k in _DESC_POINTERS else v)
     return d
 
 
@@ -448,7 +445,7 @@ def linear(x, weight, bias=None, act=None, gamma=None, residual=None, out=None, 
     sargs, ret = {}, None
     if out_split and "B_hl" in wargs and _split_ok(N) and out is None:
         ret = Split.empty(M, N, x.device)
-        sargs = dict(C_hl=_p(ret.hl), ldc_h=N)
+        sargs = dict(C_hl=ret.hl, ldc_h=N)
     elif out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=x.device)
     ldc = N if out is None else out.stride(0)
@@ -459,19 +456,19 @@ def linear(x, weight, bias=None, act=None, gamma=None, residual=None, out=None, 
         assert tuple(residual.shape) == (M, N) and residual.stride(1) == 1 and residual.stride(0) == ldc
     if isinstance(x, Split):
         assert "B_hl" in wargs
-        _run(_desc(A_hl=_p(x.hl), B=_p(weight), C=_p(out), bias=_p(bias), gamma=_p(gamma), residual=_p(residual),
+        _run(_desc(A_hl=x.hl, B=weight, C=out, bias=bias, gamma=gamma, residual=residual,
                    M=M, N=N, K=K, lda=K, ldb=K, ldc=ldc, act=ACT[act], **wargs, **sargs), written=ret if sargs else None)
         return ret
     assert x.stride(1) == 1
     if "B_hl" in wargs and N > 64 and _can_presplit(x, K, K, x.stride(0)) and M * K < 2 ** 31:
         hl = split_activation(x, 1, M, K, 0, x.stride(0), relu=relu_in)          # every column tile reuses the split
-        _run(_desc(A_hl=_p(hl), B=_p(weight), C=_p(out), bias=_p(bias), gamma=_p(gamma), residual=_p(residual),
+        _run(_desc(A_hl=hl, B=weight, C=out, bias=bias, gamma=gamma, residual=residual,
                    M=M, N=N, K=K, lda=K, ldb=K, ldc=ldc, act=ACT[act], **wargs, **sargs), written=ret if sargs else None)
         return ret
     if sargs:  # the fp32-operand kernels write planes too, but keep this rare path simple: fp32 out + split pass
         out = torch.empty(M, N, dtype=torch.float32, device=x.device)
         ret, ldc, sargs = out, N, {}
-    _run(_desc(A=_p(x), B=_p(weight), C=_p(out), bias=_p(bias), gamma=_p(gamma), residual=_p(residual), M=M, N=N, K=K,
+    _run(_desc(A=x, B=weight, C=out, bias=bias, gamma=gamma, residual=residual, M=M, N=N, K=K,
                lda=x.stride(0), ldb=K, ldc=ldc, act=ACT[act], relu_in=int(relu_in), **_fly_args(wargs, weight, cache_weight)))
     return ret
 
@@ -482,7 +479,7 @@ def split_scaled(x2d, s2):
     rows, C = x2d.shape
     assert x2d.stride(1) == 1
     sp = Split.empty(rows, C, x2d.device)
-    _lib.check(_lib.lib().pp_split_scaled_t(_p(x2d), rows, x2d.stride(0), C, _p(s2), _p(sp.hl), sp.terms, _lib.stream_ptr()), "pp_split_scaled_t")
+    _lib.call("pp_split_scaled_t", x2d, rows, x2d.stride(0), C, s2, sp.hl, sp.terms)
     return sp
 
 
@@ -493,8 +490,7 @@ def split_transposed(x2d, s2=None, k_pad=None):
     assert x2d.stride(1) == 1 and rows % 8 == 0
     k_pad = rows if k_pad is None else k_pad
     sp = Split.empty(cols, k_pad, x2d.device)
-    _lib.check(_lib.lib().pp_split_transpose_ld(_p(x2d), rows, cols, x2d.stride(0), _p(s2), _p(sp.hl), k_pad, sp.terms, _lib.stream_ptr()),
-               "pp_split_transpose_ld")
+    _lib.call("pp_split_transpose_ld", x2d, rows, cols, x2d.stride(0), s2, sp.hl, k_pad, sp.terms)
     return sp
 
 
@@ -538,15 +534,15 @@ def matmul_operands(A, Bt, alpha_dev=(), out=None, ksplit=1):
     ad = list(alpha_dev) + [None, None]
     if ksplit > 1:
         part = torch.empty(ksplit, M, N, dtype=torch.float32, device=A.device)
-        _run(_desc(A_hl=_p(A.hl), B_hl=_p(Bt.hl), b_scale=4.0, C=_p(part), M=M, N=N, K=K, lda=K, ldb=K, ldc=N, prec=_PREC[precision()],
-                   alpha_dev=_p(ad[0]), alpha_dev2=_p(ad[1]), ksplit=ksplit, _keep=(A.hl, Bt.hl, part)))
+        _run(_desc(A_hl=A.hl, B_hl=Bt.hl, b_scale=4.0, C=part, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, prec=_PREC[precision()],
+                   alpha_dev=ad[0], alpha_dev2=ad[1], ksplit=ksplit, _keep=(A.hl, Bt.hl, part)))
         tgt = out if out.is_contiguous() else torch.empty(M, N, dtype=torch.float32, device=A.device)
-        _lib.check(_lib.lib().pp_sum_slices(_p(part), ksplit, M, N, None, 0, _p(tgt), _lib.stream_ptr()), "pp_sum_slices")
+        _lib.call("pp_sum_slices", part, ksplit, M, N, None, 0, tgt)
         if tgt is not out:
             out.copy_(tgt)
         return out
-    _run(_desc(A_hl=_p(A.hl), B_hl=_p(Bt.hl), b_scale=4.0, C=_p(out), M=M, N=N, K=K, lda=K, ldb=K, ldc=out.stride(0), prec=_PREC[precision()],
-               alpha_dev=_p(ad[0]), alpha_dev2=_p(ad[1]), _keep=(A.hl, Bt.hl)))
+    _run(_desc(A_hl=A.hl, B_hl=Bt.hl, b_scale=4.0, C=out, M=M, N=N, K=K, lda=K, ldb=K, ldc=out.stride(0), prec=_PREC[precision()],
+               alpha_dev=ad[0], alpha_dev2=ad[1], _keep=(A.hl, Bt.hl)))
     return out
 
 
@@ -562,9 +558,9 @@ def matmul_nt_presplit(a, bt):
             and M * K < 2 ** 30 and N * K < 2 ** 30:
         ah = split_activation(a, 1, M, K, 0, K)
         bh = split_activation(bt, 1, N, K, 0, K)
-        _run(_desc(A_hl=_p(ah), B=_p(bt), B_hl=_p(bh), b_scale=4.0, C=_p(out), M=M, N=N, K=K, lda=K, ldb=K, ldc=N, prec=_PREC[precision()]))
+        _run(_desc(A_hl=ah, B=bt, B_hl=bh, b_scale=4.0, C=out, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, prec=_PREC[precision()]))
         return out
-    _run(_desc(A=_p(a), B=_p(bt), C=_p(out), M=M, N=N, K=K, lda=K, ldb=K, ldc=N, prec=_fly_prec()))
+    _run(_desc(A=a, B=bt, C=out, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, prec=_fly_prec()))
     return out
 
 
@@ -580,7 +576,7 @@ def linear_splitk(x, weight, bias=None, act=None, slices=32):
     kc = K // slices
     part = bmm_nt(x.view(M, slices, kc).permute(1, 0, 2)[None], weight.view(N, slices, kc).permute(1, 0, 2)[None])
     out = torch.empty(M, N, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().pp_sum_slices(_p(part), slices, M, N, _p(bias), ACT[act], _p(out), _lib.stream_ptr()), "pp_sum_slices")
+    _lib.call("pp_sum_slices", part, slices, M, N, bias, ACT[act], out)
     return out
 
 
@@ -591,7 +587,7 @@ def bmm_nt(a, b, alpha=1.0, out=None):
     assert a.stride(3) == 1 and b.stride(3) == 1
     if out is None:
         out = torch.empty(Z0, Z1, M, N, dtype=torch.float32, device=a.device)
-    _run(_desc(A=_p(a), B=_p(b), C=_p(out), M=M, N=N, K=K, lda=a.stride(2), ldb=b.stride(2), ldc=out.stride(2),
+    _run(_desc(A=a, B=b, C=out, M=M, N=N, K=K, lda=a.stride(2), ldb=b.stride(2), ldc=out.stride(2),
                batch0=Z0, batch1=Z1, a_bs0=a.stride(0), a_bs1=a.stride(1), b_bs0=b.stride(0), b_bs1=b.stride(1),
                c_bs0=out.stride(0), c_bs1=out.stride(1), alpha=float(alpha), prec=_fly_prec()))
     return out
@@ -602,7 +598,7 @@ def bmm_nn(a, b, out, alpha=1.0):
     Z0, Z1, M, K = a.shape
     N = b.shape[3]
     assert a.stride(3) == 1 and b.stride(3) == 1 and out.stride(3) == 1
-    _run(_desc(A=_p(a), B=_p(b), C=_p(out), M=M, N=N, K=K, lda=a.stride(2), ldb=b.stride(2), ldc=out.stride(2), b_kn=1,
+    _run(_desc(A=a, B=b, C=out, M=M, N=N, K=K, lda=a.stride(2), ldb=b.stride(2), ldc=out.stride(2), b_kn=1,
                batch0=Z0, batch1=Z1, a_bs0=a.stride(0), a_bs1=a.stride(1), b_bs0=b.stride(0), b_bs1=b.stride(1),
                c_bs0=out.stride(0), c_bs1=out.stride(1), alpha=float(alpha), prec=_fly_prec()))
     return out
@@ -705,8 +701,7 @@ def conv2d(x, wp, bias, ksize, stride=1, pad=0, act=None, relu_in=False, residua
         # one- / two-channel predict layers of the decoder heads: a direct convolution on the operand (pp_conv_narrow_hl)
         # instead of a GEMM tile padded from 2 to 64 columns
         out = torch.empty(B, H, W, Cout, dtype=torch.float32, device=dev)
-        _lib.check(_lib.lib().pp_conv_narrow_hl(_p(xs.hl), Cx, B, H, W, Cx, _p(wp), _p(bias), ksize, Cout, _p(residual), _p(out),
-                                                _lib.stream_ptr()), "pp_conv_narrow_hl")
+        _lib.call("pp_conv_narrow_hl", xs.hl, Cx, B, H, W, Cx, wp, bias, ksize, Cout, residual, out)
         return out
     if (xs is None and precision() == "f32" and Cout <= 2 and ksize in (1, 3) and stride == 1 and pad == ksize // 2 and act is None and out is None
             and not relu_in and residual2 is None and cin == Cx and Cx % 32 == 0 and W in (16, 32, 64) and H % (256 // W) == 0
@@ -715,8 +710,7 @@ def conv2d(x, wp, bias, ksize, stride=1, pad=0, act=None, relu_in=False, residua
             and os.environ.get("PP_CONV_NARROW", "1") != "0"):
         # the same predict layers in the strict-fp32 mode: a direct fp32 convolution on the NHWC map (pp_conv_narrow_f32)
         out = torch.empty(B, H, W, Cout, dtype=torch.float32, device=dev)
-        _lib.check(_lib.lib().pp_conv_narrow_f32(_p(x), ld_in, B, H, W, Cx, _p(wp), _p(bias), ksize, Cout, _p(residual), _p(out),
-                                                 _lib.stream_ptr()), "pp_conv_narrow_f32")
+        _lib.call("pp_conv_narrow_f32", x, ld_in, B, H, W, Cx, wp, bias, ksize, Cout, residual, out)
         return out
     if (xs is None and ksize == 3 and stride == 1 and pad == 1 and Cout >= 32 and act in (None, "none", "relu", "leaky01")
             and _winograd_ok(B, H, W, cin, ld_in, x) and wp.dtype == torch.float32 and wp.is_contiguous()
@@ -741,7 +735,7 @@ def conv2d(x, wp, bias, ksize, stride=1, pad=0, act=None, relu_in=False, residua
             ldc = out.stride(2)
             assert out.stride(3) == 1 and out.stride(1) == Wo * ldc and out.stride(0) == Ho * Wo * ldc
         hl = xs.hl if xs is not None else split_activation(x, B, H * W, cin, x.stride(0), ld_in, relu=relu_in)
-        _run(_desc(A_hl=_p(hl), B=_p(wp), C=_p(out), bias=_p(bias), conv_bstride=H * W * cin, M=B * Ho * Wo, N=Cout,
+        _run(_desc(A_hl=hl, B=wp, C=out, bias=bias, conv_bstride=H * W * cin, M=B * Ho * Wo, N=Cout,
                    K=ksize * ksize * cin, lda=cin, ldb=wp.shape[1], ldc=ldc, act=ACT[act], conv_kh=ksize, conv_kw=ksize,
                    conv_cin=cin, conv_stride=stride, conv_pad=pad, conv_h=H, conv_w=W, conv_ho=Ho, conv_wo=Wo,
                    C_hl=tgt.col_ptr(col0), ldc_h=ctot, c_relu=int(split_relu), **wargs),
@@ -752,7 +746,7 @@ def conv2d(x, wp, bias, ksize, stride=1, pad=0, act=None, relu_in=False, residua
             and all(r_ is None or (r_.is_contiguous() and tuple(r_.shape) == (B, Ho, Wo, Cout)) for r_ in (residual, residual2))):
         ret = Split.empty(B * Ho * Wo, Cout, dev)
         ret.image = (B, Ho, Wo)
-        sargs = dict(C_hl=_p(ret.hl), ldc_h=Cout, c_relu=int(split_relu))
+        sargs = dict(C_hl=ret.hl, ldc_h=Cout, c_relu=int(split_relu))
         ldc = Cout
     else:
         if out is None:
@@ -767,22 +761,22 @@ def conv2d(x, wp, bias, ksize, stride=1, pad=0, act=None, relu_in=False, residua
     if also_split is not None and presplit and _split_ok(Cout) and not sargs and out.is_contiguous():
         extra = Split.empty(B * Ho * Wo, Cout, dev)
         extra.image = (B, Ho, Wo)
-        sargs = dict(C_hl=_p(extra.hl), ldc_h=Cout, c_relu=int(also_split == "relu"))
+        sargs = dict(C_hl=extra.hl, ldc_h=Cout, c_relu=int(also_split == "relu"))
         setattr(out, "_hl_relu" if also_split == "relu" else "_hl", extra)
     if presplit:
         assert "B_hl" in wargs
         hl = xs.hl if xs is not None else split_activation(x, B, H * W, cin, x.stride(0), ld_in, relu=relu_in)  # once, not per tap / column tile
         ld_a = ld_in if a_ptr is not None else cin
         ad = list(alpha_dev) + [None, None]
-        aargs = dict(alpha_dev=_p(ad[0]), alpha_dev2=_p(ad[1]))
-        _run(_desc(A_hl=a_ptr if a_ptr is not None else _p(hl), B=_p(wp), C=_p(out), bias=_p(bias), residual=_p(residual),
-                   residual2=_p(residual2), conv_bstride=H * W * ld_a, M=B * Ho * Wo, N=Cout, K=ksize * ksize * cin, lda=ld_a,
+        aargs = dict(alpha_dev=ad[0], alpha_dev2=ad[1])
+        _run(_desc(A_hl=a_ptr if a_ptr is not None else hl, B=wp, C=out, bias=bias, residual=residual,
+                   residual2=residual2, conv_bstride=H * W * ld_a, M=B * Ho * Wo, N=Cout, K=ksize * ksize * cin, lda=ld_a,
                    ldb=wp.shape[1], ldc=ldc, act=ACT[act], conv_kh=ksize, conv_kw=ksize, conv_cin=cin, conv_stride=stride,
                    conv_pad=pad, conv_h=H, conv_w=W, conv_ho=Ho, conv_wo=Wo, **wargs, **sargs, **aargs),
              written=(extra if extra is not None else ret) if sargs else None)
         return ret
     assert not alpha_dev
-    _run(_desc(A=_p(x), B=_p(wp), C=_p(out), bias=_p(bias), residual=_p(residual), residual2=_p(residual2),
+    _run(_desc(A=x, B=wp, C=out, bias=bias, residual=residual, residual2=residual2,
                conv_bstride=x.stride(0), M=B * Ho * Wo, N=Cout,
                K=ksize * ksize * cin, lda=ld_in, ldb=wp.shape[1], ldc=ldc, act=ACT[act], relu_in=int(relu_in),
                conv_kh=ksize, conv_kw=ksize, conv_cin=cin, conv_stride=stride, conv_pad=pad, conv_h=H, conv_w=W,
@@ -806,7 +800,7 @@ def winograd_weight(wp, cin):
     if hit is None or hit[2] != wp._version:
         Cout = wp.shape[0]
         V = hit[0] if hit is not None else torch.empty(16, Cout, cin, dtype=torch.float32, device=wp.device)
-        _lib.check(_lib.lib().pp_winograd_weight_f32(_p(wp), Cout, cin, wp.shape[1], _p(V), _lib.stream_ptr()), "pp_winograd_weight_f32")
+        _lib.call("pp_winograd_weight_f32", wp, Cout, cin, wp.shape[1], V)
         if len(_wino_cache) > 1024:
             _wino_cache.clear()
         hit = _wino_cache[key] = (V, wp, wp._version)
@@ -845,8 +839,7 @@ def winograd_shared(x, relu=False, cout=None):
     if not (x.stride(3) == 1 and x.stride(1) == W * x.stride(2) and _winograd_ok(B, H, W, C, x.stride(2), x)):
         return x
     U = torch.empty(16, B * (H // 2) * (W // 2), C, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().pp_winograd_input_f32(_p(x), x.stride(2), x.stride(0), B, H, W, C, int(relu), _p(U), _lib.stream_ptr()),
-               "pp_winograd_input_f32")
+    _lib.call("pp_winograd_input_f32", x, x.stride(2), x.stride(0), B, H, W, C, int(relu), U)
     return WinoInput(U, (B, H, W, C), bool(relu))
 
 
@@ -858,7 +851,6 @@ def _conv3x3_winograd(x, wp, bias, B, H, W, cin, ld_in, Cout, act, relu_in, resi
     products on the engine, output transform with bias / activation / residuals.  Everything fp32.  x: the map, or its WinoInput.
     chain_next (True | "relu"): return the WinoInput of the next 3x3 layer (Cout -> .) instead of the map (pp_winograd_chain_f32)."""
     P = B * (H // 2) * (W // 2)
-    L = _lib.lib()
     V = winograd_weight(wp, cin)
     if isinstance(x, WinoInput):
         assert x.geom == (B, H, W, cin) and x.relu == bool(relu_in)
@@ -866,21 +858,20 @@ def _conv3x3_winograd(x, wp, bias, B, H, W, cin, ld_in, Cout, act, relu_in, resi
     else:
         dev = x.device
         U = torch.empty(16, P, cin, dtype=torch.float32, device=dev)
-        _lib.check(L.pp_winograd_input_f32(_p(x), ld_in, x.stride(0), B, H, W, cin, int(relu_in), _p(U), _lib.stream_ptr()), "pp_winograd_input_f32")
+        _lib.call("pp_winograd_input_f32", x, ld_in, x.stride(0), B, H, W, cin, int(relu_in), U)
     Y = torch.empty(16, P, Cout, dtype=torch.float32, device=dev)
     # the sixteen products as batches of one pp_gemm call each: the engine runs a batch as ONE persistent launch (row tiles of all its
     # products, include/picopose_hip.h grp_rows) while the stacked operand / result blocks stay inside its 32-bit byte offsets
     per = max(1, min(16, (0xF0000000 // (4 * P * max(cin, Cout))))) if P % 256 == 0 else 1    # (a row tile must lie inside one product)
     for x0 in range(0, 16, per):
         n = min(per, 16 - x0)
-        _run(_desc(A=_p(U[x0]), B=_p(V[x0]), C=_p(Y[x0]), M=P, N=Cout, K=cin, lda=cin, ldb=cin, ldc=Cout, prec=0, batch0=n,
+        _run(_desc(A=U[x0], B=V[x0], C=Y[x0], M=P, N=Cout, K=cin, lda=cin, ldb=cin, ldc=Cout, prec=0, batch0=n,
                    a_bs0=P * cin, b_bs0=Cout * cin, c_bs0=P * Cout))
     if (chain_next and WINO2_CHAIN and WINOGRAD and out is None and residual is None and residual2 is None and W in (16, 32, 64) and Cout % 32 == 0
             and B * H * W >= (WINOGRAD_MIN_PIXELS if P % 256 == 0 else 4 * WINOGRAD_MIN_PIXELS)):
         # the next layer's Winograd input straight from this layer's products: h = act(A^T Y A + bias) lives in LDS only
         U1 = torch.empty(16, P, Cout, dtype=torch.float32, device=dev)
-        _lib.check(L.pp_winograd_chain_f32(_p(Y), B, H, W, Cout, _p(bias), ACT[act], int(chain_next == "relu"), _p(U1), _lib.stream_ptr()),
-                   "pp_winograd_chain_f32")
+        _lib.call("pp_winograd_chain_f32", Y, B, H, W, Cout, bias, ACT[act], int(chain_next == "relu"), U1)
         return WinoInput(U1, (B, H, W, Cout), chain_next == "relu", chained=True)
     if out is None:
         out = torch.empty(B, H, W, Cout, dtype=torch.float32, device=dev)
@@ -889,8 +880,7 @@ def _conv3x3_winograd(x, wp, bias, B, H, W, cin, ld_in, Cout, act, relu_in, resi
     for r_ in (residual, residual2):
         if r_ is not None:
             assert r_.stride() == out.stride()
-    _lib.check(L.pp_winograd_output_f32(_p(Y), B, H, W, Cout, _p(bias), ACT[act], _p(residual), _p(residual2), _p(out), ldc, _lib.stream_ptr()),
-               "pp_winograd_output_f32")
+    _lib.call("pp_winograd_output_f32", Y, B, H, W, Cout, bias, ACT[act], residual, residual2, out, ldc)
     return out
 
 
@@ -933,9 +923,9 @@ def winograd4_weight(wp, cin):
         Cout = wp.shape[0]
         V = hit[0] if hit is not None else torch.empty(36 * Cout, cin, dtype=torch.float32, device=wp.device)
         hl = hit[3] if hit is not None else torch.empty(36 * Cout, 2 * cin, dtype=torch.float16, device=wp.device)
-        _lib.check(_lib.lib().pp_winograd4_weight_f32(_p(wp), Cout, cin, wp.shape[1], _p(V), _lib.stream_ptr()), "pp_winograd4_weight_f32")
+        _lib.call("pp_winograd4_weight_f32", wp, Cout, cin, wp.shape[1], V)
         scale = torch.empty(1, dtype=torch.float32, device=wp.device)
-        _lib.check(_lib.lib().pp_split_weights_t(_p(V), V.numel(), 2, _p(hl), _p(scale), _lib.stream_ptr()), "pp_split_weights_t")
+        _lib.call("pp_split_weights_t", V, V.numel(), 2, hl, scale)
         if len(_wino_cache) > 1024:
             _wino_cache.clear()
         hit = _wino_cache[key] = (V, wp, wp._version, hl, float(scale.item()))
@@ -947,7 +937,7 @@ def _winograd4_input(src_ptr, ld_x, B, H, W, cin, dev):
     Pp = _wino4_rows(P)
     # (pad rows: zeros, so that the products of the pad rows are finite — they are never read)
     U = Split((torch.empty if Pp == P else torch.zeros)(36 * Pp, 2 * cin, dtype=torch.float16, device=dev), 2)
-    _lib.check(_lib.lib().pp_winograd4_input_hl(src_ptr, ld_x, H * W * ld_x, B, H, W, cin, 0, _p(U.hl), Pp, _lib.stream_ptr()), "pp_winograd4_input_hl")
+    _lib.call("pp_winograd4_input_hl", src_ptr, ld_x, H * W * ld_x, B, H, W, cin, 0, U.hl, Pp)
     _chk(U.hl, "pp_winograd4_input_hl")
     return U
 
@@ -963,7 +953,7 @@ def _wino4_products(U, V, vhl, vscale, Pp, cin, N):
     per = max(1, min(WINO4_GROUPS_PER_LAUNCH, 0xF0000000 // (4 * Pp * max(cin, N))))
     for x0 in range(0, 36, per):
         n = min(per, 36 - x0)
-        _run(_desc(A_hl=U.hl.data_ptr() + x0 * Pp * cin * 4, B=_p(V), B_hl=vhl.data_ptr() + x0 * N * cin * 4, b_scale=vscale, C=_p(Y[x0]),
+        _run(_desc(A_hl=U.hl.data_ptr() + x0 * Pp * cin * 4, B=V, B_hl=vhl.data_ptr() + x0 * N * cin * 4, b_scale=vscale, C=Y[x0],
                    M=Pp, N=N, K=cin, lda=cin, ldb=cin, ldc=N, prec=_PREC["f16x3"], batch0=n, a_bs0=Pp * cin, b_bs0=N * cin,
                    c_bs0=Pp * N, alpha=PP_A_SCALE / WINO4_U_SCALE, _keep=(U, vhl, V)))
     return Y
@@ -973,7 +963,7 @@ def _wino4_finish(Y, col0, ldy, bias, B, H, W, Cout, act, residual, residual2, o
     """Output side of a Winograd F(4x4) layer whose products are columns col0 .. col0 + Cout of Y (36, Pp, ldy): the chained transform into
     the next layer's WinoInput4, or the output transform into an operand and / or an fp32 map."""
     P = B * (H // 4) * (W // 4)
-    Pp, dev, L = _wino4_rows(P), Y.device, _lib.lib()
+    Pp, dev = _wino4_rows(P), Y.device
     yp = Y.data_ptr() + 4 * col0
     ret, hl_t, ldc = None, None, 0
     split_relu = bool(split_relu) or chain_next == "relu"     # wino_next="relu": the consumer's input ReLU, folded into the operand either way
@@ -982,7 +972,7 @@ def _wino4_finish(Y, col0, ldy, bias, B, H, W, Cout, act, residual, residual2, o
             and _winograd4_ok(B, H, W, Cout, Cout)):
         # the next layer's Winograd input straight from this layer's products: h = act(A^T Y A + bias) lives in LDS only
         U1 = Split((torch.empty if Pp == P else torch.zeros)(36 * Pp, 2 * Cout, dtype=torch.float16, device=dev), 2)
-        _lib.check(L.pp_winograd4_chain(yp, ldy, B, H, W, Cout, _p(bias), ACT[act], int(split_relu), _p(U1.hl), Pp, _lib.stream_ptr()), "pp_winograd4_chain")
+        _lib.call("pp_winograd4_chain", yp, ldy, B, H, W, Cout, bias, ACT[act], int(split_relu), U1.hl, Pp)
         _chk(U1.hl, "pp_winograd4_chain")
         return WinoInput4(U1, (B, H, W, Cout), None)
     if out_split and out is None and residual is None and residual2 is None:
@@ -1003,8 +993,8 @@ def _wino4_finish(Y, col0, ldy, bias, B, H, W, Cout, act, residual, residual2, o
             hl_t.image = (B, H, W)
             c_relu = int(also_split == "relu")
             setattr(out, "_hl_relu" if also_split == "relu" else "_hl", hl_t)
-    _lib.check(L.pp_winograd4_output(yp, ldy, B, H, W, Cout, _p(bias), ACT[act], _p(residual), _p(residual2), _p(out), ldc,
-                                     _p(hl_t.hl) if hl_t is not None else None, Cout, c_relu, Pp, _lib.stream_ptr()), "pp_winograd4_output")
+    _lib.call("pp_winograd4_output", yp, ldy, B, H, W, Cout, bias, ACT[act], residual, residual2, out, ldc,
+              hl_t.hl if hl_t is not None else None, Cout, c_relu, Pp)
     if hl_t is not None:
         _chk(hl_t.hl, "pp_winograd4_output")
     return ret
@@ -1043,7 +1033,7 @@ def winograd4_weight_pair(wp_a, wp_b, cin):
         V = torch.cat([Va.view(36, Ca, cin), Vb.view(36, Cb, cin)], dim=1).reshape(36 * (Ca + Cb), cin).contiguous()
         hl = torch.empty(V.shape[0], 2 * cin, dtype=torch.float16, device=V.device)
         scale = torch.empty(1, dtype=torch.float32, device=V.device)
-        _lib.check(_lib.lib().pp_split_weights_t(_p(V), V.numel(), 2, _p(hl), _p(scale), _lib.stream_ptr()), "pp_split_weights_t")
+        _lib.call("pp_split_weights_t", V, V.numel(), 2, hl, scale)
         hit = _wino_cache[key] = (V, (wp_a, wp_b), (wp_a._version, wp_b._version), hl, float(scale.item()))
     return hit[0], hit[3], hit[4]
 
@@ -1095,16 +1085,16 @@ def conv_transpose2d(x, wp, bias_tiled, r, out_split=False):
         if out_split and _split_ok(Cout):
             sp = Split.empty(B * H * r * W * r, Cout, dev)
             sp.image = (B, H * r, W * r)
-            _run(_desc(A_hl=_p(hl), B=_p(wp), C=None, bias=_p(bias_tiled), M=B * H * W, N=r * r * Cout, K=Cin,
-                       lda=Cin, ldb=Cin, ldc=Cout, shuffle_r=r, shuffle_h=H, shuffle_w=W, C_hl=_p(sp.hl), ldc_h=Cout, **wargs),
+            _run(_desc(A_hl=hl, B=wp, C=None, bias=bias_tiled, M=B * H * W, N=r * r * Cout, K=Cin,
+                       lda=Cin, ldb=Cin, ldc=Cout, shuffle_r=r, shuffle_h=H, shuffle_w=W, C_hl=sp.hl, ldc_h=Cout, **wargs),
                  written=sp)
             return sp
         out = torch.empty(B, H * r, W * r, Cout, dtype=torch.float32, device=dev)
-        _run(_desc(A_hl=_p(hl), B=_p(wp), C=_p(out), bias=_p(bias_tiled), M=B * H * W, N=r * r * Cout, K=Cin,
+        _run(_desc(A_hl=hl, B=wp, C=out, bias=bias_tiled, M=B * H * W, N=r * r * Cout, K=Cin,
                    lda=Cin, ldb=Cin, ldc=Cout, shuffle_r=r, shuffle_h=H, shuffle_w=W, **wargs))
         return out
     out = torch.empty(B, H * r, W * r, Cout, dtype=torch.float32, device=x.device)
-    _run(_desc(A=_p(x), B=_p(wp), C=_p(out), bias=_p(bias_tiled), M=B * H * W, N=r * r * Cout, K=Cin, lda=Cin, ldb=Cin,
+    _run(_desc(A=x, B=wp, C=out, bias=bias_tiled, M=B * H * W, N=r * r * Cout, K=Cin, lda=Cin, ldb=Cin,
                ldc=Cout, shuffle_r=r, shuffle_h=H, shuffle_w=W, **_fly_args(wargs, wp)))
     return out
 
@@ -1120,14 +1110,12 @@ def attention(qkv, B, T, heads, hd, out_split=False):
     else:
         out = torch.empty(B * T, heads * hd, dtype=torch.float32, device=dev)
     if isinstance(qkv, Split):
-        _lib.check(_lib.lib().pp_attention_t(_p(qkv.hl), qkv.terms, B, T, heads, hd, float(hd) ** -0.5, _p(out),
-                                             _p(sp.hl) if sp else None, _lib.stream_ptr()), "pp_attention_t")
+        _lib.call("pp_attention_t", qkv.hl, qkv.terms, B, T, heads, hd, float(hd) ** -0.5, out, sp.hl if sp else None)
     else:
         assert qkv.is_contiguous()
         if sp is not None and sp.terms == 1:    # (f16 mode with an fp32 qkv: the fp32-input kernel writes hl operands only)
             sp, out = None, torch.empty(B * T, heads * hd, dtype=torch.float32, device=dev)
-        _lib.check(_lib.lib().pp_attention_ex(_p(qkv), B, T, heads, hd, float(hd) ** -0.5, _fly_prec(), _p(out),
-                                              _p(sp.hl) if sp else None, _lib.stream_ptr()), "pp_attention_ex")
+        _lib.call("pp_attention_ex", qkv, B, T, heads, hd, float(hd) ** -0.5, _fly_prec(), out, sp.hl if sp else None)
     if sp is not None:
         _chk(sp.hl, "pp_attention")
     return sp if sp is not None else out
@@ -1139,13 +1127,11 @@ def layernorm(x, weight, bias, eps, out_split=False):
     assert x.is_contiguous()
     if out_split and _split_ok(C):
         sp = Split.empty(rows, C, x.device)
-        _lib.check(_lib.lib().pp_layernorm_t(_p(x), _p(weight), _p(bias), rows, C, float(eps), None, _p(sp.hl), sp.terms,
-                                             _lib.stream_ptr()), "pp_layernorm_t")
+        _lib.call("pp_layernorm_t", x, weight, bias, rows, C, float(eps), None, sp.hl, sp.terms)
         _chk(sp.hl, "pp_layernorm_t")
         return sp
     y = torch.empty_like(x)
-    _lib.check(_lib.lib().pp_layernorm(_p(x), _p(weight), _p(bias), rows, C, float(eps), _p(y), _lib.stream_ptr()),
-               "pp_layernorm")
+    _lib.call("pp_layernorm", x, weight, bias, rows, C, float(eps), y)
     return y
 
 
@@ -1153,7 +1139,7 @@ def softmax_rows_(x):
     """In-place softmax over the last dim of a contiguous (..., n) tensor."""
     assert x.is_contiguous()
     n = x.shape[-1]
-    _lib.check(_lib.lib().pp_softmax_rows(_p(x), x.numel() // n, n, n, _lib.stream_ptr()), "pp_softmax_rows")
+    _lib.call("pp_softmax_rows", x, x.numel() // n, n, n)
     return x
 
 
@@ -1161,8 +1147,7 @@ def groupnorm(x, weight, bias, groups, eps=1e-5, relu=False):
     B, H, W, C = x.shape
     assert x.is_contiguous()
     y = torch.empty_like(x)
-    _lib.check(_lib.lib().pp_groupnorm_nhwc(_p(x), _p(weight), _p(bias), B, H * W, C, groups, float(eps), int(relu),
-                                            _p(y), _lib.stream_ptr()), "pp_groupnorm_nhwc")
+    _lib.call("pp_groupnorm_nhwc", x, weight, bias, B, H * W, C, groups, float(eps), int(relu), y)
     return y
 
 
@@ -1173,16 +1158,13 @@ def batchnorm_train(x, bn, relu=False, residual=None, residual2=None, eps=1e-5, 
     assert x.is_contiguous() and x.dtype == torch.float32
     C = x.shape[-1]
     rows = x.numel() // C
-    L = _lib.lib()
-    nbytes = L.pp_batchnorm_train_workspace_bytes(rows, C)
+    nbytes = _lib.lib().pp_batchnorm_train_workspace_bytes(rows, C)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     y = torch.empty_like(x)
     for r in (residual, residual2):
         assert r is None or (r.is_contiguous() and r.shape == x.shape)
-    _lib.check(L.pp_batchnorm_train(_p(x), _p(bn.weight), _p(bn.bias), rows, C, float(eps), float(momentum), _p(bn.running_mean),
-                                    _p(bn.running_var), int(relu), _p(residual) if residual is not None else None,
-                                    _p(residual2) if residual2 is not None else None, _p(y), _p(ws), nbytes, _lib.stream_ptr()),
-               "pp_batchnorm_train")
+    _lib.call("pp_batchnorm_train", x, bn.weight, bn.bias, rows, C, float(eps), float(momentum), bn.running_mean, bn.running_var,
+              int(relu), residual, residual2, y, ws, nbytes)
     bn.num_batches_tracked += 1
     return y
 
@@ -1193,8 +1175,7 @@ def to_nhwc(x, c_pad=None):
     x = x.contiguous().float()
     Cp = c_pad if c_pad and c_pad > C else C
     out = (torch.zeros if Cp > C else torch.empty)(B, H, W, Cp, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().pp_transpose_batched(_p(x), 0, B, C, H * W, _p(out), 0, Cp, 0, _lib.stream_ptr()),
-               "pp_transpose_batched")
+    _lib.call("pp_transpose_batched", x, 0, B, C, H * W, out, 0, Cp, 0)
     return out
 
 
@@ -1203,8 +1184,7 @@ def to_nchw(x):
     B, H, W, C = x.shape
     assert x.is_contiguous()
     out = torch.empty(B, C, H, W, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().pp_transpose_batched(_p(x), 0, B, H * W, C, _p(out), 0, H * W, 0, _lib.stream_ptr()),
-               "pp_transpose_batched")
+    _lib.call("pp_transpose_batched", x, 0, B, H * W, C, out, 0, H * W, 0)
     return out
 
 
@@ -1218,21 +1198,18 @@ def resize_bilinear(x, Ho, Wo, mul=1.0, out_split=False, also_split=False):
         out = torch.empty(B, Ho, Wo, C, dtype=torch.float32, device=x.device)
         sp = Split.empty(B * Ho * Wo, C, x.device)
         sp.image = (B, Ho, Wo)
-        _lib.check(_lib.lib().pp_resize_bilinear_nhwc_dual(_p(x), B, H, W, C, Ho, Wo, float(mul), _p(out), _p(sp.hl), sp.terms,
-                                                            _lib.stream_ptr()), "pp_resize_bilinear_nhwc_dual")
+        _lib.call("pp_resize_bilinear_nhwc_dual", x, B, H, W, C, Ho, Wo, float(mul), out, sp.hl, sp.terms)
         _chk(sp.hl, "pp_resize_bilinear_nhwc_dual")
         out._hl = sp
         return out
     if out_split and _split_ok(C) and x.data_ptr() % 16 == 0:
         sp = Split.empty(B * Ho * Wo, C, x.device)
         sp.image = (B, Ho, Wo)
-        _lib.check(_lib.lib().pp_resize_bilinear_nhwc_t(_p(x), B, H, W, C, Ho, Wo, float(mul), _p(sp.hl), sp.terms, _lib.stream_ptr()),
-                   "pp_resize_bilinear_nhwc_t")
+        _lib.call("pp_resize_bilinear_nhwc_t", x, B, H, W, C, Ho, Wo, float(mul), sp.hl, sp.terms)
         _chk(sp.hl, "pp_resize_bilinear_nhwc_t")
         return sp
     out = torch.empty(B, Ho, Wo, C, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().pp_resize_bilinear_nhwc(_p(x), B, H, W, C, Ho, Wo, float(mul), _p(out), _lib.stream_ptr()),
-               "pp_resize_bilinear_nhwc")
+    _lib.call("pp_resize_bilinear_nhwc", x, B, H, W, C, Ho, Wo, float(mul), out)
     return out
 
 
@@ -1248,15 +1225,13 @@ def warp(feat, flow, out=None, hl_into=None):
         tgt, col0 = hl_into
         ctot = tgt.shape[1]
         assert tgt.shape[0] == B * H * W and col0 % 8 == 0 and col0 + C <= ctot and C % 8 == 0
-        _lib.check(_lib.lib().pp_warp_nhwc_t(_p(feat), Bf, _p(flow), B, H, W, C, flow.stride(2), tgt.col_ptr(col0),
-                                             ctot, tgt.terms, _lib.stream_ptr()), "pp_warp_nhwc_t")
+        _lib.call("pp_warp_nhwc_t", feat, Bf, flow, B, H, W, C, flow.stride(2), tgt.col_ptr(col0), ctot, tgt.terms)
         if CHECK_SATURATION:
             _chk(tgt.cols(col0, C), "pp_warp_nhwc_t")
         return None
     if out is None:
         out = torch.empty(B, H, W, C, dtype=torch.float32, device=feat.device)
-    _lib.check(_lib.lib().pp_warp_nhwc(_p(feat), Bf, _p(flow), B, H, W, C, flow.stride(2), _p(out), out.stride(2),
-                                       _lib.stream_ptr()), "pp_warp_nhwc")
+    _lib.call("pp_warp_nhwc", feat, Bf, flow, B, H, W, C, flow.stride(2), out, out.stride(2))
     return out
 
 
@@ -1264,7 +1239,7 @@ def avgpool2(x):
     B, H, W, C = x.shape
     assert x.is_contiguous()
     out = torch.empty(B, H // 2, W // 2, C, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().pp_avgpool2_nhwc(_p(x), B, H, W, C, _p(out), _lib.stream_ptr()), "pp_avgpool2_nhwc")
+    _lib.call("pp_avgpool2_nhwc", x, B, H, W, C, out)
     return out
 
 
@@ -1276,7 +1251,7 @@ def avgpool2_hl(x, keep_f32=True):
     out = torch.empty(B, H // 2, W // 2, C, dtype=torch.float32, device=x.device) if keep_f32 else None
     sp = Split.empty(B * (H // 2) * (W // 2), C, x.device)
     sp.image = (B, H // 2, W // 2)
-    _lib.check(_lib.lib().pp_avgpool2_hl(_p(x), B, H, W, C, _p(out) if keep_f32 else None, _p(sp.hl), _lib.stream_ptr()), "pp_avgpool2_hl")
+    _lib.call("pp_avgpool2_hl", x, B, H, W, C, out, sp.hl)
     _chk(sp.hl, "pp_avgpool2_hl")
     return out, sp
 
@@ -1345,30 +1320,28 @@ def corr_lookup(f1, f2, flow, levels, radius, c_pad=None, f1_hl=None, f2_hl=None
     if operands:
         tgt, col0 = f1_hl
         assert tgt.shape[0] == B * H * W and col0 % 8 == 0 and col0 + C <= tgt.shape[1] and f2_hl.shape == (f2.shape[0] * H * W, C)
-        maps = (tgt.hl.data_ptr() + 4 * col0, tgt.shape[1], _p(hls[0]), _p(hls[1]), _p(hls[2]))
+        maps = (tgt.hl.data_ptr() + 4 * col0, tgt.shape[1], hls[0], hls[1], hls[2])
     else:
-        maps = (_p(f1), f1.stride(2), _p(pyr[0]), _p(pyr[1]), _p(pyr[2]))
-    args = maps + (f2.shape[0], _p(flow), B, H, W, C, levels, radius, flow.stride(2))   # the arguments the three entry points share
+        maps = (f1, f1.stride(2), pyr[0], pyr[1], pyr[2])
+    args = maps + (f2.shape[0], flow, B, H, W, C, levels, radius, flow.stride(2))   # the arguments the three entry points share
 
     def fp32_map():   # (the kernels write the pad channels of their rows themselves; PP_DECODER_LEAN=0: the separate fill of the whole map, as before)
         return (torch.zeros if np_ > n and not decoder_lean() else torch.empty)(B, H, W, np_, dtype=torch.float32, device=f2.device)
 
-    L = _lib.lib()
     if operands and out_split and fused:   # operands in, the operand of the reading convolution out
         out = Split.empty(B * H * W, np_, f2.device)
         out.image = (B, H, W)
-        _lib.check(L.pp_corr_lookup_nhwc_hl_op(*args, None, np_, _p(out.hl), np_, _lib.stream_ptr()), "pp_corr_lookup_nhwc_hl_op")
+        _lib.call("pp_corr_lookup_nhwc_hl_op", *args, None, np_, out.hl, np_)
         _chk(out.hl, "pp_corr_lookup_nhwc_hl_op")
     elif operands:                         # operands in, fp32 map out (split afterwards where the caller wants the operand)
         out = fp32_map()
-        _lib.check(L.pp_corr_lookup_nhwc_hl(*args, _p(out), np_, _lib.stream_ptr()), "pp_corr_lookup_nhwc_hl")
+        _lib.call("pp_corr_lookup_nhwc_hl", *args, out, np_)
         if out_split:
             out = Split(split_activation(out, B, H * W, np_, H * W * np_, np_))
             out.image = (B, H, W)
     else:                                  # fp32 maps in and out
         out = fp32_map()
-        _lib.check(L.pp_corr_lookup_nhwc_ex(*args, 2 if precision() == "f16" else _fly_prec(), _p(out), np_, _lib.stream_ptr()),
-                   "pp_corr_lookup_nhwc_ex")
+        _lib.call("pp_corr_lookup_nhwc_ex", *args, 2 if precision() == "f16" else _fly_prec(), out, np_)
     return out
 
 
@@ -1378,8 +1351,7 @@ def tokens_to_nchw(tokens, skip, H, W):
     assert tokens.is_contiguous()
     out = torch.empty(B, C, H, W, dtype=torch.float32, device=tokens.device)
     src = tokens[:, skip:]
-    _lib.check(_lib.lib().pp_transpose_batched(_p(src), T * C, B, H * W, C, _p(out), 0, H * W, 0, _lib.stream_ptr()),
-               "pp_transpose_batched")
+    _lib.call("pp_transpose_batched", src, T * C, B, H * W, C, out, 0, H * W, 0)
     return out
 
 
@@ -1388,8 +1360,7 @@ def assemble_tokens(patches, cls_token, pos):
     B, T, C = patches.shape
     assert patches.is_contiguous() and pos.is_contiguous() and cls_token.is_contiguous()
     out = torch.empty(B, T + 1, C, dtype=torch.float32, device=patches.device)
-    _lib.check(_lib.lib().pp_assemble_tokens(_p(patches), _p(cls_token), _p(pos), B, T, C, _p(out), _lib.stream_ptr()),
-               "pp_assemble_tokens")
+    _lib.call("pp_assemble_tokens", patches, cls_token, pos, B, T, C, out)
     return out
 
 
@@ -1397,7 +1368,7 @@ def normalize_rows(x, eps=1e-12):
     rows, n = x.shape
     assert x.is_contiguous()
     y = torch.empty_like(x)
-    _lib.check(_lib.lib().pp_normalize_rows(_p(x), rows, n, float(eps), _p(y), _lib.stream_ptr()), "pp_normalize_rows")
+    _lib.call("pp_normalize_rows", x, rows, n, float(eps), y)
     return y
 
 
@@ -1410,8 +1381,7 @@ def gather_rows(src, index):
         return src[index]
     index = index.contiguous()
     dst = torch.empty((index.numel(),) + tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
-    _lib.check(_lib.lib().pp_gather_rows(_p(src), _p(index), R, row, index.numel(), _p(dst), _lib.stream_ptr()),
-               "pp_gather_rows")
+    _lib.call("pp_gather_rows", src, index, R, row, index.numel(), dst)
     return dst
 
 
@@ -1427,6 +1397,5 @@ def bank_rows_to_tokens(bank, index, T, skip=1, out=None):
     if out is None:
         out = torch.empty(n * T, C, dtype=torch.float32, device=bank.device)
     assert out.dim() == 2 and out.dtype == torch.float32 and out.shape[0] == n * T and out.shape[1] >= C and out.stride(1) == 1 and out.device == bank.device
-    _lib.check(_lib.lib().pp_bank_rows_to_tokens(_p(bank), R, C, P, _p(index.contiguous()), n, _p(out), out.stride(0), T, skip,
-                                                 _lib.stream_ptr()), "pp_bank_rows_to_tokens")
+    _lib.call("pp_bank_rows_to_tokens", bank, R, C, P, index.contiguous(), n, out, out.stride(0), T, skip)
     return out

@@ -152,11 +152,9 @@ class _FusedAdam(torch.optim.Optimizer):
             h, s2 = hl.get(i, (None, None))
             t = tensors[i]
             t.p, t.m, t.v, t.n = p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
-            t.hl = h.data_ptr() if h is not None else None
-            t.scale2 = s2.data_ptr() if s2 is not None else None
+            t.hl, t.scale2 = _lib.address(h), _lib.address(s2)
             key.append((t.p, t.m, t.v, t.n, t.hl, t.scale2))
         key = (params[0].device, tuple(key))
-        L = _lib.lib()
         rebuild = key != self._table_key
         if rebuild:
             need = _lib.workspace_bytes("pp_adam_workspace_bytes", tensors, n)
@@ -169,8 +167,7 @@ class _FusedAdam(torch.optim.Optimizer):
         steps = torch.empty(nbytes, dtype=torch.uint8, device=params[0].device)
         steps.copy_(host[:nbytes], non_blocking=True)
         ev.record()
-        _lib.check(L.pp_adam_multi_tensor(tensors, n, steps.data_ptr(), ops.terms(), int(rebuild), self._workspace.data_ptr(),
-                                          self._workspace.numel(), _lib.stream_ptr()), "pp_adam_multi_tensor")
+        _lib.call("pp_adam_multi_tensor", tensors, n, steps, ops.terms(), int(rebuild), self._workspace, self._workspace.numel())
         self._table_key = key
         return stamp
 

@@ -13,8 +13,6 @@ defaults below are CNOS's as remembered.  Its later appearance and geometric sco
 The kernels are in csrc/pp_proposals.hip (include/picopose_hip.h, PROPOSAL LABELLING, states each): every dot product is one
 fixed summation tree, so the tie rules (lowest view, lowest object) are exact.  tests/proposal_oracle.py restates everything in
 numpy float64."""
-import ctypes
-
 import numpy as np
 import torch
 
@@ -24,11 +22,6 @@ from .provider.test_batch import _frame_u8, detection_window
 
 NORM_EPS = 1e-12        # pp_descriptor_normalize's floor on the norm
 LN_EPS = 1e-6           # DINOv2's LayerNorm
-_I32P = ctypes.POINTER(ctypes.c_int)
-
-
-def _call(name, *args):
-    _lib.check(getattr(_lib.lib(), name)(*args, _lib.stream_ptr()), name)
 
 
 def cls_descriptors(net, rgb, bs=16):
@@ -50,7 +43,7 @@ def normalize_descriptors(x):
     (x,) = _lib.dev_f32(x)
     y = torch.empty_like(x)
     if x.shape[0]:
-        _call("pp_descriptor_normalize", x.data_ptr(), x.shape[0], x.shape[1], NORM_EPS, y.data_ptr())
+        _lib.call("pp_descriptor_normalize", x, x.shape[0], x.shape[1], NORM_EPS, y)
     return y
 
 
@@ -104,8 +97,7 @@ def match_descriptors(query, bank, topk=5):
     label = torch.empty((P,), dtype=torch.int32, device=dev)
     best = torch.empty((P,), dtype=torch.float32, device=dev)
     if P:
-        _call("pp_proposal_match", q.data_ptr(), P, bank.rows.data_ptr(), bank.offsets.data_ptr(), bank.offsets_host.ctypes.data_as(_I32P),
-              O, C, int(topk), score.data_ptr(), view.data_ptr(), label.data_ptr(), best.data_ptr())
+        _lib.call("pp_proposal_match", q, P, bank.rows, bank.offsets, bank.offsets_host, O, C, int(topk), score, view, label, best)
     return score, view, label, best
 
 
@@ -114,7 +106,7 @@ def mask_intersections(bits):
     and j share (pp_mask_intersections)."""
     n, words = bits.shape
     inter = torch.empty((n, n), dtype=torch.int32, device=bits.device)
-    _call("pp_mask_intersections", bits.data_ptr(), n, words, inter.data_ptr())
+    _lib.call("pp_mask_intersections", bits, n, words, inter)
     return inter
 
 

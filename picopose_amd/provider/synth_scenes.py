@@ -103,19 +103,15 @@ def _scales(depth_scale, n_images):
 def _composite_call(rgba, depth_m, off, desc, bg_images, scales, H, W, out, l0, i0, masks):
     """One pp_scene_composite call: layers [l0, l0 + L) (sorted by image) onto images [i0, i0 + n) of the output tensors."""
     L_, n = int(off[-1]), len(off) - 1
-    dev, lib = out["rgb"].device, _lib.lib()
+    dev = out["rgb"].device
     ws = torch.empty(max(_lib.workspace_bytes("pp_scene_composite_workspace_bytes", L_, H, W), 256), dtype=torch.uint8, device=dev)
     off = np.ascontiguousarray(off, dtype=np.int32)
     desc = np.ascontiguousarray(desc, dtype=np.int32)
     scales = np.ascontiguousarray(scales, dtype=np.float32)
     off_d, desc_d, sc_d = (torch.from_numpy(a).to(dev) for a in (off, desc, scales))
-    at = lambda t, k, size: None if t is None else t.data_ptr() + k * size     # noqa: E731
-    _lib.check(lib.pp_scene_composite(
-        rgba.data_ptr() if L_ else None, depth_m.data_ptr() if L_ else None, off_d.data_ptr(), off.ctypes.data, L_, n, H, W,
-        desc_d.data_ptr(), desc.ctypes.data, None if bg_images is None else bg_images.data_ptr(), sc_d.data_ptr(), scales.ctypes.data,
-        ws.data_ptr(), ws.numel(), at(out["rgb"], i0 * H * W, 3), at(out["depth"], i0 * H * W, 2), at(out["instance"], i0 * H * W, 4),
-        at(out["counts"], l0 * 2, 4) if L_ else None, at(out["boxes"], l0 * 4, 4) if L_ else None,
-        at(out["mask"], l0 * H * W, 1) if masks and L_ else None, _lib.stream_ptr()), "pp_scene_composite")
+    _lib.call("pp_scene_composite", rgba if L_ else None, depth_m if L_ else None, off_d, off, L_, n, H, W, desc_d, desc, bg_images, sc_d,
+              scales, ws, ws.numel(), out["rgb"][i0:], out["depth"][i0:], out["instance"][i0:], out["counts"][l0:] if L_ else None,
+              out["boxes"][l0:] if L_ else None, out["mask"][l0:] if masks and L_ else None)
 
 
 def _outputs(n_images, L_, H, W, masks, dev):
@@ -360,8 +356,7 @@ def depth_quantize_u16(depth_m, units_per_metre):
         raise ValueError("depth_m must be a float32 device tensor")
     depth_m = depth_m.contiguous()
     out = torch.empty(depth_m.shape, dtype=torch.uint16, device=depth_m.device)
-    _lib.check(_lib.lib().pp_depth_quantize_u16(depth_m.data_ptr(), depth_m.numel(), float(units_per_metre), out.data_ptr(),
-                                                _lib.stream_ptr()), "pp_depth_quantize_u16")
+    _lib.call("pp_depth_quantize_u16", depth_m, depth_m.numel(), float(units_per_metre), out)
     return out
 
 

@@ -288,12 +288,12 @@ def texture_mips(image):
     of uchar4 texels, level 0 first, as pp_render_views_textured reads it."""
     if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3 or not image.is_cuda:
         raise ValueError(f"image must be an (Ht, Wt, 3) uint8 device tensor, got {image.dtype} {tuple(image.shape)} on {image.device}")
-    image, L = image.contiguous(), _lib.lib()
+    image = image.contiguous()
     Ht, Wt = image.shape[:2]
     need = ctypes.c_size_t()
-    _lib.check(L.pp_texture_mips_bytes(Wt, Ht, ctypes.byref(need), None), "pp_texture_mips_bytes")
+    _lib.call("pp_texture_mips_bytes", Wt, Ht, ctypes.byref(need), None)
     mips = torch.empty(need.value, dtype=torch.uint8, device=image.device)
-    _lib.check(L.pp_texture_build_mips(image.data_ptr(), Wt, Ht, mips.data_ptr(), mips.numel(), _lib.stream_ptr()), "pp_texture_build_mips")
+    _lib.call("pp_texture_build_mips", image, Wt, Ht, mips, mips.numel())
     return mips
 
 
@@ -413,8 +413,7 @@ def vertex_normals(mesh, device="cuda"):
     off, adj = vertex_face_csr(f, len(v))
     v_d, f_d, off_d, adj_d = (torch.from_numpy(a).to(device) for a in (v, f, off, adj))
     out = torch.empty(len(v), 3, dtype=torch.float32, device=device)
-    _lib.check(_lib.lib().pp_vertex_normals(v_d.data_ptr(), len(v), f_d.data_ptr(), len(f), off_d.data_ptr(), adj_d.data_ptr(), out.data_ptr(),
-                                            _lib.stream_ptr()), "pp_vertex_normals")
+    _lib.call("pp_vertex_normals", v_d, len(v), f_d, len(f), off_d, adj_d, out)
     return out
 
 
@@ -463,7 +462,7 @@ def render_views(mesh, poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", n
     poses[:, :3, 3] *= scale
     K = np.asarray(K, dtype=np.float64)
     H, W = int(resolution[0]), int(resolution[1])
-    V, L = len(poses), _lib.lib()
+    V = len(poses)
     v_m = np.ascontiguousarray((v.astype(np.float64) * scale).astype(np.float32))
     v_d, f_d, c_d = (torch.from_numpy(a).to(device) for a in (v_m, f, c))
     p_d = torch.from_numpy(np.ascontiguousarray(poses.astype(np.float32))).to(device)
@@ -477,9 +476,8 @@ def render_views(mesh, poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", n
         out["depth_m"] = torch.empty(V, H, W, dtype=torch.float32, device=device)
     if return_face_id:
         out["face_id"] = torch.empty(V, H, W, dtype=torch.int32, device=device)
-    tail = (p_d.data_ptr(), V, float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), H, W, float(near), ws.data_ptr(), ws.numel(),
-            out["rgba"].data_ptr(), out["depth_mm"].data_ptr(), out["depth_m"].data_ptr() if return_depth_m else None,
-            out["face_id"].data_ptr() if return_face_id else None, out["near_count"].data_ptr(), _lib.stream_ptr())
+    tail = (p_d, V, float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), H, W, float(near), ws, ws.numel(),
+            out["rgba"], out["depth_mm"], out.get("depth_m"), out.get("face_id"), out["near_count"])
     Ht = Wt = 0
     if tex is not None:
         image, face_uv = tex
@@ -492,19 +490,13 @@ def render_views(mesh, poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", n
         if smooth:                                                        # direction only: the unit of the vertices does not matter
             n_d = torch.from_numpy(own_normals).to(device) if own_normals is not None else vertex_normals(mesh, device)
         tone_d = None if tone is None else torch.from_numpy(tone).to(device)
-        _lib.check(L.pp_render_views_lit(v_d.data_ptr(), len(v), f_d.data_ptr(), f.ctypes.data, len(f),
-                                         c_d.data_ptr() if tex is None and base is None else None,
-                                         uv_d.data_ptr() if tex is not None and base is None else None,
-                                         mips.data_ptr() if tex is not None and base is None else None, Wt, Ht, *tail[:-1],
-                                         lights4.ctypes.data if len(lights4) else None, len(lights4), ambient, int(smooth),
-                                         None if n_d is None else n_d.data_ptr(), None if base is None else base.ctypes.data,
-                                         None if tone_d is None else tone_d.data_ptr(), 0 if tone is None else len(tone), tail[-1]),
-                   "pp_render_views_lit")
+        _lib.call("pp_render_views_lit", v_d, len(v), f_d, f, len(f), c_d if tex is None and base is None else None,
+                  uv_d if tex is not None and base is None else None, mips if tex is not None and base is None else None, Wt, Ht, *tail,
+                  lights4 if len(lights4) else None, len(lights4), ambient, int(smooth), n_d, base, tone_d, 0 if tone is None else len(tone))
     elif tex is None:
-        _lib.check(L.pp_render_views(v_d.data_ptr(), len(v), f_d.data_ptr(), f.ctypes.data, len(f), c_d.data_ptr(), *tail), "pp_render_views")
+        _lib.call("pp_render_views", v_d, len(v), f_d, f, len(f), c_d, *tail)
     else:
-        _lib.check(L.pp_render_views_textured(v_d.data_ptr(), len(v), f_d.data_ptr(), f.ctypes.data, len(f), uv_d.data_ptr(),
-                                              mips.data_ptr(), Wt, Ht, *tail), "pp_render_views_textured")
+        _lib.call("pp_render_views_textured", v_d, len(v), f_d, f, len(f), uv_d, mips, Wt, Ht, *tail)
     if check_near:
         _raise_on_near(int(out["near_count"].item()), near)
     return out
@@ -519,13 +511,13 @@ def _raise_on_near(count, near):
 def _crop_frames(rgba, depth, depth_is_f32, K, poses_mm, near_count, near, img_size, pts_size, rgb_mask_flag):
     """extents -> one device->host copy -> boxes -> one crop launch.  rgba (V,H,W,4) uint8 and depth (V,H,W) on the device."""
     V, H, W = rgba.shape[:3]
-    dev, L = rgba.device, _lib.lib()
+    dev = rgba.device
     meta = torch.empty(V * 4 + 1, dtype=torch.int32, device=dev)
     if near_count is None:
         meta[-1] = 0
     else:
         meta[-1:] = near_count
-    _lib.check(L.pp_template_extents(rgba.data_ptr(), V, H, W, meta.data_ptr(), None, _lib.stream_ptr()), "pp_template_extents")
+    _lib.call("pp_template_extents", rgba, V, H, W, meta, None)
     host = meta.cpu().numpy()                                    # the one device->host copy (it synchronises the stream)
     _raise_on_near(int(host[-1]), near)
     ext = host[:-1].reshape(V, 4)
@@ -542,9 +534,8 @@ def _crop_frames(rgba, depth, depth_is_f32, K, poses_mm, near_count, near, img_s
     mask = torch.empty(V, S, S, dtype=torch.float32, device=dev)
     pts = torch.empty(V, P, P, 3, dtype=torch.float32, device=dev)
     mean, std = (ctypes.c_double * 3)(*CLIP_MEAN), (ctypes.c_double * 3)(*CLIP_STD)
-    _lib.check(L.pp_templates_crop(rgba.data_ptr(), depth.data_ptr(), int(depth_is_f32), V, H, W, boxes_d.data_ptr(), boxes.ctypes.data,
-                                   float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), S, P, int(rgb_mask_flag), mean, std,
-                                   rgb.data_ptr(), mask.data_ptr(), pts.data_ptr(), _lib.stream_ptr()), "pp_templates_crop")
+    _lib.call("pp_templates_crop", rgba, depth, int(depth_is_f32), V, H, W, boxes_d, boxes, float(K[0, 0]), float(K[1, 1]), float(K[0, 2]),
+              float(K[1, 2]), S, P, int(rgb_mask_flag), mean, std, rgb, mask, pts)
     y1, y2, x1, x2 = (boxes[:, k].astype(np.float64) for k in range(4))
     M = np.zeros((V, 3, 3), dtype=np.float32)                    # M_resize @ M_crop of :246-254, entry by entry in float32
     M[:, 0, 0] = (S / (y2 - y1)).astype(np.float32)

@@ -310,10 +310,8 @@ def execute_augmentation(rgb0, mask0, rgba1, plan, device="cuda"):
     pt = (ctypes.c_int * (MAX_PASSES + 1))(*plan.pass_tiles)
     if rgb0.numel() != 3 * mask0.numel():
         raise ValueError("rgb0 and mask0 must hold the same frames")
-    _lib.check(_lib.lib().pp_augment_execute(rgb0.data_ptr(), mask0.data_ptr(), mask0.numel(), rgba1.data_ptr(), rgba1.numel() // 4,
-                                             d_desc.data_ptr(), n_img, d_ops.data_ptr(), n_img * MAX_OPS, d_tiles.data_ptr(), pt,
-                                             plan.n_passes, buf0.data_ptr(), buf1.data_ptr(), plan.n_buf, lsum.data_ptr(),
-                                             _lib.stream_ptr()), "pp_augment_execute")
+    _lib.call("pp_augment_execute", rgb0, mask0, mask0.numel(), rgba1, rgba1.numel() // 4, d_desc, n_img, d_ops, n_img * MAX_OPS, d_tiles, pt,
+              plan.n_passes, buf0, buf1, plan.n_buf, lsum)
     return buf0, buf1, d_desc
 
 
@@ -383,13 +381,10 @@ def assemble_training_batch(samples, img_size=224, augment_real=True, augment_te
     msk = torch.empty((n_img, S, S), dtype=torch.float32, device=device)
     real_depth = torch.empty((B, H, W), dtype=torch.float32, device=device)
     tem_depth = torch.empty((B, Ht, Wt), dtype=torch.float32, device=device)
-    L, st = _lib.lib(), _lib.stream_ptr()
     mean, std = (ctypes.c_double * 3)(*CLIP_MEAN), (ctypes.c_double * 3)(*CLIP_STD)
-    _lib.check(L.pp_augment_resize(buf0.data_ptr(), buf1.data_ptr(), plan.n_buf, d_desc.data_ptr(), n_img, S, int(rgb_mask_flag), mean,
-                                   std, rgb.data_ptr(), msk.data_ptr(), st), "pp_augment_resize")
-    _lib.check(L.pp_depth_u16_scaled(dep_r.data_ptr(), H * W, B, d_f[len(f) - B:].data_ptr(), real_depth.data_ptr(), st),
-               "pp_depth_u16_scaled")
-    _lib.check(L.pp_depth_u16_template(dep_t.data_ptr(), B * Ht * Wt, tem_depth.data_ptr(), st), "pp_depth_u16_template")
+    _lib.call("pp_augment_resize", buf0, buf1, plan.n_buf, d_desc, n_img, S, int(rgb_mask_flag), mean, std, rgb, msk)
+    _lib.call("pp_depth_u16_scaled", dep_r, H * W, B, d_f[len(f) - B:], real_depth)
+    _lib.call("pp_depth_u16_template", dep_t, B * Ht * Wt, tem_depth)
     ep = {"real_full_depth": real_depth, "tem_full_depth": tem_depth}
     o = 0
     for k, shape in (("bbox", (4,)), ("M", (3, 3)), ("K", (3, 3)), ("pose", (4, 4))):

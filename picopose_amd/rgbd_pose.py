@@ -126,11 +126,8 @@ def rgbd_launch(tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts, depth, in
     nlisted = torch.empty(P, dtype=torch.int32, device=dev)
     rms = torch.empty(P, dtype=torch.float64, device=dev)
     mask = torch.empty(P, N, dtype=torch.uint8, device=dev) if return_inliers else None
-    rc = _lib.lib().pp_rgbd_ransac(t2.data_ptr(), s3.data_ptr(), Kd.data_ptr(), pose.data_ptr(), tp.data_ptr(), sp.data_ptr(), P, H, W, N,
-                                   dep.data_ptr(), n_images, dH, dW, img.data_ptr(), dist.data_ptr(), int(iterations), rot.data_ptr(),
-                                   tvec.data_ptr(), ratio.data_ptr(), ok.data_ptr(), npts.data_ptr(), nlisted.data_ptr(), rms.data_ptr(),
-                                   mask.data_ptr() if mask is not None else None, _lib.stream_ptr())
-    _lib.check(rc, "pp_rgbd_ransac")
+    _lib.call("pp_rgbd_ransac", t2, s3, Kd, pose, tp, sp, P, H, W, N, dep, n_images, dH, dW, img, dist, int(iterations),
+              rot, tvec, ratio, ok, npts, nlisted, rms, mask)
     return (rot, tvec, ratio, ok, npts, nlisted, rms) + ((mask,) if return_inliers else ())
 
 

@@ -230,8 +230,7 @@ def depth_u16_scaled(depth, scale_f32, dev):
     is_t = isinstance(depth, torch.Tensor)
     raw = (depth.contiguous().view(torch.int16) if is_t else torch.from_numpy(np.ascontiguousarray(depth).view(np.int16))).to(dev)
     out = torch.empty((n, H, W), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().pp_depth_u16_scaled(raw.data_ptr(), H * W, n, s.data_ptr(), out.data_ptr(), _lib.stream_ptr()),
-               "pp_depth_u16_scaled")
+    _lib.call("pp_depth_u16_scaled", raw, H * W, n, s, out)
     return out
 
 
@@ -258,12 +257,12 @@ class PackedScene:
         host.append(zoff)
         self.samples, self.faces = int(zoff[-1]), int(models.face_counts[host[1]].sum())
         self._keep = (models, host, [torch.from_numpy(a).to(models.device) for a in host])      # the one upload of a call's tables
-        cams_d, obj_d, img_d, poses_d, win_d, zoff_d = (t.data_ptr() for t in self._keep[2])
-        hp = lambda a: a.ctypes.data                             # noqa: E731
-        self.scene = _lib.PpScene(
-            vertices=models.vertices.data_ptr(), vert_off=models.vert_off_d.data_ptr(), faces=models.faces.data_ptr(),
-            face_off=models.face_off_d.data_ptr(), diameters=models.diameters_d.data_ptr(), cams=cams_d, view_obj=obj_d, view_img=img_d,
-            poses=poses_d, windows=win_d, view_zoff=zoff_d, vert_off_host=hp(models.vert_off), faces_host=hp(models.faces_host),
-            face_off_host=hp(models.face_off), diameters_host=hp(models.diameters_f32), cams_host=hp(host[0]), view_obj_host=hp(host[1]),
-            view_img_host=hp(host[2]), windows_host=hp(host[4]), view_zoff_host=hp(zoff), n_objects=len(models.obj_ids),
-            n_images=len(host[0]), H=H, W=W, n_views=len(host[1]), near=float(near))
+        cams_d, obj_d, img_d, poses_d, win_d, zoff_d = self._keep[2]
+        tables = dict(                                           # device tensors and host arrays: the members take their addresses
+            vertices=models.vertices, vert_off=models.vert_off_d, faces=models.faces, face_off=models.face_off_d,
+            diameters=models.diameters_d, cams=cams_d, view_obj=obj_d, view_img=img_d, poses=poses_d, windows=win_d, view_zoff=zoff_d,
+            vert_off_host=models.vert_off, faces_host=models.faces_host, face_off_host=models.face_off,
+            diameters_host=models.diameters_f32, cams_host=host[0], view_obj_host=host[1], view_img_host=host[2], windows_host=host[4],
+            view_zoff_host=zoff)
+        self.scene = _lib.PpScene(**{k: _lib.address(v) for k, v in tables.items()}, n_objects=len(models.obj_ids),
+                                  n_images=len(host[0]), H=H, W=W, n_views=len(host[1]), near=float(near))

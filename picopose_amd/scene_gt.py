@@ -7,7 +7,6 @@ The contract is "SCENE GROUND TRUTH" of include/picopose_hip.h (csrc/pp_scene_gt
 It is the BOP toolkit's calc_gt_info / calc_gt_masks written from memory: the toolkit cannot be run next to this library, parity
 with its pixels is UNPINNED, and the header lists the known differences (sampling convention, near-plane rule, box convention).
 The planners (windows, view groups, depth conversion, cameras) and the packing of a call's tables are scene.py's."""
-import ctypes
 import math
 
 import numpy as np
@@ -157,7 +156,6 @@ def scene_gt_info(models, obj_ids, R, t, K, depth=None, resolution=None, image_i
         order = np.arange(U)
         groups = [(int(g[0][0]), int(g[0][-1]) + 1, 0, n_images) for g in scn.view_groups(models, obj, windows, None, None, workspace_bytes)]
     scn.require_gpu(dev)
-    L = _lib.lib()
     depth_d = None if depth is None else scn.depth_mm(depth, scale, dev)
     s_obj, s_img, s_pose, s_win = obj[order], img[order], poses[order], windows[order]
     counts, boxes, near_d = i32(U, 3), i32(U, 8), i32(U)
@@ -165,18 +163,15 @@ def scene_gt_info(models, obj_ids, R, t, K, depth=None, resolution=None, image_i
     m_vis = u8(U, H, W) if want_visib else None
     scene_depth = torch.zeros((n_images, H, W), dtype=torch.float32, device=dev) if composite else None
     inst_map = torch.full((n_images, H, W), -1, dtype=torch.int32, device=dev) if composite else None
-    off = lambda a, n, size: None if a is None else a.data_ptr() + n * size      # noqa: E731
+    at = lambda a, n: None if a is None else a[n:]      # noqa: E731  (an optional output from its row n on)
     for v0, v1, i0, i1 in groups:
         packed = scn.PackedScene(models, cams[i0:i1], H, W, near, s_obj[v0:v1], s_img[v0:v1] - i0, s_pose[v0:v1], s_win[v0:v1])
         ccam = np.ascontiguousarray(ccams[i0:i1])
         need = _lib.workspace_bytes("pp_scene_gt_workspace_bytes", packed.samples, packed.faces, (i1 - i0) * H * W if run_composite else 0)
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         label_d, ccam_d = torch.from_numpy(order[v0:v1].astype(np.int32)).to(dev), torch.from_numpy(ccam).to(dev)
-        _lib.check(L.pp_scene_gt(
-            ctypes.byref(packed.scene), ccam_d.data_ptr(), ccam.ctypes.data, pad_x, pad_y, off(depth_d, i0 * H * W, 4), float(delta),
-            label_d.data_ptr(), 1, ws.data_ptr(), ws.numel(), off(counts, v0 * 3, 4), off(boxes, v0 * 8, 4), off(near_d, v0, 4),
-            off(m_all, v0 * H * W, 1), off(m_vis, v0 * H * W, 1), off(scene_depth, i0 * H * W, 4), off(inst_map, i0 * H * W, 4),
-            _lib.stream_ptr()), "pp_scene_gt")
+        _lib.call("pp_scene_gt", packed.scene, ccam_d, ccam, pad_x, pad_y, at(depth_d, i0), float(delta), label_d, 1, ws, ws.numel(),
+                  counts[v0:], boxes[v0:], near_d[v0:], at(m_all, v0), at(m_vis, v0), at(scene_depth, i0), at(inst_map, i0))
     if run_composite and not np.array_equal(order, np.arange(U)):  # back to the caller's order
         inv = torch.from_numpy(np.argsort(order, kind="stable")).to(dev)
         counts, boxes, near_d = counts[inv], boxes[inv], near_d[inv]

@@ -13,9 +13,7 @@ def compute_init_correspondences(pred_Ms, tem_mask, size=(16, 16)):
     Ms, mask = _lib.dev_f32(pred_Ms, tem_mask)
     flow = torch.empty(B, 2, 16, 16, dtype=torch.float32, device=Ms.device)
     cert = torch.empty(B, 1, 16, 16, dtype=torch.float32, device=Ms.device)
-    rc = _lib.lib().pp_init_correspondences(Ms.data_ptr(), mask.data_ptr(), H, W, B, flow.data_ptr(),
-                                            cert.data_ptr(), _lib.stream_ptr())
-    _lib.check(rc, "pp_init_correspondences")
+    _lib.call("pp_init_correspondences", Ms, mask, H, W, B, flow, cert)
     return flow, cert
 
 
@@ -25,7 +23,5 @@ def compute_stage3_correspondences(pred_flow, pred_certainty, threshold=0.5):
     B, _, H, W = flow.shape
     tar = torch.empty(B, H * W, 2, dtype=torch.int64, device=flow.device)
     src = torch.empty(B, H * W, 2, dtype=torch.int64, device=flow.device)
-    rc = _lib.lib().pp_stage3_correspondences(flow.data_ptr(), cert.data_ptr(), B, H, W, float(threshold),
-                                              tar.data_ptr(), src.data_ptr(), _lib.stream_ptr())
-    _lib.check(rc, "pp_stage3_correspondences")
+    _lib.call("pp_stage3_correspondences", flow, cert, B, H, W, float(threshold), tar, src)
     return tar, src

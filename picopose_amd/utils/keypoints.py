@@ -42,13 +42,10 @@ class KeyPointSampler:
         B, mh, mw = smask.shape
         dh, dw = sdepth.shape[1:]
         assert tmask.shape == smask.shape and tdepth.shape == sdepth.shape
-        L = _lib.lib()
-        ws_bytes = L.pp_train_keypoints_workspace_bytes(B)
+        ws_bytes = _lib.lib().pp_train_keypoints_workspace_bytes(B)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=smask.device)
         src = torch.empty(B, 4096, 2, dtype=torch.float32, device=smask.device)
         tar = torch.empty_like(src)
-        p = lambda t: t.data_ptr()  # noqa: E731
-        rc = L.pp_train_keypoints(p(smask), p(tmask), mh, mw, p(sdepth), p(tdepth), dh, dw, p(sMi), p(tMi), p(sM), p(tM), p(sKi), p(tKi),
-                                  p(sK), p(tK), p(Tst), p(Tts), B, p(src), p(tar), p(ws), ws_bytes, _lib.stream_ptr())
-        _lib.check(rc, "pp_train_keypoints")
+        _lib.call("pp_train_keypoints", smask, tmask, mh, mw, sdepth, tdepth, dh, dw, sMi, tMi, sM, tM, sKi, tKi, sK, tK, Tst, Tts, B,
+                  src, tar, ws, ws_bytes)
         return {"src_pts": src, "tar_pts": tar}

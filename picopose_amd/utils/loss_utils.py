@@ -52,17 +52,14 @@ def infonce_rows(tokens_src, tokens_tar, src_pts, tar_pts, tau=0.1):
     n = s_rows.numel()
     if n == 0:
         return torch.full((), float("nan"), device=tokens_src.device)    # F.cross_entropy of an empty batch
-    L = _lib.lib()
     (ts, tt) = _lib.dev_f32(tokens_src, tokens_tar)
     q = torch.empty(n, C, dtype=torch.float32, device=ts.device)
     r = torch.empty_like(q)
-    _lib.check(L.pp_gather_normalize_rows(ts.data_ptr(), C, s_rows.contiguous().data_ptr(), n, C, 1e-12, q.data_ptr(), _lib.stream_ptr()),
-               "pp_gather_normalize_rows")
-    _lib.check(L.pp_gather_normalize_rows(tt.data_ptr(), C, t_rows.contiguous().data_ptr(), n, C, 1e-12, r.data_ptr(), _lib.stream_ptr()),
-               "pp_gather_normalize_rows")
+    _lib.call("pp_gather_normalize_rows", ts, C, s_rows.contiguous(), n, C, 1e-12, q)
+    _lib.call("pp_gather_normalize_rows", tt, C, t_rows.contiguous(), n, C, 1e-12, r)
     logits = ops.bmm_nt(q[None, None], r[None, None])[0, 0]              # (n, n) = q r^T on the GEMM engine
     rows = torch.empty(n, dtype=torch.float32, device=ts.device)
-    _lib.check(L.pp_xent_diag_rows(logits.data_ptr(), n, logits.stride(0), 1.0 / tau, rows.data_ptr(), _lib.stream_ptr()), "pp_xent_diag_rows")
+    _lib.call("pp_xent_diag_rows", logits, n, logits.stride(0), 1.0 / tau, rows)
     return rows.mean()
 
 
@@ -95,10 +92,8 @@ def flow_level_losses(flow_nhwc, cert_nhwc, tar_pts, mask_weight=1.0, flow_weigh
     """One level of compute_stage_three_loss on NHWC maps: flow (B,H,W,2), certainty (B,H,W,1) -> (loss_flow, loss_certainty)."""
     (fl, ce, tp) = _lib.dev_f32(flow_nhwc, cert_nhwc, tar_pts)
     B, H, W, _ = fl.shape
-    L = _lib.lib()
-    part = torch.empty(L.pp_flow_loss_blocks(), 3, dtype=torch.float64, device=fl.device)
-    _lib.check(L.pp_flow_loss_sums(fl.data_ptr(), ce.data_ptr(), tp.data_ptr(), B, H, W, float(max_flow), part.data_ptr(), _lib.stream_ptr()),
-               "pp_flow_loss_sums")
+    part = torch.empty(_lib.lib().pp_flow_loss_blocks(), 3, dtype=torch.float64, device=fl.device)
+    _lib.call("pp_flow_loss_sums", fl, ce, tp, B, H, W, float(max_flow), part)
     bce, l1, cnt = part.sum(0)
     return (flow_weight * l1 / (cnt + eps)).float(), (mask_weight * bce / (B * H * W)).float()
 

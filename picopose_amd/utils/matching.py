@@ -5,8 +5,6 @@
 (picopose_amd/csrc/pp_stage1.hip) through the C ABI; nothing here computes on
 the CPU and there is no torch fallback.
 """
-import ctypes
-
 import torch
 
 from .. import _lib
@@ -17,10 +15,6 @@ DEFAULT_MODE = "fast"
 _MODES = {"exact": _lib.PP_MATCH_EXACT, "fast": _lib.PP_MATCH_FAST}
 
 _ws_cache = {}
-
-
-def _stream_ptr():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _workspace(B, N, C, device, query="pp_stage1_workspace_bytes"):
@@ -58,11 +52,8 @@ def template_scores(src_feats, tar_feat, tar_mask, mode=None, eps=0.0, return_st
     ws, nbytes = _workspace(B, N, C, bank.device)
     sim_avg = torch.empty(B, N, dtype=torch.float32, device=bank.device)
     stats = torch.zeros(4, dtype=torch.int32, device=bank.device) if return_stats else None
-    rc = _lib.lib().pp_stage1_scores_ex(
-        bank.data_ptr(), _lib.PP_BANK_F16 if half else _lib.PP_BANK_F32, query.data_ptr(), mask.data_ptr(), mask.shape[1],
-        mask.shape[2], B, N, C, mode_id, float(eps), ws.data_ptr(), nbytes, sim_avg.data_ptr(),
-        stats.data_ptr() if stats is not None else None, _stream_ptr())
-    _lib.check(rc, "pp_stage1_scores_ex")
+    _lib.call("pp_stage1_scores_ex", bank, _lib.PP_BANK_F16 if half else _lib.PP_BANK_F32, query, mask, mask.shape[1], mask.shape[2],
+              B, N, C, mode_id, float(eps), ws, nbytes, sim_avg, stats)
     return (sim_avg, stats) if return_stats else sim_avg
 
 
@@ -74,8 +65,7 @@ def topk_templates(sim_avg, topk):
     sim_avg = sim_avg.contiguous().float()
     score = torch.empty(B, topk, dtype=torch.float32, device=sim_avg.device)
     index = torch.empty(B, topk, dtype=torch.int64, device=sim_avg.device)
-    rc = _lib.lib().pp_topk(sim_avg.data_ptr(), B, N, topk, score.data_ptr(), index.data_ptr(), _stream_ptr())
-    _lib.check(rc, "pp_topk")
+    _lib.call("pp_topk", sim_avg, B, N, topk, score, index)
     return score, index
 
 
@@ -97,11 +87,8 @@ def matching_templates(src_feats, tar_feat, src_masks, tar_mask, topk=5, mode=No
     score = torch.empty(B, topk, dtype=torch.float32, device=bank.device)
     index = torch.empty(B, topk, dtype=torch.int64, device=bank.device)
     # scores + top-k as one ABI call (pp_stage1_match_ex: the last resolve workgroup of a crop ranks its scores)
-    rc = _lib.lib().pp_stage1_match_ex(
-        bank.data_ptr(), _lib.PP_BANK_F16 if half else _lib.PP_BANK_F32, query.data_ptr(), mask.data_ptr(), mask.shape[1],
-        mask.shape[2], B, N, C, int(topk), _MODES[mode or DEFAULT_MODE], 0.0, ws.data_ptr(), nbytes, sim_avg.data_ptr(),
-        score.data_ptr(), index.data_ptr(), None, _stream_ptr())
-    _lib.check(rc, "pp_stage1_match_ex")
+    _lib.call("pp_stage1_match_ex", bank, _lib.PP_BANK_F16 if half else _lib.PP_BANK_F32, query, mask, mask.shape[1], mask.shape[2],
+              B, N, C, int(topk), _MODES[mode or DEFAULT_MODE], 0.0, ws, nbytes, sim_avg, score, index, None)
     return score, index
 
 
@@ -141,11 +128,8 @@ def template_scores_indexed(src_feats, obj_index, tar_feat, tar_mask, mode=None,
     ws, nbytes = _workspace(B, N, C, bank.device, "pp_stage1_indexed_workspace_bytes")
     sim_avg = torch.empty(B, N, dtype=torch.float32, device=bank.device)
     stats = torch.zeros(4, dtype=torch.int32, device=bank.device) if return_stats else None
-    rc = _lib.lib().pp_stage1_scores_indexed(
-        bank.data_ptr(), _lib.PP_BANK_F16 if half else _lib.PP_BANK_F32, idx.data_ptr(), O, query.data_ptr(), mask.data_ptr(),
-        mask.shape[1], mask.shape[2], B, N, C, mode_id, float(eps), ws.data_ptr(), nbytes, sim_avg.data_ptr(),
-        stats.data_ptr() if stats is not None else None, _stream_ptr())
-    _lib.check(rc, "pp_stage1_scores_indexed")
+    _lib.call("pp_stage1_scores_indexed", bank, _lib.PP_BANK_F16 if half else _lib.PP_BANK_F32, idx, O, query, mask,
+              mask.shape[1], mask.shape[2], B, N, C, mode_id, float(eps), ws, nbytes, sim_avg, stats)
     return (sim_avg, stats) if return_stats else sim_avg
 
 
@@ -163,11 +147,8 @@ def matching_templates_indexed(src_feats, obj_index, tar_feat, src_masks, tar_ma
     sim_avg = torch.empty(B, N, dtype=torch.float32, device=bank.device)
     score = torch.empty(B, topk, dtype=torch.float32, device=bank.device)
     index = torch.empty(B, topk, dtype=torch.int64, device=bank.device)
-    rc = _lib.lib().pp_stage1_match_indexed(
-        bank.data_ptr(), _lib.PP_BANK_F16 if half else _lib.PP_BANK_F32, idx.data_ptr(), O, query.data_ptr(), mask.data_ptr(),
-        mask.shape[1], mask.shape[2], B, N, C, int(topk), _MODES[mode or DEFAULT_MODE], 0.0, ws.data_ptr(), nbytes, sim_avg.data_ptr(),
-        score.data_ptr(), index.data_ptr(), None, _stream_ptr())
-    _lib.check(rc, "pp_stage1_match_indexed")
+    _lib.call("pp_stage1_match_indexed", bank, _lib.PP_BANK_F16 if half else _lib.PP_BANK_F32, idx, O, query, mask,
+              mask.shape[1], mask.shape[2], B, N, C, int(topk), _MODES[mode or DEFAULT_MODE], 0.0, ws, nbytes, sim_avg, score, index, None)
     return score, index
 
 
@@ -211,7 +192,5 @@ def matching_features_similarity(src_feat, tar_feat, src_mask, tar_mask):
         raise _lib.PicoPoseHipError("the HIP similarity-volume kernel is built for 16x16 patch grids")
     src, tar, mask = _lib.dev_f32(src_feat, tar_feat, src_mask)
     out = torch.empty(B, H * W, H, W, dtype=torch.float32, device=src.device)
-    rc = _lib.lib().pp_similarity_volume(src.data_ptr(), tar.data_ptr(), mask.data_ptr(), mask.shape[1],
-                                         mask.shape[2], B, C, out.data_ptr(), _lib.stream_ptr())
-    _lib.check(rc, "pp_similarity_volume")
+    _lib.call("pp_similarity_volume", src, tar, mask, mask.shape[1], mask.shape[2], B, C, out)
     return out

@@ -43,9 +43,7 @@ def pose_recovery_2d_prediction(query_M, query_K, pred_Ms, template_K, template_
         assert torch.all(qM[:, 0, 0] == qM[:, 1, 1])                                 # torch_utils.py:101
     B = qM.shape[0]
     out = torch.empty(B, 4, 4, dtype=torch.float32, device=qM.device)
-    rc = _lib.lib().pp_pose_recovery_2d(qM.data_ptr(), qK.data_ptr(), pM.data_ptr(), tK.data_ptr(), tM.data_ptr(),
-                                        tp.data_ptr(), B, out.data_ptr(), _lib.stream_ptr())
-    _lib.check(rc, "pp_pose_recovery_2d")
+    _lib.call("pp_pose_recovery_2d", qM, qK, pM, tK, tM, tp, B, out)
     return out
 
 
@@ -102,27 +100,18 @@ def pnp_launch(tar_pts_2d, src_pts_3d, K, tem_pose, tar_pts, src_pts, iterations
     rot, tvec, ratio, ok, npts = alloc_pose_outputs(P, dev)
     if branches:
         dbg = torch.empty(P, 40, dtype=torch.float64, device=dev)
-        rc = _lib.lib().pp_pnp_ransac_debug(t2.data_ptr(), s3.data_ptr(), Kd.data_ptr(), pose.data_ptr(), tp.data_ptr(), sp.data_ptr(),
-                                            P, H, W, N, int(iterations), float(reproj_error), rot.data_ptr(), tvec.data_ptr(),
-                                            ratio.data_ptr(), ok.data_ptr(), npts.data_ptr(), dbg.data_ptr(), _lib.stream_ptr())
-        _lib.check(rc, "pp_pnp_ransac_debug")
+        _lib.call("pp_pnp_ransac_debug", t2, s3, Kd, pose, tp, sp, P, H, W, N, int(iterations), float(reproj_error),
+                  rot, tvec, ratio, ok, npts, dbg)
         return rot, tvec, ratio, ok, npts, dbg
     if refining:
         rms0 = torch.empty(P, dtype=torch.float64, device=dev)
         rms1 = torch.empty(P, dtype=torch.float64, device=dev)
         its = torch.empty(P, dtype=torch.int32, device=dev)
         mask = torch.empty(P, N, dtype=torch.uint8, device=dev) if return_inliers else None
-        rc = _lib.lib().pp_pnp_ransac_refine(t2.data_ptr(), s3.data_ptr(), Kd.data_ptr(), pose.data_ptr(), tp.data_ptr(), sp.data_ptr(),
-                                             P, H, W, N, int(iterations), float(reproj_error), int(refine_iters), float(refine_eps),
-                                             rot.data_ptr(), tvec.data_ptr(), ratio.data_ptr(), ok.data_ptr(), npts.data_ptr(),
-                                             rms0.data_ptr(), rms1.data_ptr(), its.data_ptr(),
-                                             mask.data_ptr() if mask is not None else None, _lib.stream_ptr())
-        _lib.check(rc, "pp_pnp_ransac_refine")
+        _lib.call("pp_pnp_ransac_refine", t2, s3, Kd, pose, tp, sp, P, H, W, N, int(iterations), float(reproj_error),
+                  int(refine_iters), float(refine_eps), rot, tvec, ratio, ok, npts, rms0, rms1, its, mask)
         return (rot, tvec, ratio, ok, npts, rms0, rms1, its) + ((mask,) if return_inliers else ())
-    rc = _lib.lib().pp_pnp_ransac(t2.data_ptr(), s3.data_ptr(), Kd.data_ptr(), pose.data_ptr(), tp.data_ptr(), sp.data_ptr(),
-                                  P, H, W, N, int(iterations), float(reproj_error), rot.data_ptr(), tvec.data_ptr(),
-                                  ratio.data_ptr(), ok.data_ptr(), npts.data_ptr(), _lib.stream_ptr())
-    _lib.check(rc, "pp_pnp_ransac")
+    _lib.call("pp_pnp_ransac", t2, s3, Kd, pose, tp, sp, P, H, W, N, int(iterations), float(reproj_error), rot, tvec, ratio, ok, npts)
     return rot, tvec, ratio, ok, npts
 
 
@@ -318,10 +307,7 @@ def solve_pnp_refine_lm(object_points, image_points, K, R, t, counts=None, max_i
     rms0 = torch.empty(P, dtype=torch.float64, device=dev)
     rms1 = torch.empty(P, dtype=torch.float64, device=dev)
     its = torch.empty(P, dtype=torch.int32, device=dev)
-    rc = _lib.lib().pp_pnp_refine_lm(obj.data_ptr(), img.data_ptr(), cnt.data_ptr(), Kd.data_ptr(), R0.data_ptr(), t0.data_ptr(), P, Nmax,
-                                     int(max_iters), float(eps), rot.data_ptr(), tvec.data_ptr(), rms0.data_ptr(), rms1.data_ptr(),
-                                     its.data_ptr(), _lib.stream_ptr())
-    _lib.check(rc, "pp_pnp_refine_lm")
+    _lib.call("pp_pnp_refine_lm", obj, img, cnt, Kd, R0, t0, P, Nmax, int(max_iters), float(eps), rot, tvec, rms0, rms1, its)
     host = torch.cat([rot.reshape(P, 9), tvec, rms0[:, None], rms1[:, None], its.double()[:, None]], dim=1).cpu().numpy()
     return (host[:, :9].reshape(P, 3, 3).copy(), host[:, 9:12].reshape(P, 3, 1).copy(),
             dict(rms_before=host[:, 12].copy(), rms_after=host[:, 13].copy(), iterations=host[:, 14].astype("int32")))

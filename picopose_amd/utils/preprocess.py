@@ -75,9 +75,7 @@ def crop_instance(image_u8, mask_u8, det_bbox_xywh, img_size=224, pts_size=64, m
     rgb = torch.empty(3, img_size, img_size, dtype=torch.float32, device=device)
     mask = torch.empty(img_size, img_size, dtype=torch.float32, device=device)
     mean, std = (ctypes.c_double * 3)(*CLIP_MEAN), (ctypes.c_double * 3)(*CLIP_STD)
-    _lib.check(_lib.lib().pp_crop_resize_normalize(img_d.data_ptr(), h, w, msk_d.data_ptr(), y1, y2, x1, x2, img_size,
-                                                   int(rgb_mask_flag), mean, std, rgb.data_ptr(), mask.data_ptr(),
-                                                   _lib.stream_ptr()), "pp_crop_resize_normalize")
+    _lib.call("pp_crop_resize_normalize", img_d, h, w, msk_d, y1, y2, x1, x2, img_size, int(rgb_mask_flag), mean, std, rgb, mask)
     M_crop = np.array([[1, 0, -bbox[2]], [0, 1, -bbox[0]], [0, 0, 1]], dtype=np.float32)
     M_resize = np.array([[img_size / (y2 - y1), 0, 0], [0, img_size / (x2 - x1), 0], [0, 0, 1]], dtype=np.float32)
     M = M_resize @ M_crop
@@ -106,18 +104,14 @@ def crop_template(rgba_u8, depth_mm, K, object_pose_mm, img_size=224, pts_size=6
     rgb = torch.empty(3, img_size, img_size, dtype=torch.float32, device=device)
     mout = torch.empty(img_size, img_size, dtype=torch.float32, device=device)
     mean, std = (ctypes.c_double * 3)(*CLIP_MEAN), (ctypes.c_double * 3)(*CLIP_STD)
-    L = _lib.lib()
-    _lib.check(L.pp_crop_resize_normalize(img_d.data_ptr(), h, w, msk_rgb_d.data_ptr(), y1, y2, x1, x2, img_size, int(rgb_mask_flag),
-                                          mean, std, rgb.data_ptr(), None, _lib.stream_ptr()), "pp_crop_resize_normalize")
+    _lib.call("pp_crop_resize_normalize", img_d, h, w, msk_rgb_d, y1, y2, x1, x2, img_size, int(rgb_mask_flag), mean, std, rgb, None)
     dummy = torch.empty(3, img_size, img_size, dtype=torch.float32, device=device)
-    _lib.check(L.pp_crop_resize_normalize(img_d.data_ptr(), h, w, msk_d.data_ptr(), y1, y2, x1, x2, img_size, 0, mean, std,
-                                          dummy.data_ptr(), mout.data_ptr(), _lib.stream_ptr()), "pp_crop_resize_normalize")
+    _lib.call("pp_crop_resize_normalize", img_d, h, w, msk_d, y1, y2, x1, x2, img_size, 0, mean, std, dummy, mout)
     depth_d = torch.from_numpy(np.ascontiguousarray(np.asarray(depth_mm) / 1000.0, dtype=np.float32)).to(device)   # :227
     pts = torch.empty(pts_size, pts_size, 3, dtype=torch.float32, device=device)
     K = np.asarray(K, dtype=np.float64)
-    _lib.check(L.pp_depth_points_nearest(depth_d.data_ptr(), h, w, y1, y2, x1, x2, pts_size, float(K[0, 0]), float(K[1, 1]),
-                                         float(K[0, 2]), float(K[1, 2]), pts.data_ptr(), _lib.stream_ptr()),
-               "pp_depth_points_nearest")
+    _lib.call("pp_depth_points_nearest", depth_d, h, w, y1, y2, x1, x2, pts_size, float(K[0, 0]), float(K[1, 1]), float(K[0, 2]),
+              float(K[1, 2]), pts)
     pose = np.array(object_pose_mm, dtype=np.float64)
     pose[:3, 3] = pose[:3, 3] / 1000.0                                  # :246
     M_crop = np.array([[1, 0, -bbox[2]], [0, 1, -bbox[0]], [0, 0, 1]], dtype=np.float32)

@@ -9,9 +9,7 @@ def calc_pred_Ms(pred_scale, pred_inplane, pred_translation, tem_pose, tem_K, te
     s, ip, tr, pose, K, M = _lib.dev_f32(pred_scale, pred_inplane, pred_translation, tem_pose, tem_K, tem_M)
     B = s.shape[0]
     out = torch.empty(B, 3, 3, dtype=torch.float32, device=s.device)
-    rc = _lib.lib().pp_calc_pred_Ms(s.data_ptr(), ip.data_ptr(), tr.data_ptr(), pose.data_ptr(), K.data_ptr(),
-                                    M.data_ptr(), B, float(trans_scale), out.data_ptr(), _lib.stream_ptr())
-    _lib.check(rc, "pp_calc_pred_Ms")
+    _lib.call("pp_calc_pred_Ms", s, ip, tr, pose, K, M, B, float(trans_scale), out)
     return out
 
 
@@ -26,8 +24,6 @@ def gather(features, index_patches):
     N = idx.shape[1]
     out = torch.empty(B, N, C, dtype=torch.float32, device=feat.device)
     count = torch.empty(B, dtype=torch.int32, device=feat.device)
-    rc = _lib.lib().pp_gather_valid(feat.data_ptr(), idx.data_ptr(), B, C, H, W, N, out.data_ptr(),
-                                    count.data_ptr(), _lib.stream_ptr())
-    _lib.check(rc, "pp_gather_valid")
+    _lib.call("pp_gather_valid", feat, idx, B, C, H, W, N, out, count)
     counts = count.tolist()
     return torch.cat([out[b, : counts[b]] for b in range(B)], dim=0)

@@ -9,7 +9,6 @@ THIS IS THE PROJECT'S OWN RULE, not a published protocol's and not the reference
 alone).  Detection masks are modal: they hold the visible part of an object only.  Without a depth image the render cannot be
 clipped to what is visible, so the RGB-only `iou` penalises an occluded object — equally for all of its hypotheses, which leaves
 their ranking meaningful but makes the value not comparable across instances.  Accuracy on real data is unmeasured and not claimed."""
-import ctypes
 import math
 
 import numpy as np
@@ -21,7 +20,6 @@ from .masks import MAX_MASKS, RunTable, area_of_ends, rle_counts, run_ends
 from .scene import DEFAULT_WORKSPACE_BYTES
 
 COUNTS = ("render", "inter", "valid", "agree", "front", "behind", "vis", "vis_inter")       # the columns of `counts`
-_I32P = ctypes.POINTER(ctypes.c_int)
 
 
 def _ratio(num, den, empty):
@@ -126,7 +124,6 @@ def verify_poses(models, obj_ids, R, t, K, segmentations, size, mask_index=None,
     windows = scn.view_windows(models, obj, img, poses, cams, H, W, near, window)
     groups = scn.view_groups(models, obj, windows, None, None, workspace_bytes)
     scn.require_gpu(dev)
-    L = _lib.lib()
     bits, area = RunTable.upload(runs, dev).pack(H * W)
     words = bits.shape[1]
     depth_d = None if depth is None else scn.depth_mm(depth, scale, dev)
@@ -137,10 +134,8 @@ def verify_poses(models, obj_ids, R, t, K, segmentations, size, mask_index=None,
         packed = scn.PackedScene(models, cams, H, W, near, obj[v0:v1], img[v0:v1], poses[v0:v1], windows[v0:v1])
         ws = torch.empty(_lib.workspace_bytes("pp_vsd_workspace_bytes", packed.samples, packed.faces), dtype=torch.uint8, device=dev)
         vm = np.ascontiguousarray(midx[v0:v1])
-        _lib.check(L.pp_pose_verify(ctypes.byref(packed.scene), bits.data_ptr(), M, words, midx_d.data_ptr() + 4 * v0, vm.ctypes.data_as(_I32P),
-                                    None if depth_d is None else depth_d.data_ptr(), float(delta), ws.data_ptr(), ws.numel(),
-                                    counts.data_ptr() + 4 * len(COUNTS) * v0, near_d.data_ptr() + 4 * v0, _lib.stream_ptr()),
-                   "pp_pose_verify")
+        _lib.call("pp_pose_verify", packed.scene, bits, M, words, midx_d[v0:], vm, depth_d, float(delta), ws, ws.numel(), counts[v0:],
+                  near_d[v0:])
     # the scores on the host, from the integers (the call reads near_count back anyway), then back beside the counts
     iou, viou, agree, score = (torch.from_numpy(a).to(dev) for a in scores(counts.cpu().numpy(), area.cpu().numpy()[midx], depth is not None))
     return {"counts": counts, "mask_area": area, "iou": iou, "visible_iou": viou, "agreement": agree, "score": score,

@@ -58,7 +58,8 @@ int pp_Spread(const float* a, /* first */
 
 def test_header_parser_on_every_form_the_header_uses():
     c = ctypes
-    protos, structs, consts = _lib.parse_header(_MINI_HEADER)
+    protos, structs, consts, streamed = _lib.parse_header(_MINI_HEADER)
+    assert streamed == {"pp_Spread"}                 # `void* stream` LAST; pp_voids has one in the middle, which is an argument like any
     X = structs["PpX"]
     assert list(structs) == ["PpX"] and issubclass(X, c.Structure) and X.__name__ == "PpX"
     assert X._fields_ == [("a", c.c_int), ("b", c.c_int), ("c", c.c_int), ("p", c.c_void_p), ("s", c.c_longlong),
@@ -189,6 +190,81 @@ def test_argument_validation_needs_no_gpu():
     assert L.pp_corr_lookup_nhwc_ex(p, 64, p, None, None, 1, p, 1, 16, 16, 64, 1, 2, 2, 3, p, 32, None) == -1
 
 
+def _header_text():
+    import os
+
+    return open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "picopose_hip.h")).read()
+
+
+def test_call_appends_a_stream_exactly_where_the_header_has_one():
+    import re
+
+    text = re.sub(r"/\*.*?\*/", " ", _header_text(), flags=re.S)
+    last_is_stream = {m.group(1): re.search(r"(^|,)\s*void\s*\*\s*stream\s*$", m.group(2)) is not None
+                      for m in re.finditer(r"\b(pp_\w+)\s*\(([^()]*)\)\s*;", text)}
+    assert set(last_is_stream) == set(_lib.declared_symbols())
+    assert any(last_is_stream.values()) and not all(last_is_stream.values())
+    for name, want in last_is_stream.items():
+        if _lib._PROTOTYPES[name][0] is ctypes.c_int:
+            assert _lib._plan(name)[2] == want, name
+        else:                                        # a size query or pp_strerror: no status, no plan, no stream
+            assert not want, name
+            with pytest.raises(TypeError, match=name):
+                _lib._plan(name)
+
+
+def test_call_raises_on_a_rejecting_entry():
+    import torch
+
+    x, y = torch.zeros(4, 8), torch.zeros(4, 8)
+    text = _lib.lib().pp_strerror(_lib.PP_EINVAL).decode()
+    for args in ((x, 0, 8, 1e-12, y), (None, 0, 8, 1e-12, None)):        # n = 0: PP_EINVAL before any device work
+        with pytest.raises(_lib.PicoPoseHipError) as e:
+            _lib.call("pp_descriptor_normalize", *args, stream=None)
+        assert "pp_descriptor_normalize" in str(e.value) and text in str(e.value)
+        with pytest.raises(_lib.PicoPoseHipError) as e:
+            _lib.call("pp_descriptor_normalize", *args, stream=None, what="label")
+        assert "label failed" in str(e.value) and text in str(e.value) and "pp_descriptor_normalize" not in str(e.value)
+
+
+def test_call_converts_like_the_hand_written_spelling():
+    import numpy as np
+
+    def size(query, *args):
+        need = ctypes.c_size_t()
+        _lib.call(query, *args, ctypes.byref(need))
+        return need.value
+
+    off = np.array([0, 100, 350, 1000], dtype=np.int32)
+    by_hand = ctypes.c_size_t()
+    assert _lib.lib().pp_model_diameter_workspace_bytes(off.ctypes.data, 3, ctypes.byref(by_hand)) == _lib.PP_OK and by_hand.value > 0
+    assert size("pp_model_diameter_workspace_bytes", off, 3) == by_hand.value
+    assert size("pp_model_diameter_workspace_bytes", off.ctypes.data, 3) == by_hand.value
+    assert _lib.workspace_bytes("pp_model_diameter_workspace_bytes", off, 3) == by_hand.value
+    assert _lib.address(off[1:]) == off.ctypes.data + 4 and _lib.address(None) is None      # a view passes its own address
+
+    tensors = (_lib.PpAdamTensor * 2)()
+    for t, n in zip(tensors, (1000, 4096)):
+        t.p, t.m, t.v, t.n = 256, 512, 768, n            # (addresses are not read by the size query)
+    assert _lib.lib().pp_adam_workspace_bytes(tensors, 2, ctypes.byref(by_hand)) == _lib.PP_OK and by_hand.value > 0
+    assert size("pp_adam_workspace_bytes", tensors, 2) == by_hand.value
+    assert size("pp_adam_workspace_bytes", ctypes.byref(tensors[0]), 2) == by_hand.value      # (tensors[0] shares the array's memory)
+    assert size("pp_adam_workspace_bytes", tensors[0], 1) == size("pp_adam_workspace_bytes", ctypes.byref(tensors[0]), 1) > 0
+
+
+def test_call_misuse_is_a_type_error_naming_the_entry():
+    need = ctypes.c_size_t()
+    with pytest.raises(TypeError, match=r"pp_descriptor_normalize takes 5 arguments and a stream, 4 given"):
+        _lib.call("pp_descriptor_normalize", None, 0, 8, 1e-12, stream=None)
+    with pytest.raises(TypeError, match=r"pp_stage1_workspace_bytes takes 4 arguments, 5 given"):
+        _lib.call("pp_stage1_workspace_bytes", 32, 162, 768, ctypes.byref(need), None)
+    with pytest.raises(TypeError, match="pp_stage1_workspace_bytes takes no stream"):
+        _lib.call("pp_stage1_workspace_bytes", 32, 162, 768, ctypes.byref(need), stream=None)
+    for name, args in (("pp_train_keypoints_workspace_bytes", (2,)), ("pp_strerror", (0,))):       # size_t / const char*: not statuses
+        with pytest.raises(TypeError, match=name):
+            _lib.call(name, *args)
+
+
 def test_state_dict_names_shapes_equal_the_reference(golden_dir):
     """`Net(cfg).state_dict()` must carry the reference Net's tensors — same names, same ORDER, same shapes and
     dtypes — for ViT-S/B/L, so that Lite.load_from_checkpoint(..., network=model) loads the authors' checkpoint
@@ -288,6 +364,33 @@ def test_pack_cache_follows_in_place_parameter_updates():
     net.invalidate_packed()
     assert all(m._pack_cache is None for m in net.modules() if hasattr(m, "_pack_cache"))
     assert not torch.equal(fd.packed()["proj0"], third["proj0"])
+
+
+@pytest.mark.gpu
+def test_call_passes_a_views_address_and_launches_on_the_current_stream():
+    import torch
+
+    x = torch.randn(3, 8, generator=torch.Generator().manual_seed(0)).cuda()
+    ref = torch.nn.functional.normalize(x.double(), dim=1)
+    tol = 8 * 2.0 ** -24                 # unit rows from an 8-term fp32 sum of squares, a square root and a division
+    y = torch.zeros_like(x)
+    _lib.call("pp_normalize_rows", x, 3, 8, 1e-12, y)
+    torch.cuda.synchronize()
+    assert (y.double() - ref).abs().max().item() <= tol
+    y = torch.zeros(2, 8, device="cuda")
+    _lib.call("pp_normalize_rows", x[1:], 2, 8, 1e-12, y)          # a view is passed as ITS address, not its storage's
+    torch.cuda.synchronize()
+    assert (y.double() - ref[1:]).abs().max().item() <= tol
+    # the current stream is the one used: the input is produced on a side stream and only that stream is waited for
+    side = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(side):
+        big = torch.randn(1 << 22, device="cuda").sort().values           # work ahead of the launch on the same stream
+        x2 = x + big[:1] * 0
+        y2 = torch.zeros_like(x)
+        _lib.call("pp_normalize_rows", x2, 3, 8, 1e-12, y2)
+    side.synchronize()
+    assert (y2.double() - ref).abs().max().item() <= tol
 
 
 @pytest.mark.gpu

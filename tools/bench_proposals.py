@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import detections_oracle as do  # noqa: E402
 
-from picopose_amd import masks  # noqa: E402
+from picopose_amd import _lib, masks  # noqa: E402
 from picopose_amd import proposals as pr  # noqa: E402
 
 
@@ -47,11 +47,9 @@ def bench_match(iters, burst, P=200, O=30, V=42, C=1024, topk=5):
     q = pr.normalize_descriptors(torch.randn(P, C, generator=g).cuda())
     score, view = torch.empty((P, O), device="cuda"), torch.empty((P, O), dtype=torch.int32, device="cuda")
     label, best = torch.empty((P,), dtype=torch.int32, device="cuda"), torch.empty((P,), device="cuda")
-    off = bank.offsets_host.ctypes.data_as(pr._I32P)
 
     def hip():
-        pr._call("pp_proposal_match", q.data_ptr(), P, bank.rows.data_ptr(), bank.offsets.data_ptr(), off, O, C, topk, score.data_ptr(),
-                 view.data_ptr(), label.data_ptr(), best.data_ptr())
+        _lib.call("pp_proposal_match", q, P, bank.rows, bank.offsets, bank.offsets_host, O, C, topk, score, view, label, best)
 
     def torch_leg():
         cos = torch.matmul(q, bank.rows.t()).view(P, O, V)
@@ -83,7 +81,7 @@ def bench_overlaps(iters, burst, n=100, H=480, W=640):
     bits, _ = pack()
     words, n_runs = bits.shape[1], table.n_runs
     inter = torch.empty((n, n), dtype=torch.int32, device="cuda")
-    sect = lambda: pr._call("pp_mask_intersections", bits.data_ptr(), n, words, inter.data_ptr())  # noqa: E731
+    sect = lambda: _lib.call("pp_mask_intersections", bits, n, words, inter)  # noqa: E731
     for _ in range(3):
         burst_ms(pack, burst), burst_ms(sect, burst)
     t_pack, t_sect, t_call = [], [], []
