@@ -82,6 +82,13 @@ unsigned* pp_saturation_word();
 
 static inline int pp_last_launch() { return hipGetLastError() == hipSuccess ? PP_OK : PP_ELAUNCH; }
 
+// the size of a workspace section: the next one starts on a 256-byte boundary
+constexpr size_t align256(size_t n) { return (n + 255) / 256 * 256; }
+
+// argument checks of the float32 scalars and tables of a call (a NaN fails both)
+__host__ __device__ inline bool finite32(float v) { return fabsf(v) <= 3.402823466e38f; }
+inline bool positive_finite(float v) { return v > 0.f && finite32(v); }
+
 
 // Timing hooks: when enabled (pp_prof_enable) the entry point that launches a roofline
 // kernel brackets exactly that launch with two hipEvents on the caller's stream.

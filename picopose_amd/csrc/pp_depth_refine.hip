@@ -20,7 +20,7 @@
 #include "pp_common.h"
 
 #pragma clang fp contract(off)
-#include "pp_vsd_raster_dev.h"
+#include "pp_window_dev.h"
 
 namespace {
 
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(BLOCK) void refine_accumulate_kernel(Scene s, const
         const unsigned long long key = zv[i];
         if (key == ~0ull) continue;
         const int yy = i / ww, x = x0 + (i - yy * ww), y = ys + yy;
-        const float z_r = __uint_as_float((unsigned)(key >> 32));
+        const float z_r = word_depth(key);                        // (covered: the check above)
         const unsigned f = (unsigned)key;
         const float z_t = dimg[(size_t)y * s.W + x];
         if (!(z_t > 0.f)) continue;                               // missing

@@ -6,8 +6,8 @@
 //                    across the tile, running maximum of the SQUARED distance per symmetry; wave reduction by shuffles, waves through
 //                    LDS, one square root per (pair, symmetry)
 //   add_kernel       one workgroup per pair: per-lane float64 partial sums of the distances, fixed reduction tree
-//   adds_kernel      all-pairs nearest neighbour: a workgroup owns ADDS_TILE estimate-side points (ADDS_EPT per lane, in registers),
-//                    streams the ground-truth-side points through LDS, running minimum of the squared distance in difference form
+//   adds_kernel      all-pairs nearest neighbour on pp_pointset_dev.h's core: a workgroup owns ADDS_TILE estimate-side points (ADDS_EPT
+//                    per lane, in registers), streams the ground-truth-side points through LDS, running minimum of the squared distance
 //   finalize_kernel  one wave per pair: minimum over the symmetries with its index (lowest index on a tie), ADD-S tile sums in order
 //
 // Maximum and minimum are exact and order-independent and every sum has a fixed tree: the results do not depend on launch order,
@@ -18,22 +18,15 @@
 #include "pp_common.h"
 
 #pragma clang fp contract(off)
+#include "pp_pointset_dev.h"
 
 namespace {
 
-constexpr int BLOCK = 256;
+constexpr int BLOCK = POINT_BLOCK;
 constexpr int WAVES = BLOCK / 64;
 constexpr int TS = 4;                              // symmetries per workgroup of sym_max_kernel
 constexpr int ADDS_EPT = PP_EVAL_ADDS_TILE / BLOCK;  // estimate-side points per lane of adds_kernel
-constexpr int ADDS_GT = 256;                       // ground-truth-side points per LDS tile
 static_assert(PP_EVAL_ADDS_TILE % BLOCK == 0, "ADD-S tile");
-
-// X = ((T0 x + T1 y) + T2 z) + T9, ... : one rounding per operation, in this order (the numpy restatement does the same)
-__device__ __forceinline__ void apply(const float* __restrict__ T, float x, float y, float z, float& X, float& Y, float& Z) {
-    X = ((T[0] * x + T[1] * y) + T[2] * z) + T[9];
-    Y = ((T[3] * x + T[4] * y) + T[5] * z) + T[10];
-    Z = ((T[6] * x + T[7] * y) + T[8] * z) + T[11];
-}
 
 __global__ __launch_bounds__(BLOCK) void compose_kernel(const int* __restrict__ pair_obj, const float* __restrict__ R_gt,
                                                         const float* __restrict__ t_gt, const float* __restrict__ sym_R,
@@ -200,40 +193,15 @@ __global__ __launch_bounds__(BLOCK) void adds_kernel(const float* __restrict__ v
         G[9 + k] = t_gt[3 * (size_t)p + k];
     }
     const float* vp = verts + 3 * (size_t)v0;
-    float ex[ADDS_EPT], ey[ADDS_EPT], ez[ADDS_EPT], mn[ADDS_EPT];
-    bool valid[ADDS_EPT];
-#pragma unroll
-    for (int k = 0; k < ADDS_EPT; ++k) {
-        const int i = tile * PP_EVAL_ADDS_TILE + k * BLOCK + (int)threadIdx.x;
-        valid[k] = i < nv;
-        const size_t c = (size_t)(valid[k] ? i : nv - 1);
-        apply(E, vp[3 * c], vp[3 * c + 1], vp[3 * c + 2], ex[k], ey[k], ez[k]);
-        mn[k] = INFINITY;
-    }
-    __shared__ float4 sh[ADDS_GT];
-    for (int g0 = 0; g0 < nv; g0 += ADDS_GT) {
-        const int cnt = nv - g0 < ADDS_GT ? nv - g0 : ADDS_GT;
-        __syncthreads();
-        if ((int)threadIdx.x < cnt) {
-            const size_t c = (size_t)(g0 + (int)threadIdx.x);
-            float X, Y, Z;
-            apply(G, vp[3 * c], vp[3 * c + 1], vp[3 * c + 2], X, Y, Z);
-            sh[threadIdx.x] = make_float4(X, Y, Z, 0.f);
-        }
-        __syncthreads();
-        for (int q = 0; q < cnt; ++q) {
-            const float4 g = sh[q];
-#pragma unroll
-            for (int k = 0; k < ADDS_EPT; ++k) {
-                const float dx = ex[k] - g.x, dy = ey[k] - g.y, dz = ez[k] - g.z;
-                mn[k] = fminf(mn[k], (dx * dx + dy * dy) + dz * dz);
-            }
-        }
-    }
+    LanePoints<ADDS_EPT> e;
+    load_lane_points(tile * PP_EVAL_ADDS_TILE, nv, Mapped{vp, E}, e);
+    RunningMin<ADDS_EPT> mn;
+    __shared__ float4 sh[POINT_BLOCK];
+    stream_pairs(e, 0, nv, sh, Mapped{vp, G}, mn);
     double acc = 0.0;
 #pragma unroll
     for (int k = 0; k < ADDS_EPT; ++k)
-        if (valid[k]) acc = acc + (double)sqrtf(mn[k]);
+        if (e.valid[k]) acc = acc + (double)sqrtf(mn.d2[k]);
     __shared__ double sm[WAVES];
     const double s = block_sum(acc, sm);
     if (threadIdx.x == 0) part[(size_t)p * tiles_max + tile] = s;
@@ -285,8 +253,6 @@ __global__ __launch_bounds__(BLOCK) void finalize_kernel(const int* __restrict__
         adds[p] = (float)(s / (double)nv);
     }
 }
-
-inline size_t align256(size_t n) { return (n + 255) / 256 * 256; }
 
 struct Layout {
     size_t xf, err0, err1, part, total;

@@ -1,7 +1,7 @@
 // Model metadata from the vertices alone: the BOP diameter (the largest vertex-to-vertex distance, with the pair that attains it) and
 // the directed Hausdorff distance of a vertex set under candidate rigid transforms, the measurement behind a symmetry search
 // (picopose_amd/model_info.py plans every call; the contract is stated in include/picopose_hip.h, "MODEL INFO", and restated in numpy by
-// tests/model_info_oracle.py).  Both are all-pairs problems on pp_eval.hip's adds_kernel pattern: a workgroup owns MI_TILE points
+// tests/model_info_oracle.py).  Both are all-pairs problems on pp_pointset_dev.h's core, like ADD-S: a workgroup owns MI_TILE points
 // (MI_EPT per lane, in registers), the other side streams through LDS as broadcast float4s, squared distances in difference form.
 //
 //   diameter_plan_kernel      one lane: the prefix sums of the objects' work counts (tiles x ranges per object)
@@ -20,23 +20,16 @@
 #include "pp_common.h"
 
 #pragma clang fp contract(off)
+#include "pp_pointset_dev.h"
 
 namespace {
 
-constexpr int BLOCK = 256;
+constexpr int BLOCK = POINT_BLOCK;
 constexpr int WAVES = BLOCK / 64;
 constexpr int MI_TILE = PP_MODEL_INFO_TILE;
 constexpr int MI_EPT = MI_TILE / BLOCK;           // register-side points per lane
-constexpr int MI_LDS = 256;                       // streamed-side points per LDS tile
 constexpr int DIAM_JR = 2;                        // j-tiles per workgroup of diameter_kernel
-static_assert(MI_TILE % BLOCK == 0 && MI_TILE % MI_LDS == 0 && MI_LDS == BLOCK, "tiles");
-
-// X = ((T0 x + T1 y) + T2 z) + T9, ... : pp_eval.hip's apply, one rounding per operation, in this order
-__device__ __forceinline__ void apply(const float* __restrict__ T, float x, float y, float z, float& X, float& Y, float& Z) {
-    X = ((T[0] * x + T[1] * y) + T[2] * z) + T[9];
-    Y = ((T[3] * x + T[4] * y) + T[5] * z) + T[10];
-    Z = ((T[6] * x + T[7] * y) + T[8] * z) + T[11];
-}
+static_assert(MI_TILE % BLOCK == 0, "tiles");
 
 __host__ __device__ inline long long diam_work(int nv) {
     const long long tiles = ((long long)nv + MI_TILE - 1) / MI_TILE;
@@ -111,56 +104,33 @@ __global__ __launch_bounds__(BLOCK) void diameter_kernel(const float* __restrict
     }
     const int tj1 = tj0 + DIAM_JR < tiles ? tj0 + DIAM_JR : tiles;
     const float* vp = verts + 3 * (size_t)v0;
-    float px[MI_EPT], py[MI_EPT], pz[MI_EPT], bd[MI_EPT];
+    LanePoints<MI_EPT> pt;
+    load_lane_points(ti * MI_TILE, nv, Points{vp}, pt);
+    float bd[MI_EPT];
     int bj[MI_EPT];
 #pragma unroll
     for (int k = 0; k < MI_EPT; ++k) {
-        const int i = ti * MI_TILE + k * BLOCK + (int)threadIdx.x;
-        const size_t c = (size_t)(i < nv ? i : nv - 1);
-        px[k] = vp[3 * c];
-        py[k] = vp[3 * c + 1];
-        pz[k] = vp[3 * c + 2];
         bd[k] = -1.f;
         bj[k] = 0;
     }
-    __shared__ float4 sh[MI_LDS];
-    const int j_end = tj1 * MI_TILE < nv ? tj1 * MI_TILE : nv;
-    for (int g0 = tj0 * MI_TILE; g0 < j_end; g0 += MI_LDS) {
-        const int cnt = j_end - g0 < MI_LDS ? j_end - g0 : MI_LDS;
-        __syncthreads();
-        if ((int)threadIdx.x < cnt) {
-            const size_t c = (size_t)(g0 + (int)threadIdx.x);
-            sh[threadIdx.x] = make_float4(vp[3 * c], vp[3 * c + 1], vp[3 * c + 2], 0.f);
-        }
-        __syncthreads();
-        // j ascends and the compare is strict: per register-side point the lowest j that attains its maximum is kept
-        if (g0 >= (ti + 1) * MI_TILE) {                          // every j of this tile lies beyond every i of the workgroup
-            for (int q = 0; q < cnt; ++q) {
-                const float4 g = sh[q];
-#pragma unroll
-                for (int k = 0; k < MI_EPT; ++k) {
-                    const float dx = px[k] - g.x, dy = py[k] - g.y, dz = pz[k] - g.z;
-                    const float d2 = (dx * dx + dy * dy) + dz * dz;
-                    if (d2 > bd[k]) {
-                        bd[k] = d2;
-                        bj[k] = g0 + q;
-                    }
+    __shared__ float4 sh[POINT_BLOCK];
+    // j ascends and the compare is strict: per register-side point the lowest j that attains its maximum is kept
+    for (int tj = tj0; tj < tj1; ++tj) {
+        const int j0 = tj * MI_TILE, j1 = j0 + MI_TILE < nv ? j0 + MI_TILE : nv;
+        if (tj > ti) {                                           // every j of this tile lies beyond every i of the workgroup
+            stream_pairs(pt, j0, j1, sh, Points{vp}, [&](int k, int j, float d2) {
+                if (d2 > bd[k]) {
+                    bd[k] = d2;
+                    bj[k] = j;
                 }
-            }
+            });
         } else {                                                 // the diagonal tile: only j > i counts
-            for (int q = 0; q < cnt; ++q) {
-                const float4 g = sh[q];
-                const int j = g0 + q;
-#pragma unroll
-                for (int k = 0; k < MI_EPT; ++k) {
-                    const float dx = px[k] - g.x, dy = py[k] - g.y, dz = pz[k] - g.z;
-                    const float d2 = (dx * dx + dy * dy) + dz * dz;
-                    if (j > ti * MI_TILE + k * BLOCK + (int)threadIdx.x && d2 > bd[k]) {
-                        bd[k] = d2;
-                        bj[k] = j;
-                    }
+            stream_pairs(pt, j0, j1, sh, Points{vp}, [&](int k, int j, float d2) {
+                if (j > ti * MI_TILE + k * BLOCK + (int)threadIdx.x && d2 > bd[k]) {
+                    bd[k] = d2;
+                    bj[k] = j;
                 }
-            }
+            });
         }
     }
     // i ascends with k and the compare is strict: the lane's lowest i on a tie; a lane's point past the object's last one holds nothing
@@ -169,7 +139,7 @@ __global__ __launch_bounds__(BLOCK) void diameter_kernel(const float* __restrict
 #pragma unroll
     for (int k = 0; k < MI_EPT; ++k) {
         const int i = ti * MI_TILE + k * BLOCK + (int)threadIdx.x;
-        if (i < nv && bd[k] > d) {
+        if (pt.valid[k] && bd[k] > d) {
             d = bd[k];
             bi = i;
             bjj = bj[k];
@@ -219,38 +189,15 @@ __global__ __launch_bounds__(BLOCK) void hausdorff_kernel(const float* __restric
     for (int k = 0; k < 12; ++k) T[k] = cand_T[12 * (size_t)c + k];
     const float* qp = q_verts + 3 * (size_t)q0;
     const float* vp = verts + 3 * (size_t)v0;
-    float ex[MI_EPT], ey[MI_EPT], ez[MI_EPT], mn[MI_EPT];
-    bool valid[MI_EPT];
-#pragma unroll
-    for (int k = 0; k < MI_EPT; ++k) {
-        const int i = tile * MI_TILE + k * BLOCK + (int)threadIdx.x;
-        valid[k] = i < nq;
-        const size_t a = (size_t)(valid[k] ? i : nq - 1);
-        apply(T, qp[3 * a], qp[3 * a + 1], qp[3 * a + 2], ex[k], ey[k], ez[k]);
-        mn[k] = INFINITY;
-    }
-    __shared__ float4 sh[MI_LDS];
-    for (int g0 = 0; g0 < nv; g0 += MI_LDS) {
-        const int cnt = nv - g0 < MI_LDS ? nv - g0 : MI_LDS;
-        __syncthreads();
-        if ((int)threadIdx.x < cnt) {
-            const size_t a = (size_t)(g0 + (int)threadIdx.x);
-            sh[threadIdx.x] = make_float4(vp[3 * a], vp[3 * a + 1], vp[3 * a + 2], 0.f);
-        }
-        __syncthreads();
-        for (int q = 0; q < cnt; ++q) {
-            const float4 g = sh[q];
-#pragma unroll
-            for (int k = 0; k < MI_EPT; ++k) {
-                const float dx = ex[k] - g.x, dy = ey[k] - g.y, dz = ez[k] - g.z;
-                mn[k] = fminf(mn[k], (dx * dx + dy * dy) + dz * dz);
-            }
-        }
-    }
+    LanePoints<MI_EPT> e;
+    load_lane_points(tile * MI_TILE, nq, Mapped{qp, T}, e);
+    RunningMin<MI_EPT> mn;
+    __shared__ float4 sh[POINT_BLOCK];
+    stream_pairs(e, 0, nv, sh, Points{vp}, mn);
     float m = 0.f;
 #pragma unroll
     for (int k = 0; k < MI_EPT; ++k)
-        if (valid[k]) m = fmaxf(m, mn[k]);
+        if (e.valid[k]) m = fmaxf(m, mn.d2[k]);
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) m = fmaxf(m, __shfl_xor(m, s, 64));
     __shared__ float sm[WAVES];
@@ -275,8 +222,6 @@ __global__ __launch_bounds__(BLOCK) void hausdorff_finalize_kernel(const int* __
     for (int t = 0; t < nt; ++t) m = fmaxf(m, part[(size_t)c * tiles_max + t]);
     h[c] = sqrtf(m);
 }
-
-inline size_t align256(size_t n) { return (n + 255) / 256 * 256; }
 
 // -> the total work of the objects, or -1: a table that does not start at 0 or does not increase, or too much work for one grid
 inline long long diameter_total_work(const int* vert_off_host, int n_objects) {

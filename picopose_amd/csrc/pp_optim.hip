@@ -41,8 +41,6 @@ struct Layout {
     size_t off_items, off_split, off_part, table_bytes, total;
 };
 
-constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // one element, in the order of torch.optim.adam._single_tensor_adam (fp32 opmath, scalars rounded to fp32 by the host).  Every torch op
 // there is a kernel of its own, so each op's result is rounded to fp32; inside one op the compiler contracts a * b + c into an fma.  The
 // same roundings here: contraction off, the fma of each op spelled out.

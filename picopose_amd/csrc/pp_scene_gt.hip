@@ -22,15 +22,13 @@
 #include "pp_common.h"
 
 #pragma clang fp contract(off)
-#include "pp_vsd_raster_dev.h"
+#include "pp_window_dev.h"
 
 namespace {
 
-constexpr int BLOCK = 256;
-constexpr int WAVES = BLOCK / 64;
+constexpr int BLOCK = WINDOW_BLOCK;
+constexpr int WAVES = WINDOW_WAVES;
 constexpr int NV = 11;             // all, valid, visib | obj x_min, y_min, x_max, y_max | visib x_min, y_min, x_max, y_max
-constexpr int MAX_CHUNKS = 128;    // workgroups over one view's window
-constexpr int CHUNK_SAMPLES = BLOCK * 16;
 
 // the frame inside the canvas and the tables the raster does not know
 struct Frame {
@@ -38,27 +36,17 @@ struct Frame {
     int H, W, pad_x, pad_y;
 };
 
-__device__ __forceinline__ float word_depth(unsigned long long key) {
-    return key == ~0ull ? 0.f : __uint_as_float((unsigned)(key >> 32));
-}
-
 __global__ __launch_bounds__(BLOCK) void scene_gt_composite_kernel(Scene s, Frame f, const unsigned long long* __restrict__ zbuf,
                                                                    unsigned long long* __restrict__ comp) {
-    for (int v = blockIdx.y; v < s.n_views; v += gridDim.y) {
-        const int* w = s.windows + 4 * (size_t)v;
-        const int x0 = w[0], y0 = w[1], ww = w[2] - w[0], wh = w[3] - w[1];
-        if (ww <= 0 || wh <= 0) continue;
-        const unsigned long long* zv = zbuf + s.view_zoff[v];
+    for_each_window(s, zbuf, [&](int v, const Window& win) {
         unsigned long long* out = comp + (size_t)s.view_img[v] * f.H * f.W;
-        const long long n = (long long)ww * wh;
-        for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * BLOCK) {
-            const int yy = (int)(i / ww), x = x0 + (int)(i - (long long)yy * ww) - f.pad_x, y = y0 + yy - f.pad_y;
-            if (x < 0 || x >= f.W || y < 0 || y >= f.H) continue;
-            const unsigned long long key = zv[i];
-            if (key == ~0ull) continue;
+        walk_window(win, [&](int xc, int yc, unsigned long long key) {
+            const int x = xc - f.pad_x, y = yc - f.pad_y;
+            if (x < 0 || x >= f.W || y < 0 || y >= f.H) return;
+            if (key == ~0ull) return;
             atomicMin(out + (size_t)y * f.W + x, (key & 0xFFFFFFFF00000000ull) | (unsigned)v);
-        }
-    }
+        });
+    });
 }
 
 __global__ __launch_bounds__(BLOCK) void scene_gt_resolve_kernel(const unsigned long long* __restrict__ comp, long long n,
@@ -98,55 +86,36 @@ __global__ __launch_bounds__(BLOCK) void scene_gt_reduce_kernel(Scene s, Frame f
                                                                 unsigned char* __restrict__ mask_all,
                                                                 unsigned char* __restrict__ mask_visib) {
     __shared__ int sm[WAVES][NV];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int v = blockIdx.y; v < s.n_views; v += gridDim.y) {
-        const int* w = s.windows + 4 * (size_t)v;
-        const int x0 = w[0], y0 = w[1], ww = w[2] - w[0], wh = w[3] - w[1];
-        if (ww <= 0 || wh <= 0) continue;
-        const long long n = (long long)ww * wh;
-        if ((long long)blockIdx.x * BLOCK >= n) continue;         // (uniform over the workgroup)
+    for_each_window(s, zbuf, [&](int v, const Window& win) {
         const int img = s.view_img[v];
         const float* k = f.cams + 4 * (size_t)img;
         const float fx = k[0], fy = k[1], cx = k[2], cy = k[3];
-        const unsigned long long* zv = zbuf + s.view_zoff[v];
         const size_t frame = (size_t)f.H * f.W;
         int val[NV];
 #pragma unroll
         for (int c = 0; c < NV; ++c) val[c] = c < 3 ? 0 : (((c - 3) & 2) ? INT_MIN : INT_MAX);
-        for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * BLOCK) {
-            const float z = word_depth(zv[i]);
-            if (!(z > 0.f)) continue;
-            const int yy = (int)(i / ww), x = x0 + (int)(i - (long long)yy * ww) - f.pad_x, y = y0 + yy - f.pad_y;
+        walk_window(win, [&](int xc, int yc, unsigned long long key) {
+            const float z = word_depth(key);
+            if (!(z > 0.f)) return;
+            const int x = xc - f.pad_x, y = yc - f.pad_y;
             val[0] += 1;
             val[3] = min(val[3], x), val[4] = min(val[4], y), val[5] = max(val[5], x), val[6] = max(val[6], y);
-            if (x < 0 || x >= f.W || y < 0 || y >= f.H) continue;
+            if (x < 0 || x >= f.W || y < 0 || y >= f.H) return;
             const size_t pix = (size_t)y * f.W + x;
             if (mask_all) mask_all[(size_t)v * frame + pix] = 255;
             const float z_test = depth ? depth[(size_t)img * frame + pix] : word_depth(comp[(size_t)img * frame + pix]);
             const bool missing = !(z_test > 0.f);
-            const float xr = ((float)x - cx) / fx, yr = ((float)y - cy) / fy;
-            const float r = sqrtf((xr * xr + yr * yr) + 1.f);
-            const float d = z * r, d_test = z_test * r;
-            const bool visib = d > 0.f && (missing || d - d_test <= delta);
+            const float r = ray_scale(x, y, fx, fy, cx, cy);
             val[1] += missing ? 0 : 1;
-            if (visib) {
+            if (visible(z * r, z_test * r, missing, delta)) {
                 val[2] += 1;
                 val[7] = min(val[7], x), val[8] = min(val[8], y), val[9] = max(val[9], x), val[10] = max(val[10], y);
                 if (mask_visib) mask_visib[(size_t)v * frame + pix] = 255;
             }
-        }
-#pragma unroll
-        for (int c = 0; c < NV; ++c) {
-            int a = val[c];
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) a = combine(c, a, __shfl_xor(a, d, 64));
-            if (lane == 0) sm[wave][c] = a;
-        }
-        __syncthreads();
+        });
+        const int a = block_reduce(val, sm, combine);
         if (threadIdx.x < NV) {
             const int c = threadIdx.x;
-            int a = sm[0][c];
-            for (int q = 1; q < WAVES; ++q) a = combine(c, a, sm[q][c]);
             if (c < 3) {
                 if (a != 0) atomicAdd(counts + 3 * (size_t)v + c, a);
             } else if ((c - 3) & 2) {
@@ -156,7 +125,7 @@ __global__ __launch_bounds__(BLOCK) void scene_gt_reduce_kernel(Scene s, Frame f
             }
         }
         __syncthreads();                                          // sm is reused by the workgroup's next view
-    }
+    });
 }
 
 inline bool canvas_dims(int H, int W, int pad_x, int pad_y, int& Hc, int& Wc) {
@@ -207,11 +176,6 @@ int pp_scene_gt(const PpScene* scene, const float* canvas_cams, const float* can
         pp_scene_gt_workspace_bytes(n.samples, n.total_faces, comp_pixels, &need) != PP_OK)
         return PP_EINVAL;
     if (((uintptr_t)workspace % 256) != 0 || workspace_bytes < need) return PP_EWORKSPACE;
-    long long max_window = 0;
-    for (int v = 0; v < n_views; ++v) {
-        const long long m = scene->view_zoff_host[v + 1] - scene->view_zoff_host[v];
-        max_window = m > max_window ? m : max_window;
-    }
 
     hipStream_t st = (hipStream_t)stream;
     const RasterWs ws = carve(workspace, n);
@@ -223,14 +187,10 @@ int pp_scene_gt(const PpScene* scene, const float* canvas_cams, const float* can
     if (rc != PP_OK) return rc;
     if (mask_all) PP_CHECK_HIP(hipMemsetAsync(mask_all, 0, (size_t)n_views * H * W, st));
     if (mask_visib) PP_CHECK_HIP(hipMemsetAsync(mask_visib, 0, (size_t)n_views * H * W, st));
-    const unsigned gv = (unsigned)(n_views < 65535 ? n_views : 65535);                          // (the kernels' view stride)
-    long long chunks = (max_window + CHUNK_SAMPLES - 1) / CHUNK_SAMPLES;
-    const long long cap = 8192 / gv > 1 ? 8192 / gv : 1;                                        // bound the grid of a call with many views
-    chunks = chunks < 1 ? 1 : (chunks > MAX_CHUNKS ? MAX_CHUNKS : chunks);
-    chunks = chunks > cap ? cap : chunks;
+    const dim3 grid = window_grid(n_views, n.max_window);
     if (composite) {
         PP_CHECK_HIP(hipMemsetAsync(comp, 0xFF, (size_t)comp_pixels * 8, st));
-        if (n.samples > 0) hipLaunchKernelGGL(scene_gt_composite_kernel, dim3((unsigned)chunks, gv), dim3(BLOCK), 0, st, s, f, ws.zbuf, comp);
+        if (n.samples > 0) hipLaunchKernelGGL(scene_gt_composite_kernel, grid, dim3(BLOCK), 0, st, s, f, ws.zbuf, comp);
         if (scene_depth || instance_map) {
             const long long per = (comp_pixels + BLOCK - 1) / BLOCK;
             hipLaunchKernelGGL(scene_gt_resolve_kernel, dim3((unsigned)(per < 2048 ? per : 2048)), dim3(BLOCK), 0, st, comp, comp_pixels,
@@ -239,7 +199,7 @@ int pp_scene_gt(const PpScene* scene, const float* canvas_cams, const float* can
     }
     hipLaunchKernelGGL(scene_gt_init_kernel, dim3((unsigned)((n_views + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, n_views, counts, boxes);
     if (n.samples > 0)
-        hipLaunchKernelGGL(scene_gt_reduce_kernel, dim3((unsigned)chunks, gv), dim3(BLOCK), 0, st, s, f, ws.zbuf, depth,
+        hipLaunchKernelGGL(scene_gt_reduce_kernel, grid, dim3(BLOCK), 0, st, s, f, ws.zbuf, depth,
                            depth ? nullptr : comp, delta, counts, boxes, mask_all, mask_visib);
     hipLaunchKernelGGL(scene_gt_finish_kernel, dim3((unsigned)((2 * n_views + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, n_views, boxes);
     return pp_last_launch();

@@ -78,8 +78,6 @@ struct S1Ws {
     size_t total;
 };
 
-__host__ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 __host__ S1Ws carve(void* base, int B, int N, int C) {
     S1Ws w;
     char* p = (char*)base;

@@ -31,9 +31,6 @@ constexpr int LCH = 32;                        // layers per LDS flush
 constexpr int REC = 6;                         // px_all, px_visib, x_min, y_min, x_max, y_max
 static_assert(TILE == BLOCK * PX, "a workgroup's tile is four pixels per lane");
 
-inline size_t align256(size_t n) { return (n + 255) / 256 * 256; }
-inline bool positive_finite(float v) { return v > 0.f && v <= 3.402823466e38f; }
-
 struct Composite {
     const unsigned char* rgba;                 // (L, H, W, 4)
     const float* z;                            // (L, H, W)

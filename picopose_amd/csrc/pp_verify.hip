@@ -21,15 +21,13 @@
 #include "pp_common.h"
 
 #pragma clang fp contract(off)
-#include "pp_vsd_raster_dev.h"
+#include "pp_window_dev.h"
 
 namespace {
 
-constexpr int BLOCK = 256;
-constexpr int WAVES = BLOCK / 64;
+constexpr int BLOCK = WINDOW_BLOCK;
+constexpr int WAVES = WINDOW_WAVES;
 constexpr int NC = PP_VERIFY_COUNTS;   // render, inter, valid, agree, front, behind, vis, vis_inter
-constexpr int MAX_CHUNKS = 128;        // workgroups over one view's window
-constexpr int CHUNK_SAMPLES = BLOCK * 16;
 
 struct Evidence {
     const unsigned* mask_bits;         // (n_masks, words)
@@ -39,41 +37,28 @@ struct Evidence {
     float delta;
 };
 
-__device__ __forceinline__ float word_depth(unsigned long long key) {
-    return key == ~0ull ? 0.f : __uint_as_float((unsigned)(key >> 32));
-}
-
 __global__ __launch_bounds__(BLOCK) void pose_verify_reduce_kernel(Scene s, Evidence ev, const unsigned long long* __restrict__ zbuf,
                                                                    int* __restrict__ counts) {
     __shared__ int sm[WAVES][NC];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int v = blockIdx.y; v < s.n_views; v += gridDim.y) {
-        const int* w = s.windows + 4 * (size_t)v;
-        const int x0 = w[0], y0 = w[1], ww = w[2] - w[0], wh = w[3] - w[1];
-        if (ww <= 0 || wh <= 0) continue;
-        const long long n = (long long)ww * wh;
-        if ((long long)blockIdx.x * BLOCK >= n) continue;         // (uniform over the workgroup)
+    for_each_window(s, zbuf, [&](int v, const Window& win) {
         const int img = s.view_img[v];
         const float* k = s.cams + 4 * (size_t)img;
         const float fx = k[0], fy = k[1], cx = k[2], cy = k[3];
-        const unsigned long long* zv = zbuf + s.view_zoff[v];
         const unsigned* mask = ev.mask_bits + (size_t)ev.view_mask[v] * ev.words;
         const float* depth = ev.depth ? ev.depth + (size_t)img * s.H * s.W : nullptr;
         int val[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) val[c] = 0;
-        for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * BLOCK) {
-            const float z = word_depth(zv[i]);
-            if (!(z > 0.f)) continue;
-            const int yy = (int)(i / ww), x = x0 + (int)(i - (long long)yy * ww), y = y0 + yy;      // in the frame: THE SCENE CHECKS
+        walk_window(win, [&](int x, int y, unsigned long long key) {                           // in the frame: THE SCENE CHECKS
+            const float z = word_depth(key);
+            if (!(z > 0.f)) return;
             const unsigned bit = (unsigned)x * (unsigned)s.H + (unsigned)y;
             const int in_mask = (int)((mask[bit >> 5] >> (bit & 31u)) & 1u);
             int valid = 0, front = 0, behind = 0;
             if (depth) {
                 const float z_test = depth[(size_t)y * s.W + x];
                 if (z_test > 0.f) {                                // (a NaN is missing)
-                    const float xr = ((float)x - cx) / fx, yr = ((float)y - cy) / fy;
-                    const float r = sqrtf((xr * xr + yr * yr) + 1.f);
+                    const float r = ray_scale(x, y, fx, fy, cx, cy);
                     const float d = z * r, d_test = z_test * r;
                     const float e = d - d_test;
                     valid = 1, front = e > ev.delta ? 1 : 0, behind = -e > ev.delta ? 1 : 0;
@@ -82,22 +67,11 @@ __global__ __launch_bounds__(BLOCK) void pose_verify_reduce_kernel(Scene s, Evid
             const int vis = 1 - front;
             val[0] += 1, val[1] += in_mask, val[2] += valid, val[3] += valid & ~(front | behind), val[4] += front, val[5] += behind;
             val[6] += vis, val[7] += vis & in_mask;
-        }
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            int a = val[c];
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) a += __shfl_xor(a, d, 64);
-            if (lane == 0) sm[wave][c] = a;
-        }
-        __syncthreads();
-        if (threadIdx.x < NC) {
-            int a = sm[0][threadIdx.x];
-            for (int q = 1; q < WAVES; ++q) a += sm[q][threadIdx.x];
-            if (a != 0) atomicAdd(counts + NC * (size_t)v + threadIdx.x, a);
-        }
+        });
+        const int a = block_reduce(val, sm, [](int, int p, int q) { return p + q; });
+        if (threadIdx.x < NC && a != 0) atomicAdd(counts + NC * (size_t)v + threadIdx.x, a);
         __syncthreads();                                          // sm is reused by the workgroup's next view
-    }
+    });
 }
 
 }  // namespace
@@ -118,11 +92,6 @@ int pp_pose_verify(const PpScene* scene, const unsigned* mask_bits, int n_masks,
     size_t need = 0;
     if (pp_vsd_workspace_bytes(n.samples, n.total_faces, &need) != PP_OK) return PP_EINVAL;
     if (((uintptr_t)workspace % 256) != 0 || workspace_bytes < need) return PP_EWORKSPACE;
-    long long max_window = 0;
-    for (int v = 0; v < n_views; ++v) {
-        const long long m = scene->view_zoff_host[v + 1] - scene->view_zoff_host[v];
-        max_window = m > max_window ? m : max_window;
-    }
 
     hipStream_t st = (hipStream_t)stream;
     const RasterWs ws = carve(workspace, n);
@@ -133,12 +102,7 @@ int pp_pose_verify(const PpScene* scene, const unsigned* mask_bits, int n_masks,
     const int rc = raster_views(s, n, ws, near_count, st);
     if (rc != PP_OK) return rc;
     if (n.samples > 0) {
-        const unsigned gv = (unsigned)(n_views < 65535 ? n_views : 65535);                      // (the kernel's view stride)
-        long long chunks = (max_window + CHUNK_SAMPLES - 1) / CHUNK_SAMPLES;
-        const long long cap = 8192 / gv > 1 ? 8192 / gv : 1;                                    // bound the grid of a call with many views
-        chunks = chunks < 1 ? 1 : (chunks > MAX_CHUNKS ? MAX_CHUNKS : chunks);
-        chunks = chunks > cap ? cap : chunks;
-        hipLaunchKernelGGL(pose_verify_reduce_kernel, dim3((unsigned)chunks, gv), dim3(BLOCK), 0, st, s, ev, ws.zbuf, counts);
+        hipLaunchKernelGGL(pose_verify_reduce_kernel, window_grid(n_views, n.max_window), dim3(BLOCK), 0, st, s, ev, ws.zbuf, counts);
     }
     return pp_last_launch();
 }

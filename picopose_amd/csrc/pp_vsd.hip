@@ -17,37 +17,27 @@
 #include "pp_common.h"
 
 #pragma clang fp contract(off)
-#include "pp_vsd_raster_dev.h"
+#include "pp_window_dev.h"
 
 namespace {
 
-constexpr int BLOCK = 256;
-constexpr int WAVES = BLOCK / 64;
+constexpr int BLOCK = WINDOW_BLOCK;
+constexpr int WAVES = WINDOW_WAVES;
 constexpr int NC = 2 + PP_VSD_MAX_TAUS;   // counters of a pair: union, inter, n_1 .. n_16
 
 struct Taus {
     float v[PP_VSD_MAX_TAUS];
 };
 
-__device__ __forceinline__ float word_depth(unsigned long long key) {
-    return key == ~0ull ? 0.f : __uint_as_float((unsigned)(key >> 32));
-}
-
 // view blockIdx.y, ...: the covered samples of its window into the (zeroed) dense image
 __global__ __launch_bounds__(BLOCK) void vsd_depth_kernel(Scene s, const unsigned long long* __restrict__ zbuf,
                                                           float* __restrict__ depth_out) {
-    for (int v = blockIdx.y; v < s.n_views; v += gridDim.y) {
-        const int* w = s.windows + 4 * (size_t)v;
-        const int x0 = w[0], y0 = w[1], ww = w[2] - w[0], wh = w[3] - w[1];
-        if (ww <= 0 || wh <= 0) continue;
-        const unsigned long long* zv = zbuf + s.view_zoff[v];
+    for_each_window(s, zbuf, [&](int v, const Window& win) {
         float* out = depth_out + (size_t)v * s.H * s.W;
-        for (int i = blockIdx.x * BLOCK + threadIdx.x; i < ww * wh; i += gridDim.x * BLOCK) {
-            const int y = i / ww, x = i - y * ww;
-            const unsigned long long key = zv[i];
-            if (key != ~0ull) out[(size_t)(y0 + y) * s.W + (x0 + x)] = word_depth(key);
-        }
-    }
+        walk_window(win, [&](int x, int y, unsigned long long key) {
+            if (key != ~0ull) out[(size_t)y * s.W + x] = word_depth(key);
+        });
+    });
 }
 
 __global__ __launch_bounds__(BLOCK) void vsd_pair_kernel(Scene s, const unsigned long long* __restrict__ zbuf,
@@ -90,11 +80,10 @@ __global__ __launch_bounds__(BLOCK) void vsd_pair_kernel(Scene s, const unsigned
         if (!(z_est > 0.f) && !(z_gt > 0.f)) continue;           // neither model covers the sample: in no set
         const float z_test = dimg[(size_t)y * s.W + x];
         const bool missing = !(z_test > 0.f);
-        const float xr = ((float)x - cx) / fx, yr = ((float)y - cy) / fy;
-        const float r = sqrtf((xr * xr + yr * yr) + 1.f);
+        const float r = ray_scale(x, y, fx, fy, cx, cy);
         const float d_est = z_est * r, d_gt = z_gt * r, d_test = z_test * r;
-        const bool visib_gt = d_gt > 0.f && (missing || d_gt - d_test <= delta);
-        const bool visib_est = d_est > 0.f && (missing || d_est - d_test <= delta || visib_gt);
+        const bool visib_gt = visible(d_gt, d_test, missing, delta);
+        const bool visib_est = visible(d_est, d_test, missing, delta) || (d_est > 0.f && visib_gt);
         cnt[0] += (visib_gt || visib_est) ? 1 : 0;
         if (visib_gt && visib_est) {
             cnt[1] += 1;
@@ -104,19 +93,8 @@ __global__ __launch_bounds__(BLOCK) void vsd_pair_kernel(Scene s, const unsigned
         }
     }
     __shared__ int sm[WAVES][NC];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        int v = cnt[c];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-        if (lane == 0) sm[wave][c] = v;
-    }
-    __syncthreads();
+    const int v = block_reduce(cnt, sm, [](int, int a, int b) { return a + b; });
     if ((int)threadIdx.x < 2 + T) {
-        int v = sm[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < WAVES; ++w) v += sm[w][threadIdx.x];
         counts[(size_t)p * (2 + T) + threadIdx.x] = v;
         if (threadIdx.x >= 2) {
             int uni = 0, inter = 0;

@@ -74,15 +74,11 @@ __global__ __launch_bounds__(TILE * TILE) void vsd_raster_large_kernel(Scene s, 
     }
 }
 
-inline size_t align256(size_t n) { return (n + 255) / 256 * 256; }
-
-__host__ __device__ inline bool finite32(float v) { return fabsf(v) <= 3.402823466e38f; }
-inline bool positive_finite(float v) { return v > 0.f && finite32(v); }
-
 struct SceneSize {
     long long total_faces;     // over the views: the queue's capacity
     int max_faces;             // of one view
     long long samples;         // z-buffer words
+    long long max_window;      // samples of the largest window
 };
 
 // The one null check of the scene's tables.  device_diameters: whether the entry reads the device table `diameters`.
@@ -115,7 +111,7 @@ inline int check_scene(const PpScene* h, bool device_diameters, SceneSize& out) 
     }
     const long long* view_zoff = h->view_zoff_host;
     if (view_zoff[0] != 0) return PP_EINVAL;
-    out = SceneSize{0, 0, 0};
+    out = SceneSize{0, 0, 0, 0};
     for (int v = 0; v < h->n_views; ++v) {
         const int o = h->view_obj_host[v];
         if ((unsigned)o >= (unsigned)h->n_objects || (unsigned)h->view_img_host[v] >= (unsigned)h->n_images) return PP_EINVAL;
@@ -123,9 +119,11 @@ inline int check_scene(const PpScene* h, bool device_diameters, SceneSize& out) 
         if (nf <= 0) return PP_EINVAL;                            // an object of the call without faces
         const int* w = h->windows_host + 4 * (size_t)v;
         if (w[0] < 0 || w[1] < 0 || w[2] < w[0] || w[3] < w[1] || w[2] > h->W || w[3] > h->H) return PP_EINVAL;
-        if (view_zoff[v + 1] - view_zoff[v] != (long long)(w[2] - w[0]) * (w[3] - w[1])) return PP_EINVAL;
+        const long long window = (long long)(w[2] - w[0]) * (w[3] - w[1]);
+        if (view_zoff[v + 1] - view_zoff[v] != window) return PP_EINVAL;
         out.total_faces += nf;
         out.max_faces = nf > out.max_faces ? nf : out.max_faces;
+        out.max_window = window > out.max_window ? window : out.max_window;
     }
     if (out.total_faces > (long long)UINT_MAX) return PP_EINVAL;
     out.samples = view_zoff[h->n_views];

@@ -65,6 +65,30 @@ def test_mixed_call_equals_the_restatement_and_the_definitions():
 
 
 @gpu
+def test_adds_at_the_tile_edges_equals_the_restatement_and_the_definition():
+    """ADD-S vertex counts around the 256-point LDS tile and the 1024-point workgroup tile (one point, the last lane clamped, a full
+    tile, one point into the next tile), three pairs per count in ONE call, held to what the mixed call holds ADD-S to."""
+    counts = (1, 255, 256, 257, 1023, 1024, 1025, 2049)
+    rng = np.random.default_rng(11)
+    objects = {o: {"vertices": (rng.uniform(-1, 1, (n, 3)) * [120.0, 80.0, 60.0]).astype(np.float32), "info": {"diameter": 312.4}}
+               for o, n in enumerate(counts, start=1)}
+    _, pairs = po.mixed_inputs(seed=7, n_pairs=3 * len(counts))  # the poses only: near and far estimates alternate
+    ids = np.repeat(np.arange(1, len(counts) + 1), 3)
+    models = ev.ObjectModels(objects)
+    got = _host(ev.pose_errors(models, ids, pairs["R_est"], pairs["t_est"], pairs["R_gt"], pairs["t_gt"], kinds=("adds",)))
+    for i, o in enumerate(ids.tolist()):
+        sR, st, T = _syms(models, o)
+        V = objects[o]["vertices"]
+        a = [pairs[n][i] for n in ("R_est", "t_est", "R_gt", "t_gt")]
+        e32 = po.errors32(V, sR, st, *a, kinds=("adds",))
+        e64 = po.errors64(V, T, *[x.astype(np.float64) for x in a], kinds=("adds",))
+        b = po.metric_bound(po.max_norm(V, T), a[1], a[3])
+        print(len(V), i, "adds", got["adds"][i], "restatement", e32["adds"], "definition", e64["adds"], "bound", b)
+        assert abs(float(got["adds"][i]) - float(e32["adds"])) <= b, (len(V), i, got["adds"][i], e32["adds"], b)
+        assert abs(float(got["adds"][i]) - e64["adds"]) <= b, (len(V), i, got["adds"][i], e64["adds"], b)
+
+
+@gpu
 def test_a_pair_behind_the_camera_has_infinite_mspd():
     objects, pairs = po.mixed_inputs(seed=5, n_pairs=64)
     models = ev.ObjectModels(objects)
