@@ -98,6 +98,7 @@ __global__ __launch_bounds__(64 * WPB) void attn_kernel(const float* __restrict_
                 mx = fmaxf(mx, s[e]);
             }
         }
+        // (stays as written: lanes l and l + 32 hold the two halves of an MFMA fragment's column; the exchange is layout, not a reduction)
         mx = fmaxf(mx, __shfl_xor(mx, 32));
         const float mnew = fmaxf(mrun, mx);
         // the scores live in the base-2 domain (q was scaled by scale * log2 e): an exponential is ONE v_exp_f32 instead of libm's
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(64 * WPB) void attn_kernel(const float* __restrict_
             s[e] = __builtin_amdgcn_exp2f(s[e] - mnew);
             ls += s[e];
         }
-        ls += __shfl_xor(ls, 32);
+        ls += __shfl_xor(ls, 32);                            // (the same exchange)
         lrun = lrun * alpha + ls;
         mrun = mnew;
 #pragma unroll
@@ -138,7 +139,7 @@ __global__ __launch_bounds__(64 * WPB) void attn_kernel(const float* __restrict_
             sp = fmaf(kf.z, qr[p + 2], sp);
             sp = fmaf(kf.w, qr[p + 3], sp);
         }
-        const float sc = sp + __shfl_xor(sp, 32);            // the score of (key kx, query l31), the same in both lane halves
+        const float sc = sp + __shfl_xor(sp, 32);            // (stays as written, a layout exchange) the score of (key kx, query l31), the same in both lane halves
         const float mnew = fmaxf(mrun, sc);
         const float alpha = __builtin_amdgcn_exp2f(mrun - mnew);
         const float pk = __builtin_amdgcn_exp2f(sc - mnew);
@@ -303,6 +304,7 @@ __global__ __launch_bounds__(WPB > 4 ? 64 * WPB : 256) __attribute__((amdgpu_wav
     //     in those units (the final division and the log-sum-exp take the 2^10 out) — no multiply per probability;
     //   * the accumulators are rescaled only when some query's maximum moved in this chunk (wave-uniform test): after the first
     //     chunks it rarely does.
+    //   (the two __shfl_xor(x, 32) of the step stay as written: the same exchange of a fragment's lane halves as in the kernel above)
 #define SOFTMAX_STEP(K0)                                                                                          \
     float mx = -INFINITY;                                                                                         \
     if ((K0) + KC > Tm) { /* (uniform) the last, partial chunk: keys past the chunked range are masked */       \
@@ -634,7 +636,7 @@ __global__ __launch_bounds__(WPB > 4 ? 64 * WPB : 256) __attribute__((amdgpu_wav
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
                     dot = fmaf((float)qh[s4][i] + (float)ql[s4][i], tk[r * HD + 16 * s4 + 8 * lh + i], dot);
-            dot += __shfl_xor(dot, 32);
+            dot += __shfl_xor(dot, 32);                      // (stays as written: the two lane halves hold the halves of the head dimension)
             const float sv = dot * S_DESCALE;
             const float mnew = fmaxf(mrun, sv);
             const float alpha = __builtin_amdgcn_exp2f(mrun - mnew), pw = __builtin_amdgcn_exp2f(sv - mnew + 10.0f);   // 1024 p: the MFMA path's units

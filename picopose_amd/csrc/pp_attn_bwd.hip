@@ -17,6 +17,7 @@
 #include <stdint.h>
 #include "../../include/picopose_hip.h"
 #include "pp_common.h"
+#include "pp_reduce_dev.h"
 
 namespace {
 
@@ -139,7 +140,7 @@ __device__ __forceinline__ float split_ranged(const f32x16& x, h8 (&xh)[2], h8 (
     float mx = 0.f;
 #pragma unroll
     for (int e = 0; e < 16; ++e) mx = fmaxf(mx, fabsf(x[e]));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));                 // (stays as written: the two lane halves of an MFMA fragment exchange, a layout step)
     uint32_t e8 = __float_as_uint(mx) >> 23;            // biased exponent (mx >= 0); NaN / inf columns saturate below
     e8 = e8 < 40u ? 40u : (e8 > 250u ? 250u : e8);
     const float sc = __uint_as_float((263u - e8) << 23);     // 2^(9 - (e8 - 127)): the column's maximum lands in [512, 1024)
@@ -190,10 +191,7 @@ __global__ __launch_bounds__(256) void attn_bwd_d_kernel(const float* __restrict
         const f4 a = *(const f4*)(out + item * HD + 4 * sub), c = *(const f4*)(dout + item * HD + 4 * sub);
         acc = a.x * c.x + a.y * c.y + a.z * c.z + a.w * c.w;
     }
-    acc += __shfl_xor(acc, 8);
-    acc += __shfl_xor(acc, 4);
-    acc += __shfl_xor(acc, 2);
-    acc += __shfl_xor(acc, 1);
+    acc = wave_reduce_range<8, 1>(acc, op_sum{});                    // the 16 lanes of the item
     if (item < items && sub == 0) {
         const long row = item / heads;
         const int h = (int)(item - row * heads);

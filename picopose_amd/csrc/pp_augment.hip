@@ -7,6 +7,7 @@
 // only execute them.  Every op is integer, LUT-free fixed point or float32 with contraction off, so
 // tests/train_batch_oracle.py restates each one bit for bit.
 #include "pp_common.h"
+#include "pp_reduce_dev.h"
 #include "pp_hash_dev.h"             // aug_mix, aug_hash: the counter-based hash, shared with pp_synth.hip
 
 #pragma clang fp contract(off)
@@ -177,8 +178,7 @@ __global__ __launch_bounds__(256) void aug_pass_kernel(const unsigned char* __re
         lval = pil_l(v[0], v[1], v[2]);
     }
     if (sums) {  // uniform per block: integer sum, so exact and independent of the order of the adds
-        unsigned s = (unsigned)lval;
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        const unsigned s = wave_sum((unsigned)lval);
         if ((threadIdx.x & 63) == 0 && s) atomicAdd(lsum + t.x, s);
     }
 }

@@ -11,17 +11,12 @@
 #include <stdint.h>
 #include "../../include/picopose_hip.h"
 #include "pp_common.h"
+#include "pp_reduce_dev.h"
 
 namespace {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // out[c] = sum_r x[r][c] (x rows of ld floats), rows cut into gridDim.y slabs summed in slab order: part[slab][c]
 __global__ __launch_bounds__(256) void colsum_part_kernel(const float* __restrict__ x, long long rows, int cols, int ld, float* __restrict__ part) {
@@ -176,16 +171,10 @@ __global__ __launch_bounds__(256) void groupnorm_backward_kernel(const float* __
     const size_t base = (size_t)img * HW * C + grp * cg;
     const int n = HW * cg;
     auto block_sum2 = [&](float u, float w, float& su, float& sw) {
-        u = wave_sum(u);
-        w = wave_sum(w);
-        __syncthreads();
-        if ((tid & 63) == 0) {
-            red[tid >> 6] = u;
-            red[4 + (tid >> 6)] = w;
-        }
-        __syncthreads();
-        su = red[0] + red[1] + red[2] + red[3];
-        sw = red[4] + red[5] + red[6] + red[7];
+        float uw[2] = {u, w};
+        __syncthreads();   // (the previous use of `red` has been read by everyone)
+        block_reduce_all<4>(uw, red, op_sum{});
+        su = uw[0], sw = uw[1];
     };
     float s = 0.f, dummy;
     for (int i = tid; i < n; i += 256) s += x[base + (size_t)(i / cg) * C + (i % cg)];
@@ -249,8 +238,7 @@ __global__ __launch_bounds__(256) void xent_diag_backward_kernel(const float* __
     const float* lr = logits + (size_t)row * ld;
     float mx = -INFINITY;
     for (int c = lane; c < n; c += 64) mx = fmaxf(mx, lr[c] * scale);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    mx = wave_max(mx);
     float s = 0.f;
     for (int c = lane; c < n; c += 64) s += expf(lr[c] * scale - mx);
     s = wave_sum(s);

@@ -8,6 +8,7 @@
 #include <stdint.h>
 #include "../../include/picopose_hip.h"
 #include "pp_common.h"
+#include "pp_reduce_dev.h"
 #include "pp_corr_dev.h"
 
 namespace {
@@ -241,12 +242,6 @@ __global__ __launch_bounds__(256) void avgpool2_backward_kernel(const float* __r
         if ((y >> 1) < Ho && (x >> 1) < Wo) v = 0.25f * dy[((b * Ho + (y >> 1)) * Wo + (x >> 1)) * C + c];
         dx[i] = accumulate ? dx[i] + v : v;
     }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // Scatter accumulation of the two sampling adjoints.  FIXED = false: fp32 atomicAdd — fast, but the sum depends on the order the

@@ -7,7 +7,7 @@
 //                          pixels each), every lane keeps four back-projected pixels in registers, and per hypothesis a wave counts its
 //                          inliers by ballot + popcount into an LDS counter; then one integer atomicAdd per hypothesis and workgroup
 //   plane_moments_kernel   the same strips: every workgroup finds the winner from the counts (arg-max, lowest h), and sums the ten
-//                          float64 moments of its strip's consensus pixels about the winner's first sample point (block_sum's fixed order)
+//                          float64 moments of its strip's consensus pixels about the winner's first sample point (block_reduce_all's fixed order)
 //   plane_finish_kernel    one wave per image adds the strips' partial sums in a fixed order, takes the smallest eigenvector with
 //                          jacobi_sym<3> and writes the plane and the info row
 //   cc_tile_kernel         one workgroup per 32 x 128 tile: foreground test, labels and depth staged in LDS; every pixel starts at the
@@ -135,41 +135,17 @@ __global__ __launch_bounds__(BLOCK) void plane_score_kernel(const float* __restr
         if (cnt[h]) atomicAdd(counts + (size_t)b * n_hyp + h, cnt[h]);
 }
 
-// arg-max of cnt[0..n_hyp), the lowest index among equals, in every thread of the NWV-wave workgroup; sm: 2 NWV ints of LDS
-template <int NWV>
-__device__ __forceinline__ void block_winner(const int* cnt, int n_hyp, int* sm, int& best_h, int& best_c) {
-    int bc = -1, bh = INT_MAX;
-    for (int h = threadIdx.x; h < n_hyp; h += NWV * 64)
-        if (cnt[h] > bc) { bc = cnt[h]; bh = h; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int oc = __shfl_xor(bc, o), oh = __shfl_xor(bh, o);
-        if (oc > bc || (oc == bc && oh < bh)) { bc = oc; bh = oh; }
-    }
-    if constexpr (NWV > 1) {
-        if ((threadIdx.x & 63) == 0) { sm[2 * (threadIdx.x >> 6)] = bc; sm[2 * (threadIdx.x >> 6) + 1] = bh; }
-        __syncthreads();
-        bc = sm[0], bh = sm[1];
-#pragma unroll
-        for (int w = 1; w < NWV; ++w) {
-            const int oc = sm[2 * w], oh = sm[2 * w + 1];
-            if (oc > bc || (oc == bc && oh < bh)) { bc = oc; bh = oh; }
-        }
-    }
-    best_h = bh, best_c = bc;
-}
-
 __global__ __launch_bounds__(BLOCK) void plane_moments_kernel(const float* __restrict__ depth, const float* __restrict__ cams, int H, int W,
                                                               int n_hyp, unsigned seed, float tau, int min_inliers,
                                                               const int* __restrict__ counts, double* __restrict__ partial) {
-    __shared__ int sm[2 * WAVES];
+    __shared__ Winner sm[WAVES];
     __shared__ double red[WAVES * NM];
     const int b = blockIdx.y;
     const unsigned hw = (unsigned)H * (unsigned)W;
     const float* img = depth + (size_t)b * hw;
     double* out = partial + ((size_t)b * gridDim.x + blockIdx.x) * NM;
-    int wh, wc;
-    block_winner<WAVES>(counts + (size_t)b * n_hyp, n_hyp, sm, wh, wc);
+    const Winner win = winner<WAVES>(counts + (size_t)b * n_hyp, n_hyp, sm, INT_MAX);
+    const int wh = win.h, wc = win.c;
     if (wc < min_inliers) {                                          // (uniform: no plane)
         if (threadIdx.x < NM) out[threadIdx.x] = 0.0;
         return;
@@ -190,7 +166,8 @@ __global__ __launch_bounds__(BLOCK) void plane_moments_kernel(const float* __res
             v[9] += 1.0;
         }
     }
-    block_sum<WAVES, NM>(v, red);
+    __syncthreads();   // (kept: the sum has always had a barrier before its LDS write as well as after it)
+    block_reduce_all<WAVES>(v, red, op_sum{}, 0.0);
     if (threadIdx.x < NM) {
 #pragma unroll
         for (int c = 0; c < NM; ++c)
@@ -204,8 +181,8 @@ __global__ __launch_bounds__(64) void plane_finish_kernel(const float* __restric
                                                           float* __restrict__ plane, double* __restrict__ plane64, int* __restrict__ info) {
     const int b = blockIdx.x;
     const unsigned hw = (unsigned)H * (unsigned)W;
-    int wh, wc;
-    block_winner<1>(counts + (size_t)b * n_hyp, n_hyp, nullptr, wh, wc);
+    const Winner win = winner<1>(counts + (size_t)b * n_hyp, n_hyp, nullptr, INT_MAX);
+    const int wh = win.h, wc = win.c;
     double v[NM];
 #pragma unroll
     for (int c = 0; c < NM; ++c) v[c] = 0.0;
@@ -215,9 +192,7 @@ __global__ __launch_bounds__(64) void plane_finish_kernel(const float* __restric
         for (int c = 0; c < NM; ++c) v[c] += p[c];
     }
 #pragma unroll
-    for (int c = 0; c < NM; ++c)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[c] += __shfl_xor(v[c], o);
+    for (int c = 0; c < NM; ++c) v[c] = wave_sum(v[c]);
     if (threadIdx.x != 0) return;
     double n0 = 0.0, n1 = 0.0, n2 = 0.0, d = 0.0;
     const bool has = wc >= min_inliers;
@@ -417,12 +392,9 @@ __global__ __launch_bounds__(BLOCK) void stats_accumulate_kernel(const int* __re
             const bool mine = root == r;
             const int area = __popcll(__ballot(mine));
             const int bord = __ballot(mine && border) != 0ull;
-            int xmin = mine ? x : INT_MAX, xmax = mine ? x : -1, ymax = mine ? y : -1;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                xmin = min(xmin, __shfl_xor(xmin, o)), xmax = max(xmax, __shfl_xor(xmax, o)), ymax = max(ymax, __shfl_xor(ymax, o));
-            }
-            if (lane == leader) rec_add(rc + (size_t)r * REC, area, xmin, xmax, ymax, bord);
+            int box[3] = {mine ? x : INT_MAX, mine ? x : -1, mine ? y : -1};                // xmin, xmax, ymax
+            wave_reduce_each(box, [](int c, int p, int q) { return c == 0 ? min(p, q) : max(p, q); });
+            if (lane == leader) rec_add(rc + (size_t)r * REC, area, box[0], box[1], box[2], bord);
             if (mine) root = -1;
         }
         if (root >= 0) rec_add(rc + (size_t)root * REC, 1, x, x, y, border ? 1 : 0);

@@ -186,21 +186,8 @@ __global__ __launch_bounds__(BLOCK) void refine_accumulate_kernel(Scene s, const
         acc[28] += 1.0;
     }
     __shared__ double sm[WAVES][NS];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < NS; ++c) {
-        double val = acc[c];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) val += __shfl_xor(val, d, 64);
-        if (lane == 0) sm[wave][c] = val;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < NS) {
-        double val = sm[0][threadIdx.x];
-#pragma unroll
-        for (int wv = 1; wv < WAVES; ++wv) val += sm[wv][threadIdx.x];
-        partial[(size_t)strip * NS + threadIdx.x] = val;
-    }
+    const double val = block_reduce_to<WAVES>(acc, sm, op_sum{});
+    if ((int)threadIdx.x < NS) partial[(size_t)strip * NS + threadIdx.x] = val;
 }
 
 struct SolveArgs {

@@ -6,6 +6,7 @@
 #include <limits.h>
 #include <math.h>
 #include "pp_common.h"
+#include "pp_reduce_dev.h"
 
 namespace {
 
@@ -75,8 +76,7 @@ __global__ __launch_bounds__(PAIR * PAIR * PAIR_Q) void det_overlaps_segm_kernel
         for (int k = 0; k < PAIR_KW; k += PAIR_Q) count += __popc(a[ti * PAIR_LD + k + kq] & b[tj * PAIR_LD + k + kq]);
         __syncthreads();
     }
-    count += __shfl_xor(count, 1, WAVE);
-    count += __shfl_xor(count, 2, WAVE);
+    count = wave_reduce_range<PAIR_Q / 2, 1>(count, op_sum{});                // the PAIR_Q threads of a pair (integers: any order)
     if (kq == 0 && i0 + ti < G.nd && j0 + tj < G.ng) {
         const int d = G.d0 + i0 + ti, g = G.g0 + j0 + tj;
         const size_t at = (size_t)G.off + (size_t)(i0 + ti) * G.ng + j0 + tj;
@@ -106,24 +106,6 @@ __global__ __launch_bounds__(PAIR * PAIR) void det_overlaps_bbox_kernel(const do
     const double num = iw * ih, ad = wd * hd;
     const double den = (gt_flags[G.g0 + j] & PP_DET_GT_CROWD) ? ad : (ad + wg * hg) - num;
     iou[(size_t)G.off + (size_t)i * G.ng + j] = den > 0.0 ? num / den : 0.0;
-}
-
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const unsigned long long o = __shfl_xor(v, m, WAVE);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const int o = __shfl_xor(v, m, WAVE);
-        v = o > v ? o : v;
-    }
-    return v;
 }
 
 // One wave per (group, area range, threshold); the waves of a workgroup share nothing.  Lane l owns the ground truths j = l + 64 k of

@@ -19,6 +19,7 @@
 
 #pragma clang fp contract(off)
 #include "pp_pointset_dev.h"
+#include "pp_reduce_dev.h"
 
 namespace {
 
@@ -111,33 +112,8 @@ __global__ __launch_bounds__(BLOCK) void sym_max_kernel(const float* __restrict_
         }
     }
     __shared__ float sm[WAVES][TS];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < TS; ++j) {
-        float v = m[j];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-        if (lane == 0) sm[wave][j] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < TS && s_base + (int)threadIdx.x < ns) {
-        float v = sm[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < WAVES; ++w) v = fmaxf(v, sm[w][threadIdx.x]);
-        err[(size_t)p * S_max + s_base + threadIdx.x] = sqrtf(v);
-    }
-}
-
-// float64 sum over the workgroup in a fixed tree: xor-shuffles 32 .. 1 inside a wave, then the waves in order
-__device__ __forceinline__ double block_sum(double v, double* sm) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = v + __shfl_xor(v, d, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = sm[0];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) s = s + sm[w];
-    return s;
+    const float v = block_reduce_to<WAVES>(m, sm, op_max{});
+    if (threadIdx.x < TS && s_base + (int)threadIdx.x < ns) err[(size_t)p * S_max + s_base + threadIdx.x] = sqrtf(v);
 }
 
 __global__ __launch_bounds__(BLOCK) void add_kernel(const float* __restrict__ verts, const int* __restrict__ vert_off,
@@ -169,7 +145,7 @@ __global__ __launch_bounds__(BLOCK) void add_kernel(const float* __restrict__ ve
         acc = acc + (double)sqrtf((dx * dx + dy * dy) + dz * dz);
     }
     __shared__ double sm[WAVES];
-    const double s = block_sum(acc, sm);
+    const double s = block_reduce_all<WAVES>(acc, sm, op_sum{});   // (float64, in the fixed tree of pp_reduce_dev.h)
     if (threadIdx.x == 0) out[p] = (float)(s / (double)nv);
 }
 
@@ -203,33 +179,29 @@ __global__ __launch_bounds__(BLOCK) void adds_kernel(const float* __restrict__ v
     for (int k = 0; k < ADDS_EPT; ++k)
         if (e.valid[k]) acc = acc + (double)sqrtf(mn.d2[k]);
     __shared__ double sm[WAVES];
-    const double s = block_sum(acc, sm);
+    const double s = block_reduce_all<WAVES>(acc, sm, op_sum{});   // (float64, in the fixed tree of pp_reduce_dev.h)
     if (threadIdx.x == 0) part[(size_t)p * tiles_max + tile] = s;
 }
 
-__device__ __forceinline__ void wave_argmin(const float* __restrict__ e, int ns, int lane, float* out, int* out_idx) {
-    float best = INFINITY;
-    int idx = INT_MAX;
+// the least of e[0..ns) with NaN read as +inf, the lowest index among equals; one wave, lane 0 writes
+struct ErrAt {
+    float v;
+    int i;
+};
+__device__ __forceinline__ void least_error(const float* __restrict__ e, int ns, int lane, float* out, int* out_idx) {
+    const auto lower = [](ErrAt a, const ErrAt& b) {
+        if (b.v < a.v || (b.v == a.v && b.i < a.i)) a = b;
+        return a;
+    };
+    ErrAt best{INFINITY, INT_MAX};
     for (int s = lane; s < ns; s += 64) {
-        float v = e[s];
-        v = v == v ? v : INFINITY;
-        if (v < best || (v == best && s < idx)) {
-            best = v;
-            idx = s;
-        }
+        const float v = e[s];
+        best = lower(best, ErrAt{v == v ? v : INFINITY, s});
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const float ov = __shfl_xor(best, d, 64);
-        const int oi = __shfl_xor(idx, d, 64);
-        if (ov < best || (ov == best && oi < idx)) {
-            best = ov;
-            idx = oi;
-        }
-    }
+    best = wave_reduce(best, lower);
     if (lane == 0) {
-        *out = best;
-        *out_idx = idx;
+        *out = best.v;
+        *out_idx = best.i;
     }
 }
 
@@ -243,8 +215,8 @@ __global__ __launch_bounds__(BLOCK) void finalize_kernel(const int* __restrict__
     if (p >= P) return;
     const int o = pair_obj[p];
     const int ns = sym_off[o + 1] - sym_off[o];
-    if (err_mssd) wave_argmin(err_mssd + (size_t)p * S_max, ns, lane, mssd + p, mssd_sym + p);
-    if (err_mspd) wave_argmin(err_mspd + (size_t)p * S_max, ns, lane, mspd + p, mspd_sym + p);
+    if (err_mssd) least_error(err_mssd + (size_t)p * S_max, ns, lane, mssd + p, mssd_sym + p);
+    if (err_mspd) least_error(err_mspd + (size_t)p * S_max, ns, lane, mspd + p, mspd_sym + p);
     if (part && lane == 0) {
         const int nv = adds_off[o + 1] - adds_off[o];
         const int nt = (nv + PP_EVAL_ADDS_TILE - 1) / PP_EVAL_ADDS_TILE;

@@ -29,6 +29,7 @@
 #include <unordered_map>
 #include "../../include/picopose_hip.h"
 #include "pp_common.h"
+#include "pp_reduce_dev.h"
 #include "pp_gemm_dev.h"
 #include "pp_gemm_u.h"
 
@@ -617,8 +618,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 #pragma unroll
             for (int k = 0; k < 4; ++k) s += v[j][0][k] + v[j][1][k];
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        s = wave_sum(s);
         const float mean = s / (float)C;
         float q = 0.f;
 #pragma unroll
@@ -633,8 +633,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
                     }
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+        q = wave_sum(q);
         const float rstd = 1.0f / sqrtf(q / (float)C + eps);
 #pragma unroll
         for (int j = 0; j < NG; ++j) {
@@ -668,16 +667,14 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     } else {
         float s = 0.f;
         for (int c = lane; c < C; c += 64) s += xr[c];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        s = wave_sum(s);
         const float mean = s / (float)C;
         float v = 0.f;
         for (int c = lane; c < C; c += 64) {
             const float dlt = xr[c] - mean;
             v = fmaf(dlt, dlt, v);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        v = wave_sum(v);
         const float rstd = 1.0f / sqrtf(v / (float)C + eps);
         for (int c = lane; c < C; c += 64) {
             const float o = (xr[c] - mean) * rstd * g[c] + b[c];
@@ -717,16 +714,14 @@ __global__ __launch_bounds__(256) void softmax_kernel(float* __restrict__ x, int
     float* xr = x + (size_t)row * ld;
     float mx = -INFINITY;
     for (int c = lane; c < n; c += 64) mx = fmaxf(mx, xr[c]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    mx = wave_max(mx);
     float s = 0.f;
     for (int c = lane; c < n; c += 64) {
         const float e = expf(xr[c] - mx);
         xr[c] = e;
         s += e;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    s = wave_sum(s);
     const float inv = 1.0f / s;
     for (int c = lane; c < n; c += 64) xr[c] *= inv;
 }
@@ -742,21 +737,13 @@ __global__ __launch_bounds__(256) void groupnorm_kernel(const float* __restrict_
     const int n = HW * cg;
     float s = 0.f;
     for (int i = tid; i < n; i += 256) s += xi[(size_t)(i / cg) * C + (i % cg)];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((tid & 63) == 0) red[tid >> 6] = s;
-    __syncthreads();
-    const float mean = (red[0] + red[1] + red[2] + red[3]) / (float)n;
+    const float mean = block_reduce_all<4>(s, red, op_sum{}) / (float)n;
     float v = 0.f;
     for (int i = tid; i < n; i += 256) {
         const float dlt = xi[(size_t)(i / cg) * C + (i % cg)] - mean;
         v = fmaf(dlt, dlt, v);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((tid & 63) == 0) red[4 + (tid >> 6)] = v;
-    __syncthreads();
-    const float rstd = 1.0f / sqrtf((red[4] + red[5] + red[6] + red[7]) / (float)n + eps);
+    const float rstd = 1.0f / sqrtf(block_reduce_all<4>(v, red + 4, op_sum{}) / (float)n + eps);
     for (int i = tid; i < n; i += 256) {
         const int c = i % cg;
         const size_t off = (size_t)(i / cg) * C + c;
@@ -811,6 +798,8 @@ __global__ void normalize_rows_kernel(const float* __restrict__ x, int rows, int
     for (int i = 0; i < n; ++i) y[(size_t)r * n + i] = x[(size_t)r * n + i] / d;
 }
 
+// (The maxima below begin at 0.f and meet absolute values through fmaxf, which drops a NaN: no operand is NaN or -0, so fmaxf is
+// exact on them and their order does not show in the bits.)
 // max |w| -> power-of-two scale with max |s w| in [512, 1024): init / grid-wide max (the bit pattern of a non-negative float
 // orders like an unsigned integer: one atomicMax per workgroup) / finish, three small launches without a workspace
 __global__ void absmax_init_kernel(float* __restrict__ scale) { ((unsigned*)scale)[0] = 0u; }
@@ -819,12 +808,8 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ w
     __shared__ float red[4];
     float m = 0.f;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) m = fmaxf(m, fabsf(w[i]));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
+    m = block_reduce_to<4>(m, red, op_max{});
     if (threadIdx.x == 0) {
-        m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
         if (m == m) atomicMax((unsigned*)scale, __float_as_uint(m));   // (a NaN never enters the maximum)
     }
 }
@@ -851,23 +836,16 @@ __global__ __launch_bounds__(256) void absmax_part_kernel(const float* __restric
         m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
     }
     for (long long i = 4 * n4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) m = fmaxf(m, fabsf(w[i]));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));   // (fmaxf drops a NaN operand)
+    m = block_reduce_to<4>(m, red, op_max{});
+    if (threadIdx.x == 0) partial[blockIdx.x] = m;   // (fmaxf drops a NaN operand)
 }
 
 __global__ __launch_bounds__(256) void absmax_fold_kernel(const float* __restrict__ partial, int np, float* __restrict__ scale, int with_inverse, int emax) {
     __shared__ float red[4];
     float m = 0.f;
     for (int i = threadIdx.x; i < np; i += 256) m = fmaxf(m, partial[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
+    m = block_reduce_to<4>(m, red, op_max{});
     if (threadIdx.x == 0) {
-        m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
         int e = 0;
         if (m > 0.f && m < INFINITY) {
             (void)frexpf(m, &e);
@@ -915,12 +893,8 @@ __global__ __launch_bounds__(256) void split_fold_kernel(const float* __restrict
     __shared__ float s_sh;
     float m = 0.f;
     for (int i = threadIdx.x; i < np; i += 256) m = fmaxf(m, partial[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
+    m = block_reduce_to<4>(m, red, op_max{});
     if (threadIdx.x == 0) {
-        m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
         int e = 0;
         if (m > 0.f && m < INFINITY) {
             (void)frexpf(m, &e);

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void simvol_kernel(const float* __restrict__ s
         }
         __syncthreads();
     }
-    // norms: lanes l and l+32 hold the even / odd channel halves
+    // norms: lanes l and l+32 hold the even / odd channel halves (stays as written: a fragment's layout, not a reduction)
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         sa[i] += __shfl_xor(sa[i], 32);

@@ -21,6 +21,7 @@
 
 #pragma clang fp contract(off)
 #include "pp_pointset_dev.h"
+#include "pp_reduce_dev.h"
 
 namespace {
 
@@ -51,37 +52,15 @@ __device__ __forceinline__ bool beats(float ad, int ai, int aj, float bd, int bi
     return ad > bd || (ad == bd && (ai < bi || (ai == bi && aj < bj)));
 }
 
-// the workgroup's best (d2, i, j) in thread 0; sm: 3 * WAVES words
-__device__ __forceinline__ void block_best(float& d, int& i, int& j, int* sm) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        const float od = __shfl_xor(d, s, 64);
-        const int oi = __shfl_xor(i, s, 64), oj = __shfl_xor(j, s, 64);
-        if (beats(od, oi, oj, d, i, j)) {
-            d = od;
-            i = oi;
-            j = oj;
-        }
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        sm[3 * wave] = __float_as_int(d);
-        sm[3 * wave + 1] = i;
-        sm[3 * wave + 2] = j;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < WAVES; ++w) {
-            const float od = __int_as_float(sm[3 * w]);
-            const int oi = sm[3 * w + 1], oj = sm[3 * w + 2];
-            if (beats(od, oi, oj, d, i, j)) {
-                d = od;
-                i = oi;
-                j = oj;
-            }
-        }
-    }
+// the better of two (d2, i, j) records under beats, which orders distinct records totally: the workgroup's best does not depend on
+// the order in which block_reduce_to meets them
+struct Far {
+    float d;
+    int i, j;
+};
+__device__ __forceinline__ Far farther(Far a, const Far& b) {
+    if (beats(b.d, b.i, b.j, a.d, a.i, a.j)) a = b;
+    return a;
 }
 
 // part[w] = {bits of d2, i, j, 0}; d2 = -1: the work item holds no pair
@@ -145,9 +124,9 @@ __global__ __launch_bounds__(BLOCK) void diameter_kernel(const float* __restrict
             bjj = bj[k];
         }
     }
-    __shared__ int sm[3 * WAVES];
-    block_best(d, bi, bjj, sm);
-    if (threadIdx.x == 0) part[w] = make_int4(__float_as_int(d), bi, bjj, 0);
+    __shared__ Far sm[WAVES];
+    const Far best = block_reduce_to<WAVES>(Far{d, bi, bjj}, sm, farther);
+    if (threadIdx.x == 0) part[w] = make_int4(__float_as_int(best.d), best.i, best.j, 0);
 }
 
 __global__ __launch_bounds__(BLOCK) void diameter_finalize_kernel(const int* __restrict__ work_off, const int4* __restrict__ part,
@@ -165,13 +144,13 @@ __global__ __launch_bounds__(BLOCK) void diameter_finalize_kernel(const int* __r
             bj = p.z;
         }
     }
-    __shared__ int sm[3 * WAVES];
-    block_best(d, bi, bj, sm);
+    __shared__ Far sm[WAVES];
+    const Far best = block_reduce_to<WAVES>(Far{d, bi, bj}, sm, farther);
     if (threadIdx.x == 0) {
-        const bool any = d >= 0.f;                               // an object with one vertex has no pair: 0 and (0, 0)
-        d2max[o] = any ? d : 0.f;
-        pair[2 * (size_t)o] = any ? bi : 0;
-        pair[2 * (size_t)o + 1] = any ? bj : 0;
+        const bool any = best.d >= 0.f;                          // an object with one vertex has no pair: 0 and (0, 0)
+        d2max[o] = any ? best.d : 0.f;
+        pair[2 * (size_t)o] = any ? best.i : 0;
+        pair[2 * (size_t)o + 1] = any ? best.j : 0;
     }
 }
 
@@ -198,16 +177,9 @@ __global__ __launch_bounds__(BLOCK) void hausdorff_kernel(const float* __restric
 #pragma unroll
     for (int k = 0; k < MI_EPT; ++k)
         if (e.valid[k]) m = fmaxf(m, mn.d2[k]);
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) m = fmaxf(m, __shfl_xor(m, s, 64));
     __shared__ float sm[WAVES];
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < WAVES; ++w) m = fmaxf(m, sm[w]);
-        part[(size_t)c * tiles_max + tile] = m;
-    }
+    m = block_reduce_to<WAVES>(m, sm, op_max{});
+    if (threadIdx.x == 0) part[(size_t)c * tiles_max + tile] = m;
 }
 
 __global__ __launch_bounds__(BLOCK) void hausdorff_finalize_kernel(const int* __restrict__ q_off, const int* __restrict__ cand_obj,

@@ -13,6 +13,7 @@
 #include <vector>
 #include "../../include/picopose_hip.h"
 #include "pp_common.h"
+#include "pp_reduce_dev.h"
 
 namespace {
 
@@ -57,9 +58,11 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v,
     p = __builtin_fmaf(s.neg_step_size, m / den, p);                    // param.addcdiv_(exp_avg, denom, value=-step_size)
 }
 
-__device__ __forceinline__ float block_max(float m, float* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+// the workgroup's maximum in every thread.  The wave part is pp_reduce_dev.h's walk; the fold over the four waves stays the tree it
+// was, not block_reduce_all's ascending fold: the bits would be the same (the operands began at 0.f and met |p| through fmaxf: no
+// NaN, no -0), but adam_split_kernel measured above the parent's spread with the ascending fold (profiles/r21/reductions.md)
+__device__ __forceinline__ float tree_max4(float m, float* red) {
+    PP_WAVE_WALK(o, 32, 1) m = fmaxf(m, lane_xor(m, o));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
@@ -109,7 +112,7 @@ __global__ __launch_bounds__(256) void adam_update_kernel(const AdamDev* __restr
         V[i] = v;
     }
     if (d.hl != nullptr) {                                  // (uniform per workgroup)
-        mx = block_max(mx, red);
+        mx = tree_max4(mx, red);
         if (threadIdx.x == 0) partials[d.part0 + it.y] = mx;   // (fmaxf drops a NaN operand, like absmax_part_kernel)
     }
 }
@@ -121,7 +124,7 @@ __global__ __launch_bounds__(256) void adam_split_kernel(const AdamDev* __restri
     const AdamDev d = table[it.x];
     float m = 0.f;
     for (int i = threadIdx.x; i < d.nchunk; i += 256) m = fmaxf(m, partials[d.part0 + i]);
-    m = block_max(m, red);
+    m = tree_max4(m, red);
     int e = 0;                                              // the exponent rule of split_fold_kernel: s max|w| in [512, 1024)
     if (m > 0.f && m < INFINITY) {
         (void)frexpf(m, &e);

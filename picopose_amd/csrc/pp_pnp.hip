@@ -13,8 +13,9 @@
 // "unpinned"  and is defined by known-answer tests instead.  fp64 throughout.
 //
 // The rules this solver shares with the RGB-D solver (pp_rgbd_pose.hip) are stated once, in pp_ransac_dev.h: the workgroup
-// shape and the capacities (NT, NW, MAXP, MAXH), the cyclic Jacobi (jacobi_sym), the fixed-order block sum, the sampling
-// sequence (ransac_sample), the winner's tie rule (ransac_winner), the failure outputs and the object-frame source point.
+// shape and the capacities (NT, NW, MAXP, MAXH), the cyclic Jacobi (jacobi_sym), the sampling sequence (ransac_sample), the
+// failure outputs and the object-frame source point; the fixed-order block sum and the winner's tie rule are pp_reduce_dev.h's
+// (block_reduce_all from 0.0 - spelled out in set_sum below, which says why - and winner).
 // What stays here is the PnP's own: EPnP with its 12x12 one-sided Jacobi, the scoring pass, the refit and the LM tail.
 
 #include <hip/hip_runtime.h>
@@ -171,8 +172,7 @@ __device__ inline void hestenes12(double (&g)[12], double (&v)[12], int k) {
         double amax2 = 0.0;
 #pragma unroll
         for (int i = 0; i < 12; ++i) amax2 += g[i] * g[i];
-#pragma unroll
-        for (int o = 1; o < GL; o <<= 1) amax2 = fmax(amax2, __shfl_xor(amax2, o, GL));
+        amax2 = wave_reduce_range<GL / 2, 1, GL>(amax2, op_max{});
         const double floor2 = 2.5e-29 * amax2;                  // (16 eps)^2 * 2 * lambda_max^2
         int rotated = 0;
         double alpha = 0.0;                                     // |g_k|^2, recomputed once per sweep, then updated
@@ -209,8 +209,7 @@ __device__ inline void hestenes12(double (&g)[12], double (&v)[12], int k) {
                 alpha = low ? c * c * ap - 2.0 * c * sn * gamma + sn * sn * aq : sn * sn * ap + 2.0 * c * sn * gamma + c * c * aq;
             }
         }
-#pragma unroll
-        for (int o = 1; o < GL; o <<= 1) rotated |= __shfl_xor(rotated, o, GL);
+        rotated = wave_reduce_range<GL / 2, 1, GL>(rotated, [](int a, int b) { return a | b; });
         if (!rotated) break;
     }
 }
@@ -235,11 +234,36 @@ struct PointSet {
     double* vn;       // MODE 0, PHASE 1 / 2: the hypothesis' four null-space vectors [4][12] in LDS
 };
 
-// sum of vals[0..CNT) over the point set, result in every thread (MODE 0: every lane already holds the full sums)
+// sum of vals[0..CNT) over the point set, result in every thread (MODE 0: every lane already holds the full sums).
+// THE THREE SUMS OF THIS FILE THAT STAY AS WRITTEN - this one, lm_pass's and the scoring pass's count: the order is the one of
+// pp_reduce_dev.h (offsets 32 .. 1, then the waves from 0.0 in ascending order, as block_reduce_all(vals, red, op_sum{}, 0.0)
+// walks it), but pnp_ransac_kernel sits at 256 VGPRs and spills, and with these loops inside the helpers the register allocator
+// spills more of it (583 -> 624 VGPR spills, 1256 -> 1408 bytes of scratch in the refining instance; profiles/r21).
 template <int MODE, int CNT>
 __device__ inline void set_sum(const PointSet<MODE>& ps, double (&vals)[CNT]) {
     if (MODE == 0) return;
-    block_sum<NW, CNT>(vals, ps.red);
+    double* red = ps.red;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < CNT; ++c) {
+        double x = vals[c];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+        vals[c] = x;
+    }
+    __syncthreads();   // (the previous use of `red` has been read by everyone)
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < CNT; ++c) red[wv * CNT + c] = vals[c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < CNT; ++c) {
+        double x = 0.0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) x += red[w * CNT + c];
+        vals[c] = x;
+    }
 }
 
 #define PP_FOR_POINTS(ps, i, ...)                                                          \
@@ -350,6 +374,8 @@ _Pragma("unroll")
             for (int i = threadIdx.x / GL; i < ps.n; i += NG)
                 if (ps.use[i]) add_point(i);
             const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+            // (stays as written: the four 16-lane groups of a wave summed at offsets 16, then 32 - a float64 sum in an order that
+            // pp_reduce_dev.h does not walk)
 #pragma unroll
             for (int r = 0; r < 12; ++r) { g12[r] += __shfl_xor(g12[r], 16); g12[r] += __shfl_xor(g12[r], 32); }
             __syncthreads();
@@ -614,7 +640,7 @@ __device__ inline void lm_pass(const PTS& pts, const Cam& cam, const double (&R)
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
-    for (int c = 0; c < LM_NV; ++c) {
+    for (int c = 0; c < LM_NV; ++c) {                              // (stays as written: set_sum's comment)
         double x = s[c];
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
@@ -906,12 +932,15 @@ __global__ __launch_bounds__(NT) void pnp_ransac_kernel(const float* __restrict_
                 c += (du * du + dv * dv <= th2) ? 1 : 0;  // NaN (degenerate hypothesis) is never an inlier
             }
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+            for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);   // (stays as written: set_sum's comment)
             if (lane == 0 && c) atomicAdd(&cnt[h], c);
         }
     }
     __syncthreads();
-    if (tid < 64) ransac_winner(cnt, nh, &best_h, &best_c);
+    if (tid < 64) {
+        const Winner w = winner<1>(cnt, nh, nullptr, 0);
+        if (tid == 0) { best_h = w.h; best_c = w.c; }
+    }
     __syncthreads();
     if (best_c < SAMPLE) { fail(); return; }
     {

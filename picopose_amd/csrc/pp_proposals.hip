@@ -6,6 +6,7 @@
 #include <limits.h>
 #include <math.h>
 #include "pp_common.h"
+#include "pp_reduce_dev.h"
 #include "pp_runs_dev.h"
 
 namespace {
@@ -24,16 +25,14 @@ constexpr int PAIR_LD = PAIR_KW + 4;         // row stride in LDS (the kernel's 
 // in ascending element order with one fma each, starting from 0; the 64 lane sums are then folded by a butterfly over the lane
 // masks 32, 16, 8, 4, 2, 1.  a + b is commutative, so after the step with mask m lanes l and l ^ m hold the same bits: the
 // result is one value in every lane, and a lane that runs only its own branch of the butterfly (fold16 below) gets that value.
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, WAVE);
-    return v;
-}
+// (wave_sum of pp_reduce_dev.h is that butterfly.)
 
 // 16 values per lane -> the full butterfly sum of value p in the lanes with ((l >> 2) & 15) bit-reversed == p: at the steps 32,
 // 16, 8, 4 a lane keeps the half of its values that its lane bit selects and hands the other half to its partner (8 + 4 + 2 + 1
 // shuffles), the steps 2 and 1 are plain.  Value p of lane l sees the additions of wave_sum at lane l, in the same order.
-// (One template instance per step: with the step's constants known at compile time each exchange is two selects and a shuffle.)
+// (Stays as written: a step adds what the PARTNER hands over to what the lane keeps, a reduce-scatter and not a wave_reduce walk;
+// only the shuffle is the header's lane_xor.  One template instance per step: with the step's constants known at compile time
+// each exchange is two selects and a shuffle.)
 template <int HALF, int M>
 __device__ __forceinline__ void fold_step(float (&a)[MATCH_P], int lane) {
     const bool hi = (lane & M) != 0;
@@ -41,7 +40,7 @@ __device__ __forceinline__ void fold_step(float (&a)[MATCH_P], int lane) {
     for (int i = 0; i < HALF; ++i) {
         const float send = hi ? a[i] : a[i + HALF];
         const float keep = hi ? a[i + HALF] : a[i];
-        a[i] = keep + __shfl_xor(send, M, WAVE);
+        a[i] = keep + lane_xor(send, M);
     }
 }
 __device__ __forceinline__ float fold16(float (&a)[MATCH_P], int lane) {
@@ -49,10 +48,7 @@ __device__ __forceinline__ float fold16(float (&a)[MATCH_P], int lane) {
     fold_step<4, 16>(a, lane);
     fold_step<2, 8>(a, lane);
     fold_step<1, 4>(a, lane);
-    float v = a[0];
-    v += __shfl_xor(v, 2, WAVE);
-    v += __shfl_xor(v, 1, WAVE);
-    return v;
+    return wave_reduce_range<2, 1>(a[0], op_sum{});
 }
 __device__ __forceinline__ int fold16_owner(int lane) {
     return (((lane >> 5) & 1) << 3) | (((lane >> 4) & 1) << 2) | (((lane >> 3) & 1) << 1) | ((lane >> 2) & 1);
@@ -259,11 +255,8 @@ __global__ __launch_bounds__(256) void rle_pack_bits_kernel(const int* __restric
             const int len = ends[k] - ends[k - 1];
             s += len > 0 ? len : 0;
         }
-#pragma unroll
-        for (int mk = 32; mk >= 1; mk >>= 1) s += __shfl_xor(s, mk, WAVE);
-        if ((tid & 63) == 0) part[tid >> 6] = s;
-        __syncthreads();
-        if (tid == 0) area[d] = part[0] + part[1] + part[2] + part[3];
+        s = block_reduce_to<4>(s, part, op_sum{});
+        if (tid == 0) area[d] = s;
     }
 }
 
@@ -302,8 +295,7 @@ __global__ __launch_bounds__(PAIR * PAIR * PAIR_Q) void mask_intersections_kerne
         for (int k = 0; k < PAIR_KW; k += PAIR_Q) count += __popc(a[ti * PAIR_LD + k + kq] & b[tj * PAIR_LD + k + kq]);
         __syncthreads();
     }
-    count += __shfl_xor(count, 1, WAVE);
-    count += __shfl_xor(count, 2, WAVE);
+    count = wave_reduce_range<PAIR_Q / 2, 1>(count, op_sum{});               // the PAIR_Q threads of a pair (integers: any order)
     if (kq == 0 && i0 + ti < n && j0 + tj < n) inter[(size_t)(i0 + ti) * n + j0 + tj] = count;
 }
 

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "pp_hash_dev.h"
+#include "pp_reduce_dev.h"
 
 constexpr int NT = 512;           // 8 waves, one workgroup per CU (the correspondences of a problem fill most of the LDS)
 constexpr int NW = NT / 64;
@@ -80,33 +81,10 @@ __device__ inline void jacobi_sym(double (&A)[N][N], double (&V)[N][N]) {
 }
 
 // ------------------------------------------------------------------ workgroup rules
-// Sum of vals[0..CNT) over the NWAVES waves of the workgroup in a fixed order, result in every thread: xor-butterfly within each
-// wave (every lane ends with the same bits: a + b == b + a), then the wave partials summed w = 0, 1, ... by every thread.  Every
-// thread thus holds the same bits and can run the same small algebra on them without a broadcast.  red: NWAVES * CNT doubles of LDS.
-template <int NWAVES, int CNT>
-__device__ inline void block_sum(double (&vals)[CNT], double* red) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < CNT; ++c) {
-        double x = vals[c];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-        vals[c] = x;
-    }
-    __syncthreads();   // (the previous use of `red` has been read by everyone)
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < CNT; ++c) red[wv * CNT + c] = vals[c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < CNT; ++c) {
-        double x = 0.0;
-#pragma unroll
-        for (int w = 0; w < NWAVES; ++w) x += red[w * CNT + c];
-        vals[c] = x;
-    }
-}
+// The sums of vals[0..CNT) over the NW waves go through block_reduce_all<NW>(vals, red, op_sum{}, 0.0) of pp_reduce_dev.h: every
+// thread ends with the same bits and can run the same small algebra on them without a broadcast.  red: NW * CNT doubles of LDS;
+// the caller's barrier before the call guards its previous use.  The winner (arg-max of the consensus, lowest hypothesis index
+// among equals, hypothesis 0 and count -1 when there is none) is winner<1>(cnt, nh, nullptr, 0), run by the first wave.
 
 // The SAMPLE distinct indices in [0, np) of hypothesis h of problem `prob`: a counter-based sequence, keyed by the problem and
 // the hypothesis and never by the thread, so the two phases of the PnP redraw the same sample.  s = mix(0x9E3779B9 (prob + 1) ^
@@ -125,20 +103,6 @@ __device__ __forceinline__ void ransac_sample(int prob, int h, int np, int (&idx
             if (!dup) { idx[k] = c; break; }
         }
     }
-}
-
-// The winner, run by the first wave (threadIdx.x < 64, all 64 lanes): arg-max of the consensus cnt[0..nh), lowest hypothesis
-// index among equals; lane 0 writes it to *best_h / *best_c (-1 when nh is 0).
-__device__ __forceinline__ void ransac_winner(const int* cnt, int nh, int* best_h, int* best_c) {
-    int bc = -1, bh = 0;
-    for (int h = threadIdx.x; h < nh; h += 64)
-        if (cnt[h] > bc) { bc = cnt[h]; bh = h; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int oc = __shfl_xor(bc, o), oh = __shfl_xor(bh, o);
-        if (oc > bc || (oc == bc && oh < bh)) { bc = oc; bh = oh; }
-    }
-    if (threadIdx.x == 0) { *best_h = bh; *best_c = bc; }
 }
 
 // The outputs of a failed problem that both solvers share, written by one thread: (I, [0,0,1], ratio 0, ok 0), the reference's

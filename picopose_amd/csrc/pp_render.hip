@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include <limits.h>
 #include "pp_common.h"
+#include "pp_reduce_dev.h"
 #include "pp_crop_dev.h"
 
 #pragma clang fp contract(off)
@@ -321,13 +322,8 @@ __global__ __launch_bounds__(1024) void extents_kernel(const uchar4* __restrict_
             cmax = max(cmax, x);
             ++cnt;
         }
-    for (int o = 32; o > 0; o >>= 1) {
-        rmin = min(rmin, __shfl_xor(rmin, o));
-        rmax = max(rmax, __shfl_xor(rmax, o));
-        cmin = min(cmin, __shfl_xor(cmin, o));
-        cmax = max(cmax, __shfl_xor(cmax, o));
-        cnt += __shfl_xor(cnt, o);
-    }
+    rmin = wave_min(rmin), rmax = wave_max(rmax), cmin = wave_min(cmin), cmax = wave_max(cmax), cnt = wave_sum(cnt);
+    // (the fold stays as written: thread 0 takes all five values of the 16 waves, neither result convention of pp_reduce_dev.h's workgroup forms)
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         s[0][wave] = rmin;

@@ -14,9 +14,9 @@
 // popcount per 64 points.  No atomics.  Phase 3: the whole workgroup refits on the winner's consensus set, sums reduced in a fixed
 // order (xor-butterfly within a wave, then the 8 wave partials in order), every thread solving the same small system.
 //
-// The rules shared with pp_pnp_ransac — workgroup shape and capacities, the cyclic Jacobi behind horn_fit and eig3_top2, the block
-// sum, the sampling sequence, the winner's tie rule, the failure outputs, the object-frame source point — are the functions of
-// pp_ransac_dev.h, the ones pp_pnp.hip calls.  The kernel keeps 224 VGPRs, no spills and no scratch.
+// The rules shared with pp_pnp_ransac — workgroup shape and capacities, the cyclic Jacobi behind horn_fit and eig3_top2, the
+// sampling sequence, the failure outputs, the object-frame source point — are the functions of pp_ransac_dev.h, the ones pp_pnp.hip
+// calls; the block sum and the winner's tie rule are block_reduce_all and winner of pp_reduce_dev.h.  The kernel keeps 224 VGPRs, no spills and no scratch.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,7 +27,7 @@
 namespace {
 
 constexpr int SAMPLE = 3;
-constexpr int NRED = 16;          // doubles of reduction scratch per wave: block_sum<NW, CNT> needs CNT <= NRED (15 is the widest)
+constexpr int NRED = 16;          // doubles of reduction scratch per wave: block_reduce_all<NW> over CNT values needs CNT <= NRED (15 is the widest)
 constexpr double DEGENERATE = 1e-6;
 
 // ------------------------------------------------------------------ small dense helpers (double, everything in registers)
@@ -243,7 +243,10 @@ __global__ __launch_bounds__(NT) void rgbd_ransac_kernel(const float* __restrict
         if (lane == 0) cnt[h] = c;
     }
     __syncthreads();
-    if (tid < 64) ransac_winner(cnt, nh, &best_h, &best_c);
+    if (tid < 64) {
+        const Winner w = winner<1>(cnt, nh, nullptr, 0);
+        if (tid == 0) { best_h = w.h; best_c = w.c; }
+    }
     for (int i = tid; i < MAXP; i += NT) lmask[i] = 0;
     __syncthreads();
     if (best_c < SAMPLE) { fail(); return; }
@@ -265,7 +268,8 @@ __global__ __launch_bounds__(NT) void rgbd_ransac_kernel(const float* __restrict
         for (int c = 0; c < 3; ++c) { s7[c] += ps[3 * i + c]; s7[3 + c] += pq[3 * i + c]; }
         s7[6] += 1.0;
     }
-    block_sum<NW, 7>(s7, red);
+    __syncthreads();   // (the previous use of `red` has been read by everyone)
+    block_reduce_all<NW>(s7, red, op_sum{}, 0.0);
     const double n = s7[6];
     double pm[3], qm[3];
 #pragma unroll
@@ -282,7 +286,8 @@ __global__ __launch_bounds__(NT) void rgbd_ransac_kernel(const float* __restrict
         s15[6] += a2 * b0; s15[7] += a2 * b1; s15[8] += a2 * b2;
         s15[9] += a0 * a0; s15[10] += a0 * a1; s15[11] += a0 * a2; s15[12] += a1 * a1; s15[13] += a1 * a2; s15[14] += a2 * a2;
     }
-    block_sum<NW, 15>(s15, red);
+    __syncthreads();   // (the previous use of `red` has been read by everyone)
+    block_reduce_all<NW>(s15, red, op_sum{}, 0.0);
     double M[12];
     {
         double S[9], R[9], t[3];
@@ -300,7 +305,8 @@ __global__ __launch_bounds__(NT) void rgbd_ransac_kernel(const float* __restrict
     double e[1] = {0.0};
     for (int i = tid; i < np; i += NT)
         if (use[i]) e[0] += residual2(M, ps, pq, i);
-    block_sum<NW, 1>(e, red);
+    __syncthreads();   // (the previous use of `red` has been read by everyone)
+    block_reduce_all<NW>(e, red, op_sum{}, 0.0);
     if (tid == 0) {
         for (int k = 0; k < 9; ++k) rot[(size_t)prob * 9 + k] = M[k];
         for (int k = 0; k < 3; ++k) tvec[(size_t)prob * 3 + k] = M[9 + k];

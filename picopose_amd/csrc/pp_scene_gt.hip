@@ -113,7 +113,7 @@ __global__ __launch_bounds__(BLOCK) void scene_gt_reduce_kernel(Scene s, Frame f
                 if (mask_visib) mask_visib[(size_t)v * frame + pix] = 255;
             }
         });
-        const int a = block_reduce(val, sm, combine);
+        const int a = block_reduce_to<WAVES>(val, sm, combine);
         if (threadIdx.x < NV) {
             const int c = threadIdx.x;
             if (c < 3) {

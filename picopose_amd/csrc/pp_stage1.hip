@@ -43,6 +43,7 @@
 #include <type_traits>
 #include "../../include/picopose_hip.h"
 #include "pp_common.h"
+#include "pp_reduce_dev.h"
 
 namespace {
 
@@ -357,6 +358,7 @@ __device__ __forceinline__ float vmax3(float a, float b, float c) {
     asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
+// (These stay as written, not wave_reduce_range<2, 1> of pp_reduce_dev.h: DESIGN §3 has the measurement.)
 // max(own, partner's `src`) with the partner = lane^1 / lane^2 of the quad (DPP, no LDS traffic).  The s_nop
 // covers the 2 wait states a DPP read needs after a VALU write of the same register.
 __device__ __forceinline__ float vmax_xor1(float own, float src) {
@@ -715,7 +717,7 @@ __device__ __forceinline__ void s1_body(const XT* __restrict__ bank,
             //    adds up the partials of its own two columns in a fixed order
             if (MODE == PP_MATCH_FAST) {
                 *(f4*)(red + (2 * w + lh) * 128 + 4 * l31) = f4{ssq0, ssq1, ssq2, ssq3};
-            } else {
+            } else {                                   // (stays as written: the lane halves l and l + 32 of a fragment trade, a layout step)
                 const float s0 = ssq0 + __shfl_xor(ssq0, 32);
                 const float s1 = ssq1 + __shfl_xor(ssq1, 32);
                 if (wr == 0 && lh == 0) {
@@ -748,7 +750,7 @@ __device__ __forceinline__ void s1_body(const XT* __restrict__ bank,
 #pragma unroll
                 for (int k = 2; k < 64; k += 2) m = vmax3(m, acc[k >> 4][sb][k & 15], acc[(k + 1) >> 4][sb][(k + 1) & 15]);
                 if (!(wr == 0 && lh == 0)) m = vmax(m, acc[0][sb][0]);
-                cm[sb] = vmax(m, __shfl_xor(m, 32));
+                cm[sb] = vmax(m, __shfl_xor(m, 32));   // (stays as written: the same exchange of the two lane halves)
             }
             if (lh == 0) {
                 colp[wr * 128 + wc * 64 + l31] = cm[0];
@@ -931,6 +933,15 @@ __device__ __forceinline__ bool topk_better(float v, int j, float bv, int bi) {
     if (!vn && v != bv) return v > bv;
     return j < bi;
 }
+// a lane's or a wave's best (score, template); index -1: none yet.  The step of the wave reduction of both top-k kernels
+struct Scored {
+    float v;
+    int i;
+};
+__device__ __forceinline__ Scored topk_pick(Scored a, const Scored& b) {
+    if (b.i >= 0 && topk_better(b.v, b.i, a.v, a.i)) a = b;
+    return a;
+}
 
 // one crop's row by one 256-thread workgroup; sc: N floats followed by N taken flags (LDS).  COHERENT: the row was written by
 // other workgroups of THIS launch (the fused resolve + top-k): read it with agent-scope atomic loads
@@ -952,21 +963,14 @@ __device__ __forceinline__ void topk_block(const float* __restrict__ row, int N,
                 bv = sc[j];
                 bi = j;
             }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o);
-            const int oi = __shfl_xor(bi, o);
-            if (oi >= 0 && topk_better(ov, oi, bv, bi)) {
-                bv = ov;
-                bi = oi;
-            }
-        }
+        const Scored best = wave_reduce(Scored{bv, bi}, topk_pick);
+        bv = best.v, bi = best.i;
         if ((tid & 63) == 0) {
             wv[tid >> 6] = bv;
             wi[tid >> 6] = bi;
         }
         __syncthreads();
-        if (tid == 0) {
+        if (tid == 0) {                                // (the fold stays here: thread 0 goes on to write the entry and the taken flag)
             for (int q = 1; q < 4; ++q)
                 if (wi[q] >= 0 && topk_better(wv[q], wi[q], bv, bi)) {
                     bv = wv[q];
@@ -1003,15 +1007,8 @@ __global__ __launch_bounds__(256) void topk_rows_small(const float* __restrict__
                 bv = v[q];
                 bi = lane + 64 * q;
             }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o);
-            const int oi = __shfl_xor(bi, o);
-            if (oi >= 0 && topk_better(ov, oi, bv, bi)) {
-                bv = ov;
-                bi = oi;
-            }
-        }
+        const Scored best = wave_reduce(Scored{bv, bi}, topk_pick);
+        bv = best.v, bi = best.i;
         if (lane == 0) {
             out_score[(size_t)b * k + it] = bv;
             out_index[(size_t)b * k + it] = bi;
@@ -1168,12 +1165,12 @@ __global__ __launch_bounds__(256) void s1_resolve(const XT* __restrict__ bank,
                 }
                 const float sim = dot * (1.0f / fmaxf(sqrtf(se + so), 1e-12f));
                 float mx = i == 0 ? -INFINITY : sim;  // index 0 is the other side
-#pragma unroll
-                for (int d = 32; d > 0; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
+                mx = wave_max(mx);
                 if (lane == 0) wred[i >> 6] = mx;
                 if (i == 0) res[0] = sim;
                 __syncthreads();
                 if (i == idx) {
+                    // (the fold stays a tree: a similarity may be NaN or -0, where fmaxf's result could depend on the order)
                     const float mxa = fmaxf(fmaxf(wred[0], wred[1]), fmaxf(wred[2], wred[3]));
                     if (kind == 1) {
                         rme = mxa;
@@ -1194,11 +1191,7 @@ __global__ __launch_bounds__(256) void s1_resolve(const XT* __restrict__ bank,
     const float rm = fmaxf(rme, st);          // score_tar2src
     const float mall = m * cnz * rnz;
     float s = rm * mall, ms = mall;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s += __shfl_xor(s, o);
-        ms += __shfl_xor(ms, o);
-    }
+    s = wave_sum(s), ms = wave_sum(ms);
     if (lane == 0) {
         wred[i >> 6] = s;
         wred[4 + (i >> 6)] = ms;
@@ -1206,6 +1199,7 @@ __global__ __launch_bounds__(256) void s1_resolve(const XT* __restrict__ bank,
     __syncthreads();
     __shared__ int last_of_crop;
     if (i == 0) {
+        // (the fold stays a tree: a float sum, and not in the ascending order of block_reduce_all)
         const float tot = (wred[0] + wred[1]) + (wred[2] + wred[3]);
         const float mt = (wred[4] + wred[5]) + (wred[6] + wred[7]);
         const float v = mt > 0.f ? tot / 256.0f : 0.f;

@@ -17,6 +17,7 @@
 #include <limits.h>
 #include <math.h>
 #include "pp_common.h"
+#include "pp_reduce_dev.h"
 #include "pp_hash_dev.h"
 
 #pragma clang fp contract(off)
@@ -213,11 +214,7 @@ __global__ __launch_bounds__(BLOCK) void scene_composite_kernel(Composite a) {
 #pragma unroll
                 for (int j = 0; j < PX; ++j)
                     if (won[j]) e[0] = min(e[0], x[j]), e[1] = min(e[1], y[j]), e[2] = max(e[2], x[j]), e[3] = max(e[3], y[j]);
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) {
-                    e[0] = min(e[0], __shfl_xor(e[0], d, 64)), e[1] = min(e[1], __shfl_xor(e[1], d, 64));
-                    e[2] = max(e[2], __shfl_xor(e[2], d, 64)), e[3] = max(e[3], __shfl_xor(e[3], d, 64));
-                }
+                wave_reduce_each(e, [](int c, int p, int q) { return c < 2 ? min(p, q) : max(p, q); });
             }
             if (lane == 0) {
                 int* r = sm_vis[wave][l - c0];
@@ -249,12 +246,7 @@ __global__ __launch_bounds__(64) void scene_finish_kernel(const int* __restrict_
         v[0] += r[0], v[1] += r[1];
         v[2] = min(v[2], r[2]), v[3] = min(v[3], r[3]), v[4] = max(v[4], r[4]), v[5] = max(v[5], r[5]);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        v[0] += __shfl_xor(v[0], d, 64), v[1] += __shfl_xor(v[1], d, 64);
-        v[2] = min(v[2], __shfl_xor(v[2], d, 64)), v[3] = min(v[3], __shfl_xor(v[3], d, 64));
-        v[4] = max(v[4], __shfl_xor(v[4], d, 64)), v[5] = max(v[5], __shfl_xor(v[5], d, 64));
-    }
+    wave_reduce_each(v, [](int c, int p, int q) { return c < 2 ? p + q : (c < 4 ? min(p, q) : max(p, q)); });
     if (lane == 0) {
         counts[2 * (size_t)l] = v[0], counts[2 * (size_t)l + 1] = v[1];
         const bool empty = v[1] == 0;

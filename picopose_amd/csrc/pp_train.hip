@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include "../../include/picopose_hip.h"
 #include "pp_common.h"
+#include "pp_reduce_dev.h"
 
 namespace {
 
@@ -275,8 +276,7 @@ __global__ __launch_bounds__(256) void gather_normalize_kernel(const float* __re
     const float* s = src + index[row] * row_stride;
     float q = 0.f;
     for (int c = lane; c < C; c += 64) q = fmaf(s[c], s[c], q);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+    q = wave_sum(q);
     const float inv = 1.0f / fmaxf(sqrtf(q), eps);
     for (int c = lane; c < C; c += 64) out[(size_t)row * C + c] = s[c] * inv;
 }
@@ -289,12 +289,10 @@ __global__ __launch_bounds__(256) void xent_diag_kernel(const float* __restrict_
     const float* r = L + (size_t)row * ld;
     float mx = -INFINITY;
     for (int j = lane; j < n; j += 64) mx = fmaxf(mx, r[j] * scale);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    mx = wave_max(mx);
     float s = 0.f;
     for (int j = lane; j < n; j += 64) s += expf(r[j] * scale - mx);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    s = wave_sum(s);
     if (lane == 0) loss[row] = mx + logf(s) - r[row] * scale;
 }
 
@@ -306,7 +304,7 @@ __global__ __launch_bounds__(256) void xent_diag_kernel(const float* __restrict_
 __global__ __launch_bounds__(256) void flow_loss_kernel(const float* __restrict__ flow, const float* __restrict__ cert,
                                                         const float* __restrict__ tar_pts, int B, int H, int W, float max_flow,
                                                         double* __restrict__ part) {
-    __shared__ double red[3][4];
+    __shared__ double red[4][3];
     const long long total = (long long)B * H * W;
     double bce = 0.0, l1 = 0.0, cnt = 0.0;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -324,15 +322,9 @@ __global__ __launch_bounds__(256) void flow_loss_kernel(const float* __restrict_
             cnt += 1.0;
         }
     }
-    double v[3] = {bce, l1, cnt};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) part[(size_t)blockIdx.x * 3 + threadIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+    const double v[3] = {bce, l1, cnt};
+    const double sum = block_reduce_to<4>(v, red, op_sum{});
+    if (threadIdx.x < 3) part[(size_t)blockIdx.x * 3 + threadIdx.x] = sum;
 }
 
 }  // namespace

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(BLOCK) void pose_verify_reduce_kernel(Scene s, Evid
             val[0] += 1, val[1] += in_mask, val[2] += valid, val[3] += valid & ~(front | behind), val[4] += front, val[5] += behind;
             val[6] += vis, val[7] += vis & in_mask;
         });
-        const int a = block_reduce(val, sm, [](int, int p, int q) { return p + q; });
+        const int a = block_reduce_to<WAVES>(val, sm, op_sum{});
         if (threadIdx.x < NC && a != 0) atomicAdd(counts + NC * (size_t)v + threadIdx.x, a);
         __syncthreads();                                          // sm is reused by the workgroup's next view
     });

@@ -93,7 +93,7 @@ __global__ __launch_bounds__(BLOCK) void vsd_pair_kernel(Scene s, const unsigned
         }
     }
     __shared__ int sm[WAVES][NC];
-    const int v = block_reduce(cnt, sm, [](int, int a, int b) { return a + b; });
+    const int v = block_reduce_to<WAVES>(cnt, sm, op_sum{});
     if ((int)threadIdx.x < 2 + T) {
         counts[(size_t)p * (2 + T) + threadIdx.x] = v;
         if (threadIdx.x >= 2) {

@@ -9,11 +9,11 @@
 //                       raster's frame.  Callers subtract their own offsets and keep their own early-outs
 //   ray_scale, visible  BOP's distance along the ray, r with d = Z r, and its visibility rule.  Three float operations in a fixed order
 //                       and one predicate: every entry that states visibility computes the same bits
-//   block_reduce        the workgroup's total of an int[N] record under combine(c, a, b): xor-shuffles 32 .. 1 within a wave, then
-//                       the waves in order.  The tree is fixed and the values are integers: the total does not depend on the launch
+//   (the workgroup's totals of the readers' int[N] records go through block_reduce_to<WINDOW_WAVES> of pp_reduce_dev.h)
 //   window_grid (host)  the (chunk, view) grid of a launch whose kernel goes through for_each_window
 #ifndef PP_WINDOW_DEV_H
 #define PP_WINDOW_DEV_H
+#include "pp_reduce_dev.h"
 #include "pp_vsd_raster_dev.h"
 
 namespace {
@@ -71,27 +71,6 @@ __device__ __forceinline__ float ray_scale(int x, int y, float fx, float fy, flo
 // a model sample at distance d against the test distance d_test (missing: the test image holds none there)
 __device__ __forceinline__ bool visible(float d, float d_test, bool missing, float delta) {
     return d > 0.f && (missing || d - d_test <= delta);
-}
-
-// -> in thread c < N the workgroup's total of val[c]; sm is the caller's __shared__ int[WINDOW_WAVES][N] and holds the waves' totals
-// afterwards.  A caller that reduces again through the same sm puts a barrier in between.
-template <int N, class Combine>
-__device__ __forceinline__ int block_reduce(const int (&val)[N], int (*sm)[N], Combine combine) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-        int a = val[c];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) a = combine(c, a, __shfl_xor(a, d, 64));
-        if (lane == 0) sm[wave][c] = a;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x >= N) return 0;
-    const int c = threadIdx.x;
-    int a = sm[0][c];
-#pragma unroll
-    for (int q = 1; q < WINDOW_WAVES; ++q) a = combine(c, a, sm[q][c]);
-    return a;
 }
 
 inline dim3 window_grid(int n_views, long long max_window) {
