@@ -1728,6 +1728,87 @@ int pp_det_match(const double* iou, int n_pairs, const int* groups, const int* g
                  const double* area_ranges_host, int A, const double* iou_thrs, const double* iou_thrs_host, int T, int* dt_match,
                  unsigned char* dt_ignore, int* gt_match, unsigned char* gt_ignore, void* stream);
 
+/* -------------------------------------------------------------------------
+ * 6D DETECTION SCORING: average precision of pose estimates against ground truth under MSSD and MSPD, where every estimate counts
+ * and a false positive is punished — the task the chain depth_proposals -> label_proposals -> infer_proposals -> verify / refine
+ * solves (an unknown number of instances per image) — and the suppression of duplicate poses of one instance
+ * (csrc/pp_pose_det.hip; picopose_amd/pose_detection_eval.py plans every call and accumulates on the host;
+ * tests/pose_detection_oracle.py restates this text in numpy loops; every device output equals it bit for bit).  This is the BOP
+ * 2024 6D-detection protocol AS REMEMBERED: the BOP toolkit cannot be run next to this library, so parity with it is UNPINNED.
+ * The suppression rule is the project's own.  All pointers are device pointers unless named *_host; all work is enqueued on
+ * `stream`, nothing synchronises; no entry uses atomics, accumulates in floating point or needs scratch or LDS.
+ *
+ * RECORDS.  An estimate is a row of a BOP results file (evaluation.read_bop_results): scene_id, im_id, obj_id, score, R, t.  A
+ * ground truth is an instance of scene_gt.json (evaluation.read_scene_gt) with an IGNORE flag: set when its visib_fract (of
+ * scene_gt_info.json) is below min_visib_fract (default 0.1, as remembered): it is neither required nor does a match to it count.
+ * An image is one (scene_id, im_id); a GROUP is one (image, obj_id) that holds at least one record of either side.
+ *
+ * ORDER.  Within an image only the max_per_image best-scored estimates are kept (default 100, as remembered; none dropped when
+ * the caller asks for all): by descending score, the lower row first among equal scores, across all objects of the image.  Within
+ * a group the kept estimates go by descending score, the lower row first among equal scores; the ground truths stay in scene_gt
+ * order.
+ *
+ * THE TABLES OF A CALL.  n_est estimates and n_gt ground truths, each side with its groups contiguous and in the order above.
+ * groups (n_groups, PP_DET_GROUP_FIELDS) int32 with a host copy = {first estimate, E_g, first ground truth, G_g, offset of the
+ * group's block}: DETECTION SCORING's row.  err (M, n_pairs) float32, one row of n_pairs entries per metric: a group's block is
+ * E_g x G_g row-major (estimate-major), so an estimate's errors to the group's ground truths are contiguous.  An empty side
+ * (E_g = 0 or G_g = 0) is legal.  gt_ignore (n_gt) uint8, non-zero = ignored.  limits (n_groups, M, T) float64 with a host copy:
+ * what an error must stay BELOW at threshold t of metric m in that group (the Python layer: MSSD threshold x the object's
+ * diameter, MSPD threshold x image_width / 640).  A pair QUALIFIES when (double)err < limit, strictly, as evaluation.score_pairs
+ * has it; a NaN and +inf never qualify, and neither does an entry whose sign bit is set: an error is a distance.
+ *
+ * MATCHING, per group, metric m and threshold t, the group's estimates visited in order: among the group's ground truths that are
+ * not yet matched at this (m, t) and qualify, the winner is the lowest error among the NON-IGNORED ones, the lowest index among
+ * equal errors; only if no non-ignored one qualifies does the same rule apply among the ignored ones.  A matched estimate takes
+ * the winner's ignore flag and the winner is marked matched; an estimate without a winner is unmatched — a false positive, never
+ * ignored.
+ *
+ * ACCUMULATION is the host's, numpy float64, with the formulae of DETECTION SCORING's ACCUMULATION paragraph: per object, metric
+ * and threshold the estimates of all images are concatenated (groups in sorted (image, object) order) and sorted by descending score
+ * (mergesort); tp / fp are cumulative sums of (matched / unmatched) and not ignored; npig = the object's non-ignored ground truths;
+ * rc = tp / npig, pr = tp / (tp + fp + spacing(1)); pr is made non-increasing from the right and sampled at the 101 recalls
+ * np.linspace(0, 1, 101) by searchsorted(rc, r, "left"); the recall reported is rc[-1] (0 without estimates).  An object without a
+ * non-ignored ground truth stays -1.  SUMMARY: AP_MSSD = the mean over the objects (those > -1) of the mean over thresholds and
+ * recall samples, AP_MSPD likewise, AP = (AP_MSSD + AP_MSPD) / 2; -1 when no object counts.
+ *
+ * pp_pose_match.  One wave per (group, m, t): the group's ground truths are spread over the lanes (j = lane + 64 k), the matched and
+ * ignore flags of a lane's ground truths are bits of two 64-bit registers (hence G_g <= PP_POSE_MAX_GROUP), the estimates are
+ * walked in order, each reading its contiguous row of G_g errors, and the winner is found by two wave reductions (the smallest
+ * error bit pattern — non-negative floats order as unsigned integers — then the lowest index that holds it), the non-ignored
+ * class first.  Outputs:
+ *   est_match  (M, T, n_est) int32  the call-wide index of the matched ground truth, or -1;
+ *   est_ignore (M, T, n_est) uint8  the matched ground truth's ignore flag; unmatched: 0;
+ *   gt_match   (M, T, n_gt)  int32  the call-wide index of the estimate matched to it, or -1.
+ * Every element of a group of the table is written; records outside every group are not.  1 <= M <= PP_POSE_MAX_METRICS (MSSD and
+ * MSPD today; the cap leaves room for VSD).
+ * PP_EINVAL (before the launch, no GPU needed): a null pointer; n_pairs, n_est or n_gt negative; n_groups, M or T <= 0; M >
+ * PP_POSE_MAX_METRICS; a groups_host row with a negative field, a range past n_est / n_gt or a block past n_pairs; G_g >
+ * PP_POSE_MAX_GROUP; a NaN in limits_host.
+ *
+ * DUPLICATE POSES (the project's own rule; nms_dist is untuned and its effect on real data unmeasured).  Groups and the order
+ * within a group as above, without the per-image cut.  For the group's estimates in order, DIST(i, j), i < j, is the MSSD with
+ * the earlier estimate i as the ground truth and the later j as the estimate (the object's symmetries included; the roles are
+ * fixed because the value is slightly asymmetric).  Visiting j = 0 .. E_g - 1: j is DROPPED when a KEPT earlier i has
+ * (double)DIST(i, j) < limit (strict: a distance exactly at the limit keeps j); otherwise j is kept.  A dropped estimate
+ * suppresses nothing.  The Python layer's limit is nms_dist x the object's diameter (default 0.1).
+ *
+ * pp_pose_nms.  groups (n_groups, PP_POSE_NMS_FIELDS) int32 with a host copy = {first estimate, E_g, offset of the group's
+ * triangle}; dist (n_tri) float32: DIST(i, j) is at offset + j (j - 1) / 2 + i, so a candidate's earlier partners are contiguous;
+ * limit (n_groups) float64 with a host copy.  One wave per group holds the kept bits of the positions lane + 64 k in a 64-bit
+ * register (hence E_g <= PP_POSE_MAX_GROUP) and finds a near kept partner by ballot, 64 partners at a time.  Output: keep (n_est)
+ * uint8, every element of a group written.
+ * PP_EINVAL (before the launch, no GPU needed): a null pointer; n_tri or n_est negative; n_groups <= 0; a groups_host row with a
+ * negative field, a range past n_est, E_g > PP_POSE_MAX_GROUP or a triangle past n_tri; a limit_host that is NaN or negative.
+ * ------------------------------------------------------------------------- */
+#define PP_POSE_MAX_GROUP 4096
+#define PP_POSE_MAX_METRICS 4
+#define PP_POSE_NMS_FIELDS 3
+int pp_pose_match(const float* err, int M, int n_pairs, const int* groups, const int* groups_host, int n_groups, int n_est, int n_gt,
+                  const unsigned char* gt_ignore, const double* limits, const double* limits_host, int T, int* est_match,
+                  unsigned char* est_ignore, int* gt_match, void* stream);
+int pp_pose_nms(const float* dist, int n_tri, const int* groups, const int* groups_host, int n_groups, int n_est, const double* limit,
+                const double* limit_host, unsigned char* keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

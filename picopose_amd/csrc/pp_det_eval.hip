@@ -6,6 +6,7 @@
 #include <limits.h>
 #include <math.h>
 #include "pp_common.h"
+#include "pp_det_group.h"
 #include "pp_reduce_dev.h"
 
 namespace {
@@ -15,26 +16,8 @@ constexpr int PAIR = PP_DET_TILE;            // a workgroup owns PAIR x PAIR (de
 constexpr int PAIR_Q = 4;                    // PAIR_Q threads per pair (segm),
 constexpr int PAIR_KW = 64;                  // PAIR_KW words of every row staged per step,
 constexpr int PAIR_LD = PAIR_KW + 4;         // rows 68 words apart in LDS: mask_intersections_kernel's layout (pp_proposals.hip has the bank arithmetic)
-constexpr int GF = PP_DET_GROUP_FIELDS;
 constexpr int MATCH_WAVES = 4;               // pp_det_match: independent waves of one workgroup, one (group, area range, threshold) each
-
-struct Group {
-    int d0, nd, g0, ng, off;
-};
-
-// Row g of the device group table.  The entry validated the host copy; a device copy that disagrees must not lead outside the
-// buffers: then the group is empty on both sides.
-__device__ __forceinline__ Group load_group(const int* __restrict__ groups, int n_groups, int g, int n_det, int n_gt, int n_pairs) {
-    Group r = {0, 0, 0, 0, 0};
-    if (g < 0 || g >= n_groups) return r;
-    const int* p = groups + (size_t)g * GF;
-    const int d0 = p[0], nd = p[1], g0 = p[2], ng = p[3], off = p[4];
-    if (d0 < 0 || nd < 0 || g0 < 0 || ng < 0 || off < 0 || nd > n_det - d0 || ng > n_gt - g0 ||
-        (long long)off + (long long)nd * ng > (long long)n_pairs)
-        return r;
-    r.d0 = d0, r.nd = nd, r.g0 = g0, r.ng = ng, r.off = off;
-    return r;
-}
+                                             // (Group, load_group and groups_ok: pp_det_group.h)
 
 // segm: inter = popcount(det row & gt row) over the words, iou = inter / (area_d + area_g - inter), for a crowd inter / area_d.  The
 // detections are the bit rows [0, n_det), the ground truths the rows [n_det, n_det + n_gt).  Staging as mask_intersections_kernel:
@@ -180,16 +163,6 @@ __global__ __launch_bounds__(MATCH_WAVES* WAVE) void det_match_kernel(const doub
             dt_ignore[drow + d] = m >= 0 ? mig : (da < lo || da > hi);
         }
     }
-}
-
-// The host copy of the group table: ranges inside the call's detections and ground truths, blocks inside the ragged arrays.
-bool groups_ok(const int* gh, int n_groups, int n_det, int n_gt, int n_pairs, int max_gt) {
-    for (int g = 0; g < n_groups; ++g) {
-        const int* p = gh + (size_t)g * GF;
-        if (p[0] < 0 || p[1] < 0 || p[2] < 0 || p[3] < 0 || p[4] < 0 || p[1] > n_det - p[0] || p[3] > n_gt - p[2] || p[3] > max_gt) return false;
-        if ((long long)p[4] + (long long)p[1] * p[3] > (long long)n_pairs) return false;
-    }
-    return true;
 }
 
 }  // namespace

@@ -432,6 +432,26 @@ def bop_csv_lines(scene_id, img_id, obj_ids, scores, preds_image, image_time, st
     return lines
 
 
+def suppress_duplicate_poses(rows, models, nms_dist=0.1):
+    """Drop the duplicate poses of an image's or a dataset's results (pose_detection_eval.pose_nms: per image and object, by descending
+    score, an estimate within nms_dist x diameter — MSSD, symmetries included — of an earlier KEPT one is dropped).  rows: the
+    `scene_id,im_id,obj_id,score,R,t,time` content bop_csv_lines prints, as a list of lines (several images' lists concatenated; a
+    header line is kept) or as evaluation.read_bop_results' dict; models: an evaluation.ObjectModels.  -> the kept lines, in order, or
+    the dict of the kept rows.  The project's own rule: nms_dist = 0.1 is not tuned and its effect on real data is unmeasured; no
+    default path of the pipeline calls this."""
+    from .evaluation import read_bop_results
+    from .pose_detection_eval import pose_nms
+
+    if isinstance(rows, dict):
+        keep = pose_nms(rows, models, nms_dist=nms_dist)
+        return {k: np.asarray(v)[keep] for k, v in rows.items()}
+    lines = list(rows)
+    data = [n for n, line in enumerate(lines) if line.strip() and not line.strip().startswith("scene_id")]   # read_bop_results' rule
+    kept = {data[k] for k in pose_nms(read_bop_results(lines), models, nms_dist=nms_dist).tolist()}
+    blank = set(range(len(lines))) - set(data)
+    return [line for n, line in enumerate(lines) if n in kept or n in blank]
+
+
 def refine_predictions(preds_image, models, obj_ids, K, depth, depth_scale=None, hypotheses="best", rank_by="inliers_ratio",
                        start="stage_3", **kw):
     """Depth refinement of one image's predictions (depth_refine.refine_poses_depth, ONE call for the whole image) -> a new
