@@ -6,69 +6,40 @@
 #include <limits.h>
 #include <math.h>
 #include "pp_common.h"
+#include "pp_bitrows_dev.h"
 #include "pp_det_group.h"
 #include "pp_reduce_dev.h"
 
 namespace {
 
 constexpr int WAVE = 64;
-constexpr int PAIR = PP_DET_TILE;            // a workgroup owns PAIR x PAIR (detection, ground truth) pairs of ONE group,
-constexpr int PAIR_Q = 4;                    // PAIR_Q threads per pair (segm),
-constexpr int PAIR_KW = 64;                  // PAIR_KW words of every row staged per step,
-constexpr int PAIR_LD = PAIR_KW + 4;         // rows 68 words apart in LDS: mask_intersections_kernel's layout (pp_proposals.hip has the bank arithmetic)
 constexpr int MATCH_WAVES = 4;               // pp_det_match: independent waves of one workgroup, one (group, area range, threshold) each
-                                             // (Group, load_group and groups_ok: pp_det_group.h)
+                                             // (Group, load_group, groups_ok: pp_det_group.h; PAIR, a workgroup's tile of ONE group: pp_bitrows_dev.h)
 
 // segm: inter = popcount(det row & gt row) over the words, iou = inter / (area_d + area_g - inter), for a crowd inter / area_d.  The
-// detections are the bit rows [0, n_det), the ground truths the rows [n_det, n_det + n_gt).  Staging as mask_intersections_kernel:
-// 64 words of the tile's 8 + 8 rows per step, the next step's loads in flight under the counting; the four threads of a pair take
-// the words k = 4 m + kq.  Rows past the group's sides and words past the row are 0; nothing of another group is read or written.
-__global__ __launch_bounds__(PAIR * PAIR * PAIR_Q) void det_overlaps_segm_kernel(
-    const unsigned* __restrict__ bits, const int* __restrict__ area, int words, int n_det, int n_gt, const int* __restrict__ groups,
-    int n_groups, const int* __restrict__ tiles, const unsigned char* __restrict__ gt_flags, int n_pairs, int* __restrict__ inter,
-    double* __restrict__ iou) {
-    __shared__ unsigned a[PAIR * PAIR_LD], b[PAIR * PAIR_LD];
-    const int tid = threadIdx.x, kq = tid % PAIR_Q, tj = (tid / PAIR_Q) % PAIR, ti = tid / (PAIR_Q * PAIR);
-    const int* tile = tiles + (size_t)blockIdx.x * 3;
-    Group G = load_group(groups, n_groups, tile[0], n_det, n_gt, n_pairs);
-    const int i0 = tile[1], j0 = tile[2];
-    if (i0 < 0 || j0 < 0) G.nd = G.ng = 0;                                   // (workgroup-uniform: every thread still meets the barriers)
-    int count = 0;
-    constexpr int PER = PAIR * PAIR_KW / (PAIR * PAIR * PAIR_Q);
-    unsigned ra[PER], rb[PER];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            const int e = tid + u * PAIR * PAIR * PAIR_Q, r = e / PAIR_KW, c = e % PAIR_KW;
-            const bool in = k0 + c < words;
-            ra[u] = in && i0 + r < G.nd ? bits[(size_t)(G.d0 + i0 + r) * words + k0 + c] : 0u;
-            rb[u] = in && j0 + r < G.ng ? bits[(size_t)(n_det + G.g0 + j0 + r) * words + k0 + c] : 0u;
-        }
-    };
-    fetch(0);
-    for (int k0 = 0; k0 < words; k0 += PAIR_KW) {
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            const int e = tid + u * PAIR * PAIR * PAIR_Q, r = e / PAIR_KW, c = e % PAIR_KW;
-            a[r * PAIR_LD + c] = ra[u];
-            b[r * PAIR_LD + c] = rb[u];
-        }
-        __syncthreads();
-        if (k0 + PAIR_KW < words) fetch(k0 + PAIR_KW);
-#pragma unroll
-        for (int k = 0; k < PAIR_KW; k += PAIR_Q) count += __popc(a[ti * PAIR_LD + k + kq] & b[tj * PAIR_LD + k + kq]);
-        __syncthreads();
+// detections are the bit rows [0, n_det), the ground truths the rows [n_det, n_det + n_gt): bitrow_tile_kernel (pp_bitrows_dev.h)
+// with the group's detections on one side and its ground truths on the other.  Nothing of another group is read or written.
+struct DetTile {
+    const int *__restrict__ area, *__restrict__ groups, *__restrict__ tiles;
+    const unsigned char* __restrict__ gt_flags;
+    int words, n_det, n_gt, n_groups, n_pairs;
+    int* __restrict__ inter;
+    double* __restrict__ iou;
+    __device__ long long sides(int& ri, int& i0, int& ni, int& rj, int& j0, int& nj) const {
+        const int* tile = tiles + (size_t)blockIdx.x * 3;
+        Group G = load_group(groups, n_groups, tile[0], n_det, n_gt, n_pairs);
+        i0 = tile[1], j0 = tile[2];
+        if (i0 < 0 || j0 < 0) G.nd = G.ng = i0 = j0 = 0;                      // (workgroup-uniform: every thread still meets the barriers)
+        ri = G.d0 + i0, ni = G.nd, rj = n_det + G.g0 + j0, nj = G.ng;
+        return G.off;
     }
-    count = wave_reduce_range<PAIR_Q / 2, 1>(count, op_sum{});                // the PAIR_Q threads of a pair (integers: any order)
-    if (kq == 0 && i0 + ti < G.nd && j0 + tj < G.ng) {
-        const int d = G.d0 + i0 + ti, g = G.g0 + j0 + tj;
-        const size_t at = (size_t)G.off + (size_t)(i0 + ti) * G.ng + j0 + tj;
-        const long long ad = area[d], ag = area[n_det + g];
-        const long long den = (gt_flags[g] & PP_DET_GT_CROWD) ? ad : ad + ag - count;
+    __device__ void store(int d, int g, size_t at, int count) const {         // (g: the ground truth's bit row, n_det + its index)
+        const long long ad = area[d], ag = area[g];
+        const long long den = (gt_flags[g - n_det] & PP_DET_GT_CROWD) ? ad : ad + ag - count;
         inter[at] = count;
         iou[at] = den > 0 ? (double)count / (double)den : 0.0;                // one IEEE division
     }
-}
+};
 
 // bbox: one thread per pair of the tile, float64, never contracted (the header has the expression).
 __global__ __launch_bounds__(PAIR * PAIR) void det_overlaps_bbox_kernel(const double* __restrict__ boxes, int n_det, int n_gt,
@@ -185,8 +156,8 @@ int pp_det_overlaps(const unsigned* bits, const int* area, int words, const doub
     }
     if (n_tiles == 0) return PP_OK;                                           // every group has an empty side: no pair, no launch
     if (bits)
-        hipLaunchKernelGGL(det_overlaps_segm_kernel, dim3(n_tiles), dim3(PAIR * PAIR * PAIR_Q), 0, (hipStream_t)stream, bits, area, words,
-                           n_det, n_gt, groups, n_groups, tiles, gt_flags, n_pairs, inter, iou);
+        hipLaunchKernelGGL(bitrow_tile_kernel<DetTile>, dim3(n_tiles), dim3(PAIR_THREADS), 0, (hipStream_t)stream, bits,
+                           DetTile{area, groups, tiles, gt_flags, words, n_det, n_gt, n_groups, n_pairs, inter, iou});
     else
         hipLaunchKernelGGL(det_overlaps_bbox_kernel, dim3(n_tiles), dim3(PAIR * PAIR), 0, (hipStream_t)stream, boxes, n_det, n_gt, groups,
                            n_groups, tiles, gt_flags, n_pairs, iou);

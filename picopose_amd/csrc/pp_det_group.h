@@ -36,5 +36,23 @@ inline bool groups_ok(const int* gh, int n_groups, int n_det, int n_gt, int n_pa
     return true;
 }
 
+// The row of pp_pose_nms, {first estimate, E_g, offset of the group's triangle of E_g (E_g - 1) / 2 pairs}, and THE CHECKS of a row, the
+// host copy's and the device copy's alike (as load_group: a device row that disagrees with the validated host copy gives an empty group).
+struct NmsGroup {
+    int e0, ne;
+    long long off;
+};
+
+__host__ __device__ __forceinline__ bool nms_row_ok(int e0, int ne, int off, int n_est, int n_tri) {
+    return !(e0 < 0 || ne < 0 || off < 0 || ne > n_est - e0 || ne > PP_POSE_MAX_GROUP ||
+             (long long)off + (long long)ne * (ne - 1) / 2 > (long long)n_tri);
+}
+
+__device__ __forceinline__ NmsGroup load_nms_group(const int* __restrict__ groups, int g, int n_est, int n_tri) {
+    const int* p = groups + (size_t)g * PP_POSE_NMS_FIELDS;
+    const int e0 = p[0], ne = p[1], off = p[2];
+    return nms_row_ok(e0, ne, off, n_est, n_tri) ? NmsGroup{e0, ne, off} : NmsGroup{0, 0, 0};
+}
+
 }  // namespace
 #endif

@@ -14,7 +14,6 @@ namespace {
 
 constexpr int WAVE = 64;
 constexpr int POSE_WAVES = 4;                // independent waves of one workgroup, one problem each
-constexpr int NF = PP_POSE_NMS_FIELDS;
 constexpr unsigned NONE = 0xffffffffu;       // "no candidate": the pattern of a NaN, which never qualifies
 
 // One wave per (group, metric, threshold); the waves of a workgroup share nothing.  Lane l owns the ground truths j = l + 64 k of
@@ -80,25 +79,8 @@ __global__ __launch_bounds__(POSE_WAVES* WAVE) void pose_match_kernel(const floa
     }
 }
 
-struct NmsGroup {
-    int e0, ne;
-    long long off;
-};
-
-// (as load_group: a device row that disagrees with the validated host copy gives an empty group)
-__device__ __forceinline__ NmsGroup load_nms_group(const int* __restrict__ groups, int g, int n_est, int n_tri) {
-    NmsGroup r = {0, 0, 0};
-    const int* p = groups + (size_t)g * NF;
-    const int e0 = p[0], ne = p[1], off = p[2];
-    if (e0 < 0 || ne < 0 || off < 0 || ne > n_est - e0 || ne > PP_POSE_MAX_GROUP ||
-        (long long)off + (long long)ne * (ne - 1) / 2 > (long long)n_tri)
-        return r;
-    r.e0 = e0, r.ne = ne, r.off = off;
-    return r;
-}
-
-// One wave per group.  Lane l owns the positions p = l + 64 k of the group's order; bit k of `kept` says that p was kept.  Candidate
-// j reads its j earlier partners, contiguous in the triangle, 64 at a time; one ballot per 64 says whether a kept one is near.
+// One wave per group (its row: pp_det_group.h).  Lane l owns the positions p = l + 64 k of the group's order; bit k of `kept` says that
+// p was kept.  Candidate j reads its j earlier partners, contiguous in the triangle, 64 at a time; one ballot per 64 says whether a kept one is near.
 __global__ __launch_bounds__(POSE_WAVES* WAVE) void pose_nms_kernel(const float* __restrict__ dist, int n_tri, const int* __restrict__ groups,
                                                                     int n_groups, int n_est, const double* __restrict__ limit,
                                                                     unsigned char* __restrict__ keep) {
@@ -145,10 +127,8 @@ int pp_pose_nms(const float* dist, int n_tri, const int* groups, const int* grou
     if (!dist || !groups || !groups_host || !limit || !limit_host || !keep) return PP_EINVAL;
     if (n_tri < 0 || n_est < 0 || n_groups <= 0) return PP_EINVAL;
     for (int g = 0; g < n_groups; ++g) {
-        const int* p = groups_host + (size_t)g * NF;
-        if (p[0] < 0 || p[1] < 0 || p[2] < 0 || p[1] > n_est - p[0] || p[1] > PP_POSE_MAX_GROUP) return PP_EINVAL;
-        if ((long long)p[2] + (long long)p[1] * (p[1] - 1) / 2 > (long long)n_tri) return PP_EINVAL;
-        if (!(limit_host[g] >= 0.0)) return PP_EINVAL;                        // (a NaN fails too)
+        const int* p = groups_host + (size_t)g * PP_POSE_NMS_FIELDS;
+        if (!nms_row_ok(p[0], p[1], p[2], n_est, n_tri) || !(limit_host[g] >= 0.0)) return PP_EINVAL;      // (a NaN limit fails too)
     }
     hipLaunchKernelGGL(pose_nms_kernel, dim3((unsigned)((n_groups + POSE_WAVES - 1) / POSE_WAVES)), dim3(POSE_WAVES * WAVE), 0,
                        (hipStream_t)stream, dist, n_tri, groups, n_groups, n_est, limit, keep);

@@ -6,6 +6,7 @@
 #include <limits.h>
 #include <math.h>
 #include "pp_common.h"
+#include "pp_bitrows_dev.h"
 #include "pp_reduce_dev.h"
 #include "pp_runs_dev.h"
 
@@ -16,10 +17,6 @@ constexpr int MATCH_P = PP_MATCH_TILE;       // proposals of one workgroup
 constexpr int MATCH_WAVES = 4;
 constexpr int MATCH_CH = PP_MATCH_MAX_C / 4 / WAVE;   // 16-byte chunks of a row that one lane owns, at most
 constexpr int MATCH_K = PP_MATCH_MAX_TOPK;   // entries of a top-k list
-constexpr int PAIR = 8;                      // pp_mask_intersections: a workgroup owns PAIR x PAIR pairs,
-constexpr int PAIR_Q = 4;                    // PAIR_Q threads per pair
-constexpr int PAIR_KW = 64;                  // words of every row staged per step
-constexpr int PAIR_LD = PAIR_KW + 4;         // row stride in LDS (the kernel's comment has the bank arithmetic)
 
 // THE DOT-PRODUCT ORDER (the header states it): lane l owns the 16-byte chunks l, l + 64, ... of a row and adds their products
 // in ascending element order with one fma each, starting from 0; the 64 lane sums are then folded by a butterfly over the lane
@@ -260,44 +257,16 @@ __global__ __launch_bounds__(256) void rle_pack_bits_kernel(const int* __restric
     }
 }
 
-// inter[i][j] = popcount(bits[i] & bits[j]): a workgroup owns PAIR x PAIR pairs and stages PAIR_KW words of its rows i and rows j per
-// step; the four threads of a pair take the words k = 4 m + kq and add their counts up at the end (integers: any order).  A half-wave
-// reads one row i (four addresses: broadcasts) and eight rows j, PAIR_LD = 68 words apart: word 68 j + 4 m + kq lies on bank
-// (4 j + kq) mod 32 for j < 8, kq < 4: 32 different banks.
-__global__ __launch_bounds__(PAIR * PAIR * PAIR_Q) void mask_intersections_kernel(const unsigned* __restrict__ bits, int n, int words,
-                                                                                  int* __restrict__ inter) {
-    __shared__ unsigned a[PAIR * PAIR_LD], b[PAIR * PAIR_LD];
-    const int tid = threadIdx.x, kq = tid % PAIR_Q, tj = (tid / PAIR_Q) % PAIR, ti = tid / (PAIR_Q * PAIR);
-    const int i0 = blockIdx.y * PAIR, j0 = blockIdx.x * PAIR;
-    int count = 0;
-    constexpr int PER = PAIR * PAIR_KW / (PAIR * PAIR * PAIR_Q);             // staged words of a and of b per thread and step
-    unsigned ra[PER], rb[PER];
-    auto fetch = [&](int k0) {                                               // a step's words into registers: rows past n and words past the row are 0
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            const int e = tid + u * PAIR * PAIR * PAIR_Q, r = e / PAIR_KW, c = e % PAIR_KW;
-            const bool in = k0 + c < words;
-            ra[u] = in && i0 + r < n ? bits[(size_t)(i0 + r) * words + k0 + c] : 0u;
-            rb[u] = in && j0 + r < n ? bits[(size_t)(j0 + r) * words + k0 + c] : 0u;
-        }
-    };
-    fetch(0);
-    for (int k0 = 0; k0 < words; k0 += PAIR_KW) {
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            const int e = tid + u * PAIR * PAIR * PAIR_Q, r = e / PAIR_KW, c = e % PAIR_KW;
-            a[r * PAIR_LD + c] = ra[u];
-            b[r * PAIR_LD + c] = rb[u];
-        }
-        __syncthreads();
-        if (k0 + PAIR_KW < words) fetch(k0 + PAIR_KW);                       // the next step's loads fly under this step's counting
-#pragma unroll
-        for (int k = 0; k < PAIR_KW; k += PAIR_Q) count += __popc(a[ti * PAIR_LD + k + kq] & b[tj * PAIR_LD + k + kq]);
-        __syncthreads();
+// inter[i][j] = popcount(bits[i] & bits[j]): bitrow_tile_kernel (pp_bitrows_dev.h) with both sides in the one list of n rows.
+struct MaskTile {
+    int n, words;
+    int* __restrict__ inter;
+    __device__ long long sides(int& ri, int& i0, int& ni, int& rj, int& j0, int& nj) const {
+        ri = i0 = blockIdx.y * PAIR, rj = j0 = blockIdx.x * PAIR, ni = nj = n;
+        return 0;
     }
-    count = wave_reduce_range<PAIR_Q / 2, 1>(count, op_sum{});               // the PAIR_Q threads of a pair (integers: any order)
-    if (kq == 0 && i0 + ti < n && j0 + tj < n) inter[(size_t)(i0 + ti) * n + j0 + tj] = count;
-}
+    __device__ void store(int, int, size_t at, int count) const { inter[at] = count; }
+};
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
@@ -342,7 +311,7 @@ int pp_rle_pack_bits(const int* run_ends, int n_runs, const int* run_offset, con
 int pp_mask_intersections(const unsigned* bits, int n, int words, int* inter, void* stream) {
     if (!bits || !inter || n <= 0 || n > PP_MASK_MAX_N || words <= 0) return PP_EINVAL;
     const int t = (n + PAIR - 1) / PAIR;
-    hipLaunchKernelGGL(mask_intersections_kernel, dim3(t, t), dim3(PAIR * PAIR * PAIR_Q), 0, (hipStream_t)stream, bits, n, words, inter);
+    hipLaunchKernelGGL(bitrow_tile_kernel<MaskTile>, dim3(t, t), dim3(PAIR_THREADS), 0, (hipStream_t)stream, bits, MaskTile{n, words, inter});
     return pp_last_launch();
 }
 

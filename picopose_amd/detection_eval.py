@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import scoring
 from .masks import MAX_MASKS, RunTable, check_frame, rle_counts, rle_from_mask, run_ends
 from . import scene_gt as sg
 
@@ -24,7 +25,7 @@ IOU_TYPES = ("segm", "bbox")
 IOU_THRS = np.linspace(.5, .95, 10)
 AREA_RANGES = ((0.0, 1e10), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e10))      # COCO's all, small, medium, large
 MAX_DETS = (1, 10, 100)
-REC_THRS = np.linspace(0, 1, 101)
+REC_THRS = scoring.REC_THRS
 NAMES = ("AP", "AP50", "AP75", "APs", "APm", "APl", "AR1", "AR10", "AR100", "ARs", "ARm", "ARl")
 DEFAULT_WORKSPACE_BYTES = 256 << 20
 TILE = _lib.PP_DET_TILE
@@ -186,22 +187,15 @@ def _tiles(groups):
 def _run_chunk(dev, segm, hw, runs, boxes, groups, flags, det_area, gt_area, ranges, thrs, timings=None):
     """One chunk on the device: (pack,) overlaps, match -> (inter or None, iou, dt_match, dt_ignore, gt_match, gt_ignore) as numpy.
     timings: a dict that receives the device seconds of the pack, overlaps and match launches (event pairs on the current stream)."""
-    marks = {}
-
-    def mark(name):
-        if timings is not None:
-            marks.setdefault(name, []).append(torch.cuda.Event(enable_timing=True))
-            marks[name][-1].record()
-
+    mark, finish = scoring.device_marks(timings)
     n_groups = len(groups)
     n_det, n_gt = len(det_area), len(gt_area)
     n_pairs = int((groups[:, 1] * groups[:, 3]).sum())
-    if n_pairs >= 2 ** 31:
-        raise ValueError(f"{n_pairs} pairs in one chunk: more than 32-bit block offsets hold")
+    scoring.check_offsets(n_pairs, "chunk")
     A, T = len(ranges), len(thrs)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+    up = scoring.uploader(dev)
     tiles = _tiles(groups)
-    groups_d, flags_d = up(groups.ravel()), up(flags if n_gt else np.zeros(1, np.uint8))
+    groups_d, flags_d = up(groups.ravel()), up(flags, side=True)
     tiles_d = up(tiles.ravel()) if len(tiles) else None
     iou = torch.zeros(max(n_pairs, 1), dtype=torch.float64, device=dev)
     inter = bits = area = boxes_d = None
@@ -219,25 +213,20 @@ def _run_chunk(dev, segm, hw, runs, boxes, groups, flags, det_area, gt_area, ran
     _lib.call("pp_det_overlaps", bits, area, words, boxes_d, n_det, n_gt, groups_d, groups, n_groups, tiles_d, tiles, len(tiles), flags_d,
               n_pairs, inter, iou)
     mark("overlaps")
-    da_d, ga_d = up(det_area if n_det else np.zeros(1)), up(gt_area if n_gt else np.zeros(1))
+    da_d, ga_d = up(det_area, side=True), up(gt_area, side=True)
     ranges_d, thrs_d = up(ranges.ravel()), up(thrs)
     dt_match = torch.full((A, T, max(n_det, 1)), -1, dtype=torch.int32, device=dev)
     dt_ignore = torch.zeros((A, T, max(n_det, 1)), dtype=torch.uint8, device=dev)
     gt_match = torch.full((A, T, max(n_gt, 1)), -1, dtype=torch.int32, device=dev)
     gt_ignore = torch.zeros((A, max(n_gt, 1)), dtype=torch.uint8, device=dev)
     mark("match")
-    # (the kernel indexes the tables with n_det and n_gt: they are allocated with exactly that width unless a side is empty,
-    # and an empty side is never indexed)
     _lib.call("pp_det_match", iou, n_pairs, groups_d, groups, n_groups, n_det, n_gt, da_d, ga_d, flags_d, ranges_d, ranges, A, thrs_d, thrs, T,
               dt_match, dt_ignore, gt_match, gt_ignore)
     mark("match")
-    host = lambda t: t.cpu().numpy()      # noqa: E731
-    result = (host(inter)[:n_pairs] if segm else None, host(iou)[:n_pairs], host(dt_match)[:, :, :n_det], host(dt_ignore)[:, :, :n_det],
-            host(gt_match)[:, :, :n_gt], host(gt_ignore)[:, :n_gt])
-    if timings is not None:                                                   # (the downloads above waited for the stream)
-        for name, (start, end) in marks.items():
-            timings[name] = timings.get(name, 0.0) + start.elapsed_time(end) * 1e-3
-    return result
+    finish()
+    host = lambda t, n: t.cpu().numpy()[..., :n]      # noqa: E731
+    return (host(inter, n_pairs) if segm else None, host(iou, n_pairs), host(dt_match, n_det), host(dt_ignore, n_det), host(gt_match, n_gt),
+            host(gt_ignore, n_gt))
 
 
 def match_detections(detections, annotations, iou_type="segm", iou_thrs=None, area_ranges=None, max_dets=MAX_DETS, class_agnostic=False,
@@ -277,23 +266,15 @@ def match_detections(detections, annotations, iou_type="segm", iou_thrs=None, ar
     A, T = len(ranges), len(thrs)
     keys = sorted(members)
     g_img, g_cat = np.array([k[0] for k in keys], np.int64), np.array([k[1] for k in keys], np.int64)
-    det_lists, gt_lists = [], []
-    for k in keys:
-        d, g = (np.array(m, np.int64) for m in members[k])
-        if len(g) > MAX_GT:
-            raise ValueError(f"image {images[k[0]]}, category {cats[k[1]]}: {len(g)} annotations, more than the {MAX_GT} of one group")
-        det_lists.append(d[np.argsort(-D.score[d], kind="stable")][:cut])
-        gt_lists.append(g)
-    nd, ng = np.array([len(d) for d in det_lists], np.int64), np.array([len(g) for g in gt_lists], np.int64)
-    first = lambda c: np.cumsum(c) - c      # noqa: E731
-    d0, g0, p0 = first(nd), first(ng), first(nd * ng)
-    n_det, n_gt, n_pairs = int(nd.sum()), int(ng.sum()), int((nd * ng).sum())
-    det_index = np.concatenate(det_lists) if n_det else np.zeros(0, np.int64)
-    gt_index = np.concatenate(gt_lists) if n_gt else np.zeros(0, np.int64)
+    sides = [[np.array(m, np.int64) for m in members[k]] for k in keys]
+    det_lists, gt_lists = [d[np.argsort(-D.score[d], kind="stable")][:cut] for d, _ in sides], [g for _, g in sides]
+    group_det, group_gt, p0, det_index, gt_index, n_pairs = scoring.plan_groups([(images[i], cats[c]) for i, c in keys], det_lists, gt_lists,
+                                                                                MAX_GT, "category", "annotations")
+    (d0, nd), (g0, ng), n_det, n_gt = group_det.T, group_gt.T, len(det_index), len(gt_index)
     out = {"iou_type": iou_type, "iou_thrs": thrs, "area_ranges": ranges, "max_dets": max_dets, "images": images, "categories": cats,
-           "group_image": g_img, "group_category": g_cat, "group_det": np.stack([d0, nd], axis=1).reshape(-1, 2),
-           "group_gt": np.stack([g0, ng], axis=1).reshape(-1, 2), "group_pair": p0, "det_index": det_index, "gt_index": gt_index,
-           "det_score": D.score[det_index], "inter": np.zeros(n_pairs, np.int32) if segm else None, "iou": np.zeros(n_pairs, np.float64),
+           "group_image": g_img, "group_category": g_cat, "group_det": group_det, "group_gt": group_gt, "group_pair": p0,
+           "det_index": det_index, "gt_index": gt_index, "det_score": D.score[det_index],
+           "inter": np.zeros(n_pairs, np.int32) if segm else None, "iou": np.zeros(n_pairs, np.float64),
            "dt_match": np.full((A, T, n_det), -1, np.int32), "dt_ignore": np.zeros((A, T, n_det), np.uint8),
            "gt_match": np.full((A, T, n_gt), -1, np.int32), "gt_ignore": np.zeros((A, n_gt), np.uint8), "n_chunks": 0}
     if not keys:
@@ -322,18 +303,17 @@ def match_detections(detections, annotations, iou_type="segm", iou_thrs=None, ar
         c[1] += cost
         c[2] += masks
     chunks += [(size, c[0]) for size, c in cur.items()]
-    if torch.device(device).type != "cuda":
-        raise _lib.PicoPoseHipError("picopose_amd runs on the GPU only: match_detections needs a CUDA(HIP) device")
+    dev = scoring.require_cuda(device, "match_detections")
     for size, qs in chunks:
         qs = np.array(qs, np.int64)
         cd, cg = nd[qs], ng[qs]
-        groups = np.ascontiguousarray(np.stack([first(cd), cd, first(cg), cg, first(cd * cg)], axis=1), dtype=np.int32)
+        groups = scoring.group_rows(*(np.stack([scoring.first(c), c], axis=1) for c in (cd, cg)), scoring.first(cd * cg))
         span = lambda s, c: np.concatenate([np.arange(a, a + b) for a, b in zip(s, c)]) if c.sum() else np.zeros(0, np.int64)  # noqa: E731
         dpos, gpos, ppos = span(d0[qs], cd), span(g0[qs], cg), span(p0[qs], cd * cg)
         di, gi = det_index[dpos], gt_index[gpos]
         runs = [D.runs[n] for n in di] + [G.runs[n] for n in gi] if segm else None
         boxes = None if segm else np.concatenate([D.box[di], G.box[gi]])
-        inter, iou, dtm, dtig, gtm, gtig = _run_chunk(torch.device(device), segm, size[0] * size[1] if segm else 0, runs, boxes, groups,
+        inter, iou, dtm, dtig, gtm, gtig = _run_chunk(dev, segm, size[0] * size[1] if segm else 0, runs, boxes, groups,
                                                       G.flags[gi], det_area[dpos], G.area[gi], ranges, thrs, timings)
         if segm:
             out["inter"][ppos] = inter
@@ -366,25 +346,8 @@ def accumulate(matches):
             for mi, md in enumerate(max_dets):
                 sel = np.concatenate([np.arange(s, s + min(n, md)) for s, n in m["group_det"][rows]] + [np.zeros(0, np.int64)]).astype(np.int64)
                 sel = sel[np.argsort(-m["det_score"][sel], kind="mergesort")]
-                matched, ign = m["dt_match"][a][:, sel] >= 0, m["dt_ignore"][a][:, sel] != 0
-                tps = np.cumsum(matched & ~ign, axis=1).astype(np.float64)
-                fps = np.cumsum(~matched & ~ign, axis=1).astype(np.float64)
-                nd = len(sel)
-                rcs = tps / npig
-                prs = tps / (fps + tps + np.spacing(1))
-                prs = np.maximum.accumulate(prs[:, ::-1], axis=1)[:, ::-1]        # non-increasing from the right
-                recall[:, k, a, mi] = rcs[:, -1] if nd else 0
-                for t in range(T):
-                    ind = np.searchsorted(rcs[t], REC_THRS, side="left")
-                    q = np.zeros(101)
-                    q[ind < nd] = prs[t, ind[ind < nd]]
-                    precision[t, :, k, a, mi] = q
+                precision[:, :, k, a, mi], recall[:, k, a, mi] = scoring.pr_curve(m["dt_match"][a][:, sel] >= 0, m["dt_ignore"][a][:, sel] != 0, npig)
     return {"precision": precision, "recall": recall, "iou_thrs": thrs, "area_ranges": ranges, "max_dets": max_dets, "categories": cats}
-
-
-def _mean(x):
-    x = x[x > -1]
-    return float(np.mean(x)) if x.size else -1.0
 
 
 def summarize(acc):
@@ -399,13 +362,13 @@ def summarize(acc):
         if a >= A:
             return -1.0
         t = slice(None) if thr is None else np.where(thrs == thr)[0]
-        return _mean(p[t, :, :, a, M - 1])
+        return scoring.mean_valid(p[t, :, :, a, M - 1])
 
     def ar(a, mi):
-        return _mean(r[:, :, a, mi]) if a < A and mi < M else -1.0
+        return scoring.mean_valid(r[:, :, a, mi]) if a < A and mi < M else -1.0
 
     out = dict(zip(NAMES, [ap(0), ap(0, .5), ap(0, .75), ap(1), ap(2), ap(3), ar(0, 0), ar(0, 1), ar(0, 2), ar(1, M - 1), ar(2, M - 1), ar(3, M - 1)]))
-    out["per_object_AP"] = {c: _mean(p[:, :, k, 0, M - 1]) for k, c in enumerate(acc["categories"])}
+    out["per_object_AP"] = {c: scoring.mean_valid(p[:, :, k, 0, M - 1]) for k, c in enumerate(acc["categories"])}
     return out
 
 

@@ -21,15 +21,15 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import scoring
 from .evaluation import DEFAULT_WORKSPACE_BYTES, MSPD_THRESHOLDS, MSSD_THRESHOLDS, ObjectModels, _json, pose_errors
 
 MAX_GROUP = _lib.PP_POSE_MAX_GROUP
 MAX_METRICS = _lib.PP_POSE_MAX_METRICS
 METRICS = ("mssd", "mspd")
-REC_THRS = np.linspace(0, 1, 101)
+REC_THRS = scoring.REC_THRS
 MAX_PER_IMAGE = 100
 _EST_KEYS = ("scene_id", "im_id", "obj_id", "score", "R", "t")
-_first = lambda c: np.cumsum(c) - c      # noqa: E731
 
 
 def read_image_targets(path):
@@ -168,41 +168,16 @@ def plan_groups(estimates, annotations, images=None, max_per_image=MAX_PER_IMAGE
     img_of, obj_of = {k: i for i, k in enumerate(img_list)}, {o: i for i, o in enumerate(obj_list)}
     est_lists = [np.array(est_groups.get(k, []), np.int64) for k in gkeys]
     gt_lists = [np.array(gt_groups.get(k, []), np.int64) for k in gkeys]
-    for k, g in zip(gkeys, gt_lists):
-        if len(g) > MAX_GROUP:
-            raise ValueError(f"image {k[0]}, object {k[1]}: {len(g)} ground truths, more than the {MAX_GROUP} of one group")
-    ne, ng = np.array([len(e) for e in est_lists], np.int64), np.array([len(g) for g in gt_lists], np.int64)
-    n_pairs = int((ne * ng).sum())
-    if max(n_pairs, int(ne.sum()), int(ng.sum())) >= 2 ** 31:
-        raise ValueError(f"{n_pairs} pairs in one call: more than 32-bit block offsets hold")
-    est_index = np.concatenate(est_lists + [np.zeros(0, np.int64)])
-    gt_index = np.concatenate(gt_lists + [np.zeros(0, np.int64)])
+    group_est, group_gt, group_pair, est_index, gt_index, n_pairs = scoring.plan_groups(gkeys, est_lists, gt_lists, MAX_GROUP, "object",
+                                                                                        "ground truths")
+    scoring.check_offsets(n_pairs, "call", max(len(est_index), len(gt_index)))
     pair_est = np.concatenate([np.repeat(e, len(g)) for e, g in zip(est_lists, gt_lists)] + [np.zeros(0, np.int64)])
     pair_gt = np.concatenate([np.tile(g, len(e)) for e, g in zip(est_lists, gt_lists)] + [np.zeros(0, np.int64)])
     return {"images": img_list, "objects": obj_list, "group_image": np.array([img_of[k[0]] for k in gkeys], np.int64),
-            "group_object": np.array([obj_of[k[1]] for k in gkeys], np.int64),
-            "group_est": np.stack([_first(ne), ne], axis=1).reshape(-1, 2), "group_gt": np.stack([_first(ng), ng], axis=1).reshape(-1, 2),
-            "group_pair": _first(ne * ng), "est_index": est_index, "est_score": score[est_index], "gt_index": gt_index,
+            "group_object": np.array([obj_of[k[1]] for k in gkeys], np.int64), "group_est": group_est, "group_gt": group_gt,
+            "group_pair": group_pair, "est_index": est_index, "est_score": score[est_index], "gt_index": gt_index,
             "gt_ignore": np.asarray(annotations["ignore"]).astype(np.uint8)[gt_index], "pair_est": pair_est, "pair_gt": pair_gt,
             "n_pairs": n_pairs}
-
-
-def _marks(timings):
-    """-> (mark(name), finish()): event pairs on the current stream, summed into `timings` as device seconds (None: nothing recorded)."""
-    marks = {}
-
-    def mark(name):
-        if timings is not None:
-            marks.setdefault(name, []).append(torch.cuda.Event(enable_timing=True))
-            marks[name][-1].record()
-
-    def finish():
-        if timings is not None:
-            torch.cuda.synchronize()
-            for name, (start, end) in marks.items():
-                timings[name] = timings.get(name, 0.0) + start.elapsed_time(end) * 1e-3
-
-    return mark, finish
 
 
 def match_pose_errors(plan, errors, limits, device="cuda", timings=None):
@@ -233,21 +208,17 @@ def match_pose_errors(plan, errors, limits, device="cuda", timings=None):
            "gt_match": np.full((M, T, n_gt), -1, np.int32)}
     if n_groups == 0:
         return out
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise _lib.PicoPoseHipError("picopose_amd runs on the GPU only: match_pose_errors needs a CUDA(HIP) device")
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
-    groups = np.ascontiguousarray(np.concatenate([plan["group_est"], plan["group_gt"], plan["group_pair"][:, None]], axis=1), dtype=np.int32)
+    dev = scoring.require_cuda(device, "match_pose_errors")
+    up = scoring.uploader(dev)
+    groups = scoring.group_rows(plan["group_est"], plan["group_gt"], plan["group_pair"])
     err_d = (errors.to(dev) if is_tensor else up(errors)).contiguous()
     if n_pairs == 0:
         err_d = torch.zeros(1, dtype=torch.float32, device=dev)
-    groups_d, lim_d = up(groups.ravel()), up(lim.ravel())
-    ign_d = up(plan["gt_ignore"] if n_gt else np.zeros(1, np.uint8))
-    # (the kernel indexes the tables with n_est and n_gt: an empty side is never indexed)
+    groups_d, lim_d, ign_d = up(groups.ravel()), up(lim.ravel()), up(plan["gt_ignore"], side=True)
     em = torch.full((M, T, max(n_est, 1)), -1, dtype=torch.int32, device=dev)
     ei = torch.zeros((M, T, max(n_est, 1)), dtype=torch.uint8, device=dev)
     gm = torch.full((M, T, max(n_gt, 1)), -1, dtype=torch.int32, device=dev)
-    mark, finish = _marks(timings)
+    mark, finish = scoring.device_marks(timings)
     mark("match")
     _lib.call("pp_pose_match", err_d, M, n_pairs, groups_d, groups, n_groups, n_est, n_gt, ign_d, lim_d, lim, T, em, ei, gm)
     mark("match")
@@ -305,7 +276,7 @@ def match_poses(estimates, annotations, models, cameras, image_width=640, thresh
         K[i] = cam_of[(s, im)]
     diam = np.array([models.diameter(plan["objects"][o]) for o in plan["group_object"]], dtype=np.float64)
     limits = np.stack([diam[:, None] * th[0][None], np.broadcast_to(th[1][None] * (float(image_width) / 640.0), (len(diam), th.shape[1]))], axis=1)
-    mark, finish = _marks(timings if n else None)
+    mark, finish = scoring.device_marks(timings if n else None)
     mark("errors")
     err = pose_errors(models, np.asarray(estimates["obj_id"])[pe], np.asarray(estimates["R"], dtype=np.float64)[pe],
                       np.asarray(estimates["t"], dtype=np.float64)[pe], np.asarray(annotations["R"])[pg], np.asarray(annotations["t"])[pg],
@@ -324,9 +295,7 @@ def match_poses(estimates, annotations, models, cameras, image_width=640, thresh
 def accumulate(matches):
     """match_poses' result (or a plan plus `match_pose_errors`' tables) -> {"precision" (M, T, 101, K), "recall" (M, T, K)} float64, K the
     objects, plus "objects" and "metrics": per object, metric and threshold the estimates of all images, sorted by descending score
-    (mergesort); tp / fp are cumulative sums over the not-ignored estimates, rc = tp / npig, pr = tp / (tp + fp + spacing(1)), pr made
-    non-increasing from the right and sampled at np.linspace(0, 1, 101) by searchsorted(rc, r, "left"); recall = rc[-1] (0 without
-    estimates).  An object without a non-ignored ground truth stays -1."""
+    (mergesort), through `scoring.pr_curve` (recall: 0 without estimates).  An object without a non-ignored ground truth stays -1."""
     m = matches
     M, T = m["est_match"].shape[:2]
     objects = m["objects"]
@@ -339,26 +308,9 @@ def accumulate(matches):
             continue
         sel = span(m["group_est"][rows])
         sel = sel[np.argsort(-m["est_score"][sel], kind="mergesort")]
-        nd = len(sel)
         for mi in range(M):
-            matched, ign = m["est_match"][mi][:, sel] >= 0, m["est_ignore"][mi][:, sel] != 0
-            tps = np.cumsum(matched & ~ign, axis=1).astype(np.float64)
-            fps = np.cumsum(~matched & ~ign, axis=1).astype(np.float64)
-            rcs = tps / npig
-            prs = tps / (fps + tps + np.spacing(1))
-            prs = np.maximum.accumulate(prs[:, ::-1], axis=1)[:, ::-1]        # non-increasing from the right
-            recall[mi, :, k] = rcs[:, -1] if nd else 0
-            for t in range(T):
-                ind = np.searchsorted(rcs[t], REC_THRS, side="left")
-                q = np.zeros(101)
-                q[ind < nd] = prs[t, ind[ind < nd]]
-                precision[mi, t, :, k] = q
+            precision[mi, :, :, k], recall[mi, :, k] = scoring.pr_curve(m["est_match"][mi][:, sel] >= 0, m["est_ignore"][mi][:, sel] != 0, npig)
     return {"precision": precision, "recall": recall, "objects": objects, "metrics": tuple(m.get("metrics", METRICS[:M]))}
-
-
-def _mean(x):
-    x = x[x > -1]
-    return float(np.mean(x)) if x.size else -1.0
 
 
 def summarize(acc):
@@ -371,7 +323,7 @@ def summarize(acc):
     cell = np.array([[float(np.mean(p[mi, :, :, k])) if p.shape[1] and np.all(p[mi, :, :, k] > -1) else -1.0 for k in range(K)]
                      for mi in range(len(names))]).reshape(len(names), K)
     both = lambda v: float(np.mean(v)) if all(x > -1 for x in v) else -1.0      # noqa: E731
-    out = {n: _mean(cell[mi]) for mi, n in enumerate(names)}
+    out = {n: scoring.mean_valid(cell[mi]) for mi, n in enumerate(names)}
     out["AP"] = both([out[n] for n in names])
     out["per_object"] = {o: dict({n: float(cell[mi, k]) for mi, n in enumerate(names)}, AP=both(cell[:, k].tolist()))
                          for k, o in enumerate(acc["objects"])}
@@ -395,11 +347,8 @@ def plan_nms(estimates, images=None):
     groups = _grouped_estimates(keys, obj, score, _image_set(images), None)
     gkeys = sorted(groups)
     lists = [np.array(groups[k], np.int64) for k in gkeys]
-    for k, e in zip(gkeys, lists):
-        if len(e) > MAX_GROUP:
-            raise ValueError(f"image {k[0]}, object {k[1]}: {len(e)} estimates, more than the {MAX_GROUP} of one group")
-    ne = np.array([len(e) for e in lists], np.int64)
-    tri = ne * (ne - 1) // 2
+    group_est, est_index = scoring.axis(gkeys, lists, MAX_GROUP, "object", "estimates")
+    tri = group_est[:, 1] * (group_est[:, 1] - 1) // 2
     if int(tri.sum()) >= 2 ** 31:
         raise ValueError(f"{int(tri.sum())} pairs in one call: more than 32-bit offsets hold")
     early, late = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
@@ -407,8 +356,8 @@ def plan_nms(estimates, images=None):
         j, i = np.tril_indices(len(e), -1)                                     # row-major over j, i < j: offset j (j - 1) / 2 + i
         early.append(e[i])
         late.append(e[j])
-    return {"group_est": np.stack([_first(ne), ne], axis=1).reshape(-1, 2), "group_tri": _first(tri), "group_obj": np.array([k[1] for k in gkeys], np.int64),
-            "est_index": np.concatenate(lists + [np.zeros(0, np.int64)]), "tri_early": np.concatenate(early), "tri_late": np.concatenate(late),
+    return {"group_est": group_est, "group_tri": scoring.first(tri), "group_obj": np.array([k[1] for k in gkeys], np.int64),
+            "est_index": est_index, "tri_early": np.concatenate(early), "tri_late": np.concatenate(late),
             "n_tri": int(tri.sum())}
 
 
@@ -425,15 +374,13 @@ def nms_walk(plan, dist, limit, device="cuda", timings=None):
         raise ValueError(f"dist must be (n_tri = {n_tri},) float32, got {dist.dtype} {tuple(dist.shape)}")
     if n_groups == 0:
         return np.zeros(0, np.uint8)
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise _lib.PicoPoseHipError("picopose_amd runs on the GPU only: nms_walk needs a CUDA(HIP) device")
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+    dev = scoring.require_cuda(device, "nms_walk")
+    up = scoring.uploader(dev)
     groups = np.ascontiguousarray(np.concatenate([plan["group_est"], plan["group_tri"][:, None]], axis=1), dtype=np.int32)
     dist_d = (dist.to(dev) if is_tensor else up(dist)).contiguous() if n_tri else torch.zeros(1, dtype=torch.float32, device=dev)
     groups_d, lim_d = up(groups.ravel()), up(lim)
     keep = torch.zeros(n_est, dtype=torch.uint8, device=dev)
-    mark, finish = _marks(timings)
+    mark, finish = scoring.device_marks(timings)
     mark("nms")
     _lib.call("pp_pose_nms", dist_d, n_tri, groups_d, groups, n_groups, n_est, lim_d, lim, keep)
     mark("nms")
@@ -459,7 +406,7 @@ def pose_nms(estimates, models, nms_dist=0.1, images=None, device="cuda", timing
         return np.zeros(0, np.int64)
     R, t = np.asarray(estimates["R"], dtype=np.float64), np.asarray(estimates["t"], dtype=np.float64)
     i, j = plan["tri_early"], plan["tri_late"]
-    mark, finish = _marks(timings if len(i) else None)
+    mark, finish = scoring.device_marks(timings if len(i) else None)
     mark("nms_errors")
     dist = pose_errors(models, np.asarray(estimates["obj_id"])[j], R[j], t[j], R[i], t[i], kinds=("mssd",))["mssd"]
     mark("nms_errors")

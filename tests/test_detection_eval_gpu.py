@@ -88,6 +88,23 @@ def test_thresholds_crowds_and_twins_on_the_device():
 
 
 @gpu
+def test_segm_overlaps_over_a_second_part_filled_staging_step():
+    """A 48 x 64 frame is 96 words: the segm overlaps kernel stages 64 words per step, so it runs a second step, part-filled (the
+    frames of the random case are 15 and 34 words: one step).  9 detections against 3 ground truths and 1 against 9: both sides
+    cross a tile edge of 8.  Counts are integers and an IoU is one division: no tolerance."""
+    dets, anns = eo.image_case(np.random.default_rng(4), 48, 64, 1, 1, {1: (9, 3), 2: (1, 9)})
+    ref = eo.match(dets, anns)
+    # the case is worth its name: a share of the intersecting pixels lies in the words 64 .. 95, the pixels 2048 and up of the run order
+    late = [eo.do.decode(r["segmentation"]).ravel(order="F")[2048:] > 0 for r in dets + anns]
+    pairs = [(i, len(dets) + j) for i, d in enumerate(dets) for j, a in enumerate(anns) if d["category_id"] == a["category_id"]]
+    second = sum(int((late[i] & late[j]).sum()) for i, j in pairs)
+    assert (ref["inter"] > 0).sum() >= 20 and 0 < second < ref["inter"].sum() < 2 * second
+    got = de.match_detections(dets, anns)
+    assert got["n_chunks"] == 1 and got["inter"].shape == (9 * 3 + 1 * 9,)
+    _assert_tables_equal(got, ref)
+
+
+@gpu
 def test_closed_loop_from_scene_ground_truth_to_the_twelve_numbers():
     """Two instances of the 16-sample plate (one mesh under two object ids: with one category per instance AR1 is 1 as well) in a
     40 x 48 frame, composite visibility: the ground truth's own masks as detections score 1;
