@@ -973,11 +973,11 @@ int pp_render_views(const float* vertices, int n_vertices, const int* faces, con
  *      with c_yx the texels as floats: a = c00 + fx (c01 - c00), b = c10 + fx (c11 - c10), val = a + fy (b - a),
  *      out = min(255, max(0, floorf(val + 0.5))); alpha = 255.  A coordinate that is not finite (UVs that are, or overflow) reads
  *      texels inside the level and gives an unspecified colour, never a fault.
- *  T6. OUT OF SCOPE: anisotropic filtering and trilinear blending between levels (one level per face, chosen by area); multisampled
- *      edges (the reference enables 4x MSAA; silhouettes here are single-sampled as in item 5); clamp and mirror wrap modes;
- *      texture alpha (a texel's alpha is ignored: convert to RGB first); more than one texture per mesh.  (Shading is THE SHADING
- *      CONTRACT below; what it leaves out is S9.)  Parity with
- *      Panda3D's pixels stays UNPINNED, as for the rest of the render.
+ *  T6. OUT OF SCOPE: anisotropic filtering and trilinear blending between levels (one level per face, chosen by area); clamp and
+ *      mirror wrap modes; texture alpha (a texel's alpha is ignored: convert to RGB first); more than one texture per mesh.
+ *      Silhouettes of this entry are single-sampled as in item 5; multisampled edges (the reference enables 4x MSAA) are THE
+ *      MULTISAMPLE CONTRACT below, through pp_render_views_ms.  Shading is THE SHADING CONTRACT below; what it leaves out is S9.
+ *      Parity with Panda3D's pixels stays UNPINNED, as for the rest of the render.
  *
  * pp_texture_mips_bytes: *bytes = 4 * the texels of all levels, *levels (may be NULL) = their number.  PP_EINVAL: bytes NULL, Wt or
  * Ht outside [1, PP_TEXTURE_MAX].
@@ -1031,7 +1031,8 @@ int pp_render_views_textured(const float* vertices, int n_vertices, const int* f
  *      CSR pair built on the host: a stable sort of faces.reshape(-1) by vertex, so a vertex's faces come in ascending face
  *      index (a face that names v twice is listed twice and adds zero).  No float atomics: the bytes do not depend on launch order.
  *  S9. OUT OF SCOPE: specular terms, shadows, coloured or spot lights, decoding base colours from sRGB, angle-threshold "auto
- *      smooth", MSAA.  Parity with Cycles / pyrender pixels stays UNPINNED, as for the rest of the render.
+ *      smooth".  (4x multisampling is THE MULTISAMPLE CONTRACT below, through pp_render_views_ms; this entry is single-sampled.)
+ *      Parity with Cycles / pyrender pixels stays UNPINNED, as for the rest of the render.
  *
  * pp_vertex_normals: vertices (Nv, 3) fp32, faces (Nf, 3) int32, vf_offsets (Nv + 1) int32, vf_faces (3 Nf) int32, normals (Nv, 3)
  * fp32 out: device.  One launch on `stream`, nothing synchronises.  An entry of the lists that is out of range is skipped, never a
@@ -1060,6 +1061,62 @@ int pp_render_views_lit(const float* vertices, int n_vertices, const int* faces,
                         unsigned int* near_count, const float* lights_host, int n_lights, float ambient, int normal_mode,
                         const float* normals, const unsigned char* base_color_host, const unsigned char* tone_table, int tone_entries,
                         void* stream);
+/* -------------------------------------------------------------------------
+ * THE MULTISAMPLE CONTRACT: the same render with 4x anti-aliased colour and alpha.  The reference renders its templates with
+ * `framebuffer-multisample 1` / `multisamples 4` (rendering/src/megapose/panda3d_renderer/panda3d_scene_renderer.py:72-73 and
+ * set_antialias(MAuto) at :99), so its PNGs hold partial alpha along silhouettes; pp_template_extents (alpha != 0) and
+ * pp_templates_crop (mask from alpha == 255, colour mask from alpha > 0) already treat such frames as `_get_template` does.
+ * tests/multisample_oracle.py restates M1-M5 in numpy; the kernels equal it bit for bit.  Pixel parity with Panda3D stays
+ * UNPINNED, and the effect of the option on pose accuracy is UNMEASURED (no trained weights were available to measure it).
+ * A multisampled render of a view has S = 4 SAMPLE PLANES and one CENTRE PLANE.
+ *  M1. Sample positions.  Plane s of pixel (x, y) is sampled at the sub-pixel position (256 x + ox_s, 256 y + oy_s) in the 1/256
+ *      pixel fixed point of item 3, (ox, oy) = (-32, -96), (96, -32), (-96, 32), (32, 96) for s = 1 .. 4: the standard rotated-grid
+ *      4x pattern in 1/16 pixel, times 16.  The centre plane (plane 0) has offset (0, 0).  Which pattern the reference's GL driver
+ *      used is unpinned.
+ *  M2. Each plane is a full render under THE RASTER CONTRACT: items 1-7 hold with the sample point of item 5 moved by the offset.
+ *      The edge functions only see differences, so this is exactly the single-sample render of the triangle whose SNAPPED
+ *      coordinates are (xs - ox, ys - oy): area2, the winding exchange and 1 / Zc are unchanged; the sample box of item 5 is
+ *      recomputed from the shifted coordinates; the top-left rule applies per sample; the weights p_k, q, Z and the colour are
+ *      evaluated at that sample.  Consequently the centre plane is the single-sample render, bit for bit.  A triangle dropped at
+ *      the near plane is counted ONCE in *near_count, not once per plane.
+ *  M3. Colour.  Each covered sample's colour is that of the unlit (item 6), textured (T3-T5, the level per face as there) or lit
+ *      (S2-S6) contract evaluated at that sample: 4x SUPERSAMPLING at the MSAA positions, interior pixels included.  Hardware
+ *      MSAA shades once per pixel and triangle (at the centre or centroid) and only tests coverage and depth per sample; here
+ *      every sample is shaded, so interior pixels are the mean of four shaded samples, not the centre's colour.
+ *  M4. Resolve, in integer arithmetic: per channel out = (c_1 + c_2 + c_3 + c_4 + 2) >> 2 over the four sample planes.  An
+ *      uncovered sample contributes (0, 0, 0, 0), a covered one has alpha 255: alpha is one of 0, 64, 128, 191, 255 and colour is
+ *      blended towards black at silhouettes — what a multisample resolve over a (0, 0, 0, 0) clear gives and what the reference's
+ *      PNGs hold (colour premultiplied by coverage).
+ *  M5. Geometry outputs come from the centre plane alone: depth_mm, depth_m and face_id equal the samples = 1 render bit for bit;
+ *      multisampling moves colour and alpha only (the analogue of S7).  Pixels with alpha > 0 and depth 0 (a sample is covered,
+ *      the centre is not) and pixels with depth > 0 and alpha < 255 (the centre is covered, a sample is not) therefore exist.
+ *  M6. OUT OF SCOPE: sample counts other than 1 and 4; centroid or per-pixel shading; alpha-to-coverage; multisampling of the
+ *      windowed depth raster (VSD, verify, refine, scene ground truth: single-sampled by definition) and of
+ *      synth_scenes.render_scenes, whose composite picks one layer per pixel.
+ *
+ * pp_render_ms_workspace_bytes: samples = 1 gives pp_render_workspace_bytes; samples = 4 gives 256 + chunk 5 (H W + Nf) 8 bytes:
+ * per view (1 + S) planes of H W 64-bit words, and a queue slot per triangle and plane (a triangle's box is recomputed per plane,
+ * so each plane queues its own large triangles).  PP_EINVAL: samples not 1 or 4, what pp_render_workspace_bytes rejects, and
+ * with samples = 4 a chunk_views whose size does not fit a size_t.
+ * pp_render_views_ms: the argument list of pp_render_views_lit with `int shaded` in front of the shading arguments and `int
+ * samples` behind them.  shaded = 1: the colour source and shading of pp_render_views_lit, with all its checks.  shaded = 0, the
+ * UNLIT render: the colour source is `colors` (pp_render_views) or face_uv + mips (+ Wt, Ht; pp_render_views_textured), exactly
+ * one of the two; the shading arguments (lights_host ... tone_entries) are not read.  samples = 1 gives the bytes of those three
+ * entries, through the same kernels and the same workspace.  samples = 4: the coverage launches run over the 5 planes of every
+ * view of a chunk, the resolve pass shades the four samples of a pixel and applies M4 and M5; the views are rendered in chunks of
+ * as many views as the workspace holds and any chunk size gives the same bytes; all work is enqueued on `stream`, nothing
+ * synchronises.  PP_EINVAL, before any launch: samples not 1 or 4, shaded not 0 or 1, and everything the entry it stands for
+ * rejects (unlit: no colour source, both, or a bad texture argument).  PP_EWORKSPACE: workspace misaligned (256 B) or smaller than
+ * pp_render_ms_workspace_bytes(H, W, Nf, 1, samples).
+ * ------------------------------------------------------------------------- */
+int pp_render_ms_workspace_bytes(int H, int W, int n_faces, int chunk_views, int samples, size_t* bytes);
+int pp_render_views_ms(const float* vertices, int n_vertices, const int* faces, const int* faces_host, int n_faces,
+                       const unsigned char* colors, const float* face_uv, const void* mips, int Wt, int Ht, const float* poses,
+                       int n_views, float fx, float fy, float cx, float cy, int H, int W, float near, void* workspace,
+                       size_t workspace_bytes, unsigned char* rgba, unsigned short* depth_mm, float* depth_m, int* face_id,
+                       unsigned int* near_count, int shaded, const float* lights_host, int n_lights, float ambient, int normal_mode,
+                       const float* normals, const unsigned char* base_color_host, const unsigned char* tone_table, int tone_entries,
+                       int samples, void* stream);
 /* Per view the first / last row and column with alpha != 0 — the np.any / np.where of get_bbox (utils/data_utils.py:131-137) on
  * rgba[..., 3]: extents (V, 4) int32 = {rmin, rmax, cmin, cmax} (inclusive; -1 each for a view that covers nothing);
  * counts (V) int32 covered samples, may be NULL. */

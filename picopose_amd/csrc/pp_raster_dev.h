@@ -21,15 +21,18 @@ constexpr size_t WS_HEADER = 256;        // bytes of a workspace in front of the
 
 enum : int { TRI_OK = 0, TRI_NEAR = 1, TRI_SKIP = 2 };
 
-// samples are taken for clip_x0 <= x < min(clip_x1, W) and clip_y0 <= y < min(clip_y1, H): the clip rectangle defaults to the frame
+// samples are taken for clip_x0 <= x < min(clip_x1, W) and clip_y0 <= y < min(clip_y1, H): the clip rectangle defaults to the frame.
+// Pixel (x, y) is sampled at the sub-pixel position (256 x + sub_x, 256 y + sub_y): (0, 0) is the pixel centre of item 2, the
+// sample planes of THE MULTISAMPLE CONTRACT (M1) set their offset here
 struct Cam {
     float fx, fy, cx, cy, near;
     int H, W;
     int clip_x0 = 0, clip_y0 = 0, clip_x1 = INT_MAX, clip_y1 = INT_MAX;
+    int sub_x = 0, sub_y = 0;
 };
 
 struct Tri {
-    int x[3], y[3];      // snapped screen coordinates, ordered so that area2 > 0
+    int x[3], y[3];      // snapped screen coordinates less the camera's sample offset, ordered so that area2 > 0
     int id[3];           // vertex indices in that order
     int swapped;         // 1 when corners 1 and 2 were exchanged for that: per-corner attributes follow (no arithmetic reads it)
     float iz[3];         // 1 / Zc
@@ -59,8 +62,9 @@ __device__ __forceinline__ int tri_setup(const float* __restrict__ verts, const 
             t.x[k] = t.y[k] = 0;
             t.iz[k] = 0.f;
         } else {
-            t.x[k] = snap((c.fx * xc) / zc + c.cx);
-            t.y[k] = snap((c.fy * yc) / zc + c.cy);
+            // M2: the edge functions see differences only, so moving the sample point by the offset is moving the snapped corners back
+            t.x[k] = snap((c.fx * xc) / zc + c.cx) - c.sub_x;
+            t.y[k] = snap((c.fy * yc) / zc + c.cy) - c.sub_y;
             t.iz[k] = 1.f / zc;
         }
     }
@@ -150,13 +154,14 @@ __device__ __forceinline__ unsigned long long* slot_of(unsigned long long* zv, c
     return zv + (size_t)(py - vw.y0) * vw.ww + (px - vw.x0);
 }
 
-// the calling lane's triangle f of view v (z-buffer words at zv): a triangle in front of the near plane is counted, a box of at most
-// SMALL_BOX samples is walked here, a larger one goes to the queue
+// the calling lane's triangle f of view v (z-buffer words at zv): a triangle in front of the near plane is counted (in near_slot,
+// unless that is null: a further sample plane of a view that plane 0 counts), a box of at most SMALL_BOX samples is walked here, a
+// larger one goes to the queue
 __device__ __forceinline__ void cover_small(const View& vw, int v, int f, unsigned long long* zv, uint2* __restrict__ queue,
                                             unsigned* __restrict__ qcount, unsigned* __restrict__ near_slot) {
     Tri t;
     const int st = tri_setup(vw.verts, vw.faces, vw.Nv, vw.pose, vw.cam, f, t);
-    if (st == TRI_NEAR) atomicAdd(near_slot, 1u);
+    if (st == TRI_NEAR && near_slot) atomicAdd(near_slot, 1u);
     if (st != TRI_OK) return;
     if ((t.bx1 - t.bx0 + 1) * (long long)(t.by1 - t.by0 + 1) > SMALL_BOX) {
         queue[atomicAdd(qcount, 1u)] = make_uint2((unsigned)v, (unsigned)f);

@@ -20,8 +20,14 @@ A UV-textured model (BOP's `obj_NNNNNN.ply` with `texture_u texture_v` or a per-
 obj_NNNNNN.png`) is rendered from its texture, with no baking step: load_model reads the PLY and the image, a mip pyramid is built on
 the device once per render call, and the resolve pass samples it perspective-correctly — one mip level per (view, face) chosen by
 area, bilinear, wrap mode repeat, v = 0 at the bottom row (THE TEXTURE CONTRACT in include/picopose_hip.h, T1-T5).  Out of scope
-(T6): anisotropic and trilinear filtering, multisampled edges (the reference enables 4x MSAA), clamp / mirror wrap, texture alpha,
-several textures per mesh.
+(T6): anisotropic and trilinear filtering, clamp / mirror wrap, texture alpha, several textures per mesh.
+
+The reference anti-aliases its templates (4x MSAA: panda3d_scene_renderer.py:72-73, :99), so its PNGs hold partial alpha along the
+silhouette.  `render_views` / `render_templates` / `onboard_objects` take `samples=4` (THE MULTISAMPLE CONTRACT in
+include/picopose_hip.h, M1-M6): four rotated-grid samples per pixel, every sample shaded (unlit, textured or lit), colour and alpha
+their rounded integer mean, so alpha is one of 0, 64, 128, 191, 255 and colour fades to black at silhouettes; depth and face ids stay
+those of the pixel centre.  The default samples=1 is byte for byte what it was.  Pixel parity with Panda3D stays unpinned and the
+effect of the option on pose accuracy is UNMEASURED (no trained weights were available).
 
 T-LESS and ITODD need shading: the reference renders their untextured CAD meshes (`models_cad`) with BlenderProc under eight point
 lights (render_bop_templates.py:131, blenderproc.py:29-39) and, for T-LESS, a uniform grey 0.4 material (:54-57); unlit, such a
@@ -29,7 +35,7 @@ mesh — or any untextured CAD part of your own — is a flat silhouette with no
 `render_views` / `render_templates` / `onboard_objects` take `shading=` (a Shading, a dict of its fields, or "tless"): Lambert
 diffuse plus ambient under up to 16 point lights, flat or smooth normals, an optional tone table, on top of any of the three colour
 sources (THE SHADING CONTRACT in include/picopose_hip.h, S1-S8; out of scope, S9: specular terms, shadows, coloured or spot
-lights, sRGB decoding of base colours, auto-smooth, MSAA).  Shading is opt-in: without it every render is byte for byte what it was.
+lights, sRGB decoding of base colours, auto-smooth).  Shading is opt-in: without it every render is byte for byte what it was.
 The package reads no fixture: `view_poses` is the caller's array (the reference's is
 rendering/src/lib3d/predefined_poses/obj_poses_level1.npy, 162 views)."""
 import ctypes
@@ -437,7 +443,7 @@ def _unit_scale(units, vertices):
 
 
 def render_views(mesh, poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", near=1e-3, return_depth_m=False, return_face_id=False,
-                 workspace_bytes=DEFAULT_WORKSPACE_BYTES, check_near=True, device="cuda", shading=None):
+                 workspace_bytes=DEFAULT_WORKSPACE_BYTES, check_near=True, device="cuda", shading=None, samples=1):
     """Render `mesh` ({"vertices", "faces", "colors" or None}, or with "texture" (Ht,Wt,3) uint8 and "face_uv" (Nf,3,2) or "uv"
     (Nv,2): the textured path, which wins over "colors") under the object -> camera poses (V,4,4) whose translation is in
     the mesh's `units` ("mm" as BOP models are, "m", or "auto": the reference's rule, diameter < 10 -> metres).  The kernels work
@@ -450,7 +456,13 @@ def render_views(mesh, poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", n
     pyramid is built on the device once per call, before the views are rendered.  `workspace_bytes` bounds the
     rasteriser's workspace; the views are rendered in as many chunks as that takes (at least one view's worth is allocated).
     check_near: synchronise and raise ValueError when a triangle was dropped at the near plane (`near` metres); False leaves the
-    count on the device for the caller."""
+    count on the device for the caller.
+    samples: 1 (default: one sample at the pixel centre) or 4 (THE MULTISAMPLE CONTRACT): rgba is the rounded integer mean of four
+    rotated-grid samples, each shaded on its own, an uncovered one counting (0, 0, 0, 0) — alpha in {0, 64, 128, 191, 255}, colour
+    fading to black at silhouettes; depth_mm, depth_m, face_id and near_count stay the pixel centre's, equal to samples=1 bit for
+    bit, so pixels with alpha > 0 and depth 0, and with depth > 0 and alpha < 255, exist.  Its effect on pose accuracy is unmeasured.
+    ValueError for anything but the ints 1 and 4, before any device work."""
+    _check_samples(samples)
     v, f, c = _mesh_arrays(mesh)
     tex = _mesh_texture(mesh, len(v), f)
     scale = _unit_scale(units, v)
@@ -466,7 +478,10 @@ def render_views(mesh, poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", n
     v_m = np.ascontiguousarray((v.astype(np.float64) * scale).astype(np.float32))
     v_d, f_d, c_d = (torch.from_numpy(a).to(device) for a in (v_m, f, c))
     p_d = torch.from_numpy(np.ascontiguousarray(poses.astype(np.float32))).to(device)
-    per_view = _lib.workspace_bytes("pp_render_workspace_bytes", H, W, len(f), 1) - 256
+    if samples == 1:
+        per_view = _lib.workspace_bytes("pp_render_workspace_bytes", H, W, len(f), 1) - 256
+    else:
+        per_view = _lib.workspace_bytes("pp_render_ms_workspace_bytes", H, W, len(f), 1, samples) - 256
     chunk = max(1, min(V, (int(workspace_bytes) - 256) // per_view))
     ws = torch.empty(256 + chunk * per_view, dtype=torch.uint8, device=device)
     out = {"rgba": torch.empty(V, H, W, 4, dtype=torch.uint8, device=device),
@@ -490,9 +505,17 @@ def render_views(mesh, poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", n
         if smooth:                                                        # direction only: the unit of the vertices does not matter
             n_d = torch.from_numpy(own_normals).to(device) if own_normals is not None else vertex_normals(mesh, device)
         tone_d = None if tone is None else torch.from_numpy(tone).to(device)
-        _lib.call("pp_render_views_lit", v_d, len(v), f_d, f, len(f), c_d if tex is None and base is None else None,
-                  uv_d if tex is not None and base is None else None, mips if tex is not None and base is None else None, Wt, Ht, *tail,
-                  lights4 if len(lights4) else None, len(lights4), ambient, int(smooth), n_d, base, tone_d, 0 if tone is None else len(tone))
+        source = (c_d if tex is None and base is None else None, uv_d if tex is not None and base is None else None,
+                  mips if tex is not None and base is None else None, Wt, Ht)
+        light_args = (lights4 if len(lights4) else None, len(lights4), ambient, int(smooth), n_d, base, tone_d,
+                      0 if tone is None else len(tone))
+    if samples != 1:                                                      # one entry for the three colour sources, lit or not
+        if lit is None:
+            source = (c_d, None, None, 0, 0) if tex is None else (None, uv_d, mips, Wt, Ht)
+            light_args = (None, 0, 0.0, 0, None, None, None, 0)
+        _lib.call("pp_render_views_ms", v_d, len(v), f_d, f, len(f), *source, *tail, int(lit is not None), *light_args, samples)
+    elif lit is not None:
+        _lib.call("pp_render_views_lit", v_d, len(v), f_d, f, len(f), *source, *tail, *light_args)
     elif tex is None:
         _lib.call("pp_render_views", v_d, len(v), f_d, f, len(f), c_d, *tail)
     else:
@@ -500,6 +523,11 @@ def render_views(mesh, poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", n
     if check_near:
         _raise_on_near(int(out["near_count"].item()), near)
     return out
+
+
+def _check_samples(samples):
+    if type(samples) is not int or samples not in (1, 4):                 # (True is not 1)
+        raise ValueError(f"samples must be the int 1 or 4, got {samples!r}")
 
 
 def _raise_on_near(count, near):
@@ -574,7 +602,7 @@ def templates_from_frames(rgba, depth_mm, K, poses_mm, img_size=224, pts_size=64
 
 
 def render_templates(mesh, view_poses, K=TEMPLATE_K, resolution=(480, 640), units="mm", depth="png", img_size=224, pts_size=64,
-                     rgb_mask_flag=False, near=1e-3, workspace_bytes=DEFAULT_WORKSPACE_BYTES, device="cuda", shading=None):
+                     rgb_mask_flag=False, near=1e-3, workspace_bytes=DEFAULT_WORKSPACE_BYTES, device="cuda", shading=None, samples=1):
     """One object's template bank from its mesh: `tem_rgb` (V,3,S,S), `tem_mask` (V,S,S), `tem_pts3d` (V,P,P,3) metres, `tem_bbox`
     (V,4), `tem_M` (V,3,3), `tem_K` (V,3,3), `tem_pose` (V,4,4) (t in metres), float32 device tensors with `_get_template`'s values
     for the rendered frames (bop_test_dataset.py:212-264).  view_poses (V,4,4): only the rotations are used; the object sits at
@@ -582,14 +610,18 @@ def render_templates(mesh, view_poses, K=TEMPLATE_K, resolution=(480, 640), unit
     depth="png" (default): the lookup points come from the uint16 millimetres a depth file would hold, as the reference's do;
     depth="float": from the float32 depth directly — a deviation from the reference that removes the 0.5 mm quantisation.
     shading: render_views' (None: unlit; "tless" for T-LESS / ITODD-like untextured CAD models); it changes `tem_rgb` only.
-    ValueError: a triangle at the near plane, or a view that covers no pixel (named)."""
+    samples: render_views' (1, or 4: colour and alpha are the integer mean of four shaded rotated-grid samples, depth stays the pixel
+    centre's).  With 4 the box comes from alpha > 0 and `tem_mask` from alpha == 255, `_get_template`'s rule for an anti-aliased PNG, so
+    boxes can grow by a pixel and lookup points on the rim can be empty; the effect on pose accuracy is unmeasured.
+    ValueError: a triangle at the near plane, a view that covers no pixel (named), samples other than the ints 1 and 4."""
+    _check_samples(samples)
     if depth not in ("png", "float"):
         raise ValueError(f"depth must be 'png' or 'float', got {depth!r}")
     v = _mesh_arrays(mesh)[0]
     to_mm = 1.0 / (_unit_scale(units, v) * 1000.0)               # the returned pose follows the file convention: t in mm, then / 1000
     poses = template_object_poses(view_poses, v)
     r = render_views(mesh, poses, K=K, resolution=resolution, units=units, near=near, return_depth_m=depth == "float",
-                     workspace_bytes=workspace_bytes, check_near=False, device=device, shading=shading)
+                     workspace_bytes=workspace_bytes, check_near=False, device=device, shading=shading, samples=samples)
     poses_mm = poses.copy()
     poses_mm[:, :3, 3] *= to_mm
     return _crop_frames(r["rgba"], r["depth_m"] if depth == "float" else r["depth_mm"], depth == "float", K, poses_mm, r["near_count"],

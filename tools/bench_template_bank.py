@@ -12,7 +12,9 @@
     events on the stream); with --profile one textured render_templates and nothing else;
   * --shaded: the 20 k-triangle icosphere's 162 views through render_views unlit, lit flat, lit smooth (precomputed normals), textured
     and textured lit, alternately, twice (HIP events, uploads included: they are the same for every path), and pp_vertex_normals
-    alone; with --profile one render of each path and nothing else, for the per-kernel times.
+    alone; with --profile one render of each path and nothing else, for the per-kernel times;
+  * --multisample: the 20 k-triangle icosphere's bank (render_templates, 162 views) plain, textured and shading="tless", each with
+    samples=1 and samples=4 alternately, twice; with --profile one render_templates of each and nothing else.
 
 Prints one JSON line per measurement."""
 import argparse
@@ -114,6 +116,26 @@ def shaded(a, views):
                       "event_ms": round(events(lambda: tb.vertex_normals(m), a.reps, a.warmup), 4)}), flush=True)
 
 
+def multisample(a, views):
+    m = ro.icosphere(5, 50.0)
+    d = m["vertices"].astype(np.float64) / 50.0
+    uv = np.stack([np.arctan2(d[:, 1], d[:, 0]) / (2 * np.pi) + 0.5, np.arccos(np.clip(d[:, 2], -1, 1)) / np.pi], axis=1).astype(np.float32)
+    tm = {"vertices": m["vertices"], "faces": m["faces"], "uv": uv, "texture": np.random.default_rng(0).integers(0, 256, (2048, 2048, 3)).astype(np.uint8)}
+    paths = {"plain": (m, None), "textured": (tm, None), "tless": ({"vertices": m["vertices"], "faces": m["faces"]}, "tless")}
+    if a.profile:
+        for mesh, sh in paths.values():
+            for samples in (1, 4):
+                tb.render_templates(mesh, views, shading=sh, samples=samples)
+        torch.cuda.synchronize()
+        return
+    for rep in range(2):
+        for name, (mesh, sh) in paths.items():
+            ms = {s: timed(lambda: tb.render_templates(mesh, views, shading=sh, samples=s), a.reps, a.warmup) for s in (1, 4)}
+            print(json.dumps({"what": "render_templates", "path": name, "pass": rep, "mesh": "icosphere_20480", "views": 162,
+                              "samples1_host_ms": round(ms[1], 3), "samples4_host_ms": round(ms[4], 3), "ratio": round(ms[4] / ms[1], 2)}),
+                  flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -124,12 +146,15 @@ def main():
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--textured", default=None, metavar="WtxHt", help="texture size, e.g. 2048x2048")
     ap.add_argument("--shaded", action="store_true")
+    ap.add_argument("--multisample", action="store_true")
     a = ap.parse_args()
     views = np.load(os.path.join(ROOT, "tests", "golden", "template_view_poses_level1.npy"))
     if a.textured:
         return textured(a, views)
     if a.shaded:
         return shaded(a, views)
+    if a.multisample:
+        return multisample(a, views)
     meshes = {"cube_12": ro.cube(40.0), "icosphere_20480": ro.icosphere(5, 50.0)}
     big = ro.icosphere(a.big, 50.0)
     meshes[f"icosphere_{len(big['faces'])}"] = big
