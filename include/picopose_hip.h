@@ -354,7 +354,8 @@ int pp_attention_hl(const void* qkv_hl, int B, int T, int heads, int head_dim, f
 int pp_attention_train(const float* qkv, int B, int T, int heads, int head_dim, float scale, float* out, float* lse2, void* stream);
 /* Adjoint of attention.py:49-62 (what torch.autograd derives for the reference): dqkv (B*T, 3*heads*64) from qkv, the forward's out
  * and lse2, and dout (B*T, heads*64).  gpair = device (2^k, 2^-k) with max|dout| 2^k in [512, 1024) (pp_pow2_scale_ws); Dws = B*heads*T
- * floats of scratch.  Scores and probabilities are recomputed tile by tile; two kernels (dq | dk, dv), no atomics: bit-reproducible. */
+ * floats of scratch.  Scores and probabilities are recomputed tile by tile; two kernels (dq | dk, dv), no atomics: bit-reproducible.
+ * T = 1 (the soft-max of one key is constant): dq = dk = 0 and dv = dout, exactly. */
 int pp_attention_backward(const float* qkv, const float* out, const float* dout, const float* lse2, const float* gpair, int B, int T,
                           int heads, int head_dim, float scale, float* Dws, float* dqkv, void* stream);
 

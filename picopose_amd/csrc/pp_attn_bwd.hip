@@ -336,6 +336,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     write_rows(Os, dv0, dv1, ginv / (PP_A_SCALE * P_SCALE), drow + 2 * C1, C3, key0, T, lane);
 }
 
+// T = 1: the soft-max of a single key is the constant 1, so dq = dk = 0 and dv = dO exactly.  The recomputing kernels give dS = p (dP - D)
+// with dP from the three-term operand product and D from the forward's rounded output: two roundings of the same number, whose
+// difference (2^-22 of |dO.v|) would reach dq and dk as noise.  One element per lane: row b of dqkv is (dq | dk | dv), C1 floats each.
+__global__ __launch_bounds__(256) void attn_bwd_single_key_kernel(const float* __restrict__ dout, long n, int C1, float* __restrict__ dqkv) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long b = i / C1;
+    float* row = dqkv + b * 3 * C1 + (i - b * C1);
+    row[0] = 0.f;
+    row[C1] = 0.f;
+    row[2 * C1] = dout[i];
+}
+
 }  // namespace
 
 extern "C" int pp_attention_backward(const float* qkv, const float* out, const float* dout, const float* lse2, const float* gpair, int B,
@@ -344,6 +357,11 @@ extern "C" int pp_attention_backward(const float* qkv, const float* out, const f
     if (((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)dout | (uintptr_t)dqkv) % 16 != 0) return PP_EINVAL;
     if ((long)B * heads * ((T + 63) / 64) > 0x7FFFFFF0L) return PP_EINVAL;
     const long items = (long)B * T * heads;
+    if (T == 1) {
+        hipLaunchKernelGGL(attn_bwd_single_key_kernel, dim3((unsigned)((items * HD + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dout,
+                           items * HD, heads * HD, dqkv);
+        return pp_last_launch();
+    }
     hipLaunchKernelGGL(attn_bwd_d_kernel, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, (hipStream_t)stream, out, dout, gpair, B, T,
                        heads, Dws);
     const int tiles = (T + 31) / 32;
