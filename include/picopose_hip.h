@@ -1566,10 +1566,46 @@ int pp_depth_quantize_u16(const float* depth_m, long long n, float units_per_met
  * pp_mask_intersections: bits (n, words) -> inter (n, n) int32, inter[i][j] = the sum over the words of popcount(bits[i][w] &
  * bits[j][w]): symmetric, its diagonal is the area.  A workgroup owns 8 x 8 pairs, four threads per pair, and stages 64 words of its 16 rows
  * per step in LDS, the rows 68 words apart (conflict-free 4-byte reads).  PP_EINVAL: a null pointer, n <= 0 or > PP_MASK_MAX_N, words <= 0.
+ *
+ * THE APPEARANCE SCORE (csrc/pp_appearance.hip; tests/appearance_oracle.py restates it): the appearance term of SAM-6D's
+ * instance-segmentation stage (Lin et al., "SAM-6D: Segment Anything Model Meets Zero-Shot 6D Object Pose Estimation", 2024), WRITTEN
+ * FROM ITS PUBLISHED DESCRIPTION, NOT FROM ITS CODE: for every foreground patch of a proposal's crop the best cosine to any
+ * foreground patch of the best-matching template, averaged over the crop's foreground patches.  Parity with SAM-6D's code is
+ * unpinned.  Its geometric score and box NMS are not here.
+ *
+ * pp_patch_valid: mask (n, S, S) fp32 (out_mask of pp_detections_crop, or a tem_mask) and the ViT's patch size p, S % p == 0,
+ * w0 = S / p, N = w0 w0 -> valid (n, N) uint8, n_valid (n) int32.  Patch i = py w0 + px (the ViT's token order: row-major over
+ * the patch grid, cls token excluded) covers the pixels [py p, py p + p) x [px p, px p + p); count = its pixels with
+ * mask > 0.5f (a NaN is not counted); valid[i] = 1 iff 2 count >= p p, else 0; n_valid = the number of valid patches.  Integers
+ * only.  One workgroup per mask.  PP_EINVAL: a null pointer; n, S or p <= 0; S > PP_APP_MAX_S; S % p != 0.
+ *
+ * pp_appearance_match: query (P, N, C) and bank (R, N, C) hold unit rows (pp_descriptor_normalize's), q_valid (P, N) and t_valid
+ * (R, N) uint8 (non-zero: valid; pp_patch_valid's), pair_row (P) int32 with its HOST copy pair_row_host, validated before the
+ * launch: proposal p is compared with bank view pair_row[p] (a device entry outside [0, R) that the host copy does not show is
+ * answered like a view without a valid patch: 0 and -1, nothing is read).  cos(i, j) of query patch i and template patch j is computed in THE
+ * CHAIN ORDER: acc = 0, then acc = fmaf(q[i][k], t[j][k], acc) for k = 0 .. C - 1 ascending (v_mfma_f32_32x32x2_f32 is bit for bit
+ * that chain; the K tail is padded with zeros, fma(0, 0, acc) = acc).  The order depends on C alone - not on P, N, R, the
+ * proposal's place in the batch or the wave that computes it - so bit-equal rows give bit-equal cosines.
+ *   patch_sim (P, N) fp32 = for EVERY query patch i, valid or not, the largest cos(i, j) over the valid template patches j of view
+ *                           pair_row[p]; 0 when that view has no valid patch;
+ *   patch_arg (P, N) int32 = the j of that maximum, among equal maxima the lowest; -1 when the view has no valid patch;
+ *   n_valid (P) int32     = the number of valid query patches;
+ *   app (P) fp32          = (the sum of patch_sim[p][i] over the valid i in THE ROW ORDER above: lane l adds i = l, l + 64, ...
+ *                           ascending starting from 0, then the butterfly) / n_valid[p], one division; 0 when n_valid[p] == 0 or
+ *                           the view has no valid patch.
+ * One workgroup of four waves per (proposal, PP_APP_TILE query patches): the template's patches go over the waves in chunks of 256
+ * (2 x 2 tiles of 32 x 32 per wave, the template the A operand: a lane's column is one query patch), K is staged through LDS 16
+ * channels at a time; the masked (value, index) maximum is taken in the lane, across the lane halves and across the waves
+ * through LDS.  A second launch, one wave per proposal, takes the masked sum and the division.  No atomics, no scratch.
+ * PP_EINVAL (before any launch): a null pointer; P, R, N or C <= 0; N > PP_APP_MAX_N; C not a multiple of 4 or above
+ * PP_MATCH_MAX_C; query or bank not 16-byte aligned; a pair_row_host entry outside [0, R).
  * ------------------------------------------------------------------------- */
 #define PP_MATCH_TILE 16
 #define PP_MATCH_MAX_C 1024
 #define PP_MATCH_MAX_TOPK 8
+#define PP_APP_TILE 64
+#define PP_APP_MAX_N 1024 /* patches of a crop: a 448 crop at patch 14 */
+#define PP_APP_MAX_S 16384
 #define PP_MASK_MAX_N 4096
 int pp_descriptor_normalize(const float* x, int n, int C, float eps, float* y, void* stream);
 int pp_proposal_match(const float* query, int P, const float* bank, const int* offsets, const int* offsets_host, int O, int C,
@@ -1577,6 +1613,10 @@ int pp_proposal_match(const float* query, int P, const float* bank, const int* o
 int pp_rle_pack_bits(const int* run_ends, int n_runs, const int* run_offset, const int* run_offset_host, int n, int hw, int words,
                      unsigned* bits, int* area, void* stream);
 int pp_mask_intersections(const unsigned* bits, int n, int words, int* inter, void* stream);
+int pp_patch_valid(const float* mask, int n, int S, int p, unsigned char* valid, int* n_valid, void* stream);
+int pp_appearance_match(const float* query, const unsigned char* q_valid, int P, const float* bank, const unsigned char* t_valid, int R,
+                        const int* pair_row, const int* pair_row_host, int N, int C, float* patch_sim, int* patch_arg, int* n_valid,
+                        float* app, void* stream);
 
 /* -------------------------------------------------------------------------
  * POSE VERIFICATION: per pose hypothesis, how well its depth render explains the image: eight integer counts of the render held

@@ -336,7 +336,7 @@ def infer_detections(net, image_u8, detections, K, templates_data, obj_idxs, **k
     return infer_image(net, data, templates_data, **kw), data
 
 
-LABEL_KEYS = ("topk", "min_score", "max_detections", "nms_iou", "min_area_px", "time")       # label_proposals' own
+LABEL_KEYS = ("topk", "min_score", "max_detections", "nms_iou", "min_area_px", "time", "appearance", "appearance_weight")       # label_proposals' own
 LABEL_SHARED_KEYS = ("scene_id", "img_id", "img_size", "minimum_n_point", "bs", "device")       # ... and those both steps read
 
 
